@@ -16,6 +16,10 @@ import torch
 
 from . import _ref_loader, cases, detinit  # noqa
 
+# MKL's vendor-independent code path for torch's CPU log / exp: the fixtures then reproduce bit for bit on any x86 host
+# (tests/conftest.py takes the same path).  Set before the first MKL call.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 OUT = os.path.dirname(os.path.abspath(__file__))
 torch.set_num_threads(8)
 

@@ -167,7 +167,7 @@ def test_bench_infer_line(dtype):
     cases, the roofline of its longest launch and the oracle's predict path as cpu_baseline (fp32: keep-lists equal)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "infer", "--dtype", dtype, "--steps", "10", "--warmup", "3",
-                        "--train-steps", "40", "--cpu-steps", "2", "--map-cases", "4"], cwd=root, capture_output=True, text=True, timeout=900)
+                        "--train-steps", "40", "--cpu-steps", "2", "--map-cases", "4", "--full"], cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines

@@ -918,7 +918,7 @@ def test_data_parallel_two_ranks_share_one_gpu():
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--size", "64",
-           "--batch", "2", "--no-cpu-baseline"]
+           "--batch", "2", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -939,7 +939,7 @@ def test_bench_line_contract(dtype):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--cpu-steps", "1", "--dtype", dtype,
-                        "--opt", "fold_np_max=64"], cwd=root, capture_output=True, text=True, timeout=600)
+                        "--opt", "fold_np_max=64", "--full"], cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -963,6 +963,39 @@ def test_bench_line_contract(dtype):
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "volumes/s" and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
     assert d["knobs"].get("fold_np_max") == "64"
+
+
+@pytest.mark.parametrize("mode", ["train", "infer"])
+def test_bench_plain_line_and_dump(mode, tmp_path):
+    """A plain `bench.py --steps K --warmup W` times exactly K steps and prints the headline line without what `--full`
+    adds; `--dump-outputs DIR` writes what the last timed step handed its caller as float32 / float64 .npy files."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps=5", "--warmup", "2", "--size", "64", "--batch", "2",
+           "--mode", mode, "--dump-outputs", str(tmp_path)] + (["--train-steps", "2"] if mode == "infer" else [])
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["unit"] == "volumes/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["metric"]
+    assert d["steps"] == 5 and d["warmup"] == 2
+    assert abs(d["value"] - 2 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    assert not {"roofline", "cpu_baseline", "mAP_synthetic"} & set(d)
+    files = sorted(os.listdir(tmp_path))
+    assert files == (["loss.npy", "state.npy"] if mode == "train" else ["boxes.npy", "counts.npy", "labels.npy", "scores.npy"])
+    out = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    if mode == "train":
+        assert out["loss"].shape == (3,) and np.isfinite(out["loss"]).all() and out["loss"][2] > 0
+        assert out["state"].ndim == 1 and np.isfinite(out["state"]).all()
+    else:
+        n = int(out["counts"].sum())
+        assert out["counts"].shape == (2,) and out["boxes"].shape == (n, 6) and out["labels"].shape == out["scores"].shape == (n,)
 
 
 # ------------------------------------------------------------------------------------------------- three classes

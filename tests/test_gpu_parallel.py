@@ -202,7 +202,7 @@ def test_bench_under_torchrun_two_ranks(mode, extra):
     env = dict(os.environ, MSL_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--mode", mode] + extra
+           "--mode", mode, "--full"] + extra
     if mode == "infer":
         cmd += ["--map-cases", "2", "--train-steps", "2"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)

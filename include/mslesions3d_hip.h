@@ -399,6 +399,24 @@ int msl_detect_objects(const float* locs, const float* scores, const float* prio
                        float* tmp_scores, int* tmp_ref, int* select_ws, float* out_boxes, float* out_scores,
                        long long* out_labels, long long* out_prior, int* out_count, void* stream);
 
+/* ---- detection metrics: calculate_mAP / compute_metrics_per_class (utils.py:157-396), class 1 only ------------
+ * Detections in msl_detect_objects' output layout: det_boxes (N,top_k,6) f32, det_scores (N,top_k) f32, det_labels
+ * (N,top_k) i64, det_count (N) i32 (slots >= count and labels != 1 are ignored).  Ground truth packed
+ * (MultiBoxLoss.pack_targets): gt_boxes (G,6) f32, gt_labels (G) i64, obj_off (N+1) i32 (boxes of image n are
+ * [obj_off[n], obj_off[n+1]); labels != 1 ignored).  iou_thr (n_thr) f32: one workgroup per threshold, strict `>`;
+ * recall_thr (11) f32: torch.arange(0, 1.1, .1).  D = N*top_k.  Outputs, per threshold t:
+ *   summary (n_thr,8): AP, mAP, precision, recall, f1, n_true_boxes, K = class-1 detections, TP count
+ *   tp / fp (n_thr,D): first K entries, in sorted order;  gt_status (n_thr,G): 1 detected, 0 not, 2 not class 1
+ * and once: sorted_scores (D) (first K), gt_vol (G) (utils.py:152-154).  accum (NULL or n_thr*4+1 f64): += mAP,
+ * precision, recall, f1 per threshold, then += 1 (per-step sums of a training epoch).  Bit-identical to the host code.
+ * Capacity: msl_detection_metrics_max(0) detections (D), (1) ground-truth boxes (G), (2) thresholds; beyond -> -2. */
+size_t msl_detection_metrics_max(int which);
+int msl_detection_metrics(const float* det_boxes, const float* det_scores, const long long* det_labels,
+                          const int* det_count, int N, int top_k, const float* gt_boxes, const long long* gt_labels,
+                          const int* obj_off, int G, const float* iou_thr, int n_thr, const float* recall_thr,
+                          float* summary, float* tp, float* fp, float* sorted_scores, float* gt_status, float* gt_vol,
+                          double* accum, void* stream);
+
 /* ---- optimiser + NaN guard : ssd3d.py:704-722, :258-261 ---------------------------------------------------- */
 /* hp (device, 8 floats): step_size(bias), step_size(other), sqrt(bias_correction2), beta1, beta2, eps,
  * weight_decay, gradient scale.  is_bias (n bytes): 1 for elements of '.bias' parameters (2*lr group). */

@@ -385,30 +385,35 @@ class LSSD3D(nn.Module):
         key = (N, P, ncls, top_k, dev)
         ws = self._det_ws.get(key)
         if ws is None:
-            cap, k1 = 10 * top_k, ncls - 1
-            wn = (cap + 63) // 64
-            f32, i32, i64 = torch.float32, torch.int32, torch.int64
-            ws = dict(probs=torch.empty((N, k1, P), dtype=f32, device=dev),
-                      boxes=torch.empty((N, P, 6), dtype=f32, device=dev),
-                      sorted_idx=torch.zeros((N, k1, cap), dtype=i32, device=dev),
-                      ncand=torch.zeros(N * k1, dtype=i32, device=dev),
-                      mask=torch.zeros((N, k1, cap, wn), dtype=i64, device=dev),
-                      keep=torch.zeros((N, k1, wn), dtype=i64, device=dev),
-                      nkept=torch.zeros(N * k1, dtype=i32, device=dev),
-                      tmp_s=torch.empty((N, k1 * cap), dtype=f32, device=dev),
-                      tmp_r=torch.empty((N, k1 * cap), dtype=i32, device=dev),
-                      sel=torch.zeros(int(_lib.load().msl_detect_select_ws_ints(N, P, ncls)), dtype=i32, device=dev),
-                      # the four output buffers are views of ONE allocation [labels | prior indices | boxes | scores], so
-                      # that a batch's detections leave the workspace with one device copy instead of four
-                      out_all=torch.empty(N * top_k * 44, dtype=torch.uint8, device=dev),
-                      # per-image detection counts + one spare int: predict_step's eval plan keeps its NaN flag there, so that
-                      # counts and flag leave the device with ONE copy
-                      oc=torch.zeros(N + 1, dtype=i32, device=dev),
-                      # pinned landing zone of the per-image detection counts (+ one slot for a NaN flag): filled by async
-                      # copies, read after ONE stream synchronisation (a blocking 4-byte device-to-host copy costs 50-100 us)
-                      host=torch.empty(N + 1, dtype=i32).pin_memory())
-            ws.update(self._detect_out_views(ws["out_all"], N, top_k))
-            self._det_ws[key] = ws
+            ws = self._det_ws[key] = self.new_detect_workspace(N, P, ncls, top_k, dev)
+        return ws
+
+    @staticmethod
+    def new_detect_workspace(N, P, ncls, top_k, dev):
+        """Scratch and output buffers of one ``msl_detect_objects`` launch shape (FusedTrainer keeps its own)."""
+        cap, k1 = 10 * top_k, ncls - 1
+        wn = (cap + 63) // 64
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        ws = dict(probs=torch.empty((N, k1, P), dtype=f32, device=dev),
+                  boxes=torch.empty((N, P, 6), dtype=f32, device=dev),
+                  sorted_idx=torch.zeros((N, k1, cap), dtype=i32, device=dev),
+                  ncand=torch.zeros(N * k1, dtype=i32, device=dev),
+                  mask=torch.zeros((N, k1, cap, wn), dtype=i64, device=dev),
+                  keep=torch.zeros((N, k1, wn), dtype=i64, device=dev),
+                  nkept=torch.zeros(N * k1, dtype=i32, device=dev),
+                  tmp_s=torch.empty((N, k1 * cap), dtype=f32, device=dev),
+                  tmp_r=torch.empty((N, k1 * cap), dtype=i32, device=dev),
+                  sel=torch.zeros(int(_lib.load().msl_detect_select_ws_ints(N, P, ncls)), dtype=i32, device=dev),
+                  # the four output buffers are views of ONE allocation [labels | prior indices | boxes | scores], so
+                  # that a batch's detections leave the workspace with one device copy instead of four
+                  out_all=torch.empty(N * top_k * 44, dtype=torch.uint8, device=dev),
+                  # per-image detection counts + one spare int: predict_step's eval plan keeps its NaN flag there, so that
+                  # counts and flag leave the device with ONE copy
+                  oc=torch.zeros(N + 1, dtype=i32, device=dev),
+                  # pinned landing zone of the per-image detection counts (+ one slot for a NaN flag): filled by async
+                  # copies, read after ONE stream synchronisation (a blocking 4-byte device-to-host copy costs 50-100 us)
+                  host=torch.empty(N + 1, dtype=i32).pin_memory())
+        ws.update(LSSD3D._detect_out_views(ws["out_all"], N, top_k))
         return ws
 
     @staticmethod

@@ -160,8 +160,10 @@ def example(args):
         model.current_epoch = epoch
         model.train()
         dataset.set_epoch(epoch)
+        # training metrics (ssd3d.py:497-515): detection + mAP on every step's own forward outputs, on the device
+        train_metrics = epoch % (2 * max(int(model.compute_metric_every_n_epochs), 1)) == 0
         for batch in dataset.train_dataloader():
-            out = trainer.step(batch["img"].to(dev), batch["boxes"], batch["labels"])
+            out = trainer.step(batch["img"].to(dev), batch["boxes"], batch["labels"], metrics=train_metrics)
             if shard_log is not None:
                 shard_log.write(json.dumps({"step": model.global_step, "epoch": epoch, "subjects": list(batch["subject"]),
                                             "total_loss/training": out["loss"]}) + "\n")
@@ -176,6 +178,18 @@ def example(args):
             # Lightning steps a scheduler returned by configure_optimizers once per epoch (interval="epoch") on top of
             # the manual per-step call inside training_step: one extra cosine step per epoch
             trainer.sch.step()
+        if train_metrics:
+            # training_epoch_end (ssd3d.py:657-690): epoch means of the per-step values, summed over every rank's steps
+            # (the vector length depends on the epoch alone, so every rank joins the same all-reduce)
+            msums, msteps = trainer.metric_sums(reset=True)
+            mavg = _mean_over_ranks(msums, msteps, dev, dp)
+            mrec = {"step": model.global_step, "epoch": epoch}
+            for i, tag in enumerate(("0.1", "0.5")):
+                for k, name in enumerate(("mAP", "precision", "recall", "f1_score")):
+                    mrec[f"{name}/training_IoU_{tag}"] = mavg[4 * i + k]
+            mrec["hp_metric/parameter_sizes"] = float(model.compute_parameters_median_size())
+            if rank == 0:
+                log.write(json.dumps(mrec) + "\n")
         model.eval()
         vals = [model.validation_step(b, i) for i, b in enumerate(dataset.test_dataloader())]
         keys = ("val_total_loss", "val_conf_loss", "val_loc_loss")

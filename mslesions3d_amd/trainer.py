@@ -6,6 +6,11 @@ MultiBox loss -> closed-form loss gradient -> backward -> (RCCL bucketed all-red
 -> cosine LR step, as one fixed sequence of C-ABI launches with no host synchronisation inside
 (ssd3d.py:467-531 + :704-722).  ``LSSD3D.training_step`` + ``loss.backward()`` + ``optimizer.step()`` is the
 API-compatible (autograd) route through the same kernels.
+
+``step(..., metrics=True)`` adds the reference's training metrics (ssd3d.py:497-515: detection on the step's own forward
+outputs, then calculate_mAP at IoU 0.1 and 0.5) as two more launches behind the step on the trainer's stream -
+``msl_detect_objects`` and ``msl_detection_metrics`` (csrc/metrics.hip) - whose per-step values are summed in a device
+accumulator: no host synchronisation per step, one read per epoch (``training_metrics`` / ``metric_sums``).
 """
 import collections
 import os
@@ -16,7 +21,8 @@ from . import _lib
 from ._lib import ptr
 from .optim import CosineAnnealingLR, FusedAdam
 from .parallel import GradBucketReducer
-from .ssd3d import MultiBoxLoss
+from .ssd3d import LSSD3D, MultiBoxLoss
+from .utils import launch_detection_metrics, metric_capacity_check, metric_details, metric_out_size
 
 
 class _StagedOptimizer:
@@ -77,6 +83,13 @@ class FusedTrainer:
         # which stream carries the overlapped gradient collectives: "heads" | "wgrad" | "own" (see _reducer)
         self.dp_comm_stream = "heads"
         self.main_stream_priority = -1  # the dependency chain must not queue behind the side streams' bulk work
+        # training metrics (step(..., metrics=True)): IoU thresholds of the reference's two calculate_mAP calls
+        # (ssd3d.py:505-506) and the device state of the metric launches (own detection workspace: predict rebinds the eval
+        # plan's NaN flag into the model's workspace)
+        self.metric_thresholds = (0.1, 0.5)
+        self._met = {}          # (device, N, top_k, G) -> detection workspace + result buffer
+        self._met_acc = None    # f64 per-step sums [thr][mAP, precision, recall, f1] ..., steps
+        self._met_last = None   # (result buffer, N, top_k, G) of the latest metric step
 
     def _reducer(self, arena):
         if self.reducer is None or self.reducer.arena is not arena:
@@ -203,7 +216,8 @@ class FusedTrainer:
         off.copy_(obj_off, non_blocking=True)
         return x, gb, gl, off, cap
 
-    def step_packed(self, images, gt_boxes, gt_labels, obj_off, total_objects, sync=True, resident=False, fence=True):
+    def step_packed(self, images, gt_boxes, gt_labels, obj_off, total_objects, sync=True, resident=False, fence=True,
+                    metrics=False):
         """One optimisation step on already packed targets (see MultiBoxLoss.pack_targets).  With ``sync=False``
         nothing is read back: the returned dict holds the device tensor ``loss_out`` = [conf, loc, n_positives].
 
@@ -218,12 +232,20 @@ class FusedTrainer:
         two cross-queue hand-offs of ~16 us each per step, during which the GPU idles.  ``fence=False`` (with ``sync=False``
         and ``resident=True``; replayed steps only) enqueues the step straight behind the previous one: consecutive steps are
         ordered by the trainer's stream itself, and the CALLER must order anything else against it - ``trainer.fence()`` or
-        ``torch.cuda.synchronize()`` - before it reads parameters / ``loss_out`` or rewrites the resident inputs."""
+        ``torch.cuda.synchronize()`` - before it reads parameters / ``loss_out`` or rewrites the resident inputs.
+
+        ``metrics=True``: behind the step, detection on its forward outputs and the detection metrics at
+        ``metric_thresholds`` (see the module docstring); the recorded step program is the same either way."""
         m = self.model
         if not images.is_cuda:
             raise _lib.HipKernelError("FusedTrainer runs on the HIP device only (no CPU fallback)")
         dev = images.device
         m._ensure_device_state(dev)
+        if metrics and m.priors_cxcycz.size(0) <= 500:  # ssd3d.py:504-515
+            raise NotImplementedError
+        n_objects = int(total_objects)  # (staging replaces total_objects by the buffers' capacity)
+        if metrics:
+            metric_capacity_check(images.shape[0], int(m.top_k), n_objects, len(self.metric_thresholds))
         eng = m._engine
         arena = eng.ensure_arena(dev)
         red = self._reducer(arena)
@@ -296,6 +318,8 @@ class FusedTrainer:
                     if "native" not in entry:
                         entry["native"] = _lib.compile_program(prog, (), stream, dev.index or 0)
                     _lib.replay_native(entry["native"])
+            if metrics:  # after the step's launches (never recorded into its program), on the same stream
+                self._enqueue_metrics(pl, gt_boxes, gt_labels, obj_off, n_objects, dev)
         if not unfenced:
             caller.wait_stream(self._stream)
         self.last_plan = pl
@@ -309,14 +333,69 @@ class FusedTrainer:
             out.update(conf=conf, loc=loc, loss=conf + float(m.loss_fn.alpha) * loc, n_positives=int(npos))
         return out
 
+    def _enqueue_metrics(self, pl, gt_boxes, gt_labels, obj_off, total_objects, dev):
+        """msl_detect_objects on the step's forward outputs (written before the update; nothing in the step reuses them
+        as scratch) with the model's current min_score / max_overlap / top_k, then msl_detection_metrics into the
+        trainer's result buffer and accumulator.  The next step's forward pass is enqueued behind these on the same
+        stream, so it cannot overwrite locs / scores (or the staged targets) under them."""
+        m = self.model
+        N, P, ncls = pl.locs.size(0), pl.locs.size(1), pl.scores.size(2)
+        top_k, n_thr = int(m.top_k), len(self.metric_thresholds)
+        key = (dev, N, P, ncls, top_k, int(total_objects))
+        ent = self._met.get(key)
+        if ent is None:
+            ent = self._met[key] = {
+                "ws": LSSD3D.new_detect_workspace(N, P, ncls, top_k, dev),
+                "thr": torch.tensor(self.metric_thresholds, dtype=torch.float32).to(dev),
+                "out": torch.empty(metric_out_size(n_thr, N * top_k, int(total_objects)), dtype=torch.float32, device=dev)}
+        if self._met_acc is None or self._met_acc.device != dev or self._met_acc.numel() != 4 * n_thr + 1:
+            self._met_acc = torch.zeros(4 * n_thr + 1, dtype=torch.float64, device=dev)
+        w = ent["ws"]
+        m._detect_launch(pl.locs, pl.scores, w, m.min_score, m.max_overlap, top_k)
+        launch_detection_metrics(w["ob"], w["os"], w["ol"], w["oc"], gt_boxes, gt_labels, obj_off, int(total_objects),
+                                 ent["thr"], ent["out"], accum=self._met_acc)
+        self._met_last = (ent["out"], n_thr, N * top_k, int(total_objects))
+
+    def metric_sums(self, reset=True):
+        """(per-step sums [mAP, precision, recall, f1] at each of ``metric_thresholds``, number of metric steps) since the
+        last reset: one synchronisation.  What a data-parallel loop all-reduces before dividing."""
+        if self._met_acc is None:
+            return [0.0] * (4 * len(self.metric_thresholds)), 0
+        self.fence()
+        host = self._met_acc.cpu().tolist()
+        if reset:
+            with torch.cuda.stream(self._stream):
+                self._met_acc.zero_()
+        return host[:-1], int(host[-1])
+
+    def training_metrics(self, reset=True):
+        """Means over the metric steps since the last reset (training_epoch_end, ssd3d.py:657-690; a NaN step makes the
+        mean NaN, as torch.stack(...).mean() does): {"metrics_10": {mAP, precision, recall, f1_score}, "metrics_50": ...,
+        "steps": k}."""
+        sums, k = self.metric_sums(reset)
+        out = {"steps": k}
+        for i, thr in enumerate(self.metric_thresholds):
+            vals = [v / k if k else float("nan") for v in sums[4 * i:4 * i + 4]]
+            out[f"metrics_{int(round(thr * 100))}"] = dict(zip(("mAP", "precision", "recall", "f1_score"), vals))
+        return out
+
+    def last_metrics(self):
+        """The latest metric step's calculate_mAP(return_detail=True) dicts, one per threshold (one device copy)."""
+        if self._met_last is None:
+            return None
+        out, n_thr, D, G = self._met_last
+        self.fence()
+        host = out.cpu().numpy()
+        return tuple(metric_details(host, n_thr, D, G, t) for t in range(n_thr))
+
     def fence(self):
         """Order the caller's current stream behind every step enqueued so far (after ``step_packed(..., fence=False)``)."""
         if self._stream is not None:
             torch.cuda.current_stream(self._stream.device).wait_stream(self._stream)
 
-    def step(self, images, boxes, labels, sync=True):
+    def step(self, images, boxes, labels, sync=True, metrics=False):
         gb, gl, off, T = MultiBoxLoss.pack_targets(boxes, labels, images.device)
-        return self.step_packed(images, gb, gl, off, T, sync=sync)
+        return self.step_packed(images, gb, gl, off, T, sync=sync, metrics=metrics)
 
     def state_dict(self):
         return {"optimizer": self.opt.state_dict(), "scheduler": None if self.sch is None else self.sch.state_dict()}

@@ -4,6 +4,9 @@
   no CPU path for them.
 * ``calculate_mAP`` (``utils.py:157-396``) is host-side bookkeeping in the reference (a Python loop per
   detection) and stays host-side here: detections are tiny ragged lists, copied to the host once.
+* ``calculate_mAP_device`` computes the same values with one HIP launch (``csrc/metrics.hip``), bit for bit; the fused
+  trainer runs that kernel on the detections ``msl_detect_objects`` leaves in device memory (training metrics without a
+  host synchronisation per step).
 """
 import numpy as np
 import torch
@@ -193,3 +196,117 @@ def calculate_mAP(det_boxes, det_labels, det_scores, true_boxes, true_labels, tr
     return {"APs": 0., "mAP": mean_average_precision, "precision": 0., "recall": 0., "f1_score": 0.,
             "sorted_det_scores": {}, "TP": torch.zeros(0), "FP": torch.zeros(0), "n_true_boxes": n_easy,
             "found_boxes_volumes_per_class": torch.zeros(0), "not_found_boxes_volumes_per_class": T(vols)}
+
+
+# ----------------------------------------------------------------------------------------------------------
+# metrics (device side, csrc/metrics.hip)
+
+METRIC_SUMMARY = 8  # per threshold: AP, mAP, precision, recall, f1, n_true_boxes, class-1 detections, TP count
+_recall_tables = {}
+
+
+def recall_thresholds(dev):
+    """The 11 recall thresholds of utils.py:336 as f32 device table (the f32 values of ``torch.arange(0, 1.1, .1)``)."""
+    t = _recall_tables.get(dev)
+    if t is None:
+        t = _recall_tables[dev] = torch.arange(start=0, end=1.1, step=.1).to(device=dev, dtype=torch.float32)
+    return t
+
+
+def metric_capacity_check(N, top_k, G, n_thr):
+    """Host planning of ``msl_detection_metrics``: raise instead of truncating a batch the kernel cannot hold."""
+    lib = _lib.load()
+    if N * top_k > lib.msl_detection_metrics_max(0):
+        raise _lib.HipKernelError(f"detection metrics: {N} images x {top_k} detection slots exceed the kernel's "
+                                  f"{lib.msl_detection_metrics_max(0)} detections per batch")
+    if G > lib.msl_detection_metrics_max(1):
+        raise _lib.HipKernelError(f"detection metrics: {G} ground-truth boxes exceed the kernel's "
+                                  f"{lib.msl_detection_metrics_max(1)} per batch")
+    if not 0 < n_thr <= lib.msl_detection_metrics_max(2):
+        raise _lib.HipKernelError(f"detection metrics: {n_thr} IoU thresholds")
+
+
+def metric_out_size(n_thr, D, G):
+    """f32 elements of one result buffer: [summary | sorted scores | TP | FP | GT status | GT volumes]."""
+    return n_thr * METRIC_SUMMARY + D + 2 * n_thr * D + n_thr * G + G
+
+
+def _metric_views(out, n_thr, D, G):
+    sizes = [("summary", n_thr * METRIC_SUMMARY), ("scores", D), ("tp", n_thr * D), ("fp", n_thr * D),
+             ("status", n_thr * G), ("vol", G)]
+    v, o = {}, 0
+    for name, n in sizes:
+        v[name] = out[o:o + n]
+        o += n
+    v["summary"] = v["summary"].reshape(n_thr, METRIC_SUMMARY)
+    for name in ("tp", "fp", "status"):
+        v[name] = v[name].reshape(n_thr, -1)
+    return v
+
+
+def launch_detection_metrics(ob, os_, ol, oc, gt_boxes, gt_labels, obj_off, G, thresholds, out, accum=None, stream=None):
+    """Enqueue ``msl_detection_metrics`` (no synchronisation): detections in msl_detect_objects' layout (ob (N,k,6),
+    os_ (N,k), ol (N,k) i64, oc (>= N) i32), packed ground truth, f32 device table of IoU thresholds, ``out`` of
+    ``metric_out_size`` f32 elements; ``accum`` (n_thr*4+1 f64) collects per-step sums."""
+    N, top_k = ol.shape
+    n_thr, D = thresholds.numel(), N * top_k
+    metric_capacity_check(N, top_k, G, n_thr)
+    v = _metric_views(out, n_thr, D, G)
+    _lib.call("msl_detection_metrics", ptr(ob), ptr(os_), ptr(ol), ptr(oc), N, top_k, ptr(gt_boxes), ptr(gt_labels),
+              ptr(obj_off), G, ptr(thresholds), n_thr, ptr(recall_thresholds(ob.device)), ptr(v["summary"]), ptr(v["tp"]),
+              ptr(v["fp"]), ptr(v["scores"]), ptr(v["status"]), ptr(v["vol"]), ptr(accum),
+              _stream() if stream is None else stream)
+
+
+def metric_details(host_out, n_thr, D, G, t):
+    """Threshold ``t``'s detail dict (calculate_mAP's ``return_detail`` form: same keys, same types) from a host copy of a
+    result buffer.  ``G``: the batch's number of ground-truth boxes."""
+    v = _metric_views(np.asarray(host_out, dtype=np.float32), n_thr, D, G)
+    sm = v["summary"][t]
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    K = int(sm[6])
+    if K == 0:  # utils.py:370-380: nothing detected (every ground-truth volume, whatever its label, is "not found")
+        return {"APs": 0., "mAP": float(sm[1]), "precision": 0., "recall": 0., "f1_score": 0., "sorted_det_scores": {},
+                "TP": torch.zeros(0), "FP": torch.zeros(0), "n_true_boxes": int(sm[5]),
+                "found_boxes_volumes_per_class": torch.zeros(0), "not_found_boxes_volumes_per_class": T(v["vol"])}
+    st, vol = v["status"][t], v["vol"]
+    return {"APs": float(sm[0]), "mAP": float(sm[1]), "precision": float(sm[2]), "recall": float(sm[3]),
+            "f1_score": float(sm[4]), "sorted_det_scores": {1: T(v["scores"][:K])}, "TP": T(v["tp"][t, :K]),
+            "FP": T(v["fp"][t, :K]), "n_true_boxes": int(sm[5]), "found_boxes_volumes_per_class": T(vol[st == 1]),
+            "not_found_boxes_volumes_per_class": T(vol[st == 0])}
+
+
+def calculate_mAP_device(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_difficulties, min_overlap=0.5,
+                         return_detail=False):
+    """``calculate_mAP`` (utils.py:242-396) on the HIP device: same parameters, same return values, bit for bit.
+    Inputs: lists (one entry per image) of device tensors.  The ragged lists are packed into the padded layout of
+    ``msl_detect_objects``; one launch, one device-to-host copy of the results.  'difficult' ground truth (never set in
+    this repository) is not supported."""
+    from .ssd3d import MultiBoxLoss
+    assert len(det_boxes) == len(det_labels) == len(det_scores) == len(true_boxes) == len(true_labels) == len(true_difficulties)
+    if any(bool(torch.as_tensor(d).bool().any()) for d in true_difficulties):
+        raise NotImplementedError("calculate_mAP_device: 'difficult' ground-truth boxes are not supported")
+    N = len(true_labels)
+    dev = next((t.device for t in list(det_boxes) + list(true_boxes) if torch.is_tensor(t) and t.is_cuda), None)
+    if dev is None:
+        raise _lib.HipKernelError("calculate_mAP_device: expected tensors on the HIP device (no CPU fallback)")
+    counts = [int(l.shape[0]) for l in det_labels]
+    top_k = max([1] + counts)
+    gb, gl, off, G = MultiBoxLoss.pack_targets([b.reshape(-1, 6) for b in true_boxes], [l.reshape(-1) for l in true_labels], dev)
+    metric_capacity_check(N, top_k, G, 1)
+    ob = torch.zeros((N, top_k, 6), dtype=torch.float32, device=dev)
+    os_ = torch.zeros((N, top_k), dtype=torch.float32, device=dev)
+    ol = torch.zeros((N, top_k), dtype=torch.int64, device=dev)
+    for i, k in enumerate(counts):
+        if k:
+            ob[i, :k] = det_boxes[i].reshape(-1, 6).to(device=dev, dtype=torch.float32)
+            os_[i, :k] = det_scores[i].reshape(-1).to(device=dev, dtype=torch.float32)
+            ol[i, :k] = det_labels[i].reshape(-1).to(device=dev, dtype=torch.int64)
+    oc = torch.tensor(counts, dtype=torch.int32).to(dev)
+    thr = torch.tensor([min_overlap], dtype=torch.float32).to(dev)
+    out = torch.empty(metric_out_size(1, N * top_k, G), dtype=torch.float32, device=dev)
+    launch_detection_metrics(ob, os_, ol, oc, gb, gl, off, G, thr, out)
+    d = metric_details(out.cpu().numpy(), 1, N * top_k, G, 0)  # the one device-to-host copy
+    if not return_detail:
+        return {rev_label_map[1]: d["APs"]}, d["mAP"]
+    return d

@@ -417,6 +417,21 @@ int msl_detection_metrics(const float* det_boxes, const float* det_scores, const
                           float* summary, float* tp, float* fp, float* sorted_scores, float* gt_status, float* gt_vol,
                           double* accum, void* stream);
 
+/* ---- dataset-scale evaluation: the (IoU x score threshold) grid of eval.py, each point calculate_mAP (utils.py:242-396)
+ * on the detections with score >= min_score, class 1 only, no cap on detections or ground truth (csrc/evaluate.hip).
+ * det_rows (D,8) f32: box(6), score, label (as f32); det_off (N+1) i32: detections of image n are [det_off[n],
+ * det_off[n+1]).  Ground truth packed as for msl_detection_metrics.  iou_thr (n_iou) f32 (strict `>`), score_thr (n_sc)
+ * f64 (kept iff (double)score >= thr), recall_thr (11) f32.  workspace: _workspace_bytes(...) bytes (0 = unsupported
+ * sizes).  out (f32 words): summary (n_iou,n_sc,8) [AP, mAP, precision, recall, f1, n_true_boxes, K_c, TP count] |
+ * sorted scores (D) | TP flags in rank order (n_iou,D) | claim rank (n_iou,G) i32: rank of the detection that claimed
+ * the box, 0x7fffffff = never, -1 = not class 1 | volumes (G).  Values at (t, c) are those of the first K_c ranks.
+ * Bit-identical to the host code while the counts stay below 2^24.  Sizes beyond int32 indexing -> -2. */
+size_t msl_evaluate_workspace_bytes(int D, int N, int G, int n_iou, int n_sc);
+int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, int N, const float* gt_boxes,
+                            const long long* gt_labels, const int* obj_off, int G, const float* iou_thr, int n_iou,
+                            const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
+                            size_t workspace_bytes, float* out, void* stream);
+
 /* ---- optimiser + NaN guard : ssd3d.py:704-722, :258-261 ---------------------------------------------------- */
 /* hp (device, 8 floats): step_size(bias), step_size(other), sqrt(bias_correction2), beta1, beta2, eps,
  * weight_decay, gradient scale.  is_bias (n bytes): 1 for elements of '.bias' parameters (2*lr group). */

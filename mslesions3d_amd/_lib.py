@@ -132,6 +132,8 @@ _SIGNATURES = {
     "msl_detect_objects": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _I] + [_P] * 15 + [_P]),
     "msl_detection_metrics_max": (_Z, [_I]),
     "msl_detection_metrics": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P] + [_P] * 7 + [_P]),
+    "msl_evaluate_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "msl_evaluate_detections": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _Z, _P, _P]),
     "msl_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "msl_nan_flag": (_I, [_P, _Z, _P, _I, _P]),
     "msl_nan_flag2": (_I, [_P, _Z, _I, _P, _Z, _I, _P, _P]),

@@ -12,7 +12,7 @@
 //             table, numpy's pairwise f32 mean of it, precision / recall / F1 with the host's f32 expressions
 // The IoU keeps _iou_one_to_many's operation order (the one of msl_iou_matrix, multibox.hip) with FMA contraction
 // off, so every output is bit-identical to the host code, NaNs included.
-#include "common.hpp"
+#include "detmetrics.hpp"
 #pragma clang fp contract(off)
 
 namespace {
@@ -21,61 +21,13 @@ constexpr int MT_THREADS = 1024;  // 16 waves
 constexpr int MT_WAVES = MT_THREADS / 64;
 constexpr int MT_MAXD = 4096;     // detections per batch (N * top_k)
 constexpr int MT_MAXG = 4096;     // ground-truth boxes per batch
-constexpr int MT_NREC = 11;       // recall thresholds (utils.py:336)
 constexpr int MT_SUMMARY = 8;     // AP, mAP, precision, recall, f1, n_true_boxes, detections, TP count
 
-// fp32, same operation order as utils.py::_iou_one_to_many / multibox.hip box_iou (a = detection, b = ground truth)
-__device__ __forceinline__ float det_gt_iou(const float* a, const float* b) {
-  float e[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float lo = fmaxf(a[i], b[i]);
-    const float hi = fminf(a[3 + i], b[3 + i]);
-    e[i] = fmaxf(hi - lo, 0.0f);
-  }
-  const float inter = e[0] * e[1] * e[2];
-  const float va = (a[3] - a[0]) * (a[4] - a[1]) * (a[5] - a[2]);
-  const float vb = (b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);
-  return inter / (va + vb - inter);
-}
-
-struct Best {
-  float v;
-  int g;  // ground-truth index, -1 = none
-};
-
-// numpy argmax over a list: the first NaN if there is one, else the first maximum.  Commutative and associative on
-// (value, index) pairs, so a butterfly over the wave gives every lane the same answer.
-__device__ __forceinline__ Best pick(Best a, Best b) {
-  if (b.g < 0) return a;
-  if (a.g < 0) return b;
-  const bool an = isnan(a.v), bn = isnan(b.v);
-  if (an != bn) return an ? a : b;
-  if (!an && a.v != b.v) return a.v > b.v ? a : b;
-  return a.g < b.g ? a : b;
-}
-
-// block-wide exclusive prefix of one int per thread; `tot` receives the total.  Uses `scratch` (MT_WAVES ints).
-__device__ __forceinline__ int block_excl_scan(int v, int* scratch, int& tot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();  // scratch may still be read by an earlier call
-  if (lane == 63) scratch[w] = incl;
-  __syncthreads();
-  int before = 0;
-  tot = 0;
-  for (int k = 0; k < MT_WAVES; ++k) {
-    const int s = scratch[k];
-    if (k < w) before += s;
-    tot += s;
-  }
-  return before + incl - v;
-}
+using msl::Best;
+using msl::block_excl_scan;
+using msl::det_gt_iou;
+using msl::MT_NREC;
+using msl::pick;
 
 // grid (n_thr), MT_THREADS threads
 __global__ __launch_bounds__(MT_THREADS) void detection_metrics_kernel(
@@ -124,7 +76,7 @@ __global__ __launch_bounds__(MT_THREADS) void detection_metrics_kernel(
       valid = s < cnt && det_labels[j] == 1;
     }
     int tot;
-    const int pos = K + block_excl_scan(valid ? 1 : 0, scratch, tot);
+    const int pos = K + block_excl_scan<MT_WAVES>(valid ? 1 : 0, scratch, tot);
     if (valid) {
       c_j[pos] = j;
       c_s[pos] = det_scores[j];
@@ -168,11 +120,7 @@ __global__ __launch_bounds__(MT_THREADS) void detection_metrics_kernel(
         const Best c = {det_gt_iou(b, gt_boxes + (size_t)g * 6), g};
         best = pick(best, c);
       }
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const Best c = {__shfl_xor(best.v, o, 64), __shfl_xor(best.g, o, 64)};
-        best = pick(best, c);
-      }
+      best = msl::wave_pick(best);
       if (lane == 0) {
         // no class-1 GT in the image -> FP; NaN > thr is false -> FP; a claimed GT -> FP (difficult flags are all False)
         const bool tp = best.g >= 0 && best.v > thr && claim[best.g] == 0;
@@ -192,7 +140,7 @@ __global__ __launch_bounds__(MT_THREADS) void detection_metrics_kernel(
   int own = 0;
   for (int r = r0; r < r1; ++r) own += tpf[r];
   int total_tp;
-  int ctp = block_excl_scan(own, scratch, total_tp);
+  int ctp = block_excl_scan<MT_WAVES>(own, scratch, total_tp);
   float pm[MT_NREC], rt[MT_NREC];
 #pragma unroll
   for (int i = 0; i < MT_NREC; ++i) {
@@ -232,12 +180,7 @@ __global__ __launch_bounds__(MT_THREADS) void detection_metrics_kernel(
   float* out = summary + (size_t)t * MT_SUMMARY;
   float ap = 0.f, precision = 0.f, recall = 0.f, f1 = 0.f;
   if (K > 0) {
-    // precs.mean(dtype=float32): numpy's pairwise sum (eight accumulators, then the tail in sequence), then / 11
-    float s = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-    s = s + p[8];
-    s = s + p[9];
-    s = s + p[10];
-    ap = s / 11.0f;
+    ap = msl::mean11_pairwise(p);  // precs.mean(dtype=float32)
     const float tps = (float)total_tp, fps = (float)(K - total_tp), fn = (float)(n_easy - total_tp);
     recall = tps / (tps + fn);
     precision = tps / (tps + fps);

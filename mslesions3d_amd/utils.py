@@ -7,6 +7,8 @@
 * ``calculate_mAP_device`` computes the same values with one HIP launch (``csrc/metrics.hip``), bit for bit; the fused
   trainer runs that kernel on the detections ``msl_detect_objects`` leaves in device memory (training metrics without a
   host synchronisation per step).
+* ``evaluate_detections`` computes the (IoU x score threshold) grid of the reference's ``eval.py`` at dataset scale
+  (``csrc/evaluate.hip``: no cap on detections or ground truth), each grid point bit-identical to ``calculate_mAP``.
 """
 import numpy as np
 import torch
@@ -258,22 +260,28 @@ def launch_detection_metrics(ob, os_, ol, oc, gt_boxes, gt_labels, obj_off, G, t
               _stream() if stream is None else stream)
 
 
-def metric_details(host_out, n_thr, D, G, t):
-    """Threshold ``t``'s detail dict (calculate_mAP's ``return_detail`` form: same keys, same types) from a host copy of a
-    result buffer.  ``G``: the batch's number of ground-truth boxes."""
-    v = _metric_views(np.asarray(host_out, dtype=np.float32), n_thr, D, G)
-    sm = v["summary"][t]
+def _detail_dict(sm, scores, tp, fp, vol, status):
+    """calculate_mAP's ``return_detail`` dict (same keys, same types) from host copies of one grid point's device results:
+    ``sm`` its METRIC_SUMMARY values (sm[6] = K, the class-1 detections kept), ``scores`` / ``tp`` / ``fp`` in rank order
+    (first K entries used), ``vol`` every ground-truth volume, ``status`` per ground-truth box (1 detected, 0 not, 2 not
+    class 1)."""
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
     K = int(sm[6])
     if K == 0:  # utils.py:370-380: nothing detected (every ground-truth volume, whatever its label, is "not found")
         return {"APs": 0., "mAP": float(sm[1]), "precision": 0., "recall": 0., "f1_score": 0., "sorted_det_scores": {},
                 "TP": torch.zeros(0), "FP": torch.zeros(0), "n_true_boxes": int(sm[5]),
-                "found_boxes_volumes_per_class": torch.zeros(0), "not_found_boxes_volumes_per_class": T(v["vol"])}
-    st, vol = v["status"][t], v["vol"]
+                "found_boxes_volumes_per_class": torch.zeros(0), "not_found_boxes_volumes_per_class": T(vol)}
     return {"APs": float(sm[0]), "mAP": float(sm[1]), "precision": float(sm[2]), "recall": float(sm[3]),
-            "f1_score": float(sm[4]), "sorted_det_scores": {1: T(v["scores"][:K])}, "TP": T(v["tp"][t, :K]),
-            "FP": T(v["fp"][t, :K]), "n_true_boxes": int(sm[5]), "found_boxes_volumes_per_class": T(vol[st == 1]),
-            "not_found_boxes_volumes_per_class": T(vol[st == 0])}
+            "f1_score": float(sm[4]), "sorted_det_scores": {1: T(scores[:K])}, "TP": T(tp[:K]),
+            "FP": T(fp[:K]), "n_true_boxes": int(sm[5]), "found_boxes_volumes_per_class": T(vol[status == 1]),
+            "not_found_boxes_volumes_per_class": T(vol[status == 0])}
+
+
+def metric_details(host_out, n_thr, D, G, t):
+    """Threshold ``t``'s detail dict (calculate_mAP's ``return_detail`` form: same keys, same types) from a host copy of a
+    result buffer.  ``G``: the batch's number of ground-truth boxes."""
+    v = _metric_views(np.asarray(host_out, dtype=np.float32), n_thr, D, G)
+    return _detail_dict(v["summary"][t], v["scores"], v["tp"][t], v["fp"][t], v["vol"], v["status"][t])
 
 
 def calculate_mAP_device(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_difficulties, min_overlap=0.5,
@@ -310,3 +318,106 @@ def calculate_mAP_device(det_boxes, det_labels, det_scores, true_boxes, true_lab
     if not return_detail:
         return {rev_label_map[1]: d["APs"]}, d["mAP"]
     return d
+
+
+# ----------------------------------------------------------------------------------------------------------
+# dataset-scale evaluation (device side, csrc/evaluate.hip): the (IoU x score threshold) grid of the reference's eval.py
+
+def _host(x, dtype):
+    return torch.as_tensor(x).detach().to(device="cpu", dtype=dtype)
+
+
+def evaluate_capacity_check(D, N, G, n_iou, n_sc):
+    """Host planning of ``msl_evaluate_detections``: its workspace size in bytes, or HipKernelError for sizes it cannot
+    index (the limits are int32 indexing and memory; there is no fixed cap)."""
+    if N <= 0 or n_iou <= 0 or n_sc <= 0:
+        raise _lib.HipKernelError(f"evaluate_detections: {N} images, {n_iou} IoU thresholds, {n_sc} score thresholds")
+    ws = _lib.load().msl_evaluate_workspace_bytes(D, N, G, n_iou, n_sc)
+    if ws == 0:
+        raise _lib.HipKernelError(f"evaluate_detections: {D} detections, {N} images, {G} ground-truth boxes x {n_iou} IoU "
+                                  f"thresholds x {n_sc} score thresholds exceed int32 indexing")
+    return ws
+
+
+def prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores):
+    """Pack one evaluation for ``msl_evaluate_detections``: the detections into one host buffer with one host-to-device
+    copy, the ground truth with ``MultiBoxLoss.pack_targets``, the workspace and the result buffer allocated.  Returns a
+    dict with ``launch()`` (enqueue the whole pipeline on the current stream, no synchronisation), ``out`` (the device
+    result buffer) and the sizes."""
+    from .ssd3d import MultiBoxLoss
+    ious, scs = list(min_overlaps), list(min_scores)
+    N, n_iou, n_sc = len(true_labels), len(ious), len(scs)
+    dev = next((t.device for t in [*det_boxes, *det_scores, *true_boxes] if torch.is_tensor(t) and t.is_cuda), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise _lib.HipKernelError("evaluate_detections: needs the HIP device (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    boxes = [_host(b, torch.float32).reshape(-1, 6) for b in det_boxes]
+    scores = [_host(s, torch.float32).reshape(-1, 1) for s in det_scores]
+    labels = [_host(l, torch.int64).reshape(-1, 1) for l in det_labels]
+    counts = [b.shape[0] for b in boxes]
+    assert counts == [s.shape[0] for s in scores] == [l.shape[0] for l in labels]
+    D = sum(counts)
+    gb, gl, goff, G = MultiBoxLoss.pack_targets([_host(b, torch.float32).reshape(-1, 6) for b in true_boxes],
+                                                [_host(l, torch.int64).reshape(-1) for l in true_labels], dev)
+    ws_bytes = evaluate_capacity_check(D, N, G, n_iou, n_sc)
+    # one host buffer, one copy: detection rows (D,8) [box, score, label as f32] | det_off (N+1) i32 | IoU thresholds f32 |
+    # (8-byte aligned) score thresholds f64
+    det_off = np.zeros(N + 1, dtype=np.int32)
+    det_off[1:] = np.cumsum(counts)
+    rows = torch.cat([torch.cat(boxes), torch.cat(scores), torch.cat(labels).to(torch.float32)], 1) if D else torch.zeros((0, 8))
+    o_off = D * 8
+    o_iou = o_off + N + 1
+    o_sc = o_iou + n_iou + ((o_iou + n_iou) & 1)
+    packed = torch.cat([rows.reshape(-1), torch.from_numpy(det_off).view(torch.float32),
+                        torch.tensor(ious, dtype=torch.float32), torch.zeros(o_sc - o_iou - n_iou),
+                        torch.tensor(scs, dtype=torch.float64).view(torch.float32)]).to(dev)
+    base = packed.data_ptr()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(n_iou * n_sc * METRIC_SUMMARY + D + n_iou * D + n_iou * G + G, dtype=torch.float32, device=dev)
+    recall = recall_thresholds(dev)
+    args = (base, base + 4 * o_off, D, N, ptr(gb), ptr(gl), ptr(goff), G, base + 4 * o_iou, n_iou, base + 4 * o_sc, n_sc,
+            ptr(recall), ptr(ws), ws_bytes, ptr(out))
+
+    def launch():
+        _lib.call("msl_evaluate_detections", *args, _stream())
+
+    return {"launch": launch, "out": out, "D": D, "N": N, "G": G, "ious": ious, "scores": scs,
+            "keep": (packed, ws, gb, gl, goff, recall)}
+
+
+def evaluate_detections(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_difficulties,
+                        min_overlaps=(0.5,), min_scores=(0.0,), return_detail=False):
+    """The grid of the reference's eval.py on the HIP device: ``{(min_overlap, min_score): calculate_mAP(<the detections
+    with score >= min_score>, ..., min_overlap=min_overlap, return_detail=return_detail)}``, bit for bit, NaNs included.
+    A detection is kept iff ``float(score) >= float(min_score)`` (f64, as eval.py's retrieve_boxes compares).
+
+    Inputs: lists (one entry per image) of tensors on any device, or arrays.  The detections are packed on the host and
+    copied to the device once; the ground truth is packed by ``MultiBoxLoss.pack_targets``; every grid point comes from
+    one enqueue of ``msl_evaluate_detections`` and one device-to-host copy.  No cap on detections or ground truth.
+    'difficult' ground truth is not supported."""
+    assert len(det_boxes) == len(det_labels) == len(det_scores) == len(true_boxes) == len(true_labels) == len(true_difficulties)
+    if any(bool(torch.as_tensor(d).bool().any()) for d in true_difficulties):
+        raise NotImplementedError("evaluate_detections: 'difficult' ground-truth boxes are not supported")
+    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores)
+    plan["launch"]()
+    ious, scs, D, G = plan["ious"], plan["scores"], plan["D"], plan["G"]
+    n_iou, n_sc = len(ious), len(scs)
+    n_sum = n_iou * n_sc * METRIC_SUMMARY
+    host = (plan["out"] if return_detail else plan["out"][:n_sum]).cpu().numpy()  # the one device-to-host copy
+    summary = host[:n_sum].reshape(n_iou, n_sc, METRIC_SUMMARY)
+    if not return_detail:
+        return {(ious[t], scs[c]): ({rev_label_map[1]: float(summary[t, c, 0])}, float(summary[t, c, 1]))
+                for t in range(n_iou) for c in range(n_sc)}
+    sorted_scores = host[n_sum:n_sum + D]
+    tp = host[n_sum + D:n_sum + D + n_iou * D].reshape(n_iou, D)
+    claim = host[n_sum + D + n_iou * D:n_sum + D + n_iou * (D + G)].view(np.int32).reshape(n_iou, G)
+    vol = host[n_sum + D + n_iou * (D + G):]
+    res = {}
+    for t in range(n_iou):
+        fp = np.float32(1) - tp[t]
+        for c in range(n_sc):
+            K = int(summary[t, c, 6])
+            status = np.where(claim[t] < 0, 2, np.where(claim[t] < K, 1, 0))
+            res[(ious[t], scs[c])] = _detail_dict(summary[t, c], sorted_scores, tp[t], fp, vol, status)
+    return res

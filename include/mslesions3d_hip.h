@@ -131,19 +131,12 @@ int msl_dwconv_fwd_num_partials(int N, int C, int D, int H, int W, int stride);
 int msl_dwconv_fwd_variant(int N, int C, int D, int H, int W, int stride); /* 0 naive, 1 stream, 2 resident, 3 wave */
 int msl_dwconv_fwd(const float* x, const float* in_scale, const float* in_shift, const float* w, float* y,
                    double* partials, int N, int C, int D, int H, int W, int stride, int force_naive, void* stream);
-/* stride-1 bwd-data as a forward pass with reversed taps on the LDS-resident kernel (-2 if the shape is not on that path) */
-int msl_dwconv_s1_bwd_data_resident(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
-                                    int accumulate, void* stream);
 /* forward with the input's BatchNorm folded in-kernel from the producer's partials (no finalize launch on the chain) */
 int msl_dwconv_fwd_fold(const float* x, const double* in_partials, int in_np, double in_count, const float* gamma,
                         const float* beta, float eps, const float* w, float* y, double* partials, int N, int C, int D,
                         int H, int W, int stride, void* stream);
 int msl_dwconv_bwd_data(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
                         int stride, int accumulate, void* stream);
-/* bwd-weight on the LDS-tiled forward machinery (-2 / -1 when the shape is on the generic path) */
-int msl_dwconv_bwd_weight_tiled(const float* dy, const float* x, const float* in_scale, const float* in_shift,
-                                double* partials, int N, int C, int D, int H, int W, int stride, void* stream);
-int msl_dwconv_bwd_weight_tiled_num_partials(int N, int C, int D, int H, int W, int stride);
 /* stride-2 bwd-data that also emits the BatchNorm-backward partials of the layer it feeds (fp64 [2][C][NP]) */
 int msl_dwconv_bwd_data_bnreduce_num_partials(int N, int C, int D, int H, int W);
 int msl_dwconv_bwd_data_bnreduce(const float* dy, const float* w, float* g_in, const float* y_prev,

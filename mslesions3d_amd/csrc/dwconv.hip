@@ -1648,11 +1648,6 @@ void launch_rows_eval(const T* x, const float* in_scale, const float* in_shift, 
 }
 
 // weight gradient on the wave kernels (the LDS-tiled / generic kernels remain for the other shapes)
-bool wave_bww_enabled() {
-  constexpr int on = 1;
-  return on != 0;
-}
-
 int wave_bww_num_partials(const WavePlan& wp, int N) { return N * wp.nslabs * (wp.wpp > 4 ? wp.wpp / 4 : 1); }
 
 template <typename T>
@@ -1793,92 +1788,6 @@ int msl_dwconv_bwd_weight_wave_bf16(const void* dz, const void* x, const float* 
   return MSL_OK;
 }
 
-// bwd-weight on the LDS-tiled kernels (MODE 1).  Returns MSL_ERR_UNSUPPORTED for shapes on the generic path.
-// partials: fp64 [C*27][NP], NP = msl_dwconv_bwd_weight_num_partials().
-
-int msl_dwconv_bwd_weight_tiled(const float* dy, const float* x, const float* in_scale, const float* in_shift,
-                                double* partials, int N, int C, int D, int H, int W, int stride, void* stream) {
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  if (wave_bww_enabled()) {
-    const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-    if (wp.ok) {
-      launch_wave_bww(wp, stride, x, in_scale, in_shift, dy, partials, N, C, D, (hipStream_t)stream);
-      MSL_LAUNCH_CHECK();
-      return MSL_OK;
-    }
-  }
-  DwPlan pl = make_plan(N, C, D, H, W, stride);
-  // many channels per workgroup (tiny tail volumes): the per-channel epilogue reduction dominates and the
-  // barrier-free wave-per-item kernel of dwconv_bwd.hip is faster
-  if (pl.variant == 0 || pl.G > 4) return MSL_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblocks = N * (C / pl.G) * pl.nslabs;
-  const size_t lds = std::max(pl.lds_bytes, (size_t)27 * 256 * sizeof(float));
-  float* dyp = const_cast<float*>(dy);
-  if (pl.variant == 1) {
-#define MSL_DW_BWW(S_, I_, L_)                                                                                  \
-  do {                                                                                                          \
-    int e_ = set_lds(dw_fwd_stream_kernel<S_, I_, L_, 1>, lds);                                                 \
-    if (e_) return e_;                                                                                          \
-    MSL_LAUNCH((dw_fwd_stream_kernel<S_, I_, L_, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale,   \
-                       in_shift, nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.SLAB, pl.nslabs, N, nofold); \
-  } while (0)
-    if (stride == 2) {
-      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_BWW(2, 1, 4);
-      else MSL_DW_BWW(2, 4, 12);
-    } else {
-      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_BWW(1, 1, 4);
-      else MSL_DW_BWW(1, 4, 12);
-    }
-#undef MSL_DW_BWW
-  } else {
-    if (stride == 2) {
-      int e_ = set_lds(dw_fwd_resident_kernel<2, 1>, lds);
-      if (e_) return e_;
-      MSL_LAUNCH((dw_fwd_resident_kernel<2, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale, in_shift,
-                         nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, nofold);
-    } else {
-      int e_ = set_lds(dw_fwd_resident_kernel<1, 1>, lds);
-      if (e_) return e_;
-      MSL_LAUNCH((dw_fwd_resident_kernel<1, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale, in_shift,
-                         nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, nofold);
-    }
-  }
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-int msl_dwconv_bwd_weight_tiled_num_partials(int N, int C, int D, int H, int W, int stride) {
-  if (wave_bww_enabled()) {
-    const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-    if (wp.ok) return wave_bww_num_partials(wp, N);
-  }
-  DwPlan pl = make_plan(N, C, D, H, W, stride);
-  return (pl.variant == 0 || pl.G > 4) ? -1 : pl.num_partials;
-}
-
-// Stride-1 bwd-data is the forward convolution of dy with the taps reversed (w[26-k]); reuse the LDS-resident
-// forward kernel.  Returns MSL_ERR_UNSUPPORTED when the shape is not on the resident fast path.
-int msl_dwconv_s1_bwd_data_resident(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
-                                    int accumulate, void* stream) {
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, 1);
-  if (wp.ok) {
-    launch_wave(wp, dy, nullptr, nullptr, w, g_in, nullptr, N, C, D, 1, accumulate, nofold, (hipStream_t)stream);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  DwPlan pl = make_plan(N, C, D, H, W, 1);
-  if (pl.variant != 2) return MSL_ERR_UNSUPPORTED;
-  const int nblocks = N * (C / pl.G) * pl.nslabs;
-  int e_ = set_lds(dw_fwd_resident_kernel<1, 0>, pl.lds_bytes);
-  if (e_) return e_;
-  MSL_LAUNCH((dw_fwd_resident_kernel<1, 0>), dim3(nblocks), dim3(256), pl.lds_bytes, (hipStream_t)stream, dy,
-                     nullptr, nullptr, w, g_in, nullptr, C, D, H, W, D, H, W, pl.G, pl.SLAB, pl.nslabs, N, 1, accumulate, nofold);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
 // bf16 storage, statistics-free forward of a map of at most 512 voxels (dw_small_eval_kernel); MSL_ERR_UNSUPPORTED if larger
 int msl_dwconv_fwd_small_eval_bf16(const void* x, const float* in_scale, const float* in_shift, const float* w, void* y, int N,
                                    int C, int D, int H, int W, int stride, void* stream) {
@@ -1985,3 +1894,85 @@ int msl_dwconv_fwd_fold(const float* x, const double* in_partials, int in_np, do
 }
 
 }  // extern "C"
+
+// ---- library-internal entry points of the LDS-tiled kernels (C++ linkage: not part of the C ABI) ----------------------------
+// bwd-weight on the wave kernels or the LDS-tiled kernels (MODE 1), for msl_dwconv_bwd_weight (dwconv_bwd.hip).  Returns
+// MSL_ERR_UNSUPPORTED for shapes on the generic path.  partials: fp64 [C*27][NP], NP = dwconv_bwd_weight_tiled_num_partials().
+int dwconv_bwd_weight_tiled(const float* dy, const float* x, const float* in_scale, const float* in_shift,
+                            double* partials, int N, int C, int D, int H, int W, int stride, void* stream) {
+  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
+  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
+  if (wp.ok) {
+    launch_wave_bww(wp, stride, x, in_scale, in_shift, dy, partials, N, C, D, (hipStream_t)stream);
+    MSL_LAUNCH_CHECK();
+    return MSL_OK;
+  }
+  DwPlan pl = make_plan(N, C, D, H, W, stride);
+  // many channels per workgroup (tiny tail volumes): the per-channel epilogue reduction dominates and the
+  // barrier-free wave-per-item kernel of dwconv_bwd.hip is faster
+  if (pl.variant == 0 || pl.G > 4) return MSL_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblocks = N * (C / pl.G) * pl.nslabs;
+  const size_t lds = std::max(pl.lds_bytes, (size_t)27 * 256 * sizeof(float));
+  float* dyp = const_cast<float*>(dy);
+  if (pl.variant == 1) {
+#define MSL_DW_BWW(S_, I_, L_)                                                                                  \
+  do {                                                                                                          \
+    int e_ = set_lds(dw_fwd_stream_kernel<S_, I_, L_, 1>, lds);                                                 \
+    if (e_) return e_;                                                                                          \
+    MSL_LAUNCH((dw_fwd_stream_kernel<S_, I_, L_, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale,   \
+                       in_shift, nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.SLAB, pl.nslabs, N, nofold); \
+  } while (0)
+    if (stride == 2) {
+      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_BWW(2, 1, 4);
+      else MSL_DW_BWW(2, 4, 12);
+    } else {
+      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_BWW(1, 1, 4);
+      else MSL_DW_BWW(1, 4, 12);
+    }
+#undef MSL_DW_BWW
+  } else {
+    if (stride == 2) {
+      int e_ = set_lds(dw_fwd_resident_kernel<2, 1>, lds);
+      if (e_) return e_;
+      MSL_LAUNCH((dw_fwd_resident_kernel<2, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale, in_shift,
+                         nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, nofold);
+    } else {
+      int e_ = set_lds(dw_fwd_resident_kernel<1, 1>, lds);
+      if (e_) return e_;
+      MSL_LAUNCH((dw_fwd_resident_kernel<1, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale, in_shift,
+                         nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, nofold);
+    }
+  }
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int dwconv_bwd_weight_tiled_num_partials(int N, int C, int D, int H, int W, int stride) {
+  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
+  if (wp.ok) return wave_bww_num_partials(wp, N);
+  DwPlan pl = make_plan(N, C, D, H, W, stride);
+  return (pl.variant == 0 || pl.G > 4) ? -1 : pl.num_partials;
+}
+
+// Stride-1 bwd-data is the forward convolution of dy with the taps reversed (w[26-k]); reuse the wave / LDS-resident
+// forward kernels, for msl_dwconv_bwd_data (dwconv_bwd.hip).  Returns MSL_ERR_UNSUPPORTED when the shape is on neither.
+int dwconv_s1_bwd_data_resident(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
+                                int accumulate, void* stream) {
+  const WavePlan wp = make_wave_plan(N, C, D, H, W, 1);
+  if (wp.ok) {
+    launch_wave(wp, dy, nullptr, nullptr, w, g_in, nullptr, N, C, D, 1, accumulate, nofold, (hipStream_t)stream);
+    MSL_LAUNCH_CHECK();
+    return MSL_OK;
+  }
+  DwPlan pl = make_plan(N, C, D, H, W, 1);
+  if (pl.variant != 2) return MSL_ERR_UNSUPPORTED;
+  const int nblocks = N * (C / pl.G) * pl.nslabs;
+  int e_ = set_lds(dw_fwd_resident_kernel<1, 0>, pl.lds_bytes);
+  if (e_) return e_;
+  MSL_LAUNCH((dw_fwd_resident_kernel<1, 0>), dim3(nblocks), dim3(256), pl.lds_bytes, (hipStream_t)stream, dy,
+                     nullptr, nullptr, w, g_in, nullptr, C, D, H, W, D, H, W, pl.G, pl.SLAB, pl.nslabs, N, 1, accumulate, nofold);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}

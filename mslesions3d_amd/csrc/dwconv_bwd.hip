@@ -486,11 +486,12 @@ __global__ __launch_bounds__(64) void dw_bwd_weight_finalize_kernel(const double
 
 }  // namespace
 
-extern "C" int msl_dwconv_bwd_weight_tiled(const float* dy, const float* x, const float* in_scale, const float* in_shift,
-                                           double* partials, int N, int C, int D, int H, int W, int stride, void* stream);
-extern "C" int msl_dwconv_bwd_weight_tiled_num_partials(int N, int C, int D, int H, int W, int stride);
-extern "C" int msl_dwconv_s1_bwd_data_resident(const float* dy, const float* w, float* g_in, int N, int C, int D, int H,
-                                               int W, int accumulate, void* stream);
+// dwconv.hip (library-internal)
+int dwconv_bwd_weight_tiled(const float* dy, const float* x, const float* in_scale, const float* in_shift, double* partials,
+                            int N, int C, int D, int H, int W, int stride, void* stream);
+int dwconv_bwd_weight_tiled_num_partials(int N, int C, int D, int H, int W, int stride);
+int dwconv_s1_bwd_data_resident(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W, int accumulate,
+                                void* stream);
 
 extern "C" {
 
@@ -501,7 +502,7 @@ int msl_dwconv_bwd_data(const float* dy, const float* w, float* g_in, int N, int
   const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
   if (stride == 1) {
-    const int rc = msl_dwconv_s1_bwd_data_resident(dy, w, g_in, N, C, D, H, W, accumulate, stream);
+    const int rc = dwconv_s1_bwd_data_resident(dy, w, g_in, N, C, D, H, W, accumulate, stream);
     if (rc != MSL_ERR_UNSUPPORTED) return rc;
   }
   if (W % 4 == 0) {
@@ -568,7 +569,7 @@ int msl_dwconv_bwd_data_s2_patch_bf16(const void* dy, const float* w, void* g_in
 }
 
 int msl_dwconv_bwd_weight_num_partials(int N, int C, int D, int H, int W, int stride) {
-  const int tiled = msl_dwconv_bwd_weight_tiled_num_partials(N, C, D, H, W, stride);
+  const int tiled = dwconv_bwd_weight_tiled_num_partials(N, C, D, H, W, stride);
   if (tiled > 0) return tiled;
   const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
   return N * msl::cdiv(OD * OH * OW, BW_CHUNK);
@@ -582,10 +583,10 @@ int msl_dwconv_bwd_weight(const float* dy, const float* x, const float* in_scale
   const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
   {
-    const int rc = msl_dwconv_bwd_weight_tiled(dy, x, in_scale, in_shift, partials, N, C, D, H, W, stride, stream);
+    const int rc = dwconv_bwd_weight_tiled(dy, x, in_scale, in_shift, partials, N, C, D, H, W, stride, stream);
     if (rc == MSL_OK) {
       if (!dw) return MSL_OK;
-      const int NPt = msl_dwconv_bwd_weight_tiled_num_partials(N, C, D, H, W, stride);
+      const int NPt = dwconv_bwd_weight_tiled_num_partials(N, C, D, H, W, stride);
       MSL_LAUNCH(dw_bwd_weight_finalize_kernel, dim3(C * 27), dim3(64), 0, st, partials, NPt, dw, C * 27);
       MSL_LAUNCH_CHECK();
       return MSL_OK;

@@ -143,7 +143,6 @@ __global__ __launch_bounds__(SDW_NT) void stem_dw_eval_kernel(const float* __res
   for (int pi = pi0; pi < nplanes; ++pi) {
     const int p = p_first + pi;
     // ---------------- MFMA phase
-#ifndef SDW_ABL_NO_MFMA
     // The BatchNorm + ReLU + LDS store of tile t ("epilogue": ~100 VALU / LDS instructions) is written BEHIND the MFMA chain of
     // tile t + 1, which does not depend on it: the scheduler interleaves the two, so the matrix pipe works through the
     // epilogues (ablation: MFMA chains alone 33 us, epilogues 25 us, back to back before this)
@@ -200,16 +199,13 @@ __global__ __launch_bounds__(SDW_NT) void stem_dw_eval_kernel(const float* __res
 #pragma unroll
       for (int e = 0; e < 16; ++e) epi1(a_prev, dst_prev, s4, t4, e);
     }
-#endif
     __syncthreads();  // the activation plane is complete, the input tile is consumed
-#ifndef SDW_ABL_NO_FETCH
     // the next plane's input tile (requested one plane step ago) goes to LDS, the one after it is requested - BEFORE the DW
     // phase's output stores: a vmcnt wait for loads then never waits for younger stores
     if (pi + 1 < nplanes) {
       stash();
       if (pi + 2 < nplanes) fetch(p + 2);
     }
-#endif
     // ---------------- DW phase.  p % 4 fixes the tap plane (kd) and the accumulator slot (output plane parity) of the one
     // or two output planes this activation plane feeds, so each case is straight-line code on fixed registers
     if (p >= 0) {
@@ -253,14 +249,12 @@ __global__ __launch_bounds__(SDW_NT) void stem_dw_eval_kernel(const float* __res
       typedef std::integral_constant<int, 0> I0;
       typedef std::integral_constant<int, 1> I1;
       typedef std::integral_constant<int, 2> I2;
-#ifndef SDW_ABL_NO_DW
       switch (p & 3) {  // block-uniform
         case 0: step(I1{}, I0{}, std::false_type{}); break;
         case 2: step(I1{}, I1{}, std::false_type{}); break;
         case 1: step(I2{}, I0{}, std::true_type{}); break;
         default: step(I2{}, I1{}, std::true_type{}); break;
       }
-#endif
     }
     __syncthreads();  // the activation plane is consumed, the next input tile is in place
   }

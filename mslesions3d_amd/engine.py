@@ -19,6 +19,12 @@ from . import _lib
 from ._lib import ptr
 
 BN_ROWS = 8  # scale, shift, mean, invstd, c1, c2, cC, cE (the last two: msl_bn_bwd_finalize_coef)
+# a depthwise output's only consumer is the pointwise GEMM of its block (one fold per wave, 32-64 channels wide): the
+# BatchNorm of a depthwise output is folded into it up to this many partials per channel (block 1's depthwise emits 64)
+FOLD_NP_MAX_PW = 64
+# a channel link (csrc/chanlink.hip) also produces the depthwise weight gradient while it has at most this many waves per
+# channel (with more it is bound by instruction issue; the stride-2 forms above 4 waves also spill)
+LINK_BWW_MAX_WAVES = 4
 
 
 def conv_out(d, s):
@@ -272,51 +278,18 @@ class Engine:
         # depthwise what the launch saves)
         self.fold_np_max = 512     # (65536 - the stem's 1024 partials too - gains another 2 us per step but costs the roofline
         #                             kernel, block 1's depthwise forward, 4.5 us: the launch stays)
-        self.fold_np_max_pw = 64   # block 1's depthwise layer emits 64 partials per channel: folded by its pointwise consumer
-        self.fold_bf16 = True     # the same for the bf16 step
         # bf16 path: head convolutions on the fp32 kernels from an fp32 feature copy ("f32": measured faster at every size
         # tried, and no second rounding of the head operands) or on the bf16 MFMA kernel from a channels-last bf16 copy
         # ("bf16", inference only)
         self.bf16_heads = "f32"
-        self.bf16_materialize_beside = True  # bf16 pass: a scale's fp32 feature copy on the heads stream with its head convolution
         # set by a caller (FusedTrainer) while it records a step whose heads stream it orders itself, every step, behind the
         # previous step's optimiser: the forward pass then has no "fwd_start" record at the head of the chain
         self.prologue_presynced = False
-        self.early_loss_fork = True  # fp32 backward: the heads stream is released by the loss launch itself (its stop event)
-        self.eval_multi_stream_bf16 = True  # bf16 inference: heads of the earlier scales on the heads stream, as in fp32
-        self.fold_bf16_feats = True  # bf16 pass: the feature maps' BatchNorms folded into the copy / the next depthwise layer too
-        # 0: every block's weight gradients on the wgrad stream; 1: odd blocks on the heads stream (idle once the head
-        # gradients are done); 2: three ways, the third on a stream of its own
-        self.split_wgrad = 1
-        self.wgrad_on_heads = None   # explicit set of blocks whose weight gradients go to the heads stream (probes)
-        # an event record costs the chain ~6 us: the weight gradients of several blocks can share one (a set of block indices)
-        # at the price of starting later - measured slower every time (the side streams are as critical as the chain)
-        self.wgrad_record_at = None
-        self.early_pw_bww = False    # start the pointwise weight gradient when dL/dy is final (one more record: slower)
-        # the weight gradients of block i are enqueued after the chain launches of block i - wgrad_lag (host order only)
-        self.wgrad_lag = 1
         # pointwise weight gradients of the tail blocks in ONE launch (single process only).  Paid while a fork cost the chain
         # 5-7 us; with stop-event forks (~1 us) four separate launches that start as their dL/dy arrive are 1.5 % faster
         self.batch_tail_pw = False
         self.batch_head_gpack = True  # head-gradient images of all scales in one launch
-        self.prologue_on_side = True  # NaN-flag reset + head weight packing on the heads stream instead of the chain
-        # the batched BatchNorm finalize (running statistics + backward vectors of the folded layers: nothing in the forward
-        # pass reads them) on the weight-gradient stream, forked behind the last pointwise convolution and joined at the end
-        # of the pass: beside the last head convolution instead of 9 us on the chain (a fork costs ~1 us since the stop events).
-        # True: the fp32 pass (-0.4 % same-box); "all": the bf16 pass too (+0.4 %: its list is short); False: on the chain
-        self.finalize_on_side = True
-        self.side_stream_priority = 0
         self.fuse_stem = True     # block-1 / stem backward without materialising dL/d(stem activation)
-        # eval mode: stem + block-1 depthwise convolution in one pass, the stem activation never in HBM (csrc/stemdw.hip)
-        self.fuse_stem_eval = True
-        self.channel_link = True  # per-channel backward links of the tail blocks in one launch each (csrc/chanlink.hip)
-        self.fuse_pw_bwd = True   # whole pointwise backward of the big early block in one pass (csrc/pwfused.hip)
-        self.fuse_dw_bww = True   # depthwise weight gradient of a big stride-2 block inside its bwd-data pass
-        # a channel link also produces the depthwise weight gradient while it has at most this many waves per channel (with
-        # more it is bound by instruction issue; the stride-2 forms above 4 waves also spill)
-        self.link_bww_max_waves = 4
-        self.link_bww_max_waves_s1 = 4
-        self.extra = {}
         self.side = {}
         self.arena = None
         self.plans = {}
@@ -357,17 +330,10 @@ class Engine:
         """(heads, wgrad) torch streams for ``device`` (created once)."""
         key = (device.type, device.index)
         if key not in self.side:
-            pr = self.side_stream_priority
             # (restricting the side streams to a CU subset with hipExtStreamCreateWithCUMask was measured 8-9 % slower for
             # every mask - half, quarter, three quarters of the chip - so they are ordinary streams)
-            self.side[key] = (torch.cuda.Stream(device=device, priority=pr), torch.cuda.Stream(device=device, priority=pr))
+            self.side[key] = (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device))
         return self.side[key]
-
-    def extra_stream(self, device):
-        key = (device.type, device.index)
-        if key not in self.extra:
-            self.extra[key] = torch.cuda.Stream(device=device, priority=self.side_stream_priority)
-        return self.extra[key]
 
     @staticmethod
     def _event(pl, name):
@@ -480,7 +446,7 @@ class Engine:
                 every += [(feats[i].bn1, pl.bn_z[i], pl.part_z[i], pl.np_z[i], 1.0),
                           (feats[i].bn2, pl.bn_y[i], pl.part_y[i], pl.np_y[i], 1.0)]
             self._finalize_all(pl, every, st, eval_mode=True)
-        if self.multi_stream and self.prologue_on_side:
+        if self.multi_stream:
             # the NaN-flag reset and the MFMA-fragment copies of the head weights are needed 200 us into the pass (first head
             # convolution) and at its end (loss / NaN checks): on the heads stream they cost the dependency chain nothing
             # (in front of the stem they were a memset + a launch + two dispatch gaps, ~20 us).  The heads stream first waits
@@ -496,9 +462,7 @@ class Engine:
 
         fold_max = (1 << 30) if self.fold_bn else self.fold_np_max
         folds = lambda NP: training and NP <= fold_max  # is the BatchNorm with NP partials folded into its consumers?
-        # a depthwise output's only consumer is the pointwise GEMM of its block (one fold per wave, 32-64 channels wide):
-        # a threshold of its own (MSL_FOLD_NP_MAX_PW; block 1's depthwise emits 64 partials)
-        fold_max_pw = (1 << 30) if self.fold_bn else self.fold_np_max_pw
+        fold_max_pw = (1 << 30) if self.fold_bn else FOLD_NP_MAX_PW  # (a depthwise output: its pointwise consumer folds it)
         folds_z = lambda NP: training and NP <= fold_max_pw
         deferred = []
         bn_layers = []  # (bn module, vector buffer, partials, NP, element count) of every BatchNorm, in order
@@ -591,7 +555,7 @@ class Engine:
                     deferred.append(lambda ev=ev, i=i, materialize=materialize: (self._wait(stH, ev), materialize(stH),
                                                                                self._head_forward(pl, i, stH)))
                 else:
-                    if last and bn_layers and self.multi_stream and self.finalize_on_side:
+                    if last and bn_layers and self.multi_stream:
                         ev_bn_done = self._finalize_all_beside(pl, bn_layers, st)
                     materialize(st)
                     if ev_pack is not None:  # this scale's convolution runs on the chain: the packed weights come from stH
@@ -741,13 +705,13 @@ class Engine:
         pl.saved_input, pl.trained_mode = x, training
         st = self._stream()
         # heads of the earlier scales beside the backbone: the training step, and inference too when the heads run on the fp32
-        # kernels (eval_multi_stream_bf16; the bf16 inference pass used to be one stream: 86 us of feature copies and head
-        # convolutions on the chain at 192^3 x 2)
-        ms = self.multi_stream and (need_grad or (self.eval_multi_stream_bf16 and pl.f32_heads))
+        # kernels (the bf16 inference pass used to be one stream: 86 us of feature copies and head convolutions on the chain
+        # at 192^3 x 2)
+        ms = self.multi_stream and (need_grad or pl.f32_heads)
         stH = self.side_streams(x.device)[0].cuda_stream if ms else st
         N = pl.N
         ncls = m.n_classes
-        side_prologue = ms and self.prologue_on_side and pl.f32_heads  # as in the fp32 forward: off the dependency chain
+        side_prologue = ms and pl.f32_heads  # as in the fp32 forward: off the dependency chain
         ev_pack = None
         if not training:  # first launch of the pass, in front of the prologue's fork (see the fp32 pass)
             every = [(feats[0][1], pl.bn_y[0], pl.part_y[0], 1, 1.0)]
@@ -768,7 +732,6 @@ class Engine:
         L = _lib.load()
         later = []  # BatchNorms folded into their consumer: running statistics + backward vectors in ONE launch at the end
         folded_feats = set()  # feature maps among them
-        ev_bn_done = None
         D, H, W = pl.in_dims
         stem_dw = self._stem_dw_eval(specs, training, N, D, H, W)
         if stem_dw:
@@ -790,7 +753,7 @@ class Engine:
             # the consumer rebuilds (scale, shift) from the producer's partials when they are few (<= fold_np_max: every wave /
             # workgroup repeats the sum) - no finalize launch between the two; feature maps need the vectors anyway
             # (a feature map whose fp32 copy was made from the partials - folded_feats - is folded here too)
-            fold_y = (training and self.fold_bf16 and pl.np_y[i - 1] <= max(64, self.fold_np_max)
+            fold_y = (training and pl.np_y[i - 1] <= max(64, self.fold_np_max)
                       and ((i - 1) not in pl.feat_ids or (i - 1) in folded_feats)
                       and L.msl_dwconv_wave_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]) > 0)
             if training and not fold_y and (i - 1) in folded_feats:  # the copy folded, this consumer cannot: finalize after all
@@ -809,7 +772,7 @@ class Engine:
             else:
                 self._k(f"dw_fwd{i}", "msl_dwconv_fwd_bf16", ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]), ptr(pl.bn_y[i - 1][1]),
                         ptr(blk.conv1.weight), ptr(pl.z[i]), part(pl.part_z[i]), N, sp["cin"], pd, ph, pw, sp["stride"][0], st)
-            fold_z = training and self.fold_bf16 and pl.np_z[i] <= 64 and sp["cin"] <= 1024
+            fold_z = training and pl.np_z[i] <= 64 and sp["cin"] <= 1024
             if fold_z:
                 later.append((blk.bn1, pl.bn_z[i], pl.part_z[i], pl.np_z[i], N * S))
                 self._k(f"pw_fwd{i}", "msl_pwconv_fwd_bf16_fold", ptr(pl.z[i]), ptr(pl.part_z[i]), pl.np_z[i], float(N * S),
@@ -822,12 +785,10 @@ class Engine:
                         ptr(blk.conv2.weight), ptr(pl.y[i]), part(pl.part_y[i]), N, sp["cin"], sp["cout"], S, st)
             if after_block and i in after_block:
                 after_block[i](None)
-            if training and later and ms and self.finalize_on_side == "all" and i == len(specs) - 1:
-                ev_bn_done = self._finalize_all_beside(pl, later, st)  # as in the fp32 pass (bf16: measured +0.4 %, so opt-in)
             # a feature map's BatchNorm: folded into the fp32 copy (and into the next depthwise layer) from the partials when
             # they are few - no finalize launch on the chain; else finalised here (the copy below reads the vectors)
-            fold_feat = (training and i in pl.feat_ids and pl.f32_heads and self.fold_bf16 and self.fold_bf16_feats
-                         and pl.np_y[i] <= max(64, self.fold_np_max) and not want_features)
+            fold_feat = (training and i in pl.feat_ids and pl.f32_heads and pl.np_y[i] <= max(64, self.fold_np_max)
+                         and not want_features)
             if fold_feat:
                 folded_feats.add(i)
                 later.append((blk.bn2, pl.bn_y[i], pl.part_y[i], pl.np_y[i], N * S))
@@ -837,7 +798,7 @@ class Engine:
                 # the fp32 zero-haloed copy only feeds this scale's head convolution: it goes to the heads stream with it
                 # (as in the fp32 pass; 6-8 us per scale off the chain) unless the caller wants the feature map back
                 beside = ms and i != len(specs) - 1
-                on_side = beside and not want_features and self.bf16_materialize_beside
+                on_side = beside and not want_features
                 if on_side:
                     self._fork(pl, f"fwd_feat{i}", st, stH)
                 if fold_feat:
@@ -870,9 +831,7 @@ class Engine:
                         ncls, st)
                 self._k(f"head_fwd{i}", "msl_head_conv_fwd_bf16", ptr(pl.fpad_cl[i]), ptr(pl.Wp[i]), ptr(lc.bias), ptr(cc.bias),
                         ptr(pl.locs), ptr(pl.scores), N, sp["cout"], D, H, W, pl.P, pl.prior_off[i], ncls, st)
-        if ev_bn_done is not None:
-            self._wait(st, ev_bn_done)
-        elif training and later:
+        if training and later:
             self._finalize_all(pl, later, st)
         if ms:
             self._fork(pl, "fwd_heads_done", stH, st)
@@ -929,7 +888,7 @@ class Engine:
             raise RuntimeError("the last backbone feature must feed a head")
         wanted = getattr(on_bucket_ready, "stages", None)
         groups = self._bucket_groups(on_bucket_ready) if wanted else {}
-        report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, stW, ms)
+        report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, ms)
 
         def head(f, s_data, s_weight, done=None):
             C = specs[f]["cout"]
@@ -955,7 +914,7 @@ class Engine:
         head(last, st, stW)  # its data gradient starts the chain
         for f in reversed(side_feats) if ms else [f for f in pl.feat_ids if f != last]:
             head(f, stH, stH, done=f"head_done{f}" if ms else None)
-        report("heads", join_heads=True)
+        report("heads")
         for i in range(last, 0, -1):
             sp = specs[i]
             D, H, W = pl.dims[i]
@@ -973,9 +932,9 @@ class Engine:
             fused_stem = i == 1 and pl.fused_stem_np > 0
             big_producer = s == 2 and pw % 4 == 0 and not self._bn_bwd_bf16_fused(N, Sp)
             # the per-channel link of the tail blocks in one launch, as in the fp32 step (csrc/chanlink.hip on bf16 storage)
-            link_nw = L.msl_block_bwd_channel_link_supported(N, pd, ph, pw, s) if self.channel_link else 0
+            link_nw = L.msl_block_bwd_channel_link_supported(N, pd, ph, pw, s)
             link = link_nw > 0 and not fused_stem and not big_producer and i >= 2
-            link_bww = link and (link_nw <= self.link_bww_max_waves or (s == 1 and link_nw <= self.link_bww_max_waves_s1))
+            link_bww = link and link_nw <= LINK_BWW_MAX_WAVES
             if not link:
                 self._bn_bwd_bf16(pl.g_z[i], pl.z[i], pl.bn_z[i], name + ".bn1", N, sp["cin"], S, pl, st)
             if accumulate and (i - 1) in side_feats:
@@ -1017,7 +976,7 @@ class Engine:
             if not fused_stem and not link_bww:  # (its partials came with the fused pass: pl.partials_wf / the link wrote dW)
                 self._k(f"dw_bww{i}", "msl_dwconv_bwd_weight_bf16", ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]),
                         ptr(pl.bn_y[i - 1][1]), ptr(pl.dw_part[i]), N, sp["cin"], pd, ph, pw, s, sX)
-            report(i, join_heads=True)  # (odd blocks put their weight gradients on the heads stream)
+            report(i)
         # stem: BatchNorm-backward sums, then the weight gradient with the BatchNorm backward applied on load
         od, oh, ow = pl.dims[0]
         S0 = od * oh * ow
@@ -1042,11 +1001,12 @@ class Engine:
             self._fork(pl, "bwd_join_h", stH, st)
         if not groups:  # single process: ONE reduction launch for every layer's partial sums, in front of the optimiser
             self._grad_reduce(pl, "all", None, st)
-        report(0)
+        report(0, join_heads=False)
 
     def _stem_dw_eval(self, specs, training, N, D, H, W):
-        """Eval mode: may the stem and block 1's depthwise convolution run as one launch (csrc/stemdw.hip)?"""
-        if training or not self.fuse_stem_eval or len(specs) < 2:
+        """Eval mode: may the stem and block 1's depthwise convolution run as one launch (csrc/stemdw.hip: the stem
+        activation never goes to HBM)?"""
+        if training or len(specs) < 2:
             return False
         if tuple(specs[0]["stride"]) != (2, 2, 2) or tuple(specs[1]["stride"]) != (2, 2, 2) or specs[0]["cout"] != 32:
             return False
@@ -1054,7 +1014,9 @@ class Engine:
 
     def _finalize_all_beside(self, pl, bn_layers, st):
         """_finalize_all on the weight-gradient stream, ordered behind what ``st`` holds so far (the last pointwise
-        convolution: every layer's partial sums exist) -> the event the chain waits for at the end of the pass."""
+        convolution: every layer's partial sums exist) -> the event the chain waits for at the end of the pass.
+        Nothing in the forward pass reads its outputs, so in the fp32 pass it runs beside the last head convolution
+        instead of 9 us on the chain (-0.4 %).  The bf16 pass keeps it on the chain: its list is short (+0.4 % beside)."""
         stW = self.side_streams(pl.locs.device)[1].cuda_stream
         self._fork(pl, "fwd_bn_parts", st, stW)
         self._finalize_all(pl, bn_layers, stW)
@@ -1208,13 +1170,14 @@ class Engine:
         self._k(f"head_bww{f}", "msl_head_conv_bwd_weight", ptr(pl.dO[f]), ptr(pl.fpad[f]), None, None, None, None,
                 ptr(pl.head_ws[f]), pl.N, C, D, H, W, ncls, st)
 
-    def _reporter(self, pl, on_bucket_ready, groups, st, stH, stW, stX, ms):
-        """-> report(stage, join_heads=False): tell the data-parallel reducer that every launch producing the gradients of
+    def _reporter(self, pl, on_bucket_ready, groups, st, stH, stW, ms):
+        """-> report(stage, join_heads=True): tell the data-parallel reducer that every launch producing the gradients of
         ``stage`` ('heads', 7, ..., 0) has been enqueued - after making the stream the exchange will run on wait for the
-        streams that produced them and folding the stage's partial sums there."""
+        streams that produced them (the heads stream too, which carries the head gradients and the odd blocks' weight
+        gradients) and folding the stage's partial sums there."""
         wanted = getattr(on_bucket_ready, "stages", None)
 
-        def report(stage, join_heads=False):
+        def report(stage, join_heads=True):
             if on_bucket_ready is None or (wanted is not None and stage not in wanted):
                 return
             comm = getattr(on_bucket_ready, "comm_stream", None)
@@ -1234,14 +1197,10 @@ class Engine:
                         self._fork(pl, f"bucket_w{stage}", stW, dst)
                     if join_heads and dst != stH:
                         self._fork(pl, f"bucket_h{stage}", stH, dst)
-                    if stX != stW and dst != stX:
-                        self._fork(pl, f"bucket_x{stage}", stX, dst)
             elif ms:  # the exchange follows the main stream: bring the side streams' work in first
                 self._fork(pl, f"bucket_w{stage}", stW, st)
                 if join_heads:
                     self._fork(pl, f"bucket_h{stage}", stH, st)
-                if stX != stW:
-                    self._fork(pl, f"bucket_x{stage}", stX, st)
             if stage in groups:  # fold the partial sums of this stage's buckets where their exchange will run
                 comm2 = getattr(on_bucket_ready, "comm_stream", None)
                 on_main = comm2 is None or (stage == 0 and getattr(on_bucket_ready, "final_on_main", False))
@@ -1280,9 +1239,8 @@ class Engine:
         if ms:
             sH, sW = self.side_streams(pl.locs.device)
             stH, stW = sH.cuda_stream, sW.cuda_stream
-            stX = self.extra_stream(pl.locs.device).cuda_stream if self.split_wgrad > 1 else stW
         else:
-            stH = stW = stX = st
+            stH = stW = st
         N = pl.N
         specs = self.layer_specs
         feats = m.base.features
@@ -1295,7 +1253,7 @@ class Engine:
         # (stage -> parameter names); single process: one reduction at the very end
         groups = self._bucket_groups(on_bucket_ready) if wanted else {}
 
-        report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, stX, ms)
+        report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, ms)
 
         # heads: the last scale feeds the chain immediately (main stream); the earlier scales are only needed when
         # the chain reaches their feature map, so they run on the heads stream beside blocks 7..4
@@ -1308,7 +1266,7 @@ class Engine:
         pre_np = None  # set when the producer of the next activation gradient also produced its BatchNorm partials
         linked = False  # set when a channel link already applied the BatchNorm backward of the next layer's output gradient
         pending = []  # side-stream launches, issued one layer late so that the chain's launches always go first
-        sinks = []    # (layer, closure) of the weight-gradient launches still to be issued
+        sinks = []    # (closure, event) of the weight-gradient launches still to be issued
         tail = []     # blocks whose pointwise weight gradients share one launch (deepest first), and their arguments
         if ms and not groups and self.batch_tail_pw:
             for i in range(last, 0, -1):
@@ -1317,32 +1275,28 @@ class Engine:
                     tail.append(i)
             tail = tail[:4] if len(tail) >= 2 else []
         tail_args = []
-        ev_loss = None
-        if side_feats and self.early_loss_fork:
+        if side_feats:
             # the earlier scales' gradients (heads stream) need the head-gradient images - written by the launch in front
             # of this point (the loss kernel, or the batched pack), whose stop event this record becomes: no packet on the
-            # chain, and the heads stream starts one launch earlier than behind the chain's own head bwd-data
+            # chain, and the heads stream starts one launch earlier than behind the chain's own head bwd-data (which was
+            # measured 1-2 % slower: the heads stream's gradients are as critical as the chain here)
             self._fork(pl, "bwd_loss_ready", st, stH)
         for f in pl.feat_ids:  # the chain's own scale first: its data gradient starts the backward chain
             if f not in side_feats:
                 if ms:
                     self._head_backward(pl, f, dlocs, dscores, st, weight=False, packed=packed)
-                    ev = ev_loss = self._record(pl, f"head_dO{f}", st)
+                    ev = self._record(pl, f"head_dO{f}", st)
                     pending.append(lambda f=f, ev=ev: (self._wait(stW, ev),
                                                        self._head_backward(pl, f, dlocs, dscores, stW, data=False)))
                 else:
                     self._head_backward(pl, f, dlocs, dscores, st, packed=packed)
-        if side_feats and not self.early_loss_fork:
-            # (sharing the record behind the chain's own head bwd-data instead - one launch later, one record fewer - was
-            # measured 1-2 % SLOWER: the heads stream's gradients are as critical as the chain here)
-            self._fork(pl, "bwd_loss_ready", st, stH)
         for f in reversed(side_feats):  # the deeper scale is needed first
             pending.append(lambda f=f: self._head_backward(pl, f, dlocs, dscores, stH, self._event(pl, f"head_done{f}"), packed=packed))
         if wanted is not None and "heads" in wanted:
             for fn in pending:
                 fn()
             pending = []
-        report("heads", join_heads=True)
+        report("heads")
         for i in range(last, 0, -1):
             sp = specs[i]
             D, H, W = pl.dims[i]
@@ -1358,7 +1312,7 @@ class Engine:
             # ~10 us kernels, so any launch queued in front of its next link shows up as idle time.
             # big early block whose producer left the BatchNorm2-backward sums: BatchNorm backward of y_i (applied on load),
             # bwd-data GEMM, BatchNorm1-backward sums of z_i and the pointwise weight gradient in ONE pass (csrc/pwfused.hip)
-            pw_fused = (self.fuse_pw_bwd and not linked and pre_np is not None and i in pl.pw_fused
+            pw_fused = (not linked and pre_np is not None and i in pl.pw_fused
                         and 2 * sp["cout"] * pre_np <= pl.partials.numel())
             z_np = None
             if pw_fused:
@@ -1371,9 +1325,6 @@ class Engine:
             elif not linked:  # (a channel link of block i+1 has already turned g_y[i] into dL/dy_i)
                 self._bn_bwd(pl.g_y[i], pl.y[i], pl.bn_y[i], name + ".bn2", N * S, N, sp["cout"], S, pl, st, pre_np=pre_np)
             pre_np, linked = None, False
-            # dL/dy_i is final here: the pointwise weight gradient may start two or three chain kernels before dL/dz_i is
-            rec_here = self.wgrad_record_at is None or i in self.wgrad_record_at or i == 1
-            ev_dy = self._record(pl, f"dy{i}", st) if ms and self.early_pw_bww and rec_here and not pw_fused else None
             if not pw_fused:
                 self._k(f"pw_bwd{i}", "msl_pwconv_bwd_data", ptr(pl.g_y[i]), ptr(feats[i].conv2.weight), ptr(pl.g_z[i]), N,
                         sp["cin"], sp["cout"], S, st)
@@ -1383,22 +1334,21 @@ class Engine:
             fused_stem = i == 1 and self.fuse_stem and pl.fused_stem_np > 0
             # tail of the network: BatchNorm1 backward of z_i, depthwise bwd-data (+ the heads' share) and BatchNorm2 backward
             # of y_{i-1} are all per channel and a channel's population fits one workgroup: ONE launch (csrc/chanlink.hip)
-            link_nw = L.msl_block_bwd_channel_link_supported(N, pd, ph, pw, s) if self.channel_link else 0
+            link_nw = L.msl_block_bwd_channel_link_supported(N, pd, ph, pw, s)
             link = link_nw > 0 and not fused_stem and np_red <= 0 and not pw_fused
-            # (with <= 4 waves per channel the link takes the depthwise weight gradient along: no launch for it below)
-            link_bww = link and (link_nw <= self.link_bww_max_waves or (s == 1 and link_nw <= self.link_bww_max_waves_s1))
+            # (with few waves per channel the link takes the depthwise weight gradient along: no launch for it below)
+            link_bww = link and link_nw <= LINK_BWW_MAX_WAVES
             # a block whose pointwise weight gradient rides in the tail's batched launch (issued with the shallowest of them) and
             # whose depthwise weight gradient the link produces has nothing waiting for dL/dz_i: no event record on the chain
             idle_sink = (link_bww and i in tail and i != tail[-1]) or (pw_fused and fused_stem)
-            rec_here = rec_here and not idle_sink
+            rec_here = ms and not idle_sink
             if not link:
                 self._bn_bwd(pl.g_z[i], pl.z[i], pl.bn_z[i], name + ".bn1", N * S, N, sp["cin"], S, pl, st, pre_np=z_np,
                              partials=pl.pw_fused[i][1] if pw_fused else None)
-                ev_dz = self._record(pl, f"dz{i}", st) if ms and rec_here else None
+                ev_dz = self._record(pl, f"dz{i}", st) if rec_here else None
             if accumulate and (i - 1) in side_feats:
                 self._wait(st, pl.events[f"head_done{i - 1}"])
             # big producer layers: emit the BatchNorm-backward partials of y_{i-1} while its gradient is in registers
-            ev_red = None
             dw_fused = False
             if link:
                 prev = "base.features.0.1" if i == 1 else f"base.features.{i - 1}.bn2"
@@ -1409,7 +1359,7 @@ class Engine:
                         pw, s, accumulate, st)
                 if link_bww:
                     pl.dw_in_link.add(i)
-                ev_dz = self._record(pl, f"dz{i}", st) if ms and rec_here else None
+                ev_dz = self._record(pl, f"dz{i}", st) if rec_here else None
                 linked = True
             elif fused_stem:
                 # one pass over (dL/dz_1, y_0): BatchNorm-backward sums of the stem + the depthwise weight gradient;
@@ -1419,7 +1369,7 @@ class Engine:
                         ptr(vp[0]), ptr(vp[1]), ptr(vp[2]), ptr(vp[3]), ptr(pl.partials), ptr(pl.partials_wf), ptr(pl.w1_taps_t),
                         N, 32, pd, ph, pw, st)
                 pre_np = pl.fused_stem_np
-            elif np_red > 0 and self.fuse_dw_bww and i in pl.dw_fused_part:
+            elif np_red > 0 and i in pl.dw_fused_part:
                 # big stride-2 producer layer: bwd-data, the BatchNorm-backward sums of y_{i-1} AND this block's depthwise
                 # weight gradient in one pass over (dL/dz_i, y_{i-1}) - the weight-gradient launch on the side stream (the same
                 # 38 MB read again, 35 us beside the chain at block 2) disappears
@@ -1441,15 +1391,11 @@ class Engine:
                 self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight), ptr(pl.g_y[i - 1]),
                         N, sp["cin"], pd, ph, pw, s, accumulate, st)
             def wgrads(ev_dz, i=i, sp=sp, S=S, pd=pd, ph=ph, pw=pw, s=s, name=name,
-                       fused_stem=fused_stem or link_bww or dw_fused, ev_red=ev_red, ev_dy=ev_dy, idle_sink=idle_sink,
-                       pw_fused=pw_fused):
-                # split_wgrad: the heads stream is idle once the head gradients are done - odd blocks go there
-                streams = [stW, stH, stX]
-                sX = streams[i % (self.split_wgrad + 1)] if ms else st
-                if ms and self.wgrad_on_heads is not None:  # experiment knob: explicit list of blocks for the heads stream
-                    sX = stH if i in self.wgrad_on_heads else stW
-                if ms and not idle_sink:  # the pointwise gradient needs dL/dy_i, the depthwise one dL/dz_i
-                    self._wait(sX, ev_dy if ev_dy is not None else ev_dz)
+                       fused_stem=fused_stem or link_bww or dw_fused, idle_sink=idle_sink, pw_fused=pw_fused):
+                # the heads stream is idle once the head gradients are done: odd blocks go there, even ones to the wgrad stream
+                sX = (stH if i % 2 else stW) if ms else st
+                if ms and not idle_sink:  # the pointwise gradient needs dL/dy_i, the depthwise one dL/dz_i (final later)
+                    self._wait(sX, ev_dz)
                 # partial sums only: slabs / fp64 partials stay in this layer's own buffers until Engine._grad_reduce
                 out = pl.pw_slabs[i] if pl.pw_nslabs[i] > 1 else gv[name + ".conv2.weight"]
                 if pw_fused:
@@ -1462,36 +1408,27 @@ class Engine:
                 else:
                     self._k(f"pw_bww{i}", "msl_pwconv_bwd_weight_slabs", ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]),
                             ptr(pl.bn_z[i][1]), ptr(out), N, sp["cin"], sp["cout"], S, sX)
-                if ms and ev_dy is not None and not idle_sink:
-                    self._wait(sX, ev_dz)
                 if fused_stem:
                     return  # its partials came with the fused stem backward pass (pl.partials_wf) / the channel link wrote dW
                 self._k(f"dw_bww{i}", "msl_dwconv_bwd_weight", ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]),
                         ptr(pl.bn_y[i - 1][1]), None, ptr(pl.dw_part[i]), N, sp["cin"], pd, ph, pw, s, sX)
 
-            # issue what earlier layers left for the side streams (the head gradients the chain waits for: one layer late;
-            # the weight gradients, which nothing in the step waits for: wgrad_lag layers late), then queue this layer's
+            # issue what earlier layers left for the side streams (the head gradients the chain waits for and the weight
+            # gradients, which nothing in the step waits for: one layer late), then queue this layer's
             for fn in pending:
                 fn()
             pending = []
             if ms:
-                sinks.append([i, wgrads, ev_dz if not idle_sink else "none"])
-                if ev_dz is not None:  # blocks that did not record wait for the next record of the chain instead
-                    for ent in sinks:
-                        if ent[2] is None:
-                            ent[2] = ev_dz
-                while sinks and sinks[0][2] is not None and sinks[0][0] >= i + self.wgrad_lag:
-                    ent = sinks.pop(0)
-                    ent[1](ent[2])
+                for fn, e in sinks:
+                    fn(e)
+                sinks = [(wgrads, ev_dz)]
             else:
                 wgrads(None)
             if wanted is not None and i in wanted:
-                if any(e is None for _, _, e in sinks):
-                    raise RuntimeError("MSL_WGRAD_RECORD_AT must contain every block that completes a gradient bucket")
-                for _, fn, e in sinks:
+                for fn, e in sinks:
                     fn(e)
                 sinks = []
-            report(i, join_heads=self.split_wgrad > 0)
+            report(i)
         # stem
         od, oh, ow = pl.dims[0]
         S0 = od * oh * ow
@@ -1517,16 +1454,14 @@ class Engine:
                     None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, sd, sh, sw, st)
         for fn in pending:
             fn()
-        for _, fn, e in sinks:
+        for fn, e in sinks:
             fn(e)
         if ms:  # every gradient is complete once the side streams have been joined
             self._fork(pl, "bwd_join_w", stW, st)
             self._fork(pl, "bwd_join_h", stH, st)
-            if stX != stW:
-                self._fork(pl, "bwd_join_x", stX, st)
         if not groups:  # single process: ONE reduction launch for every layer's partial sums, right in front of the optimiser
             self._grad_reduce(pl, "all", None, st)
-        report(0)
+        report(0, join_heads=False)
 
     def _bucket_groups(self, reducer):
         """stage -> set of parameter names whose gradient bucket completes at that stage (GradBucketReducer layout)."""

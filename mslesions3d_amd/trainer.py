@@ -80,9 +80,6 @@ class FusedTrainer:
         # block after which the target matching is enqueued (a block that forks the heads stream anyway shares its event;
         # A/B after block 4 / 5 at the end of round 3: equal within noise)
         self.match_after = 4
-        # which stream carries the overlapped gradient collectives: "heads" | "wgrad" | "own" (see _reducer)
-        self.dp_comm_stream = "heads"
-        self.main_stream_priority = -1  # the dependency chain must not queue behind the side streams' bulk work
         # training metrics (step(..., metrics=True)): IoU thresholds of the reference's two calculate_mAP calls
         # (ssd3d.py:505-506) and the device state of the metric launches (own detection workspace: predict rebinds the eval
         # plan's NaN flag into the model's workspace)
@@ -94,15 +91,13 @@ class FusedTrainer:
     def _reducer(self, arena):
         if self.reducer is None or self.reducer.arena is not arena:
             self.reducer = GradBucketReducer(arena, self.n_buckets, self.group)
-            # which stream carries the overlapped collectives (self.dp_comm_stream = heads | wgrad | own).  A fifth HIP stream
-            # per process is not free on this runtime: in the one-rank rehearsal a stream of their own costs 3.9 % of the
-            # step, the wgrad stream 3.0 %, the heads stream 0.7 % (it is idle between the head gradients and the odd
-            # blocks' weight gradients, and a bucket has to wait for that stream's work anyway)
-            which = self.dp_comm_stream
+            # the overlapped collectives run on the heads stream.  A fifth HIP stream per process is not free on this runtime:
+            # in the one-rank rehearsal a stream of their own costs 3.9 % of the step, the wgrad stream 3.0 %, the heads
+            # stream 0.7 % (it is idle between the head gradients and the odd blocks' weight gradients, and a bucket has to
+            # wait for that stream's work anyway)
             eng = self.model._engine
-            if self.reducer.comm_stream is not None and eng.multi_stream and which in ("heads", "wgrad"):
-                sH, sW = eng.side_streams(arena.grad.device)
-                self.reducer.comm_stream = sH if which == "heads" else sW
+            if self.reducer.comm_stream is not None and eng.multi_stream:
+                self.reducer.comm_stream = eng.side_streams(arena.grad.device)[0]
         return self.reducer
 
     def _eager_step(self, images, gt_boxes, gt_labels, obj_off, total_objects, red):
@@ -147,7 +142,7 @@ class FusedTrainer:
         # The heads stream's prologue (NaN-flag reset, head-weight packing) has to follow the previous step's optimiser.  The
         # trainer orders it itself - here through torch, in every replayed step through the "step_done" event of the previous
         # step's program (see step_packed) - so the recorded forward pass carries no event record at the head of the chain
-        presync = self.presync_prologue and eng.multi_stream and eng.prologue_on_side
+        presync = self.presync_prologue and eng.multi_stream
         if presync:
             eng.side_streams(dev)[0].wait_stream(torch.cuda.current_stream(dev))
         eng.prologue_presynced = presync
@@ -178,7 +173,7 @@ class FusedTrainer:
             if red.active:
                 _lib.record_hook(red.finish, tag="hook:finish")
             self.opt.step(grad_scale=scale, gather_autograd_grads=False)
-        if eng.multi_stream and eng.prologue_on_side:
+        if eng.multi_stream:
             # "the optimiser has read its hyper-parameter vector": what the NEXT step's upload of that vector waits for.  Part
             # of the launch program (behind the Adam launch it is a stop event: no packet of its own), so that the next step
             # need not put a record at the head of the chain
@@ -251,7 +246,7 @@ class FusedTrainer:
         red = self._reducer(arena)
         if self._stream is None or self._stream.device != dev:
             # high priority: the dependency chain must not queue behind the bulk weight-gradient work of the side streams
-            self._stream = torch.cuda.Stream(device=dev, priority=self.main_stream_priority)
+            self._stream = torch.cuda.Stream(device=dev, priority=-1)
         caller = torch.cuda.current_stream(dev)
         unfenced = (not fence) and resident and not sync and self.use_programs  # decided for good once the program is known
         if not unfenced:
@@ -292,7 +287,7 @@ class FusedTrainer:
                 prog, pl, st = entry["prog"], entry["plan"], entry["state"]
                 pl.generation += 1
                 pl.saved_input, pl.trained_mode = images, True
-                if eng.multi_stream and eng.prologue_on_side:
+                if eng.multi_stream:
                     # the optimiser's hyper-parameter vector (this step's learning rate) is read by the last kernel of the
                     # step: copy it on the heads stream, which the chain joins before the optimiser anyway, instead of in
                     # front of the stem (the stream first waits for the previous step's optimiser, which still reads it)

@@ -425,6 +425,26 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
                             const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
                             size_t workspace_bytes, float* out, void* stream);
 
+/* ---- device-resident training data (csrc/datapipe.hip, devicedata.py): the host pipeline of datasets._Cases ----------
+ * msl_normalize_nonzero: NormalizeIntensity(nonzero=True) in place on n_volumes contiguous f32 volumes of `voxels` each:
+ * population mean / std of the non-zero voxels (f64, fixed order), std 0 -> 1, zeros stay zero, all-zero unchanged.
+ * msl_augment_resample: dst (N,D,H,W) f32 image / u8 mask from src volumes [0, n_src).  params (N,16) f64 per sample:
+ * source volume, source axis of output axes 0..2, reversal of output axes 0..2 (flip / rot90 as one signed axis
+ * permutation), affine on (1) / off (0), zoom 0..2, offset 0..2.  With the affine on, output voxel o samples the permuted
+ * volume at c = zoom*o + offset as scipy.ndimage.affine_transform(mode="reflect") does: order 1 (image), order 0 (mask).
+ * msl_seg_boxes: BoundingBoxesGeneratord "classes" mode (datasets.boxes_from_segmentation) on seg (N,D,H,W) u8: per image,
+ * classes 1..n_classes (<= 8), 6-connected components in scipy.ndimage.label order, inclusive extents / size, flat ones
+ * dropped -> boxes (capacity,6) f32, labels (capacity) i64, obj_off (N+1) i32 (msl_multibox_match's layout).  comp_cap
+ * bounds the components before the flat ones are dropped.  *overflow (device): 0, |1 more boxes than capacity, |2 more
+ * components than comp_cap; obj_off stays <= capacity.  workspace: _workspace_bytes(...) bytes (0 = unsupported). */
+int msl_normalize_nonzero(float* img, int n_volumes, long long voxels, void* stream);
+int msl_augment_resample(const float* src_img, const unsigned char* src_seg, int n_src, const double* params, int N,
+                         int D, int H, int W, float* dst_img, unsigned char* dst_seg, void* stream);
+size_t msl_seg_boxes_workspace_bytes(int N, int D, int H, int W, int n_classes, int comp_cap);
+int msl_seg_boxes(const unsigned char* seg, int N, int D, int H, int W, int n_classes, int capacity, int comp_cap,
+                  void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,
+                  int* overflow, void* stream);
+
 /* ---- optimiser + NaN guard : ssd3d.py:704-722, :258-261 ---------------------------------------------------- */
 /* hp (device, 8 floats): step_size(bias), step_size(other), sqrt(bias_correction2), beta1, beta2, eps,
  * weight_decay, gradient scale.  is_bias (n bytes): 1 for elements of '.bias' parameters (2*lr group). */

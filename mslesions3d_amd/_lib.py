@@ -131,6 +131,10 @@ _SIGNATURES = {
     "msl_detection_metrics": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P] + [_P] * 7 + [_P]),
     "msl_evaluate_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "msl_evaluate_detections": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _Z, _P, _P]),
+    "msl_normalize_nonzero": (_I, [_P, _I, _Q, _P]),
+    "msl_augment_resample": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "msl_seg_boxes_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "msl_seg_boxes": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "msl_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "msl_nan_flag": (_I, [_P, _Z, _P, _I, _P]),
     "msl_nan_flag2": (_I, [_P, _Z, _I, _P, _Z, _I, _P, _P]),

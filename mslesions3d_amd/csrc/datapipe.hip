@@ -1,0 +1,545 @@
+// Device-resident training data (mslesions3d_amd/devicedata.py): the per-sample host pipeline of datasets._Cases on the
+// GPU.  Host mirrors: datasets._Cases.__getitem__ (NormalizeIntensity(nonzero)), datasets._aug_flip / _aug_rotate90 /
+// _aug_affine (scipy.ndimage.affine_transform, mode "reflect") and datasets.boxes_from_segmentation (scipy.ndimage.label).
+//
+//   normalize : one workgroup per cached case, population mean / std of the non-zero voxels in f64 with a fixed
+//               combination order, then (x - mean) / std in f32 as the host writes it
+//   resample  : one launch per affine stage; the first also gathers the sample from the cache through its signed axis
+//               permutation (flip + rot90s).  Coordinates, reflection and weights follow scipy's NI_GeometricTransform
+//               for order 0 / 1 operation by operation in f64 (this file is built with -ffp-contract=off)
+//   boxes     : 6-connected components of every class by union-find (hook the larger root under the smaller: root =
+//               minimum linear index = the component's first voxel in C raster order = scipy's numbering), per-tile
+//               root counts, one scan into (image, class, tile) order, root ranks, integer min / max extents by
+//               atomics, then one workgroup drops flat components and writes the packed targets of msl_multibox_match.
+// Launch boundaries on one stream are the only hand-offs between workgroups, except the union-find links, which are
+// read with agent-scope atomic loads and written with atomicMin (the result does not depend on the order).
+#include "common.hpp"
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int DP_THREADS = 256;
+constexpr int NORM_THREADS = 1024;
+constexpr int CC_PER_THREAD = 16;
+constexpr int CC_TILE = DP_THREADS * CC_PER_THREAD;  // voxels per workgroup of the count / rank passes
+constexpr int CC_MAX_CLASSES = 8;
+constexpr int FIN_THREADS = 1024;
+constexpr int SCAN_THREADS = 1024;
+constexpr int BG = -1;  // background voxel in the link array; a root's rank r is stored as -(r + 2)
+constexpr int PARAM_STRIDE = 16;  // doubles per sample of msl_augment_resample
+
+// ---- normalize ------------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* red) {  // fixed tree order: run-to-run identical
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = NORM_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const T r = red[0];
+  __syncthreads();
+  return r;
+}
+
+__global__ __launch_bounds__(NORM_THREADS) void normalize_kernel(float* __restrict__ img, long long V) {
+  __shared__ double redd[NORM_THREADS];
+  __shared__ long long redi[NORM_THREADS];
+  float* x = img + (long long)blockIdx.x * V;
+  double s = 0.0;
+  long long c = 0;
+  for (long long i = threadIdx.x; i < V; i += NORM_THREADS) {
+    const float v = x[i];
+    if (v != 0.0f) {
+      s += (double)v;
+      ++c;
+    }
+  }
+  s = block_sum(s, redd);
+  c = block_sum(c, redi);
+  if (c == 0) return;  // all-zero volume: unchanged
+  const double mean = s / (double)c;
+  double q = 0.0;
+  for (long long i = threadIdx.x; i < V; i += NORM_THREADS) {
+    const float v = x[i];
+    if (v != 0.0f) {
+      const double d = (double)v - mean;
+      q += d * d;
+    }
+  }
+  q = block_sum(q, redd);
+  const float mean_f = (float)mean;
+  float std_f = (float)sqrt(q / (double)c);
+  if (std_f == 0.0f) std_f = 1.0f;
+  for (long long i = threadIdx.x; i < V; i += NORM_THREADS) {
+    const float v = x[i];
+    if (v != 0.0f) x[i] = __fdiv_rn(__fsub_rn(v, mean_f), std_f);
+  }
+}
+
+// ---- resample -------------------------------------------------------------------------------------------------------
+// scipy's map_coordinate for NI_EXTEND_REFLECT (half-sample symmetric)
+__device__ __forceinline__ double map_reflect(double in, int len) {
+  if (in < 0.0) {
+    if (len <= 1) return 0.0;
+    const long long sz2 = 2LL * len;
+    if (in < (double)-sz2) in = (double)(sz2 * (long long)(-in / (double)sz2)) + in;
+    in = (in < (double)-len) ? in + (double)sz2 : (in > -1e-15 ? 1e-15 : -in) - 1.0;
+  } else if (in > (double)(len - 1)) {
+    if (len <= 1) return 0.0;
+    const long long sz2 = 2LL * len;
+    in -= (double)(sz2 * (long long)(in / (double)sz2));
+    if (in >= (double)len) in = ((double)sz2 - in) - 1.0;
+  }
+  return in;
+}
+
+__device__ __forceinline__ int map_index(long long i, int len) {
+  return (i >= 0 && i < len) ? (int)i : (int)map_reflect((double)i, len);
+}
+
+// params (N, PARAM_STRIDE) f64 per sample: source volume, source axis of output axes 0..2, reversal of output axes
+// 0..2, affine on (1) / off (0), zoom 0..2, offset 0..2.  An output voxel q of the permutation reads source voxel s with
+// s[axis[a]] = rev[a] ? n_a - 1 - q[a] : q[a]; with the affine on, q is sampled at c_a = o_a * zoom_a + offset_a.
+__global__ __launch_bounds__(DP_THREADS) void resample_kernel(
+    const float* __restrict__ src_img, const unsigned char* __restrict__ src_seg, int n_src,
+    const double* __restrict__ params, int D, int H, int W, float* __restrict__ dst_img,
+    unsigned char* __restrict__ dst_seg) {
+  const long long V = (long long)D * H * W;
+  const long long o = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
+  if (o >= V) return;
+  const int n = blockIdx.y;
+  const double* p = params + (size_t)n * PARAM_STRIDE;
+  const int sv = (int)p[0];
+  float* di = dst_img + (long long)n * V + o;
+  unsigned char* ds = dst_seg + (long long)n * V + o;
+  if (sv < 0 || sv >= n_src) {  // rejected on the host; never read out of bounds
+    *di = 0.0f;
+    *ds = 0;
+    return;
+  }
+  const float* si = src_img + (long long)sv * V;
+  const unsigned char* ss = src_seg + (long long)sv * V;
+  const int dims[3] = {D, H, W};
+  const long long sstride[3] = {(long long)H * W, (long long)W, 1LL};
+  int ax[3], rev[3];
+  long long pst[3];  // source stride of output axis a (signed by the reversal) and its base
+  long long base = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ax[a] = (int)p[1 + a];
+    rev[a] = (int)p[4 + a];
+    pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
+    if (rev[a]) base += (long long)(dims[ax[a]] - 1) * sstride[ax[a]];
+  }
+  const int oc[3] = {(int)(o / ((long long)H * W)), (int)((o / W) % H), (int)(o % W)};
+  if (p[7] == 0.0) {
+    const long long s = base + oc[0] * pst[0] + oc[1] * pst[1] + oc[2] * pst[2];
+    *di = si[s];
+    *ds = ss[s];
+    return;
+  }
+  int i1[3][2], i0[3];
+  double w[3][2];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    double c = (double)oc[a] * p[8 + a];
+    c = c + p[11 + a];
+    const int len = dims[a];
+    const double cc = map_reflect(c, len);
+    const double fl = floor(cc);
+    const long long st = (long long)fl;
+    const double x = cc - fl;
+    w[a][0] = 1.0 - x;
+    w[a][1] = 1.0 - w[a][0];
+    i1[a][0] = map_index(st, len);
+    i1[a][1] = map_index(st + 1, len);
+    i0[a] = map_index((long long)floor(cc + 0.5), len);
+  }
+  double t = 0.0;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int d = 0; d < 2; ++d) {
+        const long long s = base + i1[0][a] * pst[0] + i1[1][b] * pst[1] + i1[2][d] * pst[2];
+        double coeff = (double)si[s];
+        coeff = coeff * w[0][a];
+        coeff = coeff * w[1][b];
+        coeff = coeff * w[2][d];
+        t = t + coeff;
+      }
+  *di = (float)t;
+  *ds = ss[base + i0[0] * pst[0] + i0[1] * pst[1] + i0[2] * pst[2]];
+}
+
+// ---- connected components -> boxes ----------------------------------------------------------------------------------
+__device__ __forceinline__ int ld_link(const int* L, int i) {
+  return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int find_root(const int* L, int x) {
+  int p = ld_link(L, x);
+  while (p != x) {
+    x = p;
+    p = ld_link(L, x);
+  }
+  return x;
+}
+
+__device__ void unite(int* L, int a, int b) {
+  for (;;) {
+    a = find_root(L, a);
+    b = find_root(L, b);
+    if (a == b) return;
+    if (a < b) {
+      const int old = atomicMin(L + b, a);
+      if (old == b) return;
+      b = old;
+    } else {
+      const int old = atomicMin(L + a, b);
+      if (old == a) return;
+      a = old;
+    }
+  }
+}
+
+__device__ __forceinline__ bool is_fg(unsigned v, int ncls) { return v >= 1u && v <= (unsigned)ncls; }
+
+// links, component records (min z, y, x = INT_MAX, max = -1, class), header
+__global__ __launch_bounds__(DP_THREADS) void cc_init_kernel(const unsigned char* __restrict__ seg, long long total,
+                                                             int ncls, int* __restrict__ L, int* __restrict__ comp,
+                                                             long long comp_words, int* __restrict__ hdr) {
+  const long long stride = (long long)gridDim.x * DP_THREADS;
+  for (long long i = (long long)blockIdx.x * DP_THREADS + threadIdx.x; i < total; i += stride)
+    L[i] = is_fg(seg[i], ncls) ? (int)i : BG;
+  for (long long i = (long long)blockIdx.x * DP_THREADS + threadIdx.x; i < comp_words; i += stride)
+    comp[i] = (i & 7) < 3 ? 0x7FFFFFFF : -1;
+  if (blockIdx.x == 0 && threadIdx.x < 4) hdr[threadIdx.x] = 0;
+}
+
+// grid (cdiv(V, 256), N): union with the -x, -y, -z neighbours of the same class
+__global__ __launch_bounds__(DP_THREADS) void cc_merge_kernel(const unsigned char* __restrict__ seg, int D, int H, int W,
+                                                              int ncls, int* __restrict__ L) {
+  const long long V = (long long)D * H * W;
+  const long long o = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
+  if (o >= V) return;
+  const long long i = (long long)blockIdx.y * V + o;
+  const unsigned v = seg[i];
+  if (!is_fg(v, ncls)) return;
+  const int x = (int)(o % W), y = (int)((o / W) % H), z = (int)(o / ((long long)H * W));
+  if (x > 0 && seg[i - 1] == v) unite(L, (int)i, (int)(i - 1));
+  if (y > 0 && seg[i - W] == v) unite(L, (int)i, (int)(i - W));
+  if (z > 0 && seg[i - (long long)H * W] == v) unite(L, (int)i, (int)(i - (long long)H * W));
+}
+
+// grid (ntile, N): roots per class in each tile -> cnt[(n * ncls + c - 1) * ntile + tile]
+__global__ __launch_bounds__(DP_THREADS) void cc_count_kernel(const unsigned char* __restrict__ seg,
+                                                              const int* __restrict__ L, long long V, int ncls,
+                                                              int ntile, int* __restrict__ cnt) {
+  __shared__ int sc[CC_MAX_CLASSES];
+  if (threadIdx.x < CC_MAX_CLASSES) sc[threadIdx.x] = 0;
+  __syncthreads();
+  const long long img = (long long)blockIdx.y * V;
+  const long long t0 = (long long)blockIdx.x * CC_TILE;
+  for (int k = threadIdx.x; k < CC_TILE; k += DP_THREADS) {
+    const long long o = t0 + k;
+    if (o < V && L[img + o] == (int)(img + o)) atomicAdd(&sc[seg[img + o] - 1], 1);  // integer: order-free
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ncls) cnt[((long long)blockIdx.y * ncls + threadIdx.x) * ntile + blockIdx.x] = sc[threadIdx.x];
+}
+
+__device__ __forceinline__ int block_excl_scan(int v, int* lds, int* total) {  // SCAN_THREADS == FIN_THREADS lanes
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += u;
+  }
+  if (lane == 63) lds[w] = inc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) {
+      const int s = lds[k];
+      lds[k] = run;
+      run += s;
+    }
+    lds[32] = run;
+  }
+  __syncthreads();
+  const int r = lds[w] + inc - v;
+  *total = lds[32];
+  __syncthreads();
+  return r;
+}
+
+// one workgroup: exclusive offsets of every (image, class, tile) count in that order; seg_off[s] = first rank of
+// segment s = n * ncls + c - 1, seg_off[N * ncls] = number of components
+__global__ __launch_bounds__(SCAN_THREADS) void cc_scan_kernel(const int* __restrict__ cnt, int nseg, int ntile,
+                                                               int* __restrict__ off, int* __restrict__ seg_off) {
+  __shared__ int lds[33];
+  const int n = nseg * ntile;
+  int carry = 0;
+  for (int b = 0; b < n; b += SCAN_THREADS) {
+    const int i = b + threadIdx.x;
+    const int v = i < n ? cnt[i] : 0;
+    int tot;
+    const int e = block_excl_scan(v, lds, &tot);
+    if (i < n) {
+      off[i] = carry + e;
+      if (i % ntile == 0) seg_off[i / ntile] = carry + e;
+    }
+    carry += tot;
+  }
+  if (threadIdx.x == 0) seg_off[nseg] = carry;
+}
+
+// grid (ntile, N): rank of every root (raster order within its (image, class) segment) into the link array; each
+// thread owns CC_PER_THREAD consecutive voxels of the tile
+__global__ __launch_bounds__(DP_THREADS) void cc_rank_kernel(const unsigned char* __restrict__ seg,
+                                                             int* __restrict__ L, long long V, int ncls, int ntile,
+                                                             const int* __restrict__ off, int comp_cap,
+                                                             int* __restrict__ comp, int* __restrict__ hdr) {
+  __shared__ int scan[CC_MAX_CLASSES][DP_THREADS + 1];
+  const long long img = (long long)blockIdx.y * V;
+  const long long o0 = (long long)blockIdx.x * CC_TILE + (long long)threadIdx.x * CC_PER_THREAD;
+  int mine[CC_MAX_CLASSES];
+#pragma unroll
+  for (int c = 0; c < CC_MAX_CLASSES; ++c) mine[c] = 0;
+  for (int k = 0; k < CC_PER_THREAD; ++k) {
+    const long long o = o0 + k;
+    if (o < V && L[img + o] == (int)(img + o)) {
+      const int c = seg[img + o] - 1;
+#pragma unroll
+      for (int q = 0; q < CC_MAX_CLASSES; ++q) mine[q] += (q == c);
+    }
+  }
+  for (int c = 0; c < ncls; ++c) scan[c][threadIdx.x + 1] = mine[c];
+  if (threadIdx.x < CC_MAX_CLASSES) scan[threadIdx.x][0] = 0;
+  __syncthreads();
+  if ((int)threadIdx.x < ncls) {  // serial prefix per class: 256 adds
+    int* row = scan[threadIdx.x];
+    for (int k = 1; k <= DP_THREADS; ++k) row[k] += row[k - 1];
+  }
+  __syncthreads();
+  int next[CC_MAX_CLASSES];
+  for (int c = 0; c < ncls; ++c)
+    next[c] = off[((long long)blockIdx.y * ncls + c) * ntile + blockIdx.x] + scan[c][threadIdx.x];
+  for (int k = 0; k < CC_PER_THREAD; ++k) {
+    const long long o = o0 + k;
+    if (o < V && L[img + o] == (int)(img + o)) {
+      const int c = seg[img + o] - 1;
+      int r = 0;
+      for (int q = 0; q < ncls; ++q)
+        if (q == c) r = next[q]++;
+      L[img + o] = -(r + 2);
+      if (r < comp_cap) comp[(long long)r * 8 + 6] = c + 1;
+      else atomicOr(&hdr[0], 2);
+    }
+  }
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+  return v;
+}
+
+// grid-stride over N * V: integer extents of every component (a wave whose voxels all lie in one component folds them
+// first: one set of atomics instead of 64)
+__global__ __launch_bounds__(DP_THREADS) void cc_box_kernel(const int* __restrict__ L, int N, int D, int H, int W,
+                                                            int comp_cap, int* __restrict__ comp) {
+  const long long V = (long long)D * H * W, total = (long long)N * V;
+  const long long stride = (long long)gridDim.x * DP_THREADS;
+  const long long start = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
+  const long long iters = (total + stride - 1) / stride;  // the same for every lane: the wave stays converged
+  for (long long it = 0; it < iters; ++it) {
+    const long long i = start + it * stride;
+    int r = -1, z = 0, y = 0, x = 0;
+    if (i < total) {
+      int p = L[i];
+      if (p != BG) {
+        long long q = i;
+        while (p >= 0) {
+          q = p;
+          p = L[q];
+        }
+        r = -p - 2;
+        if (r >= comp_cap) r = -1;
+        const long long o = i % V;
+        x = (int)(o % W);
+        y = (int)((o / W) % H);
+        z = (int)(o / ((long long)H * W));
+      }
+    }
+    const unsigned long long act = __ballot(r >= 0);
+    if (act == 0) continue;
+    const int r0 = __shfl(r, __ffsll((long long)act) - 1, 64);
+    if (__all(r < 0 || r == r0)) {
+      const bool a = r >= 0;
+      const int mz = wave_min(a ? z : 0x7FFFFFFF), my = wave_min(a ? y : 0x7FFFFFFF), mx = wave_min(a ? x : 0x7FFFFFFF);
+      const int Mz = wave_max(a ? z : -1), My = wave_max(a ? y : -1), Mx = wave_max(a ? x : -1);
+      if ((threadIdx.x & 63) == 0) {
+        int* b = comp + (long long)r0 * 8;
+        atomicMin(b + 0, mz); atomicMin(b + 1, my); atomicMin(b + 2, mx);
+        atomicMax(b + 3, Mz); atomicMax(b + 4, My); atomicMax(b + 5, Mx);
+      }
+    } else if (r >= 0) {
+      int* b = comp + (long long)r * 8;
+      atomicMin(b + 0, z); atomicMin(b + 1, y); atomicMin(b + 2, x);
+      atomicMax(b + 3, z); atomicMax(b + 4, y); atomicMax(b + 5, x);
+    }
+  }
+}
+
+// one workgroup: drop flat components, write kept ones in rank order as packed targets; obj_off from the segment starts
+__global__ __launch_bounds__(FIN_THREADS) void cc_final_kernel(const int* __restrict__ comp,
+                                                               const int* __restrict__ seg_off, int N, int ncls, int D,
+                                                               int H, int W, int comp_cap, int capacity,
+                                                               int* __restrict__ kept, float* __restrict__ boxes,
+                                                               long long* __restrict__ labels, int* __restrict__ obj_off,
+                                                               int* __restrict__ hdr, int* __restrict__ overflow) {
+  __shared__ int lds[33];
+  const int total = seg_off[N * ncls];
+  const int nc = total < comp_cap ? total : comp_cap;
+  const float size[3] = {(float)D, (float)H, (float)W};
+  int carry = 0;
+  for (int b = 0; b < nc; b += FIN_THREADS) {
+    const int k = b + threadIdx.x;
+    int keep = 0;
+    int e[7];
+    if (k < nc) {
+#pragma unroll
+      for (int j = 0; j < 7; ++j) e[j] = comp[(long long)k * 8 + j];
+      keep = e[3] > e[0] && e[4] > e[1] && e[5] > e[2];
+    }
+    int tot;
+    const int row = carry + block_excl_scan(keep, lds, &tot);
+    if (k < nc) {
+      kept[k] = row;
+      if (keep && row < capacity) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) boxes[(long long)row * 6 + j] = __fdiv_rn((float)e[j], size[j % 3]);
+        labels[row] = e[6];
+      }
+    }
+    carry += tot;
+  }
+  if (threadIdx.x == 0) kept[nc] = carry;
+  __syncthreads();
+  for (int n = threadIdx.x; n <= N; n += FIN_THREADS) {
+    int s = n < N ? seg_off[n * ncls] : total;
+    if (s > nc) s = nc;
+    const int v = kept[s];
+    obj_off[n] = v < capacity ? v : capacity;  // in bounds even on overflow (the flag says it happened)
+  }
+  if (threadIdx.x == 0) {
+    const int f = hdr[0] | (carry > capacity ? 1 : 0);
+    hdr[1] = carry;
+    *overflow = f;
+  }
+}
+
+struct CcPlan {
+  size_t links, cnt, off, seg_off, comp, kept, hdr, total;
+  int ntile;
+};
+
+CcPlan cc_plan(int N, int D, int H, int W, int ncls, int comp_cap) {
+  CcPlan p;
+  const long long V = (long long)D * H * W;
+  p.ntile = (int)((V + CC_TILE - 1) / CC_TILE);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  size_t at = 0;
+  p.links = at; at += up((size_t)N * V * 4);
+  p.cnt = at; at += up((size_t)N * ncls * p.ntile * 4);
+  p.off = at; at += up((size_t)N * ncls * p.ntile * 4);
+  p.seg_off = at; at += up(((size_t)N * ncls + 1) * 4);
+  p.comp = at; at += up((size_t)comp_cap * 8 * 4);
+  p.kept = at; at += up(((size_t)comp_cap + 1) * 4);
+  p.hdr = at; at += 256;
+  p.total = at;
+  return p;
+}
+
+bool cc_supported(int N, int D, int H, int W, int ncls, int comp_cap) {
+  return N > 0 && D > 0 && H > 0 && W > 0 && ncls >= 1 && ncls <= CC_MAX_CLASSES && comp_cap > 0 &&
+         (long long)N * D * H * W < 0x7FFFFFF0LL && (long long)comp_cap * 8 < 0x7FFFFFF0LL;
+}
+
+int grid_for(long long n) {
+  const long long g = (n + DP_THREADS - 1) / DP_THREADS;
+  return (int)(g < 2048 ? (g > 0 ? g : 1) : 2048);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msl_normalize_nonzero(float* img, int n_volumes, long long voxels, void* stream) {
+  if (!img || n_volumes < 0 || voxels <= 0) return MSL_ERR_ARG;
+  if (n_volumes == 0) return MSL_OK;
+  MSL_LAUNCH(normalize_kernel, dim3(n_volumes), dim3(NORM_THREADS), 0, (hipStream_t)stream, img, voxels);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int msl_augment_resample(const float* src_img, const unsigned char* src_seg, int n_src, const double* params, int N,
+                         int D, int H, int W, float* dst_img, unsigned char* dst_seg, void* stream) {
+  if (!src_img || !src_seg || !params || !dst_img || !dst_seg || N <= 0 || n_src <= 0 || D <= 0 || H <= 0 || W <= 0)
+    return MSL_ERR_ARG;
+  if (N > 65535 || (long long)D * H * W >= (1LL << 40)) return MSL_ERR_UNSUPPORTED;
+  const long long V = (long long)D * H * W;
+  MSL_LAUNCH(resample_kernel, dim3((unsigned)((V + DP_THREADS - 1) / DP_THREADS), N), dim3(DP_THREADS), 0,
+             (hipStream_t)stream, src_img, src_seg, n_src, params, D, H, W, dst_img, dst_seg);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+size_t msl_seg_boxes_workspace_bytes(int N, int D, int H, int W, int n_classes, int comp_cap) {
+  if (!cc_supported(N, D, H, W, n_classes, comp_cap)) return 0;
+  return cc_plan(N, D, H, W, n_classes, comp_cap).total;
+}
+
+int msl_seg_boxes(const unsigned char* seg, int N, int D, int H, int W, int n_classes, int capacity, int comp_cap,
+                  void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,
+                  int* overflow, void* stream) {
+  if (!seg || !workspace || !boxes || !labels || !obj_off || !overflow || capacity < 0) return MSL_ERR_ARG;
+  if (!cc_supported(N, D, H, W, n_classes, comp_cap) || N > 65535) return MSL_ERR_UNSUPPORTED;
+  const CcPlan p = cc_plan(N, D, H, W, n_classes, comp_cap);
+  if (workspace_bytes < p.total) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  int* L = (int*)(ws + p.links);
+  int* cnt = (int*)(ws + p.cnt);
+  int* off = (int*)(ws + p.off);
+  int* seg_off = (int*)(ws + p.seg_off);
+  int* comp = (int*)(ws + p.comp);
+  int* kept = (int*)(ws + p.kept);
+  int* hdr = (int*)(ws + p.hdr);
+  const long long V = (long long)D * H * W, total = (long long)N * V;
+  const unsigned vblocks = (unsigned)((V + DP_THREADS - 1) / DP_THREADS);
+  MSL_LAUNCH(cc_init_kernel, dim3(grid_for(total > (long long)comp_cap * 8 ? total : (long long)comp_cap * 8)),
+             dim3(DP_THREADS), 0, st, seg, total, n_classes, L, comp, (long long)comp_cap * 8, hdr);
+  MSL_LAUNCH(cc_merge_kernel, dim3(vblocks, N), dim3(DP_THREADS), 0, st, seg, D, H, W, n_classes, L);
+  MSL_LAUNCH(cc_count_kernel, dim3(p.ntile, N), dim3(DP_THREADS), 0, st, seg, (const int*)L, V, n_classes, p.ntile, cnt);
+  MSL_LAUNCH(cc_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, (const int*)cnt, N * n_classes, p.ntile, off, seg_off);
+  MSL_LAUNCH(cc_rank_kernel, dim3(p.ntile, N), dim3(DP_THREADS), 0, st, seg, L, V, n_classes, p.ntile,
+             (const int*)off, comp_cap, comp, hdr);
+  MSL_LAUNCH(cc_box_kernel, dim3(grid_for(total)), dim3(DP_THREADS), 0, st, (const int*)L, N, D, H, W, comp_cap, comp);
+  MSL_LAUNCH(cc_final_kernel, dim3(1), dim3(FIN_THREADS), 0, st, (const int*)comp, (const int*)seg_off, N, n_classes,
+             D, H, W, comp_cap, capacity, kept, boxes, labels, obj_off, hdr, overflow);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+}  // extern "C"

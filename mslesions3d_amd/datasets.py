@@ -64,18 +64,33 @@ def boxes_from_segmentation(seg, n_classes=1):
 # absent, so its random-number stream and its affine grid convention are NOT pinned (documented in DESIGN.md); the
 # transforms are drawn from ``np.random.RandomState(seed)``.
 
-def _aug_flip(img, seg, rs, spatial_axis=(0, 1, 2), prob=0.1):
+def _draw_flip(rs, spatial_axis=(0, 1, 2), prob=0.1):
+    """The random draws of ``_aug_flip`` -> flipped spatial axes, or None (no flip)."""
     if rs.rand() >= prob:
+        return None
+    return tuple((spatial_axis,) if np.isscalar(spatial_axis) else spatial_axis)
+
+
+def _aug_flip(img, seg, rs, spatial_axis=(0, 1, 2), prob=0.1):
+    ax = _draw_flip(rs, spatial_axis, prob)
+    if ax is None:
         return img, seg
-    ax = tuple(a + 1 for a in ((spatial_axis,) if np.isscalar(spatial_axis) else spatial_axis))
+    ax = tuple(a + 1 for a in ax)
     return np.flip(img, ax), np.flip(seg, ax)
 
 
-def _aug_rotate90(img, seg, rs, spatial_axes=(0, 1), prob=0.1, max_k=3):
+def _draw_rotate90(rs, spatial_axes=(0, 1), prob=0.1, max_k=3):
+    """The random draws of ``_aug_rotate90`` -> (k, spatial axes), or None."""
     if rs.rand() >= prob:
+        return None
+    return int(rs.randint(max_k)) + 1, tuple(spatial_axes)
+
+
+def _aug_rotate90(img, seg, rs, spatial_axes=(0, 1), prob=0.1, max_k=3):
+    d = _draw_rotate90(rs, spatial_axes, prob, max_k)
+    if d is None:
         return img, seg
-    k = int(rs.randint(max_k)) + 1
-    ax = tuple(a + 1 for a in spatial_axes)
+    k, ax = d[0], tuple(a + 1 for a in d[1])
     return np.rot90(img, k, ax), np.rot90(seg, k, ax)
 
 
@@ -88,17 +103,32 @@ def _rand_range(rs, rng, n=3):
     return out + [0.0] * (n - len(out))
 
 
+def _draw_affine(rs, mode=("bilinear", "nearest"), translate_range=None, scale_range=None, padding_mode="reflection",
+                 prob=0.1):
+    """The random draws of ``_aug_affine`` -> (zoom, shift) per spatial axis, or None."""
+    if rs.rand() >= prob:
+        return None
+    shift = _rand_range(rs, translate_range) if translate_range is not None else [0.0] * 3
+    zoom = [1.0 + v for v in _rand_range(rs, scale_range)] if scale_range is not None else [1.0] * 3
+    return zoom, shift
+
+
+def affine_offset(shape, zoom, shift):
+    """Output voxel o of ``_aug_affine`` samples input voxel diag(zoom) o + offset (f64, the host's arithmetic)."""
+    centre = (np.array(shape, dtype=np.float64) - 1) / 2
+    return centre - np.diag(zoom) @ centre + np.array(shift, dtype=np.float64)
+
+
 def _aug_affine(img, seg, rs, mode=("bilinear", "nearest"), translate_range=None, scale_range=None,
                 padding_mode="reflection", prob=0.1):
     from scipy.ndimage import affine_transform
-    if rs.rand() >= prob:
+    d = _draw_affine(rs, mode, translate_range, scale_range, padding_mode, prob)
+    if d is None:
         return img, seg
-    shift = _rand_range(rs, translate_range) if translate_range is not None else [0.0] * 3
-    zoom = [1.0 + v for v in _rand_range(rs, scale_range)] if scale_range is not None else [1.0] * 3
+    zoom, shift = d
     pad = {"reflection": "reflect", "border": "nearest", "zeros": "constant"}[padding_mode]
-    centre = (np.array(img.shape[1:], dtype=np.float64) - 1) / 2
     mat = np.diag(zoom)
-    off = centre - mat @ centre + np.array(shift, dtype=np.float64)  # output voxel o samples input voxel M o + off
+    off = affine_offset(img.shape[1:], zoom, shift)  # output voxel o samples input voxel M o + off
     outs = []
     for a, m in ((img, mode[0]), (seg, mode[1])):
         order = 1 if m == "bilinear" else 0
@@ -107,6 +137,16 @@ def _aug_affine(img, seg, rs, mode=("bilinear", "nearest"), translate_range=None
 
 
 AUGMENTATIONS = {"flip": _aug_flip, "rotate90": _aug_rotate90, "affine": _aug_affine}
+DRAWS = {"flip": _draw_flip, "rotate90": _draw_rotate90, "affine": _draw_affine}
+
+
+def draw_augmentations(augmentations, rs):
+    """The draws the host transforms make for one sample, in their call order: [(name, draw or None), ...]."""
+    out = []
+    for t in augmentations:
+        name, kw = (t, {}) if isinstance(t, str) else t
+        out.append((name, DRAWS[name](rs, **kw)))
+    return out
 
 # train.py:132-143: the names the CLI accepts and the parameters the reference binds to them
 REFERENCE_AUGMENTATIONS = [("flip", {"spatial_axis": (0, 1, 2), "prob": .5}),
@@ -165,6 +205,11 @@ class ShardSampler(Sampler):
         return -(-self.n // self.world) if self.n else 0
 
 
+def sample_rng(seed, epoch, subject):
+    """The augmentation generator of one sample: a function of (seed, epoch, subject) alone."""
+    return np.random.RandomState(zlib.crc32(f"{seed}:{epoch}:{subject}".encode()) & 0x7FFFFFFF)
+
+
 class _Cases(Dataset):
     def __init__(self, root, subjects, n_classes, augmentations=None, seed=0):
         self.root, self.subjects, self.n_classes = root, subjects, n_classes
@@ -180,8 +225,7 @@ class _Cases(Dataset):
         self.epoch = int(epoch)
 
     def sample_rng(self, i):
-        key = f"{self.seed}:{self.epoch}:{self.subjects[i]}".encode()
-        return np.random.RandomState(zlib.crc32(key) & 0x7FFFFFFF)
+        return sample_rng(self.seed, self.epoch, self.subjects[i])
 
     def __len__(self):
         return len(self.subjects)

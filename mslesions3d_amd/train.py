@@ -55,6 +55,9 @@ def build_parser():
     p.add_argument('--focal_loss', action='store_true')
     # build-side extension (the reference trains in fp32): activations and activation gradients stored as bf16
     p.add_argument('--dtype', choices=["f32", "bf16"], default="f32")
+    # train.py:51 of the reference (MONAI CacheDataset): 1 = cases normalised once into HBM, every batch augmented and
+    # labelled into boxes on the device (devicedata.DeviceCache)
+    p.add_argument('-c', '--cache', type=int, default=0)
     return p
 
 
@@ -129,6 +132,12 @@ def example(args):
         model._engine.ensure_arena(dev)
         broadcast_model(model)
     trainer = FusedTrainer(model)
+    cache = None
+    if args.cache:
+        from .devicedata import DeviceCache
+        cache = DeviceCache(dataset, dev)
+        if rank == 0:
+            print(cache.footprint())
     first_epoch = 0
     best, bad_epochs = [], 0
     if args.checkpoint:
@@ -162,8 +171,11 @@ def example(args):
         dataset.set_epoch(epoch)
         # training metrics (ssd3d.py:497-515): detection + mAP on every step's own forward outputs, on the device
         train_metrics = epoch % (2 * max(int(model.compute_metric_every_n_epochs), 1)) == 0
-        for batch in dataset.train_dataloader():
-            out = trainer.step(batch["img"].to(dev), batch["boxes"], batch["labels"], metrics=train_metrics)
+        for batch in (cache.train_batches(epoch) if cache else dataset.train_dataloader()):
+            if cache:
+                out = cache.step(trainer, batch, metrics=train_metrics)
+            else:
+                out = trainer.step(batch["img"].to(dev), batch["boxes"], batch["labels"], metrics=train_metrics)
             if shard_log is not None:
                 shard_log.write(json.dumps({"step": model.global_step, "epoch": epoch, "subjects": list(batch["subject"]),
                                             "total_loss/training": out["loss"]}) + "\n")
@@ -191,7 +203,7 @@ def example(args):
             if rank == 0:
                 log.write(json.dumps(mrec) + "\n")
         model.eval()
-        vals = [model.validation_step(b, i) for i, b in enumerate(dataset.test_dataloader())]
+        vals = [model.validation_step(b, i) for i, b in enumerate(cache.val_batches() if cache else dataset.test_dataloader())]
         keys = ("val_total_loss", "val_conf_loss", "val_loc_loss")
         sums = [float(sum(float(v["log"][k]) for v in vals)) for k in keys]
         # (decided from the epoch, not from this rank's batches: every rank must contribute a vector of the same length)

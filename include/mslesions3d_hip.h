@@ -432,6 +432,15 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
  * source volume, source axis of output axes 0..2, reversal of output axes 0..2 (flip / rot90 as one signed axis
  * permutation), affine on (1) / off (0), zoom 0..2, offset 0..2.  With the affine on, output voxel o samples the permuted
  * volume at c = zoom*o + offset as scipy.ndimage.affine_transform(mode="reflect") does: order 1 (image), order 0 (mask).
+ * msl_augment_affine: the same with a dense matrix, a boundary mode and intensity arithmetic (datasets._aug_affine with a
+ * rotate_range, _aug_shiftintensity, _aug_scaleintensity).  params (N,32) f64 per sample: [0] source volume, [1..3] source
+ * axis of output axes 0..2, [4..6] reversal of output axes 0..2, [7] affine on (1) / off (0), [8..16] matrix M row-major,
+ * [17..19] offset, both as the host computed them in f64, [20] boundary: 0 reflect, 1 nearest ("border"), 2 constant 0
+ * ("zeros"), [21] number of intensity operations (<= 4), [22+2k] kind: 1 add, 2 multiply, [23+2k] its f32 operand,
+ * [30..31] unused.  With the affine on, output voxel o samples the permuted volume at M o + offset as
+ * scipy.ndimage.affine_transform does (order 1 image, order 0 mask; bit-identical for the three boundaries); the
+ * operations then apply to the image value in list order, one rounded f32 operation each.  Affine off: a permuted copy
+ * with that arithmetic.  A row whose source volume or axes are invalid writes zeros.
  * msl_seg_boxes: BoundingBoxesGeneratord "classes" mode (datasets.boxes_from_segmentation) on seg (N,D,H,W) u8: per image,
  * classes 1..n_classes (<= 8), 6-connected components in scipy.ndimage.label order, inclusive extents / size, flat ones
  * dropped -> boxes (capacity,6) f32, labels (capacity) i64, obj_off (N+1) i32 (msl_multibox_match's layout).  comp_cap
@@ -440,6 +449,8 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
 int msl_normalize_nonzero(float* img, int n_volumes, long long voxels, void* stream);
 int msl_augment_resample(const float* src_img, const unsigned char* src_seg, int n_src, const double* params, int N,
                          int D, int H, int W, float* dst_img, unsigned char* dst_seg, void* stream);
+int msl_augment_affine(const float* src_img, const unsigned char* src_seg, int n_src, const double* params, int N,
+                       int D, int H, int W, float* dst_img, unsigned char* dst_seg, void* stream);
 size_t msl_seg_boxes_workspace_bytes(int N, int D, int H, int W, int n_classes, int comp_cap);
 int msl_seg_boxes(const unsigned char* seg, int N, int D, int H, int W, int n_classes, int capacity, int comp_cap,
                   void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,

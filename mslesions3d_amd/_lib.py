@@ -133,6 +133,7 @@ _SIGNATURES = {
     "msl_evaluate_detections": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _Z, _P, _P]),
     "msl_normalize_nonzero": (_I, [_P, _I, _Q, _P]),
     "msl_augment_resample": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "msl_augment_affine": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_seg_boxes_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "msl_seg_boxes": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "msl_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),

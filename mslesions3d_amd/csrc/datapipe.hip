@@ -7,6 +7,9 @@
 //   resample  : one launch per affine stage; the first also gathers the sample from the cache through its signed axis
 //               permutation (flip + rot90s).  Coordinates, reflection and weights follow scipy's NI_GeometricTransform
 //               for order 0 / 1 operation by operation in f64 (this file is built with -ffp-contract=off)
+//   affine    : the dense-matrix form of resample (rotation), with the boundary modes reflect / nearest / constant and up
+//               to four f32 intensity operations applied in the store; without an affine drawn, a permuted copy with
+//               that arithmetic
 //   boxes     : 6-connected components of every class by union-find (hook the larger root under the smaller: root =
 //               minimum linear index = the component's first voxel in C raster order = scipy's numbering), per-tile
 //               root counts, one scan into (image, class, tile) order, root ranks, integer min / max extents by
@@ -27,6 +30,8 @@ constexpr int FIN_THREADS = 1024;
 constexpr int SCAN_THREADS = 1024;
 constexpr int BG = -1;  // background voxel in the link array; a root's rank r is stored as -(r + 2)
 constexpr int PARAM_STRIDE = 16;  // doubles per sample of msl_augment_resample
+constexpr int AFFINE_STRIDE = 32;  // doubles per sample of msl_augment_affine
+constexpr int AFFINE_MAX_OPS = 4;  // intensity operations per sample
 
 // ---- normalize ------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -171,6 +176,133 @@ __global__ __launch_bounds__(DP_THREADS) void resample_kernel(
         t = t + coeff;
       }
   *di = (float)t;
+  *ds = ss[base + i0[0] * pst[0] + i0[1] * pst[1] + i0[2] * pst[2]];
+}
+
+// ---- rotating affine + intensity ------------------------------------------------------------------------------------
+// scipy's map_coordinate for the three boundaries of datasets._aug_affine: 0 reflect, 1 nearest ("border"), 2 constant
+// ("zeros": -1 = outside, the caller writes cval 0; a coordinate exactly on the last voxel is inside)
+__device__ __forceinline__ double map_boundary(double in, int len, int mode) {
+  if (mode == 0) return map_reflect(in, len);
+  if (mode == 1) return in < 0.0 ? 0.0 : (in > (double)(len - 1) ? (double)(len - 1) : in);
+  return (in < 0.0 || in > (double)(len - 1)) ? -1.0 : in;
+}
+
+// Filter taps beyond the edge: reflect maps them as the coordinate; with nearest / constant a tap can only leave the
+// volume by one voxel at the far edge and carries weight 0 there (scipy reads an in-range voxel too): clamped.
+__device__ __forceinline__ int map_tap(long long i, int len, int mode) {
+  if (i >= 0 && i < len) return (int)i;
+  if (mode == 0) i = (long long)map_reflect((double)i, len);
+  return i < 0 ? 0 : (i >= len ? len - 1 : (int)i);  // every source index ends inside [0, len)
+}
+
+__device__ __forceinline__ float apply_ops(float v, const double* __restrict__ p) {
+  const int n_ops = (int)p[21];
+#pragma unroll
+  for (int k = 0; k < AFFINE_MAX_OPS; ++k) {
+    if (k < n_ops) {
+      const float x = (float)p[23 + 2 * k];  // an f32 value stored exactly
+      v = p[22 + 2 * k] == 1.0 ? __fadd_rn(v, x) : __fmul_rn(v, x);
+    }
+  }
+  return v;
+}
+
+// params (N, AFFINE_STRIDE) f64 per sample: [0] source volume, [1..3] source axis of output axes 0..2, [4..6] reversal
+// of output axes 0..2, [7] affine on / off, [8..16] matrix M row-major, [17..19] offset, [20] boundary, [21] number of
+// intensity operations (<= 4), [22 + 2k] kind (1 add, 2 multiply), [23 + 2k] f32 operand.  With the affine on, output
+// voxel o samples the permuted volume at M o + offset exactly as NI_GeometricTransform does: per axis cc = 0,
+// cc += o[k] * M[h][k] for k = 0, 1, 2, cc += offset[h], then the boundary map, then order 1 (image) / order 0 (mask).
+// Every thread gathers its own eight corners straight from global memory: under the +-15 degree rotations of the
+// recipe a wave's 64 outputs stay within a few source rows, which L2 serves.
+__global__ __launch_bounds__(DP_THREADS) void affine_kernel(
+    const float* __restrict__ src_img, const unsigned char* __restrict__ src_seg, int n_src,
+    const double* __restrict__ params, int D, int H, int W, float* __restrict__ dst_img,
+    unsigned char* __restrict__ dst_seg) {
+  const long long V = (long long)D * H * W;
+  const long long o = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
+  if (o >= V) return;
+  const int n = blockIdx.y;
+  const double* p = params + (size_t)n * AFFINE_STRIDE;
+  const int sv = (int)p[0];
+  float* di = dst_img + (long long)n * V + o;
+  unsigned char* ds = dst_seg + (long long)n * V + o;
+  const int dims[3] = {D, H, W};
+  const long long sstride[3] = {(long long)H * W, (long long)W, 1LL};
+  int ax[3], rev[3];
+  bool ok = sv >= 0 && sv < n_src;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ax[a] = (int)p[1 + a];
+    rev[a] = (int)p[4 + a];
+    ok = ok && ax[a] >= 0 && ax[a] < 3;
+  }
+  // rejected on the host; never read out of bounds: the axes must be a permutation that keeps the shape
+  ok = ok && ax[0] != ax[1] && ax[0] != ax[2] && ax[1] != ax[2];
+  if (ok) ok = dims[ax[0]] == D && dims[ax[1]] == H && dims[ax[2]] == W;
+  if (!ok) {
+    *di = 0.0f;
+    *ds = 0;
+    return;
+  }
+  const float* si = src_img + (long long)sv * V;
+  const unsigned char* ss = src_seg + (long long)sv * V;
+  long long pst[3];  // source stride of output axis a (signed by the reversal) and its base
+  long long base = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
+    if (rev[a]) base += (long long)(dims[ax[a]] - 1) * sstride[ax[a]];
+  }
+  const int oc[3] = {(int)(o / ((long long)H * W)), (int)((o / W) % H), (int)(o % W)};
+  if (p[7] == 0.0) {  // permuted copy, the intensity arithmetic in the store
+    const long long s = base + oc[0] * pst[0] + oc[1] * pst[1] + oc[2] * pst[2];
+    *di = apply_ops(si[s], p);
+    *ds = ss[s];
+    return;
+  }
+  const int mode = (int)p[20];
+  int i1[3][2], i0[3];
+  double w[3][2];
+  bool outside = false;
+#pragma unroll
+  for (int h = 0; h < 3; ++h) {
+    double c = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c = c + (double)oc[k] * p[8 + 3 * h + k];
+    c = c + p[17 + h];
+    const int len = dims[h];
+    const double cc = map_boundary(c, len, mode);
+    if (mode == 2 && !(cc > -1.0)) outside = true;
+    const double fl = floor(cc);
+    const long long st = (long long)fl;
+    const double x = cc - fl;
+    w[h][0] = 1.0 - x;
+    w[h][1] = 1.0 - w[h][0];
+    i1[h][0] = map_tap(st, len, mode);
+    i1[h][1] = map_tap(st + 1, len, mode);
+    i0[h] = map_tap((long long)floor(cc + 0.5), len, mode);
+  }
+  if (outside) {  // scipy's constant: cval for image and mask alike, the intensity operations still apply
+    *di = apply_ops(0.0f, p);
+    *ds = 0;
+    return;
+  }
+  double t = 0.0;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int d = 0; d < 2; ++d) {
+        const long long s = base + i1[0][a] * pst[0] + i1[1][b] * pst[1] + i1[2][d] * pst[2];
+        double coeff = (double)si[s];
+        coeff = coeff * w[0][a];
+        coeff = coeff * w[1][b];
+        coeff = coeff * w[2][d];
+        t = t + coeff;
+      }
+  *di = apply_ops((float)t, p);
   *ds = ss[base + i0[0] * pst[0] + i0[1] * pst[1] + i0[2] * pst[2]];
 }
 
@@ -500,6 +632,18 @@ int msl_augment_resample(const float* src_img, const unsigned char* src_seg, int
   if (N > 65535 || (long long)D * H * W >= (1LL << 40)) return MSL_ERR_UNSUPPORTED;
   const long long V = (long long)D * H * W;
   MSL_LAUNCH(resample_kernel, dim3((unsigned)((V + DP_THREADS - 1) / DP_THREADS), N), dim3(DP_THREADS), 0,
+             (hipStream_t)stream, src_img, src_seg, n_src, params, D, H, W, dst_img, dst_seg);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int msl_augment_affine(const float* src_img, const unsigned char* src_seg, int n_src, const double* params, int N,
+                       int D, int H, int W, float* dst_img, unsigned char* dst_seg, void* stream) {
+  if (!src_img || !src_seg || !params || !dst_img || !dst_seg || N <= 0 || n_src <= 0 || D <= 0 || H <= 0 || W <= 0)
+    return MSL_ERR_ARG;
+  if (N > 65535 || (long long)D * H * W >= (1LL << 40)) return MSL_ERR_UNSUPPORTED;
+  const long long V = (long long)D * H * W;
+  MSL_LAUNCH(affine_kernel, dim3((unsigned)((V + DP_THREADS - 1) / DP_THREADS), N), dim3(DP_THREADS), 0,
              (hipStream_t)stream, src_img, src_seg, n_src, params, D, H, W, dst_img, dst_seg);
   MSL_LAUNCH_CHECK();
   return MSL_OK;

@@ -62,7 +62,8 @@ def boxes_from_segmentation(seg, n_classes=1):
 # front.  flip / rotate90 are index permutations (exact; MONAI calls the same flip / rot90).  translate / scale are the
 # two RandAffined uses: resampling with bilinear (image) / nearest (mask) interpolation and reflection padding.  MONAI is
 # absent, so its random-number stream and its affine grid convention are NOT pinned (documented in DESIGN.md); the
-# transforms are drawn from ``np.random.RandomState(seed)``.
+# transforms are drawn from ``np.random.RandomState(seed)``.  The same holds for the rotating affine of train_lesions()
+# (``rotate_range``: R = Rx Ry Rz about the volume's centre) and for its shiftintensity / scaleintensity.
 
 def _draw_flip(rs, spatial_axis=(0, 1, 2), prob=0.1):
     """The random draws of ``_aug_flip`` -> flipped spatial axes, or None (no flip)."""
@@ -104,13 +105,15 @@ def _rand_range(rs, rng, n=3):
 
 
 def _draw_affine(rs, mode=("bilinear", "nearest"), translate_range=None, scale_range=None, padding_mode="reflection",
-                 prob=0.1):
-    """The random draws of ``_aug_affine`` -> (zoom, shift) per spatial axis, or None."""
+                 prob=0.1, rotate_range=None):
+    """The random draws of ``_aug_affine`` -> (zoom, shift) per spatial axis, or None.  With a ``rotate_range`` the
+    angles are drawn first (then translate, then scale) and the result is (zoom, shift, angles)."""
     if rs.rand() >= prob:
         return None
+    angles = _rand_range(rs, rotate_range) if rotate_range is not None else None
     shift = _rand_range(rs, translate_range) if translate_range is not None else [0.0] * 3
     zoom = [1.0 + v for v in _rand_range(rs, scale_range)] if scale_range is not None else [1.0] * 3
-    return zoom, shift
+    return (zoom, shift) if angles is None else (zoom, shift, angles)
 
 
 def affine_offset(shape, zoom, shift):
@@ -119,16 +122,37 @@ def affine_offset(shape, zoom, shift):
     return centre - np.diag(zoom) @ centre + np.array(shift, dtype=np.float64)
 
 
+def rotation_matrix(angles):
+    """R = Rx(a0) Ry(a1) Rz(a2): rotations about array axes 0, 1, 2 (f64)."""
+    c, s = np.cos(np.asarray(angles, dtype=np.float64)), np.sin(np.asarray(angles, dtype=np.float64))
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, c[0], -s[0]], [0.0, s[0], c[0]]])
+    ry = np.array([[c[1], 0.0, s[1]], [0.0, 1.0, 0.0], [-s[1], 0.0, c[1]]])
+    rz = np.array([[c[2], -s[2], 0.0], [s[2], c[2], 0.0], [0.0, 0.0, 1.0]])
+    return rx @ ry @ rz
+
+
+def affine_matrix(shape, zoom, shift, angles=None):
+    """-> (M, offset): output voxel o of ``_aug_affine`` samples input position M o + offset, which is
+    centre + R diag(zoom) (o - centre) + shift with centre = (shape - 1) / 2.  Without angles M is diag(zoom) and the
+    offset is ``affine_offset``'s, bit for bit."""
+    if angles is None:
+        return np.diag(zoom), affine_offset(shape, zoom, shift)
+    centre = (np.array(shape, dtype=np.float64) - 1) / 2
+    mat = rotation_matrix(angles) @ np.diag(np.asarray(zoom, dtype=np.float64))
+    return mat, centre - mat @ centre + np.array(shift, dtype=np.float64)
+
+
+SCIPY_BOUNDARY = {"reflection": "reflect", "border": "nearest", "zeros": "constant"}
+
+
 def _aug_affine(img, seg, rs, mode=("bilinear", "nearest"), translate_range=None, scale_range=None,
-                padding_mode="reflection", prob=0.1):
+                padding_mode="reflection", prob=0.1, rotate_range=None):
     from scipy.ndimage import affine_transform
-    d = _draw_affine(rs, mode, translate_range, scale_range, padding_mode, prob)
+    d = _draw_affine(rs, mode, translate_range, scale_range, padding_mode, prob, rotate_range)
     if d is None:
         return img, seg
-    zoom, shift = d
-    pad = {"reflection": "reflect", "border": "nearest", "zeros": "constant"}[padding_mode]
-    mat = np.diag(zoom)
-    off = affine_offset(img.shape[1:], zoom, shift)  # output voxel o samples input voxel M o + off
+    pad = SCIPY_BOUNDARY[padding_mode]
+    mat, off = affine_matrix(img.shape[1:], *d)  # output voxel o samples input voxel M o + off
     outs = []
     for a, m in ((img, mode[0]), (seg, mode[1])):
         order = 1 if m == "bilinear" else 0
@@ -136,8 +160,37 @@ def _aug_affine(img, seg, rs, mode=("bilinear", "nearest"), translate_range=None
     return outs[0], outs[1]
 
 
-AUGMENTATIONS = {"flip": _aug_flip, "rotate90": _aug_rotate90, "affine": _aug_affine}
-DRAWS = {"flip": _draw_flip, "rotate90": _draw_rotate90, "affine": _draw_affine}
+# RandShiftIntensityd / RandScaleIntensityd: image only, one f32 operation; zeros do not stay zero (as in MONAI)
+def _draw_intensity(rs, rng, prob):
+    if rs.rand() >= prob:
+        return None
+    return float(rs.uniform(rng[0], rng[1]) if isinstance(rng, (tuple, list)) else rs.uniform(-rng, rng))
+
+
+def _draw_shiftintensity(rs, offsets=0.1, prob=0.1):
+    """The random draws of ``_aug_shiftintensity`` -> the offset (f64), or None."""
+    return _draw_intensity(rs, offsets, prob)
+
+
+def _aug_shiftintensity(img, seg, rs, offsets=0.1, prob=0.1):
+    off = _draw_shiftintensity(rs, offsets, prob)
+    return (img, seg) if off is None else (img + np.float32(off), seg)
+
+
+def _draw_scaleintensity(rs, factors=0.1, prob=0.1):
+    """The random draws of ``_aug_scaleintensity`` -> the factor f of img * (1 + f) (f64), or None."""
+    return _draw_intensity(rs, factors, prob)
+
+
+def _aug_scaleintensity(img, seg, rs, factors=0.1, prob=0.1):
+    f = _draw_scaleintensity(rs, factors, prob)
+    return (img, seg) if f is None else (img * np.float32(1.0 + f), seg)
+
+
+AUGMENTATIONS = {"flip": _aug_flip, "rotate90": _aug_rotate90, "affine": _aug_affine,
+                 "shiftintensity": _aug_shiftintensity, "scaleintensity": _aug_scaleintensity}
+DRAWS = {"flip": _draw_flip, "rotate90": _draw_rotate90, "affine": _draw_affine,
+         "shiftintensity": _draw_shiftintensity, "scaleintensity": _draw_scaleintensity}
 
 
 def draw_augmentations(augmentations, rs):
@@ -158,12 +211,23 @@ REFERENCE_AUGMENTATIONS = [("flip", {"spatial_axis": (0, 1, 2), "prob": .5}),
                                       "padding_mode": "reflection", "prob": .7})]
 
 
+# train.py:196-205, train_lesions(): the entries of the clinical recipe that the example's list lacks (its flip / rotate90
+# go by the same CLI names as the example's and keep the example's parameters)
+LESIONS_AUGMENTATIONS = [("affine", {"mode": ("bilinear", "nearest"), "rotate_range": (np.pi / 12, np.pi / 12, np.pi / 12),
+                                     "scale_range": (0.1, 0.1, 0.1), "padding_mode": "border"}),
+                         ("shiftintensity", {"offsets": 0.1, "prob": 1.0}),
+                         ("scaleintensity", {"factors": 0.1, "prob": 1.0})]
+
+
 def select_augmentations(names):
-    """train.py:145: keep the reference's entries whose name was asked for; translate / scale both become 'affine'."""
-    unknown = set(names) - {n for n, _ in REFERENCE_AUGMENTATIONS}
+    """train.py:145: keep the reference's entries whose name was asked for, each list in its own order (the example's
+    first, then train_lesions()'s); translate / scale both become 'affine'."""
+    known = [n for n, _ in REFERENCE_AUGMENTATIONS + LESIONS_AUGMENTATIONS]
+    unknown = set(names) - set(known)
     if unknown:
-        raise ValueError(f"unknown augmentation(s) {sorted(unknown)}; known: flip rotate90 translate scale")
-    return [(n.replace("translate", "affine").replace("scale", "affine"), kw) for n, kw in REFERENCE_AUGMENTATIONS if n in names]
+        raise ValueError(f"unknown augmentation(s) {sorted(unknown)}; known: {' '.join(dict.fromkeys(known))}")
+    out = [(n.replace("translate", "affine").replace("scale", "affine"), kw) for n, kw in REFERENCE_AUGMENTATIONS if n in names]
+    return out + [(n, kw) for n, kw in LESIONS_AUGMENTATIONS if n in names]
 
 
 def _load(path_noext):

@@ -3,20 +3,35 @@ are loaded and normalised ONCE into HBM, and every batch is gathered, augmented,
 ``FusedTrainer.step_packed``'s target layout on the device (csrc/datapipe.hip).  Host mirror: ``datasets._Cases`` and
 ``datasets.boxes_from_segmentation``; the per-sample random draws are the host's own (``datasets.draw_augmentations``
 on ``datasets.sample_rng``), so a batch holds the same subjects, the same masks and bit-identical boxes as the host
-loader's, and images within the normalisation bound of DESIGN.md §4.7.
+loader's, and images within the normalisation bound of DESIGN.md §4.7.  Against the host transforms applied to the
+CACHED (device-normalised) volume the images are bit-identical too: every resample restates scipy's arithmetic and the
+intensity operations are single f32 roundings.
 
-Limits: rot90 on an axis pair of unequal sizes (a shape-changing rotation) raises NotImplementedError, and so does a
-flip / rot90 placed after an affine stage (the reference's order puts them first).
+Limits: rot90 on an axis pair of unequal sizes (a shape-changing rotation) raises NotImplementedError.  The supported
+order is the reference's - flips / rot90s, then affines, then shiftintensity / scaleintensity: a flip / rot90 placed
+after an affine stage or an intensity operation, an affine placed after an intensity operation and more than
+AFFINE_MAX_OPS intensity operations raise NotImplementedError.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 from os.path import join as pjoin
 
 from . import _lib
 from ._lib import ptr
-from .datasets import ShardSampler, _load, affine_offset, draw_augmentations, sample_rng
+from .datasets import SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset, draw_augmentations, sample_rng
 
 PARAM_STRIDE = 16  # f64 per sample of msl_augment_resample
+AFFINE_STRIDE = 32  # f64 per sample of msl_augment_affine
+AFFINE_MAX_OPS = 4  # intensity operations one msl_augment_affine row carries
+BOUNDARY = {"reflection": 0, "border": 1, "zeros": 2}  # msl_augment_affine's code of a padding_mode
+OP_ADD, OP_MUL = 1, 2
+
+# a stage msl_augment_affine runs: dense matrix / offset (f64, as the host computed them) and the boundary code
+AffineStage = namedtuple("AffineStage", "matrix offset boundary")
+# kind (OP_ADD / OP_MUL) and the np.float32 operand of the host's one f32 operation
+IntensityOp = namedtuple("IntensityOp", "kind value")
 
 
 def _stream(dev):
@@ -84,22 +99,48 @@ def boxes_from_segmentation_device(seg, n_classes=1, capacity=None, comp_cap=Non
     return boxes, labels, (out.gb, out.gl, out.obj_off, capacity)
 
 
-def sample_params(draws, shape):
-    """One sample's draws (``datasets.draw_augmentations``) -> (signed axis permutation, [affine stages]).
+def sample_params(draws, shape, augmentations=None):
+    """One sample's draws (``datasets.draw_augmentations``) -> (signed axis permutation, [stages]).
 
     The permutation is (axis, rev): output axis a reads source axis axis[a], reversed iff rev[a]; it composes the flips
-    and rot90s exactly as np.flip / np.rot90 index.  Each affine stage is None (not drawn) or (zoom, offset) in f64."""
+    and rot90s exactly as np.flip / np.rot90 index.  ``augmentations`` is the transform list the draws were made from (it
+    holds each affine's ``padding_mode``; without it, reflection).  There is one stage per affine / intensity entry, in
+    list order: None (not drawn), (zoom, offset) in f64 for a diagonal affine with reflection padding (the stage
+    msl_augment_resample runs), ``AffineStage`` for a rotating affine or another boundary, ``IntensityOp``."""
     axis, rev = [0, 1, 2], [0, 0, 0]
     stages = []
+    n_ops = 0
 
     def swap(a, b):
         axis[a], axis[b] = axis[b], axis[a]
         rev[a], rev[b] = rev[b], rev[a]
 
-    for name, d in draws:
+    for k, (name, d) in enumerate(draws):
         if name == "affine":
-            stages.append(None if d is None else (list(d[0]), list(affine_offset(shape, *d))))
+            if n_ops:
+                raise NotImplementedError("device pipeline: an affine stage after an intensity operation")
+            t = augmentations[k] if augmentations is not None else name
+            pad = ({} if isinstance(t, str) else t[1]).get("padding_mode", "reflection")
+            if d is None:
+                stages.append(None)
+            elif len(d) == 2 and pad == "reflection":
+                stages.append((list(d[0]), list(affine_offset(shape, *d))))
+            else:
+                stages.append(AffineStage(*affine_matrix(shape, *d), BOUNDARY[pad]))
             continue
+        if name in ("shiftintensity", "scaleintensity"):
+            n_ops += 1
+            if n_ops > AFFINE_MAX_OPS:
+                raise NotImplementedError(f"device pipeline: more than {AFFINE_MAX_OPS} intensity operations")
+            if d is None:
+                stages.append(None)
+            elif name == "shiftintensity":
+                stages.append(IntensityOp(OP_ADD, np.float32(d)))
+            else:
+                stages.append(IntensityOp(OP_MUL, np.float32(1.0 + d)))
+            continue
+        if n_ops:
+            raise NotImplementedError("device pipeline: a flip / rot90 after an intensity operation")
         if stages:
             raise NotImplementedError("device pipeline: a flip / rot90 after an affine stage")
         if d is None:
@@ -121,6 +162,113 @@ def sample_params(draws, shape):
                 swap(a, b)
                 rev[b] ^= 1
     return (axis, rev), stages
+
+
+def affine_row(source, perm=((0, 1, 2), (0, 0, 0)), stage=None, ops=()):
+    """One msl_augment_affine parameter row (AFFINE_STRIDE f64; layout in include/mslesions3d_hip.h).  ``stage``: None, a
+    (zoom, offset) pair (reflection) or an ``AffineStage``; ``ops``: the drawn ``IntensityOp``s in order."""
+    if len(ops) > AFFINE_MAX_OPS:
+        raise NotImplementedError(f"device pipeline: more than {AFFINE_MAX_OPS} intensity operations")
+    r = np.zeros(AFFINE_STRIDE, dtype=np.float64)
+    r[0], r[1:4], r[4:7] = source, perm[0], perm[1]
+    if stage is not None:
+        if not isinstance(stage, AffineStage):
+            stage = AffineStage(np.diag(stage[0]), stage[1], BOUNDARY["reflection"])
+        r[7], r[8:17], r[17:20], r[20] = 1.0, np.asarray(stage.matrix, dtype=np.float64).reshape(9), stage.offset, stage.boundary
+    r[21] = len(ops)
+    for k, op in enumerate(ops):
+        r[22 + 2 * k], r[23 + 2 * k] = op.kind, np.float32(op.value)
+    return r
+
+
+def affine_numpy(vol, matrix, offset, order, boundary):
+    """Host mirror of msl_augment_affine's resample of one (D, H, W) volume, operation by operation in f64 (scipy 1.15's
+    NI_GeometricTransform): per axis cc = 0, cc += o[k] * M[h][k] (k = 0, 1, 2), cc += offset[h]; the boundary's
+    map_coordinate; order 1: taps floor(cc), floor(cc) + 1 with weights w0 = 1 - (cc - floor(cc)), w1 = 1 - w0, the eight
+    corners accumulated axis 0 slowest, each as ((value * w_0) * w_1) * w_2; order 0: tap floor(cc + 0.5).  Boundary 2
+    (constant) writes 0 wherever an axis maps outside [0, len - 1]."""
+    dims = vol.shape
+    o = [x.astype(np.float64) for x in np.meshgrid(*(np.arange(n) for n in dims), indexing="ij")]
+    M, off = np.asarray(matrix, dtype=np.float64), np.asarray(offset, dtype=np.float64)
+
+    def reflect(c, n):
+        c = np.array(c, dtype=np.float64)
+        if n <= 1:
+            return np.zeros_like(c)
+        sz2 = 2.0 * n
+        x = np.where(c < -sz2, sz2 * np.trunc(-c / sz2) + c, c)
+        lo = np.where(x < -n, x + sz2, np.where(x > -1e-15, 1e-15, -x) - 1.0)
+        y = c - sz2 * np.trunc(c / sz2)
+        hi = np.where(y >= n, (sz2 - y) - 1.0, y)
+        return np.where(c < 0, lo, np.where(c > n - 1, hi, c))
+
+    def tap(i, n):
+        m = reflect(i, n) if boundary == 0 else i
+        return np.clip(np.where((i >= 0) & (i < n), i, np.trunc(m)), 0, n - 1).astype(np.int64)
+
+    cc, outside = [], np.zeros(dims, dtype=bool)
+    for h in range(3):
+        c = np.zeros(dims)
+        for k in range(3):
+            c = c + o[k] * M[h, k]
+        c = c + off[h]
+        n = dims[h]
+        if boundary == 0:
+            c = reflect(c, n)
+        elif boundary == 1:
+            c = np.where(c < 0, 0.0, np.where(c > n - 1, float(n - 1), c))
+        else:
+            outside |= (c < 0) | (c > n - 1)
+            c = np.where((c < 0) | (c > n - 1), -1.0, c)
+        cc.append(c)
+    if order == 0:
+        out = vol[tuple(tap(np.floor(c + 0.5), n) for c, n in zip(cc, dims))]
+        return np.where(outside, 0, out).astype(vol.dtype)
+    idx, w = [], []
+    for c, n in zip(cc, dims):
+        fl = np.floor(c)
+        w0 = 1.0 - (c - fl)
+        w.append((w0, 1.0 - w0))
+        idx.append((tap(fl, n), tap(fl + 1, n)))
+    t = np.zeros(dims)
+    for a in range(2):
+        for b in range(2):
+            for d in range(2):
+                coeff = vol[idx[0][a], idx[1][b], idx[2][d]].astype(np.float64)
+                coeff = coeff * w[0][a]
+                coeff = coeff * w[1][b]
+                coeff = coeff * w[2][d]
+                t = t + coeff
+    return np.where(outside, 0.0, t).astype(np.float32)
+
+
+def batch_launches(slots, per_sample):
+    """-> [(entry point, (N, stride) f64 rows)]: one launch per affine stage some sample of the batch drew (a resample
+    of a resample is not one resample), or one plain gather.  The first launch reads the cache through the sample's
+    permutation; the last one carries the intensity operations.  A launch whose stages are all diagonal with
+    reflection padding and that carries no operation stays on msl_augment_resample."""
+    N = len(slots)
+    geo = [[st for st in stages if not isinstance(st, IntensityOp)] for _, stages in per_sample]
+    ops = [[st for st in stages if isinstance(st, IntensityOp)] for _, stages in per_sample]
+    n_geo = max((len(g) for g in geo), default=0)
+    used = [j for j in range(n_geo) if any(j < len(g) and g[j] is not None for g in geo)] or [None]
+    out = []
+    for k, j in enumerate(used):
+        first, last = k == 0, k == len(used) - 1
+        st = [g[j] if j is not None and j < len(g) else None for g in geo]
+        dense = any(isinstance(x, AffineStage) for x in st) or (last and any(ops))
+        rows = np.zeros((N, AFFINE_STRIDE if dense else PARAM_STRIDE), dtype=np.float64)
+        for n in range(N):
+            src = slots[n] if first else n
+            perm = per_sample[n][0] if first else ((0, 1, 2), (0, 0, 0))
+            if dense:
+                rows[n] = affine_row(src, perm, st[n], ops[n] if last else ())
+            else:
+                rows[n, 0], rows[n, 1:4], rows[n, 4:7] = src, perm[0], perm[1]
+                if st[n] is not None:
+                    rows[n, 7], rows[n, 8:11], rows[n, 11:14] = 1.0, st[n][0], st[n][1]
+        out.append(("msl_augment_affine" if dense else "msl_augment_resample", rows))
+    return out
 
 
 def train_batch_order(dataset, epoch):
@@ -203,6 +351,9 @@ class DeviceCache:
                     raise NotImplementedError(f"device pipeline: rot90 over axes {(a, b)} of sizes "
                                               f"{self.shape[a]} != {self.shape[b]} changes the volume's shape")
         self.n_affine = sum(1 for t in self.augmentations if (t if isinstance(t, str) else t[0]) == "affine")
+        # the order limits of sample_params hold for the list itself, drawn or not: refuse it here, not at the first batch
+        sample_params([((t if isinstance(t, str) else t[0]), None) for t in self.augmentations], self.shape,
+                      self.augmentations)
 
     # ---- footprint ----------------------------------------------------------------------------------------------------
     def nbytes(self):
@@ -230,36 +381,19 @@ class DeviceCache:
                                  "box": _BoxOut(N, self.shape, self.n_classes, self.capacity, self.comp_cap, dev)}
         return b
 
-    def _params(self, slots, per_sample):
-        """-> (n_stages, N, PARAM_STRIDE) f64 and which stages any sample uses (stage 0 always runs: the gather)."""
-        N, n_st = len(slots), max(1, self.n_affine)
-        p = np.zeros((n_st, N, PARAM_STRIDE), dtype=np.float64)
-        used = [True] + [False] * (n_st - 1)
-        for n, (slot, ((axis, rev), stages)) in enumerate(zip(slots, per_sample)):
-            for j in range(n_st):
-                row = p[j, n]
-                row[0] = slot if j == 0 else n
-                row[1:4] = axis if j == 0 else (0, 1, 2)
-                row[4:7] = rev if j == 0 else (0, 0, 0)
-                st = stages[j] if j < len(stages) else None
-                if st is not None:
-                    row[7], row[8:11], row[11:14] = 1.0, st[0], st[1]
-                    used[j] = True
-        return p, used
-
     def _run(self, slots, per_sample, b):
         dev = self.device
         stream = _stream(dev)
-        p, used = self._params(slots, per_sample)
-        pd = torch.from_numpy(p).pin_memory().to(dev, non_blocking=True)
+        launches = batch_launches(slots, per_sample)
+        pd = torch.from_numpy(np.concatenate([rows.reshape(-1) for _, rows in launches])).pin_memory().to(dev, non_blocking=True)
         N = len(slots)
-        stages = [j for j in range(len(used)) if used[j]]
         src_img, src_seg, n_src = self.img, self.seg, self.img.shape[0]
-        for k, j in enumerate(stages):
-            last = k == len(stages) - 1
+        at = 0
+        for k, (fn, rows) in enumerate(launches):
+            last = k == len(launches) - 1
             dst_img, dst_seg = (b["img"], b["seg"]) if last else (b["tmp"][2 * (k % 2)], b["tmp"][2 * (k % 2) + 1])
-            _lib.call("msl_augment_resample", ptr(src_img), ptr(src_seg), n_src, ptr(pd[j]), N, *self.shape,
-                      ptr(dst_img), ptr(dst_seg), stream)
+            _lib.call(fn, ptr(src_img), ptr(src_seg), n_src, ptr(pd[at:]), N, *self.shape, ptr(dst_img), ptr(dst_seg), stream)
+            at += rows.size
             src_img, src_seg, n_src = dst_img, dst_seg, N
         b["box"].launch(b["seg"], stream)
 
@@ -270,7 +404,7 @@ class DeviceCache:
             for i in idx:
                 draws = draw_augmentations(self.augmentations, sample_rng(tr.seed, epoch, tr.subjects[i])) \
                     if self.augmentations else []
-                per_sample.append(sample_params(draws, self.shape))
+                per_sample.append(sample_params(draws, self.shape, self.augmentations))
             b = self._buffers(len(idx))
             self._run([self.train_slots[i] for i in idx], per_sample, b)
             yield {"img": b["img"], "seg": b["seg"], "gb": b["box"].gb, "gl": b["box"].gl, "obj_off": b["box"].obj_off,

@@ -37,7 +37,8 @@ def build_parser():
     p.add_argument('-minos', '--min_object_size', type=int, default=6)
     p.add_argument('-maxos', '--max_object_size', type=int, default=14)
     p.add_argument('--alpha', type=float, default=1.)
-    p.add_argument('-a', '--augmentations', type=str, nargs='*', default=[])
+    p.add_argument('-a', '--augmentations', type=str, nargs='*', default=[],
+                   help='flip rotate90 translate scale (example recipe); affine shiftintensity scaleintensity (train_lesions)')
     p.add_argument('-ld', '--logdir', type=str, default=r'../logs/artificial_dataset')
     p.add_argument('-nw', '--num_workers', type=int, default=0)
     p.add_argument('-wm', '--width_mult', type=float, default=1.)
@@ -105,7 +106,7 @@ def example(args):
     layers = [int(x) for x in args.prediction_layers.split()]
     aspect_ratios = {l: [1.] for l in layers}
     scales = {int(k): v for k, v in args.scales.items()}
-    augmentations = select_augmentations(args.augmentations)  # train.py:132-145 (flip rotate90 translate scale)
+    augmentations = select_augmentations(args.augmentations)  # train.py:132-145, :196-205
     dataset = ExampleDataset(n_classes=args.n_classes, subject=args.subject, percentage=args.percentage,
                              num_workers=args.num_workers, batch_size=args.batch_size, data_dir=args.dataset_path,
                              dataset_name=args.dataset_name, augmentations=augmentations, random_state=970205,

@@ -1,5 +1,7 @@
 """Per-kernel parity on a real MI355X: every C-ABI entry point against stock torch fp32 ops on the CPU
-(the same third-party arithmetic the reference calls).  Tolerances are stated per test; integer outputs exact."""
+(the same third-party arithmetic the reference calls).  Tolerances are stated per test; integer outputs exact.
+The BatchNorm family (msl_bn_*) has one smoke-level test here; tests/test_gpu_bn.py walks every code path of those kernels
+against a float64 reference with derived bounds."""
 import numpy as np
 import pytest
 import torch

@@ -456,6 +456,31 @@ int msl_seg_boxes(const unsigned char* seg, int N, int D, int H, int W, int n_cl
                   void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,
                   int* overflow, void* stream);
 
+/* ---- clinical cases (csrc/datapipe.hip, devicedata.LesionCache): the host pipeline of datasets._LesionCases --------
+ * msl_foreground_box: box (device, 6 ints) = lo0, lo1, lo2, hi0, hi1, hi2 of datasets.foreground_box on one (D,H,W) f32
+ * volume: F = {v : vol[v] > 0}, lo = max(min F - margin, 0), hi = min(max F + margin + 1, n); empty F: the whole volume.
+ * msl_augment_fit: dst (N,T0,T1,T2) f32 image / i16 mask from ragged cases kept in two flat arenas of arena_elems
+ * elements each (f32 image, i16 mask).  table (device, n_cases x 4 i64): element offset and shape n0, n1, n2 of a case.
+ * params: msl_augment_affine's (N,32) f64 rows with [0] = case.  Output voxel o reads voxel q of the permuted case (shape
+ * n'), q = clamp(o + d, 0, n' - 1) per axis with d = -((t - n') / 2) where n' < t and n' / 2 - t / 2 otherwise
+ * (resize_with_pad_or_crop, edge replication); with the affine on the permuted case is sampled at M q + offset as
+ * msl_augment_affine samples it; then the intensity operations.  A row whose case, axes or table entry are invalid
+ * writes zeros.
+ * msl_instance_boxes: BoundingBoxesGeneratord "instances" mode (datasets.boxes_from_instances) on seg (N,D,H,W) i16, ids in
+ * [1, 32767].  thresholds (HOST, n_pairs x 2 ints, n_pairs <= 8, read during the call; inf = INT_MAX): per image, per pair
+ * (lo, hi) in order, the ids with lo <= id < hi in ascending order give inclusive extents / size with label = position + 1;
+ * the first unique value of an image is discarded (the smallest id where there is no background); flat boxes dropped.
+ * Outputs in msl_seg_boxes's layout.  *overflow (device): 0, |1 more boxes than capacity, |4 a negative value in seg;
+ * obj_off stays <= capacity.  workspace: _workspace_bytes(N) bytes (0 = unsupported). */
+int msl_foreground_box(const float* vol, int D, int H, int W, int margin, int* box, void* stream);
+int msl_augment_fit(const float* arena_img, const short* arena_seg, long long arena_elems, const long long* table,
+                    int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
+                    void* stream);
+size_t msl_instance_boxes_workspace_bytes(int N);
+int msl_instance_boxes(const short* seg, int N, int D, int H, int W, const int* thresholds, int n_pairs, int capacity,
+                       void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,
+                       int* overflow, void* stream);
+
 /* ---- optimiser + NaN guard : ssd3d.py:704-722, :258-261 ---------------------------------------------------- */
 /* hp (device, 8 floats): step_size(bias), step_size(other), sqrt(bias_correction2), beta1, beta2, eps,
  * weight_decay, gradient scale.  is_bias (n bytes): 1 for elements of '.bias' parameters (2*lr group). */

@@ -687,3 +687,437 @@ int msl_seg_boxes(const unsigned char* seg, int N, int D, int H, int W, int n_cl
 }
 
 }  // extern "C"
+
+// ---- clinical cases: foreground box, ragged augment + fit, instance boxes ---------------------------------------------
+// Host mirrors: datasets.foreground_box, datasets._LesionCases.__getitem__ (augmentations at the cropped shape, then
+// resize_with_pad_or_crop with edge replication) and datasets.boxes_from_instances.
+//
+//   foreground : one wave per (d, h) row; the w extents stay in the lanes, the d / h extents are wave-uniform; six integer
+//                atomics per wave, then one thread applies margin, clamp and the empty rule
+//   fit        : one thread per four output voxels along the last axis; the fit is a clamped shift per axis, the
+//                permutation / affine / intensity arithmetic is affine_kernel's; image stored as one 16-byte vector
+//   instances  : one 16-byte load per eight voxels, nothing else while they are all background; runs of one id are
+//                folded in registers before the integer min / max atomics into a per-image (32768, 6) extent table;
+//                one workgroup compacts it in (image, threshold pair, ascending id) order by a fixed-order scan
+namespace {
+
+constexpr int FG_THREADS = 256;
+constexpr int FIT_VEC = 4;            // output voxels per thread
+constexpr int INST_IDS = 32768;       // ids 1 .. 32767 (int16)
+constexpr int INST_VEC = 8;           // voxels per 16-byte load
+constexpr int INST_UNROLL = 4;        // loads in flight per thread
+constexpr int INST_MAX_PAIRS = 8;
+constexpr int INST_HDR = 4;           // ints per image: smallest id, largest id, background seen, unused
+constexpr int IMAX = 0x7FFFFFFF;
+
+__global__ void fg_init_kernel(int* __restrict__ box) {
+  if (threadIdx.x < 6) box[threadIdx.x] = threadIdx.x < 3 ? IMAX : -1;
+}
+
+__global__ __launch_bounds__(FG_THREADS) void fg_reduce_kernel(const float* __restrict__ vol, int D, int H, int W,
+                                                               int* __restrict__ box) {
+  const int lane = threadIdx.x & 63;
+  const long long rows = (long long)D * H;
+  const long long nwave = (long long)gridDim.x * (FG_THREADS / 64);
+  int lo_d = IMAX, lo_h = IMAX, lo_w = IMAX, hi_d = -1, hi_h = -1, hi_w = -1;
+  for (long long r = (long long)blockIdx.x * (FG_THREADS / 64) + (threadIdx.x >> 6); r < rows; r += nwave) {
+    const float* row = vol + r * W;
+    bool any = false;
+    for (int w = lane; w < W; w += 64) {
+      if (row[w] > 0.0f) {
+        any = true;
+        lo_w = min(lo_w, w);
+        hi_w = max(hi_w, w);
+      }
+    }
+    if (__any(any)) {  // wave-uniform
+      const int d = (int)(r / H), h = (int)(r % H);
+      lo_d = min(lo_d, d); hi_d = max(hi_d, d);
+      lo_h = min(lo_h, h); hi_h = max(hi_h, h);
+    }
+  }
+  lo_w = wave_min(lo_w);
+  hi_w = wave_max(hi_w);
+  if (lane == 0 && hi_d >= 0) {
+    atomicMin(box + 0, lo_d); atomicMin(box + 1, lo_h); atomicMin(box + 2, lo_w);
+    atomicMax(box + 3, hi_d); atomicMax(box + 4, hi_h); atomicMax(box + 5, hi_w);
+  }
+}
+
+__global__ void fg_final_kernel(int D, int H, int W, int margin, int* __restrict__ box) {
+  if (threadIdx.x != 0) return;
+  const int n[3] = {D, H, W};
+  if (box[3] < 0) {  // no foreground: the whole volume
+    for (int a = 0; a < 3; ++a) {
+      box[a] = 0;
+      box[3 + a] = n[a];
+    }
+    return;
+  }
+  for (int a = 0; a < 3; ++a) {
+    const long long lo = (long long)box[a] - margin, hi = (long long)box[3 + a] + margin + 1;
+    box[a] = lo < 0 ? 0 : (lo > n[a] ? n[a] : (int)lo);
+    box[3 + a] = hi > n[a] ? n[a] : (hi < 0 ? 0 : (int)hi);
+  }
+}
+
+// table (n_cases, 4) i64 per case: element offset into both arenas, shape n0, n1, n2.  params: msl_augment_affine's rows
+// with [0] = case.  Output voxel o of the (T0, T1, T2) target reads voxel q of the permuted case (shape n'), q_a =
+// clamp(o_a + d_a, 0, n'_a - 1), d_a = -((t_a - n'_a) / 2) if n'_a < t_a else n'_a / 2 - t_a / 2; with the affine on, the
+// permuted case is sampled at M q + offset as affine_kernel samples it.
+template <bool VEC>
+__global__ __launch_bounds__(DP_THREADS) void fit_kernel(
+    const float* __restrict__ src_img, const short* __restrict__ src_seg, long long arena_elems,
+    const long long* __restrict__ table, int n_cases, const double* __restrict__ params, int T0, int T1, int T2,
+    float* __restrict__ dst_img, short* __restrict__ dst_seg) {
+  const int G = (T2 + FIT_VEC - 1) / FIT_VEC;
+  const long long groups = (long long)T0 * T1 * G;
+  const long long g = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
+  if (g >= groups) return;
+  const int n = blockIdx.y;
+  const int x0 = (int)(g % G) * FIT_VEC;
+  const long long rowi = g / G;
+  const int oc0 = (int)(rowi / T1), oc1 = (int)(rowi % T1);
+  const long long out0 = (((long long)n * T0 + oc0) * T1 + oc1) * T2 + x0;
+  const int cnt = (T2 - x0) < FIT_VEC ? (T2 - x0) : FIT_VEC;
+  const double* p = params + (size_t)n * AFFINE_STRIDE;
+  float vi[FIT_VEC];
+  short vs[FIT_VEC];
+#pragma unroll
+  for (int j = 0; j < FIT_VEC; ++j) {
+    vi[j] = 0.0f;
+    vs[j] = 0;
+  }
+  const int cs = (int)p[0];
+  int ax[3], rev[3];
+  bool ok = cs >= 0 && cs < n_cases;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ax[a] = (int)p[1 + a];
+    rev[a] = (int)p[4 + a];
+    ok = ok && ax[a] >= 0 && ax[a] < 3;
+  }
+  ok = ok && ax[0] != ax[1] && ax[0] != ax[2] && ax[1] != ax[2];
+  long long coff = 0, sn[3] = {1, 1, 1};
+  if (ok) {  // rejected on the host; never read out of bounds
+    coff = table[(long long)cs * 4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) sn[a] = table[(long long)cs * 4 + 1 + a];
+    ok = coff >= 0 && sn[0] > 0 && sn[1] > 0 && sn[2] > 0 && sn[0] < (1 << 20) && sn[1] < (1 << 20) && sn[2] < (1 << 20);
+    ok = ok && coff + sn[0] * sn[1] * sn[2] <= arena_elems;
+  }
+  if (ok) {
+    const float* si = src_img + coff;
+    const short* ss = src_seg + coff;
+    const long long sstride[3] = {sn[1] * sn[2], sn[2], 1LL};
+    const int T[3] = {T0, T1, T2};
+    int dims[3], dsh[3];  // permuted shape n' and the fit's shift d
+    long long pst[3];
+    long long base = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      dims[a] = (int)sn[ax[a]];
+      dsh[a] = dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2;
+      pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
+      if (rev[a]) base += (long long)(dims[a] - 1) * sstride[ax[a]];
+    }
+    const int q0 = min(max(oc0 + dsh[0], 0), dims[0] - 1), q1 = min(max(oc1 + dsh[1], 0), dims[1] - 1);
+    const bool affine = p[7] != 0.0;
+    const int mode = (int)p[20];
+    int qprev = -1;
+    for (int j = 0; j < cnt; ++j) {
+      const int qc[3] = {q0, q1, min(max(x0 + j + dsh[2], 0), dims[2] - 1)};
+      if (j > 0 && qc[2] == qprev) {  // padded region along the last axis: the same source voxel, the same value
+        vi[j] = vi[j - 1];
+        vs[j] = vs[j - 1];
+        continue;
+      }
+      qprev = qc[2];
+      if (!affine) {
+        const long long s = base + qc[0] * pst[0] + qc[1] * pst[1] + qc[2] * pst[2];
+        vi[j] = apply_ops(si[s], p);
+        vs[j] = ss[s];
+        continue;
+      }
+      int i1[3][2], i0[3];
+      double w[3][2];
+      bool outside = false;
+#pragma unroll
+      for (int h = 0; h < 3; ++h) {
+        double c = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c = c + (double)qc[k] * p[8 + 3 * h + k];
+        c = c + p[17 + h];
+        const int len = dims[h];
+        const double cc = map_boundary(c, len, mode);
+        if (mode == 2 && !(cc > -1.0)) outside = true;
+        const double fl = floor(cc);
+        const long long st = (long long)fl;
+        const double x = cc - fl;
+        w[h][0] = 1.0 - x;
+        w[h][1] = 1.0 - w[h][0];
+        i1[h][0] = map_tap(st, len, mode);
+        i1[h][1] = map_tap(st + 1, len, mode);
+        i0[h] = map_tap((long long)floor(cc + 0.5), len, mode);
+      }
+      if (outside) {  // scipy's constant: cval for image and mask alike, the intensity operations still apply
+        vi[j] = apply_ops(0.0f, p);
+        vs[j] = 0;
+        continue;
+      }
+      double t = 0.0;
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int d = 0; d < 2; ++d) {
+            const long long s = base + i1[0][a] * pst[0] + i1[1][b] * pst[1] + i1[2][d] * pst[2];
+            double coeff = (double)si[s];
+            coeff = coeff * w[0][a];
+            coeff = coeff * w[1][b];
+            coeff = coeff * w[2][d];
+            t = t + coeff;
+          }
+      vi[j] = apply_ops((float)t, p);
+      vs[j] = ss[base + i0[0] * pst[0] + i0[1] * pst[1] + i0[2] * pst[2]];
+    }
+  }
+  if (VEC) {  // T2 % 4 == 0: every group is whole and 16-byte (image) / 8-byte (mask) aligned
+    *reinterpret_cast<float4*>(dst_img + out0) = make_float4(vi[0], vi[1], vi[2], vi[3]);
+    typedef short short4v __attribute__((ext_vector_type(4)));
+    short4v o;
+    o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2]; o[3] = vs[3];
+    *reinterpret_cast<short4v*>(dst_seg + out0) = o;
+  } else {
+    for (int j = 0; j < cnt; ++j) {
+      dst_img[out0 + j] = vi[j];
+      dst_seg[out0 + j] = vs[j];
+    }
+  }
+}
+
+struct InstPairs {
+  int n;
+  int lo[INST_MAX_PAIRS], hi[INST_MAX_PAIRS];
+};
+
+__global__ __launch_bounds__(DP_THREADS) void inst_init_kernel(int* __restrict__ ext, long long ext_words,
+                                                               int* __restrict__ hdr, int N, int* __restrict__ flags) {
+  const long long stride = (long long)gridDim.x * DP_THREADS;
+  if (blockIdx.x == 0 && threadIdx.x < 4) flags[threadIdx.x] = 0;
+  for (long long i = (long long)blockIdx.x * DP_THREADS + threadIdx.x; i < ext_words; i += stride)
+    ext[i] = (i % 6) < 3 ? IMAX : -1;
+  for (long long i = (long long)blockIdx.x * DP_THREADS + threadIdx.x; i < (long long)N * INST_HDR; i += stride) {
+    const int k = (int)(i % INST_HDR);
+    hdr[i] = k == 0 ? IMAX : (k == 1 ? -1 : 0);
+  }
+}
+
+struct InstRun {  // voxels of one id a thread met in a row of its walk
+  int id, e[6];
+};
+
+__device__ __forceinline__ void inst_flush(const InstRun& r, int* __restrict__ ext, int* __restrict__ hdr) {
+  if (r.id <= 0) return;
+  int* b = ext + (long long)r.id * 6;
+  atomicMin(b + 0, r.e[0]); atomicMin(b + 1, r.e[1]); atomicMin(b + 2, r.e[2]);
+  atomicMax(b + 3, r.e[3]); atomicMax(b + 4, r.e[4]); atomicMax(b + 5, r.e[5]);
+  atomicMin(hdr + 0, r.id);
+  atomicMax(hdr + 1, r.id);
+}
+
+// grid (x, N), grid-stride over the image's chunks of eight voxels.  VEC: V % 8 == 0 and seg 16-byte aligned.
+template <bool VEC>
+__global__ __launch_bounds__(DP_THREADS) void inst_extent_kernel(const short* __restrict__ seg, int V, int H, int W,
+                                                                 int* __restrict__ ext_all, int* __restrict__ hdr_all,
+                                                                 int* __restrict__ flags) {
+  typedef short short8v __attribute__((ext_vector_type(8)));
+  const int n = blockIdx.y;
+  const short* s = seg + (long long)n * V;
+  int* ext = ext_all + (long long)n * INST_IDS * 6;
+  int* hdr = hdr_all + n * INST_HDR;
+  const int chunks = (V + INST_VEC - 1) / INST_VEC;
+  InstRun run;
+  run.id = 0;
+  bool zero = false, bad = false;
+  const int stride = gridDim.x * DP_THREADS;
+  for (int c0 = blockIdx.x * DP_THREADS + threadIdx.x; c0 < chunks; c0 += INST_UNROLL * stride) {
+    short8v xs[INST_UNROLL];
+    if (VEC) {  // the loads of a round leave back to back, on clamped (always valid) chunks
+#pragma unroll
+      for (int u = 0; u < INST_UNROLL; ++u) {
+        const long long cu = (long long)c0 + (long long)u * stride;
+        xs[u] = *reinterpret_cast<const short8v*>(s + (cu < chunks ? cu : (long long)c0) * INST_VEC);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < INST_UNROLL; ++u) {
+      const long long cu = (long long)c0 + (long long)u * stride;
+      if (cu >= chunks) break;
+      const int o0 = (int)cu * INST_VEC;
+      short v[INST_VEC];
+      if (VEC) {
+#pragma unroll
+        for (int j = 0; j < INST_VEC; ++j) v[j] = xs[u][j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < INST_VEC; ++j) v[j] = o0 + j < V ? s[o0 + j] : (short)-1;  // -1 past the end: skipped below
+      }
+      int any = 0;
+#pragma unroll
+      for (int j = 0; j < INST_VEC; ++j) {
+        any |= v[j];
+        zero = zero || v[j] == 0;
+      }
+      if (any == 0) continue;  // background: one read and nothing else
+#pragma unroll 1
+      for (int j = 0; j < INST_VEC; ++j) {
+        const int id = v[j];
+        if (id == 0) continue;
+        if (id < 0) {
+          bad = bad || (o0 + j < V);
+          continue;
+        }
+        const int o = o0 + j;
+        const int x = o % W, y = (o / W) % H, z = o / (W * H);
+        if (id != run.id) {
+          inst_flush(run, ext, hdr);
+          run.id = id;
+          run.e[0] = run.e[3] = z; run.e[1] = run.e[4] = y; run.e[2] = run.e[5] = x;
+        } else {
+          run.e[0] = min(run.e[0], z); run.e[1] = min(run.e[1], y); run.e[2] = min(run.e[2], x);
+          run.e[3] = max(run.e[3], z); run.e[4] = max(run.e[4], y); run.e[5] = max(run.e[5], x);
+        }
+      }
+    }
+  }
+  inst_flush(run, ext, hdr);
+  const bool wz = __any(zero), wb = __any(bad);
+  if ((threadIdx.x & 63) == 0) {
+    if (wz) atomicMax(hdr + 2, 1);
+    if (wb) atomicMax(flags, 4);
+  }
+}
+
+// one workgroup: rows in (image, pair, ascending id) order.  The first unique value of an image is discarded: 0 where
+// there is background, the smallest id where there is none.
+__global__ __launch_bounds__(FIN_THREADS) void inst_final_kernel(const int* __restrict__ ext_all,
+                                                                 const int* __restrict__ hdr_all, InstPairs pairs, int N,
+                                                                 int D, int H, int W, int capacity,
+                                                                 float* __restrict__ boxes, long long* __restrict__ labels,
+                                                                 int* __restrict__ obj_off, const int* __restrict__ flags,
+                                                                 int* __restrict__ overflow) {
+  __shared__ int lds[33];
+  const float size[3] = {(float)D, (float)H, (float)W};
+  int carry = 0;
+  for (int n = 0; n < N; ++n) {
+    if (threadIdx.x == 0) obj_off[n] = carry < capacity ? carry : capacity;
+    const int* ext = ext_all + (long long)n * INST_IDS * 6;
+    const int lo_id = hdr_all[n * INST_HDR], hi_id = hdr_all[n * INST_HDR + 1];
+    const int lost = hdr_all[n * INST_HDR + 2] ? 0 : lo_id;
+    for (int pi = 0; pi < pairs.n; ++pi) {
+      const int lo = pairs.lo[pi] > 1 ? pairs.lo[pi] : 1;
+      const int hi = pairs.hi[pi] <= hi_id ? pairs.hi[pi] : hi_id + 1;  // exclusive; hi_id = -1 on an empty image
+      for (int b = lo; b < hi; b += FIN_THREADS) {
+        const int id = b + (int)threadIdx.x;
+        int keep = 0;
+        int e[6];
+        if (id < hi) {
+#pragma unroll
+          for (int j = 0; j < 6; ++j) e[j] = ext[(long long)id * 6 + j];
+          keep = id != lost && e[3] > e[0] && e[4] > e[1] && e[5] > e[2];  // absent ids have max -1 < min
+        }
+        int tot;
+        const int row = carry + block_excl_scan(keep, lds, &tot);
+        if (keep && row < capacity) {
+#pragma unroll
+          for (int j = 0; j < 6; ++j) boxes[(long long)row * 6 + j] = __fdiv_rn((float)e[j], size[j % 3]);
+          labels[row] = pi + 1;
+        }
+        carry += tot;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    obj_off[N] = carry < capacity ? carry : capacity;  // in bounds even on overflow (the flag says it happened)
+    *overflow = flags[0] | (carry > capacity ? 1 : 0);
+  }
+}
+
+size_t inst_ws_bytes(int N) { return ((size_t)N * INST_IDS * 6 + (size_t)N * INST_HDR + 4) * sizeof(int); }
+
+}  // namespace
+
+extern "C" {
+
+int msl_foreground_box(const float* vol, int D, int H, int W, int margin, int* box, void* stream) {
+  if (!vol || !box || D <= 0 || H <= 0 || W <= 0 || margin < 0) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long waves = ((long long)D * H + 3) / 4;
+  MSL_LAUNCH(fg_init_kernel, dim3(1), dim3(64), 0, st, box);
+  // the six atomics of every wave hit the same six words: few waves, many rows each
+  MSL_LAUNCH(fg_reduce_kernel, dim3((unsigned)(waves < 512 ? waves : 512)), dim3(FG_THREADS), 0, st, vol, D, H, W, box);
+  MSL_LAUNCH(fg_final_kernel, dim3(1), dim3(64), 0, st, D, H, W, margin, box);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int msl_augment_fit(const float* arena_img, const short* arena_seg, long long arena_elems, const long long* table,
+                    int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
+                    void* stream) {
+  if (!arena_img || !arena_seg || !table || !params || !dst_img || !dst_seg || arena_elems <= 0 || n_cases <= 0 ||
+      N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
+    return MSL_ERR_ARG;
+  const long long groups = (long long)T0 * T1 * ((T2 + FIT_VEC - 1) / FIT_VEC);
+  if (N > 65535 || (groups + DP_THREADS - 1) / DP_THREADS > 0x7FFFFFFFLL) return MSL_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((groups + DP_THREADS - 1) / DP_THREADS), N);
+  const bool vec = T2 % FIT_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
+  if (vec)
+    MSL_LAUNCH(fit_kernel<true>, grid, dim3(DP_THREADS), 0, (hipStream_t)stream, arena_img, arena_seg, arena_elems,
+               table, n_cases, params, T0, T1, T2, dst_img, dst_seg);
+  else
+    MSL_LAUNCH(fit_kernel<false>, grid, dim3(DP_THREADS), 0, (hipStream_t)stream, arena_img, arena_seg, arena_elems,
+               table, n_cases, params, T0, T1, T2, dst_img, dst_seg);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+size_t msl_instance_boxes_workspace_bytes(int N) { return N > 0 && N <= 65535 ? inst_ws_bytes(N) : 0; }
+
+int msl_instance_boxes(const short* seg, int N, int D, int H, int W, const int* thresholds, int n_pairs, int capacity,
+                       void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,
+                       int* overflow, void* stream) {
+  if (!seg || !thresholds || !workspace || !boxes || !labels || !obj_off || !overflow || capacity < 0) return MSL_ERR_ARG;
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || n_pairs <= 0) return MSL_ERR_ARG;
+  if (N > 65535 || n_pairs > INST_MAX_PAIRS || (long long)D * H * W >= 0x7FFFFFF0LL) return MSL_ERR_UNSUPPORTED;
+  if (workspace_bytes < inst_ws_bytes(N)) return MSL_ERR_ARG;
+  InstPairs pairs;
+  pairs.n = n_pairs;
+  for (int k = 0; k < INST_MAX_PAIRS; ++k) {  // the table is read here, on the host: it need not outlive the call
+    pairs.lo[k] = k < n_pairs ? thresholds[2 * k] : 0;
+    pairs.hi[k] = k < n_pairs ? thresholds[2 * k + 1] : 0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* ext = (int*)workspace;
+  int* hdr = ext + (size_t)N * INST_IDS * 6;
+  int* flags = hdr + (size_t)N * INST_HDR;
+  const int V = D * H * W;
+  const long long ext_words = (long long)N * INST_IDS * 6;
+  MSL_LAUNCH(inst_init_kernel, dim3(grid_for(ext_words)), dim3(DP_THREADS), 0, st, ext, ext_words, hdr, N, flags);
+  const int chunks = (V + INST_VEC - 1) / INST_VEC;
+  int gx = (chunks + DP_THREADS - 1) / DP_THREADS;
+  const int cap = (2048 + N - 1) / N;
+  if (gx > cap) gx = cap;
+  const bool vec = V % INST_VEC == 0 && ((uintptr_t)seg & 15) == 0;
+  if (vec)
+    MSL_LAUNCH(inst_extent_kernel<true>, dim3(gx, N), dim3(DP_THREADS), 0, st, seg, V, H, W, ext, hdr, flags);
+  else
+    MSL_LAUNCH(inst_extent_kernel<false>, dim3(gx, N), dim3(DP_THREADS), 0, st, seg, V, H, W, ext, hdr, flags);
+  MSL_LAUNCH(inst_final_kernel, dim3(1), dim3(FIN_THREADS), 0, st, (const int*)ext, (const int*)hdr, pairs, N, D, H, W,
+             capacity, boxes, labels, obj_off, (const int*)flags, overflow);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+}  // extern "C"

@@ -376,3 +376,215 @@ class ExampleDataset:
 
     def predict_dataloader(self):
         return self._loader(self.predict_dataset, False, 1)
+
+
+# ---- clinical cases: instance masks, foreground crop, fixed-size fit (reference datasets.py:125-335) ----------------
+# crop_foreground and resize_with_pad_or_crop restate MONAI's CropForegroundd / ResizeWithPadOrCropd, which are not
+# installed here: their parity is NOT pinned; the formulas in the docstrings are the contract.
+
+def foreground_box(img, margin=5):
+    """CropForegroundd(source_key="img", margin): F = {v : img[v] > 0}; per axis lo = max(min(F) - margin, 0),
+    hi = min(max(F) + margin + 1, n); an empty F keeps the whole volume.  -> (lo, hi), three ints each."""
+    img = np.asarray(img)
+    fg = np.argwhere(img > 0)
+    if fg.shape[0] == 0:
+        return (0,) * img.ndim, tuple(img.shape)
+    lo = np.maximum(fg.min(0) - margin, 0)
+    hi = np.minimum(fg.max(0) + margin + 1, img.shape)
+    return tuple(int(v) for v in lo), tuple(int(v) for v in hi)
+
+
+def crop_foreground(img, seg, margin=5):
+    """Image and mask (D, H, W) cropped to ``foreground_box(img, margin)``."""
+    lo, hi = foreground_box(img, margin)
+    sl = tuple(slice(a, b) for a, b in zip(lo, hi))
+    return img[sl], seg[sl]
+
+
+def fit_shift(n, t):
+    """resize_with_pad_or_crop on one axis of size n with target t: output index o reads source index
+    clamp(o + d, 0, n - 1) with d = -((t - n) // 2) when padding and d = n // 2 - t // 2 when cropping."""
+    return -((t - n) // 2) if n < t else n // 2 - t // 2
+
+
+def resize_with_pad_or_crop(vol, spatial_size):
+    """ResizeWithPadOrCropd(spatial_size, mode="replicate") on the trailing len(spatial_size) axes of ``vol``: per
+    axis, n < t pads by edge replication with before = (t - n) // 2, after = t - n - before; n > t keeps
+    [start, start + t) with start = n // 2 - t // 2."""
+    vol = np.asarray(vol)
+    first = vol.ndim - len(spatial_size)
+    for k, t in enumerate(spatial_size):
+        n = vol.shape[first + k]
+        idx = np.clip(np.arange(t) + fit_shift(n, t), 0, n - 1)
+        vol = np.take(vol, idx, axis=first + k)
+    return vol
+
+
+def boxes_from_instances(seg, thresholds, mode="instances"):
+    """BoundingBoxesGeneratord, 'instances' mode (utils.py:442-443, 472-481, 485-513) on an instance-labelled mask: the
+    ids are the sorted unique values with the FIRST one discarded (the background - on a mask without background the
+    smallest id is lost, as in the reference); per threshold pair (lo, hi) in order, the ids with lo <= id < hi give
+    the inclusive voxel extents [min..., max...] and the label is the pair's position + 1; ids outside every pair are
+    dropped; extents / image size in f32; zero-volume boxes removed.  ``mode="binary"`` (utils.py:445-448): connected
+    components of the mask first, then thresholds [(1, inf)]."""
+    seg = np.squeeze(np.asarray(seg))
+    if mode == "binary":
+        seg, _ = cc_label(seg)
+        thresholds = [(1, np.inf)]
+    elif mode != "instances":
+        raise ValueError(f"unknown segmentation mode {mode!r}")
+    size = np.array(seg.shape * 2, dtype=np.float32)
+    ids = np.unique(seg)[1:]
+    boxes, labels = [], []
+    for c, (lo, hi) in enumerate(thresholds):
+        for l in ids[(ids >= lo) & (ids < hi)]:
+            idx = np.where(seg == l)
+            boxes.append([idx[0].min(), idx[1].min(), idx[2].min(), idx[0].max(), idx[1].max(), idx[2].max()])
+            labels.append(c + 1)
+    boxes = torch.from_numpy(np.asarray(boxes, dtype=np.float32).reshape(-1, 6) / size)
+    labels = torch.tensor(labels, dtype=torch.long)
+    if boxes.numel():
+        keep = ((boxes[:, 3] - boxes[:, 0]) * (boxes[:, 4] - boxes[:, 1]) * (boxes[:, 5] - boxes[:, 2])) != 0
+        boxes, labels = boxes[keep], labels[keep]
+    return boxes, labels
+
+
+def normalize_nonzero(img):
+    """NormalizeIntensity(nonzero=True) as ``_Cases`` applies it: population mean / std over the non-zero voxels."""
+    img = np.array(img, dtype=np.float32)
+    nz = img != 0
+    if nz.any():
+        std = img[nz].std()
+        img[nz] = (img[nz] - img[nz].mean()) / (std if std != 0 else 1.0)
+    return img
+
+
+class _LesionCases(Dataset):
+    """The per-sample pipeline of LesionsDataModule (datasets.py:199-236): load -> crop_foreground(margin 5) ->
+    NormalizeIntensity(nonzero) -> training augmentations at the cropped shape -> resize_with_pad_or_crop(replicate) ->
+    boxes ('instances' / 'binary' mode)."""
+
+    def __init__(self, module, subjects, augmentations=None, seed=0):
+        self.module, self.subjects = module, list(subjects)
+        self.root = module.data_dir  # the key DeviceCache-style caches file a case under, with its subject
+        self.augmentations = list(augmentations or [])
+        for t in self.augmentations:
+            if (t if isinstance(t, str) else t[0]) not in AUGMENTATIONS:
+                raise ValueError(f"unknown transform {t!r}")
+        self.seed, self.epoch = seed, 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def sample_rng(self, i):
+        return sample_rng(self.seed, self.epoch, self.subjects[i])
+
+    def __len__(self):
+        return len(self.subjects)
+
+    def load(self, i):
+        """-> (image f32, mask) of case i as stored, (D, H, W) each."""
+        m = self.module
+        c, s = self.subjects[i]
+        img = _load(m._get_sequence(c, s, m.input_images[0])).astype(np.float32)
+        seg = np.asarray(_load(m._get_sequence(c, s, m.segmentation)))
+        if img.ndim != 3 or seg.shape != img.shape:
+            raise ValueError(f"case {(c, s)}: image {img.shape} and mask {seg.shape} must be one 3-D shape")
+        return img, seg
+
+    def __getitem__(self, i):
+        m = self.module
+        img, seg = crop_foreground(*self.load(i), margin=m.margin)
+        img = normalize_nonzero(img)
+        img, seg = img[None], seg[None]  # add_channel
+        rs = self.sample_rng(i) if self.augmentations else None
+        for t in self.augmentations:
+            name, kw = (t, {}) if isinstance(t, str) else t
+            img, seg = AUGMENTATIONS[name](img, seg, rs, **kw)
+        img = np.ascontiguousarray(resize_with_pad_or_crop(img, m.spatial_size))
+        seg = resize_with_pad_or_crop(seg, m.spatial_size)
+        boxes, labels = boxes_from_instances(seg, m.thresholds, m.segmentation_mode)
+        return {"img": torch.from_numpy(img), "boxes": boxes, "labels": labels, "seg": [boxes, labels],
+                "subject": self.subjects[i], "img_meta_dict": {"affine": np.eye(4)}, "seg_meta_dict": {},
+                "img_transforms": [], "seg_transforms": []}
+
+
+class LesionsDataModule(ExampleDataset):
+    """datasets.py:125-335 surface, the ``ExampleDataset`` way: ``setup(stage)``, ``set_epoch``, ``train_dataloader()``,
+    ``test_dataloader()``, ``predict_dataloader()``, ``train_dataset`` / ``test_dataset`` / ``predict_dataset``.
+
+    Files follow the reference's BIDS layout (``_get_data_dir`` / ``_get_sequence``) and are read through ``_load``
+    (``.npy`` first, ``.nii.gz`` with nibabel).  Subjects are the sorted (center, subject) pairs (the reference's
+    ``os.listdir`` order is not portable), split 80 / 20 by ``train_test_split(random_state)``.  A segmentation name
+    with "labeled" in it is instance-labelled ('instances' mode, thresholds [(1, inf)] for one class and
+    [(1000, 2000), (2000, inf)] for two); any other name is a binary mask ('binary' mode, one class).
+
+    Left out: ``fold`` (the reference indexes a list with an index array there and cannot run) and ``orientation`` /
+    ``spacing``, which need NIfTI affines: the volumes must already be LPI at 1 mm.  Not in the reference:
+    ``spatial_size`` (its fixed (250, 300, 300)), ``rank`` / ``world_size`` (this process's data-parallel shard)."""
+
+    margin = 5  # crop_foreground
+
+    def __init__(self, data_dir="../data/raw", centers=("CHUV_RIM_OK", "BASEL_INSIDER_OK"), input_images=("FLAIR",),
+                 segmentation="labeled_lesions", classes=("lesion",), registration="T2star", skullstripped=True,
+                 augmentations=None, subject=None, batch_size=8, percentage=1., num_workers=0, random_state=970205,
+                 cache=False, spatial_size=(250, 300, 300), rank=0, world_size=1):
+        if len(input_images) != 1:
+            raise NotImplementedError("Only supports one sequence at a time.")
+        self.data_dir, self.centers, self.registration = data_dir, tuple(centers), registration
+        self.input_images, self.segmentation, self.skullstripped = tuple(input_images), segmentation, skullstripped
+        self.classes, self.n_classes = tuple(classes), len(classes)
+        self.batch_size, self.num_workers, self.random_state = batch_size, num_workers, random_state
+        self.augmentations, self.subject, self.percentage, self.cache = augmentations, subject, percentage, cache
+        self.spatial_size = tuple(int(t) for t in spatial_size)
+        if len(self.spatial_size) != 3 or min(self.spatial_size) <= 0:
+            raise ValueError(f"spatial_size must be three positive sizes, got {spatial_size}")
+        self.rank, self.world_size, self.epoch = rank, world_size, 0
+        self.segmentation_mode = "instances" if "labeled" in segmentation else "binary"
+        if self.segmentation_mode == "binary":
+            if self.n_classes != 1:
+                raise ValueError("a binary mask carries one class")
+            self.thresholds = [(1, np.inf)]
+        elif self.n_classes == 1:
+            self.thresholds = [(1, np.inf)]
+        elif self.n_classes == 2:
+            self.thresholds = [(1000, 2000), (2000, np.inf)]
+        else:
+            raise ValueError(f"one or two classes, got {self.n_classes}")
+        subs = []
+        for c in self.centers:
+            subs += [(c, s.replace("sub-", "")) for s in os.listdir(self._get_data_dir(c)) if "sub-" in s]
+        subs = sorted(subs)
+        self.subjects_list = subs[:int(percentage * len(subs))] if percentage > 0 else subs
+        self.train_dataset = self.test_dataset = self.predict_dataset = None
+
+    def _get_data_dir(self, center):
+        """The BIDS directory of a center (datasets.py:238-243)."""
+        dd = pjoin(self.data_dir, center)
+        if self.registration is not None:
+            dd = pjoin(dd, "derivatives", "registrations", f"registrations_to_{self.registration}")
+        return dd
+
+    def _get_sequence(self, center, subject, img_name):
+        """Path of an image or a segmentation without its extension (datasets.py:245-259)."""
+        if img_name in ("FLAIR", "acq-phase_T2star", "acq-mag_T2star"):
+            if not self.skullstripped:
+                return pjoin(self._get_data_dir(center), f"sub-{subject}", "ses-01", "anat",
+                             f"sub-{subject}_ses-01_{img_name}")
+            return pjoin(self._get_data_dir(center), "derivatives", "skullstripped", f"sub-{subject}", "ses-01",
+                         f"sub-{subject}_ses-01_{img_name}")
+        return pjoin(self._get_data_dir(center), "derivatives", "lesionmasks", f"sub-{subject}", "ses-01",
+                     f"sub-{subject}_ses-01_{img_name}")
+
+    def setup(self, stage=None):
+        from sklearn.model_selection import train_test_split
+        if self.subject is not None:
+            one = tuple(self.subject) if not isinstance(self.subject, str) else \
+                next(cs for cs in self.subjects_list if cs[1] == self.subject)
+            train, test = [one], [one]
+        else:
+            train, test = train_test_split(self.subjects_list, train_size=0.8, test_size=0.2,
+                                           random_state=self.random_state)
+        self.train_dataset = _LesionCases(self, train, self.augmentations, self.random_state)
+        self.test_dataset = _LesionCases(self, test)
+        self.predict_dataset = _LesionCases(self, train if stage == "predict_train" else test)

@@ -11,6 +11,10 @@ Limits: rot90 on an axis pair of unequal sizes (a shape-changing rotation) raise
 order is the reference's - flips / rot90s, then affines, then shiftintensity / scaleintensity: a flip / rot90 placed
 after an affine stage or an intensity operation, an affine placed after an intensity operation and more than
 AFFINE_MAX_OPS intensity operations raise NotImplementedError.
+
+``LesionCache`` is the counterpart for ``datasets.LesionsDataModule``: cases of unequal shape, cropped to their
+foreground, in one flat arena; shape-changing rot90s allowed; every batch padded / cropped to one fixed size and its
+instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes).
 """
 from collections import namedtuple
 
@@ -99,14 +103,16 @@ def boxes_from_segmentation_device(seg, n_classes=1, capacity=None, comp_cap=Non
     return boxes, labels, (out.gb, out.gl, out.obj_off, capacity)
 
 
-def sample_params(draws, shape, augmentations=None):
+def sample_params(draws, shape, augmentations=None, ragged=False):
     """One sample's draws (``datasets.draw_augmentations``) -> (signed axis permutation, [stages]).
 
     The permutation is (axis, rev): output axis a reads source axis axis[a], reversed iff rev[a]; it composes the flips
     and rot90s exactly as np.flip / np.rot90 index.  ``augmentations`` is the transform list the draws were made from (it
     holds each affine's ``padding_mode``; without it, reflection).  There is one stage per affine / intensity entry, in
     list order: None (not drawn), (zoom, offset) in f64 for a diagonal affine with reflection padding (the stage
-    msl_augment_resample runs), ``AffineStage`` for a rotating affine or another boundary, ``IntensityOp``."""
+    msl_augment_resample runs), ``AffineStage`` for a rotating affine or another boundary, ``IntensityOp``.
+    ``ragged`` (msl_augment_fit): a rot90 may change the shape, and every affine stage is an ``AffineStage`` computed
+    for the permuted shape."""
     axis, rev = [0, 1, 2], [0, 0, 0]
     stages = []
     n_ops = 0
@@ -123,10 +129,10 @@ def sample_params(draws, shape, augmentations=None):
             pad = ({} if isinstance(t, str) else t[1]).get("padding_mode", "reflection")
             if d is None:
                 stages.append(None)
-            elif len(d) == 2 and pad == "reflection":
+            elif len(d) == 2 and pad == "reflection" and not ragged:
                 stages.append((list(d[0]), list(affine_offset(shape, *d))))
-            else:
-                stages.append(AffineStage(*affine_matrix(shape, *d), BOUNDARY[pad]))
+            else:  # flips / rot90s come first: the permutation is final, and it keeps the shape unless ragged
+                stages.append(AffineStage(*affine_matrix(tuple(shape[a] for a in axis), *d), BOUNDARY[pad]))
             continue
         if name in ("shiftintensity", "scaleintensity"):
             n_ops += 1
@@ -150,7 +156,7 @@ def sample_params(draws, shape, augmentations=None):
                 rev[a] ^= 1
         else:  # np.rot90(m, k, (a, b)): k=1 transpose(flip(m, b)), k=2 flip both, k=3 flip(transpose(m), b)
             k, (a, b) = d[0] % 4, d[1]
-            if shape[a] != shape[b]:
+            if not ragged and shape[axis[a]] != shape[axis[b]]:
                 raise NotImplementedError(f"device pipeline: rot90 over axes {(a, b)} of sizes {shape[a]} != {shape[b]}")
             if k == 1:
                 rev[b] ^= 1
@@ -417,6 +423,224 @@ class DeviceCache:
                                   resident=True, metrics=metrics)
         batch["_box"].raise_on_overflow()
         return out
+
+    def val_batches(self):
+        """``validation_step`` batches (device tensors, per-image box lists) of this rank's validation shard."""
+        ident = (([0, 1, 2], [0, 0, 0]), [])
+        for i0 in range(0, len(self.val_order), self.batch_size):
+            chunk = self.val_order[i0:i0 + self.batch_size]
+            b = self._buffers(len(chunk))
+            self._run([slot for _, slot in chunk], [ident] * len(chunk), b)
+            box = b["box"]
+            off = box.obj_off.cpu().tolist()
+            box.raise_on_overflow(box.flag.item())
+            boxes = [box.gb[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
+            labels = [box.gl[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
+            yield {"img": b["img"].clone(), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
+                   "subject": [s for s, _ in chunk]}
+
+
+# ---- clinical cases: ragged sources, instance masks (datasets.LesionsDataModule) ---------------------------------------
+INT_MAX = 2 ** 31 - 1
+
+
+def threshold_table(thresholds):
+    """[(lo, hi), ...] with hi possibly inf -> (n, 2) int32 array for msl_instance_boxes (inf = INT_MAX)."""
+    t = np.array([[min(float(lo), INT_MAX), min(float(hi), INT_MAX)] for lo, hi in thresholds], dtype=np.float64)
+    if t.ndim != 2 or t.shape[0] < 1 or not np.array_equal(t, np.floor(t)):
+        raise ValueError(f"integer threshold pairs expected, got {thresholds}")
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+class _InstBoxOut:
+    """Packed targets + workspace of msl_instance_boxes for one (N, D, H, W, thresholds, capacity)."""
+
+    def __init__(self, N, shape, thresholds, capacity, dev):
+        lib = _lib.load()
+        self.N, self.shape, self.capacity = N, tuple(shape), capacity
+        self.thr = threshold_table(thresholds)  # host table, read during every call
+        nbytes = lib.msl_instance_boxes_workspace_bytes(N)
+        if nbytes == 0:
+            raise _lib.HipKernelError(f"msl_instance_boxes: unsupported batch size N={N}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.gb = torch.zeros((max(capacity, 1), 6), dtype=torch.float32, device=dev)
+        self.gl = torch.ones(max(capacity, 1), dtype=torch.int64, device=dev)
+        self.obj_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.flag_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+
+    def launch(self, seg, stream):
+        _lib.call("msl_instance_boxes", ptr(seg), self.N, *self.shape, self.thr.ctypes.data, self.thr.shape[0],
+                  self.capacity, ptr(self.ws), self.ws.numel(), ptr(self.gb), ptr(self.gl), ptr(self.obj_off),
+                  ptr(self.flag), stream)
+        self.flag_host.copy_(self.flag, non_blocking=True)  # read after the next synchronising read: no sync of its own
+
+    def raise_on_overflow(self, flag=None):
+        f = int(self.flag_host.item() if flag is None else flag)
+        if f & 1:
+            raise _lib.HipKernelError(f"msl_instance_boxes: a batch holds more ground-truth boxes than the capacity of "
+                                      f"{self.capacity} rows")
+        if f & 4:
+            raise _lib.HipKernelError("msl_instance_boxes: a mask holds a negative value")
+
+
+def boxes_from_instances_device(seg, thresholds, capacity=None):
+    """``datasets.boxes_from_instances`` ('instances' mode) for every image of a device int16 (N, D, H, W) mask ->
+    (boxes list, labels list, (gb, gl, obj_off, capacity)) as ``boxes_from_segmentation_device`` returns them."""
+    if not seg.is_cuda or seg.dtype != torch.int16 or seg.dim() != 4:
+        raise _lib.HipKernelError("boxes_from_instances_device takes an int16 (N, D, H, W) tensor on the HIP device")
+    seg = seg.contiguous()
+    N = seg.shape[0]
+    capacity = 1024 * N if capacity is None else int(capacity)
+    out = _InstBoxOut(N, seg.shape[1:], thresholds, capacity, seg.device)
+    out.launch(seg, _stream(seg.device))
+    off = out.obj_off.cpu().tolist()
+    out.raise_on_overflow(out.flag.item())
+    return ([out.gb[off[n]:off[n + 1]] for n in range(N)], [out.gl[off[n]:off[n + 1]] for n in range(N)],
+            (out.gb, out.gl, out.obj_off, capacity))
+
+
+def fit_rows(cases, per_sample):
+    """-> (N, AFFINE_STRIDE) f64 rows of one msl_augment_fit launch: per sample its case and the (perm, stages) of
+    ``sample_params(..., ragged=True)``: at most one affine stage, then the intensity operations."""
+    rows = np.zeros((len(cases), AFFINE_STRIDE), dtype=np.float64)
+    for n, (case, (perm, stages)) in enumerate(zip(cases, per_sample)):
+        geo = [st for st in stages if not isinstance(st, IntensityOp)]
+        if len(geo) > 1:
+            raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
+        rows[n] = affine_row(case, perm, geo[0] if geo else None, [st for st in stages if isinstance(st, IntensityOp)])
+    return rows
+
+
+class LesionCache:
+    """The cases of a ``setup()`` ``datasets.LesionsDataModule`` in HBM, cropped to their foreground and normalised: one
+    flat arena of f32 images and one of int16 masks with a per-case (offset, shape) table, and the device pipeline that
+    turns them into fixed-size training / validation batches (msl_augment_fit, msl_instance_boxes).
+
+    Same semantics as ``DeviceCache``: ``train_batches(epoch)`` yields the batches of ``dataset.train_dataloader()`` for
+    that epoch (same subjects, same draws) in fixed buffers, ``step(trainer, batch)`` trains on one, ``val_batches()``
+    yields ``validation_step`` batches.  At construction every case is uploaded once, boxed by msl_foreground_box (the
+    six ints are the build's only read-back), cropped into the arena and normalised there; the cropped cases are staged
+    in tensors of their own until the arena's size is known.  A pipeline with two affine stages raises
+    NotImplementedError (a resample of a resample of a ragged case would need a ragged intermediate)."""
+
+    def __init__(self, dataset, device, max_objects_per_image=64):
+        if dataset.train_dataset is None:
+            raise ValueError("LesionCache needs a data module after setup()")
+        self.dataset, self.device = dataset, torch.device(device)
+        self.batch_size, self.target = int(dataset.batch_size), tuple(dataset.spatial_size)
+        self.augmentations = list(dataset.train_dataset.augmentations)
+        names = [(t if isinstance(t, str) else t[0]) for t in self.augmentations]
+        if names.count("affine") > 1:
+            raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
+        sample_params([(n, None) for n in names], (1, 1, 1), self.augmentations, ragged=True)  # the order limits
+        if dataset.segmentation_mode != "instances":
+            raise NotImplementedError("LesionCache: the device pipeline labels instance masks ('labeled' segmentations)")
+        tr, te = dataset.train_dataset, dataset.test_dataset
+        if dataset.world_size > 1:
+            val_idx = ShardSampler(len(te), dataset.rank, dataset.world_size, False, dataset.random_state).indices()
+        else:
+            val_idx = np.arange(len(te))
+        self.slot = {}
+        loaders = []
+        for ds, idx in ((tr, range(len(tr))), (te, val_idx)):
+            for i in idx:
+                if ds.subjects[i] not in self.slot:
+                    self.slot[ds.subjects[i]] = len(self.slot)
+                    loaders.append((ds, int(i)))
+        self.train_slots = [self.slot[s] for s in tr.subjects]
+        self.val_order = [(te.subjects[i], self.slot[te.subjects[i]]) for i in val_idx]
+        dev, stream = self.device, _stream(self.device)
+        box = torch.zeros(6, dtype=torch.int32, device=dev)
+        staged, self.shapes = [], []
+        for ds, i in loaders:
+            img, seg = ds.load(i)
+            seg16 = seg.astype(np.int16)
+            if not np.array_equal(seg16, seg) or (seg16.size and seg16.min() < 0):
+                raise ValueError(f"LesionCache: mask of case {ds.subjects[i]} is not integer-valued in [0, 32767]")
+            self._check_memory(img.size * 6, f"case {ds.subjects[i]} of {img.shape}")
+            vol = torch.from_numpy(img).to(dev)
+            _lib.call("msl_foreground_box", ptr(vol), *img.shape, int(dataset.margin), ptr(box), stream)
+            b = box.cpu().tolist()  # the one read that sizes the crop
+            sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
+            staged.append((vol[sl].contiguous(), torch.from_numpy(seg16).to(dev)[sl].contiguous()))
+            self.shapes.append(tuple(b[3 + a] - b[a] for a in range(3)))
+            del vol
+        sizes = [int(np.prod(s)) for s in self.shapes]
+        self.offsets = [0] + np.cumsum(sizes).tolist()
+        self.cache_bytes = self.offsets[-1] * 6
+        self._check_memory(self.cache_bytes, f"{len(sizes)} cropped cases")
+        self.img = torch.empty(max(self.offsets[-1], 1), dtype=torch.float32, device=dev)
+        self.seg = torch.empty(max(self.offsets[-1], 1), dtype=torch.int16, device=dev)
+        for k in range(len(sizes)):
+            ci, cs = staged[k]
+            staged[k] = None
+            self.img[self.offsets[k]:self.offsets[k + 1]].copy_(ci.reshape(-1))
+            self.seg[self.offsets[k]:self.offsets[k + 1]].copy_(cs.reshape(-1))
+            if sizes[k]:
+                _lib.call("msl_normalize_nonzero", self.img.data_ptr() + 4 * self.offsets[k], 1, sizes[k], stream)
+        self.table = torch.tensor([[self.offsets[k], *self.shapes[k]] for k in range(len(sizes))],
+                                  dtype=torch.int64, device=dev).reshape(-1, 4)
+        self.capacity = int(max_objects_per_image) * self.batch_size
+        self._bufs = {}
+
+    def _check_memory(self, nbytes, what):
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if nbytes > 0.8 * free:
+            raise MemoryError(f"LesionCache: {what} need {nbytes / 2**30:.2f} GiB, {free / 2**30:.2f} GiB free on "
+                              f"{self.device}")
+
+    def case(self, slot):
+        """-> (image f32, mask int16) views of a cached case, shaped."""
+        a, b = self.offsets[slot], self.offsets[slot + 1]
+        return self.img[a:b].view(self.shapes[slot]), self.seg[a:b].view(self.shapes[slot])
+
+    # ---- footprint ----------------------------------------------------------------------------------------------------
+    def nbytes(self):
+        """Device bytes held: the cached cases plus every batch buffer set allocated so far."""
+        n = self.cache_bytes
+        for b in self._bufs.values():
+            n += sum(t.numel() * t.element_size() for t in (b["img"], b["seg"], b["box"].ws, b["box"].gb, b["box"].gl))
+        return n
+
+    def footprint(self):
+        lo, hi = np.min(self.shapes, 0).tolist(), np.max(self.shapes, 0).tolist()
+        return (f"LesionCache: {len(self.shapes)} cases of {tuple(lo)} .. {tuple(hi)} fitted to {self.target} on "
+                f"{self.device}: {self.cache_bytes / 2**20:.1f} MiB cached, {self.nbytes() / 2**20:.1f} MiB with batch "
+                f"buffers")
+
+    # ---- the pipeline -------------------------------------------------------------------------------------------------
+    def _buffers(self, N):
+        b = self._bufs.get(N)
+        if b is None:
+            dev = self.device
+            b = self._bufs[N] = {"img": torch.empty((N, 1) + self.target, dtype=torch.float32, device=dev),
+                                 "seg": torch.empty((N,) + self.target, dtype=torch.int16, device=dev),
+                                 "box": _InstBoxOut(N, self.target, self.dataset.thresholds, self.capacity, dev)}
+        return b
+
+    def _run(self, slots, per_sample, b):
+        stream = _stream(self.device)
+        rows = fit_rows(slots, per_sample)
+        pd = torch.from_numpy(rows.reshape(-1)).pin_memory().to(self.device, non_blocking=True)
+        _lib.call("msl_augment_fit", ptr(self.img), ptr(self.seg), self.img.numel(), ptr(self.table), len(self.shapes),
+                  ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
+        b["box"].launch(b["seg"], stream)
+
+    def train_batches(self, epoch):
+        tr = self.dataset.train_dataset
+        for idx in train_batch_order(self.dataset, epoch):
+            per_sample = []
+            for i in idx:
+                draws = draw_augmentations(self.augmentations, sample_rng(tr.seed, epoch, tr.subjects[i])) \
+                    if self.augmentations else []
+                per_sample.append(sample_params(draws, self.shapes[self.train_slots[i]], self.augmentations, ragged=True))
+            b = self._buffers(len(idx))
+            self._run([self.train_slots[i] for i in idx], per_sample, b)
+            yield {"img": b["img"], "seg": b["seg"], "gb": b["box"].gb, "gl": b["box"].gl, "obj_off": b["box"].obj_off,
+                   "capacity": self.capacity, "subject": [tr.subjects[i] for i in idx], "_box": b["box"]}
+
+    step = DeviceCache.step
 
     def val_batches(self):
         """``validation_step`` batches (device tensors, per-image box lists) of this rank's validation shard."""

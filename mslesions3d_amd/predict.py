@@ -31,6 +31,10 @@ def build_parser():
     p.add_argument('-o', '--output_dir', type=str, default=r"../data/predictions/")
     # not in the reference's CLI: bf16 activations for the eval forward (fp32 is the reference's precision)
     p.add_argument('--dtype', type=str, choices=['f32', 'bf16'], default='f32')
+    # the clinical data module (datasets.LesionsDataModule): -d is its data_dir; files are named <center>_<subject>
+    p.add_argument('-dm', '--data_module', choices=["example", "lesions"], default="example")
+    p.add_argument('--centers', type=str, nargs='+', default=['CHUV_RIM_OK', 'BASEL_INSIDER_OK'])
+    p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
     return p
 
 
@@ -82,7 +86,7 @@ def gather_detections(records, world, rank):
 def predict_example(args):
     """predict.py:235-281.  Under ``python -m torch.distributed.run --nproc-per-node N -m mslesions3d_amd.predict ...`` the
     subjects are dealt round-robin over N replicas (one GPU each) and rank 0 writes the files and the metrics."""
-    from .datasets import ExampleDataset, ShardSampler
+    from .datasets import ExampleDataset, LesionsDataModule, ShardSampler
     from .ssd3d import LSSD3D
     from .utils import calculate_mAP
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
@@ -96,8 +100,14 @@ def predict_example(args):
     dev = torch.device("cuda", local)
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
-    dataset = ExampleDataset(n_classes=args.n_classes, batch_size=1, num_workers=args.num_workers, subject=args.subject,
-                             percentage=args.percentage, data_dir=args.dataset_path, dataset_name=args.dataset_name)
+    if getattr(args, "data_module", "example") == "lesions":
+        dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), batch_size=1,
+                                    classes=("lesion",) if args.n_classes == 1 else ("lesion", "lesion_2"),
+                                    num_workers=args.num_workers, subject=args.subject, percentage=args.percentage,
+                                    spatial_size=tuple(args.spatial_size))
+    else:
+        dataset = ExampleDataset(n_classes=args.n_classes, batch_size=1, num_workers=args.num_workers, subject=args.subject,
+                                 percentage=args.percentage, data_dir=args.dataset_path, dataset_name=args.dataset_name)
     dataset.setup(stage="predict_train" if args.predict_subset == "train" else "predict")
     model = LSSD3D.load_from_checkpoint(args.model_path, min_score=args.min_score).to(dev).eval()
     model.top_k, model.min_score = args.top_k, args.min_score  # predict.py:259-260
@@ -115,7 +125,8 @@ def predict_example(args):
 
     for boxes, labels, scores in model.predict_batches(feed(), depth=2):
         pos, batch = queued.popleft()
-        records.append((pos, batch["subject"][0],
+        subj = batch["subject"][0]
+        records.append((pos, subj if isinstance(subj, str) else "_".join(subj),
                         {"shape": tuple(batch["img"].shape[2:]), "boxes": boxes[0].cpu().numpy().tolist(),
                          "labels": labels[0].cpu().numpy().tolist(), "scores": scores[0].cpu().numpy().tolist(),
                          "gt_boxes": batch["boxes"][0].numpy().tolist(), "gt_labels": batch["labels"][0].numpy().tolist()}))

@@ -59,6 +59,11 @@ def build_parser():
     # train.py:51 of the reference (MONAI CacheDataset): 1 = cases normalised once into HBM, every batch augmented and
     # labelled into boxes on the device (devicedata.DeviceCache)
     p.add_argument('-c', '--cache', type=int, default=0)
+    # train_lesions() (train.py:191-241 of the reference): the clinical data module instead of the synthetic cubes; -d is its
+    # data_dir, -c 1 keeps the cropped cases in HBM (devicedata.LesionCache)
+    p.add_argument('-dm', '--data_module', choices=["example", "lesions"], default="example")
+    p.add_argument('--centers', type=str, nargs='+', default=['CHUV_RIM_OK', 'BASEL_INSIDER_OK'])
+    p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
     return p
 
 
@@ -89,7 +94,7 @@ def example(args):
     its shard of the cases (``datasets.ShardSampler``; BatchNorm statistics and the loss normaliser per replica), exchanges
     gradients through ``FusedTrainer``'s bucketed RCCL all-reduce overlapped with the backward pass, validates its shard of
     the validation cases, and rank 0 writes metrics and checkpoints.  N = 1 is the reference's single-GPU run."""
-    from .datasets import ExampleDataset, select_augmentations
+    from .datasets import ExampleDataset, LesionsDataModule, select_augmentations
     from .ssd3d import LSSD3D
     from .trainer import FusedTrainer
     world, rank, local = _dist_env()
@@ -107,10 +112,18 @@ def example(args):
     aspect_ratios = {l: [1.] for l in layers}
     scales = {int(k): v for k, v in args.scales.items()}
     augmentations = select_augmentations(args.augmentations)  # train.py:132-145, :196-205
-    dataset = ExampleDataset(n_classes=args.n_classes, subject=args.subject, percentage=args.percentage,
-                             num_workers=args.num_workers, batch_size=args.batch_size, data_dir=args.dataset_path,
-                             dataset_name=args.dataset_name, augmentations=augmentations, random_state=970205,
-                             rank=rank, world_size=world)
+    lesions = getattr(args, "data_module", "example") == "lesions"
+    if lesions:
+        dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), subject=args.subject,
+                                    classes=("lesion",) if args.n_classes == 1 else ("lesion", "lesion_2"),
+                                    percentage=args.percentage, num_workers=args.num_workers, batch_size=args.batch_size,
+                                    augmentations=augmentations, random_state=970205,
+                                    spatial_size=tuple(args.spatial_size), rank=rank, world_size=world)
+    else:
+        dataset = ExampleDataset(n_classes=args.n_classes, subject=args.subject, percentage=args.percentage,
+                                 num_workers=args.num_workers, batch_size=args.batch_size, data_dir=args.dataset_path,
+                                 dataset_name=args.dataset_name, augmentations=augmentations, random_state=970205,
+                                 rank=rank, world_size=world)
     dataset.setup(stage="fit")
     input_size = tuple(dataset.train_dataset[0]["img"].shape)[1:]
     threshold = args.threshold if len(args.threshold) > 1 else [args.threshold[0]]
@@ -135,8 +148,8 @@ def example(args):
     trainer = FusedTrainer(model)
     cache = None
     if args.cache:
-        from .devicedata import DeviceCache
-        cache = DeviceCache(dataset, dev)
+        from .devicedata import DeviceCache, LesionCache
+        cache = LesionCache(dataset, dev) if lesions else DeviceCache(dataset, dev)
         if rank == 0:
             print(cache.footprint())
     first_epoch = 0

@@ -1,7 +1,9 @@
 """Per-kernel parity on a real MI355X: every C-ABI entry point against stock torch fp32 ops on the CPU
 (the same third-party arithmetic the reference calls).  Tolerances are stated per test; integer outputs exact.
 The BatchNorm family (msl_bn_*) has one smoke-level test here; tests/test_gpu_bn.py walks every code path of those kernels
-against a float64 reference with derived bounds."""
+against a float64 reference with derived bounds.  Likewise the fp32 pointwise convolution (msl_pwconv_*): test_pw_fwd_bwd and
+test_pw_random_shapes here compare with torch fp32 under stated tolerances; tests/test_gpu_pw.py walks every dispatch branch and
+template instantiation of csrc/pwconv.hip / csrc/pwfused.hip against the float64 reference of tests/pw_ref.py."""
 import numpy as np
 import pytest
 import torch

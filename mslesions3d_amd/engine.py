@@ -11,6 +11,7 @@ Data convention: conv kernels write RAW outputs + fp64 statistic partials; ``msl
 a per-channel (scale, shift); the next kernel applies relu(x*scale+shift) while loading.  Only the three
 feature maps the heads read are materialised (in a zero-haloed layout).
 """
+import ctypes
 import os
 
 import torch
@@ -121,14 +122,20 @@ class ParamArena:
 
 
 class Plan:
-    """Buffers + static shape data for one (batch, input size, mode)."""
+    """Buffers + static shape data for one (batch, input size, mode, storage type).  ``dtype`` ("f32" / "bf16",
+    ``LSSD3D.compute_dtype``) is how raw convolution outputs and activation gradients are stored in HBM; weights, BatchNorm
+    vectors / statistics, head inputs and outputs and weight-gradient sums are fp32 / fp64 either way.  What the bf16 step
+    lays out differently is in the branches on ``bf16`` below; every other line serves both."""
 
-    def __init__(self, engine, N, in_dims, device, need_grad):
+    def __init__(self, engine, N, in_dims, device, need_grad, dtype="f32"):
         L = _lib.load()
-        m = engine.model
-        self.N, self.in_dims, self.need_grad = N, tuple(in_dims), need_grad
+        m, specs = engine.model, engine.layer_specs
+        ncls = m.n_classes
+        bf16 = dtype == "bf16"
+        self.N, self.in_dims, self.need_grad, self.bf16 = N, tuple(in_dims), need_grad, bf16
+        act = dict(dtype=torch.bfloat16 if bf16 else torch.float32, device=device)  # y, z, g_y, g_z
         f32 = dict(dtype=torch.float32, device=device)
-        specs = engine.layer_specs
+        f64 = dict(dtype=torch.float64, device=device)
         self.dims = []  # output dims per feature index
         cur = tuple(in_dims)
         for sp in specs:
@@ -136,35 +143,11 @@ class Plan:
             self.dims.append(cur)
         self.y = []   # raw conv output of feature i (stem conv / block pointwise)
         self.z = [None]  # raw depthwise output of block i
-        self.bn_y = []   # (6, C) BatchNorm vectors for y[i]
+        self.bn_y = []   # (BN_ROWS, C) BatchNorm vectors for y[i]
         self.bn_z = [None]
-        part_elems = 0
-        ncls = m.n_classes
-        for i, sp in enumerate(specs):
-            D, H, W = self.dims[i]
-            S = D * H * W
-            self.y.append(torch.empty((N, sp["cout"], D, H, W), **f32))
-            self.bn_y.append(torch.zeros((BN_ROWS, sp["cout"]), **f32))
-            if i == 0:
-                part_elems = max(part_elems, 2 * sp["cout"] * L.msl_stem_conv_fwd_num_partials(N, D, H, W))
-            else:
-                pd, ph, pw = self.dims[i - 1]
-                self.z.append(torch.empty((N, sp["cin"], D, H, W), **f32))
-                self.bn_z.append(torch.zeros((BN_ROWS, sp["cin"]), **f32))
-                part_elems = max(part_elems,
-                                 2 * sp["cin"] * L.msl_dwconv_fwd_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]),
-                                 2 * sp["cout"] * L.msl_pwconv_fwd_num_partials(N, sp["cin"], sp["cout"], S))
-                if need_grad:
-                    part_elems = max(part_elems,
-                                     sp["cin"] * 27 * L.msl_dwconv_bwd_weight_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]),
-                                     2 * sp["cin"] * L.msl_bn_relu_bwd_num_partials(N, S),
-                                     2 * sp["cin"] * max(L.msl_dwconv_bwd_data_bnreduce_num_partials(N, sp["cin"], pd, ph, pw), 0))
-            if need_grad:
-                part_elems = max(part_elems, 2 * sp["cout"] * L.msl_bn_relu_bwd_num_partials(N, S))
-        self.partials = torch.empty(max(part_elems, 1), dtype=torch.float64, device=device)
-        # one statistics buffer per BatchNorm: the consumer folds them in its prologue while the finalize kernel
-        # (running stats + vectors for backward) reads them on a side stream
-        f64 = dict(dtype=torch.float64, device=device)
+        # one statistics buffer per BatchNorm (np_* partials per channel: the counts of the kernels of this storage type): the
+        # consumer folds them in its prologue while the finalize kernel (running stats + vectors for backward) reads them on
+        # a side stream
         self.np_y, self.np_z, self.part_y, self.part_z = [], [None], [], [None]
         for i, sp in enumerate(specs):
             D, H, W = self.dims[i]
@@ -172,12 +155,21 @@ class Plan:
                 self.np_y.append(L.msl_stem_conv_fwd_num_partials(N, D, H, W))
             else:
                 pd, ph, pw = self.dims[i - 1]
-                self.np_z.append(L.msl_dwconv_fwd_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]))
+                self.z.append(torch.empty((N, sp["cin"], D, H, W), **act))
+                self.bn_z.append(torch.zeros((BN_ROWS, sp["cin"]), **f32))
+                if bf16:
+                    self.np_z.append(L.msl_dwconv_fwd_bf16_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]))
+                    self.np_y.append(L.msl_pwconv_fwd_bf16_num_partials(N, D * H * W))
+                else:
+                    self.np_z.append(L.msl_dwconv_fwd_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]))
+                    self.np_y.append(L.msl_pwconv_fwd_num_partials(N, sp["cin"], sp["cout"], D * H * W))
                 self.part_z.append(torch.empty(2 * sp["cin"] * self.np_z[i], **f64))
-                self.np_y.append(L.msl_pwconv_fwd_num_partials(N, sp["cin"], sp["cout"], D * H * W))
+            self.y.append(torch.empty((N, sp["cout"], D, H, W), **act))
+            self.bn_y.append(torch.zeros((BN_ROWS, sp["cout"]), **f32))
             self.part_y.append(torch.empty(2 * sp["cout"] * self.np_y[i], **f64))
 
-        # heads
+        # heads: on the fp32 kernels from a zero-haloed fp32 copy of the feature map (the fp32 step; the bf16 training step
+        # always, bf16 inference unless Engine.bf16_heads says "bf16"), else on the bf16 MFMA kernel from a channels-last copy
         self.feat_ids = list(m.aspect_ratios.keys())
         self.prior_off, off = {}, 0
         for f in self.feat_ids:
@@ -185,21 +177,44 @@ class Plan:
             D, H, W = self.dims[f]
             off += D * H * W * m.boxes_per_location
         self.P = off
-        self.fpad, self.Wf, self.Wb, self.head_ws = {}, {}, {}, {}
-        for f in self.feat_ids:
-            C = specs[f]["cout"]
-            D, H, W = self.dims[f]
-            self.fpad[f] = torch.zeros((N, C, D + 2, H + 2, W + 2), **f32)
-            ne = L.msl_head_packed_weight_elems(C, ncls)
-            self.Wf[f] = torch.empty(ne, **f32)
-            self.Wb[f] = torch.empty(ne, **f32)
-            ws = max(L.msl_head_fwd_workspace_bytes(N, C, D, H, W, ncls),
-                     L.msl_head_bwd_weight_workspace_bytes(N, C, D, H, W, ncls) if need_grad else 0)
-            self.head_ws[f] = torch.empty(max(ws // 4, 1), **f32)
+        self.f32_heads = not bf16 or need_grad or engine.bf16_heads != "bf16"
+        if self.f32_heads:
+            self.fpad, self.Wf, self.Wb, self.head_ws = {}, {}, {}, {}
+            for f in self.feat_ids:
+                C = specs[f]["cout"]
+                D, H, W = self.dims[f]
+                self.fpad[f] = torch.zeros((N, C, D + 2, H + 2, W + 2), **f32)
+                ne = L.msl_head_packed_weight_elems(C, ncls)
+                self.Wf[f] = torch.empty(ne, **f32)
+                self.Wb[f] = torch.empty(ne, **f32)
+                ws = max(L.msl_head_fwd_workspace_bytes(N, C, D, H, W, ncls),
+                         L.msl_head_bwd_weight_workspace_bytes(N, C, D, H, W, ncls) if need_grad else 0)
+                self.head_ws[f] = torch.empty(max(ws // 4, 1), **f32)
+        else:
+            bf = dict(dtype=torch.bfloat16, device=device)
+            self.fpad_cl = {f: torch.zeros((N,) + tuple(d + 2 for d in self.dims[f]) + (specs[f]["cout"],), **bf) for f in self.feat_ids}
+            self.Wp = {f: torch.empty(L.msl_head_packed_weight_bf16_elems(specs[f]["cout"]), **bf) for f in self.feat_ids}
         self.locs = torch.empty((N, self.P, 6), **f32)
         self.scores = torch.empty((N, self.P, ncls), **f32)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=device)
 
+        # fp64 scratch for per-channel sums that one kernel leaves for the next (Engine._bn_bwd and the producers of its
+        # ``pre_np``): the largest count over the layers.  The fp32 step sizes it from its forward counts too.
+        bwd_np = L.msl_bn_relu_bwd_bf16_num_partials if bf16 else L.msl_bn_relu_bwd_num_partials
+        part_elems = 0
+        for i, sp in enumerate(specs):
+            D, H, W = self.dims[i]
+            if not bf16:
+                part_elems = max(part_elems, 2 * sp["cout"] * self.np_y[i], 2 * sp["cin"] * self.np_z[i] if i else 0)
+            if need_grad:
+                part_elems = max(part_elems, 2 * sp["cout"] * bwd_np(N, D * H * W))
+                if i:
+                    part_elems = max(part_elems, 2 * sp["cin"] * bwd_np(N, D * H * W), 2 * sp["cin"] * max(
+                        L.msl_dwconv_bwd_data_bnreduce_num_partials(N, sp["cin"], *self.dims[i - 1]), 0))
+
+        # fp32-only one-pass backward kernels (filled below; a bf16 plan has none)
+        self.pw_fused = {}       # block -> (slabs [NP][Cout][Cin], fp64 statistics partials [2][Cin][NP], NP): csrc/pwfused.hip
+        self.dw_fused_part = {}  # big stride-2 block -> (fp64 partials [Cin*27][NP], NP): weight gradient with the bwd-data pass
         if need_grad:
             self.g_y = [torch.empty_like(t) for t in self.y]
             self.g_z = [None] + [torch.empty_like(t) for t in self.z[1:]]
@@ -209,54 +224,72 @@ class Plan:
             # Deferred gradient reduction (Engine._grad_reduce): every weight-gradient kernel leaves its partial sums in a
             # buffer of ITS OWN (they all stay live until the one batched reduction in front of the optimiser):
             #   pw_slabs[i]  fp32 [nslabs][Cout][Cin] (None: the kernel covers the whole position range and writes dW itself)
-            #   dw_part[i]   fp64 [Cin*27][NP]
+            #   dw_part[i]   fp64 [Cin*27][NP]  (bf16: the depthwise weight-gradient kernel has the forward's partition)
             self.pw_nslabs, self.pw_slabs, self.dw_np, self.dw_part = [0], [None], [0], [None]
             for i in range(1, len(specs)):
+                cin, cout = specs[i]["cin"], specs[i]["cout"]
                 D, H, W = self.dims[i]
                 pd, ph, pw = self.dims[i - 1]
-                ns = L.msl_pwconv_bwd_weight_nslabs(N, specs[i]["cin"], specs[i]["cout"], D * H * W)
+                if bf16:
+                    ns = L.msl_pwconv_bwd_weight_bf16_nslabs(N, cin, cout, D * H * W)
+                    if ns < 1:
+                        raise _lib.HipKernelError(f"msl_pwconv_bwd_weight_bf16_nslabs failed for block {i}")
+                    npd = self.np_z[i]
+                else:
+                    ns = L.msl_pwconv_bwd_weight_nslabs(N, cin, cout, D * H * W)
+                    npd = L.msl_dwconv_bwd_weight_num_partials(N, cin, pd, ph, pw, specs[i]["stride"][0])
+                    part_elems = max(part_elems, cin * 27 * npd)
                 self.pw_nslabs.append(ns)
-                self.pw_slabs.append(torch.empty(ns * specs[i]["cin"] * specs[i]["cout"], **f32) if ns > 1 else None)
-                npd = L.msl_dwconv_bwd_weight_num_partials(N, specs[i]["cin"], pd, ph, pw, specs[i]["stride"][0])
+                self.pw_slabs.append(torch.empty(ns * cin * cout, **f32) if ns > 1 else None)
                 self.dw_np.append(npd)
-                self.dw_part.append(torch.empty(specs[i]["cin"] * 27 * npd, dtype=torch.float64, device=device))
-            # blocks whose whole pointwise backward is one pass (csrc/pwfused.hip): per block (slabs [NP][Cout][Cin], fp64
-            # statistics partials [2][Cin][NP], NP)
-            self.pw_fused = {}
-            for i in range(1, len(specs)):
+                self.dw_part.append(torch.empty(cin * 27 * npd, **f64))
+            for i in () if bf16 else range(1, len(specs)):  # fp32 only (part_elems is final for fp32 here)
+                cin, cout = specs[i]["cin"], specs[i]["cout"]
                 D, H, W = self.dims[i]
-                nf = L.msl_pwconv_bwd_fused_num_partials(N, specs[i]["cin"], specs[i]["cout"], D * H * W)
-                if nf > 0:
-                    self.pw_fused[i] = (torch.empty(nf * specs[i]["cin"] * specs[i]["cout"], **f32),
-                                        torch.empty(2 * specs[i]["cin"] * nf, dtype=torch.float64, device=device), nf)
-            # big stride-2 blocks whose depthwise weight gradient comes with their bwd-data pass: fp64 partials [Cin*27][NP]
-            self.dw_fused_part = {}
-            for i in range(2, len(specs)):
                 pd, ph, pw = self.dims[i - 1]
-                if specs[i]["stride"][0] == 2 and N * pd * ph * pw > 65536:
-                    npw = L.msl_dwconv_s2_bwd_bnreduce_bww_num_partials(N, specs[i]["cin"], pd, ph, pw)
-                    if npw > 0 and 2 * specs[i]["cin"] * npw <= self.partials.numel():
-                        self.dw_fused_part[i] = (torch.empty(specs[i]["cin"] * 27 * npw, dtype=torch.float64, device=device), npw)
+                nf = L.msl_pwconv_bwd_fused_num_partials(N, cin, cout, D * H * W)
+                if nf > 0:
+                    self.pw_fused[i] = (torch.empty(nf * cin * cout, **f32), torch.empty(2 * cin * nf, **f64), nf)
+                if i >= 2 and specs[i]["stride"][0] == 2 and N * pd * ph * pw > 65536:
+                    npw = L.msl_dwconv_s2_bwd_bnreduce_bww_num_partials(N, cin, pd, ph, pw)
+                    if npw > 0 and 2 * cin * npw <= part_elems:
+                        self.dw_fused_part[i] = (torch.empty(cin * 27 * npw, **f64), npw)
             self.head_nslabs = {f: L.msl_head_conv_bwd_weight_nslabs(N, specs[f]["cout"], *self.dims[f], ncls) for f in self.feat_ids}
             self.stem_nslabs = L.msl_stem_conv_bwd_weight_nslabs(N, *self.in_dims, *specs[0]["stride"])
-            self.grad_tables = {}
             # fused stem backward (block 1 is a stride-2 depthwise layer fed by a 32-channel stem that is not a head
-            # feature): its dL/d(stem activation) is never materialised (Engine.backward)
+            # feature): its dL/d(stem activation) is never materialised (Engine.backward / _backward_bf16).  fp32: where the
+            # sums fit the scratch, and Engine.backward still asks Engine.fuse_stem; bf16: decided here, the scratch grows
             self.fused_stem_np = -1
-            if (len(specs) > 1 and specs[0]["cout"] == 32 and specs[1]["cin"] == 32 and tuple(specs[1]["stride"]) == (2, 2, 2)
-                    and 0 not in self.feat_ids):
+            fusable = (len(specs) > 1 and specs[0]["cout"] == 32 and specs[1]["cin"] == 32
+                       and tuple(specs[1]["stride"]) == (2, 2, 2) and 0 not in self.feat_ids)
+            if fusable and (engine.fuse_stem or not bf16):
                 np_f = L.msl_dwconv_s2_bwd_bnreduce_bww_num_partials(N, 32, *self.dims[0])
-                small = self.y[0].numel() * 4 < (1 << 32)  # the fused kernel uses 32-bit byte offsets
-                if np_f > 0 and small and 2 * 32 * np_f <= self.partials.numel():
+                small = self.y[0].numel() * self.y[0].element_size() < (1 << 32)  # the fused kernel uses 32-bit byte offsets
+                if np_f > 0 and small and (bf16 or 2 * 32 * np_f <= part_elems):
                     self.fused_stem_np = np_f
-                    self.partials_wf = torch.empty(32 * 27 * np_f, dtype=torch.float64, device=device)
+                    self.partials_wf = torch.empty(32 * 27 * np_f, **f64)
                     self.w1_taps_t = torch.empty((27, 32), **f32)
-        self.events = {}
-        self.saved_input = None
-        self.generation = 0
-        self.dw_in_link = set()  # blocks whose depthwise weight gradient a channel link writes (no partials to fold)
-        self.pw_fused_used = set()  # blocks whose pointwise weight-gradient slabs came with the fused pointwise backward
-        self.dw_fused_used = set()  # blocks whose depthwise weight-gradient partials came with their bwd-data pass
+                    if bf16:
+                        part_elems = max(part_elems, 2 * 32 * np_f)
+                        self.g_y[0] = None  # never materialised
+        if need_grad or not bf16:  # (a bf16 inference plan has none)
+            self.partials = torch.empty(max(part_elems, 1), **f64)
+
+        # ---- what the passes write later (declared here so that no reader has to probe for it) -----------------------------
+        self.events = {}           # Engine._event
+        self.saved_input = None    # Engine.forward / _forward_bf16, FusedTrainer (replayed steps)
+        self.generation = 0        # the same: +1 per forward pass
+        self.trained_mode = False  # the same: was the latest forward pass a train-mode one?
+        self.stem_dw_eval = False  # Engine.forward / _forward_bf16: stem + block-1 depthwise ran as one launch
+        self.loss_fold = None      # FusedTrainer._eager_step: (parts, nparts, loss_out, npos) of the one-launch loss
+        self.bn_table = {False: (None, None), True: (None, None)}  # Engine._finalize_all: eval_mode -> (key, (table, n, channels))
+        self.pwb_key = self.pwb_args = None      # Engine._pw_bww_batch
+        self.pack_key = self.pack_args = None    # Engine._pack_head_weights
+        self.gpack_key = self.gpack_args = None  # Engine._head_gpack_batch
+        self.grad_tables = {}       # Engine._grad_reduce
+        self.dw_in_link = set()     # Engine.backward / _backward_bf16: blocks whose depthwise weight gradient a channel link writes
+        self.pw_fused_used = set()  # Engine.backward: blocks whose pointwise weight-gradient slabs came with pw_fused
+        self.dw_fused_used = set()  # Engine.backward: blocks whose depthwise weight-gradient partials came with dw_fused_part
 
 
 class Engine:
@@ -313,13 +346,15 @@ class Engine:
         return self.arena
 
     def plan_for(self, x, need_grad):
-        if getattr(self.model, "compute_dtype", "f32") == "bf16":
-            return self._plan_bf16(x, need_grad)
-        key = (x.shape[0], tuple(x.shape[2:]), x.device, need_grad)
+        """The plan for this input shape, mode and the model's storage type (built once).  The key holds the options a plan
+        bakes in when it is built: setting one afterwards builds a new plan."""
+        dtype = getattr(self.model, "compute_dtype", "f32")
+        bf16 = dtype == "bf16"
+        key = (dtype, x.shape[0], tuple(x.shape[2:]), x.device, need_grad, self.bf16_heads if bf16 else None,
+               self.fuse_stem if bf16 and need_grad else None)
         p = self.plans.get(key)
         if p is None:
-            p = Plan(self, x.shape[0], x.shape[2:], x.device, need_grad)
-            self.plans[key] = p
+            p = self.plans[key] = Plan(self, x.shape[0], x.shape[2:], x.device, need_grad, dtype)
         return p
 
     @staticmethod
@@ -579,120 +614,6 @@ class Engine:
         return pl.locs, pl.scores
 
     # ------------------------------------------------------------------------------------------------
-    def _plan_bf16(self, x, need_grad=False):
-        """Buffers of the bf16 activation path for this input shape: inference (BASELINE configs[3]) and, with
-        ``need_grad``, the training step (configs[2])."""
-        key = ("bf16", x.shape[0], tuple(x.shape[2:]), x.device, need_grad)
-        pl = self.plans.get(key)
-        if pl is not None:
-            return pl
-        L = _lib.load()
-        m, specs = self.model, self.layer_specs
-
-        class _P:
-            pass
-        pl = _P()
-        pl.bf16 = True
-        N, dev = x.shape[0], x.device
-        pl.N, pl.in_dims = N, tuple(x.shape[2:])
-        pl.dims, cur = [], tuple(x.shape[2:])
-        for sp in specs:
-            cur = tuple(conv_out(d, s) for d, s in zip(cur, sp["stride"]))
-            pl.dims.append(cur)
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        f64 = dict(dtype=torch.float64, device=dev)
-        ncls = m.n_classes
-        pl.y = [torch.empty((N, sp["cout"]) + pl.dims[i], **bf) for i, sp in enumerate(specs)]
-        pl.z = [None] + [torch.empty((N, specs[i]["cin"]) + pl.dims[i], **bf) for i in range(1, len(specs))]
-        pl.bn_y = [torch.zeros((BN_ROWS, sp["cout"]), **f32) for sp in specs]
-        pl.bn_z = [None] + [torch.zeros((BN_ROWS, specs[i]["cin"]), **f32) for i in range(1, len(specs))]
-        # statistics partials of every BatchNorm (training): counts of the bf16 kernels
-        pl.np_y, pl.np_z = [], [None]
-        for i, sp in enumerate(specs):
-            D, H, W = pl.dims[i]
-            if i == 0:
-                pl.np_y.append(L.msl_stem_conv_fwd_num_partials(N, D, H, W))
-            else:
-                pd, ph, pw = pl.dims[i - 1]
-                pl.np_z.append(L.msl_dwconv_fwd_bf16_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]))
-                pl.np_y.append(L.msl_pwconv_fwd_bf16_num_partials(N, D * H * W))
-        pl.part_y = [torch.empty(2 * sp["cout"] * pl.np_y[i], **f64) for i, sp in enumerate(specs)]
-        pl.part_z = [None] + [torch.empty(2 * specs[i]["cin"] * pl.np_z[i], **f64) for i in range(1, len(specs))]
-        pl.feat_ids = list(m.aspect_ratios.keys())
-        pl.prior_off, off = {}, 0
-        for f in pl.feat_ids:
-            pl.prior_off[f] = off
-            D, H, W = pl.dims[f]
-            off += D * H * W * m.boxes_per_location
-        pl.P = off
-        pl.f32_heads = need_grad or self.bf16_heads != "bf16"
-        if pl.f32_heads:  # head convolutions on the fp32 kernels (faster at these sizes; the training step always)
-            pl.fpad = {f: torch.zeros((N, specs[f]["cout"]) + tuple(d + 2 for d in pl.dims[f]), **f32) for f in pl.feat_ids}
-            if not need_grad:
-                pl.Wf, pl.Wb, pl.head_ws = {}, {}, {}
-                for f in pl.feat_ids:
-                    C = specs[f]["cout"]
-                    ne = L.msl_head_packed_weight_elems(C, ncls)
-                    pl.Wf[f], pl.Wb[f] = torch.empty(ne, **f32), torch.empty(ne, **f32)
-                    pl.head_ws[f] = torch.empty(max(L.msl_head_fwd_workspace_bytes(N, C, *pl.dims[f], ncls) // 4, 1), **f32)
-        else:
-            pl.fpad_cl = {f: torch.zeros((N,) + tuple(d + 2 for d in pl.dims[f]) + (specs[f]["cout"],), **bf) for f in pl.feat_ids}
-            pl.Wp = {f: torch.empty(L.msl_head_packed_weight_bf16_elems(specs[f]["cout"]), **bf) for f in pl.feat_ids}
-        pl.locs = torch.empty((N, pl.P, 6), **f32)
-        pl.scores = torch.empty((N, pl.P, ncls), **f32)
-        pl.nan_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        pl.events, pl.generation, pl.saved_input, pl.need_grad, pl.trained_mode = {}, 0, None, need_grad, False
-        if need_grad:
-            pl.g_y = [torch.empty_like(t) for t in pl.y]
-            pl.g_z = [None] + [torch.empty_like(t) for t in pl.z[1:]]
-            mt16 = 16 * ((12 + 2 * ncls + 15) // 16)
-            pl.dO = {f: torch.zeros((N, mt16) + tuple(d + 2 for d in pl.dims[f]), **f32) for f in pl.feat_ids}
-            pl.Wf, pl.Wb, pl.head_ws = {}, {}, {}
-            for f in pl.feat_ids:
-                C = specs[f]["cout"]
-                ne = L.msl_head_packed_weight_elems(C, ncls)
-                pl.Wf[f], pl.Wb[f] = torch.empty(ne, **f32), torch.empty(ne, **f32)
-                ws = max(L.msl_head_fwd_workspace_bytes(N, C, *pl.dims[f], ncls),
-                         L.msl_head_bwd_weight_workspace_bytes(N, C, *pl.dims[f], ncls))
-                pl.head_ws[f] = torch.empty(max(ws // 4, 1), **f32)
-            pl.head_nslabs = {f: L.msl_head_conv_bwd_weight_nslabs(N, specs[f]["cout"], *pl.dims[f], ncls) for f in pl.feat_ids}
-            pl.ws_stem = torch.empty(max(L.msl_stem_conv_bwd_weight_workspace_bytes(specs[0]["cin"]) // 4, 1), **f32)
-            pl.stem_nslabs = L.msl_stem_conv_bwd_weight_nslabs(N, *pl.in_dims, *specs[0]["stride"])
-            pl.pw_nslabs, pl.pw_slabs, pl.dw_np, pl.dw_part = [0], [None], [0], [None]
-            bnp = 0
-            for i in range(1, len(specs)):
-                D, H, W = pl.dims[i]
-                pd, ph, pw = pl.dims[i - 1]
-                ns = L.msl_pwconv_bwd_weight_bf16_nslabs(N, specs[i]["cin"], specs[i]["cout"], D * H * W)
-                if ns < 1:
-                    raise _lib.HipKernelError(f"msl_pwconv_bwd_weight_bf16_nslabs failed for block {i}")
-                pl.pw_nslabs.append(ns)
-                pl.pw_slabs.append(torch.empty(ns * specs[i]["cin"] * specs[i]["cout"], **f32) if ns > 1 else None)
-                pl.dw_np.append(pl.np_z[i])
-                pl.dw_part.append(torch.empty(specs[i]["cin"] * 27 * pl.np_z[i], **f64))
-                bnp = max(bnp, 2 * specs[i]["cout"] * L.msl_bn_relu_bwd_bf16_num_partials(N, D * H * W),
-                          2 * specs[i]["cin"] * L.msl_bn_relu_bwd_bf16_num_partials(N, D * H * W),
-                          2 * specs[i]["cin"] * max(L.msl_dwconv_bwd_data_bnreduce_num_partials(N, specs[i]["cin"], pd, ph, pw), 0))
-            d0 = pl.dims[0]
-            bnp = max(bnp, 2 * specs[0]["cout"] * L.msl_bn_relu_bwd_bf16_num_partials(N, d0[0] * d0[1] * d0[2]))
-            pl.fused_stem_np = -1
-            if (len(specs) > 1 and specs[0]["cout"] == 32 and specs[1]["cin"] == 32 and tuple(specs[1]["stride"]) == (2, 2, 2)
-                    and 0 not in pl.feat_ids and self.fuse_stem):
-                # fused stem backward on bf16 storage: dL/d(stem activation) is never stored (as in the fp32 step)
-                np_f = L.msl_dwconv_s2_bwd_bnreduce_bww_num_partials(N, 32, *pl.dims[0])
-                if np_f > 0 and pl.y[0].numel() * 2 < (1 << 32):
-                    pl.fused_stem_np = np_f
-                    pl.partials_wf = torch.empty(32 * 27 * np_f, **f64)
-                    pl.w1_taps_t = torch.empty((27, 32), **f32)
-                    bnp = max(bnp, 2 * 32 * np_f)
-                    pl.g_y[0] = None  # never materialised
-            pl.partials = torch.empty(bnp, **f64)
-            pl.grad_tables = {}
-            pl.dw_in_link = set()
-        self.plans[key] = pl
-        return pl
-
     def _forward_bf16(self, x, training=False, need_grad=False, want_features=False, nan_check=True, after_block=None):
         """Forward with bf16 activations in HBM (csrc/bf16.hip + the bf16 head kernel): fp32 input volume, fp32 weights and
         BatchNorm vectors / statistics, bf16 everything in between, fp32 locs / scores out.  One stream (the head
@@ -700,7 +621,7 @@ class Engine:
         m, specs, feats = self.model, self.layer_specs, self.model.base.features
         x = x.contiguous().float()
         self.ensure_arena(x.device)
-        pl = self._plan_bf16(x, need_grad)
+        pl = self.plan_for(x, need_grad)
         pl.generation += 1
         pl.saved_input, pl.trained_mode = x, training
         st = self._stream()
@@ -1022,46 +943,41 @@ class Engine:
         self._finalize_all(pl, bn_layers, stW)
         return self._record(pl, "fwd_bn_done", stW)
 
+    @staticmethod
+    def _bn_table(bn_layers):
+        """Device table of the listed BatchNorms (bn module, vector buffer, partials, NP, element count) for
+        msl_bn_finalize_batch / msl_bn_eval_affine_batch -> (table, entries, channels)."""
+        L = _lib.load()
+        esz = L.msl_bn_finalize_entry_bytes()
+        host = (ctypes.c_ubyte * (esz * len(bn_layers)))()
+        first = 0
+        for k, (bn, vec, part, NP, count) in enumerate(bn_layers):
+            C = vec.shape[1]
+            mom = 0.1 if bn.momentum is None else bn.momentum
+            _lib.check(L.msl_bn_finalize_table_set(ctypes.addressof(host), k, first, ptr(part), NP, float(count),
+                                                   ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
+                                                   ptr(bn.running_var), ptr(bn.num_batches_tracked), mom, bn.eps,
+                                                   ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]), C),
+                       "msl_bn_finalize_table_set")
+            first += C
+        return torch.frombuffer(bytearray(host), dtype=torch.uint8).to(vec.device), len(bn_layers), first
+
     def _finalize_all(self, pl, bn_layers, st, eval_mode=False):
         """One launch for the running statistics and backward vectors of the listed BatchNorms (table built once per
         plan and mode); ``eval_mode``: one launch for their eval-mode (scale, shift) instead."""
-        import ctypes
-        L = _lib.load()
-        key = (eval_mode,) + tuple((ptr(bn.weight), ptr(bn.running_mean)) for bn, *_ in bn_layers)
+        key = tuple((ptr(bn.weight), ptr(bn.running_mean)) for bn, *_ in bn_layers)
+        if pl.bn_table[eval_mode][0] != key:
+            pl.bn_table[eval_mode] = (key, self._bn_table(bn_layers))
+        table, n, channels = pl.bn_table[eval_mode][1]
         if eval_mode:
-            if getattr(pl, "bn_eval_table_key", None) != key:
-                keep = (getattr(pl, "bn_table", None), getattr(pl, "bn_table_key", None), getattr(pl, "bn_table_n", None),
-                        getattr(pl, "bn_table_channels", None))
-                pl.bn_table_key = None
-                self._finalize_all(pl, bn_layers, None)  # builds pl.bn_table for this list (no launch: st is None)
-                pl.bn_eval_table, pl.bn_eval_n, pl.bn_eval_channels, pl.bn_eval_table_key = pl.bn_table, pl.bn_table_n, pl.bn_table_channels, key
-                pl.bn_table, pl.bn_table_key, pl.bn_table_n, pl.bn_table_channels = keep
-            _lib.call("msl_bn_eval_affine_batch", ptr(pl.bn_eval_table), pl.bn_eval_n, pl.bn_eval_channels, st, tag="bn_eval_all")
-            return
-        if getattr(pl, "bn_table_key", None) != key:
-            esz = L.msl_bn_finalize_entry_bytes()
-            host = (ctypes.c_ubyte * (esz * len(bn_layers)))()
-            first = 0
-            for k, (bn, vec, part, NP, count) in enumerate(bn_layers):
-                C = vec.shape[1]
-                mom = 0.1 if bn.momentum is None else bn.momentum
-                _lib.check(L.msl_bn_finalize_table_set(ctypes.addressof(host), k, first, ptr(part), NP, float(count),
-                                                       ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                                                       ptr(bn.running_var), ptr(bn.num_batches_tracked), mom, bn.eps,
-                                                       ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]), C),
-                           "msl_bn_finalize_table_set")
-                first += C
-            pl.bn_table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(vec.device)
-            pl.bn_table_key, pl.bn_table_n, pl.bn_table_channels = key, len(bn_layers), first
-        if st is None:
-            return
-        _lib.call("msl_bn_finalize_batch", ptr(pl.bn_table), pl.bn_table_n, pl.bn_table_channels, st, tag="bn_finalize_all")
+            _lib.call("msl_bn_eval_affine_batch", ptr(table), n, channels, st, tag="bn_eval_all")
+        else:
+            _lib.call("msl_bn_finalize_batch", ptr(table), n, channels, st, tag="bn_finalize_all")
 
     def _pw_bww_batch(self, pl, rows, N, st):
         """msl_pwconv_bwd_weight_slabs for several tail blocks in one launch; rows = (dy, z, scale, shift, out, cin, cout, S)."""
-        import ctypes
         key = tuple(rows)
-        if getattr(pl, "pwb_key", None) != key:
+        if pl.pwb_key != key:
             n = len(rows)
             P, I = ctypes.c_void_p * n, ctypes.c_int * n
             pl.pwb_args = tuple(P(*[r[c] for r in rows]) for c in range(5)) + tuple(I(*[r[c] for r in rows]) for c in range(5, 8))
@@ -1070,10 +986,9 @@ class Engine:
         self._k("pw_bww_tail", "msl_pwconv_bwd_weight_slabs_batch", *[ctypes.addressof(x) for x in a], len(rows), N, st)
 
     def _pack_head_weights(self, pl, st):
-        import ctypes
         m = self.model
         key = tuple(ptr(c.weight) for c in m.pred_convs.loc_convs) + tuple(ptr(c.weight) for c in m.pred_convs.cl_convs)
-        if getattr(pl, "pack_key", None) != key:
+        if pl.pack_key != key:
             n = len(pl.feat_ids)
             P = ctypes.c_void_p * n
             pl.pack_args = (P(*[ptr(c.weight) for c in m.pred_convs.loc_convs]), P(*[ptr(c.weight) for c in m.pred_convs.cl_convs]),
@@ -1137,9 +1052,8 @@ class Engine:
 
     def _head_gpack_batch(self, pl, dlocs, dscores, st):
         """msl_head_grad_pack of every scale in one launch."""
-        import ctypes
         key = (ptr(dlocs), ptr(dscores)) + tuple(ptr(pl.dO[f]) for f in pl.feat_ids)
-        if getattr(pl, "gpack_key", None) != key:
+        if pl.gpack_key != key:
             n = len(pl.feat_ids)
             I = ctypes.c_int * n
             pl.gpack_args = ((ctypes.c_void_p * n)(*[ptr(pl.dO[f]) for f in pl.feat_ids]),) + tuple(
@@ -1230,7 +1144,7 @@ class Engine:
         ``stages`` attribute only those stages are reported (and the side streams are joined first)."""
         if not pl.need_grad or not pl.trained_mode:
             raise RuntimeError("backward needs a train-mode forward made with gradients enabled")
-        if getattr(pl, "bf16", False):
+        if pl.bf16:
             return self._backward_bf16(pl, dlocs, dscores, on_bucket_ready)
         m = self.model
         gv = self.arena.grad_views
@@ -1477,9 +1391,8 @@ class Engine:
     def _grad_reduce(self, pl, key, names, st):
         """One launch that folds the partial weight-gradient sums (pointwise slabs, depthwise fp64 partials, head and stem
         slabs) of the parameters in ``names`` (None: all) into the gradient arena (table built once per plan and key)."""
-        import ctypes
         L = _lib.load()
-        fold = getattr(pl, "loss_fold", None)
+        fold = pl.loss_fold
         tkey = (key, None if fold is None else ptr(fold[0]))
         ent = pl.grad_tables.get(tkey)
         if ent is None:
@@ -1505,14 +1418,14 @@ class Engine:
             for i in range(len(specs) - 1, 0, -1):
                 name = f"base.features.{i}"
                 cnt = specs[i]["cin"] * specs[i]["cout"]
-                if want(name + ".conv2.weight") and i in getattr(pl, "pw_fused_used", ()):
+                if want(name + ".conv2.weight") and i in pl.pw_fused_used:
                     rows.append((0, pl.pw_fused[i][0], gv[name + ".conv2.weight"], None, pl.pw_fused[i][2], cnt, cnt, 0, 0, 0))
                 elif want(name + ".conv2.weight") and pl.pw_nslabs[i] > 1:
                     rows.append((0, pl.pw_slabs[i], gv[name + ".conv2.weight"], None, pl.pw_nslabs[i], cnt, cnt, 0, 0, 0))
-                if want(name + ".conv1.weight") and i not in getattr(pl, "dw_in_link", ()):  # (a channel link wrote it)
+                if want(name + ".conv1.weight") and i not in pl.dw_in_link:  # (a channel link wrote it)
                     if i == 1 and fused:
                         rows.append((1, pl.partials_wf, gv[name + ".conv1.weight"], None, pl.fused_stem_np, specs[i]["cin"] * 27, 0, 0, 0, 0))
-                    elif i in getattr(pl, "dw_fused_used", ()):
+                    elif i in pl.dw_fused_used:
                         part_w, np_w = pl.dw_fused_part[i]
                         rows.append((1, part_w, gv[name + ".conv1.weight"], None, np_w, specs[i]["cin"] * 27, 0, 0, 0, 0))
                     else:
@@ -1521,7 +1434,6 @@ class Engine:
                 K = specs[0]["cin"] * 27
                 nt = (K + 31) // 32
                 rows.append((2, pl.ws_stem, gv["base.features.0.0.weight"], None, pl.stem_nslabs, 1024 * nt, 1024 * nt, K, nt, 0))
-            fold = getattr(pl, "loss_fold", None)
             if fold is not None and key in ("all", 0):  # the loss values of MultiBoxLoss._run_loss_pack ride along (kind 4)
                 parts, nparts, loss_out, npos = fold
                 rows.append((4, parts, loss_out, npos, nparts, 1, 0, 0, 0, 0))

@@ -2,6 +2,8 @@
 the HIP path against the CPU oracle and against the golden vectors minted from the reference itself.
 Bar (BASELINE.json north_star): integer outputs bit-exact, fp32 regressions / losses within 1e-4."""
 import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -11,7 +13,8 @@ from oracle import detect as OD
 from oracle import multibox as OMB
 from oracle.train_step import make_optimizer, train_step
 from tests.golden import cases, detinit
-from tests.util import golden, oracle_model
+from tests.golden import make_plan_inventory as plan_inventory
+from tests.util import GOLDEN_DIR, golden, oracle_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -538,6 +541,57 @@ def test_fused_stem_backward_matches_the_materialised_path():
     # only the stem and block 1's depthwise taps and the stem BatchNorm take the other route
     same = [k for k in outs[0] if torch.equal(outs[0][k], outs[1][k])]
     assert "base.features.2.conv1.weight" in same and "pred_convs.loc_convs.0.weight" in same
+
+
+# ------------------------------------------------------------------------------------------------- plan layout
+# What a plan may hold beyond tests/golden/plan_inventory.json (minted while the fp32 and the bf16 plan had a builder each):
+# the fields Plan.__init__ declares for the methods that write them later, and the fields only one of the two builders set,
+# which every plan has now (empty / constant where they do not apply).
+PLAN_DECLARED = {"bf16", "trained_mode", "stem_dw_eval", "loss_fold", "bn_table", "pwb_key", "pwb_args", "pack_key", "pack_args",
+                 "gpack_key", "gpack_args", "grad_tables", "dw_in_link", "pw_fused_used", "dw_fused_used",
+                 "pw_fused", "dw_fused_part", "f32_heads"}
+PLAN_ZEROED = ("fpad", "fpad_cl", "dO", "bn_y", "bn_z", "nan_flag")  # kernels rely on their initial zeros (halos, flag)
+
+
+@pytest.mark.parametrize("name", list(plan_inventory.cases().keys()))
+def test_plan_buffer_inventory(name):
+    """Every buffer and every count of a fresh plan - fp32 / bf16 storage, inference / training, both head routes of bf16
+    inference, a cube and a non-cube input - is what the inventory lists: same attributes, dtypes, shapes and values.
+    Nothing may be missing; an attribute the inventory does not know must be one of PLAN_DECLARED."""
+    with open(os.path.join(GOLDEN_DIR, "plan_inventory.json")) as f:
+        want = json.load(f)[name]
+    _, pl = plan_inventory.build_plan(plan_inventory.cases()[name], DEV)
+    got = json.loads(json.dumps(plan_inventory.inventory(pl)))  # (tuples -> lists, as in the file)
+    assert not set(want) - set(got), f"missing: {sorted(set(want) - set(got))}"
+    assert set(got) - set(want) <= PLAN_DECLARED, f"unexpected: {sorted(set(got) - set(want) - PLAN_DECLARED)}"
+    for attr in want:
+        assert got[attr] == want[attr], f"{attr}: {got[attr]} != {want[attr]}"
+    zeroed = [a for a in PLAN_ZEROED if a in want]
+    assert "nan_flag" in zeroed and ("fpad" in zeroed) != ("fpad_cl" in zeroed) and ("dO" in zeroed) == pl.need_grad
+    for attr in zeroed:
+        v = getattr(pl, attr)
+        for t in [v] if torch.is_tensor(v) else (v.values() if isinstance(v, dict) else v):
+            assert t is None or not bool(t.any()), f"{attr} is not all-zero after construction"
+
+
+def test_a_changed_build_time_option_builds_a_new_plan():
+    """A bf16 plan bakes Engine.bf16_heads (and, for training, Engine.fuse_stem) in when it is built: both are part of the
+    cache key, so setting one later gives a plan with the buffers of the new route, not the cached one."""
+    m = hip_model()
+    m.compute_dtype = "bf16"
+    eng = m._engine
+    x = torch.zeros((2, 1, 64, 64, 64), device=DEV)
+    p0 = eng.plan_for(x, False)
+    assert eng.plan_for(x, False) is p0 and p0.f32_heads and not hasattr(p0, "fpad_cl")
+    eng.bf16_heads = "bf16"
+    p1 = eng.plan_for(x, False)
+    assert p1 is not p0 and not p1.f32_heads and hasattr(p1, "fpad_cl")
+    assert eng.plan_for(x, False) is p1
+    t0 = eng.plan_for(x, True)
+    assert t0.fused_stem_np > 0 and t0.g_y[0] is None
+    eng.fuse_stem = False
+    t1 = eng.plan_for(x, True)
+    assert t1 is not t0 and t1.fused_stem_np < 0 and t1.g_y[0] is not None
 
 
 def test_engine_schedule_options_agree():

@@ -480,6 +480,19 @@ size_t msl_instance_boxes_workspace_bytes(int N);
 int msl_instance_boxes(const short* seg, int N, int D, int H, int W, const int* thresholds, int n_pairs, int capacity,
                        void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,
                        int* overflow, void* stream);
+/* The same for cases of C sequences (1 <= C <= 4, the stem's limit; datasets.LesionsDataModule(input_images=...)).
+ * msl_foreground_box_mc: msl_foreground_box on a channel-first (C,D,H,W) volume: F = {v : vol[c][v] > 0 for any c}, the
+ * union of the channels' supports; one box for all channels.  C = 1 is msl_foreground_box.
+ * msl_augment_fit_mc: msl_augment_fit for C channels in one launch.  arena_seg and table are msl_augment_fit's (seg_elems
+ * i16 elements; table: element offset off_k and shape of case k).  arena_img holds C * seg_elems floats: case k is C
+ * contiguous planes of n0*n1*n2 voxels starting at element C * off_k.  dst_img (N,C,T0,T1,T2) f32, dst_seg (N,T0,T1,T2)
+ * i16.  One set of params per sample: the geometry and the mask are computed once and every channel is resampled with
+ * it, then given the same intensity operations; each plane is bit-identical to msl_augment_fit on that plane alone.  A row
+ * whose case, axes or table entry are invalid (the case must end at or before seg_elems) writes zeros to all C planes. */
+int msl_foreground_box_mc(const float* vol, int C, int D, int H, int W, int margin, int* box, void* stream);
+int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+                       int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
+                       void* stream);
 
 /* ---- optimiser + NaN guard : ssd3d.py:704-722, :258-261 ---------------------------------------------------- */
 /* hp (device, 8 floats): step_size(bias), step_size(other), sqrt(bias_correction2), beta1, beta2, eps,

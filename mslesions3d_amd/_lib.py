@@ -140,6 +140,8 @@ _SIGNATURES = {
     "msl_augment_fit": (_I, [_P, _P, _Q, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_instance_boxes_workspace_bytes": (_Z, [_I]),
     "msl_instance_boxes": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
+    "msl_foreground_box_mc": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "msl_augment_fit_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "msl_nan_flag": (_I, [_P, _Z, _P, _I, _P]),
     "msl_nan_flag2": (_I, [_P, _Z, _I, _P, _Z, _I, _P, _P]),

@@ -1121,3 +1121,253 @@ int msl_instance_boxes(const short* seg, int N, int D, int H, int W, const int* 
 }
 
 }  // extern "C"
+
+// ---- clinical cases with C sequences (1 <= C <= 4): union foreground box, ragged augment + fit of all channels ---------
+// Host mirrors: datasets.foreground_box on a (C, D, H, W) image and datasets._LesionCases.__getitem__ with
+// len(input_images) = C.  The mask arena and the table are msl_augment_fit's; the image arena holds C contiguous planes
+// per case, case k at element C * off_k.
+//
+//   foreground : fg_reduce_kernel's walk over the C * D * H rows of the channel-first volume; a row of any channel that
+//                holds a positive voxel extends the one box (the union of the channels' supports)
+//   fit        : fit_kernel's thread (four output voxels of a row), for all C channels: the clamp of the fit, the f64
+//                coordinate row, the boundary maps, the axis weights and the order-0 mask tap are computed once per
+//                voxel; only the eight gathers, the f64 accumulation and the intensity operations repeat per channel,
+//                each in fit_kernel's operation order (a channel is bit-identical to a one-channel launch on its plane)
+namespace {
+
+constexpr int FIT_MAX_CH = 4;  // the stem's limit
+
+__global__ __launch_bounds__(FG_THREADS) void fg_reduce_mc_kernel(const float* __restrict__ vol, int C, int D, int H,
+                                                                  int W, int* __restrict__ box) {
+  const int lane = threadIdx.x & 63;
+  const long long rows = (long long)C * D * H;
+  const long long nwave = (long long)gridDim.x * (FG_THREADS / 64);
+  int lo_d = IMAX, lo_h = IMAX, lo_w = IMAX, hi_d = -1, hi_h = -1, hi_w = -1;
+  for (long long r = (long long)blockIdx.x * (FG_THREADS / 64) + (threadIdx.x >> 6); r < rows; r += nwave) {
+    const float* row = vol + r * W;
+    bool any = false;
+    for (int w = lane; w < W; w += 64) {
+      if (row[w] > 0.0f) {
+        any = true;
+        lo_w = min(lo_w, w);
+        hi_w = max(hi_w, w);
+      }
+    }
+    if (__any(any)) {  // wave-uniform
+      const int d = (int)((r / H) % D), h = (int)(r % H);
+      lo_d = min(lo_d, d); hi_d = max(hi_d, d);
+      lo_h = min(lo_h, h); hi_h = max(hi_h, h);
+    }
+  }
+  lo_w = wave_min(lo_w);
+  hi_w = wave_max(hi_w);
+  if (lane == 0 && hi_d >= 0) {
+    atomicMin(box + 0, lo_d); atomicMin(box + 1, lo_h); atomicMin(box + 2, lo_w);
+    atomicMax(box + 3, hi_d); atomicMax(box + 4, hi_h); atomicMax(box + 5, hi_w);
+  }
+}
+
+template <int C, bool VEC>
+__global__ __launch_bounds__(DP_THREADS) void fit_mc_kernel(
+    const float* __restrict__ src_img, const short* __restrict__ src_seg, long long seg_elems,
+    const long long* __restrict__ table, int n_cases, const double* __restrict__ params, int T0, int T1, int T2,
+    float* __restrict__ dst_img, short* __restrict__ dst_seg) {
+  const int G = (T2 + FIT_VEC - 1) / FIT_VEC;
+  const long long groups = (long long)T0 * T1 * G;
+  const long long g = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
+  if (g >= groups) return;
+  const int n = blockIdx.y;
+  const int x0 = (int)(g % G) * FIT_VEC;
+  const long long rowi = g / G;
+  const int oc0 = (int)(rowi / T1), oc1 = (int)(rowi % T1);
+  const long long TV = (long long)T0 * T1 * T2;
+  const long long in_plane = ((long long)oc0 * T1 + oc1) * T2 + x0;
+  const int cnt = (T2 - x0) < FIT_VEC ? (T2 - x0) : FIT_VEC;
+  const double* p = params + (size_t)n * AFFINE_STRIDE;
+  float vi[C][FIT_VEC];
+  short vs[FIT_VEC];
+#pragma unroll
+  for (int j = 0; j < FIT_VEC; ++j) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) vi[c][j] = 0.0f;
+    vs[j] = 0;
+  }
+  const int cs = (int)p[0];
+  int ax[3], rev[3];
+  bool ok = cs >= 0 && cs < n_cases;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ax[a] = (int)p[1 + a];
+    rev[a] = (int)p[4 + a];
+    ok = ok && ax[a] >= 0 && ax[a] < 3;
+  }
+  ok = ok && ax[0] != ax[1] && ax[0] != ax[2] && ax[1] != ax[2];
+  long long coff = 0, sn[3] = {1, 1, 1};
+  if (ok) {  // rejected on the host; never read out of bounds
+    coff = table[(long long)cs * 4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) sn[a] = table[(long long)cs * 4 + 1 + a];
+    ok = coff >= 0 && sn[0] > 0 && sn[1] > 0 && sn[2] > 0 && sn[0] < (1 << 20) && sn[1] < (1 << 20) && sn[2] < (1 << 20);
+    // the mask ends inside its arena; the image arena holds C * seg_elems floats, so the C planes end inside theirs
+    ok = ok && coff + sn[0] * sn[1] * sn[2] <= seg_elems;
+  }
+  if (ok) {
+    const long long V = sn[0] * sn[1] * sn[2];
+    const float* si = src_img + (long long)C * coff;  // plane c at si + c * V
+    const short* ss = src_seg + coff;
+    const long long sstride[3] = {sn[1] * sn[2], sn[2], 1LL};
+    const int T[3] = {T0, T1, T2};
+    int dims[3], dsh[3];  // permuted shape n' and the fit's shift d
+    long long pst[3];
+    long long base = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      dims[a] = (int)sn[ax[a]];
+      dsh[a] = dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2;
+      pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
+      if (rev[a]) base += (long long)(dims[a] - 1) * sstride[ax[a]];
+    }
+    const int q0 = min(max(oc0 + dsh[0], 0), dims[0] - 1), q1 = min(max(oc1 + dsh[1], 0), dims[1] - 1);
+    const bool affine = p[7] != 0.0;
+    const int mode = (int)p[20];
+    int qprev = -1;
+    for (int j = 0; j < cnt; ++j) {
+      const int qc[3] = {q0, q1, min(max(x0 + j + dsh[2], 0), dims[2] - 1)};
+      if (j > 0 && qc[2] == qprev) {  // padded region along the last axis: the same source voxel, the same values
+#pragma unroll
+        for (int c = 0; c < C; ++c) vi[c][j] = vi[c][j - 1];
+        vs[j] = vs[j - 1];
+        continue;
+      }
+      qprev = qc[2];
+      if (!affine) {
+        const long long s = base + qc[0] * pst[0] + qc[1] * pst[1] + qc[2] * pst[2];
+#pragma unroll
+        for (int c = 0; c < C; ++c) vi[c][j] = apply_ops(si[c * V + s], p);
+        vs[j] = ss[s];
+        continue;
+      }
+      int i1[3][2], i0[3];
+      double w[3][2];
+      bool outside = false;
+#pragma unroll
+      for (int h = 0; h < 3; ++h) {
+        double c = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c = c + (double)qc[k] * p[8 + 3 * h + k];
+        c = c + p[17 + h];
+        const int len = dims[h];
+        const double cc = map_boundary(c, len, mode);
+        if (mode == 2 && !(cc > -1.0)) outside = true;
+        const double fl = floor(cc);
+        const long long st = (long long)fl;
+        const double x = cc - fl;
+        w[h][0] = 1.0 - x;
+        w[h][1] = 1.0 - w[h][0];
+        i1[h][0] = map_tap(st, len, mode);
+        i1[h][1] = map_tap(st + 1, len, mode);
+        i0[h] = map_tap((long long)floor(cc + 0.5), len, mode);
+      }
+      if (outside) {  // scipy's constant: cval for image and mask alike, the intensity operations still apply
+        const float cval = apply_ops(0.0f, p);
+#pragma unroll
+        for (int c = 0; c < C; ++c) vi[c][j] = cval;
+        vs[j] = 0;
+        continue;
+      }
+      double t[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) t[c] = 0.0;
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int d = 0; d < 2; ++d) {
+            const long long s = base + i1[0][a] * pst[0] + i1[1][b] * pst[1] + i1[2][d] * pst[2];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {  // per channel the corners in fit_kernel's order, each ((v * w0) * w1) * w2
+              double coeff = (double)si[c * V + s];
+              coeff = coeff * w[0][a];
+              coeff = coeff * w[1][b];
+              coeff = coeff * w[2][d];
+              t[c] = t[c] + coeff;
+            }
+          }
+#pragma unroll
+      for (int c = 0; c < C; ++c) vi[c][j] = apply_ops((float)t[c], p);
+      vs[j] = ss[base + i0[0] * pst[0] + i0[1] * pst[1] + i0[2] * pst[2]];
+    }
+  }
+  float* di = dst_img + (long long)n * C * TV + in_plane;
+  short* dsg = dst_seg + (long long)n * TV + in_plane;
+  if (VEC) {  // T2 % 4 == 0: every group is whole and 16-byte (image, every plane) / 8-byte (mask) aligned
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+      *reinterpret_cast<float4*>(di + c * TV) = make_float4(vi[c][0], vi[c][1], vi[c][2], vi[c][3]);
+    typedef short short4v __attribute__((ext_vector_type(4)));
+    short4v o;
+    o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2]; o[3] = vs[3];
+    *reinterpret_cast<short4v*>(dsg) = o;
+  } else {
+#pragma unroll
+    for (int j = 0; j < FIT_VEC; ++j) {  // unrolled: vi / vs stay in registers
+      if (j < cnt) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) di[c * TV + j] = vi[c][j];
+        dsg[j] = vs[j];
+      }
+    }
+  }
+}
+
+template <int C>
+void launch_fit_mc(bool vec, dim3 grid, hipStream_t st, const float* arena_img, const short* arena_seg, long long seg_elems,
+                   const long long* table, int n_cases, const double* params, int T0, int T1, int T2, float* dst_img,
+                   short* dst_seg) {
+  if (vec)
+    MSL_LAUNCH(fit_mc_kernel<C, true>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
+               params, T0, T1, T2, dst_img, dst_seg);
+  else
+    MSL_LAUNCH(fit_mc_kernel<C, false>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
+               params, T0, T1, T2, dst_img, dst_seg);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msl_foreground_box_mc(const float* vol, int C, int D, int H, int W, int margin, int* box, void* stream) {
+  if (!vol || !box || C < 1 || C > FIT_MAX_CH || D <= 0 || H <= 0 || W <= 0 || margin < 0) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long waves = ((long long)C * D * H + 3) / 4;
+  MSL_LAUNCH(fg_init_kernel, dim3(1), dim3(64), 0, st, box);
+  MSL_LAUNCH(fg_reduce_mc_kernel, dim3((unsigned)(waves < 512 ? waves : 512)), dim3(FG_THREADS), 0, st, vol, C, D, H, W,
+             box);
+  MSL_LAUNCH(fg_final_kernel, dim3(1), dim3(64), 0, st, D, H, W, margin, box);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+                       int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
+                       void* stream) {
+  if (!arena_img || !arena_seg || !table || !params || !dst_img || !dst_seg || seg_elems <= 0 || C < 1 ||
+      C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
+    return MSL_ERR_ARG;
+  const long long groups = (long long)T0 * T1 * ((T2 + FIT_VEC - 1) / FIT_VEC);
+  if (N > 65535 || (groups + DP_THREADS - 1) / DP_THREADS > 0x7FFFFFFFLL) return MSL_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((groups + DP_THREADS - 1) / DP_THREADS), N);
+  const bool vec = T2 % FIT_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (C) {
+    case 1: launch_fit_mc<1>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
+    case 2: launch_fit_mc<2>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
+    case 3: launch_fit_mc<3>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
+    default: launch_fit_mc<4>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
+  }
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+}  // extern "C"

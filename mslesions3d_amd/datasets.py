@@ -384,8 +384,12 @@ class ExampleDataset:
 
 def foreground_box(img, margin=5):
     """CropForegroundd(source_key="img", margin): F = {v : img[v] > 0}; per axis lo = max(min(F) - margin, 0),
-    hi = min(max(F) + margin + 1, n); an empty F keeps the whole volume.  -> (lo, hi), three ints each."""
+    hi = min(max(F) + margin + 1, n); an empty F keeps the whole volume.  -> (lo, hi), three ints each.  A channel-first
+    (C, D, H, W) image gives the box of the union F = {v : img[c, v] > 0 for any c} (CropForegroundd with
+    channel_indices=None), still three ints each."""
     img = np.asarray(img)
+    if img.ndim == 4:
+        img = (img > 0).any(0)
     fg = np.argwhere(img > 0)
     if fg.shape[0] == 0:
         return (0,) * img.ndim, tuple(img.shape)
@@ -395,10 +399,11 @@ def foreground_box(img, margin=5):
 
 
 def crop_foreground(img, seg, margin=5):
-    """Image and mask (D, H, W) cropped to ``foreground_box(img, margin)``."""
+    """Image (D, H, W) or (C, D, H, W) and mask (D, H, W) cropped to ``foreground_box(img, margin)``: one box for every
+    channel and the mask."""
     lo, hi = foreground_box(img, margin)
     sl = tuple(slice(a, b) for a, b in zip(lo, hi))
-    return img[sl], seg[sl]
+    return img[(slice(None),) * (np.ndim(img) - 3) + sl], seg[sl]
 
 
 def fit_shift(n, t):
@@ -450,7 +455,8 @@ def boxes_from_instances(seg, thresholds, mode="instances"):
 
 
 def normalize_nonzero(img):
-    """NormalizeIntensity(nonzero=True) as ``_Cases`` applies it: population mean / std over the non-zero voxels."""
+    """NormalizeIntensity(nonzero=True) as ``_Cases`` applies it: population mean / std over the non-zero voxels of the
+    whole array (``_LesionCases`` calls it once per channel)."""
     img = np.array(img, dtype=np.float32)
     nz = img != 0
     if nz.any():
@@ -462,7 +468,9 @@ def normalize_nonzero(img):
 class _LesionCases(Dataset):
     """The per-sample pipeline of LesionsDataModule (datasets.py:199-236): load -> crop_foreground(margin 5) ->
     NormalizeIntensity(nonzero) -> training augmentations at the cropped shape -> resize_with_pad_or_crop(replicate) ->
-    boxes ('instances' / 'binary' mode)."""
+    boxes ('instances' / 'binary' mode).  With C = len(input_images) > 1 the image is channel-first throughout: the crop
+    box is the union of the channels' foregrounds, every channel is normalised over its own non-zero voxels, and one set
+    of augmentation draws moves all channels and the mask (the intensity operands are shared, as in MONAI)."""
 
     def __init__(self, module, subjects, augmentations=None, seed=0):
         self.module, self.subjects = module, list(subjects)
@@ -483,20 +491,27 @@ class _LesionCases(Dataset):
         return len(self.subjects)
 
     def load(self, i):
-        """-> (image f32, mask) of case i as stored, (D, H, W) each."""
+        """-> (image f32, mask) of case i as stored: (D, H, W) each; with C > 1 sequences the image is (C, D, H, W),
+        stacked in ``input_images`` order."""
         m = self.module
         c, s = self.subjects[i]
-        img = _load(m._get_sequence(c, s, m.input_images[0])).astype(np.float32)
         seg = np.asarray(_load(m._get_sequence(c, s, m.segmentation)))
-        if img.ndim != 3 or seg.shape != img.shape:
-            raise ValueError(f"case {(c, s)}: image {img.shape} and mask {seg.shape} must be one 3-D shape")
-        return img, seg
+        imgs = []
+        for name in m.input_images:
+            img = _load(m._get_sequence(c, s, name)).astype(np.float32)
+            if img.ndim != 3 or seg.shape != img.shape:
+                raise ValueError(f"case {(c, s)}: image {name} {img.shape} and mask {seg.shape} must be one 3-D shape")
+            imgs.append(img)
+        return (imgs[0] if len(imgs) == 1 else np.stack(imgs)), seg
 
     def __getitem__(self, i):
         m = self.module
         img, seg = crop_foreground(*self.load(i), margin=m.margin)
-        img = normalize_nonzero(img)
-        img, seg = img[None], seg[None]  # add_channel
+        if img.ndim == 3:
+            img = normalize_nonzero(img)[None]  # add_channel
+        else:
+            img = np.stack([normalize_nonzero(ch) for ch in img])  # channel_wise: each sequence on its own scale
+        seg = seg[None]
         rs = self.sample_rng(i) if self.augmentations else None
         for t in self.augmentations:
             name, kw = (t, {}) if isinstance(t, str) else t
@@ -519,18 +534,34 @@ class LesionsDataModule(ExampleDataset):
     with "labeled" in it is instance-labelled ('instances' mode, thresholds [(1, inf)] for one class and
     [(1000, 2000), (2000, inf)] for two); any other name is a binary mask ('binary' mode, one class).
 
+    ``input_images`` names 1 .. 4 sequences (the stem's limit); the reference refuses more than one
+    (datasets.py:155-156), so the multi-sequence contract is this one: samples are (C,) + spatial_size in
+    ``input_images`` order; the foreground crop is the union of the channels' positive voxels (CropForegroundd with
+    channel_indices=None); and - a deviation from the reference's transform, which would pool the channels - each
+    sequence is normalised over its OWN non-zero voxels (NormalizeIntensity(channel_wise=True)): the mean and deviation of
+    two MR contrasts pooled describe neither.  At C = 1 both rules are the reference's.  With C > 1 every name must be an
+    MR sequence ``_get_sequence`` knows (anything else would be looked up among the lesion masks): NotImplementedError.
+
     Left out: ``fold`` (the reference indexes a list with an index array there and cannot run) and ``orientation`` /
     ``spacing``, which need NIfTI affines: the volumes must already be LPI at 1 mm.  Not in the reference:
     ``spatial_size`` (its fixed (250, 300, 300)), ``rank`` / ``world_size`` (this process's data-parallel shard)."""
 
     margin = 5  # crop_foreground
+    SEQUENCES = ("FLAIR", "acq-phase_T2star", "acq-mag_T2star")  # the images of _get_sequence; other names are masks
 
     def __init__(self, data_dir="../data/raw", centers=("CHUV_RIM_OK", "BASEL_INSIDER_OK"), input_images=("FLAIR",),
                  segmentation="labeled_lesions", classes=("lesion",), registration="T2star", skullstripped=True,
                  augmentations=None, subject=None, batch_size=8, percentage=1., num_workers=0, random_state=970205,
                  cache=False, spatial_size=(250, 300, 300), rank=0, world_size=1):
-        if len(input_images) != 1:
-            raise NotImplementedError("Only supports one sequence at a time.")
+        input_images = (input_images,) if isinstance(input_images, str) else tuple(input_images)
+        if not 1 <= len(input_images) <= 4:
+            raise ValueError(f"1 .. 4 input sequences (the stem's limit), got {len(input_images)}: {input_images}")
+        if len(set(input_images)) != len(input_images):
+            raise ValueError(f"duplicate input sequences: {input_images}")
+        unknown = [n for n in input_images if n not in self.SEQUENCES]
+        if len(input_images) > 1 and unknown:
+            raise NotImplementedError(f"input sequence(s) {unknown} are not among the MR sequences {self.SEQUENCES} whose "
+                                      f"files _get_sequence locates")
         self.data_dir, self.centers, self.registration = data_dir, tuple(centers), registration
         self.input_images, self.segmentation, self.skullstripped = tuple(input_images), segmentation, skullstripped
         self.classes, self.n_classes = tuple(classes), len(classes)
@@ -567,7 +598,7 @@ class LesionsDataModule(ExampleDataset):
 
     def _get_sequence(self, center, subject, img_name):
         """Path of an image or a segmentation without its extension (datasets.py:245-259)."""
-        if img_name in ("FLAIR", "acq-phase_T2star", "acq-mag_T2star"):
+        if img_name in self.SEQUENCES:
             if not self.skullstripped:
                 return pjoin(self._get_data_dir(center), f"sub-{subject}", "ses-01", "anat",
                              f"sub-{subject}_ses-01_{img_name}")

@@ -14,7 +14,8 @@ AFFINE_MAX_OPS intensity operations raise NotImplementedError.
 
 ``LesionCache`` is the counterpart for ``datasets.LesionsDataModule``: cases of unequal shape, cropped to their
 foreground, in one flat arena; shape-changing rot90s allowed; every batch padded / cropped to one fixed size and its
-instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes).
+instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes).  A module with
+C > 1 input sequences is cached channel-planar and goes through msl_foreground_box_mc / msl_augment_fit_mc.
 """
 from collections import namedtuple
 
@@ -522,13 +523,19 @@ class LesionCache:
     yields ``validation_step`` batches.  At construction every case is uploaded once, boxed by msl_foreground_box (the
     six ints are the build's only read-back), cropped into the arena and normalised there; the cropped cases are staged
     in tensors of their own until the arena's size is known.  A pipeline with two affine stages raises
-    NotImplementedError (a resample of a resample of a ragged case would need a ragged intermediate)."""
+    NotImplementedError (a resample of a resample of a ragged case would need a ragged intermediate).
+
+    With C = len(dataset.input_images) > 1 a case is C contiguous f32 planes starting at element C * offset of the image
+    arena (the mask arena and the table do not change): boxed as the union of the channels by msl_foreground_box_mc,
+    every plane normalised on its own (one msl_normalize_nonzero call over the case's C planes), batches written as
+    (N, C) + target by msl_augment_fit_mc.  C = 1 calls the one-channel entry points."""
 
     def __init__(self, dataset, device, max_objects_per_image=64):
         if dataset.train_dataset is None:
             raise ValueError("LesionCache needs a data module after setup()")
         self.dataset, self.device = dataset, torch.device(device)
         self.batch_size, self.target = int(dataset.batch_size), tuple(dataset.spatial_size)
+        self.channels = C = len(dataset.input_images)
         self.augmentations = list(dataset.train_dataset.augmentations)
         names = [(t if isinstance(t, str) else t[0]) for t in self.augmentations]
         if names.count("affine") > 1:
@@ -558,27 +565,30 @@ class LesionCache:
             seg16 = seg.astype(np.int16)
             if not np.array_equal(seg16, seg) or (seg16.size and seg16.min() < 0):
                 raise ValueError(f"LesionCache: mask of case {ds.subjects[i]} is not integer-valued in [0, 32767]")
-            self._check_memory(img.size * 6, f"case {ds.subjects[i]} of {img.shape}")
+            self._check_memory(seg.size * (4 * C + 2), f"case {ds.subjects[i]} of {img.shape}")
             vol = torch.from_numpy(img).to(dev)
-            _lib.call("msl_foreground_box", ptr(vol), *img.shape, int(dataset.margin), ptr(box), stream)
+            if C == 1:
+                _lib.call("msl_foreground_box", ptr(vol), *img.shape, int(dataset.margin), ptr(box), stream)
+            else:
+                _lib.call("msl_foreground_box_mc", ptr(vol), *img.shape, int(dataset.margin), ptr(box), stream)
             b = box.cpu().tolist()  # the one read that sizes the crop
             sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
-            staged.append((vol[sl].contiguous(), torch.from_numpy(seg16).to(dev)[sl].contiguous()))
+            staged.append((vol[(...,) + sl].contiguous(), torch.from_numpy(seg16).to(dev)[sl].contiguous()))
             self.shapes.append(tuple(b[3 + a] - b[a] for a in range(3)))
             del vol
         sizes = [int(np.prod(s)) for s in self.shapes]
         self.offsets = [0] + np.cumsum(sizes).tolist()
-        self.cache_bytes = self.offsets[-1] * 6
+        self.cache_bytes = self.offsets[-1] * (4 * C + 2)
         self._check_memory(self.cache_bytes, f"{len(sizes)} cropped cases")
-        self.img = torch.empty(max(self.offsets[-1], 1), dtype=torch.float32, device=dev)
+        self.img = torch.empty(C * max(self.offsets[-1], 1), dtype=torch.float32, device=dev)
         self.seg = torch.empty(max(self.offsets[-1], 1), dtype=torch.int16, device=dev)
         for k in range(len(sizes)):
             ci, cs = staged[k]
             staged[k] = None
-            self.img[self.offsets[k]:self.offsets[k + 1]].copy_(ci.reshape(-1))
+            self.img[C * self.offsets[k]:C * self.offsets[k + 1]].copy_(ci.reshape(-1))
             self.seg[self.offsets[k]:self.offsets[k + 1]].copy_(cs.reshape(-1))
-            if sizes[k]:
-                _lib.call("msl_normalize_nonzero", self.img.data_ptr() + 4 * self.offsets[k], 1, sizes[k], stream)
+            if sizes[k]:  # C contiguous volumes, each over its own non-zero voxels
+                _lib.call("msl_normalize_nonzero", self.img.data_ptr() + 4 * C * self.offsets[k], C, sizes[k], stream)
         self.table = torch.tensor([[self.offsets[k], *self.shapes[k]] for k in range(len(sizes))],
                                   dtype=torch.int64, device=dev).reshape(-1, 4)
         self.capacity = int(max_objects_per_image) * self.batch_size
@@ -591,9 +601,10 @@ class LesionCache:
                               f"{self.device}")
 
     def case(self, slot):
-        """-> (image f32, mask int16) views of a cached case, shaped."""
-        a, b = self.offsets[slot], self.offsets[slot + 1]
-        return self.img[a:b].view(self.shapes[slot]), self.seg[a:b].view(self.shapes[slot])
+        """-> (image f32, mask int16) views of a cached case, shaped; the image is (C, n0, n1, n2) for C > 1."""
+        a, b, C = self.offsets[slot], self.offsets[slot + 1], self.channels
+        shape = tuple(self.shapes[slot])
+        return self.img[C * a:C * b].view(shape if C == 1 else (C,) + shape), self.seg[a:b].view(shape)
 
     # ---- footprint ----------------------------------------------------------------------------------------------------
     def nbytes(self):
@@ -614,7 +625,7 @@ class LesionCache:
         b = self._bufs.get(N)
         if b is None:
             dev = self.device
-            b = self._bufs[N] = {"img": torch.empty((N, 1) + self.target, dtype=torch.float32, device=dev),
+            b = self._bufs[N] = {"img": torch.empty((N, self.channels) + self.target, dtype=torch.float32, device=dev),
                                  "seg": torch.empty((N,) + self.target, dtype=torch.int16, device=dev),
                                  "box": _InstBoxOut(N, self.target, self.dataset.thresholds, self.capacity, dev)}
         return b
@@ -623,8 +634,12 @@ class LesionCache:
         stream = _stream(self.device)
         rows = fit_rows(slots, per_sample)
         pd = torch.from_numpy(rows.reshape(-1)).pin_memory().to(self.device, non_blocking=True)
-        _lib.call("msl_augment_fit", ptr(self.img), ptr(self.seg), self.img.numel(), ptr(self.table), len(self.shapes),
-                  ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
+        if self.channels == 1:
+            _lib.call("msl_augment_fit", ptr(self.img), ptr(self.seg), self.img.numel(), ptr(self.table), len(self.shapes),
+                      ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
+        else:
+            _lib.call("msl_augment_fit_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table),
+                      len(self.shapes), ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
         b["box"].launch(b["seg"], stream)
 
     def train_batches(self, epoch):

@@ -35,6 +35,8 @@ def build_parser():
     p.add_argument('-dm', '--data_module', choices=["example", "lesions"], default="example")
     p.add_argument('--centers', type=str, nargs='+', default=['CHUV_RIM_OK', 'BASEL_INSIDER_OK'])
     p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
+    # the MR sequences of a clinical case, one input channel each: the ones the checkpoint was trained with, in order
+    p.add_argument('-ii', '--input_images', type=str, nargs='+', default=["FLAIR"])
     return p
 
 
@@ -88,7 +90,9 @@ def predict_example(args):
     subjects are dealt round-robin over N replicas (one GPU each) and rank 0 writes the files and the metrics."""
     from .datasets import ExampleDataset, LesionsDataModule, ShardSampler
     from .ssd3d import LSSD3D
+    from .train import check_input_channels, input_images_of
     from .utils import calculate_mAP
+    input_images = input_images_of(args)
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     if world > 1:
         from .parallel import init_distributed
@@ -100,8 +104,10 @@ def predict_example(args):
     dev = torch.device("cuda", local)
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
-    if getattr(args, "data_module", "example") == "lesions":
+    lesions = getattr(args, "data_module", "example") == "lesions"
+    if lesions:
         dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), batch_size=1,
+                                    input_images=input_images,
                                     classes=("lesion",) if args.n_classes == 1 else ("lesion", "lesion_2"),
                                     num_workers=args.num_workers, subject=args.subject, percentage=args.percentage,
                                     spatial_size=tuple(args.spatial_size))
@@ -109,7 +115,10 @@ def predict_example(args):
         dataset = ExampleDataset(n_classes=args.n_classes, batch_size=1, num_workers=args.num_workers, subject=args.subject,
                                  percentage=args.percentage, data_dir=args.dataset_path, dataset_name=args.dataset_name)
     dataset.setup(stage="predict_train" if args.predict_subset == "train" else "predict")
-    model = LSSD3D.load_from_checkpoint(args.model_path, min_score=args.min_score).to(dev).eval()
+    model = LSSD3D.load_from_checkpoint(args.model_path, min_score=args.min_score)
+    if lesions:
+        check_input_channels(model, input_images, args.model_path)
+    model = model.to(dev).eval()
     model.top_k, model.min_score = args.top_k, args.min_score  # predict.py:259-260
     model.compute_dtype = getattr(args, "dtype", "f32")
     ds = dataset.predict_dataset

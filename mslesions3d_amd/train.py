@@ -3,7 +3,7 @@
 
     python -m mslesions3d_amd.train -d DATA -dn NAME -b 2 -me 2 -ld LOGS
 
-dataset -> LSSD3D(n_classes + 1, input_channels=1, ...) -> loop {training_step-equivalent fused step, validation at
+dataset -> LSSD3D(n_classes + 1, input_channels=len(input_images), ...) -> loop {training_step-equivalent fused step, validation at
 epoch end} -> metrics as JSONL with the reference's scalar names -> top-3 checkpoints by ``avg_val_loss`` ->
 early stopping on the validation loss (patience 5) -> stop at ``max_iterations`` / ``max_epochs``.
 
@@ -64,7 +64,24 @@ def build_parser():
     p.add_argument('-dm', '--data_module', choices=["example", "lesions"], default="example")
     p.add_argument('--centers', type=str, nargs='+', default=['CHUV_RIM_OK', 'BASEL_INSIDER_OK'])
     p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
+    # the MR sequences of a clinical case, one input channel each (1 .. 4); the synthetic cases have one channel
+    p.add_argument('-ii', '--input_images', type=str, nargs='+', default=["FLAIR"])
     return p
+
+
+def input_images_of(args):
+    """The sequences named by -ii; more than one with the synthetic data module is an error (its cases have one channel)."""
+    names = tuple(getattr(args, "input_images", None) or ("FLAIR",))
+    if getattr(args, "data_module", "example") != "lesions" and len(names) > 1:
+        raise ValueError(f"-dm example generates one-channel cases; {len(names)} input images were named: {' '.join(names)}")
+    return names
+
+
+def check_input_channels(model, input_images, checkpoint):
+    """A checkpoint's network reads as many channels as it was trained with: refuse another number of sequences."""
+    if int(model.input_channels) != len(input_images):
+        raise ValueError(f"{checkpoint} holds a network with input_channels={model.input_channels}, but "
+                         f"{len(input_images)} input image(s) were named: {' '.join(input_images)}")
 
 
 def _dist_env():
@@ -97,6 +114,7 @@ def example(args):
     from .datasets import ExampleDataset, LesionsDataModule, select_augmentations
     from .ssd3d import LSSD3D
     from .trainer import FusedTrainer
+    input_images = input_images_of(args)  # before the first GPU call: a refused command line touches no device
     world, rank, local = _dist_env()
     dp = world > 1
     if dp:  # join the job BEFORE the first GPU call of this process (RCCL binds the communicator to the device)
@@ -115,6 +133,7 @@ def example(args):
     lesions = getattr(args, "data_module", "example") == "lesions"
     if lesions:
         dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), subject=args.subject,
+                                    input_images=input_images,
                                     classes=("lesion",) if args.n_classes == 1 else ("lesion", "lesion_2"),
                                     percentage=args.percentage, num_workers=args.num_workers, batch_size=args.batch_size,
                                     augmentations=augmentations, random_state=970205,
@@ -129,8 +148,9 @@ def example(args):
     threshold = args.threshold if len(args.threshold) > 1 else [args.threshold[0]]
     if args.checkpoint:
         model = LSSD3D.load_from_checkpoint(args.checkpoint)
+        check_input_channels(model, input_images, args.checkpoint)
     else:
-        model = LSSD3D(n_classes=args.n_classes + 1, input_channels=1, lr=args.learning_rate, width_mult=args.width_mult,
+        model = LSSD3D(n_classes=args.n_classes + 1, input_channels=len(input_images), lr=args.learning_rate, width_mult=args.width_mult,
                        scheduler=args.scheduler, batch_size=args.batch_size, comments=args.comments, input_size=input_size,
                        compute_metric_every_n_epochs=args.compute_metric_every_n_epochs, use_wandb=False,
                        aspect_ratios=aspect_ratios, scales=scales, alpha=args.alpha, threshold=threshold,

@@ -494,6 +494,26 @@ int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long
                        int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
                        void* stream);
 
+/* ---- prediction overlays (csrc/overlay.hip, devicedata.LesionPredictFeed, predict.py -si 1) ----
+ * Packed detections of N images: boxes (K,6) f32 corner boxes, labels (K) i64, scores (K) f32 on the device; offsets
+ * (HOST, N + 1 ints, read during the call): image n owns rows offsets[n] .. offsets[n+1].  Both launch on `stream` and
+ * do not synchronise.
+ * msl_boxes_to_case: datasets.fit_to_case_frame, bit for bit.  geometry (HOST, N x 12 ints, read during the call): per
+ * image the fitted size t[3], the cropped size n[3], the crop origin lo[3] and the case's size s[3].  Per axis
+ * d = -((t - n) / 2) where n < t and n / 2 - t / 2 otherwise; every coordinate c of that axis becomes
+ * (c * t + (d + lo)) / s: one f32 multiply, one add, one divide, each rounded, no contraction.  Not clamped.
+ * -1: N < 1, a negative or decreasing offset, a size < 1 or an origin < 0.  out may be boxes.
+ * msl_draw_boxes: utils.draw_boxes, bit for bit.  instances / classes (N,D,H,W) i16 (classes may be null); style 0
+ * "edges" (the reference's make_segmentation_from_bboxes), 1 "preds" (its save_predictions_example, which also skips
+ * scores < min_score).  Voxel box = trunc(clip(box, 0, 1) * size) as an f32 product, max = min(max + style, size - 1).
+ * Every voxel of both planes is written exactly once (no memset needed): j + 1 and the label of the last box of the
+ * image, counting skipped ones, whose assignments cover it, else 0.  -1 (nothing written): style not 0 / 1, a size
+ * < 1, N < 1, a negative or decreasing offset, more than 32766 boxes in one image (j + 1 is an int16). */
+#define MSL_DRAW_BOXES_CHUNK 256 /* boxes a workgroup stages in LDS at a time */
+int msl_boxes_to_case(const float* boxes, const int* offsets, const int* geometry, int N, float* out, void* stream);
+int msl_draw_boxes(const float* boxes, const long long* labels, const float* scores, const int* offsets, int N, int D,
+                   int H, int W, int style, double min_score, short* instances, short* classes, void* stream);
+
 /* ---- optimiser + NaN guard : ssd3d.py:704-722, :258-261 ---------------------------------------------------- */
 /* hp (device, 8 floats): step_size(bias), step_size(other), sqrt(bias_correction2), beta1, beta2, eps,
  * weight_decay, gradient scale.  is_bias (n bytes): 1 for elements of '.bias' parameters (2*lr group). */

@@ -142,6 +142,8 @@ _SIGNATURES = {
     "msl_instance_boxes": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "msl_foreground_box_mc": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "msl_augment_fit_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "msl_boxes_to_case": (_I, [_P, _P, _P, _I, _P, _P]),
+    "msl_draw_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P]),
     "msl_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "msl_nan_flag": (_I, [_P, _Z, _P, _I, _P]),
     "msl_nan_flag2": (_I, [_P, _Z, _I, _P, _Z, _I, _P, _P]),
@@ -163,6 +165,8 @@ _SIGNATURES = {
     "msl_event_record": (_I, [_P, _P]),
     "msl_stream_wait_event": (_I, [_P, _P]),
 }
+
+DRAW_BOXES_CHUNK = 256  # MSL_DRAW_BOXES_CHUNK of the header: boxes msl_draw_boxes stages in LDS at a time
 
 _lib = None
 

@@ -313,14 +313,21 @@ class _Cases(Dataset):
                 "img_meta_dict": {"affine": np.eye(4)}, "seg_meta_dict": {}, "img_transforms": [], "seg_transforms": []}
 
 
+GEOMETRY_KEYS = ("crop_origin", "crop_shape", "full_shape")
+
+
 def collate_fn(batch):
     """datasets.py:50-95: images stacked, ragged boxes / labels kept as lists."""
     boxes = [b["boxes"] for b in batch]
     labels = [b["labels"] for b in batch]
-    return {"img": torch.stack([b["img"] for b in batch], 0), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
-            "subject": [b["subject"] for b in batch], "img_meta_dict": [b["img_meta_dict"] for b in batch],
-            "seg_meta_dict": [b["seg_meta_dict"] for b in batch], "img_transforms": [b["img_transforms"] for b in batch],
-            "seg_transforms": [b["seg_transforms"] for b in batch]}
+    out = {"img": torch.stack([b["img"] for b in batch], 0), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
+           "subject": [b["subject"] for b in batch], "img_meta_dict": [b["img_meta_dict"] for b in batch],
+           "seg_meta_dict": [b["seg_meta_dict"] for b in batch], "img_transforms": [b["img_transforms"] for b in batch],
+           "seg_transforms": [b["seg_transforms"] for b in batch]}
+    for key in GEOMETRY_KEYS:  # LesionsDataModule samples carry them; passed through as lists
+        if all(key in b for b in batch):
+            out[key] = [b[key] for b in batch]
+    return out
 
 
 class ExampleDataset:
@@ -425,6 +432,29 @@ def resize_with_pad_or_crop(vol, spatial_size):
     return vol
 
 
+def fit_to_case_frame(boxes, target, crop_shape, crop_origin, full_shape):
+    """Corner boxes, fractional in the fitted frame of ``target`` voxels -> the same boxes, fractional in the case's own
+    frame of ``full_shape`` voxels.  ``boxes`` (K, 6) float32; ``crop_shape`` / ``crop_origin`` are the shape and the ``lo``
+    of the case's ``foreground_box`` crop.  Per axis, with t, n, lo, s from the four shape arguments and d =
+    ``fit_shift(n, t)``, fitted voxel o shows cropped voxel o + d, which is voxel o + d + lo of the case, so a
+    coordinate c becomes ``(c * t + (d + lo)) / s``: in float32, one multiply, one add of the integer d + lo, one divide.
+    Boxes are not clamped (``detect_objects`` returns unclamped boxes; the drawing clips).
+
+    This inverts the crop and the fit (steps 1 and 4 of ``_LesionCases``) only: it is defined for the un-augmented
+    pipeline, i.e. the predict and validation data sets.  Where the fit CROPS an axis, a lesion outside the kept window
+    is not in the fitted mask and a lesion across its border maps back as its part inside the window.
+    ``msl_boxes_to_case`` (csrc/overlay.hip) computes the same values on the device, bit for bit."""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 6)
+    t = np.asarray(target, dtype=np.int64)
+    n = np.asarray(crop_shape, dtype=np.int64)
+    add = np.asarray([fit_shift(int(a), int(b)) for a, b in zip(n, t)], dtype=np.int64) + np.asarray(crop_origin, dtype=np.int64)
+    s = np.asarray(full_shape, dtype=np.int64)
+    if not (t.shape == n.shape == add.shape == s.shape == (3,)):
+        raise ValueError("fit_to_case_frame: target, crop_shape, crop_origin and full_shape are three ints each")
+    t2, add2, s2 = (np.tile(v, 2).astype(np.float32) for v in (t, add, s))
+    return (boxes * t2 + add2) / s2
+
+
 def boxes_from_instances(seg, thresholds, mode="instances"):
     """BoundingBoxesGeneratord, 'instances' mode (utils.py:442-443, 472-481, 485-513) on an instance-labelled mask: the
     ids are the sorted unique values with the FIRST one discarded (the background - on a mask without background the
@@ -506,7 +536,12 @@ class _LesionCases(Dataset):
 
     def __getitem__(self, i):
         m = self.module
-        img, seg = crop_foreground(*self.load(i), margin=m.margin)
+        img, seg = self.load(i)
+        full_shape = tuple(int(v) for v in seg.shape)
+        lo, hi = foreground_box(img, m.margin)
+        sl = tuple(slice(a, b) for a, b in zip(lo, hi))  # crop_foreground
+        img, seg = img[(slice(None),) * (img.ndim - 3) + sl], seg[sl]
+        crop_shape = tuple(int(b - a) for a, b in zip(lo, hi))
         if img.ndim == 3:
             img = normalize_nonzero(img)[None]  # add_channel
         else:
@@ -521,7 +556,9 @@ class _LesionCases(Dataset):
         boxes, labels = boxes_from_instances(seg, m.thresholds, m.segmentation_mode)
         return {"img": torch.from_numpy(img), "boxes": boxes, "labels": labels, "seg": [boxes, labels],
                 "subject": self.subjects[i], "img_meta_dict": {"affine": np.eye(4)}, "seg_meta_dict": {},
-                "img_transforms": [], "seg_transforms": []}
+                "img_transforms": [], "seg_transforms": [],
+                # the geometry fit_to_case_frame needs: the crop's lo and shape, the case's shape
+                "crop_origin": lo, "crop_shape": crop_shape, "full_shape": full_shape}
 
 
 class LesionsDataModule(ExampleDataset):

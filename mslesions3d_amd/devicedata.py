@@ -559,7 +559,7 @@ class LesionCache:
         self.val_order = [(te.subjects[i], self.slot[te.subjects[i]]) for i in val_idx]
         dev, stream = self.device, _stream(self.device)
         box = torch.zeros(6, dtype=torch.int32, device=dev)
-        staged, self.shapes = [], []
+        staged, self.shapes, self.origins, self.full_shapes = [], [], [], []
         for ds, i in loaders:
             img, seg = ds.load(i)
             seg16 = seg.astype(np.int16)
@@ -575,6 +575,8 @@ class LesionCache:
             sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
             staged.append((vol[(...,) + sl].contiguous(), torch.from_numpy(seg16).to(dev)[sl].contiguous()))
             self.shapes.append(tuple(b[3 + a] - b[a] for a in range(3)))
+            self.origins.append(tuple(b[:3]))  # the crop's lo: datasets.fit_to_case_frame maps boxes back with it
+            self.full_shapes.append(tuple(int(v) for v in seg.shape))
             del vol
         sizes = [int(np.prod(s)) for s in self.shapes]
         self.offsets = [0] + np.cumsum(sizes).tolist()
@@ -670,4 +672,123 @@ class LesionCache:
             boxes = [box.gb[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
             labels = [box.gl[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
             yield {"img": b["img"].clone(), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
-                   "subject": [s for s, _ in chunk]}
+                   "subject": [s for s, _ in chunk], "crop_origin": [self.origins[slot] for _, slot in chunk],
+                   "crop_shape": [tuple(self.shapes[slot]) for _, slot in chunk],
+                   "full_shape": [self.full_shapes[slot] for _, slot in chunk]}
+
+
+def boxes_to_case_device(boxes, target, crop_shape, crop_origin, full_shape):
+    """``datasets.fit_to_case_frame`` on the HIP device (msl_boxes_to_case, current stream, no synchronisation), bit for
+    bit.  ``boxes``: a (K, 6) device tensor with one geometry, or a list of N of them with a list of N geometries each."""
+    single = torch.is_tensor(boxes)
+    if single:
+        boxes, target, crop_shape, crop_origin, full_shape = [boxes], [target], [crop_shape], [crop_origin], [full_shape]
+    if not all(b.is_cuda for b in boxes):
+        raise _lib.HipKernelError("boxes_to_case_device takes tensors on the HIP device (no CPU fallback)")
+    flat = [b.contiguous().float().reshape(-1, 6) for b in boxes]
+    off = np.concatenate([[0], np.cumsum([b.shape[0] for b in flat])]).astype(np.int32)
+    geo = np.ascontiguousarray(np.asarray([list(t) + list(n) + list(lo) + list(s) for t, n, lo, s in
+                                           zip(target, crop_shape, crop_origin, full_shape)], dtype=np.int32).reshape(-1, 12))
+    packed = flat[0] if single else torch.cat(flat)
+    out = torch.empty_like(packed)
+    _lib.call("msl_boxes_to_case", ptr(packed), off.ctypes.data, geo.ctypes.data, len(flat), ptr(out), _stream(packed.device))
+    return out if single else [out[off[n]:off[n + 1]] for n in range(len(flat))]
+
+
+class LesionPredictFeed:
+    """``dataset.predict_dataset`` of a ``setup()`` ``datasets.LesionsDataModule`` as batches of one, prepared on the
+    device case by case: upload, msl_foreground_box[_mc], crop, msl_normalize_nonzero, msl_augment_fit[_mc] with the
+    identity row into a (1, C) + spatial_size batch, msl_instance_boxes on the fitted mask - the kernels ``LesionCache``
+    runs, on one case at a time, so nothing but the case being prepared and the batches handed out is resident.
+
+    ``batches(indices)`` yields ``{"img", "subject", "boxes", "labels", "crop_origin", "crop_shape", "full_shape"}`` (and
+    "seg": [boxes, labels]) in the order of ``indices`` (default: every case): "img" a device tensor, valid until the
+    next batch is drawn (``predict_batches`` copies it into its own buffer at once); "boxes" / "labels" the ground truth of the host data set on the host, bit for bit; the
+    geometry keys as lists, as ``collate_fn`` passes them.  The six ints of the foreground box are the only host round
+    trip per case: the ground-truth counts of case k come over in pinned memory and are read after case k + 1's box read
+    has synchronised the stream, so the feed prepares one case ahead of the one it hands out.  With
+    ``LSSD3D.predict_batches(feed.batches(), depth)`` at most depth + 1 cases are resident."""
+
+    def __init__(self, dataset, device, max_objects_per_image=64):
+        if dataset.predict_dataset is None:
+            raise ValueError("LesionPredictFeed needs a data module after setup()")
+        if dataset.segmentation_mode != "instances":
+            raise NotImplementedError("LesionPredictFeed: the device pipeline labels instance masks ('labeled' segmentations)")
+        self.dataset, self.device = dataset, torch.device(device)
+        self.target, self.channels = tuple(dataset.spatial_size), len(dataset.input_images)
+        self.capacity = int(max_objects_per_image)
+        dev, C = self.device, self.channels
+        self._box = torch.zeros(6, dtype=torch.int32, device=dev)
+        self._row = torch.from_numpy(fit_rows([0], [(([0, 1, 2], [0, 0, 0]), [])]).reshape(-1)).to(dev)  # the identity row
+        self._slots = [{"img": torch.empty((1, C) + self.target, dtype=torch.float32, device=dev),
+                        "seg": torch.empty((1,) + self.target, dtype=torch.int16, device=dev),
+                        "box": _InstBoxOut(1, self.target, dataset.thresholds, self.capacity, dev),
+                        "gb": torch.zeros((max(self.capacity, 1), 6), dtype=torch.float32, pin_memory=True),
+                        "gl": torch.zeros(max(self.capacity, 1), dtype=torch.int64, pin_memory=True),
+                        "off": torch.zeros(2, dtype=torch.int32, pin_memory=True)} for _ in range(2)]
+
+    def __len__(self):
+        return len(self.dataset.predict_dataset)
+
+    def __iter__(self):
+        return self.batches()
+
+    def _start(self, pos, k):
+        """Everything of case ``pos`` enqueued; the box read is the one wait."""
+        ds, dev, C, stream = self.dataset.predict_dataset, self.device, self.channels, _stream(self.device)
+        img, seg = ds.load(pos)
+        seg16 = seg.astype(np.int16)
+        if not np.array_equal(seg16, seg) or (seg16.size and seg16.min() < 0):
+            raise ValueError(f"LesionPredictFeed: mask of case {ds.subjects[pos]} is not integer-valued in [0, 32767]")
+        vol = torch.from_numpy(img).to(dev)
+        if C == 1:
+            _lib.call("msl_foreground_box", ptr(vol), *img.shape, int(self.dataset.margin), ptr(self._box), stream)
+        else:
+            _lib.call("msl_foreground_box_mc", ptr(vol), *img.shape, int(self.dataset.margin), ptr(self._box), stream)
+        b = self._box.cpu().tolist()  # the one read that sizes the crop
+        sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
+        shape = tuple(b[3 + a] - b[a] for a in range(3))
+        ci = vol[(...,) + sl].contiguous()
+        cs = torch.from_numpy(seg16).to(dev)[sl].contiguous()
+        del vol
+        size = int(np.prod(shape))
+        slot = self._slots[k % 2]
+        if size:
+            _lib.call("msl_normalize_nonzero", ptr(ci), C, size, stream)
+        table = torch.tensor([[0, *shape]], dtype=torch.int64).to(dev)
+        if C == 1:
+            _lib.call("msl_augment_fit", ptr(ci), ptr(cs), max(size, 1), ptr(table), 1, ptr(self._row), 1, *self.target,
+                      ptr(slot["img"]), ptr(slot["seg"]), stream)
+        else:
+            _lib.call("msl_augment_fit_mc", ptr(ci), ptr(cs), max(size, 1), C, ptr(table), 1, ptr(self._row), 1,
+                      *self.target, ptr(slot["img"]), ptr(slot["seg"]), stream)
+        box = slot["box"]
+        box.launch(slot["seg"], stream)
+        slot["gb"].copy_(box.gb, non_blocking=True)
+        slot["gl"].copy_(box.gl, non_blocking=True)
+        slot["off"].copy_(box.obj_off, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        # (ci, cs and table are released on return: the caching allocator hands a freed block to this stream's later work
+        #  only, which is ordered behind these launches)
+        return {"slot": slot, "subject": ds.subjects[pos], "crop_origin": tuple(b[:3]), "crop_shape": shape,
+                "full_shape": tuple(int(v) for v in seg.shape), "done": done}
+
+    def _finish(self, h):
+        slot = h["slot"]
+        slot["box"].raise_on_overflow()
+        n = int(slot["off"][1])
+        boxes, labels = [slot["gb"][:n].clone()], [slot["gl"][:n].clone()]
+        return {"img": slot["img"], "seg": [boxes, labels], "boxes": boxes, "labels": labels, "subject": [h["subject"]],
+                "crop_origin": [h["crop_origin"]], "crop_shape": [h["crop_shape"]], "full_shape": [h["full_shape"]]}
+
+    def batches(self, indices=None):
+        pending = None
+        for k, pos in enumerate(range(len(self)) if indices is None else indices):
+            cur = self._start(int(pos), k)  # (its box read has waited for everything of the pending case)
+            if pending is not None:
+                yield self._finish(pending)
+            pending = cur
+        if pending is not None:
+            pending["done"].synchronize()
+            yield self._finish(pending)

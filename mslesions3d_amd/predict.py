@@ -2,14 +2,20 @@
 ``predict_example`` (``predict.py:235-281``): load checkpoint -> predict every subject -> write
 ``sub-XXXX_preds.json`` (``{j+1: [box_frac(6), box_voxel(6), label, score]}``, ``predict.py:149,222-232``) and
 ``sub-XXXX_preds.csv`` (``label_id,score``) -> per-subject mAP at IoU 0.5 and 0.1 (``predict.py:87-152``).
-NIfTI overlays are not written (nibabel absent; out of scope).
+With ``-si 1`` the box overlay the reference saves as ``sub-XXXX_preds.nii.gz`` (``predict.py:176-226``) is written as
+``sub-XXXX_preds.npy`` (int16; NIfTI is out of scope).  For clinical cases (``-dm lesions``) the overlay
+is drawn in the CASE's own frame, and ``sub-XXXX_preds_case.json`` holds the detections in that frame
+(``datasets.fit_to_case_frame``); ``--cache 1`` prepares the cases on the device (``devicedata.LesionPredictFeed``) and
+maps and draws there too (msl_boxes_to_case, msl_draw_boxes).  DESIGN.md §4.9.
 
     python -m mslesions3d_amd.predict -d DATA -dn NAME -m CKPT -o OUT
+    python -m mslesions3d_amd.predict -dm lesions -d RAW -m CKPT -o OUT --cache 1 -si 1
 """
 import argparse
 import json
 import collections
 import os
+import warnings
 from os.path import join as pjoin
 
 import numpy as np
@@ -37,7 +43,48 @@ def build_parser():
     p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
     # the MR sequences of a clinical case, one input channel each: the ones the checkpoint was trained with, in order
     p.add_argument('-ii', '--input_images', type=str, nargs='+', default=["FLAIR"])
+    p.add_argument('-mn', '--model_name', type=str, default=None, help="sub-directory of the output path (predict.py:241)")
+    p.add_argument('-si', '--save_images', type=int, default=0,
+                   help="1: write the box overlay of every subject as sub-XXXX_preds.npy (with -dm lesions in the case's own "
+                        "frame, plus sub-XXXX_preds_case.json).  The reference's default is 1; it is 0 here so that no "
+                        "existing command starts writing volumes")
+    # the reference's (and this parser's) -c is --n_classes, so the device feed has the long spelling only
+    p.add_argument('--cache', type=int, default=0,
+                   help="with -dm lesions, 1: prepare every case on the device (devicedata.LesionPredictFeed) and map and "
+                        "draw the overlays there; ignored with a warning for the example module")
     return p
+
+
+def output_dir_of(args):
+    """predict.py:240-241: the model's name, when given, is a sub-directory of the output path."""
+    name = getattr(args, "model_name", None)
+    return args.output_dir if name is None else pjoin(args.output_dir, name)
+
+
+def prediction_infos(boxes, labels, scores, min_score, img_shape):
+    """``{j + 1: (box_frac(6), box_voxel(6), label, score)}`` of the detections the reference keeps (predict.py:186-222)."""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 6)
+    scores = np.asarray(scores, dtype=np.float32).reshape(-1)
+    shape2 = np.asarray(tuple(img_shape) * 2, dtype=np.float32)
+    infos = {}
+    for j in range(boxes.shape[0]):
+        score = float(scores[j])
+        if score < min_score or int(labels[j]) == 0:
+            continue
+        frac = [float(v) for v in boxes[j]]
+        vox = (np.clip(boxes[j], np.float32(0), np.float32(1)) * shape2).astype(int).tolist()
+        infos[j + 1] = (frac, vox, int(labels[j]), score)
+    return infos
+
+
+def save_case_predictions(subject, record, target, min_score, output_dir):
+    """``sub-XXXX_preds_case.json``: the schema of ``sub-XXXX_preds.json`` with the boxes in the case's own frame -
+    ``fit_to_case_frame`` of the fitted-frame boxes, fractional and as voxels of ``full_shape``."""
+    from .datasets import fit_to_case_frame
+    case = fit_to_case_frame(np.asarray(record["boxes"], np.float32), target, record["crop_shape"], record["crop_origin"],
+                             record["full_shape"])
+    with open(pjoin(output_dir, f"sub-{subject}_preds_case.json"), "w") as f:
+        json.dump(prediction_infos(case, record["labels"], record["scores"], min_score, record["full_shape"]), f)
 
 
 def save_predictions(subject, img_shape, boxes, labels, scores, min_score, output_dir):
@@ -102,9 +149,15 @@ def predict_example(args):
         init_distributed(backend, rank=rank, world_size=world, device=torch.device("cuda", local) if backend == "nccl" else None)
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    if rank == 0:
-        os.makedirs(args.output_dir, exist_ok=True)
+    output_dir = output_dir_of(args)
+    save_images = bool(getattr(args, "save_images", 0))
+    if rank == 0 or save_images:  # (every rank writes the overlays of its own subjects)
+        os.makedirs(output_dir, exist_ok=True)
     lesions = getattr(args, "data_module", "example") == "lesions"
+    cache = bool(getattr(args, "cache", 0))
+    if cache and not lesions:
+        warnings.warn("--cache 1 prepares clinical cases on the device (-dm lesions); ignored for the example module")
+        cache = False
     if lesions:
         dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), batch_size=1,
                                     input_images=input_images,
@@ -127,24 +180,38 @@ def predict_example(args):
     queued = collections.deque()  # (position, batch) of the passes in flight: predict_batches yields results in order
 
     def feed():
-        for pos in mine:
-            batch = collate([ds[pos]])
-            queued.append((pos, batch))
+        if cache:  # cropped, normalised and fitted on the device, one case ahead of the pass
+            from .devicedata import LesionPredictFeed
+            source = zip(mine, LesionPredictFeed(dataset, dev).batches(mine))
+        else:
+            source = ((pos, collate([ds[pos]])) for pos in mine)
+        for pos, batch in source:
+            # (the device feed reuses its image buffer: only what the records need is kept)
+            queued.append((pos, {k: (tuple(v.shape[2:]) if k == "img" else v) for k, v in batch.items() if k != "seg"}))
             yield batch
 
     for boxes, labels, scores in model.predict_batches(feed(), depth=2):
         pos, batch = queued.popleft()
         subj = batch["subject"][0]
-        records.append((pos, subj if isinstance(subj, str) else "_".join(subj),
-                        {"shape": tuple(batch["img"].shape[2:]), "boxes": boxes[0].cpu().numpy().tolist(),
-                         "labels": labels[0].cpu().numpy().tolist(), "scores": scores[0].cpu().numpy().tolist(),
-                         "gt_boxes": batch["boxes"][0].numpy().tolist(), "gt_labels": batch["labels"][0].numpy().tolist()}))
+        subj = subj if isinstance(subj, str) else "_".join(subj)
+        rec = {"shape": batch["img"], "boxes": boxes[0].cpu().numpy().tolist(),
+               "labels": labels[0].cpu().numpy().tolist(), "scores": scores[0].cpu().numpy().tolist(),
+               "gt_boxes": batch["boxes"][0].numpy().tolist(), "gt_labels": batch["labels"][0].numpy().tolist()}
+        if lesions:
+            rec.update({k: tuple(batch[k][0]) for k in ("crop_origin", "crop_shape", "full_shape")})
+        if save_images:
+            np.save(pjoin(output_dir, f"sub-{subj}_preds.npy"),
+                    overlay_volume(rec, boxes[0], labels[0], scores[0], tuple(args.spatial_size) if lesions else None,
+                                   args.min_score, on_device=cache))
+        records.append((pos, subj, rec))
     merged = gather_detections(records, world, rank)
     metrics = {"0.5": {}, "0.1": {}}
     if merged is not None:
         for _, subj, r in merged:
             save_predictions(subj, r["shape"], np.asarray(r["boxes"], np.float32), np.asarray(r["labels"]),
-                             np.asarray(r["scores"], np.float32), args.min_score, args.output_dir)
+                             np.asarray(r["scores"], np.float32), args.min_score, output_dir)
+            if save_images and lesions:
+                save_case_predictions(subj, r, tuple(args.spatial_size), args.min_score, output_dir)
             det_b = [torch.tensor(r["boxes"], dtype=torch.float32).reshape(-1, 6)]
             det_l = [torch.tensor(r["labels"], dtype=torch.long)]
             det_s = [torch.tensor(r["scores"], dtype=torch.float32)]
@@ -155,13 +222,32 @@ def predict_example(args):
                 d = calculate_mAP(det_b, det_l, det_s, gt_b, gt_l, dif, min_overlap=iou, return_detail=True)
                 metrics[str(iou)][subj] = {k: float(d[k]) for k in ("mAP", "precision", "recall", "f1_score")}
         for iou, m in metrics.items():
-            with open(pjoin(args.output_dir, f"aa_metrics_per_subject_(min_IoU={iou}).json"), "w") as f:
+            with open(pjoin(output_dir, f"aa_metrics_per_subject_(min_IoU={iou}).json"), "w") as f:
                 json.dump(m, f, indent=4)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
     return metrics
+
+
+def overlay_volume(rec, boxes, labels, scores, target, min_score, on_device=False):
+    """The "preds"-style instance volume of one subject (``utils.draw_boxes``), int16 on the host.  ``target`` None: in
+    the image's own frame (the example module; what the reference's NIfTI holds).  Otherwise the boxes are fractions of
+    the fitted ``target`` volume of a clinical case and the volume is drawn in the case's own frame at ``full_shape``:
+    on the host by ``fit_to_case_frame`` + ``draw_boxes``, or with ``on_device`` by msl_boxes_to_case + msl_draw_boxes on
+    the detections where ``predict_batches`` left them, behind the pass on its stream, and read back once."""
+    from .utils import draw_boxes, draw_boxes_device
+    if target is None:
+        return draw_boxes(boxes.cpu(), labels.cpu(), scores.cpu(), rec["shape"], "preds", min_score)[0]
+    if not on_device:
+        from .datasets import fit_to_case_frame
+        case = fit_to_case_frame(boxes.cpu().numpy(), target, rec["crop_shape"], rec["crop_origin"], rec["full_shape"])
+        return draw_boxes(case, labels.cpu(), scores.cpu(), rec["full_shape"], "preds", min_score)[0]
+    from .devicedata import boxes_to_case_device
+    case = boxes_to_case_device(boxes, target, rec["crop_shape"], rec["crop_origin"], rec["full_shape"])
+    inst, _ = draw_boxes_device(case, labels, scores, rec["full_shape"], "preds", min_score, classes=False)
+    return inst[0].cpu().numpy()
 
 
 def collate(samples):

@@ -421,3 +421,85 @@ def evaluate_detections(det_boxes, det_labels, det_scores, true_boxes, true_labe
             status = np.where(claim[t] < 0, 2, np.where(claim[t] < K, 1, 0))
             res[(ious[t], scs[c])] = _detail_dict(summary[t, c], sorted_scores, tp[t], fp, vol, status)
     return res
+
+
+# ---- box overlays (utils.py:516-617, predict.py:186-220) ----------------------------------------------------------------
+DRAW_STYLES = {"edges": 0, "preds": 1}  # msl_draw_boxes's style argument
+
+
+def draw_boxes(boxes, labels, scores, shape, style, min_score=0.):
+    """The box-overlay volumes of the reference on the host -> ``(instances, classes)``, two int16 arrays of ``shape``.
+
+    ``style="edges"`` restates ``make_segmentation_from_bboxes`` (utils.py:559-598) for one image: label 0 is skipped
+    (``scores`` and ``min_score`` are not looked at), the voxel box is the fp32 product ``clip(box, 0, 1) * shape``
+    truncated to int with ``max = min(max, n - 1)``, and six half-open faces are assigned.  ``style="preds"`` restates
+    ``save_predictions_example`` (predict.py:186-220): ``score < min_score`` (compared as ``save_predictions`` compares, in
+    f64) and label 0 are skipped, ``max = min(max + 1, n - 1)``, and the six faces, three edge lines and the far corner are
+    assigned.  Boxes are applied in ascending j and a later box overwrites an earlier one: a drawn voxel of ``instances``
+    holds j + 1 of the last box whose assignments cover it, where j counts every detection, skipped ones included, and
+    ``classes`` holds that box's label.  The reference has the class plane for "edges" only; for "preds" it is this
+    project's extension.  An assignment on an index the reference would raise IndexError for (a min coordinate >= 1 gives
+    index n) writes nothing.  ``msl_draw_boxes`` (csrc/overlay.hip) computes the same volumes on the device, bit for bit."""
+    if style not in DRAW_STYLES:
+        raise ValueError(f"style must be one of {sorted(DRAW_STYLES)}, got {style!r}")
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"shape must be three positive sizes, got {shape}")
+    boxes = np.asarray(torch.as_tensor(boxes).cpu() if torch.is_tensor(boxes) else boxes, dtype=np.float32).reshape(-1, 6)
+    labels = np.asarray(torch.as_tensor(labels).cpu() if torch.is_tensor(labels) else labels).reshape(-1)
+    preds = style == "preds"
+    if preds:
+        scores = np.asarray(torch.as_tensor(scores).cpu() if torch.is_tensor(scores) else scores, dtype=np.float32).reshape(-1)
+    if boxes.shape[0] > 32766:
+        raise ValueError("draw_boxes: more than 32766 boxes do not fit the int16 ids")
+    shape2 = np.asarray(shape * 2, dtype=np.float32)
+    planes = np.zeros((2,) + shape, dtype=np.int16)
+    for j in range(boxes.shape[0]):
+        label = int(labels[j])
+        if label == 0 or (preds and float(scores[j]) < min_score):
+            continue
+        vox = (np.clip(boxes[j], np.float32(0), np.float32(1)) * shape2).astype(int).tolist()
+        x0, y0, z0 = vox[:3]
+        x1, y1, z1 = (min(v + preds, n - 1) for v, n in zip(vox[3:], shape))
+        value = np.array([j + 1, label], dtype=np.int16)[:, None, None]
+        # (a fixed index equal to n - only a min can be - is out of range in the reference; nothing is written there)
+        if x0 < shape[0]:
+            planes[:, x0, y0:y1, z0:z1] = value
+        planes[:, x1, y0:y1, z0:z1] = value
+        if y0 < shape[1]:
+            planes[:, x0:x1, y0, z0:z1] = value
+        planes[:, x0:x1, y1, z0:z1] = value
+        if z0 < shape[2]:
+            planes[:, x0:x1, y0:y1, z0] = value
+        planes[:, x0:x1, y0:y1, z1] = value
+        if preds:
+            planes[:, x0:x1, y1, z1] = value[:, :, 0]
+            planes[:, x1, y0:y1, z1] = value[:, :, 0]
+            planes[:, x1, y1, z0:z1] = value[:, :, 0]
+            planes[:, x1, y1, z1] = value[:, 0, 0]
+    return planes[0], planes[1]
+
+
+def draw_boxes_device(boxes, labels, scores, shape, style, min_score=0., classes=True, out=None):
+    """``draw_boxes`` for N images on the HIP device (msl_draw_boxes, one launch per image on the current stream, no
+    synchronisation): ``boxes`` / ``labels`` / ``scores`` are lists of N device tensors (or one tensor for N = 1) ->
+    ``(instances, classes)``, int16 (N,) + shape on the device; ``classes`` is None when not asked for.  ``out``: a pair
+    of buffers to write into (every voxel is written: they need no clearing)."""
+    if torch.is_tensor(boxes):
+        boxes, labels, scores = [boxes], [labels], [scores]
+    if style not in DRAW_STYLES:
+        raise ValueError(f"style must be one of {sorted(DRAW_STYLES)}, got {style!r}")
+    N, shape = len(boxes), tuple(int(n) for n in shape)
+    dev = boxes[0].device
+    b = torch.cat([_gpu(x, "draw_boxes_device").reshape(-1, 6) for x in boxes])
+    l = torch.cat([x.reshape(-1).to(device=dev, dtype=torch.int64) for x in labels])
+    s = torch.cat([_gpu(x, "draw_boxes_device").reshape(-1) for x in scores])
+    off = np.concatenate([[0], np.cumsum([x.reshape(-1, 6).shape[0] for x in boxes])]).astype(np.int32)
+    if out is None:
+        inst = torch.empty((N,) + shape, dtype=torch.int16, device=dev)
+        cls = torch.empty((N,) + shape, dtype=torch.int16, device=dev) if classes else None
+    else:
+        inst, cls = out
+    _lib.call("msl_draw_boxes", ptr(b), ptr(l), ptr(s), off.ctypes.data, N, *shape, DRAW_STYLES[style], float(min_score),
+              ptr(inst), ptr(cls) if cls is not None else None, _stream())
+    return inst, cls

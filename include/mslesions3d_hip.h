@@ -494,6 +494,19 @@ int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long
                        int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
                        void* stream);
 
+/* ---- native grid -> LPI at 1 mm (csrc/datapipe.hip, devicedata.LesionCache / LesionPredictFeed)
+ * msl_regrid: datasets.regrid of one case, bit for bit.  src_img (C,n0,n1,n2) f32 with 1 <= C <= 4, src_seg (n0,n1,n2)
+ * i16 -> dst_img (C,m0,m1,m2) f32, dst_seg (m0,m1,m2) i16.  plan (HOST, 12 doubles, read during the call): ax[3],
+ * rev[3], step[3], start[3] of datasets.regrid_plan.  The reoriented volume has source axis ax[k] as its axis k,
+ * reversed where rev[k] = 1; output voxel o samples it at c_k = step_k * o_k + start_k (one rounded f64 multiply, one
+ * rounded add, no contraction) as scipy.ndimage.affine_transform(mode="nearest") does: order 1 for every image plane,
+ * order 0 for the mask.  Either the image pair or the mask pair may be null.  Every output voxel is written exactly once:
+ * no memset, no atomics.  -1 (nothing launched, nothing written): plan null, both pairs null or a pair half null, ax not
+ * a permutation of 0..2, rev not 0 / 1, a size < 1, C outside 1..4, a step not finite or <= 0, a start not finite.
+ * -2: m2 > 65535 * 1024. */
+int msl_regrid(const float* src_img, const short* src_seg, int C, int n0, int n1, int n2, const double* plan, int m0,
+               int m1, int m2, float* dst_img, short* dst_seg, void* stream);
+
 /* ---- prediction overlays (csrc/overlay.hip, devicedata.LesionPredictFeed, predict.py -si 1) ----
  * Packed detections of N images: boxes (K,6) f32 corner boxes, labels (K) i64, scores (K) f32 on the device; offsets
  * (HOST, N + 1 ints, read during the call): image n owns rows offsets[n] .. offsets[n+1].  Both launch on `stream` and

@@ -14,6 +14,8 @@
 //               minimum linear index = the component's first voxel in C raster order = scipy's numbering), per-tile
 //               root counts, one scan into (image, class, tile) order, root ranks, integer min / max extents by
 //               atomics, then one workgroup drops flat components and writes the packed targets of msl_multibox_match.
+//   regrid    : a native case onto the LPI 1 mm grid (signed axis permutation + per-axis step), bit-identical to
+//               datasets.regrid; at the end of this file
 // Launch boundaries on one stream are the only hand-offs between workgroups, except the union-find links, which are
 // read with agent-scope atomic loads and written with atomicMin (the result does not depend on the order).
 #include "common.hpp"
@@ -1365,6 +1367,221 @@ int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long
     case 2: launch_fit_mc<2>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
     case 3: launch_fit_mc<3>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
     default: launch_fit_mc<4>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
+  }
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+}  // extern "C"
+
+// ---- native grid -> LPI at 1 mm: signed axis permutation + per-axis resample of one case -------------------------------
+// Host mirror: datasets.regrid (np.transpose / np.flip, then scipy.ndimage.affine_transform with a diagonal matrix and
+// mode "nearest": order 1 for the image planes, order 0 for the mask).  Output voxel o reads the reoriented volume at
+// c_k = step_k * o_k + start_k, which is affine_kernel's coordinate row for a diagonal matrix (its off-diagonal terms
+// add +0.0), then map_tap at boundary 1 (rg_axis below), the weights w0 = 1 - (c - floor c), w1 = 1 - w0 and the eight
+// corners in affine_kernel's order, each ((v * w_0) * w_1) * w_2.
+//
+// The map is separable, so the per-axis entries (two source indices after the boundary map and the reversal, the order-0
+// index, the f64 weight of the lower tap) are not per-voxel work: a workgroup builds the entries of its (up to RG_TW)
+// output columns once, into LDS, and then walks output rows, one wave per row; the wave computes the two entries of
+// the row's axes 0 and 1 once per row.  A lane owns four consecutive output voxels (one 16-byte image store per plane,
+// one 8-byte mask store) and loops the C channels inside, so the indices, the weights and the mask tap are formed once
+// per voxel.  FAST: the reoriented last axis is the source's last axis (flips and spacing only), so the taps of a lane
+// group lie in the four contiguous source rows (2 x 2 taps of axes 0 and 1) and the column index is the element offset.
+namespace {
+
+constexpr int RG_TW = 1024;                   // output columns per workgroup (20 KiB of LDS)
+constexpr int RG_WAVES = DP_THREADS / 64;     // output rows in flight per workgroup
+constexpr int RG_VEC = 4;                     // output voxels per lane and pass
+
+struct RgPlan {  // the reoriented volume, axis k: length, reversal, source stride (elements); the sampling step / start
+  int len[3], rev[3];
+  long long stride[3];
+  double step[3], start[3];
+};
+
+// entry of output index o on one axis: source indices of the taps floor(c), floor(c) + 1 and floor(c + 0.5), weight of
+// the first.  scipy's "nearest" as scipy 1.15 computes it: the taps are clamped into the axis, but the weights come from
+// the coordinate as it is, so past either end both taps are the end voxel with weights (1 - x, x), not (1, 0).  (That
+// differs from map_boundary's clamp of the coordinate in the last f64 bit of a sum, which decides an f32 tie wherever
+// coordinates are half-integers, as under a step of 0.5 or 2.5.)
+__device__ __forceinline__ void rg_axis(int o, double step, double start, int len, int rev, int& ia, int& ib, int& in,
+                                        double& w0) {
+  double c = 0.0;
+  c = c + (double)o * step;
+  c = c + start;
+  const double fl = floor(c);
+  const double x = c - fl;
+  w0 = 1.0 - x;
+  // floor(c) and floor(c + 0.5) clamped to [-1, len] as doubles first: the casts are defined for every finite c
+  const double hi = (double)len;
+  const long long st = (long long)(fl < -1.0 ? -1.0 : (fl > hi ? hi : fl));
+  const double fn = floor(c + 0.5);
+  ia = map_tap(st, len, 1);
+  ib = map_tap(st + 1, len, 1);
+  in = map_tap((long long)(fn < -1.0 ? -1.0 : (fn > hi ? hi : fn)), len, 1);
+  if (rev) {
+    ia = len - 1 - ia;
+    ib = len - 1 - ib;
+    in = len - 1 - in;
+  }
+}
+
+template <int C, bool FAST, bool VEC>
+__global__ __launch_bounds__(DP_THREADS) void regrid_kernel(const float* __restrict__ src_img,
+                                                            const short* __restrict__ src_seg, long long SV, RgPlan p,
+                                                            int m0, int m1, int m2, float* __restrict__ dst_img,
+                                                            short* __restrict__ dst_seg) {
+  __shared__ int t_ia[RG_TW], t_ib[RG_TW], t_in[RG_TW];
+  __shared__ double t_w[RG_TW];
+  const int x_base = blockIdx.y * RG_TW;
+  const int x_cnt = (m2 - x_base) < RG_TW ? (m2 - x_base) : RG_TW;
+  for (int i = threadIdx.x; i < x_cnt; i += DP_THREADS) {
+    int ia, ib, in;
+    double w;
+    rg_axis(x_base + i, p.step[2], p.start[2], p.len[2], p.rev[2], ia, ib, in, w);
+    t_ia[i] = ia;
+    t_ib[i] = ib;
+    t_in[i] = in;
+    t_w[i] = w;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long rows = (long long)m0 * m1;
+  const long long MV = rows * m2;
+  const long long st2 = FAST ? 1LL : p.stride[2];
+  for (long long r = (long long)blockIdx.x * RG_WAVES + wave; r < rows; r += (long long)gridDim.x * RG_WAVES) {
+    const int o0 = (int)(r / m1), o1 = (int)(r % m1);
+    int a0, b0, q0, a1, b1, q1;
+    double w[2][2];  // [axis][tap]
+    rg_axis(o0, p.step[0], p.start[0], p.len[0], p.rev[0], a0, b0, q0, w[0][0]);
+    rg_axis(o1, p.step[1], p.start[1], p.len[1], p.rev[1], a1, b1, q1, w[1][0]);
+    w[0][1] = 1.0 - w[0][0];
+    w[1][1] = 1.0 - w[1][0];
+    const long long r0[2] = {a0 * p.stride[0], b0 * p.stride[0]}, r1[2] = {a1 * p.stride[1], b1 * p.stride[1]};
+    const long long rq = q0 * p.stride[0] + q1 * p.stride[1];
+    for (int x = lane * RG_VEC; x < x_cnt; x += 64 * RG_VEC) {
+      const int cnt = VEC ? RG_VEC : ((x_cnt - x) < RG_VEC ? (x_cnt - x) : RG_VEC);
+      float vi[C][RG_VEC];
+      short vs[RG_VEC];
+#pragma unroll
+      for (int j = 0; j < RG_VEC; ++j) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) vi[c][j] = 0.0f;
+        vs[j] = 0;
+        if (j < cnt) {
+          const long long ca = t_ia[x + j] * st2, cb = t_ib[x + j] * st2;
+          const double w2[2] = {t_w[x + j], 1.0 - t_w[x + j]};
+          if (src_img) {
+            double t[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) t[c] = 0.0;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+              for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int d = 0; d < 2; ++d) {
+                  const long long s = r0[a] + r1[b] + (d ? cb : ca);
+#pragma unroll
+                  for (int c = 0; c < C; ++c) {  // per channel the corners in affine_kernel's order
+                    double coeff = (double)src_img[c * SV + s];
+                    coeff = coeff * w[0][a];
+                    coeff = coeff * w[1][b];
+                    coeff = coeff * w2[d];
+                    t[c] = t[c] + coeff;
+                  }
+                }
+#pragma unroll
+            for (int c = 0; c < C; ++c) vi[c][j] = (float)t[c];
+          }
+          if (src_seg) vs[j] = src_seg[rq + t_in[x + j] * st2];
+        }
+      }
+      const long long out = r * m2 + x_base + x;
+      if (VEC) {  // m2 % 4 == 0: every group is whole and 16-byte (image, every plane) / 8-byte (mask) aligned
+        if (dst_img) {
+#pragma unroll
+          for (int c = 0; c < C; ++c)
+            *reinterpret_cast<float4*>(dst_img + c * MV + out) = make_float4(vi[c][0], vi[c][1], vi[c][2], vi[c][3]);
+        }
+        if (dst_seg) {
+          typedef short short4v __attribute__((ext_vector_type(4)));
+          short4v o;
+          o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2]; o[3] = vs[3];
+          *reinterpret_cast<short4v*>(dst_seg + out) = o;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < RG_VEC; ++j) {
+          if (j < cnt) {
+            if (dst_img) {
+#pragma unroll
+              for (int c = 0; c < C; ++c) dst_img[c * MV + out + j] = vi[c][j];
+            }
+            if (dst_seg) dst_seg[out + j] = vs[j];
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int C>
+void launch_regrid(bool fast, bool vec, dim3 grid, hipStream_t st, const float* src_img, const short* src_seg, long long SV,
+                   const RgPlan& p, int m0, int m1, int m2, float* dst_img, short* dst_seg) {
+  if (fast && vec)
+    MSL_LAUNCH(regrid_kernel<C, true, true>, grid, dim3(DP_THREADS), 0, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg);
+  else if (fast)
+    MSL_LAUNCH(regrid_kernel<C, true, false>, grid, dim3(DP_THREADS), 0, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg);
+  else if (vec)
+    MSL_LAUNCH(regrid_kernel<C, false, true>, grid, dim3(DP_THREADS), 0, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg);
+  else
+    MSL_LAUNCH(regrid_kernel<C, false, false>, grid, dim3(DP_THREADS), 0, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msl_regrid(const float* src_img, const short* src_seg, int C, int n0, int n1, int n2, const double* plan, int m0,
+               int m1, int m2, float* dst_img, short* dst_seg, void* stream) {
+  if (!plan || (!src_img && !src_seg) || (src_img == nullptr) != (dst_img == nullptr) ||
+      (src_seg == nullptr) != (dst_seg == nullptr))
+    return MSL_ERR_ARG;
+  if (C < 1 || C > FIT_MAX_CH || n0 < 1 || n1 < 1 || n2 < 1 || m0 < 1 || m1 < 1 || m2 < 1) return MSL_ERR_ARG;
+  const int n[3] = {n0, n1, n2};
+  const long long sstride[3] = {(long long)n1 * n2, (long long)n2, 1LL};
+  RgPlan p;
+  bool seen[3] = {false, false, false};
+  for (int k = 0; k < 3; ++k) {  // the plan is read here, on the host: it need not outlive the call
+    const double a = plan[k], r = plan[3 + k], step = plan[6 + k], start = plan[9 + k];
+    if (!(a == 0.0 || a == 1.0 || a == 2.0) || !(r == 0.0 || r == 1.0)) return MSL_ERR_ARG;
+    if (seen[(int)a]) return MSL_ERR_ARG;
+    seen[(int)a] = true;
+    if (!(step > 0.0) || step - step != 0.0 || start - start != 0.0) return MSL_ERR_ARG;  // x - x != 0: inf or NaN
+    p.len[k] = n[(int)a];
+    p.rev[k] = (int)r;
+    p.stride[k] = sstride[(int)a];
+    p.step[k] = step;
+    p.start[k] = start;
+  }
+  const long long rows = (long long)m0 * m1;
+  const int gy = (m2 + RG_TW - 1) / RG_TW;
+  if (gy > 65535) return MSL_ERR_UNSUPPORTED;
+  long long gx = (rows + RG_WAVES - 1) / RG_WAVES;
+  const long long cap = 2048 / gy > 0 ? 2048 / gy : 1;  // enough workgroups to fill the chip; each amortises its table
+  if (gx > cap) gx = cap;
+  const bool fast = p.stride[2] == 1;
+  const bool vec = m2 % RG_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
+  const dim3 grid((unsigned)gx, (unsigned)gy);
+  const long long SV = (long long)n0 * n1 * n2;
+  hipStream_t st = (hipStream_t)stream;
+  switch (C) {
+    case 1: launch_regrid<1>(fast, vec, grid, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg); break;
+    case 2: launch_regrid<2>(fast, vec, grid, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg); break;
+    case 3: launch_regrid<3>(fast, vec, grid, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg); break;
+    default: launch_regrid<4>(fast, vec, grid, st, src_img, src_seg, SV, p, m0, m1, m2, dst_img, dst_seg); break;
   }
   MSL_LAUNCH_CHECK();
   return MSL_OK;

@@ -9,6 +9,8 @@ batch dict from ``collate_fn`` (``datasets.py:86-94``).  Files are ``.npy`` beca
 the reference; MONAI's exact NormalizeIntensity arithmetic is not pinned (MONAI absent) — population mean/std over
 the non-zero voxels is used.
 """
+import collections
+import itertools
 import os
 from os.path import join as pjoin
 
@@ -237,6 +239,21 @@ def _load(path_noext):
     return np.asarray(nib.load(path_noext + ".nii.gz").dataobj)
 
 
+def _load_affine(path_noext):
+    """The voxel -> world affine of a stored volume (4 x 4 f64, RAS+ mm, the NIfTI convention), or None: the sidecar
+    ``PATH.affine.npy`` of ``PATH.npy``, or ``img.affine`` of ``PATH.nii.gz`` when nibabel is importable.  No sidecar
+    means no affine: the volume is taken as already LPI at 1 mm."""
+    if os.path.exists(path_noext + ".npy"):
+        if not os.path.exists(path_noext + ".affine.npy"):
+            return None
+        affine = np.asarray(np.load(path_noext + ".affine.npy"), dtype=np.float64)
+        if affine.shape != (4, 4):
+            raise ValueError(f"{path_noext}.affine.npy: a 4 x 4 affine expected, got shape {affine.shape}")
+        return affine
+    import nibabel as nib
+    return np.asarray(nib.load(path_noext + ".nii.gz").affine, dtype=np.float64)
+
+
 class ShardSampler(Sampler):
     """Data-parallel shard of one epoch (BASELINE north_star: "data-parallel training shards synthetic volumes across the
     8 GPUs"): every rank draws the SAME permutation of the cases from (seed, epoch), pads it by wrapping around to a
@@ -324,7 +341,7 @@ def collate_fn(batch):
            "subject": [b["subject"] for b in batch], "img_meta_dict": [b["img_meta_dict"] for b in batch],
            "seg_meta_dict": [b["seg_meta_dict"] for b in batch], "img_transforms": [b["img_transforms"] for b in batch],
            "seg_transforms": [b["seg_transforms"] for b in batch]}
-    for key in GEOMETRY_KEYS:  # LesionsDataModule samples carry them; passed through as lists
+    for key in GEOMETRY_KEYS + ("native_shape",):  # LesionsDataModule samples carry them; passed through as lists
         if all(key in b for b in batch):
             out[key] = [b[key] for b in batch]
     return out
@@ -484,6 +501,122 @@ def boxes_from_instances(seg, thresholds, mode="instances"):
     return boxes, labels
 
 
+# ---- native grid -> LPI at 1 mm (reference datasets.py:199-205: orientation(axcodes="LPI"), spacing(pixdim=(1, 1, 1))) --
+# Orientationd / Spacingd are MONAI's (through nibabel's orientation codes); neither library is installed here, so the
+# rule below is this project's own and its parity is NOT pinned.  The map is axis-aligned: a
+# signed axis permutation plus one step per axis; the obliquity of an acquisition is kept, as Spacingd keeps it.
+
+RegridPlan = collections.namedtuple("RegridPlan", "ax rev step start src_shape out_shape out_affine identity")
+
+
+def regrid_plan(affine, shape, pixdim=(1., 1., 1.)):
+    """The axis-aligned map of a native volume of ``shape`` with voxel -> world ``affine`` (4 x 4, RAS+ mm) onto the LPI
+    grid of ``pixdim`` mm, all in f64 -> ``RegridPlan``:
+
+    orientation: R = affine[:3, :3], z_j = |R[:, j]|, cos = R / z.  ``ax`` is the permutation maximising
+    sum_k |cos[k, ax[k]]| (ties: the lexicographically smallest): source axis ax[k] becomes reoriented axis k.
+    ``rev[k] = cos[k, ax[k]] > 0``: LPI axes point along -x, -y, -z of RAS+ world, so a source axis that increases towards
+    R / A / S is reversed.  The reoriented volume has spacing z'_k = z[ax[k]] and shape n'_k = shape[ax[k]].
+
+    spacing: z'_k snaps to p_k = pixdim[k] when |z'_k - p_k| <= 1e-4 p_k.  Output voxel o reads the reoriented volume
+    at ``step * o + start`` with step_k = p_k / z'_k and start_k = 0 (the centres of voxel 0 coincide), and
+    ``out_shape[k] = max(1, round((n'_k - 1) z'_k / p_k + 1))``.
+
+    ``identity``: ax == (0, 1, 2), nothing reversed, every step exactly 1.  ``out_affine``: columns
+    +-R[:, ax[k]] / z[ax[k]] * p_k (minus where reversed); the translation is the world position of the source voxel
+    that becomes output voxel 0.  A singular R, a zero or non-finite z -> ValueError."""
+    affine = np.asarray(affine, dtype=np.float64)
+    shape = tuple(int(n) for n in shape)
+    p = np.asarray(pixdim, dtype=np.float64)
+    if affine.shape != (4, 4) or len(shape) != 3 or min(shape) < 1 or p.shape != (3,):
+        raise ValueError(f"regrid_plan: a 4 x 4 affine, three positive sizes and three spacings expected, got "
+                         f"{affine.shape}, {shape}, {p.shape}")
+    if not (np.isfinite(p).all() and (p > 0).all()):
+        raise ValueError(f"regrid_plan: pixdim must be positive and finite, got {pixdim}")
+    R = affine[:3, :3]
+    if not np.isfinite(affine).all():
+        raise ValueError("regrid_plan: the affine holds a non-finite value")
+    z = np.sqrt((R * R).sum(0))
+    if not (np.isfinite(z).all() and (z > 0).all()) or np.linalg.matrix_rank(R) < 3:
+        raise ValueError(f"regrid_plan: the affine's 3 x 3 part is singular (column norms {z.tolist()})")
+    cos = R / z
+    best, ax = -1.0, None
+    for perm in itertools.permutations(range(3)):  # lexicographic order; a strict > keeps the first of equals
+        score = sum(abs(cos[k, perm[k]]) for k in range(3))
+        if score > best:
+            best, ax = score, perm
+    rev = tuple(bool(cos[k, ax[k]] > 0) for k in range(3))
+    zr = np.array([z[ax[k]] for k in range(3)])
+    nr = np.array([shape[ax[k]] for k in range(3)], dtype=np.int64)
+    zr = np.where(np.abs(zr - p) <= 1e-4 * p, p, zr)
+    step = p / zr
+    start = np.zeros(3, dtype=np.float64)
+    out_shape = tuple(max(1, int(np.round((nr[k] - 1) * zr[k] / p[k] + 1.0))) for k in range(3))
+    out_affine = np.eye(4, dtype=np.float64)
+    first = np.zeros(3, dtype=np.float64)  # the source voxel that becomes output voxel 0
+    for k in range(3):
+        out_affine[:3, k] = (-1.0 if rev[k] else 1.0) * R[:, ax[k]] / z[ax[k]] * p[k]
+        first[ax[k]] = shape[ax[k]] - 1 if rev[k] else 0
+    out_affine[:3, 3] = R @ first + affine[:3, 3]
+    identity = ax == (0, 1, 2) and not any(rev) and bool((step == 1.0).all())
+    return RegridPlan(ax, rev, tuple(float(v) for v in step), tuple(float(v) for v in start), shape, out_shape,
+                      out_affine, identity)
+
+
+def reorient(vol, plan):
+    """The trailing three axes of ``vol`` in the plan's reoriented order: np.transpose, then np.flip (a view)."""
+    lead = vol.ndim - 3
+    vol = np.transpose(vol, tuple(range(lead)) + tuple(lead + a for a in plan.ax))
+    flip = tuple(lead + k for k in range(3) if plan.rev[k])
+    return np.flip(vol, flip) if flip else vol
+
+
+def regrid(img, seg, plan):
+    """Image (D, H, W) or (C, D, H, W) and mask (D, H, W) of a native case on the plan's grid (either may be None).  An
+    identity plan returns the inputs untouched.  Otherwise: ``reorient``, then per channel and for the mask
+    ``scipy.ndimage.affine_transform(a.astype(float32), diag(step), offset=start, output_shape=out_shape, order=1
+    (image) / 0 (mask), mode="nearest")``, cast back to the input's dtype as ``_aug_affine`` does.  ``msl_regrid``
+    (csrc/datapipe.hip) computes the same arrays on the device, bit for bit."""
+    if plan.identity:
+        return img, seg
+    from scipy.ndimage import affine_transform
+    mat, off = np.diag(np.asarray(plan.step, dtype=np.float64)), np.asarray(plan.start, dtype=np.float64)
+
+    def one(a, order):
+        return affine_transform(np.ascontiguousarray(a).astype(np.float32), mat, offset=off, output_shape=plan.out_shape,
+                                order=order, mode="nearest").astype(a.dtype)
+
+    if img is not None:
+        img = np.asarray(img)
+        if img.shape[-3:] != tuple(plan.src_shape) or img.ndim not in (3, 4):
+            raise ValueError(f"regrid: image of shape {img.shape} on a plan for {plan.src_shape}")
+        r = reorient(img, plan)
+        img = one(r, 1) if img.ndim == 3 else np.stack([one(ch, 1) for ch in r])
+    if seg is not None:
+        seg = np.asarray(seg)
+        if seg.shape != tuple(plan.src_shape):
+            raise ValueError(f"regrid: mask of shape {seg.shape} on a plan for {plan.src_shape}")
+        seg = one(reorient(seg, plan), 0)
+    return img, seg
+
+
+def regrid_to_native(boxes, plan):
+    """Corner boxes, fractional in the plan's regridded frame -> the same boxes, fractional in the native frame, computed
+    in f64 and returned as (K, 6) f32.  Per regridded axis k a coordinate c is voxel r = step_k * (c * out_shape_k) of
+    the reoriented volume, which is v = r, or v = (n'_k - 1) - r where the axis is reversed (min and max then swap), of
+    source axis ax[k]; v / n'_k is the native fraction.  Nothing is clamped."""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 6)
+    out = np.empty_like(b)
+    for k in range(3):
+        a, n = plan.ax[k], float(plan.src_shape[plan.ax[k]])
+        lo = plan.step[k] * (b[:, k] * plan.out_shape[k])
+        hi = plan.step[k] * (b[:, 3 + k] * plan.out_shape[k])
+        if plan.rev[k]:
+            lo, hi = (n - 1.0) - hi, (n - 1.0) - lo
+        out[:, a], out[:, 3 + a] = lo / n, hi / n
+    return out.astype(np.float32)
+
+
 def normalize_nonzero(img):
     """NormalizeIntensity(nonzero=True) as ``_Cases`` applies it: population mean / std over the non-zero voxels of the
     whole array (``_LesionCases`` calls it once per channel)."""
@@ -495,8 +628,15 @@ def normalize_nonzero(img):
     return img
 
 
+def _same_affine(affine, other, case, name):
+    """Image(s) and mask of one case share one affine (or none of them has one): ValueError otherwise."""
+    if (affine is None) != (other is None) or (affine is not None and not np.allclose(affine, other, rtol=0.0, atol=1e-4)):
+        raise ValueError(f"case {case}: image {name} and the mask carry different affines")
+
+
 class _LesionCases(Dataset):
-    """The per-sample pipeline of LesionsDataModule (datasets.py:199-236): load -> crop_foreground(margin 5) ->
+    """The per-sample pipeline of LesionsDataModule (datasets.py:199-236): load -> orientation("LPI") + spacing(1 mm)
+    for a case that carries an affine (``regrid_plan`` / ``regrid``) -> crop_foreground(margin 5) ->
     NormalizeIntensity(nonzero) -> training augmentations at the cropped shape -> resize_with_pad_or_crop(replicate) ->
     boxes ('instances' / 'binary' mode).  With C = len(input_images) > 1 the image is channel-first throughout: the crop
     box is the union of the channels' foregrounds, every channel is normalised over its own non-zero voxels, and one set
@@ -510,6 +650,7 @@ class _LesionCases(Dataset):
             if (t if isinstance(t, str) else t[0]) not in AUGMENTATIONS:
                 raise ValueError(f"unknown transform {t!r}")
         self.seed, self.epoch = seed, 0
+        self._plans = {}  # position -> the RegridPlan of the case's last load (None: no affine); native_plan
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -520,23 +661,45 @@ class _LesionCases(Dataset):
     def __len__(self):
         return len(self.subjects)
 
-    def load(self, i):
-        """-> (image f32, mask) of case i as stored: (D, H, W) each; with C > 1 sequences the image is (C, D, H, W),
-        stacked in ``input_images`` order."""
+    def load_native(self, i):
+        """-> (image f32, mask, affine or None) of case i as stored, on its native grid: (D, H, W) each; with C > 1
+        sequences the image is (C, D, H, W), stacked in ``input_images`` order.  The affine is the one the image(s) and
+        the mask share (np.allclose at atol 1e-4, else ValueError); None when no file of the case carries one."""
         m = self.module
         c, s = self.subjects[i]
         seg = np.asarray(_load(m._get_sequence(c, s, m.segmentation)))
+        affine = _load_affine(m._get_sequence(c, s, m.segmentation))
         imgs = []
         for name in m.input_images:
             img = _load(m._get_sequence(c, s, name)).astype(np.float32)
             if img.ndim != 3 or seg.shape != img.shape:
                 raise ValueError(f"case {(c, s)}: image {name} {img.shape} and mask {seg.shape} must be one 3-D shape")
+            _same_affine(affine, _load_affine(m._get_sequence(c, s, name)), (c, s), name)
             imgs.append(img)
-        return (imgs[0] if len(imgs) == 1 else np.stack(imgs)), seg
+        return (imgs[0] if len(imgs) == 1 else np.stack(imgs)), seg, affine
+
+    def native_plan(self, i):
+        """The ``RegridPlan`` case i was put on the LPI 1 mm grid with, or None for a case without an affine: the one its
+        last load made (``__getitem__`` and ``load`` leave it behind); a case not loaded yet in this process is loaded."""
+        if i not in self._plans:
+            self.load_regridded(i)
+        return self._plans[i]
+
+    def load_regridded(self, i):
+        """-> (image, mask, plan or None): ``load_native`` put on the LPI 1 mm grid by the host ``regrid``; a case without
+        an affine is returned as stored."""
+        img, seg, affine = self.load_native(i)
+        plan = self._plans[i] = None if affine is None else regrid_plan(affine, seg.shape)
+        return (img, seg, None) if plan is None else regrid(img, seg, plan) + (plan,)
+
+    def load(self, i):
+        """-> (image f32, mask) of case i on the LPI 1 mm grid (``load_regridded``); as stored for a case without an
+        affine."""
+        return self.load_regridded(i)[:2]
 
     def __getitem__(self, i):
         m = self.module
-        img, seg = self.load(i)
+        img, seg, plan = self.load_regridded(i)
         full_shape = tuple(int(v) for v in seg.shape)
         lo, hi = foreground_box(img, m.margin)
         sl = tuple(slice(a, b) for a, b in zip(lo, hi))  # crop_foreground
@@ -554,11 +717,15 @@ class _LesionCases(Dataset):
         img = np.ascontiguousarray(resize_with_pad_or_crop(img, m.spatial_size))
         seg = resize_with_pad_or_crop(seg, m.spatial_size)
         boxes, labels = boxes_from_instances(seg, m.thresholds, m.segmentation_mode)
-        return {"img": torch.from_numpy(img), "boxes": boxes, "labels": labels, "seg": [boxes, labels],
-                "subject": self.subjects[i], "img_meta_dict": {"affine": np.eye(4)}, "seg_meta_dict": {},
-                "img_transforms": [], "seg_transforms": [],
-                # the geometry fit_to_case_frame needs: the crop's lo and shape, the case's shape
-                "crop_origin": lo, "crop_shape": crop_shape, "full_shape": full_shape}
+        out = {"img": torch.from_numpy(img), "boxes": boxes, "labels": labels, "seg": [boxes, labels],
+               "subject": self.subjects[i], "img_meta_dict": {"affine": np.eye(4)}, "seg_meta_dict": {},
+               "img_transforms": [], "seg_transforms": [],
+               # the geometry fit_to_case_frame needs: the crop's lo and shape, the case's shape
+               "crop_origin": lo, "crop_shape": crop_shape, "full_shape": full_shape}
+        if plan is not None:  # a case with an affine: full_shape is the regridded shape, the stored one rides along
+            out["img_meta_dict"] = {"affine": plan.out_affine}
+            out["native_shape"] = tuple(plan.src_shape)
+        return out
 
 
 class LesionsDataModule(ExampleDataset):
@@ -579,8 +746,12 @@ class LesionsDataModule(ExampleDataset):
     two MR contrasts pooled describe neither.  At C = 1 both rules are the reference's.  With C > 1 every name must be an
     MR sequence ``_get_sequence`` knows (anything else would be looked up among the lesion masks): NotImplementedError.
 
-    Left out: ``fold`` (the reference indexes a list with an index array there and cannot run) and ``orientation`` /
-    ``spacing``, which need NIfTI affines: the volumes must already be LPI at 1 mm.  Not in the reference:
+    ``orientation`` / ``spacing``: a stored volume ``PATH.npy`` may have a sidecar ``PATH.affine.npy`` (4 x 4 f64, voxel ->
+    world, RAS+ mm; ``img.affine`` for ``.nii.gz``); such a case is reoriented to LPI and resampled to 1 mm by the
+    axis-aligned ``regrid_plan`` / ``regrid`` (bilinear image, nearest mask) in front of the crop, its samples carry the
+    regridded grid's affine and ``native_shape``, and ``full_shape`` is the regridded shape.  A case without an affine is
+    taken as already LPI at 1 mm.  Left out: ``fold`` (the reference indexes a list with an index array there and cannot
+    run) and the rotational resampling of oblique acquisitions (the obliquity is kept).  Not in the reference:
     ``spatial_size`` (its fixed (250, 300, 300)), ``rank`` / ``world_size`` (this process's data-parallel shard)."""
 
     margin = 5  # crop_foreground

@@ -15,7 +15,9 @@ AFFINE_MAX_OPS intensity operations raise NotImplementedError.
 ``LesionCache`` is the counterpart for ``datasets.LesionsDataModule``: cases of unequal shape, cropped to their
 foreground, in one flat arena; shape-changing rot90s allowed; every batch padded / cropped to one fixed size and its
 instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes).  A module with
-C > 1 input sequences is cached channel-planar and goes through msl_foreground_box_mc / msl_augment_fit_mc.
+C > 1 input sequences is cached channel-planar and goes through msl_foreground_box_mc / msl_augment_fit_mc.  A case that
+carries an affine is uploaded on its native grid and put on the LPI 1 mm grid by msl_regrid (``regrid_device``, the
+device form of ``datasets.regrid``, bit for bit) in front of the foreground box.
 """
 from collections import namedtuple
 
@@ -25,13 +27,15 @@ from os.path import join as pjoin
 
 from . import _lib
 from ._lib import ptr
-from .datasets import SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset, draw_augmentations, sample_rng
+from .datasets import (SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset, draw_augmentations, regrid_plan,
+                       sample_rng)
 
 PARAM_STRIDE = 16  # f64 per sample of msl_augment_resample
 AFFINE_STRIDE = 32  # f64 per sample of msl_augment_affine
 AFFINE_MAX_OPS = 4  # intensity operations one msl_augment_affine row carries
 BOUNDARY = {"reflection": 0, "border": 1, "zeros": 2}  # msl_augment_affine's code of a padding_mode
 OP_ADD, OP_MUL = 1, 2
+NEAREST_UNCLAMPED = 3  # affine_numpy only: the boundary rule of msl_regrid (scipy's "nearest", exactly)
 
 # a stage msl_augment_affine runs: dense matrix / offset (f64, as the host computed them) and the boundary code
 AffineStage = namedtuple("AffineStage", "matrix offset boundary")
@@ -188,14 +192,20 @@ def affine_row(source, perm=((0, 1, 2), (0, 0, 0)), stage=None, ops=()):
     return r
 
 
-def affine_numpy(vol, matrix, offset, order, boundary):
+def affine_numpy(vol, matrix, offset, order, boundary, output_shape=None):
     """Host mirror of msl_augment_affine's resample of one (D, H, W) volume, operation by operation in f64 (scipy 1.15's
     NI_GeometricTransform): per axis cc = 0, cc += o[k] * M[h][k] (k = 0, 1, 2), cc += offset[h]; the boundary's
     map_coordinate; order 1: taps floor(cc), floor(cc) + 1 with weights w0 = 1 - (cc - floor(cc)), w1 = 1 - w0, the eight
     corners accumulated axis 0 slowest, each as ((value * w_0) * w_1) * w_2; order 0: tap floor(cc + 0.5).  Boundary 2
-    (constant) writes 0 wherever an axis maps outside [0, len - 1]."""
+    (constant) writes 0 wherever an axis maps outside [0, len - 1].  ``output_shape`` (msl_regrid, ``datasets.regrid``):
+    the output grid where it is not the volume's own.  Boundary ``NEAREST_UNCLAMPED`` (3) is msl_regrid's: "nearest" as
+    scipy 1.15 computes it, the taps clamped into the axis but the weights taken from the coordinate as it is, so past
+    either end both taps are the end voxel with weights (1 - x, x).  Boundary 1 clamps the coordinate itself, which
+    gives (1, 0) there: the same value up to the last f64 bit of the sum, and so another f32 wherever that sum is a tie
+    (half-integer coordinates: a step of 0.5 or 2.5).  msl_augment_affine is boundary 1; DESIGN.md section 4.10."""
     dims = vol.shape
-    o = [x.astype(np.float64) for x in np.meshgrid(*(np.arange(n) for n in dims), indexing="ij")]
+    odims = dims if output_shape is None else tuple(int(n) for n in output_shape)
+    o = [x.astype(np.float64) for x in np.meshgrid(*(np.arange(n) for n in odims), indexing="ij")]
     M, off = np.asarray(matrix, dtype=np.float64), np.asarray(offset, dtype=np.float64)
 
     def reflect(c, n):
@@ -213,15 +223,17 @@ def affine_numpy(vol, matrix, offset, order, boundary):
         m = reflect(i, n) if boundary == 0 else i
         return np.clip(np.where((i >= 0) & (i < n), i, np.trunc(m)), 0, n - 1).astype(np.int64)
 
-    cc, outside = [], np.zeros(dims, dtype=bool)
+    cc, outside = [], np.zeros(odims, dtype=bool)
     for h in range(3):
-        c = np.zeros(dims)
+        c = np.zeros(odims)
         for k in range(3):
             c = c + o[k] * M[h, k]
         c = c + off[h]
         n = dims[h]
         if boundary == 0:
             c = reflect(c, n)
+        elif boundary == NEAREST_UNCLAMPED:
+            pass
         elif boundary == 1:
             c = np.where(c < 0, 0.0, np.where(c > n - 1, float(n - 1), c))
         else:
@@ -237,7 +249,7 @@ def affine_numpy(vol, matrix, offset, order, boundary):
         w0 = 1.0 - (c - fl)
         w.append((w0, 1.0 - w0))
         idx.append((tap(fl, n), tap(fl + 1, n)))
-    t = np.zeros(dims)
+    t = np.zeros(odims)
     for a in range(2):
         for b in range(2):
             for d in range(2):
@@ -513,6 +525,59 @@ def fit_rows(cases, per_sample):
     return rows
 
 
+def plan_row(plan):
+    """The 12 f64 msl_regrid reads on the host: ax[3], rev[3], step[3], start[3] of a ``datasets.RegridPlan``."""
+    return np.ascontiguousarray(np.concatenate([plan.ax, [int(r) for r in plan.rev], plan.step, plan.start]),
+                                dtype=np.float64)
+
+
+def regrid_device(img, seg, plan):
+    """``datasets.regrid`` on the HIP device (msl_regrid, current stream, no synchronisation), bit for bit: ``img`` f32
+    (n0, n1, n2) or (C, n0, n1, n2) and ``seg`` int16 (n0, n1, n2) device tensors on the plan's native grid (either may
+    be None) -> the pair on the plan's output grid.  An identity plan returns the inputs untouched."""
+    if plan.identity:
+        return img, seg
+    ref = img if img is not None else seg
+    if ref is None or not ref.is_cuda:
+        raise _lib.HipKernelError("regrid_device takes tensors on the HIP device (no CPU fallback)")
+    if (img is not None and (img.dtype != torch.float32 or tuple(img.shape[-3:]) != tuple(plan.src_shape)
+                             or img.dim() not in (3, 4))) or \
+            (seg is not None and (seg.dtype != torch.int16 or tuple(seg.shape) != tuple(plan.src_shape))):
+        raise ValueError(f"regrid_device: f32 image / int16 mask of the plan's native shape {plan.src_shape} expected")
+    C = img.shape[0] if img is not None and img.dim() == 4 else 1
+    img = img.contiguous() if img is not None else None
+    seg = seg.contiguous() if seg is not None else None
+    out_shape = tuple(plan.out_shape)
+    di = None if img is None else torch.empty((out_shape if img.dim() == 3 else (C,) + out_shape), dtype=torch.float32,
+                                              device=ref.device)
+    dseg = None if seg is None else torch.empty(out_shape, dtype=torch.int16, device=ref.device)
+    row = plan_row(plan)  # host table, read during the call
+    _lib.call("msl_regrid", ptr(img), ptr(seg), C, *plan.src_shape, row.ctypes.data, *out_shape, ptr(di), ptr(dseg),
+              _stream(ref.device))
+    return di, dseg
+
+
+def _case_on_device(ds, i, dev, who, check_memory=None):
+    """Case i of a ``_LesionCases`` data set on the device, on the LPI 1 mm grid: uploaded as stored and, where it
+    carries an affine with a non-identity plan, regridded there -> (image f32 (n) / (C, n), mask int16 (n), plan or
+    None).  ``check_memory(nbytes, what)`` is asked for the native copy plus the regridded one."""
+    img, seg, affine = ds.load_native(i)
+    seg16 = seg.astype(np.int16)
+    if not np.array_equal(seg16, seg) or (seg16.size and seg16.min() < 0):
+        raise ValueError(f"{who}: mask of case {ds.subjects[i]} is not integer-valued in [0, 32767]")
+    plan = None if affine is None else regrid_plan(affine, seg.shape)
+    per_voxel = 4 * (img.shape[0] if img.ndim == 4 else 1) + 2
+    nbytes = seg.size * per_voxel
+    if plan is not None and not plan.identity:
+        nbytes += int(np.prod(plan.out_shape)) * per_voxel
+    if check_memory is not None:
+        check_memory(nbytes, f"case {ds.subjects[i]} of {img.shape}")
+    vol, mask = torch.from_numpy(img).to(dev), torch.from_numpy(seg16).to(dev)
+    if plan is not None:
+        vol, mask = regrid_device(vol, mask, plan)
+    return vol, mask, plan
+
+
 class LesionCache:
     """The cases of a ``setup()`` ``datasets.LesionsDataModule`` in HBM, cropped to their foreground and normalised: one
     flat arena of f32 images and one of int16 masks with a per-case (offset, shape) table, and the device pipeline that
@@ -520,10 +585,11 @@ class LesionCache:
 
     Same semantics as ``DeviceCache``: ``train_batches(epoch)`` yields the batches of ``dataset.train_dataloader()`` for
     that epoch (same subjects, same draws) in fixed buffers, ``step(trainer, batch)`` trains on one, ``val_batches()``
-    yields ``validation_step`` batches.  At construction every case is uploaded once, boxed by msl_foreground_box (the
-    six ints are the build's only read-back), cropped into the arena and normalised there; the cropped cases are staged
-    in tensors of their own until the arena's size is known.  A pipeline with two affine stages raises
-    NotImplementedError (a resample of a resample of a ragged case would need a ragged intermediate).
+    yields ``validation_step`` batches.  At construction every case is uploaded once (a case with an affine on its
+    native grid, then regridded by msl_regrid: ``plans`` holds its ``RegridPlan``, None otherwise), boxed by
+    msl_foreground_box (the six ints are the build's only read-back), cropped into the arena and normalised there; the
+    cropped cases are staged in tensors of their own until the arena's size is known.  A pipeline with two affine
+    stages raises NotImplementedError (a resample of a resample of a ragged case would need a ragged intermediate).
 
     With C = len(dataset.input_images) > 1 a case is C contiguous f32 planes starting at element C * offset of the image
     arena (the mask arena and the table do not change): boxed as the union of the channels by msl_foreground_box_mc,
@@ -559,25 +625,21 @@ class LesionCache:
         self.val_order = [(te.subjects[i], self.slot[te.subjects[i]]) for i in val_idx]
         dev, stream = self.device, _stream(self.device)
         box = torch.zeros(6, dtype=torch.int32, device=dev)
-        staged, self.shapes, self.origins, self.full_shapes = [], [], [], []
+        staged, self.shapes, self.origins, self.full_shapes, self.plans = [], [], [], [], []
         for ds, i in loaders:
-            img, seg = ds.load(i)
-            seg16 = seg.astype(np.int16)
-            if not np.array_equal(seg16, seg) or (seg16.size and seg16.min() < 0):
-                raise ValueError(f"LesionCache: mask of case {ds.subjects[i]} is not integer-valued in [0, 32767]")
-            self._check_memory(seg.size * (4 * C + 2), f"case {ds.subjects[i]} of {img.shape}")
-            vol = torch.from_numpy(img).to(dev)
+            vol, mask, plan = _case_on_device(ds, i, dev, "LesionCache", self._check_memory)
             if C == 1:
-                _lib.call("msl_foreground_box", ptr(vol), *img.shape, int(dataset.margin), ptr(box), stream)
+                _lib.call("msl_foreground_box", ptr(vol), *vol.shape, int(dataset.margin), ptr(box), stream)
             else:
-                _lib.call("msl_foreground_box_mc", ptr(vol), *img.shape, int(dataset.margin), ptr(box), stream)
+                _lib.call("msl_foreground_box_mc", ptr(vol), *vol.shape, int(dataset.margin), ptr(box), stream)
             b = box.cpu().tolist()  # the one read that sizes the crop
             sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
-            staged.append((vol[(...,) + sl].contiguous(), torch.from_numpy(seg16).to(dev)[sl].contiguous()))
+            staged.append((vol[(...,) + sl].contiguous(), mask[sl].contiguous()))
             self.shapes.append(tuple(b[3 + a] - b[a] for a in range(3)))
             self.origins.append(tuple(b[:3]))  # the crop's lo: datasets.fit_to_case_frame maps boxes back with it
-            self.full_shapes.append(tuple(int(v) for v in seg.shape))
-            del vol
+            self.full_shapes.append(tuple(int(v) for v in mask.shape))  # the regridded shape of a case with an affine
+            self.plans.append(plan)  # datasets.regrid_to_native maps case-frame boxes on to the stored grid with it
+            del vol, mask
         sizes = [int(np.prod(s)) for s in self.shapes]
         self.offsets = [0] + np.cumsum(sizes).tolist()
         self.cache_bytes = self.offsets[-1] * (4 * C + 2)
@@ -697,9 +759,11 @@ def boxes_to_case_device(boxes, target, crop_shape, crop_origin, full_shape):
 
 class LesionPredictFeed:
     """``dataset.predict_dataset`` of a ``setup()`` ``datasets.LesionsDataModule`` as batches of one, prepared on the
-    device case by case: upload, msl_foreground_box[_mc], crop, msl_normalize_nonzero, msl_augment_fit[_mc] with the
-    identity row into a (1, C) + spatial_size batch, msl_instance_boxes on the fitted mask - the kernels ``LesionCache``
-    runs, on one case at a time, so nothing but the case being prepared and the batches handed out is resident.
+    device case by case: upload (a case with an affine on its native grid, then msl_regrid), msl_foreground_box[_mc],
+    crop, msl_normalize_nonzero, msl_augment_fit[_mc] with the identity row into a (1, C) + spatial_size batch,
+    msl_instance_boxes on the fitted mask - the kernels ``LesionCache`` runs, on one case at a time, so nothing but the
+    case being prepared and the batches handed out is resident.  A batch of a case with an affine also carries
+    "native_shape" and "plan" (its ``RegridPlan``), as lists.
 
     ``batches(indices)`` yields ``{"img", "subject", "boxes", "labels", "crop_origin", "crop_shape", "full_shape"}`` (and
     "seg": [boxes, labels]) in the order of ``indices`` (default: every case): "img" a device tensor, valid until the
@@ -736,21 +800,18 @@ class LesionPredictFeed:
     def _start(self, pos, k):
         """Everything of case ``pos`` enqueued; the box read is the one wait."""
         ds, dev, C, stream = self.dataset.predict_dataset, self.device, self.channels, _stream(self.device)
-        img, seg = ds.load(pos)
-        seg16 = seg.astype(np.int16)
-        if not np.array_equal(seg16, seg) or (seg16.size and seg16.min() < 0):
-            raise ValueError(f"LesionPredictFeed: mask of case {ds.subjects[pos]} is not integer-valued in [0, 32767]")
-        vol = torch.from_numpy(img).to(dev)
+        vol, mask, plan = _case_on_device(ds, pos, dev, "LesionPredictFeed")
+        full_shape = tuple(int(v) for v in mask.shape)
         if C == 1:
-            _lib.call("msl_foreground_box", ptr(vol), *img.shape, int(self.dataset.margin), ptr(self._box), stream)
+            _lib.call("msl_foreground_box", ptr(vol), *vol.shape, int(self.dataset.margin), ptr(self._box), stream)
         else:
-            _lib.call("msl_foreground_box_mc", ptr(vol), *img.shape, int(self.dataset.margin), ptr(self._box), stream)
+            _lib.call("msl_foreground_box_mc", ptr(vol), *vol.shape, int(self.dataset.margin), ptr(self._box), stream)
         b = self._box.cpu().tolist()  # the one read that sizes the crop
         sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
         shape = tuple(b[3 + a] - b[a] for a in range(3))
         ci = vol[(...,) + sl].contiguous()
-        cs = torch.from_numpy(seg16).to(dev)[sl].contiguous()
-        del vol
+        cs = mask[sl].contiguous()
+        del vol, mask
         size = int(np.prod(shape))
         slot = self._slots[k % 2]
         if size:
@@ -772,15 +833,18 @@ class LesionPredictFeed:
         # (ci, cs and table are released on return: the caching allocator hands a freed block to this stream's later work
         #  only, which is ordered behind these launches)
         return {"slot": slot, "subject": ds.subjects[pos], "crop_origin": tuple(b[:3]), "crop_shape": shape,
-                "full_shape": tuple(int(v) for v in seg.shape), "done": done}
+                "full_shape": full_shape, "plan": plan, "done": done}
 
     def _finish(self, h):
         slot = h["slot"]
         slot["box"].raise_on_overflow()
         n = int(slot["off"][1])
         boxes, labels = [slot["gb"][:n].clone()], [slot["gl"][:n].clone()]
-        return {"img": slot["img"], "seg": [boxes, labels], "boxes": boxes, "labels": labels, "subject": [h["subject"]],
-                "crop_origin": [h["crop_origin"]], "crop_shape": [h["crop_shape"]], "full_shape": [h["full_shape"]]}
+        out = {"img": slot["img"], "seg": [boxes, labels], "boxes": boxes, "labels": labels, "subject": [h["subject"]],
+               "crop_origin": [h["crop_origin"]], "crop_shape": [h["crop_shape"]], "full_shape": [h["full_shape"]]}
+        if h["plan"] is not None:  # as the host samples of a case with an affine
+            out["native_shape"], out["plan"] = [tuple(h["plan"].src_shape)], [h["plan"]]
+        return out
 
     def batches(self, indices=None):
         pending = None

@@ -6,7 +6,10 @@ With ``-si 1`` the box overlay the reference saves as ``sub-XXXX_preds.nii.gz`` 
 ``sub-XXXX_preds.npy`` (int16; NIfTI is out of scope).  For clinical cases (``-dm lesions``) the overlay
 is drawn in the CASE's own frame, and ``sub-XXXX_preds_case.json`` holds the detections in that frame
 (``datasets.fit_to_case_frame``); ``--cache 1`` prepares the cases on the device (``devicedata.LesionPredictFeed``) and
-maps and draws there too (msl_boxes_to_case, msl_draw_boxes).  DESIGN.md §4.9.
+maps and draws there too (msl_boxes_to_case, msl_draw_boxes).  DESIGN.md §4.9.  A case that carries an affine was put on
+the LPI 1 mm grid first (``datasets.regrid_plan``): its ``_preds_case.json`` gains a ``"native"`` block with the boxes on
+the stored grid (``datasets.regrid_to_native``) and ``-si 1`` also writes ``sub-XXXX_preds_native.npy`` at the stored
+shape.  DESIGN.md §4.10.
 
     python -m mslesions3d_amd.predict -d DATA -dn NAME -m CKPT -o OUT
     python -m mslesions3d_amd.predict -dm lesions -d RAW -m CKPT -o OUT --cache 1 -si 1
@@ -46,7 +49,8 @@ def build_parser():
     p.add_argument('-mn', '--model_name', type=str, default=None, help="sub-directory of the output path (predict.py:241)")
     p.add_argument('-si', '--save_images', type=int, default=0,
                    help="1: write the box overlay of every subject as sub-XXXX_preds.npy (with -dm lesions in the case's own "
-                        "frame, plus sub-XXXX_preds_case.json).  The reference's default is 1; it is 0 here so that no "
+                        "frame, plus sub-XXXX_preds_case.json; for a case with an affine also sub-XXXX_preds_native.npy at "
+                        "the stored shape).  The reference's default is 1; it is 0 here so that no "
                         "existing command starts writing volumes")
     # the reference's (and this parser's) -c is --n_classes, so the device feed has the long spelling only
     p.add_argument('--cache', type=int, default=0,
@@ -79,12 +83,21 @@ def prediction_infos(boxes, labels, scores, min_score, img_shape):
 
 def save_case_predictions(subject, record, target, min_score, output_dir):
     """``sub-XXXX_preds_case.json``: the schema of ``sub-XXXX_preds.json`` with the boxes in the case's own frame -
-    ``fit_to_case_frame`` of the fitted-frame boxes, fractional and as voxels of ``full_shape``."""
-    from .datasets import fit_to_case_frame
+    ``fit_to_case_frame`` of the fitted-frame boxes, fractional and as voxels of ``full_shape``.  For a case that had an
+    affine (``record["plan"]``) the case frame is the regridded one and the file gains
+    ``"native": {"shape": stored shape, "boxes": [box_frac(6) of every kept detection, in key order]}``, the case-frame
+    boxes mapped on to the stored grid by ``regrid_to_native``."""
+    from .datasets import fit_to_case_frame, regrid_to_native
     case = fit_to_case_frame(np.asarray(record["boxes"], np.float32), target, record["crop_shape"], record["crop_origin"],
                              record["full_shape"])
+    infos = prediction_infos(case, record["labels"], record["scores"], min_score, record["full_shape"])
+    plan = record.get("plan")
+    if plan is not None:
+        native = regrid_to_native(case, plan)
+        infos["native"] = {"shape": [int(n) for n in plan.src_shape],
+                           "boxes": [[float(v) for v in native[j - 1]] for j in list(infos)]}
     with open(pjoin(output_dir, f"sub-{subject}_preds_case.json"), "w") as f:
-        json.dump(prediction_infos(case, record["labels"], record["scores"], min_score, record["full_shape"]), f)
+        json.dump(infos, f)
 
 
 def save_predictions(subject, img_shape, boxes, labels, scores, min_score, output_dir):
@@ -199,10 +212,18 @@ def predict_example(args):
                "gt_boxes": batch["boxes"][0].numpy().tolist(), "gt_labels": batch["labels"][0].numpy().tolist()}
         if lesions:
             rec.update({k: tuple(batch[k][0]) for k in ("crop_origin", "crop_shape", "full_shape")})
+            # the plan the case was regridded with: the device feed hands it out, the host data set kept it at the load
+            plan = batch["plan"][0] if "plan" in batch else (None if cache else ds.native_plan(pos))
+            if plan is not None:
+                rec["plan"] = plan
         if save_images:
             np.save(pjoin(output_dir, f"sub-{subj}_preds.npy"),
                     overlay_volume(rec, boxes[0], labels[0], scores[0], tuple(args.spatial_size) if lesions else None,
                                    args.min_score, on_device=cache))
+            if "plan" in rec:
+                np.save(pjoin(output_dir, f"sub-{subj}_preds_native.npy"),
+                        overlay_volume(rec, boxes[0], labels[0], scores[0], tuple(args.spatial_size), args.min_score,
+                                       on_device=cache, native=True))
         records.append((pos, subj, rec))
     merged = gather_detections(records, world, rank)
     metrics = {"0.5": {}, "0.1": {}}
@@ -231,22 +252,30 @@ def predict_example(args):
     return metrics
 
 
-def overlay_volume(rec, boxes, labels, scores, target, min_score, on_device=False):
+def overlay_volume(rec, boxes, labels, scores, target, min_score, on_device=False, native=False):
     """The "preds"-style instance volume of one subject (``utils.draw_boxes``), int16 on the host.  ``target`` None: in
     the image's own frame (the example module; what the reference's NIfTI holds).  Otherwise the boxes are fractions of
     the fitted ``target`` volume of a clinical case and the volume is drawn in the case's own frame at ``full_shape``:
     on the host by ``fit_to_case_frame`` + ``draw_boxes``, or with ``on_device`` by msl_boxes_to_case + msl_draw_boxes on
-    the detections where ``predict_batches`` left them, behind the pass on its stream, and read back once."""
+    the detections where ``predict_batches`` left them, behind the pass on its stream, and read back once.  ``native``
+    (a case that had an affine, ``rec["plan"]``): the case-frame boxes are mapped on to the stored grid by
+    ``regrid_to_native`` (host f64 on both routes) and drawn at the stored shape, by the same two drawing routes."""
     from .utils import draw_boxes, draw_boxes_device
     if target is None:
         return draw_boxes(boxes.cpu(), labels.cpu(), scores.cpu(), rec["shape"], "preds", min_score)[0]
+    shape = tuple(rec["plan"].src_shape) if native else rec["full_shape"]
     if not on_device:
-        from .datasets import fit_to_case_frame
+        from .datasets import fit_to_case_frame, regrid_to_native
         case = fit_to_case_frame(boxes.cpu().numpy(), target, rec["crop_shape"], rec["crop_origin"], rec["full_shape"])
-        return draw_boxes(case, labels.cpu(), scores.cpu(), rec["full_shape"], "preds", min_score)[0]
+        if native:
+            case = regrid_to_native(case, rec["plan"])
+        return draw_boxes(case, labels.cpu(), scores.cpu(), shape, "preds", min_score)[0]
     from .devicedata import boxes_to_case_device
     case = boxes_to_case_device(boxes, target, rec["crop_shape"], rec["crop_origin"], rec["full_shape"])
-    inst, _ = draw_boxes_device(case, labels, scores, rec["full_shape"], "preds", min_score, classes=False)
+    if native:
+        from .datasets import regrid_to_native
+        case = torch.from_numpy(regrid_to_native(case.cpu().numpy(), rec["plan"])).to(case.device)
+    inst, _ = draw_boxes_device(case, labels, scores, shape, "preds", min_score, classes=False)
     return inst[0].cpu().numpy()
 
 

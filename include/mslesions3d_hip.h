@@ -527,6 +527,42 @@ int msl_boxes_to_case(const float* boxes, const int* offsets, const int* geometr
 int msl_draw_boxes(const float* boxes, const long long* labels, const float* scores, const int* offsets, int N, int D,
                    int H, int W, int style, double min_score, short* instances, short* classes, void* stream);
 
+/* ---- multi-view prediction (csrc/views.hip, LSSD3D.predict_views, predict.py --views tiles) ----
+ * A view is a window of T0 x T1 x T2 voxels at origin o of a case, optionally mirrored along some axes.  views (HOST,
+ * V x 6 ints, read during the call): rows o0, o1, o2, f0, f1, f2 (datasets.view_plan).  Both launch on `stream` and do
+ * not synchronise.
+ * msl_view_gather: datasets.gather_views, bit for bit.  src (C,n0,n1,n2) f32, dst (V,C,T0,T1,T2) f32.  Output voxel p of
+ * view v reads src[c][s] with q_k = f_k ? T_k - 1 - p_k : p_k and s_k = clamp(o_k + q_k, 0, n_k - 1).  Every output
+ * voxel is written exactly once: no memset, no atomics.  -1 (nothing launched, nothing written): a null or misaligned
+ * pointer, V < 1, a size < 1, C outside 1..4, a flip flag not 0 / 1.  -2: C * T0 > 65535 or T1 * (T2 / 4 + 2) >= 2^31.
+ * msl_views_merge: utils.merge_views, bit for bit.  boxes (V,top_k,6) f32, scores (V,top_k) f32, labels (V,top_k) i64,
+ * counts (V) i32 on the device: the detections of the V views in msl_detect_objects' output layout (corner boxes as
+ * fractions of the view).  geometry (HOST, 12 ints, read during the call): tile[3], case[3], margin[3], V, top_k,
+ * out_top_k.  All f32 arithmetic is single rounded operations, no contraction.  Map, per axis k: a corner pair (a, b) of a
+ * view with f_k becomes (1 - b, 1 - a); voxel x = a * T_k + o_k; case fraction x / n_k; not clamped.  Candidates: slots
+ * j < counts[v] with label >= 1 and a score that is not NaN whose centre (x_lo + x_hi) * 0.5f passes the ownership test of
+ * their view: on every axis c >= o_k + m_k unless o_k <= 0, and c < o_k + T_k - m_k unless o_k + T_k >= n_k.  Per class,
+ * ascending: rank by descending score, ties by ascending (view, slot); greedy NMS with iou > max_overlap (detect.hip's
+ * iou6) on the case-frame boxes; a suppressed candidate is assigned to the earliest-ranked kept one that overlaps it;
+ * support = distinct views among a kept candidate and its members.  mode 0 "nms": the kept candidate's box and score.
+ * mode 1 "fuse": box = sum(s_i * B_i) / sum(s_i) over the cluster in rank order (f64: one rounded multiply and add per
+ * term, one divide, rounded to f32); score = sum over views, ascending, of the view's best member score (f64) over
+ * max(cover, support), cover = views whose ownership test the kept centre passes, rounded to f32.  Output: every class, by
+ * descending final score, ties by (class, rank of the kept candidate), the first out_top_k: out_boxes (out_top_k,6),
+ * out_scores, out_labels i64, out_support i32, out_count (1), possibly 0; rows past the count are not written.
+ * workspace: msl_views_merge_workspace_bytes(V, top_k) bytes, 16-byte aligned; 0 = beyond capacity (V > 64 or
+ * V * top_k > 8192: 2 x 2 x 2 tiles x 8 flips x top_k 100 = 6400).  -1 (nothing launched): a null pointer, V, top_k or
+ * out_top_k < 1, a size < 1, a margin < 0, a flip flag or mode not 0 / 1, a workspace too small.  -2: beyond capacity. */
+#define MSL_VIEWS_MAX 64
+#define MSL_VIEWS_MAX_DETECTIONS 8192
+int msl_view_gather(const float* src, int C, int n0, int n1, int n2, const int* views, int V, int T0, int T1, int T2,
+                    float* dst, void* stream);
+size_t msl_views_merge_workspace_bytes(int V, int top_k);
+int msl_views_merge(const float* boxes, const float* scores, const long long* labels, const int* counts, const int* views,
+                    const int* geometry, float max_overlap, int mode, void* workspace, size_t workspace_bytes,
+                    float* out_boxes, float* out_scores, long long* out_labels, int* out_support, int* out_count,
+                    void* stream);
+
 /* ---- optimiser + NaN guard : ssd3d.py:704-722, :258-261 ---------------------------------------------------- */
 /* hp (device, 8 floats): step_size(bias), step_size(other), sqrt(bias_correction2), beta1, beta2, eps,
  * weight_decay, gradient scale.  is_bias (n bytes): 1 for elements of '.bias' parameters (2*lr group). */

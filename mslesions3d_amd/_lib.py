@@ -145,6 +145,9 @@ _SIGNATURES = {
     "msl_regrid": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "msl_boxes_to_case": (_I, [_P, _P, _P, _I, _P, _P]),
     "msl_draw_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P]),
+    "msl_view_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "msl_views_merge_workspace_bytes": (_Z, [_I, _I]),
+    "msl_views_merge": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _P, _Z, _P, _P, _P, _P, _P, _P]),
     "msl_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "msl_nan_flag": (_I, [_P, _Z, _P, _I, _P]),
     "msl_nan_flag2": (_I, [_P, _Z, _I, _P, _Z, _I, _P, _P]),

@@ -472,6 +472,78 @@ def fit_to_case_frame(boxes, target, crop_shape, crop_origin, full_shape):
     return (boxes * t2 + add2) / s2
 
 
+# ---- multi-view prediction: tiled and flipped views of one case ------------------------------
+MAX_VIEWS = 64  # msl_views_merge's capacity
+
+
+def view_plan(case_shape, tile, margin=(8, 8, 8), flip_axes=()):
+    """The views prediction shows the network of one case of ``case_shape``: windows of ``tile`` voxels, optionally
+    mirrored -> int32 (V, 6), rows ``o0, o1, o2, f0, f1, f2`` (origin in case voxels, 0 / 1 flip flags).  Per axis with
+    case size n, tile t, margin m: n <= t gives the one origin ``fit_shift(n, t)`` (<= 0: the view pads by edge
+    replication as the fit does); n > t gives K = ceil((n - t) / (t - 2m)) + 1 origins o_i = (i * (n - t)) // (K - 1),
+    the first 0, the last n - t, neighbours overlapping by at least 2m (t <= 2m raises ValueError).  Tiles are the product
+    of the three axes, axis 0 slowest; every tile is followed by its flipped copies, one per subset of ``flip_axes``
+    (subset i holds flip_axes[b] for every set bit b of i, so the unflipped one comes first): tile-major, flip-minor.
+    More than 64 views raise ValueError."""
+    case_shape, tile, margin = (tuple(int(v) for v in x) for x in (case_shape, tile, margin))
+    flip_axes = tuple(int(a) for a in flip_axes)
+    if not (len(case_shape) == len(tile) == len(margin) == 3) or min(case_shape + tile) < 1 or min(margin) < 0:
+        raise ValueError("view_plan: case_shape, tile and margin are three ints each (sizes >= 1, margins >= 0)")
+    if len(set(flip_axes)) != len(flip_axes) or any(a not in (0, 1, 2) for a in flip_axes):
+        raise ValueError(f"view_plan: flip_axes {flip_axes} must be distinct axes out of 0, 1, 2")
+    origins = []
+    for n, t, m in zip(case_shape, tile, margin):
+        if n <= t:
+            origins.append([fit_shift(n, t)])
+            continue
+        if t <= 2 * m:
+            raise ValueError(f"view_plan: a tile of {t} voxels has no core left inside a margin of {m} (--tile_margin)")
+        K = -(-(n - t) // (t - 2 * m)) + 1
+        origins.append([(i * (n - t)) // (K - 1) for i in range(K)])
+    flips = []
+    for sub in range(1 << len(flip_axes)):
+        f = [0, 0, 0]
+        for b, a in enumerate(flip_axes):
+            if (sub >> b) & 1:
+                f[a] = 1
+        flips.append(f)
+    V = len(origins[0]) * len(origins[1]) * len(origins[2]) * len(flips)
+    if V > MAX_VIEWS:
+        raise ValueError(f"view_plan: {V} views of a {case_shape} case exceed the merge capacity of {MAX_VIEWS}: a larger "
+                         "--spatial_size, a smaller --tile_margin or fewer --flip_views axes reduce it")
+    rows = [[a, b, c] + f for a in origins[0] for b in origins[1] for c in origins[2] for f in flips]
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 6)
+
+
+def check_views(views):
+    """(V, 6) int32 view table with 0 / 1 flip flags, V >= 1 (ValueError otherwise)."""
+    views = np.ascontiguousarray(np.asarray(views, dtype=np.int32))
+    if views.ndim != 2 or views.shape[1] != 6 or views.shape[0] < 1 or not np.isin(views[:, 3:], (0, 1)).all():
+        raise ValueError("views: (V, 6) rows o0, o1, o2, f0, f1, f2 with V >= 1 and 0 / 1 flip flags")
+    return views
+
+
+def gather_views(case, views, tile):
+    """The views of a (C, n0, n1, n2) case as one (V, C, T0, T1, T2) float32 batch: output voxel p of view v reads
+    ``case[c][s]`` with q_k = T_k - 1 - p_k where the view is flipped along k (else p_k) and s_k = clamp(o_k + q_k, 0,
+    n_k - 1).  One unflipped view at the ``fit_shift`` origins is ``resize_with_pad_or_crop(case, tile)``.
+    ``msl_view_gather`` (csrc/views.hip) computes the same values on the device, bit for bit."""
+    case = np.asarray(case, dtype=np.float32)
+    views = check_views(views)
+    if case.ndim != 4 or len(tile) != 3:
+        raise ValueError("gather_views: case is (C, n0, n1, n2) and tile three ints")
+    out = np.empty((views.shape[0], case.shape[0]) + tuple(int(t) for t in tile), dtype=np.float32)
+    for v, row in enumerate(views):
+        vol = case
+        for k in range(3):
+            n, t = case.shape[1 + k], int(tile[k])
+            vol = np.take(vol, np.clip(np.arange(t) + int(row[k]), 0, n - 1), axis=1 + k)
+            if row[3 + k]:
+                vol = np.flip(vol, axis=1 + k)
+        out[v] = vol
+    return out
+
+
 def boxes_from_instances(seg, thresholds, mode="instances"):
     """BoundingBoxesGeneratord, 'instances' mode (utils.py:442-443, 472-481, 485-513) on an instance-labelled mask: the
     ids are the sorted unique values with the FIRST one discarded (the background - on a mask without background the
@@ -698,6 +770,17 @@ class _LesionCases(Dataset):
         return self.load_regridded(i)[:2]
 
     def __getitem__(self, i):
+        return self._sample(i, True)
+
+    def case_sample(self, i):
+        """The sample of case i WITHOUT the fit (multi-view prediction): "img" is the normalised
+        foreground crop (C,) + crop_shape, whatever its size, and the ground-truth boxes are taken on the cropped mask, as
+        fractions of crop_shape.  Un-augmented data sets only."""
+        if self.augmentations:
+            raise ValueError("case_sample: the case frame is defined for the un-augmented pipeline")
+        return self._sample(i, False)
+
+    def _sample(self, i, fit):
         m = self.module
         img, seg, plan = self.load_regridded(i)
         full_shape = tuple(int(v) for v in seg.shape)
@@ -714,8 +797,9 @@ class _LesionCases(Dataset):
         for t in self.augmentations:
             name, kw = (t, {}) if isinstance(t, str) else t
             img, seg = AUGMENTATIONS[name](img, seg, rs, **kw)
-        img = np.ascontiguousarray(resize_with_pad_or_crop(img, m.spatial_size))
-        seg = resize_with_pad_or_crop(seg, m.spatial_size)
+        if fit:
+            img, seg = resize_with_pad_or_crop(img, m.spatial_size), resize_with_pad_or_crop(seg, m.spatial_size)
+        img = np.ascontiguousarray(img)
         boxes, labels = boxes_from_instances(seg, m.thresholds, m.segmentation_mode)
         out = {"img": torch.from_numpy(img), "boxes": boxes, "labels": labels, "seg": [boxes, labels],
                "subject": self.subjects[i], "img_meta_dict": {"affine": np.eye(4)}, "seg_meta_dict": {},

@@ -9,10 +9,13 @@ is drawn in the CASE's own frame, and ``sub-XXXX_preds_case.json`` holds the det
 maps and draws there too (msl_boxes_to_case, msl_draw_boxes).  DESIGN.md §4.9.  A case that carries an affine was put on
 the LPI 1 mm grid first (``datasets.regrid_plan``): its ``_preds_case.json`` gains a ``"native"`` block with the boxes on
 the stored grid (``datasets.regrid_to_native``) and ``-si 1`` also writes ``sub-XXXX_preds_native.npy`` at the stored
-shape.  DESIGN.md §4.10.
+shape.  DESIGN.md §4.10.  ``--views tiles`` and / or ``--flip_views AXES`` show the network several views of every case
+(tiles of the input size where the case is larger, mirrored copies) and merge their detections in the case's own frame
+(``LSSD3D.predict_views``; ``sub-XXXX_preds_views.json`` records the views and every detection's support).  DESIGN.md §4.11.
 
     python -m mslesions3d_amd.predict -d DATA -dn NAME -m CKPT -o OUT
     python -m mslesions3d_amd.predict -dm lesions -d RAW -m CKPT -o OUT --cache 1 -si 1
+    python -m mslesions3d_amd.predict -dm lesions -d RAW -m CKPT -o OUT --cache 1 --views tiles --flip_views 2 --merge fuse
 """
 import argparse
 import json
@@ -56,7 +59,85 @@ def build_parser():
     p.add_argument('--cache', type=int, default=0,
                    help="with -dm lesions, 1: prepare every case on the device (devicedata.LesionPredictFeed) and map and "
                         "draw the overlays there; ignored with a warning for the example module")
+    # multi-view prediction (not in the reference).  A flag that is not given leaves NO attribute behind (SUPPRESS), so the
+    # namespace of a command without them is the one every caller of the single-view route has always seen; the route
+    # reads them through view_options(), where the defaults (VIEW_DEFAULTS) live
+    S = argparse.SUPPRESS
+    p.add_argument('--views', choices=["fit", "tiles"], default=S,
+                   help="tiles: a case larger than the input size is covered by overlapping tiles instead of being "
+                        "centre-cropped; their detections are merged in the case's own frame (default: fit)")
+    p.add_argument('--tile_margin', type=int, nargs=3, default=S, metavar=('D', 'H', 'W'),
+                   help="a tile owns the detections centred at least this far inside it; neighbours overlap by twice this "
+                        "(default: 8 8 8)")
+    p.add_argument('--flip_views', type=int, nargs='*', default=S, metavar='AXIS',
+                   help="flip test-time augmentation: every view is also shown mirrored along each subset of these axes "
+                        "(default: none)")
+    p.add_argument('--merge', choices=["nms", "fuse"], default=S,
+                   help="how overlapping detections of several views become one: the best one, or their score-weighted mean "
+                        "(default: nms)")
+    p.add_argument('--view_batch', type=int, default=S, help="views per forward pass of the multi-view route (default: 2)")
     return p
+
+
+VIEW_DEFAULTS = {"views": "fit", "tile_margin": (8, 8, 8), "flip_views": (), "merge": "nms", "view_batch": 2}
+
+
+def view_options(args):
+    """The multi-view flags of a namespace with their defaults filled in -> a namespace of exactly those five."""
+    return argparse.Namespace(**{k: (d if getattr(args, k, None) is None else getattr(args, k))
+                                 for k, d in VIEW_DEFAULTS.items()})
+
+
+def multi_view(args):
+    """--views tiles or a non-empty --flip_views select the multi-view route."""
+    o = view_options(args)
+    return o.views == "tiles" or bool(o.flip_views)
+
+
+def views_of(case_shape, tile, args):
+    """The view table of one case: ``datasets.view_plan`` for --views tiles; for the fitted view, that one window with
+    its mirrored copies."""
+    from .datasets import fit_shift, view_plan
+    args = view_options(args)
+    flips = tuple(args.flip_views)
+    if args.views == "tiles":
+        return view_plan(case_shape, tile, tuple(args.tile_margin), flips)
+    views = view_plan(tile, tile, (0, 0, 0), flips)
+    views[:, :3] = [fit_shift(int(n), int(t)) for n, t in zip(case_shape, tile)]
+    return views
+
+
+def merge_margin(args):
+    """--tile_margin between tiles; the fitted window and its mirrored copies own all of the window."""
+    args = view_options(args)
+    return tuple(args.tile_margin) if args.views == "tiles" else (0, 0, 0)
+
+
+def predict_case_views(model, case, views, args, on_device):
+    """One case through the multi-view route -> (boxes, labels, scores, support) tensors in the case's frame.
+    ``on_device``: ``LSSD3D.predict_views`` (msl_view_gather, msl_views_merge); else their host twins around
+    ``predict_step``: ``gather_views``, the views ``--view_batch`` at a time (the last chunk filled up with the last view,
+    as on the device), ``merge_views``.  Both give the same bits."""
+    margin, args = merge_margin(args), view_options(args)
+    vb = max(1, int(args.view_batch))
+    if on_device:
+        return model.predict_views(case.to(model.device), views, margin, merge=args.merge, view_batch=vb)
+    from .datasets import gather_views
+    from .utils import merge_views
+    tile, V, k = tuple(model.input_size), views.shape[0], int(model.top_k)
+    x = gather_views(case.numpy(), views, tile)
+    x = np.concatenate([x, np.repeat(x[-1:], -V % vb, axis=0)])
+    boxes, scores = np.zeros((V, k, 6), np.float32), np.zeros((V, k), np.float32)
+    labels, counts = np.zeros((V, k), np.int64), np.zeros(V, np.int32)
+    for v0 in range(0, V, vb):
+        b, l, s = model.predict_step({"img": torch.from_numpy(x[v0:v0 + vb])})
+        for i in range(min(vb, V - v0)):
+            n = counts[v0 + i] = b[i].shape[0]
+            boxes[v0 + i, :n], labels[v0 + i, :n], scores[v0 + i, :n] = b[i].cpu().numpy(), l[i].cpu().numpy(), s[i].cpu().numpy()
+    out = merge_views(boxes, scores, labels, counts, views, tile, case.shape[1:], margin, model.max_overlap, args.merge, k)
+    if out[0].shape[0] == 0:  # ssd3d.py:437-440
+        out = (np.asarray([[0, 0, 0, 1, 1, 1]], np.float32), np.zeros(1, np.int64), np.zeros(1, np.float32), np.zeros(1, np.int32))
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in out)
 
 
 def output_dir_of(args):
@@ -168,7 +249,7 @@ def predict_example(args):
         os.makedirs(output_dir, exist_ok=True)
     lesions = getattr(args, "data_module", "example") == "lesions"
     cache = bool(getattr(args, "cache", 0))
-    if cache and not lesions:
+    if cache and not lesions and not multi_view(args):
         warnings.warn("--cache 1 prepares clinical cases on the device (-dm lesions); ignored for the example module")
         cache = False
     if lesions:
@@ -203,7 +284,40 @@ def predict_example(args):
             queued.append((pos, {k: (tuple(v.shape[2:]) if k == "img" else v) for k, v in batch.items() if k != "seg"}))
             yield batch
 
-    for boxes, labels, scores in model.predict_batches(feed(), depth=2):
+    multi = multi_view(args)
+    tile = tuple(model.input_size)
+    if multi and lesions and tuple(args.spatial_size) != tile:
+        raise ValueError(f"--spatial_size {tuple(args.spatial_size)} is the tile of the multi-view route: it must be the "
+                         f"checkpoint's input size {tile}")
+    for pos in (mine if multi else ()):
+        # the case frame: the image itself (example module) or the normalised foreground crop, not fitted (lesions)
+        batch = collate([ds.case_sample(pos) if lesions else ds[pos]])
+        case = batch["img"][0].float()
+        views = views_of(tuple(case.shape[1:]), tile, args)
+        boxes, labels, scores, support = predict_case_views(model, case, views, args, on_device=cache)
+        subj = batch["subject"][0]
+        subj = subj if isinstance(subj, str) else "_".join(subj)
+        rec = {"shape": tuple(case.shape[1:]), "boxes": boxes.cpu().numpy().tolist(), "labels": labels.cpu().numpy().tolist(),
+               "scores": scores.cpu().numpy().tolist(), "gt_boxes": batch["boxes"][0].numpy().tolist(),
+               "gt_labels": batch["labels"][0].numpy().tolist(),
+               "views": {"views": views.tolist(), "tile": list(tile), "margin": list(merge_margin(args)), "merge": view_options(args).merge,
+                         "support": support.cpu().numpy().tolist()}}
+        if lesions:
+            rec.update({k: tuple(batch[k][0]) for k in ("crop_origin", "crop_shape", "full_shape")})
+            plan = ds.native_plan(pos)
+            if plan is not None:
+                rec["plan"] = plan
+        if save_images:  # the case frame IS the crop: fit_to_case_frame with target = crop_shape has d = 0
+            on_dev = boxes.is_cuda
+            np.save(pjoin(output_dir, f"sub-{subj}_preds.npy"),
+                    overlay_volume(rec, boxes, labels, scores, rec["crop_shape"] if lesions else None, args.min_score,
+                                   on_device=on_dev))
+            if "plan" in rec:
+                np.save(pjoin(output_dir, f"sub-{subj}_preds_native.npy"),
+                        overlay_volume(rec, boxes, labels, scores, rec["crop_shape"], args.min_score, on_device=on_dev,
+                                       native=True))
+        records.append((pos, subj, rec))
+    for boxes, labels, scores in model.predict_batches(feed() if not multi else (), depth=2):
         pos, batch = queued.popleft()
         subj = batch["subject"][0]
         subj = subj if isinstance(subj, str) else "_".join(subj)
@@ -232,7 +346,10 @@ def predict_example(args):
             save_predictions(subj, r["shape"], np.asarray(r["boxes"], np.float32), np.asarray(r["labels"]),
                              np.asarray(r["scores"], np.float32), args.min_score, output_dir)
             if save_images and lesions:
-                save_case_predictions(subj, r, tuple(args.spatial_size), args.min_score, output_dir)
+                save_case_predictions(subj, r, r["crop_shape"] if multi else tuple(args.spatial_size), args.min_score, output_dir)
+            if multi:
+                with open(pjoin(output_dir, f"sub-{subj}_preds_views.json"), "w") as f:
+                    json.dump(r["views"], f)
             det_b = [torch.tensor(r["boxes"], dtype=torch.float32).reshape(-1, 6)]
             det_l = [torch.tensor(r["labels"], dtype=torch.long)]
             det_s = [torch.tensor(r["scores"], dtype=torch.float32)]

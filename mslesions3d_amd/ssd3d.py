@@ -578,6 +578,12 @@ class LSSD3D(nn.Module):
     def _predict_enqueue(self, img, slot=0):
         """The device half of ``_predict_replay``: stage the batch, replay (or record) the launch program, enqueue the
         copies that take the detections out -> handle for ``_predict_finish``.  No host synchronisation."""
+        ent = self._predict_launch(img)
+        return self._detect_collect_begin(ent["ws"], img.size(0), nan_flag=ent["plan"].nan_flag, slot=slot)
+
+    def _predict_launch(self, img):
+        """Stage the batch and replay (or record) the launch program of its shape -> the program's entry: the detections
+        are in ``entry["ws"]`` (``msl_detect_objects``' output layout) behind the launches on the current stream."""
         dev = self.device
         x = img  # a host tensor goes straight into the staging buffer below (one host-to-device copy, no device-side second copy)
         self._ensure_device_state(dev)
@@ -612,7 +618,7 @@ class LSSD3D(nn.Module):
                 _lib.replay_native(timed[tags], eng.prof)
             else:
                 _lib.replay_native(ent["compiled"], None)
-        return self._detect_collect_begin(ent["ws"], x.size(0), nan_flag=ent["plan"].nan_flag, slot=slot)
+        return ent
 
     def _predict_finish(self, handle):
         *out, flag = self._detect_collect_end(handle)
@@ -639,6 +645,72 @@ class LSSD3D(nn.Module):
                     yield self._predict_finish(inflight.pop(0))
             while inflight:
                 yield self._predict_finish(inflight.pop(0))
+
+    def predict_views(self, case, views, margin, merge="nms", view_batch=2):
+        """Multi-view prediction of ONE case: ``case`` (C, n0, n1, n2) on the device, ``views``
+        the (V, 6) table of ``datasets.view_plan`` for tiles of ``input_size``.  The views are gathered on the device
+        (msl_view_gather) ``view_batch`` at a time and go through ``predict_step``'s launch program; the last chunk is
+        filled up by repeating the last view, so one program shape is recorded, and the repeats' detections are dropped.
+        The detections stay on the device in the workspace's layout; one msl_views_merge (``utils.merge_views``) behind the
+        chunks, then ONE host synchronisation -> ``(boxes (n, 6), labels (n,), scores (n,), support (n,))`` device
+        tensors in the case's own frame; with nothing detected, the reference's placeholder (box [0, 0, 0, 1, 1, 1], label
+        0, score 0) with support 0."""
+        from .datasets import check_views
+        from .utils import MERGE_MAX_VIEWS, merge_views_device, merge_views_workspace
+        if self.training or not self.use_predict_programs:
+            raise _lib.HipKernelError("predict_views runs the eval-mode launch program (model.eval(), use_predict_programs)")
+        views = check_views(views)
+        V, vb, top_k = views.shape[0], max(1, int(view_batch)), int(self.top_k)
+        dev = self.device
+        if not (torch.is_tensor(case) and case.is_cuda and case.dim() == 4):
+            raise _lib.HipKernelError("predict_views: case is a (C, n0, n1, n2) tensor on the HIP device (no CPU fallback)")
+        if V > MERGE_MAX_VIEWS:
+            raise ValueError(f"predict_views: {V} views exceed the merge capacity of {MERGE_MAX_VIEWS}")
+        case = case.contiguous().float()
+        C, tile = case.size(0), tuple(self.input_size)
+        chunks = (V + vb - 1) // vb
+        table = np.ascontiguousarray(np.concatenate([views, np.repeat(views[-1:], chunks * vb - V, axis=0)]))
+        shape = (vb, C) + tile
+        with torch.no_grad():
+            key = ("views", V, vb, top_k, dev)
+            st = self._det_ws.get(key)
+            if st is None:  # the views' detections side by side, the merge's workspace and outputs, a pinned landing zone
+                f32, i32 = torch.float32, torch.int32
+                st = self._det_ws[key] = dict(
+                    ob=torch.empty((chunks * vb, top_k, 6), dtype=f32, device=dev),
+                    os=torch.empty((chunks * vb, top_k), dtype=f32, device=dev),
+                    ol=torch.empty((chunks * vb, top_k), dtype=torch.int64, device=dev),
+                    oc=torch.empty((chunks, vb + 1), dtype=i32, device=dev),  # per chunk: counts and the pass's NaN flag
+                    ws=merge_views_workspace(V, top_k, dev), tail=torch.empty(chunks + 1, dtype=i32, device=dev),
+                    host=torch.empty(chunks + 1, dtype=i32).pin_memory(), event=torch.cuda.Event())
+            for k in range(chunks):
+                buf = self.predict_input_buffer(shape)
+                x = buf if buf is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+                rows = table[k * vb:(k + 1) * vb]
+                _lib.call("msl_view_gather", ptr(case), C, *case.shape[1:], rows.ctypes.data, vb, *tile, ptr(x), _stream())
+                ent = self._predict_launch(x)
+                w, sl = ent["ws"], slice(k * vb, (k + 1) * vb)
+                if ent["plan"].nan_flag.data_ptr() != w["oc"][vb:].data_ptr():
+                    raise _lib.HipKernelError("predict_views: the eval plan's NaN flag is not behind the detection counts")
+                st["ob"][sl].copy_(w["ob"], non_blocking=True)
+                st["os"][sl].copy_(w["os"], non_blocking=True)
+                st["ol"][sl].copy_(w["ol"], non_blocking=True)
+                st["oc"][k].copy_(w["oc"], non_blocking=True)
+            counts = st["oc"][:, :vb].reshape(-1)[:V].contiguous()
+            out = merge_views_device(st["ob"][:V], st["os"][:V], st["ol"][:V], counts, views, tile, case.shape[1:], margin,
+                                     self.max_overlap, merge, top_k, workspace=st["ws"])
+            st["tail"][:1].copy_(out["count"], non_blocking=True)
+            st["tail"][1:].copy_(st["oc"][:, vb], non_blocking=True)
+            st["host"].copy_(st["tail"], non_blocking=True)
+            st["event"].record(torch.cuda.current_stream(dev))
+            st["event"].synchronize()  # the only host sync
+            n, flags = int(st["host"][0]), st["host"][1:].tolist()
+            for flag in flags:
+                self._engine.raise_on_nan_flag(flag)
+            if n == 0:  # ssd3d.py:437-440
+                return (torch.tensor([[0., 0., 0., 1., 1., 1.]], device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                        torch.zeros(1, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+            return out["boxes"][:n], out["labels"][:n], out["scores"][:n], out["support"][:n]
 
     def predict_input_buffer(self, shape):
         """The persistent device buffer ``predict_step`` stages batches of ``shape`` in (None before the first batch of that

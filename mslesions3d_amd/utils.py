@@ -503,3 +503,158 @@ def draw_boxes_device(boxes, labels, scores, shape, style, min_score=0., classes
     _lib.call("msl_draw_boxes", ptr(b), ptr(l), ptr(s), off.ctypes.data, N, *shape, DRAW_STYLES[style], float(min_score),
               ptr(inst), ptr(cls) if cls is not None else None, _stream())
     return inst, cls
+
+
+# ---- multi-view prediction: detections of V views of one case merged in the case frame --------
+MERGE_MODES = {"nms": 0, "fuse": 1}  # msl_views_merge's mode argument
+MERGE_MAX_VIEWS, MERGE_MAX_CANDIDATES = 64, 8192  # msl_views_merge's capacity: V and V * top_k
+
+
+def _merge_geometry(views, tile, case_shape, margin):
+    views = np.ascontiguousarray(np.asarray(views, dtype=np.int32))
+    tile, case_shape, margin = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (tile, case_shape, margin))
+    if views.ndim != 2 or views.shape[1] != 6 or views.shape[0] < 1 or not np.isin(views[:, 3:], (0, 1)).all():
+        raise ValueError("merge_views: views is (V, 6) rows o0, o1, o2, f0, f1, f2 with V >= 1 and 0 / 1 flip flags")
+    if not (tile.shape == case_shape.shape == margin.shape == (3,)) or tile.min() < 1 or case_shape.min() < 1 or margin.min() < 0:
+        raise ValueError("merge_views: tile, case_shape and margin are three ints each (sizes >= 1, margins >= 0)")
+    return views, tile, case_shape, margin
+
+
+def _owned(centre, origin, tile, case_shape, margin):
+    """The ownership test of a centre (..., 3) f32 in case voxels by the view(s) at ``origin`` (..., 3) ints: per axis
+    ``c >= o + m`` unless the tile starts at or before the case border, ``c < o + T - m`` unless it ends at or behind it."""
+    lo, hi = origin + margin, origin + tile - margin
+    return (((origin <= 0) | (centre >= lo.astype(np.float32))) &
+            ((origin + tile >= case_shape) | (centre < hi.astype(np.float32)))).all(-1)
+
+
+def _iou6_rows(a, b):
+    """csrc/iou6.hpp on the host: IoU of box ``a`` (6,) with the rows of ``b`` (M, 6), f32, the same operation order."""
+    e = np.maximum(np.minimum(a[3:], b[:, 3:]) - np.maximum(a[:3], b[:, :3]), np.float32(0))
+    inter = e[:, 0] * e[:, 1] * e[:, 2]
+    va = (a[3] - a[0]) * (a[4] - a[1]) * (a[5] - a[2])
+    vb = (b[:, 3] - b[:, 0]) * (b[:, 4] - b[:, 1]) * (b[:, 5] - b[:, 2])
+    return inter / (va + vb - inter)
+
+
+def merge_views(boxes, scores, labels, counts, views, tile, case_shape, margin, max_overlap, mode="nms", out_top_k=None):
+    """The detections of the V views of one case (``datasets.view_plan``) as ONE list in the case's own frame ->
+    ``(boxes (n, 6) f32, labels (n,) i64, scores (n,) f32, support (n,) i32)``, n <= ``out_top_k`` and possibly 0.
+
+    ``boxes`` (V, top_k, 6), ``scores`` (V, top_k), ``labels`` (V, top_k), ``counts`` (V,): what ``msl_detect_objects``
+    leaves per view (corner boxes as fractions of the view).  All f32 steps are single rounded operations.
+
+    Map: per axis k a corner pair (a, b) of a view flipped along k becomes (1 - b, 1 - a); voxel x = a * T_k + o_k; case
+    fraction x / n_k; nothing is clamped.  Candidates: slots j < counts[v] with label >= 1 (0 is the empty image's
+    placeholder) and a score that is not NaN whose centre (x_lo + x_hi) * 0.5 passes the view's ownership test
+    (``_owned``): a tile owns its core, out to the case border where it touches it, so of the copies of one lesion in
+    overlapping tiles only one is taken.  Per class, ascending: candidates ranked by descending score, ties by ascending
+    (view, slot); greedy NMS with ``iou > max_overlap`` on the case-frame boxes; a suppressed candidate is assigned to the
+    earliest-ranked kept one that overlaps it; ``support`` of a kept box = distinct views among it and its members.
+    ``mode="nms"``: the kept candidate's own box and score.  ``mode="fuse"``: box = sum(s_i * B_i) / sum(s_i) over the
+    cluster in rank order, accumulated in f64 and rounded to f32 once; score = the sum over views (ascending) of the view's
+    best member score, in f64, over max(cover, support), where cover = the views whose ownership test the kept centre
+    passes - a lesion one flip of eight sees is demoted, one all of them see keeps about its mean score.  Output: all
+    classes, by descending final score, ties by (class, rank of the kept candidate), the first ``out_top_k``.
+    ``msl_views_merge`` (csrc/views.hip) computes the same values on the device, bit for bit."""
+    f32 = np.float32
+    views, tile, case_shape, margin = _merge_geometry(views, tile, case_shape, margin)
+    if mode not in MERGE_MODES:
+        raise ValueError(f"merge must be one of {sorted(MERGE_MODES)}, got {mode!r}")
+    V = views.shape[0]
+    boxes = np.asarray(boxes, dtype=f32).reshape(V, -1, 6)
+    K = boxes.shape[1]
+    scores = np.asarray(scores, dtype=f32).reshape(V, K)
+    labels = np.asarray(labels, dtype=np.int64).reshape(V, K)
+    counts = np.asarray(counts, dtype=np.int64).reshape(V)
+    out_top_k = V * K if out_top_k is None else int(out_top_k)
+    origin, flip = views[:, None, :3].astype(np.int64), views[:, None, 3:] != 0
+    lo, hi = boxes[..., :3], boxes[..., 3:]
+    a, b = np.where(flip, f32(1) - hi, lo), np.where(flip, f32(1) - lo, hi)
+    x_lo, x_hi = a * tile.astype(f32) + origin.astype(f32), b * tile.astype(f32) + origin.astype(f32)
+    centre = (x_lo + x_hi) * f32(0.5)
+    cand = (np.arange(K)[None, :] < counts[:, None]) & (labels >= 1) & (scores == scores)
+    cand &= _owned(centre, origin, tile, case_shape, margin)
+    idx = np.flatnonzero(cand.reshape(-1))
+    frac = np.concatenate([x_lo / case_shape.astype(f32), x_hi / case_shape.astype(f32)], axis=-1).reshape(-1, 6)[idx]
+    sc, lab, view, cen = scores.reshape(-1)[idx], labels.reshape(-1)[idx], idx // K, centre.reshape(-1, 3)[idx]
+    order = np.lexsort((idx, -sc, lab))  # class ascending, score descending, (view, slot) ascending
+    frac, sc, lab, view, cen = frac[order], sc[order], lab[order], view[order], cen[order]
+    M = order.shape[0]
+    assign = np.full(M, -1, dtype=np.int64)
+    thr = f32(max_overlap)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for k in range(M):
+            if assign[k] >= 0:
+                continue
+            assign[k] = k
+            end = k + 1 + int(np.searchsorted(lab[k + 1:], lab[k], side="right"))  # the class ends here
+            if end > k + 1:
+                over = (_iou6_rows(frac[k], frac[k + 1:end]) > thr) & (assign[k + 1:end] < 0)
+                assign[k + 1:end][over] = k
+        kept = np.flatnonzero(assign == np.arange(M))
+        ob, os_ = np.empty((kept.shape[0], 6), dtype=f32), np.empty(kept.shape[0], dtype=f32)
+        support = np.empty(kept.shape[0], dtype=np.int32)
+        members = {int(k): [] for k in kept}
+        for i in range(M):
+            members[int(assign[i])].append(i)  # rank order
+        for r, k in enumerate(kept):
+            mem = members[int(k)]
+            seen = sorted(set(int(view[i]) for i in mem))
+            support[r] = len(seen)
+            if MERGE_MODES[mode] == 0:
+                ob[r], os_[r] = frac[k], sc[k]
+                continue
+            acc, wsum = np.zeros(6, dtype=np.float64), np.float64(0)
+            for i in mem:
+                w = np.float64(sc[i])
+                acc = acc + w * frac[i].astype(np.float64)
+                wsum = wsum + w
+            ob[r] = (acc / wsum).astype(f32)
+            total = np.float64(0)
+            for v in seen:
+                total = total + np.float64(max(sc[i] for i in mem if view[i] == v))
+            cover = int(_owned(cen[k][None, :], views[:, :3].astype(np.int64), tile, case_shape, margin).sum())
+            os_[r] = f32(total / np.float64(max(cover, int(support[r]))))
+    final = np.argsort(-os_, kind="stable")[:out_top_k]  # ties: (class, rank of the kept candidate) = position in kept
+    return ob[final], lab[kept][final].astype(np.int64), os_[final], support[final]
+
+
+def merge_views_workspace(V, top_k, dev):
+    """Workspace and output buffers of one ``msl_views_merge`` shape (raises beyond its capacity)."""
+    nbytes = int(_lib.load().msl_views_merge_workspace_bytes(int(V), int(top_k)))
+    if nbytes == 0:
+        raise ValueError(f"msl_views_merge takes at most {MERGE_MAX_VIEWS} views and {MERGE_MAX_CANDIDATES} detections "
+                         f"(views x top_k), got {V} x {top_k}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def merge_views_device(boxes, scores, labels, counts, views, tile, case_shape, margin, max_overlap, mode="nms",
+                       out_top_k=None, workspace=None, out=None):
+    """``merge_views`` on the HIP device (msl_views_merge on the current stream, no synchronisation): ``boxes`` (V, top_k,
+    6) f32, ``scores`` (V, top_k) f32, ``labels`` (V, top_k) i64 and ``counts`` (V,) i32 are device tensors in
+    ``msl_detect_objects``' output layout -> dict of device tensors ``boxes`` (out_top_k, 6), ``scores``, ``labels``,
+    ``support`` and ``count`` (1,): rows past ``count`` are not written."""
+    views, tile, case_shape, margin = _merge_geometry(views, tile, case_shape, margin)
+    if mode not in MERGE_MODES:
+        raise ValueError(f"merge must be one of {sorted(MERGE_MODES)}, got {mode!r}")
+    V, K = views.shape[0], boxes.shape[1]
+    if tuple(boxes.shape) != (V, K, 6) or tuple(scores.shape) != (V, K) or tuple(labels.shape) != (V, K) or counts.numel() != V:
+        raise ValueError("merge_views_device: boxes (V, top_k, 6), scores / labels (V, top_k), counts (V,)")
+    boxes, scores = _gpu(boxes, "merge_views_device"), _gpu(scores, "merge_views_device")
+    dev = boxes.device
+    labels, counts = labels.to(device=dev, dtype=torch.int64).contiguous(), counts.to(device=dev, dtype=torch.int32).contiguous()
+    out_top_k = V * K if out_top_k is None else int(out_top_k)
+    if workspace is None:
+        workspace = merge_views_workspace(V, K, dev)
+    if out is None:
+        out = dict(boxes=torch.empty((out_top_k, 6), dtype=torch.float32, device=dev),
+                   scores=torch.empty(out_top_k, dtype=torch.float32, device=dev),
+                   labels=torch.empty(out_top_k, dtype=torch.int64, device=dev),
+                   support=torch.empty(out_top_k, dtype=torch.int32, device=dev),
+                   count=torch.empty(1, dtype=torch.int32, device=dev))
+    geometry = np.asarray(list(tile) + list(case_shape) + list(margin) + [V, K, out_top_k], dtype=np.int32)
+    _lib.call("msl_views_merge", ptr(boxes), ptr(scores), ptr(labels), ptr(counts), views.ctypes.data, geometry.ctypes.data,
+              float(max_overlap), MERGE_MODES[mode], ptr(workspace), workspace.numel(), ptr(out["boxes"]), ptr(out["scores"]),
+              ptr(out["labels"]), ptr(out["support"]), ptr(out["count"]), _stream())
+    return out

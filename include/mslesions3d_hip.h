@@ -493,6 +493,16 @@ int msl_foreground_box_mc(const float* vol, int C, int D, int H, int W, int marg
 int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
                        int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
                        void* stream);
+/* Patch training (datasets.window / patch_origin, devicedata.LesionCache with a patch size).
+ * msl_augment_window_mc: msl_augment_fit_mc in every respect (1 <= C <= 4, the same arenas, table, params, outputs and
+ * zero rows) except the shift: windows (device, N x 3 i32) gives sample n its own d_k = windows[3n + k] in place of the
+ * centred value, so output voxel o reads voxel q = clamp(o + d, 0, n' - 1) of the permuted case: the window of
+ * T0 x T1 x T2 voxels at origin d, edge-replicated outside the case.  Any int is an origin (o + d is formed in 64 bits).
+ * windows = the fit's shifts gives msl_augment_fit_mc's output bit for bit.  Every output voxel is written exactly once:
+ * no memset, no atomics.  -1 (nothing launched, nothing written): windows null, or what msl_augment_fit_mc refuses. */
+int msl_augment_window_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                          const long long* table, int n_cases, const double* params, const int* windows, int N, int T0,
+                          int T1, int T2, float* dst_img, short* dst_seg, void* stream);
 
 /* ---- native grid -> LPI at 1 mm (csrc/datapipe.hip, devicedata.LesionCache / LesionPredictFeed)
  * msl_regrid: datasets.regrid of one case, bit for bit.  src_img (C,n0,n1,n2) f32 with 1 <= C <= 4, src_seg (n0,n1,n2)

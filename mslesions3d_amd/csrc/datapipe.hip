@@ -1135,6 +1135,11 @@ int msl_instance_boxes(const short* seg, int N, int D, int H, int W, const int* 
 //                coordinate row, the boundary maps, the axis weights and the order-0 mask tap are computed once per
 //                voxel; only the eight gathers, the f64 accumulation and the intensity operations repeat per channel,
 //                each in fit_kernel's operation order (a channel is bit-identical to a one-channel launch on its plane)
+//   window     : the same body (WIN) with the shift d read per sample from `windows` instead of centred: a training patch
+//                or a validation tile (datasets.window).  With the affine off, a thread whose four
+//                sources are one in-range run of an unreversed last axis reads them with one 16-byte load per plane and
+//                one 8-byte load of the mask where those addresses are aligned (views.hip's rule) - a patch inside a
+//                large head is that case nearly everywhere
 namespace {
 
 constexpr int FIT_MAX_CH = 4;  // the stem's limit
@@ -1169,11 +1174,20 @@ __global__ __launch_bounds__(FG_THREADS) void fg_reduce_mc_kernel(const float* _
   }
 }
 
-template <int C, bool VEC>
+// source index of output index o under the shift d on an axis of n voxels.  The fit's d is bounded by the sizes; a window's
+// origin is any int (far outside the case it repeats the border voxel), so that sum is formed in 64 bits
+template <bool WIN>
+__device__ __forceinline__ int fit_src(int o, int d, int n) {
+  if (!WIN) return min(max(o + d, 0), n - 1);
+  const long long q = (long long)o + d;
+  return q < 0 ? 0 : (q > n - 1 ? n - 1 : (int)q);
+}
+
+template <int C, bool VEC, bool WIN>
 __global__ __launch_bounds__(DP_THREADS) void fit_mc_kernel(
     const float* __restrict__ src_img, const short* __restrict__ src_seg, long long seg_elems,
-    const long long* __restrict__ table, int n_cases, const double* __restrict__ params, int T0, int T1, int T2,
-    float* __restrict__ dst_img, short* __restrict__ dst_seg) {
+    const long long* __restrict__ table, int n_cases, const double* __restrict__ params,
+    const int* __restrict__ windows, int T0, int T1, int T2, float* __restrict__ dst_img, short* __restrict__ dst_seg) {
   const int G = (T2 + FIT_VEC - 1) / FIT_VEC;
   const long long groups = (long long)T0 * T1 * G;
   const long long g = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
@@ -1225,16 +1239,46 @@ __global__ __launch_bounds__(DP_THREADS) void fit_mc_kernel(
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       dims[a] = (int)sn[ax[a]];
-      dsh[a] = dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2;
+      dsh[a] = WIN ? windows[3 * (long long)n + a]
+                   : (dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2);
       pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
       if (rev[a]) base += (long long)(dims[a] - 1) * sstride[ax[a]];
     }
-    const int q0 = min(max(oc0 + dsh[0], 0), dims[0] - 1), q1 = min(max(oc1 + dsh[1], 0), dims[1] - 1);
+    const int q0 = fit_src<WIN>(oc0, dsh[0], dims[0]), q1 = fit_src<WIN>(oc1, dsh[1], dims[1]);
     const bool affine = p[7] != 0.0;
     const int mode = (int)p[20];
     int qprev = -1;
-    for (int j = 0; j < cnt; ++j) {
-      const int qc[3] = {q0, q1, min(max(x0 + j + dsh[2], 0), dims[2] - 1)};
+    int jn = cnt;  // voxels the loop below still has to fill
+    const long long xs = (long long)x0 + dsh[2];  // source of the thread's first voxel, before the clamp
+    if (WIN && !affine && cnt == FIT_VEC && pst[2] == 1 && xs >= 0 && xs + FIT_VEC <= dims[2]) {
+      // interior run: sources s .. s + 3 of one row of the case, the values the loop would read one by one
+      const long long s = base + q0 * pst[0] + q1 * pst[1] + xs;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float* sp = si + c * V + s;
+        float4 x;
+        if (((uintptr_t)sp & 15u) == 0) {
+          x = *reinterpret_cast<const float4*>(sp);
+        } else {
+          x = make_float4(sp[0], sp[1], sp[2], sp[3]);
+        }
+        vi[c][0] = apply_ops(x.x, p);
+        vi[c][1] = apply_ops(x.y, p);
+        vi[c][2] = apply_ops(x.z, p);
+        vi[c][3] = apply_ops(x.w, p);
+      }
+      const short* mp = ss + s;
+      if (((uintptr_t)mp & 7u) == 0) {
+        typedef short short4v __attribute__((ext_vector_type(4)));
+        const short4v m = *reinterpret_cast<const short4v*>(mp);
+        vs[0] = m[0]; vs[1] = m[1]; vs[2] = m[2]; vs[3] = m[3];
+      } else {
+        vs[0] = mp[0]; vs[1] = mp[1]; vs[2] = mp[2]; vs[3] = mp[3];
+      }
+      jn = 0;
+    }
+    for (int j = 0; j < jn; ++j) {
+      const int qc[3] = {q0, q1, fit_src<WIN>(x0 + j, dsh[2], dims[2])};
       if (j > 0 && qc[2] == qprev) {  // padded region along the last axis: the same source voxel, the same values
 #pragma unroll
         for (int c = 0; c < C; ++c) vi[c][j] = vi[c][j - 1];
@@ -1323,16 +1367,39 @@ __global__ __launch_bounds__(DP_THREADS) void fit_mc_kernel(
   }
 }
 
-template <int C>
+template <int C, bool WIN>
 void launch_fit_mc(bool vec, dim3 grid, hipStream_t st, const float* arena_img, const short* arena_seg, long long seg_elems,
-                   const long long* table, int n_cases, const double* params, int T0, int T1, int T2, float* dst_img,
-                   short* dst_seg) {
+                   const long long* table, int n_cases, const double* params, const int* windows, int T0, int T1, int T2,
+                   float* dst_img, short* dst_seg) {
   if (vec)
-    MSL_LAUNCH(fit_mc_kernel<C, true>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
-               params, T0, T1, T2, dst_img, dst_seg);
+    MSL_LAUNCH(fit_mc_kernel<C, true, WIN>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
+               params, windows, T0, T1, T2, dst_img, dst_seg);
   else
-    MSL_LAUNCH(fit_mc_kernel<C, false>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
-               params, T0, T1, T2, dst_img, dst_seg);
+    MSL_LAUNCH(fit_mc_kernel<C, false, WIN>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
+               params, windows, T0, T1, T2, dst_img, dst_seg);
+}
+
+// the launch of msl_augment_fit_mc (windows null: the centred fit) and msl_augment_window_mc
+template <bool WIN>
+int augment_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+               int n_cases, const double* params, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
+               short* dst_seg, void* stream) {
+  if (!arena_img || !arena_seg || !table || !params || !dst_img || !dst_seg || seg_elems <= 0 || C < 1 ||
+      C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
+    return MSL_ERR_ARG;
+  const long long groups = (long long)T0 * T1 * ((T2 + FIT_VEC - 1) / FIT_VEC);
+  if (N > 65535 || (groups + DP_THREADS - 1) / DP_THREADS > 0x7FFFFFFFLL) return MSL_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((groups + DP_THREADS - 1) / DP_THREADS), N);
+  const bool vec = T2 % FIT_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (C) {
+    case 1: launch_fit_mc<1, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+    case 2: launch_fit_mc<2, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+    case 3: launch_fit_mc<3, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+    default: launch_fit_mc<4, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+  }
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
 }
 
 }  // namespace
@@ -1354,22 +1421,16 @@ int msl_foreground_box_mc(const float* vol, int C, int D, int H, int W, int marg
 int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
                        int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
                        void* stream) {
-  if (!arena_img || !arena_seg || !table || !params || !dst_img || !dst_seg || seg_elems <= 0 || C < 1 ||
-      C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
-    return MSL_ERR_ARG;
-  const long long groups = (long long)T0 * T1 * ((T2 + FIT_VEC - 1) / FIT_VEC);
-  if (N > 65535 || (groups + DP_THREADS - 1) / DP_THREADS > 0x7FFFFFFFLL) return MSL_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)((groups + DP_THREADS - 1) / DP_THREADS), N);
-  const bool vec = T2 % FIT_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
-  hipStream_t st = (hipStream_t)stream;
-  switch (C) {
-    case 1: launch_fit_mc<1>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
-    case 2: launch_fit_mc<2>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
-    case 3: launch_fit_mc<3>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
-    default: launch_fit_mc<4>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, T0, T1, T2, dst_img, dst_seg); break;
-  }
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return augment_mc<false>(arena_img, arena_seg, seg_elems, C, table, n_cases, params, nullptr, N, T0, T1, T2, dst_img,
+                           dst_seg, stream);
+}
+
+int msl_augment_window_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                          const long long* table, int n_cases, const double* params, const int* windows, int N, int T0,
+                          int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
+  if (!windows) return MSL_ERR_ARG;
+  return augment_mc<true>(arena_img, arena_seg, seg_elems, C, table, n_cases, params, windows, N, T0, T1, T2, dst_img,
+                          dst_seg, stream);
 }
 
 }  // extern "C"

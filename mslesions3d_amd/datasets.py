@@ -341,7 +341,7 @@ def collate_fn(batch):
            "subject": [b["subject"] for b in batch], "img_meta_dict": [b["img_meta_dict"] for b in batch],
            "seg_meta_dict": [b["seg_meta_dict"] for b in batch], "img_transforms": [b["img_transforms"] for b in batch],
            "seg_transforms": [b["seg_transforms"] for b in batch]}
-    for key in GEOMETRY_KEYS + ("native_shape",):  # LesionsDataModule samples carry them; passed through as lists
+    for key in GEOMETRY_KEYS + ("native_shape", "patch_origin"):  # LesionsDataModule samples carry them; passed through as lists
         if all(key in b for b in batch):
             out[key] = [b[key] for b in batch]
     return out
@@ -449,6 +449,21 @@ def resize_with_pad_or_crop(vol, spatial_size):
     return vol
 
 
+def window(vol, origin, size):
+    """The window of ``size`` voxels at ``origin`` of the trailing three axes of ``vol``: output index p of axis k reads
+    source index clamp(p + origin_k, 0, n_k - 1) - edge replication; origins may be negative and windows may overhang.
+    ``window(v, [fit_shift(n, t) ...], t)`` is ``resize_with_pad_or_crop(v, t)``, and it is the unflipped row
+    (origin, 0, 0, 0) of ``gather_views``.  ``msl_augment_window_mc`` (csrc/datapipe.hip) takes the same origins."""
+    vol = np.asarray(vol)
+    if len(origin) != 3 or len(size) != 3 or vol.ndim < 3:
+        raise ValueError("window: three origins and three sizes on an array of at least three axes")
+    first = vol.ndim - 3
+    for k in range(3):
+        n = vol.shape[first + k]
+        vol = np.take(vol, np.clip(np.arange(int(size[k])) + int(origin[k]), 0, n - 1), axis=first + k)
+    return vol
+
+
 def fit_to_case_frame(boxes, target, crop_shape, crop_origin, full_shape):
     """Corner boxes, fractional in the fitted frame of ``target`` voxels -> the same boxes, fractional in the case's own
     frame of ``full_shape`` voxels.  ``boxes`` (K, 6) float32; ``crop_shape`` / ``crop_origin`` are the shape and the ``lo``
@@ -544,6 +559,33 @@ def gather_views(case, views, tile):
     return out
 
 
+def _instance_extents(seg, thresholds, mode):
+    """The walk of ``boxes_from_instances`` -> (inclusive integer extents [min..., max...] as a list of rows, labels,
+    the mask's shape), flat boxes still in."""
+    seg = np.squeeze(np.asarray(seg))
+    if mode == "binary":
+        seg, _ = cc_label(seg)
+        thresholds = [(1, np.inf)]
+    elif mode != "instances":
+        raise ValueError(f"unknown segmentation mode {mode!r}")
+    ids = np.unique(seg)[1:]
+    extents, labels = [], []
+    for c, (lo, hi) in enumerate(thresholds):
+        for l in ids[(ids >= lo) & (ids < hi)]:
+            idx = np.where(seg == l)
+            extents.append([idx[0].min(), idx[1].min(), idx[2].min(), idx[0].max(), idx[1].max(), idx[2].max()])
+            labels.append(c + 1)
+    return extents, labels, seg.shape
+
+
+def _fractional_boxes(extents, shape):
+    """Integer extents / image size in f32 -> ((K, 6) boxes, keep mask of the boxes with a volume)."""
+    size = np.array(tuple(shape) * 2, dtype=np.float32)
+    boxes = torch.from_numpy(np.asarray(extents, dtype=np.float32).reshape(-1, 6) / size)
+    keep = ((boxes[:, 3] - boxes[:, 0]) * (boxes[:, 4] - boxes[:, 1]) * (boxes[:, 5] - boxes[:, 2])) != 0
+    return boxes, keep
+
+
 def boxes_from_instances(seg, thresholds, mode="instances"):
     """BoundingBoxesGeneratord, 'instances' mode (utils.py:442-443, 472-481, 485-513) on an instance-labelled mask: the
     ids are the sorted unique values with the FIRST one discarded (the background - on a mask without background the
@@ -551,26 +593,67 @@ def boxes_from_instances(seg, thresholds, mode="instances"):
     the inclusive voxel extents [min..., max...] and the label is the pair's position + 1; ids outside every pair are
     dropped; extents / image size in f32; zero-volume boxes removed.  ``mode="binary"`` (utils.py:445-448): connected
     components of the mask first, then thresholds [(1, inf)]."""
-    seg = np.squeeze(np.asarray(seg))
-    if mode == "binary":
-        seg, _ = cc_label(seg)
-        thresholds = [(1, np.inf)]
-    elif mode != "instances":
-        raise ValueError(f"unknown segmentation mode {mode!r}")
-    size = np.array(seg.shape * 2, dtype=np.float32)
-    ids = np.unique(seg)[1:]
-    boxes, labels = [], []
-    for c, (lo, hi) in enumerate(thresholds):
-        for l in ids[(ids >= lo) & (ids < hi)]:
-            idx = np.where(seg == l)
-            boxes.append([idx[0].min(), idx[1].min(), idx[2].min(), idx[0].max(), idx[1].max(), idx[2].max()])
-            labels.append(c + 1)
-    boxes = torch.from_numpy(np.asarray(boxes, dtype=np.float32).reshape(-1, 6) / size)
+    extents, labels, shape = _instance_extents(seg, thresholds, mode)
+    boxes, keep = _fractional_boxes(extents, shape)
     labels = torch.tensor(labels, dtype=torch.long)
     if boxes.numel():
-        keep = ((boxes[:, 3] - boxes[:, 0]) * (boxes[:, 4] - boxes[:, 1]) * (boxes[:, 5] - boxes[:, 2])) != 0
         boxes, labels = boxes[keep], labels[keep]
     return boxes, labels
+
+
+# ---- patch training: one sampled window per case and epoch (DESIGN.md section 4.12) -----------------------------------
+def lesion_centres(seg, thresholds, mode="instances"):
+    """-> f64 (K, 3): per box ``boxes_from_instances`` keeps, in its order, the centre (min + max) / 2 of the inclusive
+    integer voxel extents (so a lesion of an even number of voxels along an axis has a half-integer centre there)."""
+    extents, _, shape = _instance_extents(seg, thresholds, mode)
+    ext = np.asarray(extents, dtype=np.float64).reshape(-1, 6)
+    if ext.shape[0]:
+        ext = ext[_fractional_boxes(extents, shape)[1].numpy()]
+    return (ext[:, :3] + ext[:, 3:]) / 2
+
+
+def centres_to_augmented(centres, shape, perm, stages=()):
+    """Voxel positions (K, 3) f64 of a case of ``shape`` -> the same points in the frame of the augmented case.  ``perm``
+    = (ax, rev) and ``stages`` come from ``devicedata.sample_params(..., ragged=True)``, the parameters both routes share.
+    Signed permutation: c'_a = n'_a - 1 - c[ax_a] where rev_a, else c[ax_a], with n'_a = shape[ax_a].  Then per affine
+    stage, in order, q = solve(M, c' - offset): the inverse of "output voxel q samples at M q + offset" (f64).  Stages
+    without a matrix (None, intensity operations) do not move a point."""
+    c = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+    ax, rev = perm
+    out = np.empty_like(c)
+    for a in range(3):
+        out[:, a] = (shape[ax[a]] - 1) - c[:, ax[a]] if rev[a] else c[:, ax[a]]
+    for st in stages:
+        if hasattr(st, "matrix") and out.shape[0]:
+            out = np.linalg.solve(np.asarray(st.matrix, dtype=np.float64),
+                                  (out - np.asarray(st.offset, dtype=np.float64)).T).T
+    return out
+
+
+def patch_origin(rs, shape, patch, centres, foreground):
+    """The origin (three ints) of one training window of ``patch`` voxels in a case of ``shape`` (the augmented case's n');
+    ``centres`` (K, 3) are lesion centres in that frame.  Always eight draws, in this order, whichever branch is taken:
+    ``u, ku = rs.random_sample(2)``, ``j = rs.random_sample(3)``, ``r = rs.random_sample(3)``.  With K > 0 and
+    u < foreground the window goes on lesion k = min(int(ku * K), K - 1): per axis o = floor(c_k) - t // 2 +
+    floor((j - 0.5) * (t // 2)), a jitter of up to a quarter patch either way; otherwise o = floor(r * (n' - t + 1)),
+    uniform over the positions inside the case.  Then per axis: n' <= t gives ``fit_shift(n', t)`` (the whole axis,
+    padded as the fit pads it), else o is clamped to [0, n' - t].  On the lesion branch with the centre inside the case,
+    floor(c) lies in [o, o + t) on every axis: the jitter leaves it between t // 4 and 3 t // 4 + 1 voxels in, and a
+    clamp moves the window towards it."""
+    u, ku = rs.random_sample(2)
+    j = rs.random_sample(3)
+    r = rs.random_sample(3)
+    centres = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+    K = centres.shape[0]
+    shape, patch = [int(n) for n in shape], [int(t) for t in patch]
+    if len(shape) != 3 or len(patch) != 3 or min(shape + patch) < 1:
+        raise ValueError(f"patch_origin: three positive sizes each, got {shape} and {patch}")
+    if K > 0 and u < foreground:
+        c = centres[min(int(ku * K), K - 1)]
+        o = [int(np.floor(c[a])) - patch[a] // 2 + int(np.floor((j[a] - 0.5) * (patch[a] // 2))) for a in range(3)]
+    else:
+        o = [int(np.floor(r[a] * (shape[a] - patch[a] + 1))) for a in range(3)]
+    return tuple(fit_shift(n, t) if n <= t else min(max(v, 0), n - t) for v, n, t in zip(o, shape, patch))
 
 
 # ---- native grid -> LPI at 1 mm (reference datasets.py:199-205: orientation(axcodes="LPI"), spacing(pixdim=(1, 1, 1))) --
@@ -700,6 +783,46 @@ def normalize_nonzero(img):
     return img
 
 
+NORM_LANES = 1024  # NORM_THREADS of csrc/datapipe.hip
+
+
+def _lane_sum(values):
+    """f64 sum of a flat f64 array in msl_normalize_nonzero's order: lane t adds elements t, t + 1024, ... one after the
+    other from 0.0, then the lanes fold as a tree, lane t += lane t + s for s = 512 .. 1."""
+    pad = (-values.size) % NORM_LANES
+    rows = np.concatenate([values, np.zeros(pad)]).reshape(-1, NORM_LANES)
+    acc = np.zeros(NORM_LANES, dtype=np.float64)
+    for row in rows:
+        acc = acc + row
+    s = NORM_LANES // 2
+    while s:
+        acc = acc[:s] + acc[s:2 * s]
+        s //= 2
+    return float(acc[0])
+
+
+def normalize_nonzero_device(img):
+    """NormalizeIntensity(nonzero=True) with the arithmetic of msl_normalize_nonzero (csrc/datapipe.hip), bit for bit:
+    the sum of the non-zero voxels and, with mean = sum / count, the sum of their (v - mean)^2, both in f64 in the
+    kernel's fixed order (``_lane_sum``; a zero voxel adds 0.0, which changes nothing); then (v - f32(mean)) /
+    f32(sqrt(q / count)) in f32 on the non-zero voxels, a deviation of 0 taken as 1.  Within the bound of DESIGN.md section
+    4.7 of ``normalize_nonzero``, whose f32 sums are numpy's.  Patch training normalises with it on the host, so that the
+    host and the device route train on the same bits."""
+    img = np.array(img, dtype=np.float32)
+    nz = img != 0
+    count = int(nz.sum())
+    if count == 0:
+        return img
+    flat = img.reshape(-1).astype(np.float64)
+    mean = _lane_sum(flat) / float(count)
+    dev = np.where(nz.reshape(-1), flat - mean, 0.0)
+    std = np.float32(np.sqrt(_lane_sum(dev * dev) / float(count)))
+    if std == 0:
+        std = np.float32(1.0)
+    img[nz] = (img[nz] - np.float32(mean)) / std
+    return img
+
+
 def _same_affine(affine, other, case, name):
     """Image(s) and mask of one case share one affine (or none of them has one): ValueError otherwise."""
     if (affine is None) != (other is None) or (affine is not None and not np.allclose(affine, other, rtol=0.0, atol=1e-4)):
@@ -714,7 +837,7 @@ class _LesionCases(Dataset):
     box is the union of the channels' foregrounds, every channel is normalised over its own non-zero voxels, and one set
     of augmentation draws moves all channels and the mask (the intensity operands are shared, as in MONAI)."""
 
-    def __init__(self, module, subjects, augmentations=None, seed=0):
+    def __init__(self, module, subjects, augmentations=None, seed=0, patch=None):
         self.module, self.subjects = module, list(subjects)
         self.root = module.data_dir  # the key DeviceCache-style caches file a case under, with its subject
         self.augmentations = list(augmentations or [])
@@ -722,6 +845,7 @@ class _LesionCases(Dataset):
             if (t if isinstance(t, str) else t[0]) not in AUGMENTATIONS:
                 raise ValueError(f"unknown transform {t!r}")
         self.seed, self.epoch = seed, 0
+        self.patch = None if patch is None else tuple(int(t) for t in patch)  # training windows instead of the fit
         self._plans = {}  # position -> the RegridPlan of the case's last load (None: no affine); native_plan
 
     def set_epoch(self, epoch):
@@ -780,7 +904,9 @@ class _LesionCases(Dataset):
             raise ValueError("case_sample: the case frame is defined for the un-augmented pipeline")
         return self._sample(i, False)
 
-    def _sample(self, i, fit):
+    def cropped(self, i):
+        """Steps 1-3 of case i -> (image (C,) + crop_shape f32 normalised, mask (1,) + crop_shape, plan or None, crop
+        origin, crop_shape, full_shape)."""
         m = self.module
         img, seg, plan = self.load_regridded(i)
         full_shape = tuple(int(v) for v in seg.shape)
@@ -788,16 +914,42 @@ class _LesionCases(Dataset):
         sl = tuple(slice(a, b) for a, b in zip(lo, hi))  # crop_foreground
         img, seg = img[(slice(None),) * (img.ndim - 3) + sl], seg[sl]
         crop_shape = tuple(int(b - a) for a, b in zip(lo, hi))
+        # patch training: the device route's arithmetic, so that both routes train on the same bits
+        norm = normalize_nonzero if getattr(m, "patch_size", None) is None else normalize_nonzero_device
         if img.ndim == 3:
-            img = normalize_nonzero(img)[None]  # add_channel
+            img = norm(img)[None]  # add_channel
         else:
-            img = np.stack([normalize_nonzero(ch) for ch in img])  # channel_wise: each sequence on its own scale
-        seg = seg[None]
-        rs = self.sample_rng(i) if self.augmentations else None
+            img = np.stack([norm(ch) for ch in img])  # channel_wise: each sequence on its own scale
+        return img, seg[None], plan, lo, crop_shape, full_shape
+
+    def crop_shape(self, i):
+        """The shape of case i's foreground crop (the case is loaded for it)."""
+        lo, hi = foreground_box(self.load(i)[0], self.module.margin)
+        return tuple(int(b - a) for a, b in zip(lo, hi))
+
+    def _sample(self, i, fit, origin=None, cropped=None):
+        """``origin``: window the un-augmented case there at the module's patch size instead of fitting it (a validation
+        tile of patch training); ``cropped``: the case's ``cropped(i)`` where the caller holds it already."""
+        m = self.module
+        img, seg, plan, lo, crop_shape, full_shape = self.cropped(i) if cropped is None else cropped
+        patch = self.patch if origin is None else m.patch_size
+        centres = None
+        if patch is not None and origin is None:  # on the cropped mask, before it moves
+            centres = lesion_centres(seg, m.thresholds, m.segmentation_mode)
+        rs = self.sample_rng(i) if self.augmentations or centres is not None else None
         for t in self.augmentations:
             name, kw = (t, {}) if isinstance(t, str) else t
             img, seg = AUGMENTATIONS[name](img, seg, rs, **kw)
-        if fit:
+        if centres is not None:
+            # the window's draws follow every augmentation draw: a sample's augmentation does not depend on patch mode
+            from .devicedata import sample_params  # (devicedata imports this module)
+            draws = draw_augmentations(self.augmentations, self.sample_rng(i))
+            perm, stages = sample_params(draws, crop_shape, self.augmentations, ragged=True)
+            origin = patch_origin(rs, img.shape[1:], patch, centres_to_augmented(centres, crop_shape, perm, stages),
+                                  m.patch_foreground)
+        if origin is not None:
+            img, seg = window(img, origin, patch), window(seg, origin, patch)
+        elif fit:
             img, seg = resize_with_pad_or_crop(img, m.spatial_size), resize_with_pad_or_crop(seg, m.spatial_size)
         img = np.ascontiguousarray(img)
         boxes, labels = boxes_from_instances(seg, m.thresholds, m.segmentation_mode)
@@ -806,10 +958,40 @@ class _LesionCases(Dataset):
                "img_transforms": [], "seg_transforms": [],
                # the geometry fit_to_case_frame needs: the crop's lo and shape, the case's shape
                "crop_origin": lo, "crop_shape": crop_shape, "full_shape": full_shape}
+        if origin is not None:  # of the window, in the (augmented) cropped case's voxels
+            out["patch_origin"] = tuple(int(v) for v in origin)
         if plan is not None:  # a case with an affine: full_shape is the regridded shape, the stored one rides along
             out["img_meta_dict"] = {"affine": plan.out_affine}
             out["native_shape"] = tuple(plan.src_shape)
         return out
+
+
+class _LesionTiles(Dataset):
+    """The validation set of patch training: case-major, tile-minor, the unflipped tiles of ``view_plan(crop_shape, patch,
+    margin)`` of every case of an un-augmented ``_LesionCases`` - the windows ``predict.py --views tiles`` shows the
+    network.  A sample is the case windowed at the tile's origin, with the boxes of the windowed mask.  ``tiles`` lists
+    (case position, origin); it needs every case's crop shape, so the first use loads each case once.  The last case
+    prepared is kept, so walking the tiles in order prepares every case once more, not once per tile."""
+
+    def __init__(self, cases, patch, margin):
+        self.cases, self.patch, self.margin = cases, tuple(patch), tuple(margin)
+        self._tiles, self._held = None, (None, None)
+
+    @property
+    def tiles(self):
+        if self._tiles is None:
+            self._tiles = [(i, tuple(int(v) for v in row[:3])) for i in range(len(self.cases))
+                           for row in view_plan(self.cases.crop_shape(i), self.patch, self.margin)]
+        return self._tiles
+
+    def __len__(self):
+        return len(self.tiles)
+
+    def __getitem__(self, k):
+        i, origin = self.tiles[k]
+        if self._held[0] != i:
+            self._held = (i, self.cases.cropped(i))
+        return self.cases._sample(i, False, origin=origin, cropped=self._held[1])
 
 
 class LesionsDataModule(ExampleDataset):
@@ -836,7 +1018,16 @@ class LesionsDataModule(ExampleDataset):
     regridded grid's affine and ``native_shape``, and ``full_shape`` is the regridded shape.  A case without an affine is
     taken as already LPI at 1 mm.  Left out: ``fold`` (the reference indexes a list with an index array there and cannot
     run) and the rotational resampling of oblique acquisitions (the obliquity is kept).  Not in the reference:
-    ``spatial_size`` (its fixed (250, 300, 300)), ``rank`` / ``world_size`` (this process's data-parallel shard)."""
+    ``spatial_size`` (its fixed (250, 300, 300)), ``rank`` / ``world_size`` (this process's data-parallel shard).
+
+    ``patch_size`` (patch training; not in the reference): every training sample is one window
+    of that size of the cropped, normalised, augmented case at ``patch_origin`` (with probability ``patch_foreground`` on
+    a lesion, else uniform) instead of the fit, and carries "patch_origin"; a lesion the window cuts is labelled by its
+    visible part, as the fit's crop labels it.  The validation set becomes ``_LesionTiles``: the un-augmented tiles of
+    ``view_plan(crop_shape, patch_size, tile_margin)`` of every validation case.  ``spatial_size`` is then not used (the
+    prediction data set still fits to it).  Cases are normalised by ``normalize_nonzero_device``, the arithmetic of the
+    device route, so ``-c 0`` and ``-c 1`` train on the same bits.  The augmentation list must be in the order ``devicedata.sample_params``
+    takes (the lesion centres follow the sample through its parameters)."""
 
     margin = 5  # crop_foreground
     SEQUENCES = ("FLAIR", "acq-phase_T2star", "acq-mag_T2star")  # the images of _get_sequence; other names are masks
@@ -844,7 +1035,8 @@ class LesionsDataModule(ExampleDataset):
     def __init__(self, data_dir="../data/raw", centers=("CHUV_RIM_OK", "BASEL_INSIDER_OK"), input_images=("FLAIR",),
                  segmentation="labeled_lesions", classes=("lesion",), registration="T2star", skullstripped=True,
                  augmentations=None, subject=None, batch_size=8, percentage=1., num_workers=0, random_state=970205,
-                 cache=False, spatial_size=(250, 300, 300), rank=0, world_size=1):
+                 cache=False, spatial_size=(250, 300, 300), rank=0, world_size=1, patch_size=None, patch_foreground=0.67,
+                 tile_margin=(8, 8, 8)):
         input_images = (input_images,) if isinstance(input_images, str) else tuple(input_images)
         if not 1 <= len(input_images) <= 4:
             raise ValueError(f"1 .. 4 input sequences (the stem's limit), got {len(input_images)}: {input_images}")
@@ -862,6 +1054,14 @@ class LesionsDataModule(ExampleDataset):
         self.spatial_size = tuple(int(t) for t in spatial_size)
         if len(self.spatial_size) != 3 or min(self.spatial_size) <= 0:
             raise ValueError(f"spatial_size must be three positive sizes, got {spatial_size}")
+        self.patch_size = None if patch_size is None else tuple(int(t) for t in patch_size)
+        self.patch_foreground, self.tile_margin = float(patch_foreground), tuple(int(v) for v in tile_margin)
+        if self.patch_size is not None and (len(self.patch_size) != 3 or min(self.patch_size) <= 0):
+            raise ValueError(f"patch_size must be three positive sizes, got {patch_size}")
+        if not 0.0 <= self.patch_foreground <= 1.0:
+            raise ValueError(f"patch_foreground is a probability, got {patch_foreground}")
+        if len(self.tile_margin) != 3 or min(self.tile_margin) < 0:
+            raise ValueError(f"tile_margin must be three margins >= 0, got {tile_margin}")
         self.rank, self.world_size, self.epoch = rank, world_size, 0
         self.segmentation_mode = "instances" if "labeled" in segmentation else "binary"
         if self.segmentation_mode == "binary":
@@ -908,6 +1108,8 @@ class LesionsDataModule(ExampleDataset):
         else:
             train, test = train_test_split(self.subjects_list, train_size=0.8, test_size=0.2,
                                            random_state=self.random_state)
-        self.train_dataset = _LesionCases(self, train, self.augmentations, self.random_state)
+        self.train_dataset = _LesionCases(self, train, self.augmentations, self.random_state, patch=self.patch_size)
         self.test_dataset = _LesionCases(self, test)
+        if self.patch_size is not None:
+            self.test_dataset = _LesionTiles(self.test_dataset, self.patch_size, self.tile_margin)
         self.predict_dataset = _LesionCases(self, train if stage == "predict_train" else test)

@@ -17,7 +17,9 @@ foreground, in one flat arena; shape-changing rot90s allowed; every batch padded
 instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes).  A module with
 C > 1 input sequences is cached channel-planar and goes through msl_foreground_box_mc / msl_augment_fit_mc.  A case that
 carries an affine is uploaded on its native grid and put on the LPI 1 mm grid by msl_regrid (``regrid_device``, the
-device form of ``datasets.regrid``, bit for bit) in front of the foreground box.
+device form of ``datasets.regrid``, bit for bit) in front of the foreground box.  A module with a ``patch_size`` (patch
+training) gets one sampled window per case and epoch instead of the fit, and validation tiles
+(msl_augment_window_mc with the origins ``datasets.patch_origin`` / ``datasets.view_plan`` give on the host).
 """
 from collections import namedtuple
 
@@ -27,8 +29,8 @@ from os.path import join as pjoin
 
 from . import _lib
 from ._lib import ptr
-from .datasets import (SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset, draw_augmentations, regrid_plan,
-                       sample_rng)
+from .datasets import (SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset, centres_to_augmented,
+                       draw_augmentations, patch_origin, regrid_plan, sample_rng, view_plan)
 
 PARAM_STRIDE = 16  # f64 per sample of msl_augment_resample
 AFFINE_STRIDE = 32  # f64 per sample of msl_augment_affine
@@ -455,6 +457,7 @@ class DeviceCache:
 
 # ---- clinical cases: ragged sources, instance masks (datasets.LesionsDataModule) ---------------------------------------
 INT_MAX = 2 ** 31 - 1
+INST_MAX_IDS = 32767  # msl_instance_boxes labels ids 1 .. 32767: no image holds more boxes
 
 
 def threshold_table(thresholds):
@@ -594,13 +597,22 @@ class LesionCache:
     With C = len(dataset.input_images) > 1 a case is C contiguous f32 planes starting at element C * offset of the image
     arena (the mask arena and the table do not change): boxed as the union of the channels by msl_foreground_box_mc,
     every plane normalised on its own (one msl_normalize_nonzero call over the case's C planes), batches written as
-    (N, C) + target by msl_augment_fit_mc.  C = 1 calls the one-channel entry points."""
+    (N, C) + target by msl_augment_fit_mc.  C = 1 calls the one-channel entry points.
+
+    Patch mode (``dataset.patch_size`` set): the batch shape is the patch.  ``train_batches`` makes the host's draws for
+    every sample - the augmentation's, then ``datasets.patch_origin``'s eight from the same generator - and
+    msl_augment_window_mc cuts the window out of the augmented case in the launch that augments it; the batch carries
+    "patch_origin".  The lesion centres ``patch_origin`` aims at are taken once per training case at construction
+    (``centres``).  ``val_batches`` yields the tiles of ``datasets._LesionTiles`` (every validation case is cached on every
+    rank: the tile list, not the case list, is what the ranks share out), ``batch_size`` tiles at a time."""
 
     def __init__(self, dataset, device, max_objects_per_image=64):
         if dataset.train_dataset is None:
             raise ValueError("LesionCache needs a data module after setup()")
         self.dataset, self.device = dataset, torch.device(device)
-        self.batch_size, self.target = int(dataset.batch_size), tuple(dataset.spatial_size)
+        self.patch = getattr(dataset, "patch_size", None)
+        self.batch_size = int(dataset.batch_size)
+        self.target = tuple(dataset.spatial_size) if self.patch is None else tuple(self.patch)
         self.channels = C = len(dataset.input_images)
         self.augmentations = list(dataset.train_dataset.augmentations)
         names = [(t if isinstance(t, str) else t[0]) for t in self.augmentations]
@@ -610,7 +622,10 @@ class LesionCache:
         if dataset.segmentation_mode != "instances":
             raise NotImplementedError("LesionCache: the device pipeline labels instance masks ('labeled' segmentations)")
         tr, te = dataset.train_dataset, dataset.test_dataset
-        if dataset.world_size > 1:
+        if self.patch is not None:
+            te = te.cases  # datasets._LesionTiles: its tiles are dealt to the ranks below, once the crop shapes are known
+            val_idx = np.arange(len(te))
+        elif dataset.world_size > 1:
             val_idx = ShardSampler(len(te), dataset.rank, dataset.world_size, False, dataset.random_state).indices()
         else:
             val_idx = np.arange(len(te))
@@ -657,6 +672,30 @@ class LesionCache:
                                   dtype=torch.int64, device=dev).reshape(-1, 4)
         self.capacity = int(max_objects_per_image) * self.batch_size
         self._bufs = {}
+        if self.patch is not None:
+            self.centres = {k: self._case_centres(k) for k in sorted(set(self.train_slots))}
+            tiles = [(s, k, tuple(int(v) for v in row[:3])) for s, k in self.val_order
+                     for row in view_plan(self.shapes[k], self.patch, dataset.tile_margin)]
+            if dataset.world_size > 1:
+                own = ShardSampler(len(tiles), dataset.rank, dataset.world_size, False, dataset.random_state).indices()
+                tiles = [tiles[i] for i in own]
+            self.val_tiles = tiles  # (subject, slot, origin): this rank's share of dataset.test_dataset.tiles
+
+    def _case_centres(self, slot):
+        """``datasets.lesion_centres`` of a cached case -> f64 (K, 3): one msl_instance_boxes call on the cropped mask,
+        read back once.  The kernel writes f32(e / n) for an inclusive integer extent e on an axis of n voxels; the extent
+        is recovered as rint(f32(e / n) * n) in f64.  The division's relative error is at most 2^-24 and the f64 product
+        adds 2^-53, so the product is within e * 2^-23 of e: exact while e < 2^22, and the arena refuses axes of 2^20
+        voxels or more."""
+        shape = self.shapes[slot]
+        if not int(np.prod(shape)):
+            return np.zeros((0, 3), dtype=np.float64)
+        out = _InstBoxOut(1, shape, self.dataset.thresholds, INST_MAX_IDS, self.device)
+        out.launch(self.case(slot)[1], _stream(self.device))
+        n = out.obj_off.cpu().tolist()[1]  # (synchronises: the flag and the rows are there too)
+        out.raise_on_overflow(out.flag.item())
+        ext = np.rint(out.gb[:n].cpu().numpy().astype(np.float64) * np.asarray(shape * 2, dtype=np.float64))
+        return (ext[:, :3] + ext[:, 3:]) / 2
 
     def _check_memory(self, nbytes, what):
         free, _ = torch.cuda.mem_get_info(self.device)
@@ -680,7 +719,9 @@ class LesionCache:
 
     def footprint(self):
         lo, hi = np.min(self.shapes, 0).tolist(), np.max(self.shapes, 0).tolist()
-        return (f"LesionCache: {len(self.shapes)} cases of {tuple(lo)} .. {tuple(hi)} fitted to {self.target} on "
+        how = f"fitted to {self.target}" if self.patch is None else \
+            f"in patches of {self.target} ({len(self.val_tiles)} validation tiles)"
+        return (f"LesionCache: {len(self.shapes)} cases of {tuple(lo)} .. {tuple(hi)} {how} on "
                 f"{self.device}: {self.cache_bytes / 2**20:.1f} MiB cached, {self.nbytes() / 2**20:.1f} MiB with batch "
                 f"buffers")
 
@@ -694,9 +735,20 @@ class LesionCache:
                                  "box": _InstBoxOut(N, self.target, self.dataset.thresholds, self.capacity, dev)}
         return b
 
-    def _run(self, slots, per_sample, b):
+    def _run(self, slots, per_sample, b, windows=None):
         stream = _stream(self.device)
         rows = fit_rows(slots, per_sample)
+        if windows is not None:  # one upload: the f64 rows, then the (N, 3) int32 origins in the doubles behind them
+            N = len(slots)
+            packed = np.zeros(rows.size + (3 * N + 1) // 2, dtype=np.float64)
+            packed[:rows.size] = rows.reshape(-1)
+            packed[rows.size:].view(np.int32)[:3 * N] = np.asarray(windows, dtype=np.int32).reshape(-1)
+            pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
+            _lib.call("msl_augment_window_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels,
+                      ptr(self.table), len(self.shapes), ptr(pd), pd.data_ptr() + 8 * rows.size, N, *self.target,
+                      ptr(b["img"]), ptr(b["seg"]), stream)
+            b["box"].launch(b["seg"], stream)
+            return
         pd = torch.from_numpy(rows.reshape(-1)).pin_memory().to(self.device, non_blocking=True)
         if self.channels == 1:
             _lib.call("msl_augment_fit", ptr(self.img), ptr(self.seg), self.img.numel(), ptr(self.table), len(self.shapes),
@@ -710,19 +762,50 @@ class LesionCache:
         tr = self.dataset.train_dataset
         for idx in train_batch_order(self.dataset, epoch):
             per_sample = []
+            windows = None if self.patch is None else []
             for i in idx:
-                draws = draw_augmentations(self.augmentations, sample_rng(tr.seed, epoch, tr.subjects[i])) \
-                    if self.augmentations else []
-                per_sample.append(sample_params(draws, self.shapes[self.train_slots[i]], self.augmentations, ragged=True))
+                slot = self.train_slots[i]
+                rs = sample_rng(tr.seed, epoch, tr.subjects[i])
+                draws = draw_augmentations(self.augmentations, rs) if self.augmentations else []
+                per_sample.append(sample_params(draws, self.shapes[slot], self.augmentations, ragged=True))
+                if windows is not None:  # the host's eight draws, behind the augmentation's, in the augmented frame
+                    perm, stages = per_sample[-1]
+                    centres = centres_to_augmented(self.centres[slot], self.shapes[slot], perm, stages)
+                    windows.append(patch_origin(rs, tuple(self.shapes[slot][a] for a in perm[0]), self.patch, centres,
+                                                self.dataset.patch_foreground))
             b = self._buffers(len(idx))
-            self._run([self.train_slots[i] for i in idx], per_sample, b)
-            yield {"img": b["img"], "seg": b["seg"], "gb": b["box"].gb, "gl": b["box"].gl, "obj_off": b["box"].obj_off,
+            self._run([self.train_slots[i] for i in idx], per_sample, b, windows)
+            out = {"img": b["img"], "seg": b["seg"], "gb": b["box"].gb, "gl": b["box"].gl, "obj_off": b["box"].obj_off,
                    "capacity": self.capacity, "subject": [tr.subjects[i] for i in idx], "_box": b["box"]}
+            if windows is not None:
+                out["patch_origin"] = windows
+            yield out
 
     step = DeviceCache.step
 
+    def _val_tile_batches(self):
+        ident = (([0, 1, 2], [0, 0, 0]), [])
+        for i0 in range(0, len(self.val_tiles), self.batch_size):
+            chunk = self.val_tiles[i0:i0 + self.batch_size]
+            b = self._buffers(len(chunk))
+            self._run([slot for _, slot, _ in chunk], [ident] * len(chunk), b, [o for _, _, o in chunk])
+            box = b["box"]
+            off = box.obj_off.cpu().tolist()
+            box.raise_on_overflow(box.flag.item())
+            boxes = [box.gb[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
+            labels = [box.gl[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
+            yield {"img": b["img"].clone(), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
+                   "subject": [s for s, _, _ in chunk], "patch_origin": [o for _, _, o in chunk],
+                   "crop_origin": [self.origins[slot] for _, slot, _ in chunk],
+                   "crop_shape": [tuple(self.shapes[slot]) for _, slot, _ in chunk],
+                   "full_shape": [self.full_shapes[slot] for _, slot, _ in chunk]}
+
     def val_batches(self):
-        """``validation_step`` batches (device tensors, per-image box lists) of this rank's validation shard."""
+        """``validation_step`` batches (device tensors, per-image box lists) of this rank's validation shard; in patch
+        mode, of this rank's share of the validation tiles."""
+        if self.patch is not None:
+            yield from self._val_tile_batches()
+            return
         ident = (([0, 1, 2], [0, 0, 0]), [])
         for i0 in range(0, len(self.val_order), self.batch_size):
             chunk = self.val_order[i0:i0 + self.batch_size]

@@ -66,6 +66,12 @@ def build_parser():
     p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
     # the MR sequences of a clinical case, one input channel each (1 .. 4); the synthetic cases have one channel
     p.add_argument('-ii', '--input_images', type=str, nargs='+', default=["FLAIR"])
+    # patch training (-dm lesions only): one sampled window of this size per case and epoch
+    # instead of the fit to --spatial_size, validation on the tiles `predict --views tiles` shows the network
+    p.add_argument('--patch_size', type=int, nargs=3, default=None, metavar=('D', 'H', 'W'))
+    p.add_argument('--patch_foreground', type=float, default=0.67, metavar='P',
+                   help='probability that a training window is placed on a lesion (else uniformly)')
+    p.add_argument('--tile_margin', type=int, nargs=3, default=[8, 8, 8], metavar=('D', 'H', 'W'))
     return p
 
 
@@ -75,6 +81,18 @@ def input_images_of(args):
     if getattr(args, "data_module", "example") != "lesions" and len(names) > 1:
         raise ValueError(f"-dm example generates one-channel cases; {len(names)} input images were named: {' '.join(names)}")
     return names
+
+
+def patch_options_of(args):
+    """--patch_size / --patch_foreground / --tile_margin as LesionsDataModule keywords; {} without --patch_size.  Patch
+    training with the synthetic data module is an error (its cubes are the network's input already)."""
+    patch = getattr(args, "patch_size", None)
+    if patch is None:
+        return {}
+    if getattr(args, "data_module", "example") != "lesions":
+        raise ValueError("--patch_size samples windows of clinical cases: it needs -dm lesions")
+    return {"patch_size": tuple(patch), "patch_foreground": getattr(args, "patch_foreground", 0.67),
+            "tile_margin": tuple(getattr(args, "tile_margin", (8, 8, 8)))}
 
 
 def check_input_channels(model, input_images, checkpoint):
@@ -115,6 +133,7 @@ def example(args):
     from .ssd3d import LSSD3D
     from .trainer import FusedTrainer
     input_images = input_images_of(args)  # before the first GPU call: a refused command line touches no device
+    patch_options = patch_options_of(args)
     world, rank, local = _dist_env()
     dp = world > 1
     if dp:  # join the job BEFORE the first GPU call of this process (RCCL binds the communicator to the device)
@@ -137,7 +156,7 @@ def example(args):
                                     classes=("lesion",) if args.n_classes == 1 else ("lesion", "lesion_2"),
                                     percentage=args.percentage, num_workers=args.num_workers, batch_size=args.batch_size,
                                     augmentations=augmentations, random_state=970205,
-                                    spatial_size=tuple(args.spatial_size), rank=rank, world_size=world)
+                                    spatial_size=tuple(args.spatial_size), rank=rank, world_size=world, **patch_options)
     else:
         dataset = ExampleDataset(n_classes=args.n_classes, subject=args.subject, percentage=args.percentage,
                                  num_workers=args.num_workers, batch_size=args.batch_size, data_dir=args.dataset_path,

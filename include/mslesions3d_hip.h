@@ -425,6 +425,18 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
                             const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
                             size_t workspace_bytes, float* out, void* stream);
 
+/* ---- FROC from a completed msl_evaluate_detections call ("FROC"): eval_workspace is that call's workspace,
+ * sorted_scores the sorted-scores part of its result buffer, and D, N, G, n_iou its sizes, on the same stream.  The
+ * workspace keeps the rank order, the image of every detection, the TP flag per (IoU threshold, rank) and K.
+ * gt_count (N) i32: class-1 ground-truth boxes per image.  weights (R1, N) i32 >= 0: one multiplicity per image and row
+ * (row 0 all ones = the plain curve, further rows = bootstrap resamples).  rates (n_rates, 2) i64: numerator and
+ * denominator, 1 .. 2^20 each, n_rates <= 16 (more -> -2).  Per (row, IoU threshold, rate): k* = the largest admissible
+ * prefix length (0, K, or a cut between two different scores) with FPw(k) * den <= num * Nw, and TPw(k*).
+ * out (i64): (R1, n_iou, n_rates, 2) [k*, TPw(k*)] | (R1, 2) [Gw, Nw].  Integer arithmetic only. */
+int msl_evaluate_froc(const void* eval_workspace, size_t eval_workspace_bytes, const float* sorted_scores, int D, int N,
+                      int G, int n_iou, const int* gt_count, const int* weights, int R1, const long long* rates,
+                      int n_rates, long long* out, void* stream);
+
 /* ---- device-resident training data (csrc/datapipe.hip, devicedata.py): the host pipeline of datasets._Cases ----------
  * msl_normalize_nonzero: NormalizeIntensity(nonzero=True) in place on n_volumes contiguous f32 volumes of `voxels` each:
  * population mean / std of the non-zero voxels (f64, fixed order), std 0 -> 1, zeros stay zero, all-zero unchanged.

@@ -439,7 +439,193 @@ __global__ __launch_bounds__(EV_THREADS) void ev_sweep_kernel(
   out[7] = (float)tpc;
 }
 
+// ---- FROC: sensitivity at fixed numbers of false positives per image, for (R1 weight rows) x (IoU thresholds), from the
+// rank order and the TP flags msl_evaluate_detections left in its workspace ("FROC").  One workgroup per
+// (weights row, IoU threshold) walks the K ranked detections in tiles of EV_FROC_TILE: a thread takes EV_FROC_PER
+// consecutive ranks, gathers the weight of each detection's image (the row is a few hundred bytes and stays in cache; it is
+// read from global memory, so any N takes the same path), and a 64-bit workgroup scan of the (TP, FP) pair with running
+// carries gives TPw(k), FPw(k) at every prefix.  FPw(k) * den <= num * Nw is tested as FPw(k) <= floor(num * Nw / den),
+// computed once per rate without leaving 64 bits.  Everything is integer: the result does not depend on any order.
+constexpr int EV_FROC_PER = 4;
+constexpr int EV_FROC_TILE = EV_THREADS * EV_FROC_PER;  // utils.FROC_TILE
+constexpr int EV_FROC_MAX_RATES = 16;                   // utils.FROC_MAX_RATES
+constexpr long long EV_FROC_RATE_MAX = 1LL << 20;       // numerator and denominator of a rate
+constexpr long long I64_MAX = 0x7FFFFFFFFFFFFFFFLL;
+
+__device__ __forceinline__ long long shfl_up_i64(long long v, int o) {
+  const int lo = __shfl_up((int)(v & 0xFFFFFFFFLL), o, 64), hi = __shfl_up((int)(v >> 32), o, 64);
+  return ((long long)hi << 32) | (long long)(unsigned)lo;
+}
+
+__device__ __forceinline__ long long shfl_xor_i64(long long v, int o) {
+  const int lo = __shfl_xor((int)(v & 0xFFFFFFFFLL), o, 64), hi = __shfl_xor((int)(v >> 32), o, 64);
+  return ((long long)hi << 32) | (long long)(unsigned)lo;
+}
+
+// grid (R1, n_iou).  out: (R1, n_iou, n_rates, 2) [k*, TPw(k*)] | (R1, 2) [Gw, Nw]
+__global__ __launch_bounds__(EV_THREADS) void ev_froc_kernel(
+    const int* __restrict__ order, const int* __restrict__ img_of, const int* __restrict__ tpf,
+    const float* __restrict__ sorted_scores, const int* __restrict__ hdr, int D, int N, const int* __restrict__ gt_count,
+    const int* __restrict__ weights, const long long* __restrict__ rates, int n_rates, long long* __restrict__ out) {
+  __shared__ long long scan_a[EV_WAVES], scan_b[EV_WAVES];
+  __shared__ long long lim_s[EV_FROC_MAX_RATES];
+  __shared__ long long best_tp_s[EV_WAVES][EV_FROC_MAX_RATES];
+  __shared__ int best_k_s[EV_WAVES][EV_FROC_MAX_RATES];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int row = blockIdx.x, t = blockIdx.y, n_iou = gridDim.y, R1 = gridDim.x;
+  const int K = min(max(hdr[1], 0), D);
+  const int* __restrict__ w = weights + (size_t)row * N;
+  const int* __restrict__ tp = tpf + (size_t)t * D;
+
+  // Gw = sum w[n] * g[n], Nw = sum w[n]
+  long long gw = 0, nw = 0;
+  for (int n = tid; n < N; n += EV_THREADS) {
+    const long long wn = w[n];
+    nw += wn;
+    gw += wn * (long long)gt_count[n];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    gw += shfl_xor_i64(gw, o);
+    nw += shfl_xor_i64(nw, o);
+  }
+  if (lane == 0) {
+    scan_a[wv] = gw;
+    scan_b[wv] = nw;
+  }
+  __syncthreads();
+  gw = 0;
+  nw = 0;
+  for (int q = 0; q < EV_WAVES; ++q) {
+    gw += scan_a[q];
+    nw += scan_b[q];
+  }
+  if (tid < EV_FROC_MAX_RATES) {
+    // floor(num * Nw / den) = num * (Nw / den) + floor(num * (Nw % den) / den); the second term stays below 2^40
+    long long lim = 0;
+    if (tid < n_rates) {
+      const long long num = min(max(rates[2 * tid], 0LL), EV_FROC_RATE_MAX);
+      const long long den = min(max(rates[2 * tid + 1], 1LL), EV_FROC_RATE_MAX);
+      const long long nwp = max(nw, 0LL), qd = nwp / den, rd = nwp % den;
+      lim = (num > 0 && qd > (I64_MAX - EV_FROC_RATE_MAX * EV_FROC_RATE_MAX) / num) ? I64_MAX : num * qd + (num * rd) / den;
+    }
+    lim_s[tid] = lim;
+  }
+  __syncthreads();  // lim_s written; scan_a / scan_b free again
+  long long lim[EV_FROC_MAX_RATES], best_tp[EV_FROC_MAX_RATES];
+  int best_k[EV_FROC_MAX_RATES];
+#pragma unroll
+  for (int c = 0; c < EV_FROC_MAX_RATES; ++c) {
+    lim[c] = lim_s[c];
+    best_tp[c] = 0;  // k = 0 always qualifies
+    best_k[c] = 0;
+  }
+
+  long long carry_a = 0, carry_b = 0;
+  for (int base = 0; base < K; base += EV_FROC_TILE) {  // workgroup-uniform trip count
+    const int r0 = base + tid * EV_FROC_PER;
+    long long a[EV_FROC_PER], b[EV_FROC_PER];
+    float s[EV_FROC_PER + 1];
+    long long sa = 0, sb = 0;
+#pragma unroll
+    for (int q = 0; q < EV_FROC_PER; ++q) {
+      const int r = r0 + q;
+      a[q] = 0;
+      b[q] = 0;
+      s[q] = 0.f;
+      if (r < K) {
+        const long long wi = w[img_of[order[r]]];
+        if (tp[r] != 0) a[q] = wi;
+        else b[q] = wi;
+        s[q] = sorted_scores[r];
+      }
+      sa += a[q];
+      sb += b[q];
+    }
+    s[EV_FROC_PER] = r0 + EV_FROC_PER < K ? sorted_scores[r0 + EV_FROC_PER] : 0.f;
+    // exclusive workgroup scan of (sa, sb)
+    long long ia = sa, ib = sb;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long ua = shfl_up_i64(ia, o), ub = shfl_up_i64(ib, o);
+      if (lane >= o) {
+        ia += ua;
+        ib += ub;
+      }
+    }
+    __syncthreads();  // the previous tile's totals have been read
+    if (lane == 63) {
+      scan_a[wv] = ia;
+      scan_b[wv] = ib;
+    }
+    __syncthreads();
+    long long run_a = carry_a + ia - sa, run_b = carry_b + ib - sb;
+    for (int q = 0; q < EV_WAVES; ++q) {
+      const long long ta = scan_a[q], tb = scan_b[q];
+      if (q < wv) {
+        run_a += ta;
+        run_b += tb;
+      }
+      carry_a += ta;
+      carry_b += tb;
+    }
+#pragma unroll
+    for (int q = 0; q < EV_FROC_PER; ++q) {
+      const int k = r0 + q + 1;  // prefix length
+      if (k > K) break;
+      run_a += a[q];
+      run_b += b[q];
+      if (k == K || s[q] != s[q + 1]) {  // admissible: not inside a run of tied scores
+#pragma unroll
+        for (int c = 0; c < EV_FROC_MAX_RATES; ++c)
+          if (c < n_rates && run_b <= lim[c]) {
+            best_k[c] = k;  // ranks ascend within a thread and from tile to tile
+            best_tp[c] = run_a;
+          }
+      }
+    }
+  }
+
+  // TPw never decreases with k: TPw(k*) is the maximum over the qualifying admissible prefixes
+#pragma unroll
+  for (int c = 0; c < EV_FROC_MAX_RATES; ++c) {
+    int k = best_k[c];
+    long long v = best_tp[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      k = max(k, __shfl_xor(k, o, 64));
+      v = max(v, shfl_xor_i64(v, o));
+    }
+    if (lane == 0) {
+      best_k_s[wv][c] = k;
+      best_tp_s[wv][c] = v;
+    }
+  }
+  __syncthreads();
+  if (tid < n_rates) {
+    int k = 0;
+    long long v = 0;
+    for (int q = 0; q < EV_WAVES; ++q) {
+      k = max(k, best_k_s[q][tid]);
+      v = max(v, best_tp_s[q][tid]);
+    }
+    long long* o = out + (((size_t)row * n_iou + t) * n_rates + tid) * 2;
+    o[0] = k;
+    o[1] = v;
+  }
+  if (t == 0 && tid == 0) {
+    long long* o = out + (size_t)R1 * n_iou * n_rates * 2 + (size_t)row * 2;
+    o[0] = gw;
+    o[1] = nw;
+  }
+}
+
 // ---- host planning ------------------------------------------------------------------------------------------
+// Workspace hand-off (msl_evaluate_froc): after a completed msl_evaluate_detections call the workspace keeps, for the
+// same (D, N, G, n_iou), hdr[1] = K (class-1 detections), valA = the rank -> detection index order (the global sort ends
+// in (keyA, valA) after its four passes), img_of = image of every detection index, tpf = the TP flag per (IoU threshold,
+// rank).  The sorted scores live in the caller's result buffer, not here.  Nothing reads these after the sweep, so a
+// consumer on the same stream may; the layout below is part of that contract.
 struct EvPlan {
   int nblk, ntile, radix2_passes;
   size_t hdr, keyA, keyB, keyC, valA, valB, valC, img_of, hist, sums, tpf, cum, cprec, tile_max, total;
@@ -586,6 +772,23 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
   MSL_LAUNCH(ev_sweep_kernel, dim3(n_sc, n_iou), dim3(EV_THREADS), 0, st, (const float*)sorted_scores, (const int*)tpf,
              (const int*)cum, (const float*)cprec, (const float*)tile_max, p.ntile, D, (const int*)hdr, score_thr, n_sc,
              recall_thr, summary);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int msl_evaluate_froc(const void* eval_workspace, size_t eval_workspace_bytes, const float* sorted_scores, int D, int N,
+                      int G, int n_iou, const int* gt_count, const int* weights, int R1, const long long* rates,
+                      int n_rates, long long* out, void* stream) {
+  if (N <= 0 || D < 0 || G < 0 || n_iou <= 0 || R1 <= 0 || n_rates <= 0 || !eval_workspace || !gt_count || !weights ||
+      !rates || !out || (D > 0 && !sorted_scores))
+    return MSL_ERR_ARG;
+  if (n_rates > EV_FROC_MAX_RATES || !ev_supported(D, N, G, n_iou, 1)) return MSL_ERR_UNSUPPORTED;
+  const EvPlan p = ev_plan(D, N, G, n_iou);
+  if (eval_workspace_bytes < p.total) return MSL_ERR_ARG;
+  const char* ws = (const char*)eval_workspace;
+  MSL_LAUNCH(ev_froc_kernel, dim3(R1, n_iou), dim3(EV_THREADS), 0, (hipStream_t)stream, (const int*)(ws + p.valA),
+             (const int*)(ws + p.img_of), (const int*)(ws + p.tpf), sorted_scores, (const int*)(ws + p.hdr), D, N, gt_count,
+             weights, rates, n_rates, out);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

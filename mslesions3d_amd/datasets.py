@@ -904,6 +904,19 @@ class _LesionCases(Dataset):
             raise ValueError("case_sample: the case frame is defined for the un-augmented pipeline")
         return self._sample(i, False)
 
+    def case_boxes(self, i, fit=True):
+        """-> (boxes, labels) of the un-augmented case i: those of ``self[i]`` (``fit``) or of ``case_sample(i)``, from
+        the mask alone - loaded, regridded and cropped as the sample's is, without normalising the image."""
+        if self.augmentations or self.patch is not None:
+            raise ValueError("case_boxes: defined for the un-augmented, un-windowed pipeline")
+        m = self.module
+        img, seg, _ = self.load_regridded(i)
+        lo, hi = foreground_box(img, m.margin)
+        seg = seg[tuple(slice(a, b) for a, b in zip(lo, hi))][None]
+        if fit:
+            seg = resize_with_pad_or_crop(seg, m.spatial_size)
+        return boxes_from_instances(seg, m.thresholds, m.segmentation_mode)
+
     def cropped(self, i):
         """Steps 1-3 of case i -> (image (C,) + crop_shape f32 normalised, mask (1,) + crop_shape, plan or None, crop
         origin, crop_shape, full_shape)."""

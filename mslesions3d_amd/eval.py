@@ -7,6 +7,13 @@ One extension: ``-sc`` and ``-iou`` take comma-separated lists; the whole grid c
 (``utils.evaluate_detections``), every grid point bit-identical to the host ``calculate_mAP`` on the filtered detections.
 
     python -m mslesions3d_amd.eval -d DATA -dn NAME -pd PREDICTIONS -sc 0.1,0.5 -iou 0.1,0.5
+
+Not in the reference: ``--froc`` adds the FROC curve of ALL predictions in the files (sensitivity at ``--froc_rates`` false
+positives per case, their mean CPM, ``--bootstrap R`` resamples of the cases for a 95 % interval; DESIGN.md "FROC") as
+``froc_(min_IoU=<iou>).json`` per ``-iou``; ``-dm lesions`` scores the predictions of clinical cases
+(``datasets.LesionsDataModule``) in the frame ``predict`` wrote them in.
+
+    python -m mslesions3d_amd.eval -dm lesions -d RAW --centers C1 C2 --spatial_size 96 96 96 -pd PREDICTIONS --froc --bootstrap 1000
 """
 import argparse
 import json
@@ -41,7 +48,48 @@ def build_parser():
                    help="minimum overlap(s) between a candidate box and a ground-truth box; comma-separated list for a sweep")
     p.add_argument('-k', '--top_k', type=int, default=100)
     p.add_argument('-pd', '--prediction_dir', type=str, default=r"../data/predictions/")
+    # not in the reference.  A flag that is not given leaves NO attribute behind (SUPPRESS, as predict.view_options): the
+    # namespace of a command without them is the one it has always been; eval_options() fills in the defaults
+    S = argparse.SUPPRESS
+    p.add_argument('--froc', action="store_true", default=S,
+                   help="also write froc_(min_IoU=<iou>).json: sensitivity at fixed false positives per case, CPM")
+    p.add_argument('--froc_rates', type=rate_list, default=S,
+                   help="false positives per case of the FROC curve, comma-separated exact rationals (default: "
+                        "0.125,0.25,0.5,1,2,4,8)")
+    p.add_argument('--bootstrap', type=int, default=S, help="bootstrap resamples of the cases for the 95 %% interval (default: 0)")
+    p.add_argument('--bootstrap_seed', type=int, default=S, help="seed of the resampling (default: 0)")
+    p.add_argument('-dm', '--data_module', choices=["example", "lesions"], default=S,
+                   help="lesions: the clinical data module, -d is its data_dir (default: example)")
+    p.add_argument('--centers', type=str, nargs='+', default=S, help="as predict.py (default: CHUV_RIM_OK BASEL_INSIDER_OK)")
+    p.add_argument('--spatial_size', type=int, nargs=3, default=S, metavar=('D', 'H', 'W'),
+                   help="as predict.py (default: 250 300 300)")
+    p.add_argument('-ii', '--input_images', type=str, nargs='+', default=S, help="as predict.py (default: FLAIR)")
     return p
+
+
+def rate_list(text):
+    """``0.125,1/4,2`` -> [(1, 8), (1, 4), (2, 1)]: every entry parsed exactly by ``fractions.Fraction``."""
+    from fractions import Fraction
+    try:
+        vals = [Fraction(v.strip()) for v in str(text).split(",") if v.strip() != ""]
+    except (ValueError, ZeroDivisionError):
+        raise argparse.ArgumentTypeError(f"expected comma-separated rationals, got {text!r}")
+    if not vals or any(v <= 0 for v in vals):
+        raise argparse.ArgumentTypeError(f"expected one or more positive rates, got {text!r}")
+    return [(v.numerator, v.denominator) for v in vals]
+
+
+EVAL_DEFAULTS = {"froc": False, "froc_rates": None, "bootstrap": 0, "bootstrap_seed": 0, "data_module": "example",
+                 "centers": ('CHUV_RIM_OK', 'BASEL_INSIDER_OK'), "spatial_size": (250, 300, 300), "input_images": ("FLAIR",)}
+
+
+def eval_options(args):
+    """The flags the reference does not have, with their defaults filled in -> a namespace of exactly those."""
+    o = argparse.Namespace(**{k: (d if getattr(args, k, None) is None else getattr(args, k)) for k, d in EVAL_DEFAULTS.items()})
+    if o.froc_rates is None:
+        from .utils import DEFAULT_FP_RATES
+        o.froc_rates = list(DEFAULT_FP_RATES)
+    return o
 
 
 def as_list(v):
@@ -77,6 +125,10 @@ def resolve_prediction_dir(prediction_dir, dataset_name=None, model_name=None, p
 
 def metrics_file_name(min_iou, min_score):
     return f"metrics_(min_IoU={min_iou}_min_score={min_score}).json"
+
+
+def froc_file_name(min_iou):
+    return f"froc_(min_IoU={min_iou}).json"
 
 
 def convert_tensor(tensor):
@@ -119,24 +171,87 @@ def gather_batches(batches, prediction_dir, confidence_threshold, log=print):
     return det_b, det_l, det_s, gt_b, gt_l
 
 
+def gather_lesion_cases(cases, prediction_dir, confidence_threshold, log=print):
+    """``gather_batches`` for the predict data set of a ``LesionsDataModule`` (``cases``, un-augmented): the detections at
+    or above ``confidence_threshold`` of every case with a ``sub-<center>_<subject>_preds.json`` and its ground truth in
+    the frame ``predict`` wrote those detections in - the case frame (the foreground crop, not fitted: the boxes of
+    ``case_sample``) when a ``sub-*_preds_views.json`` lies beside the file (``predict --views`` / ``--flip_views``), else
+    the fitted sample's.  A case without a prediction file is skipped and reported through ``log``.  Host only: the
+    ground truth comes from ``cases.case_boxes``, which loads and crops the mask without preparing the image."""
+    det_b, det_l, det_s, gt_b, gt_l = [], [], [], [], []
+    for pos in range(len(cases)):
+        subj = cases.subjects[pos]
+        subj = subj if isinstance(subj, str) else "_".join(subj)
+        if not os.path.exists(pjoin(prediction_dir, f"sub-{subj}_preds.json")):
+            log(f"skipped subject {subj}: no prediction file")
+            continue
+        b, l, s = retrieve_boxes(prediction_dir, subj, confidence_threshold=confidence_threshold)
+        case_frame = os.path.exists(pjoin(prediction_dir, f"sub-{subj}_preds_views.json"))
+        boxes, labels = cases.case_boxes(pos, fit=not case_frame)
+        det_b.append(b), det_l.append(l), det_s.append(s), gt_b.append(boxes), gt_l.append(labels)
+    return det_b, det_l, det_s, gt_b, gt_l
+
+
+def froc_json(summary):
+    """The JSON form of one IoU threshold's ``utils.froc_summary`` dict: the same keys; an infinite score threshold (no
+    detection kept at that rate) and a NaN sensitivity (no ground truth at all) become null."""
+    import math
+
+    def conv(v):
+        if isinstance(v, (list, tuple)):
+            return [conv(x) for x in v]
+        return None if isinstance(v, float) and not math.isfinite(v) else v
+    return {k: conv(v) for k, v in summary.items()}
+
+
 def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_workers=8, predict_subset="train",
-             n_classes=1, percentage=1., confidence_threshold=0.5, min_iou=0.5):
+             n_classes=1, percentage=1., confidence_threshold=0.5, min_iou=0.5, options=None):
     """eval.py:61-151 for every (min_iou, confidence_threshold) pair of the given values (a number or a list each).
-    Returns ``{(iou, score): detail dict}``."""
+    Returns ``{(iou, score): detail dict}``.  ``options``: an ``eval_options`` namespace (FROC, clinical cases)."""
     from .datasets import ExampleDataset
     from .utils import evaluate_detections
     if not torch.cuda.is_available():
         raise RuntimeError("mslesions3d_amd.eval needs the HIP device (no host fallback)")
+    opt = eval_options(argparse.Namespace() if options is None else options)
     ious, scores = as_list(min_iou), as_list(confidence_threshold)
-    dataset = ExampleDataset(n_classes=n_classes, percentage=percentage, cache=False, num_workers=num_workers,
-                             objects="multiple", batch_size=1, data_dir=dataset_path, dataset_name=dataset_name)
+    lesions = opt.data_module == "lesions"
+    if lesions:
+        from .datasets import LesionsDataModule
+        dataset = LesionsDataModule(data_dir=dataset_path, centers=tuple(opt.centers), batch_size=1,
+                                    input_images=tuple(opt.input_images),
+                                    classes=("lesion",) if n_classes == 1 else ("lesion", "lesion_2"),
+                                    num_workers=num_workers, percentage=percentage, spatial_size=tuple(opt.spatial_size))
+    else:
+        dataset = ExampleDataset(n_classes=n_classes, percentage=percentage, cache=False, num_workers=num_workers,
+                                 objects="multiple", batch_size=1, data_dir=dataset_path, dataset_name=dataset_name)
     dataset.setup(stage="predict_train" if predict_subset == "train" else "predict")
-    loader = dataset._loader(dataset.predict_dataset, False, BATCH)
+    loader = None if lesions else dataset._loader(dataset.predict_dataset, False, BATCH)
     prediction_dir = resolve_prediction_dir(prediction_dir, dataset_name, model_name, predict_subset)
     print(f"Prediction directory: {prediction_dir}")
+    if opt.froc and not lesions:  # two passes over the prediction files, one over the volumes
+        loader = [{k: b[k] for k in ("subject", "boxes", "labels")} for b in loader]
+
+    def gather(threshold, log=print):
+        if lesions:
+            return gather_lesion_cases(dataset.predict_dataset, prediction_dir, threshold, log=log)
+        return gather_batches(loader, prediction_dir, threshold, log=log)
+
+    if opt.froc:
+        from .utils import evaluate_froc
+        # every prediction in the files counts (NaN scores fail the compare and stay out)
+        det_b, det_l, det_s, gt_b, gt_l = gather(float("-inf"), log=lambda *_: None)
+        if not gt_l:
+            raise RuntimeError("FROC: no case with a prediction file")
+        froc = evaluate_froc(det_b, det_l, det_s, gt_b, gt_l, min_overlaps=ious, fp_rates=opt.froc_rates,
+                             n_boot=opt.bootstrap, seed=opt.bootstrap_seed)
+        for iou in ious:
+            d = froc_json(froc[iou])
+            print(f"\nFROC for IoU = {iou}: CPM {d['cpm']}  sensitivity {d['sensitivity']} at {d['rates']} FP / case")
+            with open(pjoin(prediction_dir, froc_file_name(iou)), "w") as json_file:
+                json.dump(d, json_file, indent=4)
 
     with torch.no_grad():
-        det_b, det_l, det_s, gt_b, gt_l = gather_batches(loader, prediction_dir, min(scores))
+        det_b, det_l, det_s, gt_b, gt_l = gather(min(scores))
         dif = [torch.zeros(len(l), dtype=torch.bool) for l in gt_l]
         print("\n+-+-+- Computing metrics! +-+-+-+")
         grid = evaluate_detections(det_b, det_l, det_s, gt_b, gt_l, dif, min_overlaps=ious, min_scores=scores,
@@ -162,7 +277,8 @@ def main(argv=None):
     print(f"Confidence threshold set to {args.min_score}")
     return evaluate(args.prediction_dir, args.dataset_path, dataset_name=args.dataset_name, model_name=args.model_name,
                     num_workers=args.num_workers, predict_subset=args.predict_subset, n_classes=args.n_classes,
-                    percentage=args.percentage, confidence_threshold=args.min_score, min_iou=args.min_iou)
+                    percentage=args.percentage, confidence_threshold=args.min_score, min_iou=args.min_iou,
+                    options=eval_options(args))
 
 
 if __name__ == "__main__":

@@ -382,7 +382,9 @@ def prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_label
     def launch():
         _lib.call("msl_evaluate_detections", *args, _stream())
 
+    # "ws" / "ws_bytes" / "sorted_scores": what msl_evaluate_froc consumes after launch() on the same stream
     return {"launch": launch, "out": out, "D": D, "N": N, "G": G, "ious": ious, "scores": scs,
+            "ws": ws, "ws_bytes": ws_bytes, "sorted_scores": out[n_iou * n_sc * METRIC_SUMMARY:n_iou * n_sc * METRIC_SUMMARY + D],
             "keep": (packed, ws, gb, gl, goff, recall)}
 
 
@@ -421,6 +423,194 @@ def evaluate_detections(det_boxes, det_labels, det_scores, true_boxes, true_labe
             status = np.where(claim[t] < 0, 2, np.where(claim[t] < K, 1, 0))
             res[(ious[t], scs[c])] = _detail_dict(summary[t, c], sorted_scores, tp[t], fp, vol, status)
     return res
+
+
+# ----------------------------------------------------------------------------------------------------------
+# FROC ("FROC"): sensitivity at fixed numbers of false positives per image, CPM, bootstrap intervals over
+# cases.  Not in the reference; the matching rule is calculate_mAP's (rank order and TP flags of the existing pipeline).
+
+FROC_TILE = 1024      # EV_FROC_TILE of csrc/evaluate.hip: ranks one workgroup of ev_froc_kernel takes per step
+FROC_MAX_RATES = 16   # EV_FROC_MAX_RATES
+FROC_RATE_MAX = 1 << 20
+DEFAULT_FP_RATES = ((1, 8), (1, 4), (1, 2), (1, 1), (2, 1), (4, 1), (8, 1))  # false positives per image, as num / den
+
+
+def froc_rates(fp_rates):
+    """-> [(num, den)] of exact positive rationals, each part <= 2^20, at most 16.  An entry is a (num, den) pair or
+    anything ``fractions.Fraction`` takes (a float stands for its exact binary value)."""
+    from fractions import Fraction
+    out = []
+    for r in fp_rates:
+        f = Fraction(int(r[0]), int(r[1])) if isinstance(r, (tuple, list)) else Fraction(r)
+        if not (0 < f.numerator <= FROC_RATE_MAX and 0 < f.denominator <= FROC_RATE_MAX):
+            raise ValueError(f"FROC rate {r!r}: a positive rational with numerator and denominator up to 2^20")
+        out.append((f.numerator, f.denominator))
+    if not 1 <= len(out) <= FROC_MAX_RATES:
+        raise ValueError(f"1 .. {FROC_MAX_RATES} FROC rates, got {len(out)}")
+    return out
+
+
+def bootstrap_weights(n_images, n_boot, seed=0):
+    """(n_boot + 1, N) int32: row 0 all ones (the plain curve), row r > 0 the multiplicities of the r-th resample of
+    ``np.random.default_rng(seed).integers(0, N, size=(n_boot, N))``."""
+    N, R = int(n_images), int(n_boot)
+    if N <= 0 or R < 0:
+        raise ValueError(f"bootstrap_weights: {N} images, {R} resamples")
+    w = np.ones((R + 1, N), dtype=np.int32)
+    if R:
+        draws = np.random.default_rng(seed).integers(0, N, size=(R, N))
+        w[1:] = np.stack([np.bincount(d, minlength=N) for d in draws]).astype(np.int32)
+    return w
+
+
+def _froc_weights(weights, N, n_boot, seed):
+    if weights is None:
+        return bootstrap_weights(N, n_boot, seed)
+    w = np.asarray(weights)
+    if w.ndim != 2 or w.shape[1] != N or w.shape[0] < 1 or not np.issubdtype(w.dtype, np.integer) or (w < 0).any() \
+            or (w > 0x7FFFFFFF).any():
+        raise ValueError(f"FROC weights: an integer array (rows, {N}) of values >= 0")
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels):
+    """The class-1 detections and ground truth as calculate_mAP concatenates them, the per-image ground-truth counts and
+    the scores in rank order (compute_metrics_per_class's lexsort).  NaN scores: ValueError."""
+    n_img = len(true_labels)
+    assert len(det_boxes) == len(det_labels) == len(det_scores) == len(true_boxes) == n_img > 0
+    t_lab = [_np(l, np.int64).reshape(-1) for l in true_labels]
+    d_lab = [_np(l, np.int64).reshape(-1) for l in det_labels]
+    t_img = np.concatenate([np.full(len(l), i, dtype=np.int64) for i, l in enumerate(t_lab)])
+    d_img = np.concatenate([np.full(len(l), i, dtype=np.int64) for i, l in enumerate(d_lab)])
+    t_box = np.concatenate([_np(b, np.float32).reshape(-1, 6) for b in true_boxes])
+    d_box = np.concatenate([_np(b, np.float32).reshape(-1, 6) for b in det_boxes])
+    d_sco = np.concatenate([_np(s, np.float32).reshape(-1) for s in det_scores])
+    ts, ds = np.concatenate(t_lab) == 1, np.concatenate(d_lab) == 1
+    d_img, d_box, d_sco = d_img[ds], d_box[ds], d_sco[ds]
+    if np.isnan(d_sco).any():
+        raise ValueError("FROC: NaN detection scores")
+    order = np.lexsort((np.arange(d_sco.shape[0]), -d_sco.astype(np.float64)))
+    return {"d_img": d_img, "d_box": d_box, "d_sco": d_sco, "t_img": t_img[ts], "t_box": t_box[ts], "order": order,
+            "g": np.bincount(t_img[ts], minlength=n_img).astype(np.int64), "N": n_img}
+
+
+def froc_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, fp_rates, weights):
+    """The numpy twin of ``msl_evaluate_froc``: rank order and TP flags from ``compute_metrics_per_class``, then the
+    definitions of DESIGN.md "FROC" as written.  -> ``{"k", "tp": (rows, n_iou, n_rates) int64, "gw", "nw": (rows,)
+    int64, "scores": the class-1 scores in rank order (K,) f32}``: the integers the kernel writes."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)
+    ious, rates, N = list(min_overlaps), froc_rates(fp_rates), c["N"]
+    w = _froc_weights(weights, N, 0, 0).astype(np.int64)
+    R1, K = w.shape[0], c["d_sco"].shape[0]
+    gw, nw = (w * c["g"][None, :]).sum(1), w.sum(1)
+    scores = c["d_sco"][c["order"]]
+    img = c["d_img"][c["order"]]
+    adm = np.ones(K + 1, dtype=bool)  # prefix lengths a score threshold can realise
+    adm[1:K] = scores[:-1] != scores[1:]
+    k_out = np.zeros((R1, len(ious), len(rates)), dtype=np.int64)
+    tp_out = np.zeros_like(k_out)
+    # int64 holds every product while these stay below 2^63; Python integers otherwise
+    big = int(w.max(initial=0)) * K * max(d for _, d in rates) >= 2 ** 63 or \
+        int(nw.max(initial=0)) * max(n for n, _ in rates) >= 2 ** 63
+    dt = object if big else np.int64
+    for t, ov in enumerate(ious):
+        tp = np.zeros(K, dtype=np.int64)
+        if K:
+            tp = compute_metrics_per_class(c["d_img"], c["d_box"], c["d_sco"], c["t_img"], c["t_box"],
+                                           np.zeros(c["t_box"].shape[0], dtype=bool), ov)[0].astype(np.int64)
+        for r0 in range(0, R1, 128):
+            wj = w[r0:r0 + 128][:, img].astype(dt)  # (rows, K): the weight of every ranked detection's image
+            TP = np.zeros((wj.shape[0], K + 1), dtype=dt)
+            FP = np.zeros((wj.shape[0], K + 1), dtype=dt)
+            TP[:, 1:] = np.cumsum(wj * tp[None, :], axis=1)
+            FP[:, 1:] = np.cumsum(wj * (1 - tp)[None, :], axis=1)
+            for ci, (num, den) in enumerate(rates):
+                ok = adm[None, :] & (FP * den <= (nw[r0:r0 + 128].astype(dt) * num)[:, None])
+                ks = K - np.argmax(ok[:, ::-1], axis=1)  # the largest qualifying admissible k (k = 0 always qualifies)
+                k_out[r0:r0 + 128, t, ci] = ks
+                tp_out[r0:r0 + 128, t, ci] = TP[np.arange(wj.shape[0]), ks].astype(np.int64)
+    return {"k": k_out, "tp": tp_out, "gw": gw, "nw": nw, "scores": scores}
+
+
+def froc_summary(ints, min_overlaps, fp_rates):
+    """``{min_overlap: {"rates", "sensitivity", "score_threshold", "cpm", "ci_low", "ci_high", "cpm_ci", "n_cases",
+    "n_lesions", "n_boot", "dropped"}}`` from the integers of ``froc_host`` / ``msl_evaluate_froc``.  Row 0 is the plain
+    curve (sensitivity NaN without any ground truth); rows 1.. are bootstrap resamples: the interval is
+    ``np.percentile(sens[1:], [2.5, 97.5])`` over the rows with Gw > 0, ``dropped`` counts the others; without resamples
+    (or with every one dropped) the interval entries are None."""
+    rates = froc_rates(fp_rates)
+    k, tp, gw, nw, scores = ints["k"], ints["tp"], ints["gw"], ints["nw"], ints["scores"]
+    n_boot = int(k.shape[0]) - 1
+    keep = np.nonzero(gw[1:] > 0)[0] + 1
+    out = {}
+    for t, ov in enumerate(min_overlaps):
+        sens = [int(tp[0, t, c]) / int(gw[0]) if gw[0] > 0 else float("nan") for c in range(len(rates))]
+        thr = [float(scores[int(k[0, t, c]) - 1]) if k[0, t, c] > 0 else float("inf") for c in range(len(rates))]
+        d = {"rates": [n / m for n, m in rates], "sensitivity": sens, "score_threshold": thr,
+             "cpm": sum(sens) / len(sens), "ci_low": None, "ci_high": None, "cpm_ci": None, "n_cases": int(nw[0]),
+             "n_lesions": int(gw[0]), "n_boot": n_boot, "dropped": n_boot - int(keep.size)}
+        if keep.size:
+            boot = np.array([[int(tp[r, t, c]) / int(gw[r]) for c in range(len(rates))] for r in keep], dtype=np.float64)
+            lo, hi = np.percentile(boot, [2.5, 97.5], axis=0)
+            d["ci_low"], d["ci_high"] = [float(v) for v in lo], [float(v) for v in hi]
+            d["cpm_ci"] = [float(v) for v in np.percentile(boot.mean(axis=1), [2.5, 97.5])]
+        out[ov] = d
+    return out
+
+
+def prepare_froc(plan, gt_count, weights, rates):
+    """Pack one ``msl_evaluate_froc`` call behind ``plan`` (``prepare_evaluation``): rates, weights and ground-truth counts
+    in one host buffer with one host-to-device copy, the result buffer allocated.  Returns ``launch()`` (enqueue on the
+    current stream after ``plan["launch"]()``, no synchronisation), ``out`` (device, int64) and the sizes."""
+    dev = plan["out"].device
+    w = np.ascontiguousarray(weights, dtype=np.int32)
+    R1, N, n_iou, n_rates = w.shape[0], plan["N"], len(plan["ious"]), len(rates)
+    assert w.shape == (R1, N) and len(gt_count) == N and 1 <= n_rates <= FROC_MAX_RATES
+    host = np.concatenate([np.asarray(rates, dtype=np.int64).reshape(-1).view(np.int32), w.reshape(-1),
+                           np.asarray(gt_count, dtype=np.int32)])
+    packed = torch.from_numpy(host).to(dev)
+    base = packed.data_ptr()
+    o_w = 4 * n_rates
+    out = torch.empty(R1 * n_iou * n_rates * 2 + R1 * 2, dtype=torch.int64, device=dev)
+    args = (ptr(plan["ws"]), plan["ws_bytes"], ptr(plan["sorted_scores"]) if plan["D"] else None, plan["D"], N, plan["G"],
+            n_iou, base + 4 * (o_w + R1 * N), base + 4 * o_w, R1, base, n_rates, ptr(out))
+
+    def launch():
+        _lib.call("msl_evaluate_froc", *args, _stream())
+
+    return {"launch": launch, "out": out, "R1": R1, "n_iou": n_iou, "n_rates": n_rates, "keep": (packed, plan)}
+
+
+def froc_ints(host_out, R1, n_iou, n_rates, scores):
+    """The result buffer of ``msl_evaluate_froc`` (host copy) as the dict ``froc_host`` returns."""
+    a = np.asarray(host_out, dtype=np.int64)
+    n = R1 * n_iou * n_rates * 2
+    kt, gn = a[:n].reshape(R1, n_iou, n_rates, 2), a[n:n + 2 * R1].reshape(R1, 2)
+    return {"k": kt[..., 0].copy(), "tp": kt[..., 1].copy(), "gw": gn[:, 0].copy(), "nw": gn[:, 1].copy(), "scores": scores}
+
+
+def evaluate_froc_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, fp_rates, weights):
+    """``froc_host`` on the HIP device: the sweep of ``prepare_evaluation``, one upload of weights, rates and ground-truth
+    counts, ``msl_evaluate_froc`` on the workspace the sweep left, one device-to-host copy."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)  # rejects NaN scores; rank-ordered scores
+    rates = froc_rates(fp_rates)
+    w = _froc_weights(weights, c["N"], 0, 0)
+    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, [0.0])
+    f = prepare_froc(plan, c["g"], w, rates)
+    plan["launch"]()
+    f["launch"]()
+    host = f["out"].cpu().numpy()  # the one device-to-host copy
+    return froc_ints(host, f["R1"], f["n_iou"], f["n_rates"], c["d_sco"][c["order"]])
+
+
+def evaluate_froc(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps=(0.5,),
+                  fp_rates=DEFAULT_FP_RATES, n_boot=0, seed=0, weights=None):
+    """FROC of a detection set on the HIP device -> ``froc_summary``'s dict per IoU threshold.  ``weights`` (rows, N)
+    replaces the bootstrap matrix ``bootstrap_weights(N, n_boot, seed)``; its row 0 is reported as the plain curve."""
+    ious = list(min_overlaps)
+    w = _froc_weights(weights, len(true_labels), n_boot, seed)
+    ints = evaluate_froc_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, ious, fp_rates, w)
+    return froc_summary(ints, ious, fp_rates)
 
 
 # ---- box overlays (utils.py:516-617, predict.py:186-220) ----------------------------------------------------------------

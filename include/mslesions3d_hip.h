@@ -103,7 +103,9 @@ int msl_pwconv_bwd_fused(const float* g_y, const float* y, const float* bn_y_vec
                          const float* bn_z_vec, float* g_z, double* z_partials, float* dw_slabs, int N, int Cin, int Cout, int S,
                          void* stream);
 
-/* ---- stem: Conv3d(Cin->32,k3,stride (sd,sh,sw),p1,no bias) : mobilenet.py:26-31 via ssd3d.py:60-61 ------- */
+/* ---- stem: Conv3d(Cin->32,k3,stride (sd,sh,sw),p1,no bias) : mobilenet.py:26-31 via ssd3d.py:60-61 -------
+ * Every stem entry point takes Cin 1..4 and strides 1..2 and refuses before any launch: Cin < 1, a stride outside 1..2 or
+ * N, D, H, W <= 0 with MSL_ERR_ARG, Cin > 4 with MSL_ERR_UNSUPPORTED. */
 int msl_stem_conv_fwd_num_partials(int N, int OD, int OH, int OW);
 int msl_stem_conv_fwd(const float* x, const float* w, float* y, double* partials, int N, int Cin, int D, int H,
                       int W, int sd, int sh, int sw, void* stream);

@@ -1167,6 +1167,9 @@ int msl_stem_conv_fwd_num_partials(int N, int OD, int OH, int OW) { return N * s
 // x (N,Cin,D,H,W) -> y (N,32,OD,OH,OW) raw conv output (fp32, or bf16 when `bf16_out`) + fp64 stat partials [2][32][NP].
 static int stem_fwd_impl(const float* x, const float* w, void* y, double* partials, int N, int Cin, int D, int H, int W,
                          int sd, int sh, int sw, bool bf16_out, void* stream) {
+  // ahead of everything: the row-staged branch below takes every Cin <= 2 as stem_fwd_rows_kernel<2> (Cin > 4 is refused
+  // by the switch of the general path, the only one it can reach)
+  if (Cin < 1) return MSL_ERR_ARG;
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || sd < 1 || sd > 2 || sh < 1 || sh > 2 || sw < 1 || sw > 2)
     return MSL_ERR_ARG;
   if ((long long)Cin * D * H * W >= (1ll << 30)) return MSL_ERR_UNSUPPORTED;  // in-image byte offsets are 32-bit
@@ -1259,6 +1262,7 @@ int msl_stem_conv_bwd_weight_fused(const float* dz, const float* w1_t, const flo
                                    const float* x, float* dw, float* workspace, int N, int Cin, int D, int H, int W,
                                    int sd, int sh, int sw, void* stream) {
   if (!dz || !w1_t || !yraw || !bn_vec) return MSL_ERR_ARG;
+  if (sd < 1 || sh < 1 || sw < 1) return MSL_ERR_ARG;  // divided by below
   {  // the kernel addresses y and dz with 32-bit byte offsets
     const long long OD = (D - 1) / sd + 1, OH = (H - 1) / sh + 1, OW = (W - 1) / sw + 1;
     if ((long long)N * 32 * OD * OH * OW * 4 >= (1ll << 32)) return MSL_ERR_UNSUPPORTED;
@@ -1280,6 +1284,7 @@ int msl_stem_conv_bwd_weight_fused_bf16(const void* dz, const float* w1_t, const
                                         float* dw, float* workspace, int N, int Cin, int D, int H, int W, int sd, int sh, int sw,
                                         void* stream) {
   if (!dz || !w1_t || !yraw || !bn_vec) return MSL_ERR_ARG;
+  if (sd < 1 || sh < 1 || sw < 1) return MSL_ERR_ARG;  // divided by below
   {
     const long long OD = (D - 1) / sd + 1, OH = (H - 1) / sh + 1, OW = (W - 1) / sw + 1;
     if ((long long)N * 32 * OD * OH * OW * 2 >= (1ll << 32)) return MSL_ERR_UNSUPPORTED;
@@ -1300,6 +1305,9 @@ int msl_stem_conv_bwd_weight_bnapply_bf16(const void* g, const void* yraw, const
 static int stem_bww_impl(const float* dy, const float* x, float* dw, float* workspace, int N, int Cin, int D, int H, int W,
                          int sd, int sh, int sw, const float* yraw, const float* bnv, const float* w1, void* stream,
                          bool bf16act) {
+  // ahead of everything: the tile-staged branch below takes every Cin <= 2 as stem_bww_tile_kernel<2> (Cin > 4 is refused
+  // by the switch of the wave-private path, the only one it can reach)
+  if (Cin < 1) return MSL_ERR_ARG;
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || sd < 1 || sd > 2 || sh < 1 || sh > 2 || sw < 1 || sw > 2)
     return MSL_ERR_ARG;
   const int OD = (D - 1) / sd + 1, OH = (H - 1) / sh + 1, OW = (W - 1) / sw + 1;

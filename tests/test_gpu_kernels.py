@@ -3,7 +3,9 @@
 The BatchNorm family (msl_bn_*) has one smoke-level test here; tests/test_gpu_bn.py walks every code path of those kernels
 against a float64 reference with derived bounds.  Likewise the fp32 pointwise convolution (msl_pwconv_*): test_pw_fwd_bwd and
 test_pw_random_shapes here compare with torch fp32 under stated tolerances; tests/test_gpu_pw.py walks every dispatch branch and
-template instantiation of csrc/pwconv.hip / csrc/pwfused.hip against the float64 reference of tests/pw_ref.py."""
+template instantiation of csrc/pwconv.hip / csrc/pwfused.hip against the float64 reference of tests/pw_ref.py.  And the stem
+(msl_stem_conv_*): the stem tests here compare with torch fp32 at a few shapes; tests/test_gpu_stem.py walks every dispatch
+branch and template instantiation of csrc/stem.hip against the float64 reference of tests/stem_ref.py."""
 import numpy as np
 import pytest
 import torch

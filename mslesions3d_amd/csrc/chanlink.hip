@@ -54,10 +54,54 @@ __device__ __forceinline__ void chan_sum2(double& a, double& b, double* scratch)
   }
 }
 
+constexpr int ilog2c(int v) { return v <= 1 ? 0 : 1 + ilog2c(v >> 1); }
+
+// STRIDE == 2: which taps an input quad needs depends on the parities of its plane id and its row ih (an even index meets
+// tap 1 only, an odd one taps 0 and 2), so the input quads are dealt to the threads sorted by parity.  Slot p = q * NT + tid
+// of the QI * NT slots: its top two bits are the parity class (id & 1 = bit 1, ih & 1 = bit 1 ^ bit 0), the rest counts the
+// quads of one class in the natural order (n, id >> 1, ih >> 1, iw / 4).  The top two bits are q itself (QI == 4), q and the
+// upper half of the waves (QI == 2: a thread takes classes ee + oo = 5 tap rows or eo + oe = 4) or the wave's quarter of the
+// workgroup (QI == 1): never the lane, so every (q, wave) runs the straight-line tap rows of ONE class.
+template <int NW, int QI>
+__device__ __forceinline__ int link_parity_class(int q, int tid) {
+  constexpr int LNT = ilog2c(NW * 64);
+  static_assert(QI == 4 || (QI == 2 && NW >= 2) || (QI == 1 && NW >= 4), "the class bits must lie above the lane bits");
+  if (QI == 4) return q;
+  if (QI == 2) return 2 * q + __builtin_amdgcn_readfirstlane(tid >> (LNT - 1));
+  return __builtin_amdgcn_readfirstlane(tid >> (LNT - 2));
+}
+
+// one tap row (KD, KH) of the stride-2 gather for an input quad at columns iw .. iw+3; row = the LDS row at output column
+// iw / 2.  Input column w: even -> tap 1 of output w/2; odd -> tap 0 of output (w+1)/2 and tap 2 of output (w-1)/2: an
+// 8-byte aligned pair + one more column.
+template <bool BWW, int KD, int KH>
+__device__ __forceinline__ f32x4v link_row_s2(const float* row, const float* wt, f32x4v av, f32x4v acc, float* dwa) {
+  constexpr int K = KD * 9 + KH * 3;
+  const float w0 = wt[K], w1 = wt[K + 1], w2 = wt[K + 2];
+  const float2 r01 = *reinterpret_cast<const float2*>(row);
+  const float r2 = row[2];
+  acc[0] = fmaf(w1, r01.x, acc[0]);
+  acc[1] = fmaf(w0, r01.y, fmaf(w2, r01.x, acc[1]));
+  acc[2] = fmaf(w1, r01.y, acc[2]);
+  acc[3] = fmaf(w0, r2, fmaf(w2, r01.y, acc[3]));
+  if (BWW) {
+    dwa[K] = fmaf(av[1], r01.y, fmaf(av[3], r2, dwa[K]));
+    dwa[K + 1] = fmaf(av[0], r01.x, fmaf(av[2], r01.y, dwa[K + 1]));
+    dwa[K + 2] = fmaf(av[1], r01.x, fmaf(av[3], r01.y, dwa[K + 2]));
+  }
+  return acc;
+}
+
 // NW waves = one channel; QO / QI: float4 quads of z (output side of the depthwise layer) / y (input side) per thread.
 // Extents are powers of two (lD, lH, lW = log2 of the INPUT extents): every index split is a shift or a mask - with one to
 // four waves per SIMD these kernels are bound by the number of instructions a wave issues, not by memory.
 // LDS image of dL/dz: [N][OD+2][OH+2][OW+8] floats, a row's data at columns 4 .. OW+3 (16-byte aligned), zero elsewhere.
+// STRIDE == 2 reads it with one ds_read_b64 + one ds_read_b32 per tap row; the parity-sorted lanes of a 32-lane half walk
+// W/4 quads of a row (8 bytes apart), then every row, then every plane of the class.  ds_read_b64 (banks mod 64): a row's
+// lanes cover OW of the OW+8 dwords of the pitch, so at OW = 8 (pitch 16, block 4) rows 4 apart share banks, 2-way; at
+// OW = 4 (pitch 12, plane pitch 72, block 6) 8 of the 64 dwords collide, 2-way.  ds_read_b32 (banks mod 32): 4-way at
+// OW = 8 (every second row aliases, 4 of 16 dwords used), 2-way at OW = 4.  The masked form it replaces had the same conflict
+// degree per ACTIVE lane with half the lanes idle; 9 rows x 12 LDS cycles per wave stay far below the instructions issued.
 // BWW: the link also produces the depthwise WEIGHT gradient dW[c][k] = sum_i relu(bn2(y))[i] * dL/dz[(i + 1 - k) / s] (the very
 // operand pairs of the transposed convolution: one more FMA per pair) - the weight-gradient launch of the block disappears.
 template <typename T, int NW, int QO, int QI, int STRIDE, bool BWW>
@@ -77,6 +121,25 @@ __global__ __launch_bounds__(NW * 64) void block_bwd_channel_link_kernel(
   // (BWW: the image region is reused for the 27 x NT tap-gradient exchange once the gather is done)
   double* scratch = reinterpret_cast<double*>(lds + (BWW ? max(ptot, 27 * NT + 27 * 4) : ptot));
 
+  // input quad of slot (q, tid): image n, quad r of the image (clamped to a valid one); false: the slot is masked
+  auto in_quad = [&](int q, int& n, int& r) -> bool {
+    if constexpr (STRIDE == 1) {
+      const int qi = tid + q * NT, qc = min(qi, tot_qi - 1);
+      n = qc >> (lSi - 2);
+      r = qc & ((1 << (lSi - 2)) - 1);
+      return qi < tot_qi;
+    } else {
+      const int cls = link_parity_class<NW, QI>(q, tid), pa = cls >> 1, pb = (cls ^ pa) & 1;  // parity of id, of ih
+      const int rest = tid & ((NT * QI >> 2) - 1);
+      const int x = rest & ((1 << (lSi - 4)) - 1), nn = rest >> (lSi - 4);
+      const int iwq = x & ((1 << (lW - 2)) - 1), ih = ((x >> (lW - 2)) & ((1 << (lH - 1)) - 1)) * 2 + pb;
+      const int id = (x >> (lW + lH - 3)) * 2 + pa;
+      n = min(nn, N - 1);
+      r = (((id << lH) + ih) << (lW - 2)) + iwq;
+      return nn < N;
+    }
+  };
+
   // ---- every global load of the link, back to back (clamped addresses, masked later) -------------------------------
   f32x4v gq[QO], zq[QO], yq[QI], aq[QI];
 #pragma unroll
@@ -88,13 +151,15 @@ __global__ __launch_bounds__(NW * 64) void block_bwd_channel_link_kernel(
   }
 #pragma unroll
   for (int q = 0; q < QI; ++q) {
-    const int qi = min(tid + q * NT, tot_qi - 1), n = qi >> (lSi - 2), r = qi & ((1 << (lSi - 2)) - 1);
+    int n, r;
+    in_quad(q, n, r);
     yq[q] = ldq(y_prev + (((size_t)n * C + c) << lSi) + 4 * r);
   }
   if (accumulate) {  // (uniform branch around the whole group: the loads still leave back to back)
 #pragma unroll
     for (int q = 0; q < QI; ++q) {
-      const int qi = min(tid + q * NT, tot_qi - 1), n = qi >> (lSi - 2), r = qi & ((1 << (lSi - 2)) - 1);
+      int n, r;
+      in_quad(q, n, r);
       aq[q] = ldq(g_y + (((size_t)n * C + c) << lSi) + 4 * r);
     }
   } else {
@@ -154,34 +219,29 @@ __global__ __launch_bounds__(NW * 64) void block_bwd_channel_link_kernel(
   // ---- depthwise bwd-data (transposed 3x3x3, padding 1) + head share, then BatchNorm2 + ReLU backward of y_{i-1} ----------
   s1 = 0.f;
   s2 = 0.f;
-  const int W = 1 << lW, H = 1 << lH;
   float dwa[BWW ? 27 : 1];
 #pragma unroll
   for (int k = 0; k < (BWW ? 27 : 1); ++k) dwa[k] = 0.f;
 #pragma unroll
   for (int q = 0; q < QI; ++q) {
-    const int qi = tid + q * NT;
-    const bool in = qi < tot_qi;
-    const int qc = in ? qi : 0, n = qc >> (lSi - 2), r = qc & ((1 << (lSi - 2)) - 1);
-    const int s = 4 * r, iw = s & (W - 1), ih = (s >> lW) & (H - 1), id = s >> (lW + lH);
+    int n, r;
+    const bool in = in_quad(q, n, r);
+    const int iwq = r & ((1 << (lW - 2)) - 1), ih = (r >> (lW - 2)) & ((1 << lH) - 1), id = r >> (lW + lH - 2);
     f32x4v acc = aq[q];
     f32x4v av;  // the block's input activation relu(bn2(y_{i-1})) at the quad (zero for a masked quad)
 #pragma unroll
     for (int e = 0; e < 4; ++e) av[e] = (BWW && in) ? msl::act(yq[q][e], sc2, sh2) : 0.f;
     const float* img = lds + n * pimg + 4;  // (+4: the data columns of a row)
+    if constexpr (STRIDE == 1) {
+      const int iw = 4 * iwq;
 #pragma unroll
-    for (int kd = 0; kd < 3; ++kd) {
-      const int td = id + 1 - kd;
-      if (STRIDE == 2 && (td & 1)) continue;
-      const int pd = (STRIDE == 2 ? (td >> 1) : td) + 1;  // padded plane index, 0 .. OD+1
+      for (int kd = 0; kd < 3; ++kd) {
+        const int pd = id + 2 - kd;  // padded plane index, 0 .. OD+1
 #pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        const int th = ih + 1 - kh;
-        if (STRIDE == 2 && (th & 1)) continue;
-        const int ph = (STRIDE == 2 ? (th >> 1) : th) + 1;
-        const float* row = img + pd * PP + ph * PW;
-        const float w0 = wt[kd * 9 + kh * 3], w1 = wt[kd * 9 + kh * 3 + 1], w2 = wt[kd * 9 + kh * 3 + 2];
-        if (STRIDE == 1) {
+        for (int kh = 0; kh < 3; ++kh) {
+          const int ph = ih + 2 - kh;
+          const float* row = img + pd * PP + ph * PW;
+          const float w0 = wt[kd * 9 + kh * 3], w1 = wt[kd * 9 + kh * 3 + 1], w2 = wt[kd * 9 + kh * 3 + 2];
           // g[w] += sum_kw w[kw] * dz[w + 1 - kw]: columns iw-1 .. iw+4 of the row = one 4-byte, one 16-byte, one 4-byte read
           const float lft = row[iw - 1], rgt = row[iw + 4];
           const f32x4v m = *reinterpret_cast<const f32x4v*>(row + iw);
@@ -197,24 +257,27 @@ __global__ __launch_bounds__(NW * 64) void block_bwd_channel_link_kernel(
             d1 = fmaf(av[0], m[0], fmaf(av[1], m[1], fmaf(av[2], m[2], fmaf(av[3], m[3], d1))));
             d2 = fmaf(av[0], lft, fmaf(av[1], m[0], fmaf(av[2], m[1], fmaf(av[3], m[2], d2))));
           }
-        } else {
-          // input column w = iw + j: even -> tap 1 of output w/2; odd -> tap 0 of output (w+1)/2 and tap 2 of output (w-1)/2
-          const int o = iw >> 1;  // even: an 8-byte aligned pair + one more column
-          const float2 r01 = *reinterpret_cast<const float2*>(row + o);
-          const float r2 = row[o + 2];
-          acc[0] = fmaf(w1, r01.x, acc[0]);
-          acc[1] = fmaf(w0, r01.y, fmaf(w2, r01.x, acc[1]));
-          acc[2] = fmaf(w1, r01.y, acc[2]);
-          acc[3] = fmaf(w0, r2, fmaf(w2, r01.y, acc[3]));
-          if (BWW) {
-            float& d0 = dwa[kd * 9 + kh * 3];
-            float& d1 = dwa[kd * 9 + kh * 3 + 1];
-            float& d2 = dwa[kd * 9 + kh * 3 + 2];
-            d0 = fmaf(av[1], r01.y, fmaf(av[3], r2, d0));
-            d1 = fmaf(av[0], r01.x, fmaf(av[2], r01.y, d1));
-            d2 = fmaf(av[1], r01.x, fmaf(av[3], r01.y, d2));
-          }
         }
+      }
+    } else {
+      // tap kd meets plane id + 1 - kd where that is even: kd = 1 for an even id (padded plane id/2 + 1), kd = 0 and 2 for an
+      // odd one (padded planes id/2 + 2 and id/2 + 1); rows alike.  The class is the same for every lane of the wave (a
+      // constant where QI == 4): four straight-line cases of 1 / 2 / 2 / 4 tap rows, taken in the order of (kd, kh).
+      const int cls = link_parity_class<NW, QI>(q, tid), pa = cls >> 1, pb = (cls ^ pa) & 1;
+      const float* row = img + ((id >> 1) + 1) * PP + ((ih >> 1) + 1) * PW + 2 * iwq;
+      if (pa == 0 && pb == 0) {
+        acc = link_row_s2<BWW, 1, 1>(row, wt, av, acc, dwa);
+      } else if (pa == 0) {
+        acc = link_row_s2<BWW, 1, 0>(row + PW, wt, av, acc, dwa);
+        acc = link_row_s2<BWW, 1, 2>(row, wt, av, acc, dwa);
+      } else if (pb == 0) {
+        acc = link_row_s2<BWW, 0, 1>(row + PP, wt, av, acc, dwa);
+        acc = link_row_s2<BWW, 2, 1>(row, wt, av, acc, dwa);
+      } else {
+        acc = link_row_s2<BWW, 0, 0>(row + PP + PW, wt, av, acc, dwa);
+        acc = link_row_s2<BWW, 0, 2>(row + PP, wt, av, acc, dwa);
+        acc = link_row_s2<BWW, 2, 0>(row + PW, wt, av, acc, dwa);
+        acc = link_row_s2<BWW, 2, 2>(row, wt, av, acc, dwa);
       }
     }
     acc = rounded(g_y, acc);  // (bf16 storage: dL/d relu(bn2(y)) as the separate depthwise launch stores it)
@@ -265,9 +328,8 @@ __global__ __launch_bounds__(NW * 64) void block_bwd_channel_link_kernel(
   }
 #pragma unroll
   for (int q = 0; q < QI; ++q) {
-    const int qi = tid + q * NT;
-    if (qi < tot_qi) {
-      const int n = qi >> (lSi - 2), r = qi & ((1 << (lSi - 2)) - 1);
+    int n, r;
+    if (in_quad(q, n, r)) {
       f32x4v dy;
 #pragma unroll
       for (int e = 0; e < 4; ++e) dy[e] = sc2 * (aq[q][e] - k1 - yq[q][e] * k2);
@@ -307,7 +369,9 @@ bool link_plan(int N, int D, int H, int W, int stride, LinkPlan& p) {
   auto up = [](long long v) { return v <= 1 ? 1 : v <= 2 ? 2 : 4; };
   p.qi = up((tqi + nt - 1) / nt);
   p.qo = up((tqo + nt - 1) / nt);
-  if (p.qo > 1) p.qo = p.qi;  // instantiated: QO == 1 or QO == QI
+  if (p.qo > 1) p.qo = p.qi;  // instantiated: QO == QI (stride 1) or QO == 1 (stride 2: an eighth of the input quads)
+  // stride 2, one wave: the parity class of a quad (link_parity_class) cannot come from the wave index, so it comes from q
+  if (stride == 2 && p.nw == 1) p.qi = 4;
   const size_t ptot = (size_t)N * (OD + 2) * (OH + 2) * (OW + 8);
   p.smem = std::max(ptot, (size_t)27 * nt + 27 * 4) * 4 + 2 * p.nw * sizeof(double);
   return p.smem <= 156 * 1024;
@@ -340,25 +404,24 @@ static int link_launch(T* g_z, const T* z, const float* vec_z, const float* w_dw
     if (dw_dw) MSL_LINK_B(NW_, QO_, QI_, S_, true);    \
     else MSL_LINK_B(NW_, QO_, QI_, S_, false);         \
   } while (0)
-#define MSL_LINK_Q(NW_, S_)                                            \
-  do {                                                                 \
-    if (p.qi == 1) MSL_LINK_S(NW_, 1, 1, S_);                          \
-    else if (p.qi == 2 && p.qo == 1) MSL_LINK_S(NW_, 1, 2, S_);        \
-    else if (p.qi == 2) MSL_LINK_S(NW_, 2, 2, S_);                     \
-    else if (p.qo == 1) MSL_LINK_S(NW_, 1, 4, S_);                     \
-    else MSL_LINK_S(NW_, 4, 4, S_);                                    \
+  // what link_plan can give: stride 1 -> QO == QI, stride 2 -> QO == 1; one wave: QI <= 2 (stride 1) or QI == 4 (stride 2),
+  // four waves: QI = 1 / 2 / 4, eight and sixteen waves: QI == 4
+  if (p.qo != (stride == 1 ? p.qi : 1)) return MSL_ERR_UNSUPPORTED;
+#define MSL_LINK(NW_, QI_)                              \
+  do {                                                  \
+    if (stride == 1) MSL_LINK_S(NW_, QI_, QI_, 1);      \
+    else MSL_LINK_S(NW_, 1, QI_, 2);                    \
   } while (0)
-#define MSL_LINK(NW_)                       \
-  do {                                      \
-    if (stride == 1) MSL_LINK_Q(NW_, 1);    \
-    else MSL_LINK_Q(NW_, 2);                \
-  } while (0)
-  if (p.nw == 1) MSL_LINK(1);
-  else if (p.nw == 4) MSL_LINK(4);
-  else if (p.nw == 8) MSL_LINK(8);
-  else MSL_LINK(16);
+  if (p.nw == 1 && stride == 2 && p.qi == 4) MSL_LINK_S(1, 1, 4, 2);
+  else if (p.nw == 1 && stride == 1 && p.qi == 1) MSL_LINK_S(1, 1, 1, 1);
+  else if (p.nw == 1 && stride == 1 && p.qi == 2) MSL_LINK_S(1, 2, 2, 1);
+  else if (p.nw == 4 && p.qi == 1) MSL_LINK(4, 1);
+  else if (p.nw == 4 && p.qi == 2) MSL_LINK(4, 2);
+  else if (p.nw == 4 && p.qi == 4) MSL_LINK(4, 4);
+  else if (p.nw == 8 && p.qi == 4) MSL_LINK(8, 4);
+  else if (p.nw == 16 && p.qi == 4) MSL_LINK(16, 4);
+  else return MSL_ERR_UNSUPPORTED;
 #undef MSL_LINK
-#undef MSL_LINK_Q
 #undef MSL_LINK_S
 #undef MSL_LINK_B
   MSL_LAUNCH_CHECK();

@@ -13,6 +13,7 @@ feature maps the heads read are materialised (in a zero-haloed layout).
 """
 import ctypes
 import os
+import typing
 
 import torch
 
@@ -30,6 +31,81 @@ LINK_BWW_MAX_WAVES = 4
 
 def conv_out(d, s):
     return (d - 1) // s + 1
+
+
+def bn_bwd_one_launch(bf16, N, S):
+    """Is the BatchNorm backward of N x S values per channel one launch (reduce + finalize + apply; bf16: the channel's data
+    held in registers)?  If not, a stride-2 depthwise backward emits the reduce sums of such a producer along the way."""
+    return ((N * S <= 32768 and S % 8 == 0) or N * S <= 4096) if bf16 else N * S <= 65536
+
+
+class Route(typing.NamedTuple):
+    """How the backward pass runs block i >= 1: ``Plan.routes[i]``, chosen by ``plan_routes``."""
+    bn2: str         # who turns g_y[i] into dL/dy_i: "link" (block i+1's channel link), "pw_fused" (msl_pwconv_bwd_fused) or "bn"
+    y_np: object     # "pw_fused" / "bn" (_bn_bwd): reduce sums per channel that block i+1's depthwise form left in pl.partials
+    dw: str          # depthwise backward: "link" | "link_bww" (writes dW too) | "fused_stem" | "s2_bww" | "bnreduce" | "s2_patch" | "plain"
+    pw_part: object  # (slabs, count) Engine._grad_reduce folds into the pointwise dW; None: the kernel wrote the arena itself
+    dw_part: object  # (fp64 partials, count) it folds into the depthwise dW; None: the channel link wrote the arena
+
+
+class StemRoute(typing.NamedTuple):
+    """The same for the stem: ``Plan.routes[0]``."""
+    bn: str       # "link": block 1's channel link left dL/dy_0 (tiny inputs); "bn": the stem does its own BatchNorm backward
+    y_np: object  # "bn": reduce sums per channel that block 1's depthwise form left in pl.partials (None: none)
+    wgrad: str    # weight gradient from dL/dy_0 ("plain"), with the BatchNorm backward applied on load ("bnapply"), or rebuilt
+    #               from dL/dz_1 ("fused": after the fused stem pass, on the coefficients of msl_bn_bwd_finalize_coef)
+
+
+DW_BWW = ("link", "bnreduce", "s2_patch", "plain")  # Route.dw forms that leave the depthwise weight gradient to its own launch
+
+
+def plan_routes(pl, engine):
+    """-> ``Plan.routes`` of a training plan: which kernel form carries each piece of the backward pass, from the tail (a
+    block's depthwise form decides what is left to do for its producer).  All of it follows from the plan's shapes, its
+    scratch size and ``Engine.fuse_stem``; both backward passes and ``Engine._grad_reduce`` read the result, so they cannot
+    disagree about where a gradient was summed."""
+    L = _lib.load()
+    specs, N, bf16 = engine.layer_specs, pl.N, pl.bf16
+    fuse_stem = engine.fuse_stem and pl.fused_stem_np > 0
+    routes = [None] * len(specs)
+    y_np, linked = None, False  # what the depthwise form of block i+1 did for y_i
+    for i in range(len(specs) - 1, 0, -1):
+        cin, cout, s = specs[i]["cin"], specs[i]["cout"], specs[i]["stride"][0]
+        pd, ph, pw = pl.dims[i - 1]
+        # big early block whose producer left the BatchNorm2-backward sums: one pass (csrc/pwfused.hip; fp32 plans only)
+        pw_fused = not linked and y_np is not None and i in pl.pw_fused and 2 * cout * y_np <= pl.partials.numel()
+        # big stride-2 producer layer: emit the BatchNorm-backward sums of y_{i-1} while its gradient is in registers
+        big = s == 2 and not bn_bwd_one_launch(bf16, N, pd * ph * pw) and (not bf16 or pw % 4 == 0)
+        np_red = L.msl_dwconv_bwd_data_bnreduce_num_partials(N, cin, pd, ph, pw) if big else -1
+        fused_stem = i == 1 and fuse_stem
+        # tail of the network: BatchNorm1 backward of z_i, depthwise bwd-data (+ the heads' share) and BatchNorm2 backward of
+        # y_{i-1} are all per channel and a channel's population fits one workgroup: ONE launch (csrc/chanlink.hip)
+        link_nw = L.msl_block_bwd_channel_link_supported(N, pd, ph, pw, s)
+        link = link_nw > 0 and not fused_stem and not pw_fused and (i >= 2 and not big if bf16 else np_red <= 0)
+        left, dw_part = None, (pl.dw_part[i], pl.dw_np[i])
+        if link and link_nw <= LINK_BWW_MAX_WAVES:  # (with few waves per channel the link takes the weight gradient along)
+            dw, dw_part = "link_bww", None
+        elif link:
+            dw = "link"
+        elif fused_stem:
+            dw, left, dw_part = "fused_stem", pl.fused_stem_np, (pl.partials_wf, pl.fused_stem_np)
+        elif bf16 and big:
+            dw, left = "s2_patch", np_red
+        elif np_red > 0 and i in pl.dw_fused_part:
+            dw, left, dw_part = "s2_bww", pl.dw_fused_part[i][1], pl.dw_fused_part[i]
+        elif np_red > 0 and 2 * cin * np_red <= pl.partials.numel():
+            dw, left = "bnreduce", np_red
+        else:
+            dw = "plain"
+        pw_part = (pl.pw_slabs[i], pl.pw_nslabs[i]) if pl.pw_nslabs[i] > 1 else None
+        if pw_fused:
+            pw_part = (pl.pw_fused[i][0], pl.pw_fused[i][2])
+        routes[i] = Route("link" if linked else "pw_fused" if pw_fused else "bn", y_np, dw, pw_part, dw_part)
+        y_np, linked = left, link
+    # (fp32: the apply-on-load kernel is built for the 32-channel stem and needs the sums of block 1's depthwise form)
+    bnapply = bf16 or (y_np is not None and specs[0]["cout"] == 32)
+    routes[0] = StemRoute("link" if linked else "bn", y_np, "fused" if fuse_stem else "bnapply" if bnapply else "plain")
+    return routes
 
 
 class ParamArena:
@@ -125,7 +201,8 @@ class Plan:
     """Buffers + static shape data for one (batch, input size, mode, storage type).  ``dtype`` ("f32" / "bf16",
     ``LSSD3D.compute_dtype``) is how raw convolution outputs and activation gradients are stored in HBM; weights, BatchNorm
     vectors / statistics, head inputs and outputs and weight-gradient sums are fp32 / fp64 either way.  What the bf16 step
-    lays out differently is in the branches on ``bf16`` below; every other line serves both."""
+    lays out differently is in the branches on ``bf16`` below; every other line serves both.  A training plan also holds the
+    kernel routes of its backward pass (``routes``: see ``plan_routes``), fixed like its buffers when it is built."""
 
     def __init__(self, engine, N, in_dims, device, need_grad, dtype="f32"):
         L = _lib.load()
@@ -257,8 +334,8 @@ class Plan:
             self.head_nslabs = {f: L.msl_head_conv_bwd_weight_nslabs(N, specs[f]["cout"], *self.dims[f], ncls) for f in self.feat_ids}
             self.stem_nslabs = L.msl_stem_conv_bwd_weight_nslabs(N, *self.in_dims, *specs[0]["stride"])
             # fused stem backward (block 1 is a stride-2 depthwise layer fed by a 32-channel stem that is not a head
-            # feature): its dL/d(stem activation) is never materialised (Engine.backward / _backward_bf16).  fp32: where the
-            # sums fit the scratch, and Engine.backward still asks Engine.fuse_stem; bf16: decided here, the scratch grows
+            # feature): its dL/d(stem activation) is never materialised (plan_routes: "fused_stem").  fp32: where the sums
+            # fit the scratch, laid out whatever Engine.fuse_stem says; bf16: only with Engine.fuse_stem, the scratch grows
             self.fused_stem_np = -1
             fusable = (len(specs) > 1 and specs[0]["cout"] == 32 and specs[1]["cin"] == 32
                        and tuple(specs[1]["stride"]) == (2, 2, 2) and 0 not in self.feat_ids)
@@ -287,9 +364,8 @@ class Plan:
         self.pack_key = self.pack_args = None    # Engine._pack_head_weights
         self.gpack_key = self.gpack_args = None  # Engine._head_gpack_batch
         self.grad_tables = {}       # Engine._grad_reduce
-        self.dw_in_link = set()     # Engine.backward / _backward_bf16: blocks whose depthwise weight gradient a channel link writes
-        self.pw_fused_used = set()  # Engine.backward: blocks whose pointwise weight-gradient slabs came with pw_fused
-        self.dw_fused_used = set()  # Engine.backward: blocks whose depthwise weight-gradient partials came with dw_fused_part
+        # the backward pass, decided once: what Engine.backward / _backward_bf16 launch and Engine._grad_reduce folds
+        self.routes = plan_routes(self, engine) if need_grad else None  # [StemRoute, Route of block 1, ...]
 
 
 class Engine:
@@ -298,7 +374,9 @@ class Engine:
     * ``heads``  — forward: the head convolutions of scales 3 and 5 run beside backbone blocks 4-7; backward: their
       weight / data gradients run beside the backward of blocks 7..4;
     * ``wgrad``  — every pointwise / depthwise weight gradient runs beside the next layer's data-gradient chain.
-    Forks and joins are hipEvents recorded through the C ABI, so the schedule survives launch-program replay."""
+    Forks and joins are hipEvents recorded through the C ABI, so the schedule survives launch-program replay.
+    Which kernel form carries each piece of the backward pass is fixed per plan (``Plan.routes``); ``backward`` and
+    ``_backward_bf16`` only decide per call what the caller can change between calls (streams, reducer stages, batching)."""
 
     def __init__(self, model):
         self.model = model
@@ -351,7 +429,7 @@ class Engine:
         dtype = getattr(self.model, "compute_dtype", "f32")
         bf16 = dtype == "bf16"
         key = (dtype, x.shape[0], tuple(x.shape[2:]), x.device, need_grad, self.bf16_heads if bf16 else None,
-               self.fuse_stem if bf16 and need_grad else None)
+               self.fuse_stem if need_grad else None)
         p = self.plans.get(key)
         if p is None:
             p = self.plans[key] = Plan(self, x.shape[0], x.shape[2:], x.device, need_grad, dtype)
@@ -762,25 +840,19 @@ class Engine:
             return pl.locs, pl.scores, out_feats
         return pl.locs, pl.scores
 
-    @staticmethod
-    def _bn_bwd_bf16_fused(N, S):
-        """One launch (the channel's data held in registers) instead of reduce + finalize + apply?"""
-        return (N * S <= 32768 and S % 8 == 0) or N * S <= 4096
-
     def _bn_bwd_bf16(self, g, y, vec, bn_name, N, C, S, pl, st, pre_np=None):
         """In place: g (bf16, = dL/d relu(bn(y))) becomes dL/dy; dgamma / dbeta into the gradient arena.
         ``pre_np``: the producer of g already left that many reduce partials per channel in pl.partials."""
-        L = _lib.load()
         gv = self.arena.grad_views
-        if pre_np is None and self._bn_bwd_bf16_fused(N, S):
-            self._k("bn_bwd_fused:" + bn_name, "msl_bn_relu_bwd_fused_bf16", ptr(g), ptr(y), ptr(vec), ptr(gv[bn_name + ".weight"]),
-                    ptr(gv[bn_name + ".bias"]), ptr(g), N, C, S, st)
-            return
-        NP = pre_np if pre_np is not None else L.msl_bn_relu_bwd_bf16_num_partials(N, S)
         if pre_np is None:
+            if bn_bwd_one_launch(True, N, S):
+                self._k("bn_bwd_fused:" + bn_name, "msl_bn_relu_bwd_fused_bf16", ptr(g), ptr(y), ptr(vec), ptr(gv[bn_name + ".weight"]),
+                        ptr(gv[bn_name + ".bias"]), ptr(g), N, C, S, st)
+                return
+            pre_np = _lib.load().msl_bn_relu_bwd_bf16_num_partials(N, S)
             self._k("bn_bwd_reduce:" + bn_name, "msl_bn_relu_bwd_reduce_bf16", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
                     ptr(vec[3]), ptr(pl.partials), N, C, S, st)
-        _lib.call("msl_bn_bwd_finalize", ptr(pl.partials), NP, float(N * S), ptr(gv[bn_name + ".weight"]),
+        _lib.call("msl_bn_bwd_finalize", ptr(pl.partials), pre_np, float(N * S), ptr(gv[bn_name + ".weight"]),
                   ptr(gv[bn_name + ".bias"]), ptr(vec[4]), ptr(vec[5]), C, st)
         self._k("bn_bwd_apply:" + bn_name, "msl_bn_relu_bwd_apply_bf16", ptr(g), ptr(y), ptr(vec), ptr(g), N, C, S, st)
 
@@ -803,8 +875,6 @@ class Engine:
         if not prepacked:
             dlocs, dscores = dlocs.contiguous(), dscores.contiguous()
         last = len(specs) - 1
-        L = _lib.load()
-        pre_np, linked = None, False
         if last not in pl.feat_ids:
             raise RuntimeError("the last backbone feature must feed a head")
         wanted = getattr(on_bucket_ready, "stages", None)
@@ -843,19 +913,13 @@ class Engine:
             pd, ph, pw = pl.dims[i - 1]
             s = sp["stride"][0]
             name = f"base.features.{i}"
-            if not linked:  # (a channel link of block i+1 has already turned g_y[i] into dL/dy_i)
-                self._bn_bwd_bf16(pl.g_y[i], pl.y[i], pl.bn_y[i], name + ".bn2", N, sp["cout"], S, pl, st, pre_np=pre_np)
-            pre_np, linked = None, False
+            r = pl.routes[i]
+            link = r.dw in ("link", "link_bww")  # the per-channel link of the tail blocks, as in the fp32 step
+            if r.bn2 == "bn":  # ("link": the channel link of block i+1 has already turned g_y[i] into dL/dy_i)
+                self._bn_bwd_bf16(pl.g_y[i], pl.y[i], pl.bn_y[i], name + ".bn2", N, sp["cout"], S, pl, st, pre_np=r.y_np)
             self._k(f"pw_bwd{i}", "msl_pwconv_bwd_data_bf16", ptr(pl.g_y[i]), ptr(feats[i].conv2.weight), ptr(pl.g_z[i]), N,
                     sp["cin"], sp["cout"], S, st)
             accumulate = 1 if (i - 1) in pl.feat_ids else 0  # the heads already wrote their share
-            Sp = pd * ph * pw
-            fused_stem = i == 1 and pl.fused_stem_np > 0
-            big_producer = s == 2 and pw % 4 == 0 and not self._bn_bwd_bf16_fused(N, Sp)
-            # the per-channel link of the tail blocks in one launch, as in the fp32 step (csrc/chanlink.hip on bf16 storage)
-            link_nw = L.msl_block_bwd_channel_link_supported(N, pd, ph, pw, s)
-            link = link_nw > 0 and not fused_stem and not big_producer and i >= 2
-            link_bww = link and link_nw <= LINK_BWW_MAX_WAVES
             if not link:
                 self._bn_bwd_bf16(pl.g_z[i], pl.z[i], pl.bn_z[i], name + ".bn1", N, sp["cin"], S, pl, st)
             if accumulate and (i - 1) in side_feats:
@@ -865,36 +929,29 @@ class Engine:
                 self._k(f"link{i}", "msl_block_bwd_channel_link_bf16", ptr(pl.g_z[i]), ptr(pl.z[i]), ptr(pl.bn_z[i]),
                         ptr(feats[i].conv1.weight), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1]), ptr(pl.g_y[i - 1]),
                         ptr(gv[name + ".bn1.weight"]), ptr(gv[name + ".bn1.bias"]), ptr(gv[prev + ".weight"]),
-                        ptr(gv[prev + ".bias"]), ptr(gv[name + ".conv1.weight"]) if link_bww else None, N, sp["cin"], pd, ph,
-                        pw, s, accumulate, st)
-                linked = True
-                if link_bww:
-                    pl.dw_in_link.add(i)
+                        ptr(gv[prev + ".bias"]), ptr(gv[name + ".conv1.weight"]) if r.dw == "link_bww" else None, N, sp["cin"],
+                        pd, ph, pw, s, accumulate, st)
             sX = st
             if ms:  # both weight gradients of the block on a side stream, once dL/dy_i and dL/dz_i are final
                 sX = stW if i % 2 else stH
                 self._wait(sX, self._record(pl, f"dz{i}", st))
-            if link:
-                pass
-            elif fused_stem:
+            if r.dw == "fused_stem":
                 # one pass over (dL/dz_1, y_0): the stem's BatchNorm-backward sums + this block's depthwise weight gradient;
                 # the stem weight gradient below rebuilds dL/d(stem activation) from dL/dz_1 on the fly
                 self._k("dw_bwd1", "msl_dwconv_s2_bwd_bnreduce_bww_bf16", ptr(pl.g_z[1]), ptr(feats[1].conv1.weight), ptr(pl.y[0]),
                         ptr(pl.bn_y[0]), ptr(pl.partials), ptr(pl.partials_wf), ptr(pl.w1_taps_t), N, 32, pd, ph, pw, st)
-                pre_np = pl.fused_stem_np
-            elif s == 2 and pw % 4 == 0 and not self._bn_bwd_bf16_fused(N, Sp):
+            elif r.dw == "s2_patch":
                 # big producer layer: emit the BatchNorm-backward partials of y_{i-1} while its gradient is in registers
-                pre_np = L.msl_dwconv_bwd_data_bnreduce_num_partials(N, sp["cin"], pd, ph, pw)
                 self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data_s2_patch_bf16", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight),
                         ptr(pl.g_y[i - 1]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1]), ptr(pl.partials), N, sp["cin"], pd, ph, pw,
                         accumulate, st)
-            else:
+            elif not link:
                 self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data_bf16", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight), ptr(pl.g_y[i - 1]),
                         N, sp["cin"], pd, ph, pw, s, accumulate, st)
-            out = pl.pw_slabs[i] if pl.pw_nslabs[i] > 1 else gv[name + ".conv2.weight"]
+            out = r.pw_part[0] if r.pw_part is not None else gv[name + ".conv2.weight"]
             self._k(f"pw_bww{i}", "msl_pwconv_bwd_weight_slabs_bf16", ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]),
                     ptr(pl.bn_z[i][1]), ptr(out), N, sp["cin"], sp["cout"], S, sX)
-            if not fused_stem and not link_bww:  # (its partials came with the fused pass: pl.partials_wf / the link wrote dW)
+            if r.dw in DW_BWW:  # (else its partials came with the fused pass: pl.partials_wf / the link wrote dW)
                 self._k(f"dw_bww{i}", "msl_dwconv_bwd_weight_bf16", ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]),
                         ptr(pl.bn_y[i - 1][1]), ptr(pl.dw_part[i]), N, sp["cin"], pd, ph, pw, s, sX)
             report(i)
@@ -903,11 +960,13 @@ class Engine:
         S0 = od * oh * ow
         D, H, W = pl.in_dims
         vec = pl.bn_y[0]
-        NP = pre_np if pre_np is not None else L.msl_bn_relu_bwd_bf16_num_partials(N, S0)
-        if pre_np is None:
+        r = pl.routes[0]
+        NP = r.y_np
+        if NP is None:
+            NP = _lib.load().msl_bn_relu_bwd_bf16_num_partials(N, S0)
             self._k("bn_bwd_reduce:stem", "msl_bn_relu_bwd_reduce_bf16", ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(vec[0]), ptr(vec[1]),
                     ptr(vec[2]), ptr(vec[3]), ptr(pl.partials), N, specs[0]["cout"], S0, st)
-        if pl.fused_stem_np > 0:
+        if r.wgrad == "fused":
             _lib.call("msl_bn_bwd_finalize_coef", ptr(pl.partials), NP, float(N * S0), ptr(gv["base.features.0.1.weight"]),
                       ptr(gv["base.features.0.1.bias"]), ptr(vec), specs[0]["cout"], st)
             self._k("stem_bww", "msl_stem_conv_bwd_weight_fused_bf16", ptr(pl.g_z[1]), ptr(pl.w1_taps_t), ptr(pl.y[0]), ptr(vec),
@@ -1016,39 +1075,29 @@ class Engine:
         """In place: g (= dL/d relu(bn(y))) becomes dL/dy; writes dgamma/dbeta into the gradient arena.
         ``pre_np``: the producer of g already emitted the reduce partials (pl.partials, that many per channel);
         ``apply=False``: the consumer applies the BatchNorm backward itself while loading (only c1/c2 are produced)."""
-        L = _lib.load()
         gv = self.arena.grad_views
         part = pl.partials if partials is None else partials  # (``partials``: where the producer left its pre_np sums)
         if pre_np is not None and coef:
             _lib.call("msl_bn_bwd_finalize_coef", ptr(part), pre_np, float(count), ptr(gv[bn_name + ".weight"]),
                       ptr(gv[bn_name + ".bias"]), ptr(vec), C, st)
             return
-        if pre_np is not None and apply and pre_np <= 256:
+        if pre_np is None:  # nobody left the sums
+            if bn_bwd_one_launch(False, N, S):  # small per-channel data: reduce + finalize + apply
+                self._k("bn_bwd_fused:" + bn_name, "msl_bn_relu_bwd_fused", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]),
+                        ptr(vec[2]), ptr(vec[3]), ptr(gv[bn_name + ".weight"]), ptr(gv[bn_name + ".bias"]), ptr(g), N, C, S, st)
+                return
+            pre_np, part, apply = _lib.load().msl_bn_relu_bwd_num_partials(N, S), pl.partials, True
+            self._k("bn_bwd_reduce:" + bn_name, "msl_bn_relu_bwd_reduce", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
+                    ptr(vec[3]), ptr(pl.partials), N, C, S, st)
+        if apply and pre_np <= 256:
             self._k("bn_bwd_apply:" + bn_name, "msl_bn_relu_bwd_finalize_apply", ptr(part), pre_np, float(count), ptr(g),
                     ptr(y), ptr(vec), ptr(gv[bn_name + ".weight"]), ptr(gv[bn_name + ".bias"]), ptr(g), N, C, S, st)
             return
-        if pre_np is not None:
-            _lib.call("msl_bn_bwd_finalize", ptr(pl.partials), pre_np, float(count), ptr(gv[bn_name + ".weight"]),
-                      ptr(gv[bn_name + ".bias"]), ptr(vec[4]), ptr(vec[5]), C, st)
-            if apply:
-                self._k("bn_bwd_apply:" + bn_name, "msl_bn_relu_bwd_apply", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
-                        ptr(vec[3]), ptr(vec[4]), ptr(vec[5]), ptr(g), N, C, S, st)
-            return
-        if N * S <= 65536:  # small per-channel data: reduce + finalize + apply in one launch
-            self._k("bn_bwd_fused:" + bn_name, "msl_bn_relu_bwd_fused", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]),
-                    ptr(vec[2]), ptr(vec[3]), ptr(gv[bn_name + ".weight"]), ptr(gv[bn_name + ".bias"]), ptr(g), N, C, S, st)
-            return
-        NP = L.msl_bn_relu_bwd_num_partials(N, S)
-        self._k("bn_bwd_reduce:" + bn_name, "msl_bn_relu_bwd_reduce", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]),
-                  ptr(pl.partials), N, C, S, st)
-        if NP <= 256:
-            self._k("bn_bwd_apply:" + bn_name, "msl_bn_relu_bwd_finalize_apply", ptr(pl.partials), NP, float(count), ptr(g),
-                    ptr(y), ptr(vec), ptr(gv[bn_name + ".weight"]), ptr(gv[bn_name + ".bias"]), ptr(g), N, C, S, st)
-            return
-        _lib.call("msl_bn_bwd_finalize", ptr(pl.partials), NP, float(count), ptr(gv[bn_name + ".weight"]),
+        _lib.call("msl_bn_bwd_finalize", ptr(pl.partials), pre_np, float(count), ptr(gv[bn_name + ".weight"]),
                   ptr(gv[bn_name + ".bias"]), ptr(vec[4]), ptr(vec[5]), C, st)
-        self._k("bn_bwd_apply:" + bn_name, "msl_bn_relu_bwd_apply", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]),
-                  ptr(vec[4]), ptr(vec[5]), ptr(g), N, C, S, st)
+        if apply:
+            self._k("bn_bwd_apply:" + bn_name, "msl_bn_relu_bwd_apply", ptr(g), ptr(y), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
+                    ptr(vec[3]), ptr(vec[4]), ptr(vec[5]), ptr(g), N, C, S, st)
 
     def _head_gpack_batch(self, pl, dlocs, dscores, st):
         """msl_head_grad_pack of every scale in one launch."""
@@ -1066,11 +1115,9 @@ class Engine:
                     *[ctypes.addressof(x) + 4 * g0 for x in a[1:]], min(4, n - g0), pl.N, pl.P, self.model.n_classes, st)
 
     def _head_backward(self, pl, f, dlocs, dscores, st, data_done_event=None, data=True, weight=True, packed=False):
-        m, gv, ncls = self.model, self.arena.grad_views, self.model.n_classes
-        k = pl.feat_ids.index(f)
+        ncls = self.model.n_classes
         C = self.layer_specs[f]["cout"]
         D, H, W = pl.dims[f]
-        pre = f"pred_convs.loc_convs.{k}", f"pred_convs.cl_convs.{k}"
         if data:
             if not packed:
                 self._k(f"head_gpack{f}", "msl_head_grad_pack", ptr(dlocs), ptr(dscores), ptr(pl.dO[f]), pl.N, D, H, W, pl.P,
@@ -1146,7 +1193,7 @@ class Engine:
             raise RuntimeError("backward needs a train-mode forward made with gradients enabled")
         if pl.bf16:
             return self._backward_bf16(pl, dlocs, dscores, on_bucket_ready)
-        m = self.model
+        specs, feats, N = self.layer_specs, self.model.base.features, pl.N
         gv = self.arena.grad_views
         st = self._stream()
         ms = self.multi_stream
@@ -1155,20 +1202,14 @@ class Engine:
             stH, stW = sH.cuda_stream, sW.cuda_stream
         else:
             stH = stW = st
-        N = pl.N
-        specs = self.layer_specs
-        feats = m.base.features
         prepacked = dlocs is None  # the loss kernel wrote the head-gradient images itself (MultiBoxLoss._run_loss_pack)
         if not prepacked:
-            dlocs = dlocs.contiguous()
-            dscores = dscores.contiguous()
+            dlocs, dscores = dlocs.contiguous(), dscores.contiguous()
         wanted = getattr(on_bucket_ready, "stages", None)
         # data parallel: the partial sums of a gradient bucket are folded when the bucket's last stage has been enqueued
         # (stage -> parameter names); single process: one reduction at the very end
         groups = self._bucket_groups(on_bucket_ready) if wanted else {}
-
         report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, ms)
-
         # heads: the last scale feeds the chain immediately (main stream); the earlier scales are only needed when
         # the chain reaches their feature map, so they run on the heads stream beside blocks 7..4
         last = len(specs) - 1
@@ -1177,8 +1218,6 @@ class Engine:
         if packed and not prepacked:
             self._head_gpack_batch(pl, dlocs, dscores, st)
         L = _lib.load()
-        pre_np = None  # set when the producer of the next activation gradient also produced its BatchNorm partials
-        linked = False  # set when a channel link already applied the BatchNorm backward of the next layer's output gradient
         pending = []  # side-stream launches, issued one layer late so that the chain's launches always go first
         sinks = []    # (closure, event) of the weight-gradient launches still to be issued
         tail = []     # blocks whose pointwise weight gradients share one launch (deepest first), and their arguments
@@ -1224,108 +1263,82 @@ class Engine:
             # then the depthwise gradients.  The host enqueues the dependency chain (main stream) FIRST and the two
             # weight gradients (wgrad stream, waiting on events recorded in the chain) afterwards: the chain is made of
             # ~10 us kernels, so any launch queued in front of its next link shows up as idle time.
-            # big early block whose producer left the BatchNorm2-backward sums: BatchNorm backward of y_i (applied on load),
-            # bwd-data GEMM, BatchNorm1-backward sums of z_i and the pointwise weight gradient in ONE pass (csrc/pwfused.hip)
-            pw_fused = (not linked and pre_np is not None and i in pl.pw_fused
-                        and 2 * sp["cout"] * pre_np <= pl.partials.numel())
-            z_np = None
+            r = pl.routes[i]
+            pw_fused, link = r.bn2 == "pw_fused", r.dw in ("link", "link_bww")
+            slabs_f, part_f, z_np = pl.pw_fused[i] if pw_fused else (None, None, None)
             if pw_fused:
-                slabs_f, part_f, z_np = pl.pw_fused[i]
+                # BatchNorm backward of y_i (applied on load), bwd-data GEMM, BatchNorm1-backward sums of z_i and the pointwise
+                # weight gradient in ONE pass (csrc/pwfused.hip)
                 self._k(f"pw_bwd_fused{i}", "msl_pwconv_bwd_fused", ptr(pl.g_y[i]), ptr(pl.y[i]), ptr(pl.bn_y[i]), ptr(pl.partials),
-                        pre_np, float(N * S), ptr(gv[name + ".bn2.weight"]), ptr(gv[name + ".bn2.bias"]),
+                        r.y_np, float(N * S), ptr(gv[name + ".bn2.weight"]), ptr(gv[name + ".bn2.bias"]),
                         ptr(feats[i].conv2.weight), ptr(pl.z[i]), ptr(pl.bn_z[i]), ptr(pl.g_z[i]), ptr(part_f), ptr(slabs_f), N,
                         sp["cin"], sp["cout"], S, st)
-                pl.pw_fused_used.add(i)
-            elif not linked:  # (a channel link of block i+1 has already turned g_y[i] into dL/dy_i)
-                self._bn_bwd(pl.g_y[i], pl.y[i], pl.bn_y[i], name + ".bn2", N * S, N, sp["cout"], S, pl, st, pre_np=pre_np)
-            pre_np, linked = None, False
-            if not pw_fused:
+            else:
+                if r.bn2 == "bn":  # ("link": the channel link of block i+1 has already turned g_y[i] into dL/dy_i)
+                    self._bn_bwd(pl.g_y[i], pl.y[i], pl.bn_y[i], name + ".bn2", N * S, N, sp["cout"], S, pl, st, pre_np=r.y_np)
                 self._k(f"pw_bwd{i}", "msl_pwconv_bwd_data", ptr(pl.g_y[i]), ptr(feats[i].conv2.weight), ptr(pl.g_z[i]), N,
                         sp["cin"], sp["cout"], S, st)
             accumulate = 1 if (i - 1) in pl.fpad else 0  # the heads already wrote their share
-            Sp = pd * ph * pw
-            np_red = L.msl_dwconv_bwd_data_bnreduce_num_partials(N, sp["cin"], pd, ph, pw) if (s == 2 and N * Sp > 65536) else -1
-            fused_stem = i == 1 and self.fuse_stem and pl.fused_stem_np > 0
-            # tail of the network: BatchNorm1 backward of z_i, depthwise bwd-data (+ the heads' share) and BatchNorm2 backward
-            # of y_{i-1} are all per channel and a channel's population fits one workgroup: ONE launch (csrc/chanlink.hip)
-            link_nw = L.msl_block_bwd_channel_link_supported(N, pd, ph, pw, s)
-            link = link_nw > 0 and not fused_stem and np_red <= 0 and not pw_fused
-            # (with few waves per channel the link takes the depthwise weight gradient along: no launch for it below)
-            link_bww = link and link_nw <= LINK_BWW_MAX_WAVES
             # a block whose pointwise weight gradient rides in the tail's batched launch (issued with the shallowest of them) and
             # whose depthwise weight gradient the link produces has nothing waiting for dL/dz_i: no event record on the chain
-            idle_sink = (link_bww and i in tail and i != tail[-1]) or (pw_fused and fused_stem)
+            idle_sink = (r.dw == "link_bww" and i in tail and i != tail[-1]) or (pw_fused and r.dw == "fused_stem")
             rec_here = ms and not idle_sink
             if not link:
                 self._bn_bwd(pl.g_z[i], pl.z[i], pl.bn_z[i], name + ".bn1", N * S, N, sp["cin"], S, pl, st, pre_np=z_np,
-                             partials=pl.pw_fused[i][1] if pw_fused else None)
+                             partials=part_f)
                 ev_dz = self._record(pl, f"dz{i}", st) if rec_here else None
             if accumulate and (i - 1) in side_feats:
                 self._wait(st, pl.events[f"head_done{i - 1}"])
-            # big producer layers: emit the BatchNorm-backward partials of y_{i-1} while its gradient is in registers
-            dw_fused = False
             if link:
                 prev = "base.features.0.1" if i == 1 else f"base.features.{i - 1}.bn2"
                 self._k(f"link{i}", "msl_block_bwd_channel_link", ptr(pl.g_z[i]), ptr(pl.z[i]), ptr(pl.bn_z[i]),
                         ptr(feats[i].conv1.weight), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1]), ptr(pl.g_y[i - 1]),
                         ptr(gv[name + ".bn1.weight"]), ptr(gv[name + ".bn1.bias"]), ptr(gv[prev + ".weight"]),
-                        ptr(gv[prev + ".bias"]), ptr(gv[name + ".conv1.weight"]) if link_bww else None, N, sp["cin"], pd, ph,
-                        pw, s, accumulate, st)
-                if link_bww:
-                    pl.dw_in_link.add(i)
+                        ptr(gv[prev + ".bias"]), ptr(gv[name + ".conv1.weight"]) if r.dw == "link_bww" else None, N, sp["cin"],
+                        pd, ph, pw, s, accumulate, st)
                 ev_dz = self._record(pl, f"dz{i}", st) if rec_here else None
-                linked = True
-            elif fused_stem:
+            elif r.dw == "fused_stem":
                 # one pass over (dL/dz_1, y_0): BatchNorm-backward sums of the stem + the depthwise weight gradient;
                 # the stem weight gradient below rebuilds dL/d(stem activation) from dL/dz_1 on the fly
                 vp = pl.bn_y[0]
                 self._k("dw_bwd1", "msl_dwconv_s2_bwd_bnreduce_bww", ptr(pl.g_z[1]), ptr(feats[1].conv1.weight), ptr(pl.y[0]),
                         ptr(vp[0]), ptr(vp[1]), ptr(vp[2]), ptr(vp[3]), ptr(pl.partials), ptr(pl.partials_wf), ptr(pl.w1_taps_t),
                         N, 32, pd, ph, pw, st)
-                pre_np = pl.fused_stem_np
-            elif np_red > 0 and i in pl.dw_fused_part:
+            elif r.dw == "s2_bww":
                 # big stride-2 producer layer: bwd-data, the BatchNorm-backward sums of y_{i-1} AND this block's depthwise
                 # weight gradient in one pass over (dL/dz_i, y_{i-1}) - the weight-gradient launch on the side stream (the same
                 # 38 MB read again, 35 us beside the chain at block 2) disappears
                 vp = pl.bn_y[i - 1]
-                part_w, np_w = pl.dw_fused_part[i]
                 self._k(f"dw_bwd{i}", "msl_dwconv_s2_bwd_data_bnreduce_bww", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight),
                         ptr(pl.g_y[i - 1]), ptr(pl.y[i - 1]), ptr(vp[0]), ptr(vp[1]), ptr(vp[2]), ptr(vp[3]), ptr(pl.partials),
-                        ptr(part_w), N, sp["cin"], pd, ph, pw, accumulate, st)
-                pre_np = np_w
-                dw_fused = True
-                pl.dw_fused_used.add(i)
-            elif np_red > 0 and 2 * sp["cin"] * np_red <= pl.partials.numel():
+                        ptr(r.dw_part[0]), N, sp["cin"], pd, ph, pw, accumulate, st)
+            elif r.dw == "bnreduce":
+                # big producer layer: emit the BatchNorm-backward partials of y_{i-1} while its gradient is in registers
                 vp = pl.bn_y[i - 1]
                 self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data_bnreduce", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight),
                         ptr(pl.g_y[i - 1]), ptr(pl.y[i - 1]), ptr(vp[0]), ptr(vp[1]), ptr(vp[2]), ptr(vp[3]), ptr(pl.partials),
                         N, sp["cin"], pd, ph, pw, s, accumulate, st)
-                pre_np = np_red
             else:
                 self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight), ptr(pl.g_y[i - 1]),
                         N, sp["cin"], pd, ph, pw, s, accumulate, st)
-            def wgrads(ev_dz, i=i, sp=sp, S=S, pd=pd, ph=ph, pw=pw, s=s, name=name,
-                       fused_stem=fused_stem or link_bww or dw_fused, idle_sink=idle_sink, pw_fused=pw_fused):
+            def wgrads(ev_dz, i=i, sp=sp, S=S, pd=pd, ph=ph, pw=pw, s=s, name=name, r=r, idle_sink=idle_sink, pw_fused=pw_fused):
                 # the heads stream is idle once the head gradients are done: odd blocks go there, even ones to the wgrad stream
                 sX = (stH if i % 2 else stW) if ms else st
                 if ms and not idle_sink:  # the pointwise gradient needs dL/dy_i, the depthwise one dL/dz_i (final later)
                     self._wait(sX, ev_dz)
                 # partial sums only: slabs / fp64 partials stay in this layer's own buffers until Engine._grad_reduce
-                out = pl.pw_slabs[i] if pl.pw_nslabs[i] > 1 else gv[name + ".conv2.weight"]
-                if pw_fused:
-                    pass  # (its slabs came with the fused pointwise backward)
-                elif i in tail:
+                out = r.pw_part[0] if r.pw_part is not None else gv[name + ".conv2.weight"]
+                if i in tail and not pw_fused:  # (pw_fused: its slabs came with the fused pointwise backward)
                     tail_args.append((ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]), ptr(out), sp["cin"],
                                       sp["cout"], S))
                     if i == tail[-1]:  # the shallowest: every dL/dy of the group is final (same chain, earlier)
                         self._pw_bww_batch(pl, tail_args, N, sX)
-                else:
+                elif not pw_fused:
                     self._k(f"pw_bww{i}", "msl_pwconv_bwd_weight_slabs", ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]),
                             ptr(pl.bn_z[i][1]), ptr(out), N, sp["cin"], sp["cout"], S, sX)
-                if fused_stem:
-                    return  # its partials came with the fused stem backward pass (pl.partials_wf) / the channel link wrote dW
-                self._k(f"dw_bww{i}", "msl_dwconv_bwd_weight", ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]),
-                        ptr(pl.bn_y[i - 1][1]), None, ptr(pl.dw_part[i]), N, sp["cin"], pd, ph, pw, s, sX)
+                if r.dw in DW_BWW:  # (else its partials came with the depthwise backward pass: r.dw_part / the link wrote dW)
+                    self._k(f"dw_bww{i}", "msl_dwconv_bwd_weight", ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]),
+                            ptr(pl.bn_y[i - 1][1]), None, ptr(pl.dw_part[i]), N, sp["cin"], pd, ph, pw, s, sX)
 
             # issue what earlier layers left for the side streams (the head gradients the chain waits for and the weight
             # gradients, which nothing in the step waits for: one layer late), then queue this layer's
@@ -1347,25 +1360,20 @@ class Engine:
         od, oh, ow = pl.dims[0]
         S0 = od * oh * ow
         D, H, W = pl.in_dims
-        sd, sh, sw = specs[0]["stride"]
-        if pre_np is not None and specs[0]["cout"] == 32:
-            # reduce came with the depthwise bwd-data above; the apply is fused into the stem weight gradient
-            fused = self.fuse_stem and pl.fused_stem_np > 0
-            self._bn_bwd(pl.g_y[0], pl.y[0], pl.bn_y[0], "base.features.0.1", N * S0, N, 32, S0, pl, st, pre_np=pre_np,
-                         apply=False, coef=fused)
-            if fused:
-                self._k("stem_bww", "msl_stem_conv_bwd_weight_fused", ptr(pl.g_z[1]), ptr(pl.w1_taps_t), ptr(pl.y[0]),
-                        ptr(pl.bn_y[0]), ptr(pl.saved_input), None, ptr(pl.ws_stem), N,
-                        specs[0]["cin"], D, H, W, sd, sh, sw, st)
-            else:
-                self._k("stem_bww", "msl_stem_conv_bwd_weight_bnapply", ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(pl.bn_y[0]),
-                        ptr(pl.saved_input), None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, sd, sh, sw, st)
+        r = pl.routes[0]
+        if r.bn == "bn":  # ("link", tiny inputs: block 1's channel link has already applied the stem's BatchNorm backward)
+            # "bnapply" / "fused": the reduce came with the depthwise bwd-data above, the apply is part of the weight gradient
+            self._bn_bwd(pl.g_y[0], pl.y[0], pl.bn_y[0], "base.features.0.1", N * S0, N, specs[0]["cout"], S0, pl, st,
+                         pre_np=r.y_np, apply=r.wgrad == "plain", coef=r.wgrad == "fused")
+        if r.wgrad == "fused":
+            self._k("stem_bww", "msl_stem_conv_bwd_weight_fused", ptr(pl.g_z[1]), ptr(pl.w1_taps_t), ptr(pl.y[0]),
+                    ptr(pl.bn_y[0]), ptr(pl.saved_input), None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
+        elif r.wgrad == "bnapply":
+            self._k("stem_bww", "msl_stem_conv_bwd_weight_bnapply", ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(pl.bn_y[0]),
+                    ptr(pl.saved_input), None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
         else:
-            if not linked:  # (tiny inputs: block 1's channel link has already applied the stem's BatchNorm backward)
-                self._bn_bwd(pl.g_y[0], pl.y[0], pl.bn_y[0], "base.features.0.1", N * S0, N, specs[0]["cout"], S0, pl, st,
-                             pre_np=pre_np)
             self._k("stem_bww", "msl_stem_conv_bwd_weight", ptr(pl.g_y[0]), ptr(pl.saved_input),
-                    None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, sd, sh, sw, st)
+                    None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
         for fn in pending:
             fn()
         for fn, e in sinks:
@@ -1414,22 +1422,13 @@ class Engine:
                     bias = pl.head_ws[f][ns * slab:]  # [ns][16*mt] row sums of dO: rows 0-11 loc, 12.. cls
                     rows.append((0, bias, gv[lw[:-6] + "bias"], None, ns, 12, 16 * mt, 0, 0, 0))
                     rows.append((0, bias[12:], gv[cw[:-6] + "bias"], None, ns, 2 * ncls, 16 * mt, 0, 0, 0))
-            fused = self.fuse_stem and pl.fused_stem_np > 0
-            for i in range(len(specs) - 1, 0, -1):
-                name = f"base.features.{i}"
+            for i in range(len(specs) - 1, 0, -1):  # (a gradient without partials was written to the arena by its kernel)
+                name, r = f"base.features.{i}", pl.routes[i]
                 cnt = specs[i]["cin"] * specs[i]["cout"]
-                if want(name + ".conv2.weight") and i in pl.pw_fused_used:
-                    rows.append((0, pl.pw_fused[i][0], gv[name + ".conv2.weight"], None, pl.pw_fused[i][2], cnt, cnt, 0, 0, 0))
-                elif want(name + ".conv2.weight") and pl.pw_nslabs[i] > 1:
-                    rows.append((0, pl.pw_slabs[i], gv[name + ".conv2.weight"], None, pl.pw_nslabs[i], cnt, cnt, 0, 0, 0))
-                if want(name + ".conv1.weight") and i not in pl.dw_in_link:  # (a channel link wrote it)
-                    if i == 1 and fused:
-                        rows.append((1, pl.partials_wf, gv[name + ".conv1.weight"], None, pl.fused_stem_np, specs[i]["cin"] * 27, 0, 0, 0, 0))
-                    elif i in pl.dw_fused_used:
-                        part_w, np_w = pl.dw_fused_part[i]
-                        rows.append((1, part_w, gv[name + ".conv1.weight"], None, np_w, specs[i]["cin"] * 27, 0, 0, 0, 0))
-                    else:
-                        rows.append((1, pl.dw_part[i], gv[name + ".conv1.weight"], None, pl.dw_np[i], specs[i]["cin"] * 27, 0, 0, 0, 0))
+                if want(name + ".conv2.weight") and r.pw_part is not None:
+                    rows.append((0, r.pw_part[0], gv[name + ".conv2.weight"], None, r.pw_part[1], cnt, cnt, 0, 0, 0))
+                if want(name + ".conv1.weight") and r.dw_part is not None:
+                    rows.append((1, r.dw_part[0], gv[name + ".conv1.weight"], None, r.dw_part[1], specs[i]["cin"] * 27, 0, 0, 0, 0))
             if want("base.features.0.0.weight"):
                 K = specs[0]["cin"] * 27
                 nt = (K + 31) // 32

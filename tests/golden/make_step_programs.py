@@ -1,0 +1,164 @@
+"""Mint ``step_programs.json``: the launch program one ``FusedTrainer`` step records per input shape, storage type and
+``Engine.fuse_stem``, taken at the commit BEFORE the backward passes read their kernel routes from ``Plan.routes`` (so the
+file pins which entry point the inline decisions of ``Engine.backward`` / ``_backward_bf16`` chose, on which stream, in which
+order and with which arguments):
+
+    python -m tests.golden.make_step_programs            # writes the file (needs the GPU)
+    python -m tests.golden.make_step_programs --dump     # prints every normalised program instead (to diff two commits)
+
+Per case, the first step of a fresh trainer is recorded and taken through ``_lib._fuse_stop_events`` (what the native replay
+compiles).  Every entry becomes ``[role, entry point, tag, arguments]``: ``role`` is the stream it is issued on (chain /
+heads / wgrad / other), an integer argument below 2^31 in magnitude and a float are kept by value, ``None`` stays ``None``
+and every larger integer - device pointers, host-array addresses, event and stream handles - is replaced by ``"#k"``, k the
+ordinal of its first appearance in the program.  A Python hook becomes ``["hook", tag]``.  The file keeps, per case, the
+``[role, entry point, tag]`` list and a SHA-256 over the fully normalised entries.
+``tests/test_gpu_model.py::test_step_program_is_the_recorded_one`` rebuilds the same cases and compares.
+
+When minting, every backward route the engine can take must show among the cases of each storage type that has it
+(``ROUTES``).  Two fp32 routes are out of reach of these cases: ``msl_pwconv_bwd_fused`` and
+``msl_dwconv_s2_bwd_data_bnreduce_bww`` both need a block i >= 2 whose input has more than 65536 positions per channel over
+the batch; at 128^3 x 2, the largest case allowed here, block 2's input has exactly 65536 (128^3 x 4 is the smallest cube
+that takes them).
+"""
+import argparse
+import hashlib
+import json
+import os
+
+from tests.golden import detinit
+
+OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "step_programs.json")
+TINY = 16  # edge of the tiny cube (see tiny_cube)
+# name -> (batch, input size, input channels, Engine.fuse_stem); each with fp32 and bf16 storage, 2 classes
+SHAPES = {"64x2": (2, (64, 64, 64), 1, True),
+          "48x64x64x2-2ch": (2, (48, 64, 64), 2, True),  # smallest shape of the suite on the big-producer paths
+          "64x2-nofuse": (2, (64, 64, 64), 1, False),
+          # block 1 itself takes a channel link, which leaves the stem its BatchNorm backward done (fp32; the fused stem pass
+          # goes first wherever it is enabled, so this route only exists with Engine.fuse_stem off)
+          "tiny-nofuse": (2, (TINY,) * 3, 1, False),
+          "128x2": (2, (128, 128, 128), 1, True),          # bf16: a stride-2 patch pass feeding block 1's BatchNorm backward
+          "128x2-nofuse": (2, (128, 128, 128), 1, False)}  # fp32: msl_dwconv_bwd_data_bnreduce, the stem's bn-apply weight gradient
+
+
+def _entry(name):
+    return lambda p, sfx: any(e == name for e, _ in p)
+
+
+def _link(with_dw_bww):
+    return lambda p, sfx: any((f"msl_block_bwd_channel_link{sfx}", f"link{i}") in p
+                              and any(t == f"dw_bww{i}" for _, t in p) == with_dw_bww for i in range(1, 16))
+
+
+# route -> (storage types in which some case must take it, predicate over the program's (entry point, tag) pairs and the
+# entry points' storage suffix)
+ROUTES = {
+    "link": (("f32", "bf16"), _link(True)),
+    "link without a following dw_bww": (("f32", "bf16"), _link(False)),
+    "msl_dwconv_bwd_data_bnreduce": (("f32",), _entry("msl_dwconv_bwd_data_bnreduce")),
+    "s2_patch": (("bf16",), _entry("msl_dwconv_bwd_data_s2_patch_bf16")),
+    "dw_bwd1 fused": (("f32", "bf16"), lambda p, sfx: (f"msl_dwconv_s2_bwd_bnreduce_bww{sfx}", "dw_bwd1") in p),
+    "plain": (("f32", "bf16"), lambda p, sfx: any(e == f"msl_dwconv_bwd_data{sfx}" for e, _ in p)),
+    # fp32 routes no case reaches (module docstring): minting asserts that too, so that the docstring stays true
+    "pw_bwd_fused": ((), _entry("msl_pwconv_bwd_fused")),
+    "msl_dwconv_s2_bwd_data_bnreduce_bww": ((), _entry("msl_dwconv_s2_bwd_data_bnreduce_bww")),
+}
+
+
+def cases():
+    """name -> (batch, input size, input channels, Engine.fuse_stem, dtype)."""
+    return {f"{tag}-{dtype}": shape + (dtype,) for tag, shape in SHAPES.items() for dtype in ("f32", "bf16")}
+
+
+def tiny_cube(batch=2):
+    """Edge of the smallest cube (a multiple of 8) at which block 1 itself can take a channel link: the link serves its
+    producer, the stem activation.  A host query; TINY must be its answer."""
+    from mslesions3d_amd import _lib
+    for edge in range(8, 129, 8):
+        half = (edge - 1) // 2 + 1
+        if _lib.load().msl_block_bwd_channel_link_supported(batch, half, half, half, 2) > 0:
+            return edge
+    return None
+
+
+def record(case, device="cuda"):
+    """One step of a fresh trainer on ``case`` -> (normalised program, the step's plan)."""
+    from mslesions3d_amd import _lib
+    from mslesions3d_amd.ssd3d import LSSD3D
+    from mslesions3d_amd.trainer import FusedTrainer
+    n, size, cin, fuse, dtype = case
+    m = LSSD3D(n_classes=2, input_channels=cin, input_size=size, threshold=[0.1, 0.2], lr=1e-3, batch_size=n)
+    m.load_state_dict(detinit.fill_state_dict(m.state_dict(), 1234))
+    m = m.to(device).train()
+    m.compute_dtype = dtype
+    m._engine.fuse_stem = fuse
+    tr = FusedTrainer(m)
+    x = detinit.make_volume_batch(5, n, cin, size).to(device)
+    boxes, labels = detinit.make_gt(8, n, size)
+    tr.step(x, [b.to(device) for b in boxes], [t.to(device) for t in labels])
+    entry = list(tr._programs.values())[-1]
+    heads, wgrad = (s.cuda_stream for s in m._engine.side_streams(x.device))
+    roles = {tr._stream.cuda_stream: "chain", heads: "heads", wgrad: "wgrad"}
+    seen = {}
+
+    def norm(a):
+        if a is None or isinstance(a, float):
+            return a
+        a = int(a)
+        return a if abs(a) < (1 << 31) else "#%d" % seen.setdefault(a, len(seen))
+    prog = []
+    for fn, args, tag, stream in _lib._fuse_stop_events(entry["prog"], ()):
+        if fn is None:
+            prog.append(["hook", tag])
+        else:
+            prog.append([roles.get(stream, "other"), fn.__name__, tag, [norm(a) for a in args]])
+    return prog, entry["plan"]
+
+
+def summary(prog):
+    """What the file keeps of a normalised program."""
+    return {"sha256": hashlib.sha256(json.dumps(prog).encode()).hexdigest(), "entries": [e[:3] for e in prog]}
+
+
+def write(progs, out):
+    with open(out, "w") as f:  # one entry per line
+        body = []
+        for name, prog in progs.items():
+            s = summary(prog)
+            body.append(f' "{name}": {{"sha256": "{s["sha256"]}", "entries": [\n  '
+                        + ",\n  ".join(json.dumps(e) for e in s["entries"]) + "]}")
+        f.write("{\n" + ",\n".join(body) + "\n}\n")
+    print(f"{out}: {len(progs)} cases, {sum(len(p) for p in progs.values())} entries")
+
+
+def check_routes(progs):
+    """Every route of ROUTES shows in a case of each storage type listed for it (and in none where none is listed)."""
+    pairs = {name: {(e[1], e[2]) for e in prog if e[0] != "hook"} for name, prog in progs.items()}
+    for route, (dtypes, found) in ROUTES.items():
+        for dtype in dtypes:
+            hit = [name for name, p in pairs.items() if name.endswith("-" + dtype) and found(p, "_bf16" if dtype == "bf16" else "")]
+            print(f"route {route!r} ({dtype}): {hit}")
+            assert hit, f"no {dtype} case takes the route {route!r}"
+        if not dtypes:
+            assert not any(found(p, "") for p in pairs.values()), f"{route!r} is reached after all: list it for fp32"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--dump", action="store_true", help="print the full normalised programs instead of writing the file")
+    args = ap.parse_args()
+    assert tiny_cube() == TINY, f"the tiny case must be the {tiny_cube()}^3 cube"
+    progs = {name: record(c, args.device)[0] for name, c in cases().items()}
+    if args.dump:
+        for name, prog in progs.items():
+            print(f"== {name}")
+            for k, e in enumerate(prog):
+                print(f"{k:4d} " + " ".join(json.dumps(v) for v in e))
+        return
+    write(progs, args.out)
+    check_routes(progs)
+
+
+if __name__ == "__main__":
+    main()

@@ -14,6 +14,7 @@ from oracle import multibox as OMB
 from oracle.train_step import make_optimizer, train_step
 from tests.golden import cases, detinit
 from tests.golden import make_plan_inventory as plan_inventory
+from tests.golden import make_step_programs as step_programs
 from tests.util import GOLDEN_DIR, golden, oracle_model
 
 pytestmark = pytest.mark.gpu
@@ -543,13 +544,41 @@ def test_fused_stem_backward_matches_the_materialised_path():
     assert "base.features.2.conv1.weight" in same and "pred_convs.loc_convs.0.weight" in same
 
 
+def test_fuse_stem_set_between_two_passes_takes_effect_in_every_gradient():
+    """Engine.fuse_stem decides where block 1's depthwise weight gradient is summed (the fused stem pass's own partials or
+    the depthwise weight-gradient kernel's), and the batched gradient reduction folds what its table lists.  Setting the
+    option between two eager passes of one fp32 model therefore has to reach that table too: every gradient of the second
+    pass is bit-equal to that of a fresh model run once with the new value on the same weights and input, in both orders.
+    (The first pass runs on another input, so that a table still folding its leftovers cannot pass by coincidence.)"""
+    size, n = (64, 64, 64), 2
+    xs = [detinit.make_volume_batch(seed, n, 1, size).to(DEV) for seed in (5, 6)]
+    boxes, labels = detinit.make_gt(8, n, size)
+    boxes, labels = [b.to(DEV) for b in boxes], [t.to(DEV) for t in labels]
+
+    def grads(m, fuse, x):
+        m._engine.fuse_stem = fuse
+        m.zero_grad(set_to_none=True)
+        l, s = m(x)
+        c, lc = m.loss_fn(l, s, boxes, labels)
+        (c + lc).backward()
+        return {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}
+
+    for first in (True, False):
+        m = hip_model(1, size).train()
+        grads(m, first, xs[0])
+        got = grads(m, not first, xs[1])
+        want = grads(hip_model(1, size).train(), not first, xs[1])
+        assert got.keys() == want.keys()
+        differ = [k for k in want if not torch.equal(got[k], want[k])]
+        assert not differ, f"fuse_stem {first} -> {not first}: {differ}"
+
+
 # ------------------------------------------------------------------------------------------------- plan layout
 # What a plan may hold beyond tests/golden/plan_inventory.json (minted while the fp32 and the bf16 plan had a builder each):
 # the fields Plan.__init__ declares for the methods that write them later, and the fields only one of the two builders set,
 # which every plan has now (empty / constant where they do not apply).
 PLAN_DECLARED = {"bf16", "trained_mode", "stem_dw_eval", "loss_fold", "bn_table", "pwb_key", "pwb_args", "pack_key", "pack_args",
-                 "gpack_key", "gpack_args", "grad_tables", "dw_in_link", "pw_fused_used", "dw_fused_used",
-                 "pw_fused", "dw_fused_part", "f32_heads"}
+                 "gpack_key", "gpack_args", "grad_tables", "routes", "pw_fused", "dw_fused_part", "f32_heads"}
 PLAN_ZEROED = ("fpad", "fpad_cl", "dO", "bn_y", "bn_z", "nan_flag")  # kernels rely on their initial zeros (halos, flag)
 
 
@@ -574,9 +603,52 @@ def test_plan_buffer_inventory(name):
             assert t is None or not bool(t.any()), f"{attr} is not all-zero after construction"
 
 
+@pytest.mark.parametrize("name", list(step_programs.cases().keys()))
+def test_step_program_is_the_recorded_one(name):
+    """The launch program of one training step - entry points, streams, tags, order and arguments (pointers, handles and
+    host addresses by order of first appearance) - is the one tests/golden/step_programs.json recorded before the backward
+    passes took their kernel routes from Plan.routes; `python -m tests.golden.make_step_programs --dump` prints the full
+    programs of a commit for a diff.  And the routes agree with the plan: every buffer they send a weight gradient to is
+    the plan's buffer of that kernel form, so no gradient has two sources or none."""
+    from mslesions3d_amd.engine import DW_BWW
+    with open(os.path.join(GOLDEN_DIR, "step_programs.json")) as f:
+        want = json.load(f)[name]
+    prog, pl = step_programs.record(step_programs.cases()[name], DEV)
+    got = step_programs.summary(prog)
+    assert got["entries"] == want["entries"]
+    assert got["sha256"] == want["sha256"], "same launches, other arguments"
+    tags = {e[2] for e in prog if e[0] != "hook"}
+    assert len(pl.routes) == len(pl.y) and pl.routes[0].bn in ("link", "bn") and pl.routes[0].wgrad in ("plain", "bnapply", "fused")
+    for i in range(1, len(pl.routes)):
+        r = pl.routes[i]
+        assert r.dw in ("link", "link_bww", "fused_stem", "s2_bww", "bnreduce", "s2_patch", "plain") and r.bn2 in ("link", "pw_fused", "bn")
+        if r.dw == "link_bww":  # the link writes the gradient itself
+            buf, cnt = None, None
+        elif r.dw == "fused_stem":
+            buf, cnt = pl.partials_wf, pl.fused_stem_np
+        elif r.dw == "s2_bww":
+            buf, cnt = pl.dw_fused_part[i]
+        else:
+            buf, cnt = pl.dw_part[i], pl.dw_np[i]
+        assert r.dw_part is None if buf is None else (r.dw_part[0] is buf and r.dw_part[1] == cnt)
+        # the weight-gradient kernel runs exactly when no other pass sums the gradient, into the buffer the reduction folds
+        assert (f"dw_bww{i}" in tags) == (r.dw in DW_BWW) == (buf is pl.dw_part[i])
+        if r.bn2 == "pw_fused":
+            assert r.pw_part[0] is pl.pw_fused[i][0] and r.pw_part[1] == pl.pw_fused[i][2] and f"pw_bww{i}" not in tags
+        elif pl.pw_nslabs[i] > 1:
+            assert r.pw_part[0] is pl.pw_slabs[i] and r.pw_part[1] == pl.pw_nslabs[i]
+        else:
+            assert r.pw_part is None
+        # what block i+1 did for y_i is what block i expects
+        nxt = pl.routes[i + 1].dw if i + 1 < len(pl.routes) else "plain"
+        assert (r.bn2 == "link") == (nxt in ("link", "link_bww")) and (r.y_np is not None) <= (nxt in ("fused_stem", "s2_bww", "bnreduce", "s2_patch"))
+    assert (pl.routes[0].bn == "link") == (pl.routes[1].dw in ("link", "link_bww"))
+    assert (pl.routes[0].wgrad == "fused") == (pl.routes[1].dw == "fused_stem")
+
+
 def test_a_changed_build_time_option_builds_a_new_plan():
-    """A bf16 plan bakes Engine.bf16_heads (and, for training, Engine.fuse_stem) in when it is built: both are part of the
-    cache key, so setting one later gives a plan with the buffers of the new route, not the cached one."""
+    """A bf16 plan bakes Engine.bf16_heads in when it is built, and every training plan Engine.fuse_stem: both are part of
+    the cache key, so setting one later gives a plan with the buffers (and routes) of the new value, not the cached one."""
     m = hip_model()
     m.compute_dtype = "bf16"
     eng = m._engine

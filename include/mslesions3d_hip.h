@@ -609,6 +609,31 @@ int msl_grad_reduce_table_set(void* host_table, int index, int first_block, int 
 int msl_grad_reduce_batch(const void* table, int n_entries, int total_blocks, void* stream);
 /* the same; block_entry[total_blocks] (device) names every workgroup's table entry, so no workgroup searches the table */
 int msl_grad_reduce_batch_indexed(const void* table, int n_entries, const int* block_entry, int total_blocks, void* stream);
+/* ---- per-tensor histograms and moments : ssd3d.py:729-738 (on_after_backward, add_histogram) ------------------- */
+/* One pass over n_src (1 .. 4) flat fp32 device arrays that share one segment table: segment s is elements
+ * [seg_off[s], seg_off[s] + seg_len[s]) of every source (seg_off (n_seg) i64, seg_len (n_seg) i32, device).  Outputs, per
+ * (source k, segment s), at index k * n_seg + s:
+ * hist (x 128 i32), keyed on the fp32 bit pattern with integer operations only: bin 0 non-finite (NaN, +-Inf), 1 +-0,
+ * 2 + c negative and 65 + c positive finite non-zero values of magnitude class c = clamp(E - 127, -42, 20) + 42 for a
+ * normal number with biased exponent field E (floor(log2|x|) clamped to [-42, 20]), c = 0 for a subnormal;
+ * moments (x 5 f64) over the finite values: sum, sum of squares, sum of magnitudes, min, max (+inf / -inf if none).
+ * Every output word is (re)written by each call - the caller clears nothing - and results are run-to-run bit-identical
+ * (integer adds for the bins; the f64 sums go through per-workgroup partials folded in a fixed order, no float atomics).
+ * A workgroup takes one chunk of msl_tensor_stats_chunk() elements of one segment, named by block_table (device copy of
+ * what msl_tensor_stats_block_table fills on the HOST: n_seg + 1 prefix sums "first workgroup of segment s", then
+ * (segment, chunk) per workgroup); that helper returns n_blocks (0: a null pointer, n_seg < 1, a length < 1, a table
+ * capacity below n_seg + 1 + 2 * n_blocks ints) and only counts when host_table is NULL.  partials: workspace of
+ * msl_tensor_stats_workspace_bytes(n_src, n_blocks) bytes, 8-byte aligned (0: bad argument).
+ * -1 (nothing launched): a null or misaligned pointer, n_src outside 1 .. 4, n_seg outside 1 .. 65535, n_blocks < n_seg. */
+#define MSL_TENSOR_STATS_BINS 128
+#define MSL_TENSOR_STATS_CHUNK 4096
+#define MSL_TENSOR_STATS_MAX_SOURCES 4
+size_t msl_tensor_stats_chunk(void);
+size_t msl_tensor_stats_block_table(const int* seg_len, int n_seg, int* host_table, size_t capacity_ints);
+size_t msl_tensor_stats_workspace_bytes(int n_src, int n_blocks);
+int msl_tensor_stats(const float* src0, const float* src1, const float* src2, const float* src3, int n_src,
+                     const long long* seg_off, const int* seg_len, int n_seg, const int* block_table, int n_blocks,
+                     double* partials, int* hist, double* moments, void* stream);
 /* stream fork/join (hipEvent with timing disabled): record on the producer stream, wait on the consumer stream */
 int msl_event_create(void** out);
 int msl_event_create_device(void** out);                      /* orders streams of ONE device only (hipEventDisableSystemFence): never for host waits or other devices */

@@ -153,6 +153,10 @@ _SIGNATURES = {
     "msl_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "msl_nan_flag": (_I, [_P, _Z, _P, _I, _P]),
     "msl_nan_flag2": (_I, [_P, _Z, _I, _P, _Z, _I, _P, _P]),
+    "msl_tensor_stats_chunk": (_Z, []),
+    "msl_tensor_stats_block_table": (_Z, [_P, _I, _P, _Z]),
+    "msl_tensor_stats_workspace_bytes": (_Z, [_I, _I]),
+    "msl_tensor_stats": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "msl_program_fn_id": (_I, [_P]),
     "msl_run_program": (_I, [_P, _P, _I, _I, _P]),
     "msl_run_program_mt": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),

@@ -431,11 +431,11 @@ class DeviceCache:
             yield {"img": b["img"], "seg": b["seg"], "gb": b["box"].gb, "gl": b["box"].gl, "obj_off": b["box"].obj_off,
                    "capacity": self.capacity, "subject": [tr.subjects[i] for i in idx], "_box": b["box"]}
 
-    def step(self, trainer, batch, metrics=False):
+    def step(self, trainer, batch, metrics=False, stats=False):
         """One ``FusedTrainer.step_packed`` on a ``train_batches`` batch; raises HipKernelError if the batch overflowed
         the capacity (checked after the step's own loss read: no extra synchronisation)."""
         out = trainer.step_packed(batch["img"], batch["gb"], batch["gl"], batch["obj_off"], batch["capacity"],
-                                  resident=True, metrics=metrics)
+                                  resident=True, metrics=metrics, stats=stats)
         batch["_box"].raise_on_overflow()
         return out
 

@@ -72,7 +72,44 @@ def build_parser():
     p.add_argument('--patch_foreground', type=float, default=0.67, metavar='P',
                    help='probability that a training window is placed on a lesion (else uniformly)')
     p.add_argument('--tile_margin', type=int, nargs=3, default=[8, 8, 8], metavar=('D', 'H', 'W'))
+    # on_after_backward of the reference (ssd3d.py:729-738: a gradient histogram per parameter every 25 steps), on the
+    # device: every N-th step appends one record to LOGDIR/EXPERIMENT/grad_hist.jsonl (mslesions3d_amd.diagnostics prints it)
+    p.add_argument('--grad_histograms', type=int, default=0, metavar='N',
+                   help='per-parameter gradient / weight histograms every N steps (0: off; the reference logs every 25)')
     return p
+
+
+class GradHistogramLog:
+    """``--grad_histograms N``: the steps that start from a ``global_step`` divisible by N run with ``stats=True``, and rank 0
+    appends their records to ``grad_hist.jsonl``.  A record is read back at the NEXT logging point (or at ``close``), never
+    right after its own step, so the read never waits for the pass it asked for."""
+
+    def __init__(self, every, path):
+        self.every, self.path = int(every), path
+        self.pending = None  # epoch of the stats step whose record is still on the device
+
+    def wanted(self, global_step):
+        return self.every > 0 and global_step % self.every == 0
+
+    def flush(self, trainer):
+        if self.pending is None:
+            return
+        from .diagnostics import to_record
+        stats = trainer.last_stats()
+        if self.path is not None:
+            with open(self.path, "a") as f:
+                f.write(json.dumps(to_record(stats, stats["step"], self.pending)) + "\n")
+        self.pending = None
+
+    def before_step(self, trainer, global_step, epoch):
+        """-> the ``stats`` argument of this step (flushes the previous record first: this step overwrites the snapshot)."""
+        if not self.wanted(global_step):
+            return False
+        self.flush(trainer)
+        self.pending = epoch
+        return True
+
+    close = flush
 
 
 def input_images_of(args):
@@ -212,6 +249,9 @@ def example(args):
     if rank == 0:
         os.makedirs(logdir, exist_ok=True)
         log = open(pjoin(logdir, "metrics.jsonl"), "a")
+    # rank 0 alone runs the statistics pass (it reads this rank's arena: the reduced gradient is the same on every rank)
+    ghist = GradHistogramLog(args.grad_histograms, pjoin(logdir, "grad_hist.jsonl")) \
+        if rank == 0 and getattr(args, "grad_histograms", 0) > 0 else None
     if dp:  # every rank's own shard: which subjects it trained on and what they cost (rank 0's losses are in metrics.jsonl too)
         dist_barrier()
         shard_log = open(pjoin(logdir, f"shard_rank{rank}.jsonl"), "a")
@@ -225,10 +265,11 @@ def example(args):
         # training metrics (ssd3d.py:497-515): detection + mAP on every step's own forward outputs, on the device
         train_metrics = epoch % (2 * max(int(model.compute_metric_every_n_epochs), 1)) == 0
         for batch in (cache.train_batches(epoch) if cache else dataset.train_dataloader()):
+            stats = ghist.before_step(trainer, model.global_step, epoch) if ghist is not None else False
             if cache:
-                out = cache.step(trainer, batch, metrics=train_metrics)
+                out = cache.step(trainer, batch, metrics=train_metrics, stats=stats)
             else:
-                out = trainer.step(batch["img"].to(dev), batch["boxes"], batch["labels"], metrics=train_metrics)
+                out = trainer.step(batch["img"].to(dev), batch["boxes"], batch["labels"], metrics=train_metrics, stats=stats)
             if shard_log is not None:
                 shard_log.write(json.dumps({"step": model.global_step, "epoch": epoch, "subjects": list(batch["subject"]),
                                             "total_loss/training": out["loss"]}) + "\n")
@@ -292,6 +333,8 @@ def example(args):
         best = keep
         if done or (args.early_stopping and bad_epochs >= 5):
             break
+    if ghist is not None:
+        ghist.close(trainer)
     if log is not None:
         log.close()
     if shard_log is not None:

@@ -11,6 +11,10 @@ API-compatible (autograd) route through the same kernels.
 outputs, then calculate_mAP at IoU 0.1 and 0.5) as two more launches behind the step on the trainer's stream -
 ``msl_detect_objects`` and ``msl_detection_metrics`` (csrc/metrics.hip) - whose per-step values are summed in a device
 accumulator: no host synchronisation per step, one read per epoch (``training_metrics`` / ``metric_sums``).
+
+``step(..., stats=True)`` adds the reference's gradient histograms (ssd3d.py:729-738, ``on_after_backward``) the same way:
+``msl_tensor_stats`` (csrc/tensorstats.hip, ``diagnostics.TensorStats``) over the gradient the optimiser just read and the
+parameters it just wrote, behind the step on the trainer's stream; ``last_stats`` reads the snapshot.
 """
 import collections
 import os
@@ -87,6 +91,10 @@ class FusedTrainer:
         self._met = {}          # (device, N, top_k, G) -> detection workspace + result buffer
         self._met_acc = None    # f64 per-step sums [thr][mAP, precision, recall, f1] ..., steps
         self._met_last = None   # (result buffer, N, top_k, G) of the latest metric step
+        # gradient / parameter histograms (step(..., stats=True)): which flat buffers the pass reads, its device state
+        self.stats_sources = ("grad", "param")
+        self._stats = None       # diagnostics.TensorStats of the current arena
+        self._stats_meta = None  # {"step", "grad_scale"} of the latest stats step
 
     def _reducer(self, arena):
         if self.reducer is None or self.reducer.arena is not arena:
@@ -212,7 +220,7 @@ class FusedTrainer:
         return x, gb, gl, off, cap
 
     def step_packed(self, images, gt_boxes, gt_labels, obj_off, total_objects, sync=True, resident=False, fence=True,
-                    metrics=False):
+                    metrics=False, stats=False):
         """One optimisation step on already packed targets (see MultiBoxLoss.pack_targets).  With ``sync=False``
         nothing is read back: the returned dict holds the device tensor ``loss_out`` = [conf, loc, n_positives].
 
@@ -230,7 +238,10 @@ class FusedTrainer:
         ``torch.cuda.synchronize()`` - before it reads parameters / ``loss_out`` or rewrites the resident inputs.
 
         ``metrics=True``: behind the step, detection on its forward outputs and the detection metrics at
-        ``metric_thresholds`` (see the module docstring); the recorded step program is the same either way."""
+        ``metric_thresholds`` (see the module docstring); the recorded step program is the same either way.
+
+        ``stats=True``: behind the step, per-tensor histograms and moments of ``stats_sources`` (``last_stats``); never
+        recorded into the program either, no host synchronisation."""
         m = self.model
         if not images.is_cuda:
             raise _lib.HipKernelError("FusedTrainer runs on the HIP device only (no CPU fallback)")
@@ -315,6 +326,8 @@ class FusedTrainer:
                     _lib.replay_native(entry["native"])
             if metrics:  # after the step's launches (never recorded into its program), on the same stream
                 self._enqueue_metrics(pl, gt_boxes, gt_labels, obj_off, n_objects, dev)
+            if stats:  # likewise: the gradient arena still holds what the optimiser read (msl_adam_step takes it as const)
+                self._enqueue_stats(arena, red, stream)
         if not unfenced:
             caller.wait_stream(self._stream)
         self.last_plan = pl
@@ -383,14 +396,33 @@ class FusedTrainer:
         host = out.cpu().numpy()
         return tuple(metric_details(host, n_thr, D, G, t) for t in range(n_thr))
 
+    def _enqueue_stats(self, arena, red, stream):
+        from .diagnostics import TensorStats
+        if self._stats is None or self._stats.arena is not arena or self._stats.sources != tuple(self.stats_sources):
+            self._stats = TensorStats(arena, self.stats_sources, optimizer=self.opt)
+        self._stats.enqueue(stream)
+        self._stats_meta = {"step": int(self.model.global_step), "grad_scale": 1.0 / red.world}
+
+    def last_stats(self):
+        """The latest ``stats=True`` step as {"step", "grad_scale", "tensors": {name: {source: {count, nonfinite, zeros, min,
+        max, mean, rms, l1, hist}}}} (None before the first one): a fence and one device copy.  ``step`` is the model's
+        ``global_step`` the step started from (what the reference's ``on_after_backward`` sees).  The "grad" source is the raw
+        gradient arena - under data parallelism the SUM over the ranks; ``grad_scale`` (1 / world) turns it into the mean the
+        optimiser applied.  "param" is the parameters AFTER that step's update.  Later steps without ``stats`` leave the
+        snapshot alone."""
+        if self._stats is None or self._stats_meta is None:
+            return None
+        self.fence()
+        return dict(self._stats_meta, tensors=self._stats.read())
+
     def fence(self):
         """Order the caller's current stream behind every step enqueued so far (after ``step_packed(..., fence=False)``)."""
         if self._stream is not None:
             torch.cuda.current_stream(self._stream.device).wait_stream(self._stream)
 
-    def step(self, images, boxes, labels, sync=True, metrics=False):
+    def step(self, images, boxes, labels, sync=True, metrics=False, stats=False):
         gb, gl, off, T = MultiBoxLoss.pack_targets(boxes, labels, images.device)
-        return self.step_packed(images, gb, gl, off, T, sync=sync, metrics=metrics)
+        return self.step_packed(images, gb, gl, off, T, sync=sync, metrics=metrics, stats=stats)
 
     def state_dict(self):
         return {"optimizer": self.opt.state_dict(), "scheduler": None if self.sch is None else self.sch.state_dict()}

@@ -24,6 +24,8 @@ BN_ROWS = 8  # scale, shift, mean, invstd, c1, c2, cC, cE (the last two: msl_bn_
 # a depthwise output's only consumer is the pointwise GEMM of its block (one fold per wave, 32-64 channels wide): the
 # BatchNorm of a depthwise output is folded into it up to this many partials per channel (block 1's depthwise emits 64)
 FOLD_NP_MAX_PW = 64
+# the bf16 step (plan_folds): the floor of its threshold for y, and what its pointwise GEMM folds (partials, input channels)
+BF16_FOLD_NP_FLOOR, BF16_FOLD_NP_MAX_PW, BF16_FOLD_CIN_MAX_PW = 64, 64, 1024
 # a channel link (csrc/chanlink.hip) also produces the depthwise weight gradient while it has at most this many waves per
 # channel (with more it is bound by instruction issue; the stride-2 forms above 4 waves also spill)
 LINK_BWW_MAX_WAVES = 4
@@ -106,6 +108,53 @@ def plan_routes(pl, engine):
     bnapply = bf16 or (y_np is not None and specs[0]["cout"] == 32)
     routes[0] = StemRoute("link" if linked else "bn", y_np, "fused" if fuse_stem else "bnapply" if bnapply else "plain")
     return routes
+
+
+class Fold(typing.NamedTuple):
+    """What a train-mode forward pass does with the BatchNorms of feature index i: ``Plan.folds.at[i]``."""
+    dw: bool       # block i+1's depthwise layer rebuilds (scale, shift) of y[i] from the statistics partials
+    copy: bool     # y[i] is a feature map and the copy its head reads does the same
+    chain: object  # msl_bn_finalize of y[i] on the chain: "producer" (right behind the launch that wrote y[i]) or "consumer"
+    #                (right in front of block i+1's depthwise layer); None: in the batched finalize
+    pw: bool       # block i's pointwise layer folds the BatchNorm of z[i]; else it is finalized on the chain in front of it
+
+
+class Folds(typing.NamedTuple):
+    at: list     # Fold per feature index
+    batch: list  # ("y" | "z", i) of the BatchNorms left to the one msl_bn_finalize_batch, in the order of its table
+
+
+NO_FOLD = Fold(False, False, None, False)  # every layer of an eval-mode pass: nothing folds, nothing is finalized
+
+
+def plan_folds(pl, engine):
+    """-> ``Plan.folds``: which BatchNorms a train-mode forward pass folds into their consumers from the statistics partials
+    (no launch between producer and consumer; running statistics and backward vectors come from one batched launch at the
+    end) and where the others are finalized.  All of it follows from the plan's partial counts, ``Engine.fold_bn`` and
+    ``Engine.fold_np_max``; both forward passes launch what it says."""
+    L = _lib.load()
+    specs, last = engine.layer_specs, len(engine.layer_specs) - 1
+    at = []
+    for i, sp in enumerate(specs):
+        feat = i in pl.feat_ids
+        if pl.bf16:  # (Engine.fold_bn is not consulted)
+            y_max = max(BF16_FOLD_NP_FLOOR, engine.fold_np_max)
+            copy = feat and pl.f32_heads and pl.np_y[i] <= y_max
+            # (a feature map that is finalized for its copy has its vectors: the depthwise layer reads them)
+            dw = (i < last and pl.np_y[i] <= y_max and (copy or not feat)
+                  and L.msl_dwconv_wave_num_partials(pl.N, specs[i + 1]["cin"], *pl.dims[i], specs[i + 1]["stride"][0]) > 0)
+            if feat:  # "consumer": the copy folded, the depthwise layer cannot
+                chain = "producer" if not copy else None if dw or i == last else "consumer"
+            else:
+                chain = None if dw else "consumer"
+            pw = i > 0 and pl.np_z[i] <= BF16_FOLD_NP_MAX_PW and sp["cin"] <= BF16_FOLD_CIN_MAX_PW
+        else:
+            fold = engine.fold_bn or pl.np_y[i] <= engine.fold_np_max
+            dw, copy, chain = fold and i < last, fold and feat, None if fold else "producer"
+            pw = i > 0 and (engine.fold_bn or pl.np_z[i] <= FOLD_NP_MAX_PW)
+        at.append(Fold(dw, copy, chain, pw))
+    batch = [(k, i) for i, f in enumerate(at) for k in ("z", "y") if (f.pw if k == "z" else f.chain is None)]
+    return Folds(at, batch)
 
 
 class ParamArena:
@@ -201,8 +250,9 @@ class Plan:
     """Buffers + static shape data for one (batch, input size, mode, storage type).  ``dtype`` ("f32" / "bf16",
     ``LSSD3D.compute_dtype``) is how raw convolution outputs and activation gradients are stored in HBM; weights, BatchNorm
     vectors / statistics, head inputs and outputs and weight-gradient sums are fp32 / fp64 either way.  What the bf16 step
-    lays out differently is in the branches on ``bf16`` below; every other line serves both.  A training plan also holds the
-    kernel routes of its backward pass (``routes``: see ``plan_routes``), fixed like its buffers when it is built."""
+    lays out differently is in the branches on ``bf16`` below; every other line serves both.  A plan also holds the BatchNorm
+    folds of its forward pass (``folds``: see ``plan_folds``) and a training plan the kernel routes of its backward pass
+    (``routes``: see ``plan_routes``), fixed like its buffers when it is built."""
 
     def __init__(self, engine, N, in_dims, device, need_grad, dtype="f32"):
         L = _lib.load()
@@ -366,6 +416,8 @@ class Plan:
         self.grad_tables = {}       # Engine._grad_reduce
         # the backward pass, decided once: what Engine.backward / _backward_bf16 launch and Engine._grad_reduce folds
         self.routes = plan_routes(self, engine) if need_grad else None  # [StemRoute, Route of block 1, ...]
+        # and the BatchNorm folds of a train-mode forward pass (an eval-mode pass folds nothing and finalizes nothing)
+        self.folds = plan_folds(self, engine)
 
 
 class Engine:
@@ -375,14 +427,16 @@ class Engine:
       weight / data gradients run beside the backward of blocks 7..4;
     * ``wgrad``  — every pointwise / depthwise weight gradient runs beside the next layer's data-gradient chain.
     Forks and joins are hipEvents recorded through the C ABI, so the schedule survives launch-program replay.
-    Which kernel form carries each piece of the backward pass is fixed per plan (``Plan.routes``); ``backward`` and
-    ``_backward_bf16`` only decide per call what the caller can change between calls (streams, reducer stages, batching)."""
+    Which kernel form carries each piece of the backward pass is fixed per plan (``Plan.routes``), and so is which
+    BatchNorms the forward pass folds into their consumers (``Plan.folds``); the four passes only decide per call what the
+    caller can change between calls (train / eval mode, streams, reducer stages, batching)."""
 
     def __init__(self, model):
         self.model = model
         # ---- schedule options: plain attributes (defaults = what the measurements of rounds 1-3 chose; probes and
         #      `bench.py --opt name=value` set them; the library reads no environment variable for any of them) ------------
         self.multi_stream = True
+        # (fold_bn, fold_np_max, bf16_heads and fuse_stem are baked into a plan when it is built: see plan_for)
         self.fold_bn = False      # fold EVERY BatchNorm into its consumers (slower: big layers have thousands of partials)
         # fold only the BatchNorms with at most this many statistics partials per channel into their depthwise / pointwise
         # consumers (one finalize launch less on the chain each; a folded stem BatchNorm - 1024 partials - costs block 1's
@@ -429,7 +483,7 @@ class Engine:
         dtype = getattr(self.model, "compute_dtype", "f32")
         bf16 = dtype == "bf16"
         key = (dtype, x.shape[0], tuple(x.shape[2:]), x.device, need_grad, self.bf16_heads if bf16 else None,
-               self.fuse_stem if need_grad else None)
+               self.fuse_stem if need_grad else None, self.fold_bn, self.fold_np_max)
         p = self.plans.get(key)
         if p is None:
             p = self.plans[key] = Plan(self, x.shape[0], x.shape[2:], x.device, need_grad, dtype)
@@ -513,30 +567,64 @@ class Engine:
             cb(tag)
             _lib.record_hook(lambda: cb(tag), tag=f"hook:{tag}")
 
-    def _bn_fwd(self, bn, vec, partials, NP, count, training, st):
-        C = vec.shape[1]
-        if training:
-            mom = 0.1 if bn.momentum is None else bn.momentum
-            _lib.call("msl_bn_finalize", ptr(partials), NP, float(count), ptr(bn.weight), ptr(bn.bias),
-                      ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked), mom, bn.eps,
-                      ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]), C, st)
-        else:
-            _lib.call("msl_bn_eval_affine", ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
-                      bn.eps, ptr(vec[0]), ptr(vec[1]), C, st)
+    def _bn_entry(self, pl, kind, i):
+        """(bn module, vector buffer, statistics partials, NP, element count) of the BatchNorm of y[i] ("y") or z[i] ("z")."""
+        feats = self.model.base.features
+        D, H, W = pl.dims[i]
+        if kind == "z":
+            return feats[i].bn1, pl.bn_z[i], pl.part_z[i], pl.np_z[i], pl.N * D * H * W
+        return (feats[i].bn2 if i else feats[0][1]), pl.bn_y[i], pl.part_y[i], pl.np_y[i], pl.N * D * H * W
+
+    def _bn_finalize(self, pl, kind, i, st):
+        """One BatchNorm of a train-mode pass finalized by a launch of its own (``Fold.chain`` / not ``Fold.pw``)."""
+        bn, vec, partials, NP, count = self._bn_entry(pl, kind, i)
+        mom = 0.1 if bn.momentum is None else bn.momentum
+        _lib.call("msl_bn_finalize", ptr(partials), NP, float(count), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
+                  ptr(bn.running_var), ptr(bn.num_batches_tracked), mom, bn.eps, ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
+                  ptr(vec[3]), vec.shape[1], st)
+
+    def _forward_prologue(self, pl, training, eval_np, st, stH):
+        """What a forward pass starts with -> the event behind the packed head weights (None: they are on the chain).
+        ``stH`` is the heads stream, or ``st`` for a pass without one; ``eval_np``: the partial counts (of y[i], of z[i]) the
+        eval-mode table is built with."""
+        if not training:
+            # eval mode: (scale, shift) of all BatchNorms depend on parameters and running statistics only - one launch.  It
+            # is the FIRST launch of the pass, in front of the prologue's fork: the fork's record then rides on it as a stop
+            # event instead of being a packet of its own at the head of the chain (the heads stream still starts behind
+            # everything the chain held before this pass)
+            every = []
+            for kind, i in [("y", 0)] + [(k, i) for i in range(1, len(pl.y)) for k in ("z", "y")]:
+                every.append(self._bn_entry(pl, kind, i)[:3] + (eval_np[1 if kind == "z" else 0][i], 1.0))
+            self._finalize_all(pl, every, st, eval_mode=True)
+        # the NaN-flag reset and the MFMA-fragment copies of the head weights (all scales, once per pass) are needed 200 us
+        # into the pass (first head convolution) and at its end (loss / NaN checks): on the heads stream they cost the
+        # dependency chain nothing (in front of the stem they were a memset + a launch + two dispatch gaps, ~20 us).  The
+        # heads stream first waits for everything the chain has done so far (the previous step's optimiser wrote the weights).
+        if stH != st and not self.prologue_presynced:  # (a caller that orders the heads stream itself: FusedTrainer)
+            self._fork(pl, "fwd_start", st, stH)
+        _lib.call("msl_fill_u32", ptr(pl.nan_flag), 0, 1, stH)
+        if pl.f32_heads:  # (the bf16 head kernel packs its weights scale by scale)
+            self._pack_head_weights(pl, stH)
+        return self._record(pl, "head_pack_done", stH) if stH != st else None
+
+    def _forward_epilogue(self, pl, nan_check, st, stH):
+        if stH != st:
+            self._fork(pl, "fwd_heads_done", stH, st)
+        if nan_check:  # the fused training step lets the loss kernel set the flag instead (it reads both tensors anyway)
+            _lib.call("msl_nan_flag2", ptr(pl.locs), pl.locs.numel(), 1, ptr(pl.scores), pl.scores.numel(), 2, ptr(pl.nan_flag), st)
+        return pl.locs, pl.scores
 
     # ------------------------------------------------------------------------------------------------
-    def forward(self, x, training, need_grad, want_features=False, nan_check=True, after_block=None):
-        """x (N,Cin,D,H,W) fp32 on the GPU -> (locs (N,P,6), scores (N,P,n_classes)) [+ dict of feature maps].
+    def forward(self, x, training, need_grad, nan_check=True, after_block=None):
+        """x (N,Cin,D,H,W) fp32 on the GPU -> (locs (N,P,6), scores (N,P,n_classes)).
         ``after_block``: {block index: callable} - side work (the trainer's target matching) to enqueue once that block's
         launches have been issued."""
         if not x.is_cuda:
             raise _lib.HipKernelError("mslesions3d_amd runs on the HIP device only (no CPU fallback): move the "
                                       "model and the input to 'cuda'")
-        L = _lib.load()
         m = self.model
         if getattr(m, "compute_dtype", "f32") == "bf16":
-            return self._forward_bf16(x, training=training, need_grad=need_grad, want_features=want_features,
-                                      nan_check=nan_check, after_block=after_block)
+            return self._forward_bf16(x, training=training, need_grad=need_grad, nan_check=nan_check, after_block=after_block)
         x = x.contiguous().float()
         self.ensure_arena(x.device)
         pl = self.plan_for(x, need_grad)
@@ -548,43 +636,14 @@ class Engine:
         N = pl.N
         feats = m.base.features
         specs = self.layer_specs
-        ev_pack = None
-        if not training:
-            # eval mode: (scale, shift) of all BatchNorms depend on parameters and running statistics only - one launch.  It
-            # is the FIRST launch of the pass, in front of the prologue's fork: the fork's record then rides on it as a stop
-            # event instead of being a packet of its own at the head of the chain (the heads stream still starts behind
-            # everything the chain held before this pass)
-            every = [(feats[0][1], pl.bn_y[0], pl.part_y[0], pl.np_y[0], 1.0)]
-            for i in range(1, len(specs)):
-                every += [(feats[i].bn1, pl.bn_z[i], pl.part_z[i], pl.np_z[i], 1.0),
-                          (feats[i].bn2, pl.bn_y[i], pl.part_y[i], pl.np_y[i], 1.0)]
-            self._finalize_all(pl, every, st, eval_mode=True)
-        if self.multi_stream:
-            # the NaN-flag reset and the MFMA-fragment copies of the head weights are needed 200 us into the pass (first head
-            # convolution) and at its end (loss / NaN checks): on the heads stream they cost the dependency chain nothing
-            # (in front of the stem they were a memset + a launch + two dispatch gaps, ~20 us).  The heads stream first waits
-            # for everything the chain has done so far (the previous step's optimiser wrote the weights).
-            if not self.prologue_presynced:  # (a caller that orders the heads stream itself: FusedTrainer)
-                self._fork(pl, "fwd_start", st, stH)
-            _lib.call("msl_fill_u32", ptr(pl.nan_flag), 0, 1, stH)
-            self._pack_head_weights(pl, stH)
-            ev_pack = self._record(pl, "head_pack_done", stH)
-        else:
-            _lib.call("msl_fill_u32", ptr(pl.nan_flag), 0, 1, st)
-            self._pack_head_weights(pl, st)  # MFMA-fragment copies of the head weights, all scales, once per pass
-
-        fold_max = (1 << 30) if self.fold_bn else self.fold_np_max
-        folds = lambda NP: training and NP <= fold_max  # is the BatchNorm with NP partials folded into its consumers?
-        fold_max_pw = (1 << 30) if self.fold_bn else FOLD_NP_MAX_PW  # (a depthwise output: its pointwise consumer folds it)
-        folds_z = lambda NP: training and NP <= fold_max_pw
+        ev_pack = self._forward_prologue(pl, training, (pl.np_y, pl.np_z), st, stH)
+        # which BatchNorms the consumers fold from the partials, and which a launch on the chain finalizes right behind its
+        # producer: fixed per plan.  The folded ones (bn module, vector buffer, partials, NP, element count) get their running
+        # statistics and backward vectors from ONE launch after the last block: nothing in the forward pass reads them
+        fo = pl.folds.at if training else [NO_FOLD] * len(specs)
+        bn_layers = [self._bn_entry(pl, k, i) for k, i in pl.folds.batch] if training else []
         deferred = []
-        bn_layers = []  # (bn module, vector buffer, partials, NP, element count) of every BatchNorm, in order
         ev_bn_done = None
-
-        def finalize_later(bn, vec, part, NP, count, name):
-            """BatchNorm finalize (running stats + vectors for backward): all layers in ONE launch after the last
-            block — nothing in the forward pass reads its outputs."""
-            bn_layers.append((bn, vec, part, NP, count))
 
         def flush():
             nonlocal deferred
@@ -603,17 +662,8 @@ class Engine:
             self._k("stem_fwd", "msl_stem_conv_fwd", ptr(x), ptr(feats[0][0].weight), ptr(pl.y[0]),
                     ptr(pl.part_y[0]) if training else None, N, specs[0]["cin"], D, H, W, sd, sh, sw, st)
         pl.stem_dw_eval = stem_dw
-        od, oh, ow = pl.dims[0]
-        def bn_done(bn, vec, part, NP, count, name, folded=None):
-            if not training:
-                return  # done above, for all layers at once
-            if folds(NP) if folded is None else folded:
-                finalize_later(bn, vec, part, NP, count, name)
-            else:
-                self._bn_fwd(bn, vec, part, NP, count, training, st)
-
-        bn_done(feats[0][1], pl.bn_y[0], pl.part_y[0], pl.np_y[0], N * od * oh * ow, "stat_y0")
-        out_feats = {}
+        if fo[0].chain:
+            self._bn_finalize(pl, "y", 0, st)
         for i in range(1, len(specs)):
             sp, blk = specs[i], feats[i]
             pd, ph, pw = pl.dims[i - 1]
@@ -623,7 +673,7 @@ class Engine:
             bn_prev = feats[0][1] if i == 1 else feats[i - 1].bn2
             if i == 1 and stem_dw:
                 pass  # z1 came with the stem
-            elif folds(pl.np_y[i - 1]):
+            elif fo[i - 1].dw:
                 self._k(f"dw_fwd{i}", "msl_dwconv_fwd_fold", ptr(pl.y[i - 1]), ptr(pl.part_y[i - 1]), pl.np_y[i - 1],
                         float(N * pd * ph * pw), ptr(bn_prev.weight), ptr(bn_prev.bias), bn_prev.eps, ptr(blk.conv1.weight),
                         ptr(pl.z[i]), ptr(pl.part_z[i]), N, sp["cin"], pd, ph, pw, s, st)
@@ -632,32 +682,29 @@ class Engine:
                         ptr(blk.conv1.weight), ptr(pl.z[i]), ptr(pl.part_z[i]) if training else None, N, sp["cin"], pd, ph,
                         pw, s, 0, st)
             flush()
-            bn_done(blk.bn1, pl.bn_z[i], pl.part_z[i], pl.np_z[i], N * S, f"stat_z{i}", folded=folds_z(pl.np_z[i]))
-            if folds_z(pl.np_z[i]):
+            if fo[i].pw:
                 self._k(f"pw_fwd{i}", "msl_pwconv_fwd_fold", ptr(pl.z[i]), ptr(pl.part_z[i]), pl.np_z[i], float(N * S),
                         ptr(blk.bn1.weight), ptr(blk.bn1.bias), blk.bn1.eps, ptr(blk.conv2.weight), ptr(pl.y[i]),
                         ptr(pl.part_y[i]), N, sp["cin"], sp["cout"], S, st)
             else:
+                if training:
+                    self._bn_finalize(pl, "z", i, st)
                 self._k(f"pw_fwd{i}", "msl_pwconv_fwd", ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]),
                         ptr(blk.conv2.weight), ptr(pl.y[i]), ptr(pl.part_y[i]) if training else None, N, sp["cin"],
                         sp["cout"], S, st)
             flush()
-            bn_done(blk.bn2, pl.bn_y[i], pl.part_y[i], pl.np_y[i], N * S, f"stat_y{i}")
+            if fo[i].chain:
+                self._bn_finalize(pl, "y", i, st)
             ev_feat = None  # the event a side stream waits for at this block, shared by everything forked here
             if i in pl.fpad:
-                plain = None
-                if want_features:
-                    plain = torch.empty((N, sp["cout"], D, H, W), dtype=torch.float32, device=x.device)
-                    out_feats[i] = plain
-
-                def materialize(s_, i=i, sp=sp, blk=blk, plain=plain, D=D, H=H, W=W, S=S):
-                    if folds(pl.np_y[i]):
+                def materialize(s_, i=i, sp=sp, blk=blk, D=D, H=H, W=W, S=S):
+                    if fo[i].copy:
                         self._k(f"materialize{i}", "msl_bn_relu_materialize_fold", ptr(pl.y[i]), ptr(pl.part_y[i]), pl.np_y[i],
-                                float(N * S), ptr(blk.bn2.weight), ptr(blk.bn2.bias), blk.bn2.eps, ptr(plain), ptr(pl.fpad[i]),
+                                float(N * S), ptr(blk.bn2.weight), ptr(blk.bn2.bias), blk.bn2.eps, None, ptr(pl.fpad[i]),
                                 N, sp["cout"], D, H, W, s_)
                     else:
                         self._k(f"materialize{i}", "msl_bn_relu_materialize", ptr(pl.y[i]), ptr(pl.bn_y[i][0]),
-                                ptr(pl.bn_y[i][1]), ptr(plain), ptr(pl.fpad[i]), N, sp["cout"], D, H, W, s_)
+                                ptr(pl.bn_y[i][1]), None, ptr(pl.fpad[i]), N, sp["cout"], D, H, W, s_)
                 # this scale's head convolution only needs the feature map: run it beside the remaining blocks - and with it
                 # the zero-haloed activation copy it reads (nothing on the chain reads that copy: the next depthwise layer
                 # re-creates the activation from the raw output itself), when the BatchNorm is folded from the partials
@@ -681,21 +728,14 @@ class Engine:
         if ev_bn_done is not None:
             self._wait(st, ev_bn_done)
         elif bn_layers:
-            # running statistics and backward vectors of the folded BatchNorms: one launch
             self._finalize_all(pl, bn_layers, st)
-        if self.multi_stream:
-            self._fork(pl, "fwd_heads_done", stH, st)
-        if nan_check:  # the fused training step lets the loss kernel set the flag instead (it reads both tensors anyway)
-            _lib.call("msl_nan_flag2", ptr(pl.locs), pl.locs.numel(), 1, ptr(pl.scores), pl.scores.numel(), 2, ptr(pl.nan_flag), st)
-        if want_features:
-            return pl.locs, pl.scores, out_feats
-        return pl.locs, pl.scores
+        return self._forward_epilogue(pl, nan_check, st, stH)
 
     # ------------------------------------------------------------------------------------------------
-    def _forward_bf16(self, x, training=False, need_grad=False, want_features=False, nan_check=True, after_block=None):
+    def _forward_bf16(self, x, training=False, need_grad=False, nan_check=True, after_block=None):
         """Forward with bf16 activations in HBM (csrc/bf16.hip + the bf16 head kernel): fp32 input volume, fp32 weights and
-        BatchNorm vectors / statistics, bf16 everything in between, fp32 locs / scores out.  One stream (the head
-        convolutions are issued in line)."""
+        BatchNorm vectors / statistics, bf16 everything in between, fp32 locs / scores out.  A BatchNorm that is not folded is
+        finalized in front of the first launch that reads its vectors (``Fold.chain``)."""
         m, specs, feats = self.model, self.layer_specs, self.model.base.features
         x = x.contiguous().float()
         self.ensure_arena(x.device)
@@ -706,31 +746,15 @@ class Engine:
         # heads of the earlier scales beside the backbone: the training step, and inference too when the heads run on the fp32
         # kernels (the bf16 inference pass used to be one stream: 86 us of feature copies and head convolutions on the chain
         # at 192^3 x 2)
-        ms = self.multi_stream and (need_grad or pl.f32_heads)
+        ms = self.multi_stream and pl.f32_heads
         stH = self.side_streams(x.device)[0].cuda_stream if ms else st
         N = pl.N
         ncls = m.n_classes
-        side_prologue = ms and pl.f32_heads  # as in the fp32 forward: off the dependency chain
-        ev_pack = None
-        if not training:  # first launch of the pass, in front of the prologue's fork (see the fp32 pass)
-            every = [(feats[0][1], pl.bn_y[0], pl.part_y[0], 1, 1.0)]
-            for i in range(1, len(specs)):
-                every += [(feats[i].bn1, pl.bn_z[i], pl.part_z[i], 1, 1.0), (feats[i].bn2, pl.bn_y[i], pl.part_y[i], 1, 1.0)]
-            self._finalize_all(pl, every, st, eval_mode=True)
-        if side_prologue:
-            if not self.prologue_presynced:
-                self._fork(pl, "fwd_start", st, stH)
-            _lib.call("msl_fill_u32", ptr(pl.nan_flag), 0, 1, stH)
-            self._pack_head_weights(pl, stH)
-            ev_pack = self._record(pl, "head_pack_done", stH)
-        else:
-            _lib.call("msl_fill_u32", ptr(pl.nan_flag), 0, 1, st)
-        if pl.f32_heads and not side_prologue:  # MFMA-fragment copies of the head weights (forward and, in training, bwd-data)
-            self._pack_head_weights(pl, st)
+        last = len(specs) - 1
+        ones = [1] * len(specs)
+        ev_pack = self._forward_prologue(pl, training, (ones, ones), st, stH)
         part = (lambda t: ptr(t)) if training else (lambda t: None)
-        L = _lib.load()
-        later = []  # BatchNorms folded into their consumer: running statistics + backward vectors in ONE launch at the end
-        folded_feats = set()  # feature maps among them
+        fo = pl.folds.at if training else [NO_FOLD] * len(specs)
         D, H, W = pl.in_dims
         stem_dw = self._stem_dw_eval(specs, training, N, D, H, W)
         if stem_dw:
@@ -740,105 +764,69 @@ class Engine:
             self._k("stem_fwd", "msl_stem_conv_fwd_bf16", ptr(x), ptr(feats[0][0].weight), ptr(pl.y[0]), part(pl.part_y[0]), N,
                     specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
         pl.stem_dw_eval = stem_dw
-        od, oh, ow = pl.dims[0]
-        out_feats = {}
         for i in range(1, len(specs)):
             sp, blk = specs[i], feats[i]
             pd, ph, pw = pl.dims[i - 1]
             D, H, W = pl.dims[i]
             S = D * H * W
             bn_prev = feats[0][1] if i == 1 else feats[i - 1].bn2
-            cnt_prev = N * pd * ph * pw
-            # the consumer rebuilds (scale, shift) from the producer's partials when they are few (<= fold_np_max: every wave /
-            # workgroup repeats the sum) - no finalize launch between the two; feature maps need the vectors anyway
-            # (a feature map whose fp32 copy was made from the partials - folded_feats - is folded here too)
-            fold_y = (training and pl.np_y[i - 1] <= max(64, self.fold_np_max)
-                      and ((i - 1) not in pl.feat_ids or (i - 1) in folded_feats)
-                      and L.msl_dwconv_wave_num_partials(N, sp["cin"], pd, ph, pw, sp["stride"][0]) > 0)
-            if training and not fold_y and (i - 1) in folded_feats:  # the copy folded, this consumer cannot: finalize after all
-                self._bn_fwd(bn_prev, pl.bn_y[i - 1], pl.part_y[i - 1], pl.np_y[i - 1], cnt_prev, True, st)
-                later.pop([id(e[1]) for e in later].index(id(pl.bn_y[i - 1])))
-            elif training and not fold_y and (i - 1) not in pl.feat_ids:  # (a feature map's vectors exist already)
-                self._bn_fwd(bn_prev, pl.bn_y[i - 1], pl.part_y[i - 1], pl.np_y[i - 1], cnt_prev, True, st)
+            # the consumer rebuilds (scale, shift) from the producer's partials when they are few (every wave / workgroup
+            # repeats the sum) - no finalize launch between the two
+            if fo[i - 1].chain == "consumer":
+                self._bn_finalize(pl, "y", i - 1, st)
             if i == 1 and stem_dw:
                 pass  # z1 came with the stem
-            elif fold_y:
-                if (i - 1) not in folded_feats:
-                    later.append((bn_prev, pl.bn_y[i - 1], pl.part_y[i - 1], pl.np_y[i - 1], cnt_prev))
+            elif fo[i - 1].dw:
                 self._k(f"dw_fwd{i}", "msl_dwconv_fwd_wave_bf16_fold", ptr(pl.y[i - 1]), ptr(pl.part_y[i - 1]), pl.np_y[i - 1],
-                        float(cnt_prev), ptr(bn_prev.weight), ptr(bn_prev.bias), bn_prev.eps, ptr(blk.conv1.weight), ptr(pl.z[i]),
-                        ptr(pl.part_z[i]), N, sp["cin"], pd, ph, pw, sp["stride"][0], st)
+                        float(N * pd * ph * pw), ptr(bn_prev.weight), ptr(bn_prev.bias), bn_prev.eps, ptr(blk.conv1.weight),
+                        ptr(pl.z[i]), ptr(pl.part_z[i]), N, sp["cin"], pd, ph, pw, sp["stride"][0], st)
             else:
                 self._k(f"dw_fwd{i}", "msl_dwconv_fwd_bf16", ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]), ptr(pl.bn_y[i - 1][1]),
                         ptr(blk.conv1.weight), ptr(pl.z[i]), part(pl.part_z[i]), N, sp["cin"], pd, ph, pw, sp["stride"][0], st)
-            fold_z = training and pl.np_z[i] <= 64 and sp["cin"] <= 1024
-            if fold_z:
-                later.append((blk.bn1, pl.bn_z[i], pl.part_z[i], pl.np_z[i], N * S))
+            if fo[i].pw:
                 self._k(f"pw_fwd{i}", "msl_pwconv_fwd_bf16_fold", ptr(pl.z[i]), ptr(pl.part_z[i]), pl.np_z[i], float(N * S),
                         ptr(blk.bn1.weight), ptr(blk.bn1.bias), blk.bn1.eps, ptr(blk.conv2.weight), ptr(pl.y[i]),
                         ptr(pl.part_y[i]), N, sp["cin"], sp["cout"], S, st)
             else:
                 if training:
-                    self._bn_fwd(blk.bn1, pl.bn_z[i], pl.part_z[i], pl.np_z[i], N * S, True, st)
+                    self._bn_finalize(pl, "z", i, st)
                 self._k(f"pw_fwd{i}", "msl_pwconv_fwd_bf16", ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]),
                         ptr(blk.conv2.weight), ptr(pl.y[i]), part(pl.part_y[i]), N, sp["cin"], sp["cout"], S, st)
             if after_block and i in after_block:
                 after_block[i](None)
             # a feature map's BatchNorm: folded into the fp32 copy (and into the next depthwise layer) from the partials when
             # they are few - no finalize launch on the chain; else finalised here (the copy below reads the vectors)
-            fold_feat = (training and i in pl.feat_ids and pl.f32_heads and pl.np_y[i] <= max(64, self.fold_np_max)
-                         and not want_features)
-            if fold_feat:
-                folded_feats.add(i)
-                later.append((blk.bn2, pl.bn_y[i], pl.part_y[i], pl.np_y[i], N * S))
-            elif training and i in pl.feat_ids:
-                self._bn_fwd(blk.bn2, pl.bn_y[i], pl.part_y[i], pl.np_y[i], N * S, True, st)
+            if fo[i].chain == "producer":
+                self._bn_finalize(pl, "y", i, st)
             if i in pl.feat_ids and pl.f32_heads:
                 # the fp32 zero-haloed copy only feeds this scale's head convolution: it goes to the heads stream with it
-                # (as in the fp32 pass; 6-8 us per scale off the chain) unless the caller wants the feature map back
-                beside = ms and i != len(specs) - 1
-                on_side = beside and not want_features
-                if on_side:
+                # (as in the fp32 pass; 6-8 us per scale off the chain)
+                sF = stH if i != last else st
+                if sF != st:
                     self._fork(pl, f"fwd_feat{i}", st, stH)
-                if fold_feat:
+                if fo[i].copy:
                     self._k(f"materialize{i}", "msl_bn_relu_materialize_bf16_pad32_fold", ptr(pl.y[i]), ptr(pl.part_y[i]),
                             pl.np_y[i], float(N * S), ptr(blk.bn2.weight), ptr(blk.bn2.bias), blk.bn2.eps, ptr(pl.fpad[i]), N,
-                            sp["cout"], D, H, W, stH if on_side else st)
+                            sp["cout"], D, H, W, sF)
                 else:
                     self._k(f"materialize{i}", "msl_bn_relu_materialize_bf16_pad32", ptr(pl.y[i]), ptr(pl.bn_y[i][0]),
-                            ptr(pl.bn_y[i][1]), ptr(pl.fpad[i]), N, sp["cout"], D, H, W, stH if on_side else st)
-                if want_features:
-                    out_feats[i] = pl.fpad[i][:, :, 1:-1, 1:-1, 1:-1].clone()
-                if beside:  # beside the next blocks, on the heads stream
-                    if not on_side:
-                        self._fork(pl, f"fwd_feat{i}", st, stH)
-                    self._head_forward(pl, i, stH)
-                else:
-                    if ev_pack is not None:  # the packed weights come from the heads stream
-                        self._wait(st, ev_pack)
-                        ev_pack = None
-                    self._head_forward(pl, i, st)
+                            ptr(pl.bn_y[i][1]), ptr(pl.fpad[i]), N, sp["cout"], D, H, W, sF)
+                if sF == st and ev_pack is not None:  # the packed weights come from the heads stream
+                    self._wait(st, ev_pack)
+                    ev_pack = None
+                self._head_forward(pl, i, sF)
             elif i in pl.feat_ids:
-                plain = None
-                if want_features:
-                    plain = out_feats[i] = torch.empty((N, sp["cout"], D, H, W), dtype=torch.float32, device=x.device)
                 self._k(f"materialize{i}", "msl_bn_relu_materialize_bf16", ptr(pl.y[i]), ptr(pl.bn_y[i][0]), ptr(pl.bn_y[i][1]),
-                        ptr(plain), ptr(pl.fpad_cl[i]), N, sp["cout"], D, H, W, st)
+                        None, ptr(pl.fpad_cl[i]), N, sp["cout"], D, H, W, st)
                 k = pl.feat_ids.index(i)
                 lc, cc = m.pred_convs.loc_convs[k], m.pred_convs.cl_convs[k]
                 self._k(f"head_pack{i}", "msl_head_pack_weights_bf16", ptr(lc.weight), ptr(cc.weight), ptr(pl.Wp[i]), sp["cout"],
                         ncls, st)
                 self._k(f"head_fwd{i}", "msl_head_conv_fwd_bf16", ptr(pl.fpad_cl[i]), ptr(pl.Wp[i]), ptr(lc.bias), ptr(cc.bias),
                         ptr(pl.locs), ptr(pl.scores), N, sp["cout"], D, H, W, pl.P, pl.prior_off[i], ncls, st)
-        if training and later:
-            self._finalize_all(pl, later, st)
-        if ms:
-            self._fork(pl, "fwd_heads_done", stH, st)
-        if nan_check:
-            _lib.call("msl_nan_flag2", ptr(pl.locs), pl.locs.numel(), 1, ptr(pl.scores), pl.scores.numel(), 2, ptr(pl.nan_flag), st)
-        if want_features:
-            return pl.locs, pl.scores, out_feats
-        return pl.locs, pl.scores
+        if training and pl.folds.batch:  # running statistics and backward vectors of the folded BatchNorms: one launch
+            self._finalize_all(pl, [self._bn_entry(pl, k, i) for k, i in pl.folds.batch], st)
+        return self._forward_epilogue(pl, nan_check, st, stH)
 
     def _bn_bwd_bf16(self, g, y, vec, bn_name, N, C, S, pl, st, pre_np=None):
         """In place: g (bf16, = dL/d relu(bn(y))) becomes dL/dy; dgamma / dbeta into the gradient arena.

@@ -578,7 +578,7 @@ def test_fuse_stem_set_between_two_passes_takes_effect_in_every_gradient():
 # the fields Plan.__init__ declares for the methods that write them later, and the fields only one of the two builders set,
 # which every plan has now (empty / constant where they do not apply).
 PLAN_DECLARED = {"bf16", "trained_mode", "stem_dw_eval", "loss_fold", "bn_table", "pwb_key", "pwb_args", "pack_key", "pack_args",
-                 "gpack_key", "gpack_args", "grad_tables", "routes", "pw_fused", "dw_fused_part", "f32_heads"}
+                 "gpack_key", "gpack_args", "grad_tables", "routes", "folds", "pw_fused", "dw_fused_part", "f32_heads"}
 PLAN_ZEROED = ("fpad", "fpad_cl", "dO", "bn_y", "bn_z", "nan_flag")  # kernels rely on their initial zeros (halos, flag)
 
 
@@ -609,7 +609,9 @@ def test_step_program_is_the_recorded_one(name):
     host addresses by order of first appearance) - is the one tests/golden/step_programs.json recorded before the backward
     passes took their kernel routes from Plan.routes; `python -m tests.golden.make_step_programs --dump` prints the full
     programs of a commit for a diff.  And the routes agree with the plan: every buffer they send a weight gradient to is
-    the plan's buffer of that kernel form, so no gradient has two sources or none."""
+    the plan's buffer of that kernel form, so no gradient has two sources or none.  So do the forward folds (Plan.folds):
+    a launch takes its folding form exactly where they say so, and every BatchNorm is finalized exactly once - by a launch
+    of its own on the chain or in the batched one."""
     from mslesions3d_amd.engine import DW_BWW
     with open(os.path.join(GOLDEN_DIR, "step_programs.json")) as f:
         want = json.load(f)[name]
@@ -644,11 +646,41 @@ def test_step_program_is_the_recorded_one(name):
         assert (r.bn2 == "link") == (nxt in ("link", "link_bww")) and (r.y_np is not None) <= (nxt in ("fused_stem", "s2_bww", "bnreduce", "s2_patch"))
     assert (pl.routes[0].bn == "link") == (pl.routes[1].dw in ("link", "link_bww"))
     assert (pl.routes[0].wgrad == "fused") == (pl.routes[1].dw == "fused_stem")
+    calls = {e[2]: e[1] for e in prog if e[0] != "hook"}  # tag -> entry point
+    at, nb = pl.folds.at, len(pl.y)
+    assert len(at) == nb and all(f.chain in (None, "producer", "consumer") for f in at) and not at[0].pw and not at[-1].dw
+    for i in range(1, nb):
+        assert calls[f"dw_fwd{i}"].endswith("_fold") == at[i - 1].dw, f"dw_fwd{i}"
+        assert calls[f"pw_fwd{i}"].endswith("_fold") == at[i].pw, f"pw_fwd{i}"
+    for i in range(nb):
+        assert (f"materialize{i}" in calls) == (i in pl.feat_ids)
+        assert calls.get(f"materialize{i}", "").endswith("_fold") == at[i].copy, f"materialize{i}"
+    chain = [("y", i) for i in range(nb) if at[i].chain is not None] + [("z", i) for i in range(1, nb) if not at[i].pw]
+    assert sum(e[1] == "msl_bn_finalize" for e in prog if e[0] != "hook") == len(chain)
+    assert ("bn_finalize_all" in calls) == bool(pl.folds.batch)
+    assert sorted(chain + list(pl.folds.batch)) == sorted([("y", i) for i in range(nb)] + [("z", i) for i in range(1, nb)])
+
+
+@pytest.mark.parametrize("name", list(step_programs.eval_cases().keys()))
+def test_eval_program_is_the_recorded_one(name):
+    """The same for a bare eval-mode forward pass (fp32, bf16 on either head route, and a shape the one-launch stem +
+    block-1 depthwise kernel refuses): the recorded program, in which nothing folds and nothing is finalized."""
+    with open(os.path.join(GOLDEN_DIR, "step_programs.json")) as f:
+        want = json.load(f)[name]
+    prog, pl = step_programs.record_eval(step_programs.eval_cases()[name], DEV)
+    got = step_programs.summary(prog)
+    assert got["entries"] == want["entries"]
+    assert got["sha256"] == want["sha256"], "same launches, other arguments"
+    names = [e[1] for e in prog if e[0] != "hook"]
+    assert not any(n.endswith("_fold") or n.startswith("msl_bn_finalize") for n in names)
+    assert names.count("msl_bn_eval_affine_batch") == 1 and not pl.trained_mode
+    assert pl.stem_dw_eval == any(n.startswith("msl_stem_dw_fwd_eval") for n in names) == (name != "eval-32x32x96x2-f32")
 
 
 def test_a_changed_build_time_option_builds_a_new_plan():
-    """A bf16 plan bakes Engine.bf16_heads in when it is built, and every training plan Engine.fuse_stem: both are part of
-    the cache key, so setting one later gives a plan with the buffers (and routes) of the new value, not the cached one."""
+    """A bf16 plan bakes Engine.bf16_heads in when it is built, every training plan Engine.fuse_stem and every plan the fold
+    options Engine.fold_bn / fold_np_max: all are part of the cache key, so setting one later gives a plan with the buffers
+    (and routes, and folds) of the new value, not the cached one."""
     m = hip_model()
     m.compute_dtype = "bf16"
     eng = m._engine
@@ -664,6 +696,23 @@ def test_a_changed_build_time_option_builds_a_new_plan():
     eng.fuse_stem = False
     t1 = eng.plan_for(x, True)
     assert t1 is not t0 and t1.fused_stem_np < 0 and t1.g_y[0] is not None
+    m.compute_dtype = "f32"
+    f0 = eng.plan_for(x, True)  # (fold_np_max = 512: the stem's 512 partials and everything after fold)
+    assert eng.plan_for(x, True) is f0 and f0.np_y[0] == eng.fold_np_max == 512 and f0.np_y[1] == 64
+    assert f0.folds.at[0].dw and f0.folds.at[0].chain is None and ("y", 0) in f0.folds.batch
+    eng.fold_np_max = 64
+    f1 = eng.plan_for(x, True)
+    assert f1 is not f0 and not f1.folds.at[0].dw and f1.folds.at[0].chain == "producer" and ("y", 0) not in f1.folds.batch
+    assert f1.folds.at[1].dw and ("y", 1) in f1.folds.batch
+    eng.fold_np_max = 0
+    f2 = eng.plan_for(x, True)
+    assert f2 is not f0 and f2 is not f1 and not any(f.dw or f.copy for f in f2.folds.at)
+    assert f2.folds.batch == [("z", i) for i in range(1, len(f2.y))]  # (a depthwise output's fold has its own threshold)
+    eng.fold_bn = True
+    f3 = eng.plan_for(x, True)
+    assert f3 is not f2 and f3.folds.batch == f0.folds.batch and all(f.chain is None for f in f3.folds.at)
+    eng.fold_bn, eng.fold_np_max = False, 512
+    assert eng.plan_for(x, True) is f0
 
 
 def test_engine_schedule_options_agree():

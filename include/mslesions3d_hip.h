@@ -439,6 +439,23 @@ int msl_evaluate_froc(const void* eval_workspace, size_t eval_workspace_bytes, c
                       int G, int n_iou, const int* gt_count, const int* weights, int R1, const long long* rates,
                       int n_rates, long long* out, void* stream);
 
+/* ---- sensitivity and false positives by lesion size from a completed msl_evaluate_detections call ("Eval by
+ * lesion size"): eval_workspace / eval_out are that call's workspace and result buffer, D, N, G, n_iou, n_sc its sizes and
+ * det_rows, obj_off its inputs, on the same stream; all of them are only read.  The size of a box is its bounding-box
+ * volume in f32 (utils.volume: the volumes (G) of eval_out for ground truth, the same expression on det_rows for a
+ * detection) times voxels[image] in f64, one rounded multiply; voxels (N) f64 > 0.  edges (n_edges) f64, finite, strictly
+ * ascending, n_edges <= 15 (more -> -2): stratum = number of edges <= size, n_edges + 1 strata; a NaN size is unbinned.
+ * weights (R1, N) i32 >= 0 as for msl_evaluate_froc.  cuts (R1, n_iou, n_cuts) i64: prefix lengths of the rank order
+ * (clamped to 0 .. K), in any order, repeats allowed, n_cuts <= 32 (more -> -2).  strata_workspace: 5 * (D + G) bytes,
+ * 4-byte aligned, overwritten.  With S1 = n_edges + 2 slots per cut (the strata, then the unbinned slot), out (i64):
+ * (R1, n_iou, n_cuts, S1, 2) [TPw, FPw] | (R1, S1) Gw_s | (R1, 2) [unbinned class-1 detections, Nw], where per slot s
+ * TPw = sum over class-1 boxes g of w[img(g)] [claim rank of g < cut], FPw = sum over ranks j < cut of w[img(j)] (1 - tp[j]),
+ * Gw_s = sum over class-1 boxes of w[img(g)].  Integer arithmetic only.  Null or inconsistent arguments -> -1. */
+int msl_evaluate_strata(const void* eval_workspace, size_t eval_workspace_bytes, const float* eval_out, int D, int N, int G,
+                        int n_iou, int n_sc, const float* det_rows, const int* obj_off, const double* voxels,
+                        const double* edges, int n_edges, const int* weights, int R1, const long long* cuts, int n_cuts,
+                        void* strata_workspace, size_t strata_workspace_bytes, long long* out, void* stream);
+
 /* ---- device-resident training data (csrc/datapipe.hip, devicedata.py): the host pipeline of datasets._Cases ----------
  * msl_normalize_nonzero: NormalizeIntensity(nonzero=True) in place on n_volumes contiguous f32 volumes of `voxels` each:
  * population mean / std of the non-zero voxels (f64, fixed order), std 0 -> 1, zeros stay zero, all-zero unchanged.

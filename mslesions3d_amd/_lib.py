@@ -132,6 +132,7 @@ _SIGNATURES = {
     "msl_evaluate_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "msl_evaluate_detections": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _Z, _P, _P]),
     "msl_evaluate_froc": (_I, [_P, _Z, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "msl_evaluate_strata": (_I, [_P, _Z, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _Z, _P, _P]),
     "msl_normalize_nonzero": (_I, [_P, _I, _Q, _P]),
     "msl_augment_resample": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_augment_affine": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),

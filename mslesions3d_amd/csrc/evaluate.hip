@@ -620,12 +620,172 @@ __global__ __launch_bounds__(EV_THREADS) void ev_froc_kernel(
   }
 }
 
+// ---- strata: TPw / FPw per lesion-size bin at given cuts of the rank order ("Eval by lesion size"), the second
+// read-only consumer of a completed sweep.  Two launches on the caller's stream:
+//   stratify : one thread per rank and per ground-truth box: the bounding-box volume in f32 (utils.volume, this file is
+//              compiled without contraction), times the voxel count of its image's frame in f64, counted against the edges
+//   count    : one workgroup per (weights row, IoU threshold): the cuts are sorted in LDS; an element (a ground-truth box
+//              with its claim rank, a false positive with its rank) adds its weight to the accumulator of (number of cuts
+//              <= its rank, stratum); a running sum over the sorted cuts then gives every cut.  64-bit integer LDS
+//              atomics: exact and order-free.
+constexpr int EV_STRATA_MAX_EDGES = 15;  // utils.STRATA_MAX_EDGES
+constexpr int EV_STRATA_MAX_CUTS = 32;   // utils.STRATA_MAX_CUTS
+constexpr int EV_STRATA_SLOTS = EV_STRATA_MAX_EDGES + 2;  // up to 16 strata and the unbinned slot
+constexpr int STRATUM_NAN = -1, STRATUM_SKIP = -2;        // NaN volume: unbinned; not class 1 / not of any image: ignored
+
+__device__ __forceinline__ float box_volume(const float* b) {  // utils.py:152-154
+  return (b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);
+}
+
+// number of edges <= v; NaN -> STRATUM_NAN
+__device__ __forceinline__ int stratum_of(float vol, double voxels, const double* __restrict__ edges, int m) {
+  const double v = (double)vol * voxels;
+  if (v != v) return STRATUM_NAN;
+  int s = 0;
+  for (int j = 0; j < m; ++j) s += edges[j] <= v ? 1 : 0;
+  return s;
+}
+
+// grid cdiv(max(D, G), EV_THREADS).  rk_img / rk_str: image and stratum of the detection at every rank < K (0 /
+// STRATUM_SKIP behind K); gt_img / gt_str: the same per ground-truth box
+__global__ __launch_bounds__(EV_THREADS) void ev_stratify_kernel(
+    const float* __restrict__ det_rows, const int* __restrict__ order, const int* __restrict__ img_of,
+    const int* __restrict__ hdr, int D, int N, const int* __restrict__ obj_off, const int* __restrict__ claim0,
+    const float* __restrict__ gt_vol, int G, const double* __restrict__ voxels, const double* __restrict__ edges, int m,
+    int* __restrict__ rk_img, signed char* __restrict__ rk_str, int* __restrict__ gt_img, signed char* __restrict__ gt_str) {
+  const int i = blockIdx.x * EV_THREADS + threadIdx.x;
+  const int K = min(max(hdr[1], 0), D);
+  if (i < D) {
+    int n = 0, s = STRATUM_SKIP;
+    if (i < K) {
+      const int d = min(max(order[i], 0), D - 1);
+      n = min(max(img_of[d], 0), N - 1);
+      s = stratum_of(box_volume(det_rows + (size_t)d * 8), voxels[n], edges, m);
+    }
+    rk_img[i] = n;
+    rk_str[i] = (signed char)s;
+  }
+  if (i < G) {
+    int lo = 0, hi = N;  // the image n with obj_off[n] <= i < obj_off[n + 1]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (obj_off[mid] <= i) lo = mid;
+      else hi = mid;
+    }
+    const bool counts = claim0[i] >= 0 && i >= obj_off[lo] && i < obj_off[lo + 1];  // class 1 and inside its image
+    gt_img[i] = lo;
+    gt_str[i] = (signed char)(counts ? stratum_of(gt_vol[i], voxels[lo], edges, m) : STRATUM_SKIP);
+  }
+}
+
+__device__ __forceinline__ void lds_add_i64(long long* p, long long v) {
+  atomicAdd((unsigned long long*)p, (unsigned long long)v);
+}
+
+// number of sorted cuts <= r: an element of rank r lies inside exactly the cuts from that position on
+__device__ __forceinline__ int cuts_upto(const int* sc, int n, int r) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sc[mid] <= r) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// grid (R1, n_iou).  S1 = strata + 1 (the last slot is the unbinned one).
+// out: (R1, n_iou, n_cuts, S1, 2) [TPw, FPw] | (R1, S1) Gw_s | (R1, 2) [unbinned detections, Nw]
+__global__ __launch_bounds__(EV_THREADS) void ev_strata_count_kernel(
+    const int* __restrict__ tpf, const int* __restrict__ claim, const int* __restrict__ hdr, int D, int N, int G,
+    const int* __restrict__ rk_img, const signed char* __restrict__ rk_str, const int* __restrict__ gt_img,
+    const signed char* __restrict__ gt_str, const int* __restrict__ weights, const long long* __restrict__ cuts, int n_cuts,
+    int S1, long long* __restrict__ out) {
+  __shared__ long long acc[EV_STRATA_MAX_CUTS * EV_STRATA_SLOTS * 2];
+  __shared__ long long gws[EV_STRATA_SLOTS], tail[2];
+  __shared__ int raw[EV_STRATA_MAX_CUTS], sc[EV_STRATA_MAX_CUTS], pos[EV_STRATA_MAX_CUTS];
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x, t = blockIdx.y, n_iou = gridDim.y, R1 = gridDim.x;
+  const int K = min(max(hdr[1], 0), D);
+  const int* __restrict__ w = weights + (size_t)row * N;
+  const int cell = S1 * 2;  // accumulators of one cut interval
+  for (int q = tid; q < n_cuts * cell; q += EV_THREADS) acc[q] = 0;
+  if (tid < EV_STRATA_SLOTS) gws[tid] = 0;
+  if (tid < 2) tail[tid] = 0;
+  if (tid < n_cuts) {
+    const long long c = cuts[((size_t)row * n_iou + t) * n_cuts + tid];
+    raw[tid] = (int)min(max(c, 0LL), (long long)K);
+  }
+  __syncthreads();
+  if (tid < n_cuts) {  // stable counting sort of at most 32 cuts
+    const int c = raw[tid];
+    int p = 0;
+    for (int q = 0; q < n_cuts; ++q) p += (raw[q] < c || (raw[q] == c && q < tid)) ? 1 : 0;
+    pos[tid] = p;
+    sc[p] = c;
+  }
+  __syncthreads();
+  const int top = sc[n_cuts - 1];  // the longest prefix any cut asks for
+  const bool first = t == 0;       // the per-row results are written by the workgroup of the first threshold
+
+  // ground truth: Gw_s, and TPw through the claim rank
+  const int* __restrict__ cl = claim + (size_t)t * G;
+  for (int g = tid; g < G; g += EV_THREADS) {
+    const int s = gt_str[g];
+    if (s == STRATUM_SKIP) continue;
+    const long long wi = w[min(max(gt_img[g], 0), N - 1)];
+    if (wi == 0) continue;
+    const int slot = s < 0 ? S1 - 1 : min(s, S1 - 2);
+    if (first) lds_add_i64(&gws[slot], wi);
+    const int c = cl[g];
+    if (c < 0) continue;
+    const int i = cuts_upto(sc, n_cuts, c);  // NEVER lies behind every cut
+    if (i < n_cuts) lds_add_i64(&acc[i * cell + slot * 2], wi);
+  }
+  // detections: FPw over the ranks below the longest cut; the first threshold also counts the unbinned ones of all K
+  const int* __restrict__ tp = tpf + (size_t)t * D;
+  long long unb = 0, nw = 0;
+  const int end = first ? K : top;
+  for (int j = tid; j < end; j += EV_THREADS) {
+    const int s = rk_str[j];
+    const long long wi = w[min(max(rk_img[j], 0), N - 1)];
+    if (wi == 0 || s == STRATUM_SKIP) continue;
+    if (first && s < 0) unb += wi;
+    if (j < top && tp[j] == 0) {
+      const int slot = s < 0 ? S1 - 1 : min(s, S1 - 2);
+      lds_add_i64(&acc[cuts_upto(sc, n_cuts, j) * cell + slot * 2 + 1], wi);
+    }
+  }
+  if (first) {
+    for (int n = tid; n < N; n += EV_THREADS) nw += w[n];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      unb += shfl_xor_i64(unb, o);
+      nw += shfl_xor_i64(nw, o);
+    }
+    if ((tid & 63) == 0) {
+      lds_add_i64(&tail[0], unb);
+      lds_add_i64(&tail[1], nw);
+    }
+  }
+  __syncthreads();
+  if (tid < cell)  // running sum over the sorted cuts, one thread per (slot, TP / FP)
+    for (int i = 1; i < n_cuts; ++i) acc[i * cell + tid] += acc[(i - 1) * cell + tid];
+  __syncthreads();
+  long long* o = out + ((size_t)row * n_iou + t) * n_cuts * cell;
+  for (int q = tid; q < n_cuts * cell; q += EV_THREADS) o[q] = acc[pos[q / cell] * cell + q % cell];
+  if (first) {
+    long long* og = out + (size_t)R1 * n_iou * n_cuts * cell;
+    if (tid < S1) og[(size_t)row * S1 + tid] = gws[tid];
+    if (tid < 2) og[(size_t)R1 * S1 + (size_t)row * 2 + tid] = tail[tid];
+  }
+}
+
 // ---- host planning ------------------------------------------------------------------------------------------
-// Workspace hand-off (msl_evaluate_froc): after a completed msl_evaluate_detections call the workspace keeps, for the
+// Workspace hand-off (msl_evaluate_froc, msl_evaluate_strata): after a completed msl_evaluate_detections call the workspace keeps, for the
 // same (D, N, G, n_iou), hdr[1] = K (class-1 detections), valA = the rank -> detection index order (the global sort ends
 // in (keyA, valA) after its four passes), img_of = image of every detection index, tpf = the TP flag per (IoU threshold,
-// rank).  The sorted scores live in the caller's result buffer, not here.  Nothing reads these after the sweep, so a
-// consumer on the same stream may; the layout below is part of that contract.
+// rank).  The sorted scores, the claim ranks and the ground-truth volumes live in the caller's result buffer, not here.
+// Nothing reads these after the sweep, so a consumer on the same stream may; the layout below is part of that contract.
 struct EvPlan {
   int nblk, ntile, radix2_passes;
   size_t hdr, keyA, keyB, keyC, valA, valB, valC, img_of, hist, sums, tpf, cum, cprec, tile_max, total;
@@ -789,6 +949,40 @@ int msl_evaluate_froc(const void* eval_workspace, size_t eval_workspace_bytes, c
   MSL_LAUNCH(ev_froc_kernel, dim3(R1, n_iou), dim3(EV_THREADS), 0, (hipStream_t)stream, (const int*)(ws + p.valA),
              (const int*)(ws + p.img_of), (const int*)(ws + p.tpf), sorted_scores, (const int*)(ws + p.hdr), D, N, gt_count,
              weights, rates, n_rates, out);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int msl_evaluate_strata(const void* eval_workspace, size_t eval_workspace_bytes, const float* eval_out, int D, int N, int G,
+                        int n_iou, int n_sc, const float* det_rows, const int* obj_off, const double* voxels,
+                        const double* edges, int n_edges, const int* weights, int R1, const long long* cuts, int n_cuts,
+                        void* strata_workspace, size_t strata_workspace_bytes, long long* out, void* stream) {
+  if (N <= 0 || D < 0 || G < 0 || n_iou <= 0 || n_sc <= 0 || R1 <= 0 || n_edges <= 0 || n_cuts <= 0 || !eval_workspace ||
+      !eval_out || !obj_off || !voxels || !edges || !weights || !cuts || !out || (D > 0 && !det_rows) ||
+      (D + (long long)G > 0 && !strata_workspace))
+    return MSL_ERR_ARG;
+  if (n_edges > EV_STRATA_MAX_EDGES || n_cuts > EV_STRATA_MAX_CUTS || !ev_supported(D, N, G, n_iou, n_sc))
+    return MSL_ERR_UNSUPPORTED;
+  const EvPlan p = ev_plan(D, N, G, n_iou);
+  if (eval_workspace_bytes < p.total || strata_workspace_bytes < 5 * ((size_t)D + (size_t)G)) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const char* ws = (const char*)eval_workspace;
+  const int* hdr = (const int*)(ws + p.hdr);
+  // the sweep's result buffer: summary | sorted scores (D) | TP flags (n_iou, D) | claim rank (n_iou, G) | volumes (G)
+  const int* claim = (const int*)(eval_out + (size_t)n_iou * n_sc * EV_SUMMARY + D + (size_t)n_iou * D);
+  const float* gt_vol = (const float*)(claim + (size_t)n_iou * G);
+  // own workspace: image per rank (D) i32 | image per box (G) i32 | stratum per rank (D) i8 | stratum per box (G) i8
+  int* rk_img = (int*)strata_workspace;
+  int* gt_img = rk_img + D;
+  signed char* rk_str = (signed char*)(gt_img + G);
+  signed char* gt_str = rk_str + D;
+  if (D > 0 || G > 0)
+    MSL_LAUNCH(ev_stratify_kernel, dim3(msl::cdiv(D > G ? D : G, EV_THREADS)), dim3(EV_THREADS), 0, st, det_rows,
+               (const int*)(ws + p.valA), (const int*)(ws + p.img_of), hdr, D, N, obj_off, claim, gt_vol, G, voxels, edges,
+               n_edges, rk_img, rk_str, gt_img, gt_str);
+  MSL_LAUNCH(ev_strata_count_kernel, dim3(R1, n_iou), dim3(EV_THREADS), 0, st, (const int*)(ws + p.tpf), claim, hdr, D, N, G,
+             (const int*)rk_img, (const signed char*)rk_str, (const int*)gt_img, (const signed char*)gt_str, weights, cuts,
+             n_cuts, n_edges + 2, out);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

@@ -14,6 +14,11 @@ positives per case, their mean CPM, ``--bootstrap R`` resamples of the cases for
 (``datasets.LesionsDataModule``) in the frame ``predict`` wrote them in.
 
     python -m mslesions3d_amd.eval -dm lesions -d RAW --centers C1 C2 --spatial_size 96 96 96 -pd PREDICTIONS --froc --bootstrap 1000
+
+``--size_bins 27,125,1000`` (ascending bounding-box volumes in voxels of the frame the boxes are fractions of; mm3 at 1 mm)
+adds ``strata_(min_IoU=<iou>).json`` per ``-iou``: lesions, sensitivity and false positives per case in every size bin, at
+each ``-sc`` threshold and, with ``--froc``, at each FROC rate, with ``--bootstrap`` intervals (DESIGN.md "Eval by lesion
+size").
 """
 import argparse
 import json
@@ -58,6 +63,9 @@ def build_parser():
                         "0.125,0.25,0.5,1,2,4,8)")
     p.add_argument('--bootstrap', type=int, default=S, help="bootstrap resamples of the cases for the 95 %% interval (default: 0)")
     p.add_argument('--bootstrap_seed', type=int, default=S, help="seed of the resampling (default: 0)")
+    p.add_argument('--size_bins', type=size_bin_list, default=S,
+                   help="also write strata_(min_IoU=<iou>).json: sensitivity and false positives per case by lesion size; "
+                        "comma-separated ascending bounding-box volumes in voxels, e.g. 27,125,1000")
     p.add_argument('-dm', '--data_module', choices=["example", "lesions"], default=S,
                    help="lesions: the clinical data module, -d is its data_dir (default: example)")
     p.add_argument('--centers', type=str, nargs='+', default=S, help="as predict.py (default: CHUV_RIM_OK BASEL_INSIDER_OK)")
@@ -79,7 +87,19 @@ def rate_list(text):
     return [(v.numerator, v.denominator) for v in vals]
 
 
-EVAL_DEFAULTS = {"froc": False, "froc_rates": None, "bootstrap": 0, "bootstrap_seed": 0, "data_module": "example",
+def size_bin_list(text):
+    """``27,125,1000`` -> [27.0, 125.0, 1000.0]: 1 .. 15 finite, strictly ascending bin edges."""
+    import math
+    try:
+        vals = [float(v) for v in str(text).split(",") if v.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected comma-separated numbers, got {text!r}")
+    if not 1 <= len(vals) <= 15 or not all(math.isfinite(v) for v in vals) or any(a >= b for a, b in zip(vals, vals[1:])):
+        raise argparse.ArgumentTypeError(f"expected 1 .. 15 finite, strictly ascending sizes, got {text!r}")
+    return vals
+
+
+EVAL_DEFAULTS = {"size_bins": None, "froc": False, "froc_rates": None, "bootstrap": 0, "bootstrap_seed": 0, "data_module": "example",
                  "centers": ('CHUV_RIM_OK', 'BASEL_INSIDER_OK'), "spatial_size": (250, 300, 300), "input_images": ("FLAIR",)}
 
 
@@ -131,6 +151,10 @@ def froc_file_name(min_iou):
     return f"froc_(min_IoU={min_iou}).json"
 
 
+def strata_file_name(min_iou):
+    return f"strata_(min_IoU={min_iou}).json"
+
+
 def convert_tensor(tensor):
     """eval.py:134-138 under the torch of the reference's era: a one-element tensor becomes a number, any other tensor
     (the empty one included) a list."""
@@ -151,10 +175,21 @@ def convert_metrics(metrics):
     return metrx
 
 
-def gather_batches(batches, prediction_dir, confidence_threshold, log=print):
+def batch_voxels(batch):
+    """The voxel count of every image of a collated batch (the frame its boxes are fractions of)."""
+    if "voxels" in batch:
+        return list(batch["voxels"])
+    n = 1
+    for v in batch["img"].shape[2:]:
+        n *= int(v)
+    return [n] * len(batch["subject"])
+
+
+def gather_batches(batches, prediction_dir, confidence_threshold, log=print, frames=None):
     """eval.py:99-120 over an iterable of collated batches: the detections at or above ``confidence_threshold`` and the
     ground truth of every batch whose subjects all have a prediction file.  A batch with a missing file is skipped whole
-    (the reference's behaviour); its subjects are reported through ``log``."""
+    (the reference's behaviour); its subjects are reported through ``log``.  ``frames``: a list that receives the voxel
+    count of every gathered image."""
     det_b, det_l, det_s, gt_b, gt_l = [], [], [], [], []
     for batch in batches:
         subjects = list(batch["subject"])
@@ -168,16 +203,19 @@ def gather_batches(batches, prediction_dir, confidence_threshold, log=print):
         det_s.extend(s for _, _, s in preds)
         gt_b.extend(batch["boxes"])
         gt_l.extend(batch["labels"])
+        if frames is not None:
+            frames.extend(batch_voxels(batch))
     return det_b, det_l, det_s, gt_b, gt_l
 
 
-def gather_lesion_cases(cases, prediction_dir, confidence_threshold, log=print):
+def gather_lesion_cases(cases, prediction_dir, confidence_threshold, log=print, frames=None):
     """``gather_batches`` for the predict data set of a ``LesionsDataModule`` (``cases``, un-augmented): the detections at
     or above ``confidence_threshold`` of every case with a ``sub-<center>_<subject>_preds.json`` and its ground truth in
     the frame ``predict`` wrote those detections in - the case frame (the foreground crop, not fitted: the boxes of
     ``case_sample``) when a ``sub-*_preds_views.json`` lies beside the file (``predict --views`` / ``--flip_views``), else
     the fitted sample's.  A case without a prediction file is skipped and reported through ``log``.  Host only: the
-    ground truth comes from ``cases.case_boxes``, which loads and crops the mask without preparing the image."""
+    ground truth comes from ``cases.case_boxes``, which loads and crops the mask without preparing the image.  ``frames``: a
+    list that receives the voxel count of the frame every gathered case is scored in."""
     det_b, det_l, det_s, gt_b, gt_l = [], [], [], [], []
     for pos in range(len(cases)):
         subj = cases.subjects[pos]
@@ -189,6 +227,9 @@ def gather_lesion_cases(cases, prediction_dir, confidence_threshold, log=print):
         case_frame = os.path.exists(pjoin(prediction_dir, f"sub-{subj}_preds_views.json"))
         boxes, labels = cases.case_boxes(pos, fit=not case_frame)
         det_b.append(b), det_l.append(l), det_s.append(s), gt_b.append(boxes), gt_l.append(labels)
+        if frames is not None:
+            shape = cases.crop_shape(pos) if case_frame else cases.module.spatial_size
+            frames.append(int(shape[0]) * int(shape[1]) * int(shape[2]))
     return det_b, det_l, det_s, gt_b, gt_l
 
 
@@ -202,6 +243,20 @@ def froc_json(summary):
             return [conv(x) for x in v]
         return None if isinstance(v, float) and not math.isfinite(v) else v
     return {k: conv(v) for k, v in summary.items()}
+
+
+def strata_json(summary):
+    """The JSON form of one IoU threshold's ``utils.strata_summary`` dict: the same keys; a NaN (the sensitivity of a bin
+    without lesions) becomes null."""
+    import math
+
+    def conv(v):
+        if isinstance(v, dict):
+            return {k: conv(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [conv(x) for x in v]
+        return None if isinstance(v, float) and not math.isfinite(v) else v
+    return conv(summary)
 
 
 def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_workers=8, predict_subset="train",
@@ -228,13 +283,13 @@ def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_wo
     loader = None if lesions else dataset._loader(dataset.predict_dataset, False, BATCH)
     prediction_dir = resolve_prediction_dir(prediction_dir, dataset_name, model_name, predict_subset)
     print(f"Prediction directory: {prediction_dir}")
-    if opt.froc and not lesions:  # two passes over the prediction files, one over the volumes
-        loader = [{k: b[k] for k in ("subject", "boxes", "labels")} for b in loader]
+    if (opt.froc or opt.size_bins) and not lesions:  # two passes over the prediction files, one over the volumes
+        loader = [dict({k: b[k] for k in ("subject", "boxes", "labels")}, voxels=batch_voxels(b)) for b in loader]
 
-    def gather(threshold, log=print):
+    def gather(threshold, log=print, frames=None):
         if lesions:
-            return gather_lesion_cases(dataset.predict_dataset, prediction_dir, threshold, log=log)
-        return gather_batches(loader, prediction_dir, threshold, log=log)
+            return gather_lesion_cases(dataset.predict_dataset, prediction_dir, threshold, log=log, frames=frames)
+        return gather_batches(loader, prediction_dir, threshold, log=log, frames=frames)
 
     if opt.froc:
         from .utils import evaluate_froc
@@ -248,6 +303,23 @@ def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_wo
             d = froc_json(froc[iou])
             print(f"\nFROC for IoU = {iou}: CPM {d['cpm']}  sensitivity {d['sensitivity']} at {d['rates']} FP / case")
             with open(pjoin(prediction_dir, froc_file_name(iou)), "w") as json_file:
+                json.dump(d, json_file, indent=4)
+
+    if opt.size_bins:
+        from .utils import evaluate_strata
+        voxels = []
+        det_b, det_l, det_s, gt_b, gt_l = gather(float("-inf"), log=lambda *_: None, frames=voxels)
+        if not gt_l:
+            raise RuntimeError("size bins: no case with a prediction file")
+        strata = evaluate_strata(det_b, det_l, det_s, gt_b, gt_l, voxels, opt.size_bins, min_overlaps=ious, min_scores=scores,
+                                 fp_rates=opt.froc_rates if opt.froc else None, n_boot=opt.bootstrap, seed=opt.bootstrap_seed)
+        for iou in ious:
+            d = strata_json(strata[iou])
+            print(f"\nLesions by size for IoU = {iou}: edges {d['edges']} lesions {d['n_lesions']}")
+            for cut in d["cuts"]:
+                at = f"min score {cut['min_score']}" if "min_score" in cut else f"{cut['fp_rate']} FP / case"
+                print(f"  at {at}: sensitivity {cut['sensitivity']}  FP / case {cut['fp_per_case']}")
+            with open(pjoin(prediction_dir, strata_file_name(iou)), "w") as json_file:
                 json.dump(d, json_file, indent=4)
 
     with torch.no_grad():

@@ -9,6 +9,8 @@
   host synchronisation per step).
 * ``evaluate_detections`` computes the (IoU x score threshold) grid of the reference's ``eval.py`` at dataset scale
   (``csrc/evaluate.hip``: no cap on detections or ground truth), each grid point bit-identical to ``calculate_mAP``.
+* ``evaluate_froc`` and ``evaluate_strata`` read what that sweep leaves on the device: FROC with bootstrap intervals, and
+  sensitivity / false positives per lesion-size bin (not in the reference; numpy twins ``froc_host``, ``strata_host``).
 """
 import numpy as np
 import torch
@@ -382,9 +384,11 @@ def prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_label
     def launch():
         _lib.call("msl_evaluate_detections", *args, _stream())
 
-    # "ws" / "ws_bytes" / "sorted_scores": what msl_evaluate_froc consumes after launch() on the same stream
+    # "ws" / "ws_bytes" / "sorted_scores": what msl_evaluate_froc consumes after launch() on the same stream;
+    # msl_evaluate_strata also reads "det_rows" and "obj_off" (device addresses of this call's inputs)
     return {"launch": launch, "out": out, "D": D, "N": N, "G": G, "ious": ious, "scores": scs,
             "ws": ws, "ws_bytes": ws_bytes, "sorted_scores": out[n_iou * n_sc * METRIC_SUMMARY:n_iou * n_sc * METRIC_SUMMARY + D],
+            "det_rows": base, "obj_off": ptr(goff),
             "keep": (packed, ws, gb, gl, goff, recall)}
 
 
@@ -611,6 +615,261 @@ def evaluate_froc(det_boxes, det_labels, det_scores, true_boxes, true_labels, mi
     w = _froc_weights(weights, len(true_labels), n_boot, seed)
     ints = evaluate_froc_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, ious, fp_rates, w)
     return froc_summary(ints, ious, fp_rates)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Eval by lesion size ("Eval by lesion size"): weighted TP / FP counts per size bin at cuts of the rank order.
+# Not in the reference, which only lists the found / not-found volumes; the matching rule is calculate_mAP's.
+
+STRATA_MAX_EDGES = 15  # EV_STRATA_MAX_EDGES of csrc/evaluate.hip
+STRATA_MAX_CUTS = 32   # EV_STRATA_MAX_CUTS
+_NEVER = 0x7FFFFFFF    # claim rank of a ground-truth box nobody claimed
+
+
+def strata_edges(size_edges):
+    """-> (m,) f64: 1 .. 15 finite, strictly ascending bin edges (in voxels of the frame ``voxels`` counts)."""
+    e = np.asarray(list(size_edges), dtype=np.float64).reshape(-1)
+    if not 1 <= e.size <= STRATA_MAX_EDGES or not np.isfinite(e).all() or (np.diff(e) <= 0).any():
+        raise ValueError(f"size edges: 1 .. {STRATA_MAX_EDGES} finite, strictly ascending values, got {size_edges!r}")
+    return e
+
+
+def _strata_voxels(voxels, N):
+    v = np.asarray(voxels, dtype=np.float64).reshape(-1)
+    v = np.full(N, v[0]) if v.size == 1 else v
+    if v.shape != (N,) or not np.isfinite(v).all() or (v <= 0).any():
+        raise ValueError(f"voxels: one finite value > 0 per image ({N}), or one for all")
+    return np.ascontiguousarray(v)
+
+
+def _volume_f32(boxes):
+    """``volume`` of every row in f32, left to right."""
+    b = np.asarray(boxes, np.float32).reshape(-1, 6)
+    return (b[:, 3] - b[:, 0]) * (b[:, 4] - b[:, 1]) * (b[:, 5] - b[:, 2])
+
+
+def size_stratum(vol_f32, voxels, edges):
+    """Stratum of every box: the number of edges <= ``float64(vol_f32) * voxels``; -1 where that size is NaN."""
+    with np.errstate(invalid="ignore"):
+        v = np.asarray(vol_f32, np.float32).astype(np.float64) * np.asarray(voxels, np.float64)
+    s = np.searchsorted(edges, v, side="right").astype(np.int64)
+    s[np.isnan(v)] = -1
+    return s
+
+
+def _strata_cuts(cuts, R1, n_iou):
+    c = np.asarray(cuts)
+    if not np.issubdtype(c.dtype, np.integer) or c.ndim not in (1, 3):
+        raise ValueError("cuts: integers, (n_cuts,) or (rows, n_iou, n_cuts)")
+    c = np.broadcast_to(c if c.ndim == 3 else c[None, None, :], (R1, n_iou, c.shape[-1]))
+    if not 1 <= c.shape[2] <= STRATA_MAX_CUTS:
+        raise ValueError(f"1 .. {STRATA_MAX_CUTS} cuts, got {c.shape[2]}")
+    return np.ascontiguousarray(c, dtype=np.int64)
+
+
+def strata_cuts_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores, fp_rates, weights):
+    """The cuts ``evaluate_strata`` takes, on the host -> (rows, n_iou, n_sc + n_rates) int64: ``K_c`` of every score
+    threshold (class-1 detections with ``float(score) >= float(threshold)``, the same for every row and IoU), then
+    ``froc_host``'s ``k*`` of every rate (``fp_rates`` None: none)."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)
+    w = _froc_weights(weights, c["N"], 0, 0)
+    ious = list(min_overlaps)
+    kc = np.array([int((c["d_sco"].astype(np.float64) >= float(s)).sum()) for s in min_scores], dtype=np.int64)
+    cuts = np.broadcast_to(kc[None, None, :], (w.shape[0], len(ious), kc.size))
+    if fp_rates is not None:
+        k = froc_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, ious, fp_rates, w)["k"]
+        cuts = np.concatenate([cuts, k], axis=2)
+    return np.ascontiguousarray(cuts, dtype=np.int64)
+
+
+def _cum_by_slot(values, slots, S1):
+    """(n,) int64 values, (n,) slots -> (n + 1, S1): the sum of the first i values per slot."""
+    m = np.zeros((values.shape[0] + 1, S1), dtype=np.int64)
+    m[np.arange(1, values.shape[0] + 1), slots] = values
+    return np.cumsum(m, axis=0)
+
+
+def strata_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, min_overlaps, weights, cuts):
+    """The numpy twin of ``msl_evaluate_strata``: rank order and TP flags from ``compute_metrics_per_class``, the claim rank
+    of a ground-truth box = the rank of the true positive whose first-maximum IoU it is, then the definitions of DESIGN.md
+    "Eval by lesion size" as written.  ``cuts``: prefix lengths, (n_cuts,) or (rows, n_iou, n_cuts), clamped to 0 .. K.
+    With S strata and slot S the unbinned one -> ``{"tp", "fp": (rows, n_iou, n_cuts, S + 1), "gw": (rows, S + 1),
+    "det_unbinned", "nw": (rows,), "cuts": the clamped cuts}``, all int64: the integers the kernel writes."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)
+    ious, N, edges = list(min_overlaps), c["N"], strata_edges(size_edges)
+    vox = _strata_voxels(voxels, N)
+    w = _froc_weights(weights, N, 0, 0).astype(np.int64)
+    R1, K, S1 = w.shape[0], c["d_sco"].shape[0], edges.size + 2
+    cuts = np.clip(_strata_cuts(cuts, R1, len(ious)), 0, K)
+    order = c["order"]
+    img, box = c["d_img"][order], c["d_box"][order]
+    t_img, t_box = c["t_img"], c["t_box"]
+    d_slot = size_stratum(_volume_f32(box), vox[img], edges)
+    g_slot = size_stratum(_volume_f32(t_box), vox[t_img], edges)
+    d_slot[d_slot < 0] = S1 - 1
+    g_slot[g_slot < 0] = S1 - 1
+    gw = np.zeros((R1, S1), dtype=np.int64)
+    for s in range(S1):
+        gw[:, s] = w[:, t_img[g_slot == s]].sum(1)
+    tp_out = np.zeros((R1, len(ious), cuts.shape[2], S1), dtype=np.int64)
+    fp_out = np.zeros_like(tp_out)
+    for t, ov in enumerate(ious):
+        tp = np.zeros(K, dtype=np.int64)
+        if K:
+            tp = compute_metrics_per_class(c["d_img"], c["d_box"], c["d_sco"], t_img, t_box,
+                                           np.zeros(t_box.shape[0], dtype=bool), ov)[0].astype(np.int64)
+        claim = np.full(t_box.shape[0], _NEVER, dtype=np.int64)
+        for j in np.nonzero(tp)[0]:
+            same = np.nonzero(t_img == img[j])[0]
+            claim[same[int(np.argmax(_iou_one_to_many(box[j], t_box[same])))]] = j
+        by_claim = np.argsort(claim, kind="stable")
+        for r in range(R1):
+            TP = _cum_by_slot(w[r, t_img[by_claim]], g_slot[by_claim], S1)  # boxes in claim-rank order
+            FP = _cum_by_slot(w[r, img] * (1 - tp), d_slot, S1)
+            k = cuts[r, t]
+            tp_out[r, t] = TP[np.searchsorted(claim[by_claim], k, side="left")]  # boxes with claim rank < k
+            fp_out[r, t] = FP[k]
+    unb = (w[:, img] * (d_slot == S1 - 1)[None, :]).sum(1) if K else np.zeros(R1, dtype=np.int64)
+    return {"tp": tp_out, "fp": fp_out, "gw": gw, "det_unbinned": unb.astype(np.int64), "nw": w.sum(1), "cuts": cuts}
+
+
+def strata_ints(host_out, R1, n_iou, n_cuts, S1, cuts=None):
+    """The result buffer of ``msl_evaluate_strata`` (host copy) as the dict ``strata_host`` returns."""
+    a = np.asarray(host_out, dtype=np.int64)
+    n = R1 * n_iou * n_cuts * S1 * 2
+    cnt = a[:n].reshape(R1, n_iou, n_cuts, S1, 2)
+    tail = a[n + R1 * S1:n + R1 * S1 + 2 * R1].reshape(R1, 2)
+    return {"tp": cnt[..., 0].copy(), "fp": cnt[..., 1].copy(), "gw": a[n:n + R1 * S1].reshape(R1, S1).copy(),
+            "det_unbinned": tail[:, 0].copy(), "nw": tail[:, 1].copy(), "cuts": cuts}
+
+
+def prepare_strata(plan, voxels, size_edges, weights, cuts):
+    """Pack one ``msl_evaluate_strata`` call behind ``plan`` (``prepare_evaluation``): voxels, edges and weights in one host
+    buffer with one host-to-device copy; workspace and result buffer allocated.  ``cuts``: a device int64 tensor (rows,
+    n_iou, n_cuts) - whatever wrote it on the current stream before ``launch()`` - or host integers, which ride in the same
+    upload.  Returns ``launch()`` (enqueue after ``plan["launch"]()``, no synchronisation), ``out`` (device, int64), the
+    device ``cuts`` and the sizes."""
+    dev = plan["out"].device
+    w = np.ascontiguousarray(weights, dtype=np.int32)
+    R1, N, D, G, n_iou = w.shape[0], plan["N"], plan["D"], plan["G"], len(plan["ious"])
+    edges, vox = strata_edges(size_edges), _strata_voxels(voxels, N)
+    assert w.shape == (R1, N)
+    parts = [vox.view(np.int32), edges.view(np.int32)]
+    if not torch.is_tensor(cuts):
+        parts.append(_strata_cuts(cuts, R1, n_iou).reshape(-1).view(np.int32))
+    packed = torch.from_numpy(np.concatenate(parts + [w.reshape(-1)])).to(dev)
+    base = packed.data_ptr()
+    o_e = 2 * N
+    o_c = o_e + 2 * edges.size
+    if torch.is_tensor(cuts):
+        assert cuts.dtype == torch.int64 and cuts.device == dev and cuts.is_contiguous() and cuts.shape[:2] == (R1, n_iou)
+        n_cuts, cuts_ptr, o_w = int(cuts.shape[2]), cuts.data_ptr(), o_c
+    else:
+        n_cuts = (packed.numel() - o_c - R1 * N) // (2 * R1 * n_iou)
+        cuts_ptr, o_w = base + 4 * o_c, o_c + 2 * R1 * n_iou * n_cuts
+        cuts = packed[o_c:o_w].view(torch.int64).reshape(R1, n_iou, n_cuts)
+    if not 1 <= n_cuts <= STRATA_MAX_CUTS:
+        raise ValueError(f"1 .. {STRATA_MAX_CUTS} cuts, got {n_cuts}")
+    S1 = edges.size + 2
+    ws_bytes = 5 * (D + G)
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+    out = torch.empty(R1 * n_iou * n_cuts * S1 * 2 + R1 * S1 + R1 * 2, dtype=torch.int64, device=dev)
+    args = (ptr(plan["ws"]), plan["ws_bytes"], ptr(plan["out"]), D, N, G, n_iou, len(plan["scores"]),
+            plan["det_rows"] if D else None, plan["obj_off"], base, base + 4 * o_e, int(edges.size), base + 4 * o_w, R1, cuts_ptr, n_cuts, ptr(ws), ws_bytes, ptr(out))
+
+    def launch():
+        _lib.call("msl_evaluate_strata", *args, _stream())
+
+    return {"launch": launch, "out": out, "cuts": cuts, "R1": R1, "n_iou": n_iou, "n_cuts": n_cuts, "S1": S1, "ws": ws,
+            "args": args, "keep": (packed, plan)}
+
+
+def evaluate_strata_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, min_overlaps,
+                         min_scores, fp_rates, weights):
+    """``strata_host`` at the cuts of ``strata_cuts_host``, on the HIP device: the sweep of ``prepare_evaluation``, FROC
+    when ``fp_rates`` is given, one upload of voxels, edges and weights, ``msl_evaluate_strata`` at cuts that never leave
+    the device (``K_c`` from the sweep's summary, ``k*`` from FROC's result), one device-to-host copy."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)  # rejects NaN scores
+    w = _froc_weights(weights, c["N"], 0, 0)
+    scs = list(min_scores)
+    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, scs)
+    n_iou, n_sc, R1 = len(plan["ious"]), len(scs), w.shape[0]
+    f = prepare_froc(plan, c["g"], w, froc_rates(fp_rates)) if fp_rates is not None else None
+    plan["launch"]()
+    kc = plan["out"][:n_iou * n_sc * METRIC_SUMMARY].reshape(n_iou, n_sc, METRIC_SUMMARY)[:, :, 6].to(torch.int64)
+    cuts = kc[None].expand(R1, n_iou, n_sc)
+    if f is not None:
+        f["launch"]()
+        k = f["out"][:R1 * n_iou * f["n_rates"] * 2].reshape(R1, n_iou, f["n_rates"], 2)[..., 0]
+        cuts = torch.cat([cuts, k], dim=2)
+    s = prepare_strata(plan, voxels, size_edges, w, cuts.contiguous())
+    s["launch"]()
+    host = torch.cat([s["out"], s["cuts"].reshape(-1)]).cpu().numpy()  # the one device-to-host copy
+    n = s["out"].numel()
+    return strata_ints(host[:n], R1, n_iou, s["n_cuts"], s["S1"], host[n:].reshape(R1, n_iou, s["n_cuts"]).copy())
+
+
+def _ratio(a, b):
+    return int(a) / int(b) if b > 0 else float("nan")
+
+
+def strata_summary(ints, size_edges, min_overlaps, cut_labels):
+    """``{min_overlap: {...}}`` from the integers of ``strata_host`` / ``msl_evaluate_strata``.  Per IoU threshold:
+    ``edges``, ``n_lesions`` (Gw_s of row 0 per bin), ``cuts`` (one dict per cut: the entries of ``cut_labels`` plus ``k``,
+    row 0's prefix length, ``sensitivity`` = TPw / Gw_s per bin, NaN for a bin without lesions, ``fp_per_case`` = FPw / Nw
+    per bin and, with bootstrap rows, ``ci_low`` / ``ci_high`` / ``fp_ci_low`` / ``fp_ci_high``), ``dropped`` (per bin: the
+    bootstrap rows with Gw_s = 0, left out of that bin's sensitivity interval), ``unbinned`` (row 0: lesions, detections,
+    and per cut the true and false positives among them), ``n_cases``, ``n_boot``.  Sizes are bounding-box volumes.  The
+    intervals are ``np.percentile(rows 1.., [2.5, 97.5])``; an interval without a row to take it over is None."""
+    edges = strata_edges(size_edges)
+    tp, fp, gw, nw = ints["tp"], ints["fp"], ints["gw"], ints["nw"]
+    R1, n_iou, n_cuts, S1 = tp.shape
+    S = S1 - 1
+    assert S == edges.size + 1 and n_iou == len(min_overlaps) and n_cuts == len(cut_labels)
+    keep = [np.nonzero(gw[1:, s] > 0)[0] + 1 for s in range(S)]
+    rows_fp = np.nonzero(nw[1:] > 0)[0] + 1
+    pct = lambda vals: [float(v) for v in np.percentile(np.asarray(vals, dtype=np.float64), [2.5, 97.5])]
+    out = {}
+    for t, ov in enumerate(min_overlaps):
+        cut_dicts = []
+        for q, label in enumerate(cut_labels):
+            d = dict(label)
+            d["k"] = int(ints["cuts"][0, t, q])
+            d["sensitivity"] = [_ratio(tp[0, t, q, s], gw[0, s]) for s in range(S)]
+            d["fp_per_case"] = [_ratio(fp[0, t, q, s], nw[0]) for s in range(S)]
+            ci = [pct([_ratio(tp[r, t, q, s], gw[r, s]) for r in keep[s]]) if keep[s].size else None for s in range(S)]
+            fci = [pct([_ratio(fp[r, t, q, s], nw[r]) for r in rows_fp]) if rows_fp.size else None for s in range(S)]
+            d["ci_low"], d["ci_high"] = [c and c[0] for c in ci], [c and c[1] for c in ci]
+            d["fp_ci_low"], d["fp_ci_high"] = [c and c[0] for c in fci], [c and c[1] for c in fci]
+            d["unbinned_tp"], d["unbinned_fp"] = int(tp[0, t, q, S]), int(fp[0, t, q, S])
+            cut_dicts.append(d)
+        out[ov] = {"edges": [float(e) for e in edges], "n_lesions": [int(v) for v in gw[0, :S]], "cuts": cut_dicts,
+                   "dropped": [R1 - 1 - int(k.size) for k in keep],
+                   "unbinned": {"n_lesions": int(gw[0, S]), "detections": int(ints["det_unbinned"][0])},
+                   "n_cases": int(nw[0]), "n_boot": R1 - 1}
+    return out
+
+
+def strata_cut_labels(min_scores, fp_rates):
+    """One label per cut, in the order of ``strata_cuts_host``."""
+    labels = [{"min_score": float(s)} for s in min_scores]
+    if fp_rates is not None:
+        labels += [{"fp_rate": n / d} for n, d in froc_rates(fp_rates)]
+    return labels
+
+
+def evaluate_strata(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, min_overlaps=(0.5,),
+                    min_scores=(0.5,), fp_rates=None, n_boot=0, seed=0, weights=None):
+    """Sensitivity and false positives per case by lesion size on the HIP device -> ``strata_summary``'s dict per IoU
+    threshold, at every score threshold of ``min_scores`` and, with ``fp_rates``, at the FROC operating point of every rate.
+    ``voxels``: the voxel count of the frame each image's boxes are fractions of (one value, or one per image);
+    ``size_edges``: ascending bin edges in voxels.  ``weights`` replaces ``bootstrap_weights(N, n_boot, seed)``.  NaN
+    scores: ValueError."""
+    ious, scs = list(min_overlaps), list(min_scores)
+    w = _froc_weights(weights, len(true_labels), n_boot, seed)
+    ints = evaluate_strata_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, ious, scs,
+                                fp_rates, w)
+    return strata_summary(ints, size_edges, ious, strata_cut_labels(scs, fp_rates))
 
 
 # ---- box overlays (utils.py:516-617, predict.py:186-220) ----------------------------------------------------------------

@@ -456,6 +456,31 @@ int msl_evaluate_strata(const void* eval_workspace, size_t eval_workspace_bytes,
                         const double* edges, int n_edges, const int* weights, int R1, const long long* cuts, int n_cuts,
                         void* strata_workspace, size_t strata_workspace_bytes, long long* out, void* stream);
 
+/* ---- prior fit report (csrc/priorfit.hip): what the matching of MultiBoxLoss (ssd3d.py:786-887)
+ * gives every ground-truth box, for n_thr thresholds at once, without an (N,P) buffer.  gt_boxes (G,6) f32 fractional corner
+ * boxes, finite with max >= min per axis, and obj_off (N+1) i32 on the device (msl_multibox_match's layout, any number of
+ * boxes per image); priors_c (P,6) f32 centre-size on the device; scale_off (S+1) i32 HOST array of ascending prior-row
+ * offsets, scale_off[0] = 0, scale_off[S] = P (one range per feature map); thr (n_thr) f32 HOST array.  S <= 8 and
+ * n_thr <= 8 (more -> -2).  workspace: _workspace_bytes(G) bytes, 8-byte aligned, initialised by the call.  Outputs, exactly
+ * what the matching implies for the image of box g (oracle/multibox.py:match_image with every label 1):
+ *   best_iou (G) f32 / best_prior (G) i32: the maximum IoU of g over all priors and the FIRST prior attaining it (before
+ *     the force-match);
+ *   held (G) i32: 1 if g is the last box of its image with that best_prior (it keeps the prior the force-match gives it);
+ *   pos (G, n_thr, S) i32: the priors p of range s with obj[p] == g and overlap[p] >= thr[t], obj / overlap taken AFTER the
+ *     force-match (a forced prior has overlap 1 and belongs to the last claimant, every other prior to the first box with
+ *     the maximum IoU).  sum_s pos[g,t,s] = positive priors of g in training; 0 = a box that trains nothing.
+ * Two streaming passes over (image, tile of MSL_PRIOR_FIT_TILE priors), the image's boxes staged through LDS
+ * MSL_PRIOR_FIT_CHUNK at a time; integer / max-of-keys atomics only: the result does not depend on scheduling.  G = 0
+ * launches nothing.  Null or inconsistent arguments -> -1. */
+#define MSL_PRIOR_FIT_TILE 1024 /* priors per workgroup */
+#define MSL_PRIOR_FIT_CHUNK 64  /* boxes of one image staged in LDS at a time */
+#define MSL_PRIOR_FIT_MAX_SCALES 8
+#define MSL_PRIOR_FIT_MAX_THRESHOLDS 8
+size_t msl_prior_fit_workspace_bytes(int G);
+int msl_prior_fit(const float* gt_boxes, const int* obj_off, int N, int G, const float* priors_c, int P, const int* scale_off,
+                  int S, const float* thr, int n_thr, void* workspace, size_t workspace_bytes, float* best_iou,
+                  int* best_prior, int* held, int* pos, void* stream);
+
 /* ---- device-resident training data (csrc/datapipe.hip, devicedata.py): the host pipeline of datasets._Cases ----------
  * msl_normalize_nonzero: NormalizeIntensity(nonzero=True) in place on n_volumes contiguous f32 volumes of `voxels` each:
  * population mean / std of the non-zero voxels (f64, fixed order), std 0 -> 1, zeros stay zero, all-zero unchanged.

@@ -133,6 +133,8 @@ _SIGNATURES = {
     "msl_evaluate_detections": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _Z, _P, _P]),
     "msl_evaluate_froc": (_I, [_P, _Z, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
     "msl_evaluate_strata": (_I, [_P, _Z, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _Z, _P, _P]),
+    "msl_prior_fit_workspace_bytes": (_Z, [_I]),
+    "msl_prior_fit": (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "msl_normalize_nonzero": (_I, [_P, _I, _Q, _P]),
     "msl_augment_resample": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_augment_affine": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -178,6 +180,9 @@ _SIGNATURES = {
 }
 
 DRAW_BOXES_CHUNK = 256  # MSL_DRAW_BOXES_CHUNK of the header: boxes msl_draw_boxes stages in LDS at a time
+PRIOR_FIT_TILE = 1024   # MSL_PRIOR_FIT_TILE: priors one workgroup of msl_prior_fit takes
+PRIOR_FIT_CHUNK = 64    # MSL_PRIOR_FIT_CHUNK: boxes of an image it stages in LDS at a time
+PRIOR_FIT_MAX_SCALES = PRIOR_FIT_MAX_THRESHOLDS = 8
 
 _lib = None
 

@@ -13,28 +13,8 @@
 
 namespace {
 
-struct Box {
-  float v[6];
-};
+#include "boxmath.hpp"  // Box, load_box, c_to_xyz, box_vol, box_inter, box_iou (shared with priorfit.hip)
 
-__device__ __forceinline__ Box load_box(const float* p) {
-  Box b;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) b.v[i] = p[i];
-  return b;
-}
-
-// utils.py:42-51
-__device__ __forceinline__ Box c_to_xyz(const Box& c) {
-  Box o;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float h = c.v[3 + i] / 2.0f;
-    o.v[i] = c.v[i] - h;
-    o.v[3 + i] = c.v[i] + h;
-  }
-  return o;
-}
 // utils.py:92-102
 __device__ __forceinline__ Box xyz_to_c(const Box& b) {
   Box o;
@@ -64,25 +44,6 @@ __device__ __forceinline__ Box decode_box(const Box& g, const Box& p) {
     o.v[3 + i] = expf(g.v[3 + i] / 5.0f) * p.v[3 + i];
   }
   return o;
-}
-__device__ __forceinline__ float box_vol(const Box& b) {
-  return (b.v[3] - b.v[0]) * (b.v[4] - b.v[1]) * (b.v[5] - b.v[2]);
-}
-// utils.py:105-149
-__device__ __forceinline__ float box_inter(const Box& a, const Box& b) {
-  float e[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float lo = fmaxf(a.v[i], b.v[i]);
-    const float hi = fminf(a.v[3 + i], b.v[3 + i]);
-    e[i] = fmaxf(hi - lo, 0.0f);
-  }
-  return e[0] * e[1] * e[2];
-}
-__device__ __forceinline__ float box_iou(const Box& a, float vol_a, const Box& b, float vol_b) {
-  const float inter = box_inter(a, b);
-  const float uni = vol_a + vol_b - inter;
-  return inter / uni;
 }
 
 // ---- priors -------------------------------------------------------------------------------------

@@ -325,21 +325,52 @@ class LSSD3D(nn.Module):
                else self.base.feature_map_dims(self.input_size))[0]
         if not torch.cuda.is_available():
             raise _lib.HipKernelError("create_prior_boxes needs the HIP device (no CPU fallback)")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        feats = list(self.aspect_ratios.keys())
-        P = sum(fmd[f][0] * fmd[f][1] * fmd[f][2] * self.boxes_per_location for f in feats)
-        out = torch.empty((P, 6), dtype=torch.float32, device=dev)
-        off, ranges = 0, {}
-        for f in feats:
-            d0, d1, d2 = fmd[f]
-            _lib.call("msl_make_priors", ptr(out), off, d0, d1, d2, float(self.scales[f]), self.boxes_per_location,
-                      _stream())
-            ranges[f] = (off, off + d0 * d1 * d2 * self.boxes_per_location)
-            off = ranges[f][1]
+        ranges = self.prior_ranges(fmd)
+        out = self.make_priors(self.scales, fmd, ranges)
         if not per_feature_map:
             return out
         host = out.cpu()
         return {f: host[lo:hi].tolist() for f, (lo, hi) in ranges.items()}
+
+    def prior_ranges(self, fmd=None):
+        """``{feature map: (lo, hi)}``: the rows of ``priors_cxcycz`` that belong to each prediction layer, in row order."""
+        fmd = self.base.feature_map_dims(self.input_size)[0] if fmd is None else fmd
+        off, ranges = 0, {}
+        for f in self.aspect_ratios.keys():
+            d0, d1, d2 = fmd[f]
+            ranges[f] = (off, off + d0 * d1 * d2 * self.boxes_per_location)
+            off = ranges[f][1]
+        return ranges
+
+    def make_priors(self, scales, fmd=None, ranges=None):
+        """The (P,6) priors of this network's feature maps at the given ``{feature map: scale}`` (one ``msl_make_priors``
+        launch per map): ``create_prior_boxes`` with ``self.scales``, a candidate scale set in a prior-fit sweep."""
+        fmd = self.base.feature_map_dims(self.input_size)[0] if fmd is None else fmd
+        ranges = self.prior_ranges(fmd) if ranges is None else ranges
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((max(hi for _, hi in ranges.values()), 6), dtype=torch.float32, device=dev)
+        for f, (lo, _) in ranges.items():
+            d0, d1, d2 = fmd[f]
+            _lib.call("msl_make_priors", ptr(out), lo, d0, d1, d2, float(scales[f]), self.boxes_per_location, _stream())
+        return out
+
+    def prior_fit(self, true_boxes, voxels=None, size_edges=()):
+        """``utils.prior_fit`` with this model's priors, feature-map ranges and matching threshold(s) (for a soft band
+        ``[lo, hi]`` both: a prior is a positive from ``hi`` on) -> ``(fit, summary)``, the summary from
+        ``utils.prior_fit_summary`` with extents in voxels of ``input_size``.  ``voxels`` defaults to the voxel count of
+        ``input_size``."""
+        from . import utils
+        thr = [float(t) for t in self.threshold] if isinstance(self.threshold, (list, tuple)) else [float(self.threshold)]
+        boxes = utils._prior_fit_boxes(true_boxes)  # a bad box is refused before the first GPU call
+        dev = self.device if self.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+        with torch.cuda.device(dev):
+            self._ensure_device_state(dev)
+            ranges = self.prior_ranges()
+            fit = utils.prior_fit(boxes, self.priors_cxcycz, thr, ranges)
+        if voxels is None:
+            voxels = int(np.prod(self.input_size))
+        return fit, utils.prior_fit_summary(fit, boxes, voxels, size_edges, thr, shapes=self.input_size,
+                                            scale_names=list(ranges.keys()))
 
     def _ensure_device_state(self, dev):
         if self.priors_cxcycz is None or self.priors_cxcycz.device != dev:

@@ -872,6 +872,152 @@ def evaluate_strata(det_boxes, det_labels, det_scores, true_boxes, true_labels, 
     return strata_summary(ints, size_edges, ious, strata_cut_labels(scs, fp_rates))
 
 
+# ---- prior fit report (csrc/priorfit.hip): which lesions the prior boxes can match ---------------
+PRIOR_FIT_QUANTILES = (0.0, 0.05, 0.25, 0.5)  # of best_iou: the low end is where lesions are lost
+
+
+def _prior_fit_boxes(true_boxes):
+    """list of per-image (n_i,6) boxes -> list of f32 arrays; a non-finite or inverted box is a ValueError."""
+    boxes = [np.ascontiguousarray(_np(b, np.float32).reshape(-1, 6)) for b in true_boxes]
+    for n, b in enumerate(boxes):
+        if not np.isfinite(b).all():
+            raise ValueError(f"prior_fit: image {n} has a non-finite ground-truth box")
+        if (b[:, 3:] < b[:, :3]).any():
+            raise ValueError(f"prior_fit: image {n} has a ground-truth box with max < min")
+    return boxes
+
+
+def prior_fit_ranges(scale_ranges, P):
+    """``{feature map: (lo, hi)}`` (or a list of pairs) -> (S + 1,) int32 offsets: contiguous ascending ranges from 0 to P."""
+    pairs = list(scale_ranges.values()) if isinstance(scale_ranges, dict) else list(scale_ranges)
+    off = [0]
+    for lo, hi in pairs:
+        if int(lo) != off[-1] or int(hi) < int(lo):
+            raise ValueError(f"scale ranges must be contiguous and ascending from 0, got {pairs}")
+        off.append(int(hi))
+    if not 1 <= len(pairs) <= _lib.PRIOR_FIT_MAX_SCALES or off[-1] != int(P):
+        raise ValueError(f"1 .. {_lib.PRIOR_FIT_MAX_SCALES} scale ranges that end at the number of priors ({P}), got {pairs}")
+    return np.asarray(off, dtype=np.int32)
+
+
+def _prior_fit_thresholds(thresholds):
+    thr = np.asarray(list(thresholds), dtype=np.float32).reshape(-1)
+    if not 1 <= thr.size <= _lib.PRIOR_FIT_MAX_THRESHOLDS or np.isnan(thr).any():
+        raise ValueError(f"1 .. {_lib.PRIOR_FIT_MAX_THRESHOLDS} thresholds (no NaN), got {thresholds!r}")
+    return thr
+
+
+def prepare_prior_fit(true_boxes, dev=None):
+    """Validate and upload the ground truth of a data set once -> a plan ``run_prior_fit`` takes any number of times (one
+    call per candidate prior set of a sweep).  Raises ValueError for a bad box before anything touches the device."""
+    from .ssd3d import MultiBoxLoss
+    boxes = _prior_fit_boxes(true_boxes)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise _lib.HipKernelError("prior_fit: needs the HIP device (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    gb, _, off, G = MultiBoxLoss.pack_targets([torch.from_numpy(b) for b in boxes],
+                                              [torch.zeros(b.shape[0], dtype=torch.int64) for b in boxes], dev)
+    image = np.repeat(np.arange(len(boxes), dtype=np.int64), [b.shape[0] for b in boxes])
+    return {"gb": gb, "off": off, "G": G, "N": len(boxes), "image": image, "dev": dev}
+
+
+def run_prior_fit(plan, priors_cxcycz, thresholds, scale_ranges):
+    """One ``msl_prior_fit`` call and one device-to-host copy -> dict of CPU tensors over the G ground-truth boxes:
+    ``best_iou`` f32, ``best_prior`` / ``best_scale`` / ``held`` / ``image`` i64, ``pos`` (G, n_thr, S) i64."""
+    priors = _gpu(priors_cxcycz, "prior_fit").reshape(-1, 6)
+    P, G, N = int(priors.shape[0]), plan["G"], plan["N"]
+    off, thr = prior_fit_ranges(scale_ranges, P), _prior_fit_thresholds(thresholds)
+    if N < 1:
+        raise ValueError("prior_fit: no image")
+    S, T = off.size - 1, thr.size
+    dev = plan["dev"]
+    ws_bytes = _lib.load().msl_prior_fit_workspace_bytes(G)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    out = torch.empty(max(G * (3 + T * S), 1), dtype=torch.int32, device=dev)  # best_iou bits | best_prior | held | pos
+    base = out.data_ptr()
+    _lib.call("msl_prior_fit", ptr(plan["gb"]), ptr(plan["off"]), N, G, ptr(priors), P, off.ctypes.data, S, thr.ctypes.data, T,
+              ptr(ws), ws_bytes, base, base + 4 * G, base + 8 * G, base + 12 * G, _stream())
+    host = out.cpu().numpy()[:G * (3 + T * S)]  # the one device-to-host copy
+    best_prior = host[G:2 * G].astype(np.int64)
+    return {"best_iou": torch.from_numpy(host[:G].view(np.float32).copy()),
+            "best_prior": torch.from_numpy(best_prior),
+            "best_scale": torch.from_numpy((np.searchsorted(off, best_prior, side="right") - 1).astype(np.int64)),
+            "held": torch.from_numpy(host[2 * G:3 * G].astype(np.int64)),
+            "pos": torch.from_numpy(host[3 * G:].astype(np.int64).reshape(G, T, S)),
+            "image": torch.from_numpy(plan["image"].copy())}
+
+
+def prior_fit(true_boxes, priors_cxcycz, thresholds, scale_ranges):
+    """What the matching of ``MultiBoxLoss`` gives every ground-truth box, for every threshold at once, on the HIP device
+    (``msl_prior_fit``: no (N,P) buffer).  ``true_boxes``: list of per-image (n_i,6) fractional corner boxes;
+    ``priors_cxcycz`` (P,6) on the device; ``scale_ranges``: ``LSSD3D.prior_ranges()``.  Per box, in packed order:
+    ``best_iou`` / ``best_prior`` (first maximum, before the force-match), ``best_scale`` (the range of that prior),
+    ``held`` (1: the box keeps its force-matched prior), ``pos[g, t, s]`` (positive priors of range s at threshold t that
+    train on box g; their sum over s is 0 for an orphaned box), ``image``."""
+    return run_prior_fit(prepare_prior_fit(true_boxes, priors_cxcycz.device if torch.is_tensor(priors_cxcycz) else None),
+                         priors_cxcycz, thresholds, scale_ranges)
+
+
+def _quantiles(values, qs):
+    v = np.asarray(values, dtype=np.float64)
+    return [float(x) for x in np.quantile(v, qs)] if v.size else [None] * len(qs)
+
+
+def prior_fit_summary(fit, true_boxes, voxels, size_edges, thresholds, shapes=None, scale_names=None):
+    """Host-side summary of a ``prior_fit`` result (G is small: numpy).  Lesion size and ``size_edges`` mean what they mean
+    in ``evaluate_strata``: bounding-box volume in f32 times ``voxels`` of the image (one value, or one per image), stratum
+    = number of edges <= size; ``size_edges`` may be empty (the "all" row only).  Per threshold: one row per stratum plus
+    "all", each with ``lesions``, ``matchable`` (best_iou >= thr), ``forced_only`` (best_iou < thr and held: positive only
+    through the force-match), ``orphaned`` (no positive prior), ``positives`` per lesion (mean / median / max),
+    ``positives_per_scale`` (sums), ``best_iou`` quantiles (min, 5 %, 25 %, 50 %); and ``positives_per_image`` (the mean
+    over ALL images: the loss normaliser).  ``extent``: box extents per axis (min, quartiles, max), in voxels when
+    ``shapes`` (one (D,H,W), or one per image) is given, else as fractions of the frame."""
+    boxes = _prior_fit_boxes(true_boxes)
+    N = len(boxes)
+    flat = np.concatenate(boxes) if boxes else np.zeros((0, 6), np.float32)
+    G = flat.shape[0]
+    img = np.repeat(np.arange(N), [b.shape[0] for b in boxes])
+    host = {k: _np(v) for k, v in fit.items()}
+    thr = _prior_fit_thresholds(thresholds)
+    pos = host["pos"].reshape(G, thr.size, -1).astype(np.int64)
+    best, held = host["best_iou"].astype(np.float32), host["held"].astype(np.int64)
+    S = pos.shape[2]
+    names = [str(s) for s in (scale_names if scale_names is not None else range(S))]
+    assert len(names) == S and best.shape == (G,) and np.array_equal(host["image"], img)
+    edges = strata_edges(size_edges) if len(list(size_edges)) else np.zeros(0)
+    stratum = size_stratum(_volume_f32(flat), _strata_voxels(voxels, N)[img], edges) if G else np.zeros(0, np.int64)
+    groups = [("all", np.ones(G, dtype=bool))]
+    if edges.size:
+        bounds = [0.0] + [float(e) for e in edges] + [float("inf")]
+        groups += [(f"[{bounds[s]:g}, {bounds[s + 1]:g})", stratum == s) for s in range(edges.size + 1)]
+    out = {"n_images": N, "n_lesions": G, "edges": [float(e) for e in edges], "scales": names, "thresholds": []}
+    for t in range(thr.size):
+        total = pos[:, t, :].sum(1)
+        rows = []
+        for name, m in groups:
+            n = int(m.sum())
+            rows.append({"stratum": name, "lesions": n,
+                         "matchable": int((best[m] >= thr[t]).sum()),
+                         "forced_only": int(((best[m] < thr[t]) & (held[m] == 1)).sum()),
+                         "orphaned": int((total[m] == 0).sum()),
+                         "positives": {"mean": float(total[m].mean()) if n else None,
+                                       "median": float(np.median(total[m])) if n else None,
+                                       "max": int(total[m].max()) if n else None},
+                         "positives_per_scale": {names[s]: int(pos[m, t, s].sum()) for s in range(S)},
+                         "best_iou": dict(zip(("min", "q05", "q25", "q50"), _quantiles(best[m], PRIOR_FIT_QUANTILES)))})
+        out["thresholds"].append({"threshold": float(thr[t]), "positives_per_image": int(total.sum()) / N if N else None,
+                                  "strata": rows})
+    ext = flat[:, 3:] - flat[:, :3]
+    if shapes is not None:
+        sh = np.asarray(shapes, dtype=np.float64).reshape(-1, 3)
+        ext = ext.astype(np.float64) * (np.broadcast_to(sh, (N, 3)) if sh.shape[0] == 1 else sh)[img]
+    out["extent"] = {"unit": "voxels" if shapes is not None else "fraction",
+                     "axes": [dict(zip(("min", "q25", "q50", "q75", "max"), _quantiles(ext[:, a], (0, .25, .5, .75, 1))))
+                              for a in range(3)]}
+    return out
+
+
 # ---- box overlays (utils.py:516-617, predict.py:186-220) ----------------------------------------------------------------
 DRAW_STYLES = {"edges": 0, "preds": 1}  # msl_draw_boxes's style argument
 

@@ -527,7 +527,21 @@ int msl_seg_boxes(const unsigned char* seg, int N, int D, int H, int W, int n_cl
  * (lo, hi) in order, the ids with lo <= id < hi in ascending order give inclusive extents / size with label = position + 1;
  * the first unique value of an image is discarded (the smallest id where there is no background); flat boxes dropped.
  * Outputs in msl_seg_boxes's layout.  *overflow (device): 0, |1 more boxes than capacity, |4 a negative value in seg;
- * obj_off stays <= capacity.  workspace: _workspace_bytes(N) bytes (0 = unsupported). */
+ * obj_off stays <= capacity.  workspace: _workspace_bytes(N) bytes (0 = unsupported).
+ * msl_binary_boxes: BoundingBoxesGeneratord "binary" mode (datasets.boxes_from_instances(seg, [(1, inf)], "binary")) on seg
+ * (N,D,H,W) i16: per image, the 6-connected components of the non-zero voxels (negative values count, as for
+ * scipy.ndimage.label) in scipy's order - by a component's first voxel in C raster order - give inclusive extents / size
+ * with label 1; an image without a background voxel yields no box (its one component is the first unique value, which
+ * is discarded); flat boxes - a one-voxel component among them - are dropped, by msl_instance_boxes's arithmetic.
+ * Outputs in msl_seg_boxes's layout; rows past obj_off[N] are not touched.  Run-based: the unit of the union-find is a
+ * run of consecutive non-zero voxels of a row, the mask is read twice (the second time only its rows with a run) and no
+ * per-voxel array is kept.  run_cap bounds the runs of the call (all images together).  *overflow (device): 0, |1 more
+ * boxes than capacity, |8 more runs than run_cap (the runs behind it are left out: the rows are then not the mask's);
+ * obj_off stays <= capacity and nothing is written outside the buffers.  Integer min / max atomics and order-free links
+ * only: the result does not depend on scheduling.  workspace: _workspace_bytes(N, D, H, W, run_cap) bytes =
+ * up(4 (N D H + 1)) + 4 up(4 run_cap) + up(20 run_cap) + up(4 N) + 256 with up() rounding to 256 (0 = unsupported).
+ * Returns -1 for null pointers, sizes <= 0, capacity < 0 or a workspace too small, -2 for N > 65535, N D H >= 2^31 - 2^16
+ * or run_cap > 2^31 / 5, nothing launched in either case. */
 int msl_foreground_box(const float* vol, int D, int H, int W, int margin, int* box, void* stream);
 int msl_augment_fit(const float* arena_img, const short* arena_seg, long long arena_elems, const long long* table,
                     int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
@@ -536,6 +550,10 @@ size_t msl_instance_boxes_workspace_bytes(int N);
 int msl_instance_boxes(const short* seg, int N, int D, int H, int W, const int* thresholds, int n_pairs, int capacity,
                        void* workspace, size_t workspace_bytes, float* boxes, long long* labels, int* obj_off,
                        int* overflow, void* stream);
+size_t msl_binary_boxes_workspace_bytes(int N, int D, int H, int W, int run_cap);
+int msl_binary_boxes(const short* seg, int N, int D, int H, int W, int capacity, int run_cap, void* workspace,
+                     size_t workspace_bytes, float* boxes, long long* labels, int* obj_off, int* overflow,
+                     void* stream);
 /* The same for cases of C sequences (1 <= C <= 4, the stem's limit; datasets.LesionsDataModule(input_images=...)).
  * msl_foreground_box_mc: msl_foreground_box on a channel-first (C,D,H,W) volume: F = {v : vol[c][v] > 0 for any c}, the
  * union of the channels' supports; one box for all channels.  C = 1 is msl_foreground_box.

@@ -144,6 +144,8 @@ _SIGNATURES = {
     "msl_augment_fit": (_I, [_P, _P, _Q, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_instance_boxes_workspace_bytes": (_Z, [_I]),
     "msl_instance_boxes": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
+    "msl_binary_boxes_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "msl_binary_boxes": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "msl_foreground_box_mc": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "msl_augment_fit_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_augment_window_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

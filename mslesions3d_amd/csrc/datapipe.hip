@@ -1002,6 +1002,17 @@ __global__ __launch_bounds__(DP_THREADS) void inst_extent_kernel(const short* __
   }
 }
 
+// The finalisation both clinical box routes (instances, binary) share: a box is kept where its inclusive integer extents
+// differ on every axis (then, and only then, the f32 volume product is not 0) and is written as f32(extent) / f32(size).
+__device__ __forceinline__ bool ext_has_volume(const int* e) { return e[3] > e[0] && e[4] > e[1] && e[5] > e[2]; }
+
+__device__ __forceinline__ void write_box_row(const int* e, const float* size, int row, int label,
+                                              float* __restrict__ boxes, long long* __restrict__ labels) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) boxes[(long long)row * 6 + j] = __fdiv_rn((float)e[j], size[j % 3]);
+  labels[row] = label;
+}
+
 // one workgroup: rows in (image, pair, ascending id) order.  The first unique value of an image is discarded: 0 where
 // there is background, the smallest id where there is none.
 __global__ __launch_bounds__(FIN_THREADS) void inst_final_kernel(const int* __restrict__ ext_all,
@@ -1028,15 +1039,11 @@ __global__ __launch_bounds__(FIN_THREADS) void inst_final_kernel(const int* __re
         if (id < hi) {
 #pragma unroll
           for (int j = 0; j < 6; ++j) e[j] = ext[(long long)id * 6 + j];
-          keep = id != lost && e[3] > e[0] && e[4] > e[1] && e[5] > e[2];  // absent ids have max -1 < min
+          keep = id != lost && ext_has_volume(e);  // absent ids have max -1 < min
         }
         int tot;
         const int row = carry + block_excl_scan(keep, lds, &tot);
-        if (keep && row < capacity) {
-#pragma unroll
-          for (int j = 0; j < 6; ++j) boxes[(long long)row * 6 + j] = __fdiv_rn((float)e[j], size[j % 3]);
-          labels[row] = pi + 1;
-        }
+        if (keep && row < capacity) write_box_row(e, size, row, pi + 1, boxes, labels);
         carry += tot;
       }
     }
@@ -1118,6 +1125,389 @@ int msl_instance_boxes(const short* seg, int N, int D, int H, int W, const int* 
     MSL_LAUNCH(inst_extent_kernel<false>, dim3(gx, N), dim3(DP_THREADS), 0, st, seg, V, H, W, ext, hdr, flags);
   MSL_LAUNCH(inst_final_kernel, dim3(1), dim3(FIN_THREADS), 0, st, (const int*)ext, (const int*)hdr, pairs, N, D, H, W,
              capacity, boxes, labels, obj_off, (const int*)flags, overflow);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+}  // extern "C"
+
+// ---- binary masks: run-based connected components -> boxes ----------------------------------------------------------
+// Host mirror: datasets.boxes_from_instances(seg, [(1, inf)], mode="binary") (scipy.ndimage.label, then the instance walk).
+// The unit of the union-find is a run of consecutive non-zero voxels of one row: the mask is
+// sparse, so everything behind the two dense reads scales with the number of runs, and no per-voxel array is kept.
+//
+//   count  : one wave per row (BIN_ROWS rows per round, their loads leaving back to back); a lane holds one aligned
+//            16-byte chunk of the row as a bit mask, a run starts where a set bit follows a clear one (the neighbour
+//            lane's last bit comes over a shuffle); the row's count is a plain store, a background voxel marks its image
+//   scan   : one workgroup, exclusive offsets of the N*D*H counts in place: runs are numbered in raster order
+//   write  : the count pass again on the rows that hold a run: the k-th start of a row is written by the lane that holds
+//            it and the k-th end by the lane that holds that (both ranks from one packed wave scan), so a run may cross
+//            lanes and spans without anybody walking along it
+//   union  : one thread per run: the runs of rows y-1 and z-1 that share a column (binary search for the first, then a
+//            walk while they overlap) are united, larger root under smaller: a component's root is its first run in
+//            raster order, which holds its first voxel: scipy's numbering
+//   fold   : one thread per run: integer min / max of its extents into the root's record (a wave whose runs share a root
+//            folds them first); min z needs no record, it is the root's own row
+//   final  : one workgroup ranks the roots of each image by the fixed-order scan, drops the first component of an image
+//            without background (np.unique(...)[1:]) and the flat boxes, writes the rows with the instance route's
+//            arithmetic
+namespace {
+
+constexpr int BIN_ROWS = 4;                // rows per wave and round
+constexpr int BIN_SPAN = 64 * INST_VEC;    // voxels a wave covers with one load per lane
+constexpr int BIN_EXT = 5;                 // ints per run: min y, min x, max z, max y, max x (of its component, at the root)
+constexpr int BIN_WAVES = DP_THREADS / 64;
+
+struct BinPlan {
+  size_t rowoff, rrow, rx0, rx1, link, ext, bg, hdr, total;
+};
+
+bool bin_supported(int N, int D, int H, int W, int run_cap) {
+  return N > 0 && D > 0 && H > 0 && W > 0 && run_cap > 0 && N <= 65535 && W <= 0x3FFFFFFF &&
+         (long long)N * D * H < 0x7FFF0000LL && (long long)run_cap * BIN_EXT < 0x7FFFFFF0LL;
+}
+
+// rowoff (N*D*H + 1), four ints per run (row, first x, last x, link), BIN_EXT ints per run, one int per image, header
+BinPlan bin_plan(int N, int D, int H, int run_cap) {
+  BinPlan p;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  size_t at = 0;
+  p.rowoff = at; at += up(((size_t)N * D * H + 1) * 4);
+  p.rrow = at; at += up((size_t)run_cap * 4);
+  p.rx0 = at; at += up((size_t)run_cap * 4);
+  p.rx1 = at; at += up((size_t)run_cap * 4);
+  p.link = at; at += up((size_t)run_cap * 4);
+  p.ext = at; at += up((size_t)run_cap * BIN_EXT * 4);
+  p.bg = at; at += up((size_t)N * 4);
+  p.hdr = at; at += 256;
+  p.total = at;
+  return p;
+}
+
+typedef short short8v __attribute__((ext_vector_type(8)));
+
+// eight voxels from global voxel g0 (a multiple of eight) of a buffer of `total` voxels; past the end reads as 0
+template <bool VEC>
+__device__ __forceinline__ short8v bin_load8(const short* __restrict__ seg, long long g0, long long total) {
+  if (VEC && g0 + INST_VEC <= total) return *reinterpret_cast<const short8v*>(seg + g0);
+  short8v v;
+#pragma unroll
+  for (int j = 0; j < INST_VEC; ++j) v[j] = g0 + j < total ? seg[g0 + j] : (short)0;
+  return v;
+}
+
+__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(v, d, 64);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(DP_THREADS) void bin_init_kernel(int* __restrict__ bg, int N) {
+  for (int i = blockIdx.x * DP_THREADS + threadIdx.x; i < N; i += gridDim.x * DP_THREADS) bg[i] = 0;
+}
+
+// WRITE = false: rowoff[r] = runs of row r, bg[n] = 1 where image n holds a zero.  WRITE = true: rowoff holds the scanned
+// offsets; the records of the runs below run_cap are written.  VEC: seg is 16-byte aligned (chunks are counted from the
+// start of the buffer, so a row may begin inside one: the voxels of a chunk outside the row are masked out).
+template <bool VEC, bool WRITE>
+__global__ __launch_bounds__(DP_THREADS) void bin_rows_kernel(const short* __restrict__ seg, int N, int D, int H, int W,
+                                                              int run_cap, int* __restrict__ rowoff,
+                                                              int* __restrict__ rrow, int* __restrict__ rx0,
+                                                              int* __restrict__ rx1, int* __restrict__ link,
+                                                              int* __restrict__ ext, int* __restrict__ bg) {
+  const int lane = threadIdx.x & 63;
+  const int DH = D * H;
+  const long long R = (long long)N * DH, total = R * W;
+  const long long step = (long long)gridDim.x * BIN_WAVES * BIN_ROWS;
+  int zimg = -1;
+  bool zero = false;
+  for (long long r0 = ((long long)blockIdx.x * BIN_WAVES + (threadIdx.x >> 6)) * BIN_ROWS; r0 < R; r0 += step) {
+    short8v xs[BIN_ROWS];
+    int base[BIN_ROWS], cnt[BIN_ROWS];
+#pragma unroll
+    for (int u = 0; u < BIN_ROWS; ++u) {  // the first loads of the round leave back to back
+      const long long r = r0 + u;
+      base[u] = 0;
+      cnt[u] = r < R;
+      if (WRITE && r < R) {
+        base[u] = rowoff[r];
+        cnt[u] = rowoff[r + 1] - base[u];  // a row without a run is not read again
+      }
+      xs[u] = (short8v)(short)0;
+      if (cnt[u] > 0) {
+        const long long g = r * W, gl = ((g >> 3) + lane) * INST_VEC;
+        if (gl < g + W) xs[u] = bin_load8<VEC>(seg, gl, total);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < BIN_ROWS; ++u) {  // (unrolled: xs stays in registers)
+      if (cnt[u] <= 0) continue;
+      const int r = (int)(r0 + u);
+      const long long g = (long long)r * W;
+      const int y = r % H, z = (r / H) % D, n = r / DH;
+      if (!WRITE && n != zimg) {  // a wave's rows ascend: one atomic per wave and image
+        if (__any(zero) && lane == 0) atomicMax(bg + zimg, 1);
+        zimg = n;
+        zero = false;
+      }
+      const int nspan = (int)(((g & 7) + W + BIN_SPAN - 1) / BIN_SPAN);
+      int carry_s = 0, carry_e = 0;
+      unsigned carry_prev = 0;
+      for (int s = 0; s < nspan; ++s) {
+        const long long gl = ((g >> 3) + (long long)s * 64 + lane) * INST_VEC;
+        short8v x = xs[u];
+        if (s > 0) {
+          x = (short8v)(short)0;
+          if (gl < g + W) x = bin_load8<VEC>(seg, gl, total);
+        }
+        // bits of the chunk that lie in the row
+        const long long lo = g - gl, hi = g + W - gl;
+        const int blo = lo > 0 ? (int)lo : 0, bhi = hi < INST_VEC ? (int)hi : INST_VEC;
+        const unsigned vmask = bhi > blo ? ((1u << bhi) - 1u) & ~((1u << blo) - 1u) : 0u;
+        unsigned nz = 0;
+#pragma unroll
+        for (int j = 0; j < INST_VEC; ++j) nz |= (x[j] != 0 ? 1u : 0u) << j;
+        const unsigned m = nz & vmask;
+        if (!WRITE) zero = zero || (vmask & ~nz) != 0;
+        if (__ballot(m != 0) == 0) {  // background: one read and nothing else
+          carry_prev = 0;
+          continue;
+        }
+        const unsigned up = (unsigned)__shfl_up((int)m, 1, 64);
+        const unsigned prev = lane ? (up >> 7) & 1u : carry_prev;
+        const unsigned starts = m & ~((m << 1) | prev) & 0xFFu;
+        carry_prev = ((unsigned)__shfl((int)m, 63, 64) >> 7) & 1u;
+        if (!WRITE) {
+          int c = __popc(starts);
+#pragma unroll
+          for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+          carry_s += c;
+        } else {
+          const unsigned dn = (unsigned)__shfl_down((int)m, 1, 64);
+          unsigned next = dn & 1u;
+          if (lane == 63) {  // the voxel behind the span decides whether a run ends at its last voxel
+            next = 0;
+            if ((m >> 7) && gl + INST_VEC < g + W) next = seg[gl + INST_VEC] != 0;
+          }
+          const unsigned ends = m & ~((m >> 1) | (next << 7));
+          const int packed = __popc(starts) | (__popc(ends) << 16);  // at most 256 of either per span
+          const int inc = wave_incl_scan(packed, lane);
+          const int tot = __shfl(inc, 63, 64);
+          int si = base[u] + carry_s + ((inc - packed) & 0xFFFF);
+          int ei = base[u] + carry_e + ((inc - packed) >> 16);
+          const int end = base[u] + cnt[u] < run_cap ? base[u] + cnt[u] : run_cap;
+          for (unsigned b = starts; b; b &= b - 1, ++si) {
+            if (si >= end) break;
+            const int xv = (int)(gl + (__ffs((int)b) - 1) - g);
+            rrow[si] = r;
+            rx0[si] = xv;
+            link[si] = si;
+            int* e = ext + (long long)si * BIN_EXT;
+            e[0] = y; e[1] = xv; e[2] = z; e[3] = y;
+          }
+          for (unsigned b = ends; b; b &= b - 1, ++ei) {
+            if (ei >= end) break;
+            const int xv = (int)(gl + (__ffs((int)b) - 1) - g);
+            rx1[ei] = xv;
+            ext[(long long)ei * BIN_EXT + 4] = xv;
+          }
+          carry_s += tot & 0xFFFF;
+          carry_e += tot >> 16;
+        }
+      }
+      if (!WRITE && lane == 0) rowoff[r] = carry_s;
+    }
+  }
+  if (!WRITE && __any(zero) && lane == 0) atomicMax(bg + zimg, 1);
+}
+
+// one workgroup: exclusive offsets of the R row counts in place, rowoff[R] = number of runs; eight rows per thread
+__global__ __launch_bounds__(SCAN_THREADS) void bin_scan_kernel(int* __restrict__ rowoff, int R, int run_cap,
+                                                                int* __restrict__ hdr) {
+  __shared__ int lds[33];
+  int carry = 0;
+  for (long long b = 0; b < R; b += SCAN_THREADS * 8) {
+    const long long i0 = b + (long long)threadIdx.x * 8;
+    int v[8], sum = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      v[k] = i0 + k < R ? rowoff[i0 + k] : 0;
+      sum += v[k];
+    }
+    int tot;
+    int at = carry + block_excl_scan(sum, lds, &tot);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (i0 + k < R) rowoff[i0 + k] = at;
+      at += v[k];
+    }
+    carry += tot;
+  }
+  if (threadIdx.x == 0) {
+    rowoff[R] = carry;
+    hdr[0] = carry > run_cap ? 8 : 0;
+  }
+}
+
+__device__ __forceinline__ void bin_unite_row(int i, int x0, int x1, int lo, int hi, const int* __restrict__ rx0,
+                                              const int* __restrict__ rx1, int* link) {
+  int a = lo, b = hi;  // the first run of the row that ends at or behind x0 (the runs of a row ascend)
+  while (a < b) {
+    const int mid = a + (b - a) / 2;
+    if (rx1[mid] < x0) a = mid + 1;
+    else b = mid;
+  }
+  for (int j = a; j < hi && rx0[j] <= x1; ++j) unite(link, i, j);
+}
+
+__global__ __launch_bounds__(DP_THREADS) void bin_union_kernel(const int* __restrict__ rowoff,
+                                                               const int* __restrict__ rrow, const int* __restrict__ rx0,
+                                                               const int* __restrict__ rx1, int* link, int D, int H,
+                                                               int R, int run_cap) {
+  const int total = rowoff[R] < run_cap ? rowoff[R] : run_cap;
+  for (int i = blockIdx.x * DP_THREADS + threadIdx.x; i < total; i += gridDim.x * DP_THREADS) {
+    const int r = rrow[i], x0 = rx0[i], x1 = rx1[i];
+    const int y = r % H, z = (r / H) % D;
+    if (y > 0) bin_unite_row(i, x0, x1, rowoff[r - 1], rowoff[r], rx0, rx1, link);  // (r < its own index: below the cap)
+    if (z > 0) bin_unite_row(i, x0, x1, rowoff[r - H], rowoff[r - H + 1], rx0, rx1, link);
+  }
+}
+
+__global__ __launch_bounds__(DP_THREADS) void bin_fold_kernel(const int* __restrict__ rowoff,
+                                                              const int* __restrict__ rrow, const int* __restrict__ rx0,
+                                                              const int* __restrict__ rx1, const int* link,
+                                                              int* __restrict__ ext, int D, int H, int R, int run_cap) {
+  const int total = rowoff[R] < run_cap ? rowoff[R] : run_cap;
+  const int stride = gridDim.x * DP_THREADS;
+  const int start = blockIdx.x * DP_THREADS + threadIdx.x;
+  const int iters = (total + stride - 1) / stride;  // the same for every lane: the wave stays converged
+  for (int it = 0; it < iters; ++it) {
+    const long long i = (long long)start + (long long)it * stride;
+    int root = -1, y = 0, z = 0, x0 = 0, x1 = 0;
+    if (i < total) {
+      const int q = find_root(link, (int)i);
+      if (q != (int)i) {  // a root's record already holds its own run
+        root = q;
+        const int r = rrow[i];
+        y = r % H; z = (r / H) % D; x0 = rx0[i]; x1 = rx1[i];
+      }
+    }
+    const unsigned long long act = __ballot(root >= 0);
+    if (act == 0) continue;
+    const int r0 = __shfl(root, __ffsll((long long)act) - 1, 64);
+    if (__all(root < 0 || root == r0)) {
+      const bool a = root >= 0;
+      const int my = wave_min(a ? y : IMAX), mx = wave_min(a ? x0 : IMAX);
+      const int Mz = wave_max(a ? z : -1), My = wave_max(a ? y : -1), Mx = wave_max(a ? x1 : -1);
+      if ((threadIdx.x & 63) == 0) {
+        int* e = ext + (long long)r0 * BIN_EXT;
+        atomicMin(e + 0, my); atomicMin(e + 1, mx); atomicMax(e + 2, Mz); atomicMax(e + 3, My); atomicMax(e + 4, Mx);
+      }
+    } else if (root >= 0) {
+      int* e = ext + (long long)root * BIN_EXT;
+      atomicMin(e + 0, y); atomicMin(e + 1, x0); atomicMax(e + 2, z); atomicMax(e + 3, y); atomicMax(e + 4, x1);
+    }
+  }
+}
+
+// one workgroup: per image its roots in run order (= scipy's label order), label 1.  An image without a background voxel is
+// one component, whose root is the image's first run: np.unique(...)[1:] drops it.
+__global__ __launch_bounds__(FIN_THREADS) void bin_final_kernel(const int* __restrict__ rowoff,
+                                                                const int* __restrict__ rrow,
+                                                                const int* __restrict__ link,
+                                                                const int* __restrict__ ext, const int* __restrict__ bg,
+                                                                const int* __restrict__ hdr, int N, int D, int H, int W,
+                                                                int run_cap, int capacity, float* __restrict__ boxes,
+                                                                long long* __restrict__ labels, int* __restrict__ obj_off,
+                                                                int* __restrict__ overflow) {
+  __shared__ int lds[33];
+  const float size[3] = {(float)D, (float)H, (float)W};
+  const int DH = D * H;
+  int carry = 0;
+  for (int n = 0; n < N; ++n) {
+    if (threadIdx.x == 0) obj_off[n] = carry < capacity ? carry : capacity;
+    int lo = rowoff[(long long)n * DH], hi = rowoff[(long long)(n + 1) * DH];
+    lo = lo < run_cap ? lo : run_cap;
+    hi = hi < run_cap ? hi : run_cap;
+    const int lost = bg[n] ? -1 : lo;
+    for (int b = lo; b < hi; b += FIN_THREADS) {
+      const int i = b + (int)threadIdx.x;
+      int keep = 0;
+      int e[6];
+      if (i < hi && link[i] == i && i != lost) {
+        e[0] = (rrow[i] / H) % D;  // the root is the component's first run in raster order: its row holds the smallest z
+        e[1] = ext[(long long)i * BIN_EXT + 0]; e[2] = ext[(long long)i * BIN_EXT + 1];
+        e[3] = ext[(long long)i * BIN_EXT + 2]; e[4] = ext[(long long)i * BIN_EXT + 3];
+        e[5] = ext[(long long)i * BIN_EXT + 4];
+        keep = ext_has_volume(e);
+      }
+      int tot;
+      const int row = carry + block_excl_scan(keep, lds, &tot);
+      if (keep && row < capacity) write_box_row(e, size, row, 1, boxes, labels);
+      carry += tot;
+    }
+  }
+  if (threadIdx.x == 0) {
+    obj_off[N] = carry < capacity ? carry : capacity;  // in bounds even on overflow (the flag says it happened)
+    *overflow = hdr[0] | (carry > capacity ? 1 : 0);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t msl_binary_boxes_workspace_bytes(int N, int D, int H, int W, int run_cap) {
+  return bin_supported(N, D, H, W, run_cap) ? bin_plan(N, D, H, run_cap).total : 0;
+}
+
+int msl_binary_boxes(const short* seg, int N, int D, int H, int W, int capacity, int run_cap, void* workspace,
+                     size_t workspace_bytes, float* boxes, long long* labels, int* obj_off, int* overflow,
+                     void* stream) {
+  if (!seg || !workspace || !boxes || !labels || !obj_off || !overflow || capacity < 0) return MSL_ERR_ARG;
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || run_cap <= 0) return MSL_ERR_ARG;
+  if (!bin_supported(N, D, H, W, run_cap)) return MSL_ERR_UNSUPPORTED;
+  const BinPlan p = bin_plan(N, D, H, run_cap);
+  if (workspace_bytes < p.total || ((uintptr_t)workspace & 3) != 0 || ((uintptr_t)seg & 1) != 0) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  int* rowoff = (int*)(ws + p.rowoff);
+  int* rrow = (int*)(ws + p.rrow);
+  int* rx0 = (int*)(ws + p.rx0);
+  int* rx1 = (int*)(ws + p.rx1);
+  int* link = (int*)(ws + p.link);
+  int* ext = (int*)(ws + p.ext);
+  int* bg = (int*)(ws + p.bg);
+  int* hdr = (int*)(ws + p.hdr);
+  const int R = N * D * H;
+  const long long rounds = ((long long)R + BIN_WAVES * BIN_ROWS - 1) / (BIN_WAVES * BIN_ROWS);
+  const dim3 rgrid((unsigned)(rounds < 2048 ? rounds : 2048));
+  const dim3 ugrid(grid_for(run_cap));
+  const bool vec = ((uintptr_t)seg & 15) == 0;
+  MSL_LAUNCH(bin_init_kernel, dim3(grid_for(N)), dim3(DP_THREADS), 0, st, bg, N);
+  if (vec)
+    MSL_LAUNCH(bin_rows_kernel<true, false>, rgrid, dim3(DP_THREADS), 0, st, seg, N, D, H, W, run_cap, rowoff, rrow, rx0,
+               rx1, link, ext, bg);
+  else
+    MSL_LAUNCH(bin_rows_kernel<false, false>, rgrid, dim3(DP_THREADS), 0, st, seg, N, D, H, W, run_cap, rowoff, rrow,
+               rx0, rx1, link, ext, bg);
+  MSL_LAUNCH(bin_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, rowoff, R, run_cap, hdr);
+  if (vec)
+    MSL_LAUNCH(bin_rows_kernel<true, true>, rgrid, dim3(DP_THREADS), 0, st, seg, N, D, H, W, run_cap, rowoff, rrow, rx0,
+               rx1, link, ext, bg);
+  else
+    MSL_LAUNCH(bin_rows_kernel<false, true>, rgrid, dim3(DP_THREADS), 0, st, seg, N, D, H, W, run_cap, rowoff, rrow, rx0,
+               rx1, link, ext, bg);
+  MSL_LAUNCH(bin_union_kernel, ugrid, dim3(DP_THREADS), 0, st, (const int*)rowoff, (const int*)rrow, (const int*)rx0,
+             (const int*)rx1, link, D, H, R, run_cap);
+  MSL_LAUNCH(bin_fold_kernel, ugrid, dim3(DP_THREADS), 0, st, (const int*)rowoff, (const int*)rrow, (const int*)rx0,
+             (const int*)rx1, (const int*)link, ext, D, H, R, run_cap);
+  MSL_LAUNCH(bin_final_kernel, dim3(1), dim3(FIN_THREADS), 0, st, (const int*)rowoff, (const int*)rrow,
+             (const int*)link, (const int*)ext, (const int*)bg, (const int*)hdr, N, D, H, W, run_cap, capacity, boxes,
+             labels, obj_off, overflow);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

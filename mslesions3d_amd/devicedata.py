@@ -14,7 +14,8 @@ AFFINE_MAX_OPS intensity operations raise NotImplementedError.
 
 ``LesionCache`` is the counterpart for ``datasets.LesionsDataModule``: cases of unequal shape, cropped to their
 foreground, in one flat arena; shape-changing rot90s allowed; every batch padded / cropped to one fixed size and its
-instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes).  A module with
+instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes); binary masks
+(``segmentation_mode == "binary"``) are labelled per batch by msl_binary_boxes instead.  A module with
 C > 1 input sequences is cached channel-planar and goes through msl_foreground_box_mc / msl_augment_fit_mc.  A case that
 carries an affine is uploaded on its native grid and put on the LPI 1 mm grid by msl_regrid (``regrid_device``, the
 device form of ``datasets.regrid``, bit for bit) in front of the foreground box.  A module with a ``patch_size`` (patch
@@ -516,6 +517,72 @@ def boxes_from_instances_device(seg, thresholds, capacity=None):
             (out.gb, out.gl, out.obj_off, capacity))
 
 
+MAX_RUNS_PER_IMAGE = 262144  # msl_binary_boxes: runs of non-zero voxels per image (about ten times a 50 mL lesion load)
+
+
+class _BinBoxOut:
+    """Packed targets + workspace of msl_binary_boxes for one (N, D, H, W, capacity, run_cap): ``_InstBoxOut``'s
+    attributes, for binary masks (their 6-connected components are the lesions)."""
+
+    def __init__(self, N, shape, capacity, dev, max_runs_per_image=MAX_RUNS_PER_IMAGE):
+        lib = _lib.load()
+        self.N, self.shape, self.capacity = N, tuple(shape), capacity
+        self.run_cap = int(max_runs_per_image) * N
+        nbytes = lib.msl_binary_boxes_workspace_bytes(N, *self.shape, self.run_cap) if self.run_cap > 0 else 0
+        if nbytes == 0:
+            raise _lib.HipKernelError(f"msl_binary_boxes: unsupported sizes N={N} shape={self.shape} "
+                                      f"max_runs_per_image={max_runs_per_image}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.gb = torch.zeros((max(capacity, 1), 6), dtype=torch.float32, device=dev)
+        self.gl = torch.ones(max(capacity, 1), dtype=torch.int64, device=dev)
+        self.obj_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.flag_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+
+    def launch(self, seg, stream):
+        _lib.call("msl_binary_boxes", ptr(seg), self.N, *self.shape, self.capacity, self.run_cap, ptr(self.ws),
+                  self.ws.numel(), ptr(self.gb), ptr(self.gl), ptr(self.obj_off), ptr(self.flag), stream)
+        self.flag_host.copy_(self.flag, non_blocking=True)  # read after the next synchronising read: no sync of its own
+
+    def raise_on_overflow(self, flag=None):
+        f = int(self.flag_host.item() if flag is None else flag)
+        if f & 8:
+            raise _lib.HipKernelError(f"msl_binary_boxes: a batch holds more runs of lesion voxels than "
+                                      f"max_runs_per_image = {self.run_cap // self.N} per image allows: raise "
+                                      f"max_runs_per_image")
+        if f & 1:
+            raise _lib.HipKernelError(f"msl_binary_boxes: a batch holds more ground-truth boxes than the capacity of "
+                                      f"{self.capacity} rows: raise max_objects_per_image")
+
+
+def boxes_from_binary_device(seg, capacity=None, max_runs_per_image=MAX_RUNS_PER_IMAGE):
+    """``datasets.boxes_from_instances(seg[n], [(1, inf)], mode="binary")`` for every image of a device int16
+    (N, D, H, W) mask -> (boxes list, labels list, (gb, gl, obj_off, capacity)) as ``boxes_from_instances_device``
+    returns them."""
+    if not seg.is_cuda or seg.dtype != torch.int16 or seg.dim() != 4:
+        raise _lib.HipKernelError("boxes_from_binary_device takes an int16 (N, D, H, W) tensor on the HIP device")
+    seg = seg.contiguous()
+    N = seg.shape[0]
+    capacity = 1024 * N if capacity is None else int(capacity)
+    out = _BinBoxOut(N, seg.shape[1:], capacity, seg.device, max_runs_per_image)
+    out.launch(seg, _stream(seg.device))
+    off = out.obj_off.cpu().tolist()
+    out.raise_on_overflow(out.flag.item())
+    return ([out.gb[off[n]:off[n + 1]] for n in range(N)], [out.gl[off[n]:off[n + 1]] for n in range(N)],
+            (out.gb, out.gl, out.obj_off, capacity))
+
+
+def _box_stage(dataset, N, shape, capacity, dev, max_runs_per_image=MAX_RUNS_PER_IMAGE, who="device pipeline"):
+    """The box stage of a data module's segmentation mode for (N,) + shape masks: msl_instance_boxes on instance-labelled
+    masks, msl_binary_boxes on binary ones."""
+    mode = dataset.segmentation_mode
+    if mode == "instances":
+        return _InstBoxOut(N, shape, dataset.thresholds, capacity, dev)
+    if mode == "binary":
+        return _BinBoxOut(N, shape, capacity, dev, max_runs_per_image)
+    raise NotImplementedError(f"{who}: no device box stage for segmentation mode {mode!r}")
+
+
 def fit_rows(cases, per_sample):
     """-> (N, AFFINE_STRIDE) f64 rows of one msl_augment_fit launch: per sample its case and the (perm, stages) of
     ``sample_params(..., ragged=True)``: at most one affine stage, then the intensity operations."""
@@ -606,7 +673,7 @@ class LesionCache:
     (``centres``).  ``val_batches`` yields the tiles of ``datasets._LesionTiles`` (every validation case is cached on every
     rank: the tile list, not the case list, is what the ranks share out), ``batch_size`` tiles at a time."""
 
-    def __init__(self, dataset, device, max_objects_per_image=64):
+    def __init__(self, dataset, device, max_objects_per_image=64, max_runs_per_image=MAX_RUNS_PER_IMAGE):
         if dataset.train_dataset is None:
             raise ValueError("LesionCache needs a data module after setup()")
         self.dataset, self.device = dataset, torch.device(device)
@@ -619,8 +686,10 @@ class LesionCache:
         if names.count("affine") > 1:
             raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
         sample_params([(n, None) for n in names], (1, 1, 1), self.augmentations, ragged=True)  # the order limits
-        if dataset.segmentation_mode != "instances":
-            raise NotImplementedError("LesionCache: the device pipeline labels instance masks ('labeled' segmentations)")
+        if dataset.segmentation_mode not in ("instances", "binary"):
+            raise NotImplementedError(f"LesionCache: no device box stage for segmentation mode "
+                                      f"{dataset.segmentation_mode!r}")
+        self.max_runs_per_image = int(max_runs_per_image)
         tr, te = dataset.train_dataset, dataset.test_dataset
         if self.patch is not None:
             te = te.cases  # datasets._LesionTiles: its tiles are dealt to the ranks below, once the crop shapes are known
@@ -682,15 +751,18 @@ class LesionCache:
             self.val_tiles = tiles  # (subject, slot, origin): this rank's share of dataset.test_dataset.tiles
 
     def _case_centres(self, slot):
-        """``datasets.lesion_centres`` of a cached case -> f64 (K, 3): one msl_instance_boxes call on the cropped mask,
-        read back once.  The kernel writes f32(e / n) for an inclusive integer extent e on an axis of n voxels; the extent
+        """``datasets.lesion_centres`` of a cached case -> f64 (K, 3): one msl_instance_boxes call (msl_binary_boxes on
+        a binary mask: the components of the cropped, un-augmented mask) on the cropped mask, read back once.  The kernel writes f32(e / n) for an inclusive integer extent e on an axis of n voxels; the extent
         is recovered as rint(f32(e / n) * n) in f64.  The division's relative error is at most 2^-24 and the f64 product
         adds 2^-53, so the product is within e * 2^-23 of e: exact while e < 2^22, and the arena refuses axes of 2^20
         voxels or more."""
         shape = self.shapes[slot]
         if not int(np.prod(shape)):
             return np.zeros((0, 3), dtype=np.float64)
-        out = _InstBoxOut(1, shape, self.dataset.thresholds, INST_MAX_IDS, self.device)
+        if self.dataset.segmentation_mode == "binary":
+            out = _BinBoxOut(1, shape, INST_MAX_IDS, self.device, self.max_runs_per_image)
+        else:
+            out = _InstBoxOut(1, shape, self.dataset.thresholds, INST_MAX_IDS, self.device)
         out.launch(self.case(slot)[1], _stream(self.device))
         n = out.obj_off.cpu().tolist()[1]  # (synchronises: the flag and the rows are there too)
         out.raise_on_overflow(out.flag.item())
@@ -732,7 +804,8 @@ class LesionCache:
             dev = self.device
             b = self._bufs[N] = {"img": torch.empty((N, self.channels) + self.target, dtype=torch.float32, device=dev),
                                  "seg": torch.empty((N,) + self.target, dtype=torch.int16, device=dev),
-                                 "box": _InstBoxOut(N, self.target, self.dataset.thresholds, self.capacity, dev)}
+                                 "box": _box_stage(self.dataset, N, self.target, self.capacity, dev,
+                                                   self.max_runs_per_image, "LesionCache")}
         return b
 
     def _run(self, slots, per_sample, b, windows=None):
@@ -856,11 +929,9 @@ class LesionPredictFeed:
     has synchronised the stream, so the feed prepares one case ahead of the one it hands out.  With
     ``LSSD3D.predict_batches(feed.batches(), depth)`` at most depth + 1 cases are resident."""
 
-    def __init__(self, dataset, device, max_objects_per_image=64):
+    def __init__(self, dataset, device, max_objects_per_image=64, max_runs_per_image=MAX_RUNS_PER_IMAGE):
         if dataset.predict_dataset is None:
             raise ValueError("LesionPredictFeed needs a data module after setup()")
-        if dataset.segmentation_mode != "instances":
-            raise NotImplementedError("LesionPredictFeed: the device pipeline labels instance masks ('labeled' segmentations)")
         self.dataset, self.device = dataset, torch.device(device)
         self.target, self.channels = tuple(dataset.spatial_size), len(dataset.input_images)
         self.capacity = int(max_objects_per_image)
@@ -869,7 +940,8 @@ class LesionPredictFeed:
         self._row = torch.from_numpy(fit_rows([0], [(([0, 1, 2], [0, 0, 0]), [])]).reshape(-1)).to(dev)  # the identity row
         self._slots = [{"img": torch.empty((1, C) + self.target, dtype=torch.float32, device=dev),
                         "seg": torch.empty((1,) + self.target, dtype=torch.int16, device=dev),
-                        "box": _InstBoxOut(1, self.target, dataset.thresholds, self.capacity, dev),
+                        "box": _box_stage(dataset, 1, self.target, self.capacity, dev, max_runs_per_image,
+                                          "LesionPredictFeed"),
                         "gb": torch.zeros((max(self.capacity, 1), 6), dtype=torch.float32, pin_memory=True),
                         "gl": torch.zeros(max(self.capacity, 1), dtype=torch.int64, pin_memory=True),
                         "off": torch.zeros(2, dtype=torch.int32, pin_memory=True)} for _ in range(2)]

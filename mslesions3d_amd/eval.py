@@ -72,6 +72,7 @@ def build_parser():
     p.add_argument('--spatial_size', type=int, nargs=3, default=S, metavar=('D', 'H', 'W'),
                    help="as predict.py (default: 250 300 300)")
     p.add_argument('-ii', '--input_images', type=str, nargs='+', default=S, help="as predict.py (default: FLAIR)")
+    p.add_argument('--segmentation', type=str, default=S, metavar='NAME', help="as predict.py (default: labeled_lesions)")
     return p
 
 
@@ -100,7 +101,8 @@ def size_bin_list(text):
 
 
 EVAL_DEFAULTS = {"size_bins": None, "froc": False, "froc_rates": None, "bootstrap": 0, "bootstrap_seed": 0, "data_module": "example",
-                 "centers": ('CHUV_RIM_OK', 'BASEL_INSIDER_OK'), "spatial_size": (250, 300, 300), "input_images": ("FLAIR",)}
+                 "centers": ('CHUV_RIM_OK', 'BASEL_INSIDER_OK'), "spatial_size": (250, 300, 300), "input_images": ("FLAIR",),
+                 "segmentation": "labeled_lesions"}
 
 
 def eval_options(args):
@@ -264,16 +266,18 @@ def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_wo
     """eval.py:61-151 for every (min_iou, confidence_threshold) pair of the given values (a number or a list each).
     Returns ``{(iou, score): detail dict}``.  ``options``: an ``eval_options`` namespace (FROC, clinical cases)."""
     from .datasets import ExampleDataset
+    from .train import segmentation_of
     from .utils import evaluate_detections
+    opt = eval_options(argparse.Namespace() if options is None else options)
+    segmentation_of(opt)  # before the first GPU call: a refused command line touches no device
     if not torch.cuda.is_available():
         raise RuntimeError("mslesions3d_amd.eval needs the HIP device (no host fallback)")
-    opt = eval_options(argparse.Namespace() if options is None else options)
     ious, scores = as_list(min_iou), as_list(confidence_threshold)
     lesions = opt.data_module == "lesions"
     if lesions:
         from .datasets import LesionsDataModule
         dataset = LesionsDataModule(data_dir=dataset_path, centers=tuple(opt.centers), batch_size=1,
-                                    input_images=tuple(opt.input_images),
+                                    input_images=tuple(opt.input_images), segmentation=opt.segmentation,
                                     classes=("lesion",) if n_classes == 1 else ("lesion", "lesion_2"),
                                     num_workers=num_workers, percentage=percentage, spatial_size=tuple(opt.spatial_size))
     else:

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .eval import BATCH, batch_voxels, float_list, size_bin_list
-from .train import input_images_of, patch_options_of
+from .train import input_images_of, patch_options_of, segmentation_of
 
 MAX_DRAWN_PRIORS = 32766  # utils.draw_boxes: int16 ids
 
@@ -46,6 +46,8 @@ def build_parser():
     p.add_argument('--centers', type=str, nargs='+', default=['CHUV_RIM_OK', 'BASEL_INSIDER_OK'])
     p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
     p.add_argument('-ii', '--input_images', type=str, nargs='+', default=["FLAIR"])
+    p.add_argument('--segmentation', type=str, default="labeled_lesions", metavar='NAME',
+                   help="as train.py: a mask name without 'labeled' in it is a binary mask")
     p.add_argument('-ps', '--predict_subset', type=str, choices=['train', 'validation', 'test', 'all'], default=r'train')
     p.add_argument('-nw', '--num_workers', type=int, default=0)
     p.add_argument('--patch_size', type=int, nargs=3, default=None, metavar=('D', 'H', 'W'))
@@ -64,6 +66,7 @@ def check_options(args):
     options, thresholds, scale factors)."""
     input_images = input_images_of(args)
     patch_options = patch_options_of(args)
+    segmentation_of(args)
     thr = [float(t) for t in args.threshold]
     if not 1 <= len(thr) <= 2 or any(not 0.0 <= t <= 1.0 for t in thr) or thr != sorted(thr):
         raise ValueError(f"-th takes one threshold or an ascending [lo, hi] band inside [0, 1], got {args.threshold}")
@@ -89,7 +92,8 @@ def gather_ground_truth(args, input_images, patch_options):
     boxes, voxels = [], []
     if args.data_module == "lesions":
         module = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), batch_size=1,
-                                   input_images=input_images, num_workers=args.num_workers, percentage=args.percentage,
+                                   input_images=input_images, segmentation=segmentation_of(args),
+                                   num_workers=args.num_workers, percentage=args.percentage,
                                    spatial_size=tuple(args.spatial_size), **patch_options)
         module.setup(stage=stage)
         cases = module.predict_dataset

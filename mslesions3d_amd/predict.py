@@ -63,6 +63,9 @@ def build_parser():
     # namespace of a command without them is the one every caller of the single-view route has always seen; the route
     # reads them through view_options(), where the defaults (VIEW_DEFAULTS) live
     S = argparse.SUPPRESS
+    p.add_argument('--segmentation', type=str, default=S, metavar='NAME',
+                   help="the mask of a clinical case, as train.py: a name without 'labeled' in it is a binary mask "
+                        "(default: labeled_lesions)")
     p.add_argument('--views', choices=["fit", "tiles"], default=S,
                    help="tiles: a case larger than the input size is covered by overlapping tiles instead of being "
                         "centre-cropped; their detections are merged in the case's own frame (default: fit)")
@@ -231,9 +234,10 @@ def predict_example(args):
     subjects are dealt round-robin over N replicas (one GPU each) and rank 0 writes the files and the metrics."""
     from .datasets import ExampleDataset, LesionsDataModule, ShardSampler
     from .ssd3d import LSSD3D
-    from .train import check_input_channels, input_images_of
+    from .train import check_input_channels, input_images_of, segmentation_of
     from .utils import calculate_mAP
     input_images = input_images_of(args)
+    segmentation = segmentation_of(args)
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     if world > 1:
         from .parallel import init_distributed
@@ -254,7 +258,7 @@ def predict_example(args):
         cache = False
     if lesions:
         dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), batch_size=1,
-                                    input_images=input_images,
+                                    input_images=input_images, segmentation=segmentation,
                                     classes=("lesion",) if args.n_classes == 1 else ("lesion", "lesion_2"),
                                     num_workers=args.num_workers, subject=args.subject, percentage=args.percentage,
                                     spatial_size=tuple(args.spatial_size))

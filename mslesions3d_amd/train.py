@@ -66,6 +66,9 @@ def build_parser():
     p.add_argument('--spatial_size', type=int, nargs=3, default=[250, 300, 300], metavar=('D', 'H', 'W'))
     # the MR sequences of a clinical case, one input channel each (1 .. 4); the synthetic cases have one channel
     p.add_argument('-ii', '--input_images', type=str, nargs='+', default=["FLAIR"])
+    # the mask of a clinical case: a name with "labeled" in it is instance-labelled, any other name is a binary mask whose
+    # 6-connected components are the lesions (the reference's BoundingBoxesGeneratord "binary" mode)
+    p.add_argument('--segmentation', type=str, default=DEFAULT_SEGMENTATION, metavar='NAME')
     # patch training (-dm lesions only): one sampled window of this size per case and epoch
     # instead of the fit to --spatial_size, validation on the tiles `predict --views tiles` shows the network
     p.add_argument('--patch_size', type=int, nargs=3, default=None, metavar=('D', 'H', 'W'))
@@ -120,6 +123,18 @@ def input_images_of(args):
     return names
 
 
+DEFAULT_SEGMENTATION = "labeled_lesions"
+
+
+def segmentation_of(args):
+    """The mask named by --segmentation; another name than the default with the synthetic data module is an error (its
+    cases carry class masks of their own)."""
+    name = getattr(args, "segmentation", None) or DEFAULT_SEGMENTATION
+    if getattr(args, "data_module", "example") != "lesions" and name != DEFAULT_SEGMENTATION:
+        raise ValueError(f"--segmentation names the mask of clinical cases: it needs -dm lesions, got {name!r}")
+    return name
+
+
 def patch_options_of(args):
     """--patch_size / --patch_foreground / --tile_margin as LesionsDataModule keywords; {} without --patch_size.  Patch
     training with the synthetic data module is an error (its cubes are the network's input already)."""
@@ -171,6 +186,7 @@ def example(args):
     from .trainer import FusedTrainer
     input_images = input_images_of(args)  # before the first GPU call: a refused command line touches no device
     patch_options = patch_options_of(args)
+    segmentation = segmentation_of(args)
     world, rank, local = _dist_env()
     dp = world > 1
     if dp:  # join the job BEFORE the first GPU call of this process (RCCL binds the communicator to the device)
@@ -189,7 +205,7 @@ def example(args):
     lesions = getattr(args, "data_module", "example") == "lesions"
     if lesions:
         dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), subject=args.subject,
-                                    input_images=input_images,
+                                    input_images=input_images, segmentation=segmentation,
                                     classes=("lesion",) if args.n_classes == 1 else ("lesion", "lesion_2"),
                                     percentage=args.percentage, num_workers=args.num_workers, batch_size=args.batch_size,
                                     augmentations=augmentations, random_state=970205,

@@ -561,8 +561,9 @@ int msl_binary_boxes(const short* seg, int N, int D, int H, int W, int capacity,
  * i16 elements; table: element offset off_k and shape of case k).  arena_img holds C * seg_elems floats: case k is C
  * contiguous planes of n0*n1*n2 voxels starting at element C * off_k.  dst_img (N,C,T0,T1,T2) f32, dst_seg (N,T0,T1,T2)
  * i16.  One set of params per sample: the geometry and the mask are computed once and every channel is resampled with
- * it, then given the same intensity operations; each plane is bit-identical to msl_augment_fit on that plane alone.  A row
- * whose case, axes or table entry are invalid (the case must end at or before seg_elems) writes zeros to all C planes. */
+ * it, then given the same intensity operations; each plane is bit-identical to a C = 1 launch on that plane alone, which
+ * is what msl_augment_fit is (the same kernel with seg_elems = arena_elems, C = 1).  A row whose case, axes or table entry
+ * are invalid (the case must end at or before seg_elems) writes zeros to all C planes. */
 int msl_foreground_box_mc(const float* vol, int C, int D, int H, int W, int margin, int* box, void* stream);
 int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
                        int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,

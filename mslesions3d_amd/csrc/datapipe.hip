@@ -690,14 +690,28 @@ int msl_seg_boxes(const unsigned char* seg, int N, int D, int H, int W, int n_cl
 
 }  // extern "C"
 
-// ---- clinical cases: foreground box, ragged augment + fit, instance boxes ---------------------------------------------
-// Host mirrors: datasets.foreground_box, datasets._LesionCases.__getitem__ (augmentations at the cropped shape, then
-// resize_with_pad_or_crop with edge replication) and datasets.boxes_from_instances.
+// ---- clinical cases of C sequences (1 <= C <= 4): foreground box, ragged augment + fit / window, instance boxes ---------
+// Host mirrors: datasets.foreground_box on a (D, H, W) or channel-first (C, D, H, W) image, datasets._LesionCases
+// .__getitem__ with len(input_images) = C (augmentations at the cropped shape, then resize_with_pad_or_crop with edge
+// replication) and datasets.boxes_from_instances.  The mask arena and the table are the same for every C; the image arena
+// holds C contiguous planes per case, case k at element C * off_k.  There is one kernel of each kind: the one-channel
+// entry points (msl_foreground_box, msl_augment_fit) are its C = 1 launch.
 //
-//   foreground : one wave per (d, h) row; the w extents stay in the lanes, the d / h extents are wave-uniform; six integer
-//                atomics per wave, then one thread applies margin, clamp and the empty rule
-//   fit        : one thread per four output voxels along the last axis; the fit is a clamped shift per axis, the
-//                permutation / affine / intensity arithmetic is affine_kernel's; image stored as one 16-byte vector
+//   foreground : one wave per row of the C * D * H rows; the w extents stay in the lanes, the d / h extents are
+//                wave-uniform; a row of any channel that holds a positive voxel extends the one box (the union of the
+//                channels' supports); six integer atomics per wave, then one thread applies margin, clamp and the empty
+//                rule
+//   fit        : one thread per four output voxels along the last axis, for all C channels; the fit is a clamped shift
+//                per axis, the permutation / affine / intensity arithmetic is affine_kernel's.  The clamp of the fit, the
+//                f64 coordinate row, the boundary maps, the axis weights and the order-0 mask tap are computed once per
+//                voxel; only the eight gathers, the f64 accumulation and the intensity operations repeat per channel,
+//                each in the same operation order (a channel is bit-identical to a C = 1 launch on its plane); every
+//                plane of the image stored as one 16-byte vector
+//   window     : the same body (WIN) with the shift d read per sample from `windows` instead of centred: a training patch
+//                or a validation tile (datasets.window, DESIGN.md section 4.12).  With the affine off, a thread whose four
+//                sources are one in-range run of an unreversed last axis reads them with one 16-byte load per plane and
+//                one 8-byte load of the mask where those addresses are aligned (views.hip's rule) - a patch inside a
+//                large head is that case nearly everywhere
 //   instances  : one 16-byte load per eight voxels, nothing else while they are all background; runs of one id are
 //                folded in registers before the integer min / max atomics into a per-image (32768, 6) extent table;
 //                one workgroup compacts it in (image, threshold pair, ascending id) order by a fixed-order scan
@@ -705,6 +719,7 @@ namespace {
 
 constexpr int FG_THREADS = 256;
 constexpr int FIT_VEC = 4;            // output voxels per thread
+constexpr int FIT_MAX_CH = 4;         // the stem's limit
 constexpr int INST_IDS = 32768;       // ids 1 .. 32767 (int16)
 constexpr int INST_VEC = 8;           // voxels per 16-byte load
 constexpr int INST_UNROLL = 4;        // loads in flight per thread
@@ -716,10 +731,10 @@ __global__ void fg_init_kernel(int* __restrict__ box) {
   if (threadIdx.x < 6) box[threadIdx.x] = threadIdx.x < 3 ? IMAX : -1;
 }
 
-__global__ __launch_bounds__(FG_THREADS) void fg_reduce_kernel(const float* __restrict__ vol, int D, int H, int W,
+__global__ __launch_bounds__(FG_THREADS) void fg_reduce_kernel(const float* __restrict__ vol, int C, int D, int H, int W,
                                                                int* __restrict__ box) {
   const int lane = threadIdx.x & 63;
-  const long long rows = (long long)D * H;
+  const long long rows = (long long)C * D * H;
   const long long nwave = (long long)gridDim.x * (FG_THREADS / 64);
   int lo_d = IMAX, lo_h = IMAX, lo_w = IMAX, hi_d = -1, hi_h = -1, hi_w = -1;
   for (long long r = (long long)blockIdx.x * (FG_THREADS / 64) + (threadIdx.x >> 6); r < rows; r += nwave) {
@@ -733,7 +748,9 @@ __global__ __launch_bounds__(FG_THREADS) void fg_reduce_kernel(const float* __re
       }
     }
     if (__any(any)) {  // wave-uniform
-      const int d = (int)(r / H), h = (int)(r % H);
+      long long cd = r / H;  // c * D + d with c < C <= FIT_MAX_CH: d by subtraction, not a second 64-bit division
+      while (cd >= D) cd -= D;
+      const int d = (int)cd, h = (int)(r % H);
       lo_d = min(lo_d, d); hi_d = max(hi_d, d);
       lo_h = min(lo_h, h); hi_h = max(hi_h, h);
     }
@@ -763,15 +780,38 @@ __global__ void fg_final_kernel(int D, int H, int W, int margin, int* __restrict
   }
 }
 
-// table (n_cases, 4) i64 per case: element offset into both arenas, shape n0, n1, n2.  params: msl_augment_affine's rows
-// with [0] = case.  Output voxel o of the (T0, T1, T2) target reads voxel q of the permuted case (shape n'), q_a =
-// clamp(o_a + d_a, 0, n'_a - 1), d_a = -((t_a - n'_a) / 2) if n'_a < t_a else n'_a / 2 - t_a / 2; with the affine on, the
-// permuted case is sampled at M q + offset as affine_kernel samples it.
-template <bool VEC>
+// the three launches of a foreground box over the C * D * H rows of a channel-first volume
+int foreground_box(const float* vol, int C, int D, int H, int W, int margin, int* box, void* stream) {
+  if (!vol || !box || C < 1 || C > FIT_MAX_CH || D <= 0 || H <= 0 || W <= 0 || margin < 0) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long waves = ((long long)C * D * H + 3) / 4;
+  MSL_LAUNCH(fg_init_kernel, dim3(1), dim3(64), 0, st, box);
+  // the six atomics of every wave hit the same six words: few waves, many rows each
+  MSL_LAUNCH(fg_reduce_kernel, dim3((unsigned)(waves < 512 ? waves : 512)), dim3(FG_THREADS), 0, st, vol, C, D, H, W, box);
+  MSL_LAUNCH(fg_final_kernel, dim3(1), dim3(64), 0, st, D, H, W, margin, box);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+// source index of output index o under the shift d on an axis of n voxels.  The fit's d is bounded by the sizes; a window's
+// origin is any int (far outside the case it repeats the border voxel), so that sum is formed in 64 bits
+template <bool WIN>
+__device__ __forceinline__ int fit_src(int o, int d, int n) {
+  if (!WIN) return min(max(o + d, 0), n - 1);
+  const long long q = (long long)o + d;
+  return q < 0 ? 0 : (q > n - 1 ? n - 1 : (int)q);
+}
+
+// table (n_cases, 4) i64 per case: element offset into the mask arena (times C into the image arena), shape n0, n1, n2.
+// params: msl_augment_affine's rows with [0] = case.  Output voxel o of the (T0, T1, T2) target reads voxel q of the
+// permuted case (shape n'), q_a = clamp(o_a + d_a, 0, n'_a - 1), d_a = -((t_a - n'_a) / 2) if n'_a < t_a else n'_a / 2 -
+// t_a / 2 (WIN: d_a = windows[n][a]); with the affine on, the permuted case is sampled at M q + offset as affine_kernel
+// samples it.
+template <int C, bool VEC, bool WIN>
 __global__ __launch_bounds__(DP_THREADS) void fit_kernel(
-    const float* __restrict__ src_img, const short* __restrict__ src_seg, long long arena_elems,
-    const long long* __restrict__ table, int n_cases, const double* __restrict__ params, int T0, int T1, int T2,
-    float* __restrict__ dst_img, short* __restrict__ dst_seg) {
+    const float* __restrict__ src_img, const short* __restrict__ src_seg, long long seg_elems,
+    const long long* __restrict__ table, int n_cases, const double* __restrict__ params,
+    const int* __restrict__ windows, int T0, int T1, int T2, float* __restrict__ dst_img, short* __restrict__ dst_seg) {
   const int G = (T2 + FIT_VEC - 1) / FIT_VEC;
   const long long groups = (long long)T0 * T1 * G;
   const long long g = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
@@ -780,14 +820,16 @@ __global__ __launch_bounds__(DP_THREADS) void fit_kernel(
   const int x0 = (int)(g % G) * FIT_VEC;
   const long long rowi = g / G;
   const int oc0 = (int)(rowi / T1), oc1 = (int)(rowi % T1);
-  const long long out0 = (((long long)n * T0 + oc0) * T1 + oc1) * T2 + x0;
+  const long long TV = (long long)T0 * T1 * T2;
+  const long long in_plane = ((long long)oc0 * T1 + oc1) * T2 + x0;
   const int cnt = (T2 - x0) < FIT_VEC ? (T2 - x0) : FIT_VEC;
   const double* p = params + (size_t)n * AFFINE_STRIDE;
-  float vi[FIT_VEC];
+  float vi[C][FIT_VEC];
   short vs[FIT_VEC];
 #pragma unroll
   for (int j = 0; j < FIT_VEC; ++j) {
-    vi[j] = 0.0f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) vi[c][j] = 0.0f;
     vs[j] = 0;
   }
   const int cs = (int)p[0];
@@ -806,10 +848,12 @@ __global__ __launch_bounds__(DP_THREADS) void fit_kernel(
 #pragma unroll
     for (int a = 0; a < 3; ++a) sn[a] = table[(long long)cs * 4 + 1 + a];
     ok = coff >= 0 && sn[0] > 0 && sn[1] > 0 && sn[2] > 0 && sn[0] < (1 << 20) && sn[1] < (1 << 20) && sn[2] < (1 << 20);
-    ok = ok && coff + sn[0] * sn[1] * sn[2] <= arena_elems;
+    // the mask ends inside its arena; the image arena holds C * seg_elems floats, so the C planes end inside theirs
+    ok = ok && coff + sn[0] * sn[1] * sn[2] <= seg_elems;
   }
   if (ok) {
-    const float* si = src_img + coff;
+    const long long V = sn[0] * sn[1] * sn[2];
+    const float* si = src_img + (long long)C * coff;  // plane c at si + c * V
     const short* ss = src_seg + coff;
     const long long sstride[3] = {sn[1] * sn[2], sn[2], 1LL};
     const int T[3] = {T0, T1, T2};
@@ -819,25 +863,57 @@ __global__ __launch_bounds__(DP_THREADS) void fit_kernel(
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       dims[a] = (int)sn[ax[a]];
-      dsh[a] = dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2;
+      dsh[a] = WIN ? windows[3 * (long long)n + a]
+                   : (dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2);
       pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
       if (rev[a]) base += (long long)(dims[a] - 1) * sstride[ax[a]];
     }
-    const int q0 = min(max(oc0 + dsh[0], 0), dims[0] - 1), q1 = min(max(oc1 + dsh[1], 0), dims[1] - 1);
+    const int q0 = fit_src<WIN>(oc0, dsh[0], dims[0]), q1 = fit_src<WIN>(oc1, dsh[1], dims[1]);
     const bool affine = p[7] != 0.0;
     const int mode = (int)p[20];
     int qprev = -1;
-    for (int j = 0; j < cnt; ++j) {
-      const int qc[3] = {q0, q1, min(max(x0 + j + dsh[2], 0), dims[2] - 1)};
-      if (j > 0 && qc[2] == qprev) {  // padded region along the last axis: the same source voxel, the same value
-        vi[j] = vi[j - 1];
+    int jn = cnt;  // voxels the loop below still has to fill
+    const long long xs = (long long)x0 + dsh[2];  // source of the thread's first voxel, before the clamp
+    if (WIN && !affine && cnt == FIT_VEC && pst[2] == 1 && xs >= 0 && xs + FIT_VEC <= dims[2]) {
+      // interior run: sources s .. s + 3 of one row of the case, the values the loop would read one by one
+      const long long s = base + q0 * pst[0] + q1 * pst[1] + xs;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float* sp = si + c * V + s;
+        float4 x;
+        if (((uintptr_t)sp & 15u) == 0) {
+          x = *reinterpret_cast<const float4*>(sp);
+        } else {
+          x = make_float4(sp[0], sp[1], sp[2], sp[3]);
+        }
+        vi[c][0] = apply_ops(x.x, p);
+        vi[c][1] = apply_ops(x.y, p);
+        vi[c][2] = apply_ops(x.z, p);
+        vi[c][3] = apply_ops(x.w, p);
+      }
+      const short* mp = ss + s;
+      if (((uintptr_t)mp & 7u) == 0) {
+        typedef short short4v __attribute__((ext_vector_type(4)));
+        const short4v m = *reinterpret_cast<const short4v*>(mp);
+        vs[0] = m[0]; vs[1] = m[1]; vs[2] = m[2]; vs[3] = m[3];
+      } else {
+        vs[0] = mp[0]; vs[1] = mp[1]; vs[2] = mp[2]; vs[3] = mp[3];
+      }
+      jn = 0;
+    }
+    for (int j = 0; j < jn; ++j) {
+      const int qc[3] = {q0, q1, fit_src<WIN>(x0 + j, dsh[2], dims[2])};
+      if (j > 0 && qc[2] == qprev) {  // padded region along the last axis: the same source voxel, the same values
+#pragma unroll
+        for (int c = 0; c < C; ++c) vi[c][j] = vi[c][j - 1];
         vs[j] = vs[j - 1];
         continue;
       }
       qprev = qc[2];
       if (!affine) {
         const long long s = base + qc[0] * pst[0] + qc[1] * pst[1] + qc[2] * pst[2];
-        vi[j] = apply_ops(si[s], p);
+#pragma unroll
+        for (int c = 0; c < C; ++c) vi[c][j] = apply_ops(si[c * V + s], p);
         vs[j] = ss[s];
         continue;
       }
@@ -863,11 +939,15 @@ __global__ __launch_bounds__(DP_THREADS) void fit_kernel(
         i0[h] = map_tap((long long)floor(cc + 0.5), len, mode);
       }
       if (outside) {  // scipy's constant: cval for image and mask alike, the intensity operations still apply
-        vi[j] = apply_ops(0.0f, p);
+        const float cval = apply_ops(0.0f, p);
+#pragma unroll
+        for (int c = 0; c < C; ++c) vi[c][j] = cval;
         vs[j] = 0;
         continue;
       }
-      double t = 0.0;
+      double t[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) t[c] = 0.0;
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -875,28 +955,75 @@ __global__ __launch_bounds__(DP_THREADS) void fit_kernel(
 #pragma unroll
           for (int d = 0; d < 2; ++d) {
             const long long s = base + i1[0][a] * pst[0] + i1[1][b] * pst[1] + i1[2][d] * pst[2];
-            double coeff = (double)si[s];
-            coeff = coeff * w[0][a];
-            coeff = coeff * w[1][b];
-            coeff = coeff * w[2][d];
-            t = t + coeff;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {  // per channel the corners in one order, each ((v * w0) * w1) * w2
+              double coeff = (double)si[c * V + s];
+              coeff = coeff * w[0][a];
+              coeff = coeff * w[1][b];
+              coeff = coeff * w[2][d];
+              t[c] = t[c] + coeff;
+            }
           }
-      vi[j] = apply_ops((float)t, p);
+#pragma unroll
+      for (int c = 0; c < C; ++c) vi[c][j] = apply_ops((float)t[c], p);
       vs[j] = ss[base + i0[0] * pst[0] + i0[1] * pst[1] + i0[2] * pst[2]];
     }
   }
-  if (VEC) {  // T2 % 4 == 0: every group is whole and 16-byte (image) / 8-byte (mask) aligned
-    *reinterpret_cast<float4*>(dst_img + out0) = make_float4(vi[0], vi[1], vi[2], vi[3]);
+  float* di = dst_img + (long long)n * C * TV + in_plane;
+  short* dsg = dst_seg + (long long)n * TV + in_plane;
+  if (VEC) {  // T2 % 4 == 0: every group is whole and 16-byte (image, every plane) / 8-byte (mask) aligned
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+      *reinterpret_cast<float4*>(di + c * TV) = make_float4(vi[c][0], vi[c][1], vi[c][2], vi[c][3]);
     typedef short short4v __attribute__((ext_vector_type(4)));
     short4v o;
     o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2]; o[3] = vs[3];
-    *reinterpret_cast<short4v*>(dst_seg + out0) = o;
+    *reinterpret_cast<short4v*>(dsg) = o;
   } else {
-    for (int j = 0; j < cnt; ++j) {
-      dst_img[out0 + j] = vi[j];
-      dst_seg[out0 + j] = vs[j];
+#pragma unroll
+    for (int j = 0; j < FIT_VEC; ++j) {  // unrolled: vi / vs stay in registers
+      if (j < cnt) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) di[c * TV + j] = vi[c][j];
+        dsg[j] = vs[j];
+      }
     }
   }
+}
+
+template <int C, bool WIN>
+void launch_fit(bool vec, dim3 grid, hipStream_t st, const float* arena_img, const short* arena_seg, long long seg_elems,
+                const long long* table, int n_cases, const double* params, const int* windows, int T0, int T1, int T2,
+                float* dst_img, short* dst_seg) {
+  if (vec)
+    MSL_LAUNCH(fit_kernel<C, true, WIN>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
+               params, windows, T0, T1, T2, dst_img, dst_seg);
+  else
+    MSL_LAUNCH(fit_kernel<C, false, WIN>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
+               params, windows, T0, T1, T2, dst_img, dst_seg);
+}
+
+// the launch of msl_augment_fit[_mc] (windows null: the centred fit) and msl_augment_window_mc
+template <bool WIN>
+int augment_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+               int n_cases, const double* params, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
+               short* dst_seg, void* stream) {
+  if (!arena_img || !arena_seg || !table || !params || !dst_img || !dst_seg || seg_elems <= 0 || C < 1 ||
+      C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
+    return MSL_ERR_ARG;
+  const long long groups = (long long)T0 * T1 * ((T2 + FIT_VEC - 1) / FIT_VEC);
+  if (N > 65535 || (groups + DP_THREADS - 1) / DP_THREADS > 0x7FFFFFFFLL) return MSL_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((groups + DP_THREADS - 1) / DP_THREADS), N);
+  const bool vec = T2 % FIT_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (C) {
+    case 1: launch_fit<1, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+    case 2: launch_fit<2, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+    case 3: launch_fit<3, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+    default: launch_fit<4, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
+  }
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
 }
 
 struct InstPairs {
@@ -1061,35 +1188,34 @@ size_t inst_ws_bytes(int N) { return ((size_t)N * INST_IDS * 6 + (size_t)N * INS
 extern "C" {
 
 int msl_foreground_box(const float* vol, int D, int H, int W, int margin, int* box, void* stream) {
-  if (!vol || !box || D <= 0 || H <= 0 || W <= 0 || margin < 0) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const long long waves = ((long long)D * H + 3) / 4;
-  MSL_LAUNCH(fg_init_kernel, dim3(1), dim3(64), 0, st, box);
-  // the six atomics of every wave hit the same six words: few waves, many rows each
-  MSL_LAUNCH(fg_reduce_kernel, dim3((unsigned)(waves < 512 ? waves : 512)), dim3(FG_THREADS), 0, st, vol, D, H, W, box);
-  MSL_LAUNCH(fg_final_kernel, dim3(1), dim3(64), 0, st, D, H, W, margin, box);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return foreground_box(vol, 1, D, H, W, margin, box, stream);
 }
 
+int msl_foreground_box_mc(const float* vol, int C, int D, int H, int W, int margin, int* box, void* stream) {
+  return foreground_box(vol, C, D, H, W, margin, box, stream);
+}
+
+// one sequence: both arenas hold arena_elems elements, the C = 1 case of the launch below
 int msl_augment_fit(const float* arena_img, const short* arena_seg, long long arena_elems, const long long* table,
                     int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
                     void* stream) {
-  if (!arena_img || !arena_seg || !table || !params || !dst_img || !dst_seg || arena_elems <= 0 || n_cases <= 0 ||
-      N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
-    return MSL_ERR_ARG;
-  const long long groups = (long long)T0 * T1 * ((T2 + FIT_VEC - 1) / FIT_VEC);
-  if (N > 65535 || (groups + DP_THREADS - 1) / DP_THREADS > 0x7FFFFFFFLL) return MSL_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)((groups + DP_THREADS - 1) / DP_THREADS), N);
-  const bool vec = T2 % FIT_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
-  if (vec)
-    MSL_LAUNCH(fit_kernel<true>, grid, dim3(DP_THREADS), 0, (hipStream_t)stream, arena_img, arena_seg, arena_elems,
-               table, n_cases, params, T0, T1, T2, dst_img, dst_seg);
-  else
-    MSL_LAUNCH(fit_kernel<false>, grid, dim3(DP_THREADS), 0, (hipStream_t)stream, arena_img, arena_seg, arena_elems,
-               table, n_cases, params, T0, T1, T2, dst_img, dst_seg);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return augment_mc<false>(arena_img, arena_seg, /*seg_elems=*/arena_elems, /*C=*/1, table, n_cases, params,
+                           /*windows=*/nullptr, N, T0, T1, T2, dst_img, dst_seg, stream);
+}
+
+int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+                       int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
+                       void* stream) {
+  return augment_mc<false>(arena_img, arena_seg, seg_elems, C, table, n_cases, params, nullptr, N, T0, T1, T2, dst_img,
+                           dst_seg, stream);
+}
+
+int msl_augment_window_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                          const long long* table, int n_cases, const double* params, const int* windows, int N, int T0,
+                          int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
+  if (!windows) return MSL_ERR_ARG;
+  return augment_mc<true>(arena_img, arena_seg, seg_elems, C, table, n_cases, params, windows, N, T0, T1, T2, dst_img,
+                          dst_seg, stream);
 }
 
 size_t msl_instance_boxes_workspace_bytes(int N) { return N > 0 && N <= 65535 ? inst_ws_bytes(N) : 0; }
@@ -1510,317 +1636,6 @@ int msl_binary_boxes(const short* seg, int N, int D, int H, int W, int capacity,
              labels, obj_off, overflow);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
-}
-
-}  // extern "C"
-
-// ---- clinical cases with C sequences (1 <= C <= 4): union foreground box, ragged augment + fit of all channels ---------
-// Host mirrors: datasets.foreground_box on a (C, D, H, W) image and datasets._LesionCases.__getitem__ with
-// len(input_images) = C.  The mask arena and the table are msl_augment_fit's; the image arena holds C contiguous planes
-// per case, case k at element C * off_k.
-//
-//   foreground : fg_reduce_kernel's walk over the C * D * H rows of the channel-first volume; a row of any channel that
-//                holds a positive voxel extends the one box (the union of the channels' supports)
-//   fit        : fit_kernel's thread (four output voxels of a row), for all C channels: the clamp of the fit, the f64
-//                coordinate row, the boundary maps, the axis weights and the order-0 mask tap are computed once per
-//                voxel; only the eight gathers, the f64 accumulation and the intensity operations repeat per channel,
-//                each in fit_kernel's operation order (a channel is bit-identical to a one-channel launch on its plane)
-//   window     : the same body (WIN) with the shift d read per sample from `windows` instead of centred: a training patch
-//                or a validation tile (datasets.window, DESIGN.md section 4.12).  With the affine off, a thread whose four
-//                sources are one in-range run of an unreversed last axis reads them with one 16-byte load per plane and
-//                one 8-byte load of the mask where those addresses are aligned (views.hip's rule) - a patch inside a
-//                large head is that case nearly everywhere
-namespace {
-
-constexpr int FIT_MAX_CH = 4;  // the stem's limit
-
-__global__ __launch_bounds__(FG_THREADS) void fg_reduce_mc_kernel(const float* __restrict__ vol, int C, int D, int H,
-                                                                  int W, int* __restrict__ box) {
-  const int lane = threadIdx.x & 63;
-  const long long rows = (long long)C * D * H;
-  const long long nwave = (long long)gridDim.x * (FG_THREADS / 64);
-  int lo_d = IMAX, lo_h = IMAX, lo_w = IMAX, hi_d = -1, hi_h = -1, hi_w = -1;
-  for (long long r = (long long)blockIdx.x * (FG_THREADS / 64) + (threadIdx.x >> 6); r < rows; r += nwave) {
-    const float* row = vol + r * W;
-    bool any = false;
-    for (int w = lane; w < W; w += 64) {
-      if (row[w] > 0.0f) {
-        any = true;
-        lo_w = min(lo_w, w);
-        hi_w = max(hi_w, w);
-      }
-    }
-    if (__any(any)) {  // wave-uniform
-      const int d = (int)((r / H) % D), h = (int)(r % H);
-      lo_d = min(lo_d, d); hi_d = max(hi_d, d);
-      lo_h = min(lo_h, h); hi_h = max(hi_h, h);
-    }
-  }
-  lo_w = wave_min(lo_w);
-  hi_w = wave_max(hi_w);
-  if (lane == 0 && hi_d >= 0) {
-    atomicMin(box + 0, lo_d); atomicMin(box + 1, lo_h); atomicMin(box + 2, lo_w);
-    atomicMax(box + 3, hi_d); atomicMax(box + 4, hi_h); atomicMax(box + 5, hi_w);
-  }
-}
-
-// source index of output index o under the shift d on an axis of n voxels.  The fit's d is bounded by the sizes; a window's
-// origin is any int (far outside the case it repeats the border voxel), so that sum is formed in 64 bits
-template <bool WIN>
-__device__ __forceinline__ int fit_src(int o, int d, int n) {
-  if (!WIN) return min(max(o + d, 0), n - 1);
-  const long long q = (long long)o + d;
-  return q < 0 ? 0 : (q > n - 1 ? n - 1 : (int)q);
-}
-
-template <int C, bool VEC, bool WIN>
-__global__ __launch_bounds__(DP_THREADS) void fit_mc_kernel(
-    const float* __restrict__ src_img, const short* __restrict__ src_seg, long long seg_elems,
-    const long long* __restrict__ table, int n_cases, const double* __restrict__ params,
-    const int* __restrict__ windows, int T0, int T1, int T2, float* __restrict__ dst_img, short* __restrict__ dst_seg) {
-  const int G = (T2 + FIT_VEC - 1) / FIT_VEC;
-  const long long groups = (long long)T0 * T1 * G;
-  const long long g = (long long)blockIdx.x * DP_THREADS + threadIdx.x;
-  if (g >= groups) return;
-  const int n = blockIdx.y;
-  const int x0 = (int)(g % G) * FIT_VEC;
-  const long long rowi = g / G;
-  const int oc0 = (int)(rowi / T1), oc1 = (int)(rowi % T1);
-  const long long TV = (long long)T0 * T1 * T2;
-  const long long in_plane = ((long long)oc0 * T1 + oc1) * T2 + x0;
-  const int cnt = (T2 - x0) < FIT_VEC ? (T2 - x0) : FIT_VEC;
-  const double* p = params + (size_t)n * AFFINE_STRIDE;
-  float vi[C][FIT_VEC];
-  short vs[FIT_VEC];
-#pragma unroll
-  for (int j = 0; j < FIT_VEC; ++j) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) vi[c][j] = 0.0f;
-    vs[j] = 0;
-  }
-  const int cs = (int)p[0];
-  int ax[3], rev[3];
-  bool ok = cs >= 0 && cs < n_cases;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    ax[a] = (int)p[1 + a];
-    rev[a] = (int)p[4 + a];
-    ok = ok && ax[a] >= 0 && ax[a] < 3;
-  }
-  ok = ok && ax[0] != ax[1] && ax[0] != ax[2] && ax[1] != ax[2];
-  long long coff = 0, sn[3] = {1, 1, 1};
-  if (ok) {  // rejected on the host; never read out of bounds
-    coff = table[(long long)cs * 4];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) sn[a] = table[(long long)cs * 4 + 1 + a];
-    ok = coff >= 0 && sn[0] > 0 && sn[1] > 0 && sn[2] > 0 && sn[0] < (1 << 20) && sn[1] < (1 << 20) && sn[2] < (1 << 20);
-    // the mask ends inside its arena; the image arena holds C * seg_elems floats, so the C planes end inside theirs
-    ok = ok && coff + sn[0] * sn[1] * sn[2] <= seg_elems;
-  }
-  if (ok) {
-    const long long V = sn[0] * sn[1] * sn[2];
-    const float* si = src_img + (long long)C * coff;  // plane c at si + c * V
-    const short* ss = src_seg + coff;
-    const long long sstride[3] = {sn[1] * sn[2], sn[2], 1LL};
-    const int T[3] = {T0, T1, T2};
-    int dims[3], dsh[3];  // permuted shape n' and the fit's shift d
-    long long pst[3];
-    long long base = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      dims[a] = (int)sn[ax[a]];
-      dsh[a] = WIN ? windows[3 * (long long)n + a]
-                   : (dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2);
-      pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
-      if (rev[a]) base += (long long)(dims[a] - 1) * sstride[ax[a]];
-    }
-    const int q0 = fit_src<WIN>(oc0, dsh[0], dims[0]), q1 = fit_src<WIN>(oc1, dsh[1], dims[1]);
-    const bool affine = p[7] != 0.0;
-    const int mode = (int)p[20];
-    int qprev = -1;
-    int jn = cnt;  // voxels the loop below still has to fill
-    const long long xs = (long long)x0 + dsh[2];  // source of the thread's first voxel, before the clamp
-    if (WIN && !affine && cnt == FIT_VEC && pst[2] == 1 && xs >= 0 && xs + FIT_VEC <= dims[2]) {
-      // interior run: sources s .. s + 3 of one row of the case, the values the loop would read one by one
-      const long long s = base + q0 * pst[0] + q1 * pst[1] + xs;
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float* sp = si + c * V + s;
-        float4 x;
-        if (((uintptr_t)sp & 15u) == 0) {
-          x = *reinterpret_cast<const float4*>(sp);
-        } else {
-          x = make_float4(sp[0], sp[1], sp[2], sp[3]);
-        }
-        vi[c][0] = apply_ops(x.x, p);
-        vi[c][1] = apply_ops(x.y, p);
-        vi[c][2] = apply_ops(x.z, p);
-        vi[c][3] = apply_ops(x.w, p);
-      }
-      const short* mp = ss + s;
-      if (((uintptr_t)mp & 7u) == 0) {
-        typedef short short4v __attribute__((ext_vector_type(4)));
-        const short4v m = *reinterpret_cast<const short4v*>(mp);
-        vs[0] = m[0]; vs[1] = m[1]; vs[2] = m[2]; vs[3] = m[3];
-      } else {
-        vs[0] = mp[0]; vs[1] = mp[1]; vs[2] = mp[2]; vs[3] = mp[3];
-      }
-      jn = 0;
-    }
-    for (int j = 0; j < jn; ++j) {
-      const int qc[3] = {q0, q1, fit_src<WIN>(x0 + j, dsh[2], dims[2])};
-      if (j > 0 && qc[2] == qprev) {  // padded region along the last axis: the same source voxel, the same values
-#pragma unroll
-        for (int c = 0; c < C; ++c) vi[c][j] = vi[c][j - 1];
-        vs[j] = vs[j - 1];
-        continue;
-      }
-      qprev = qc[2];
-      if (!affine) {
-        const long long s = base + qc[0] * pst[0] + qc[1] * pst[1] + qc[2] * pst[2];
-#pragma unroll
-        for (int c = 0; c < C; ++c) vi[c][j] = apply_ops(si[c * V + s], p);
-        vs[j] = ss[s];
-        continue;
-      }
-      int i1[3][2], i0[3];
-      double w[3][2];
-      bool outside = false;
-#pragma unroll
-      for (int h = 0; h < 3; ++h) {
-        double c = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c = c + (double)qc[k] * p[8 + 3 * h + k];
-        c = c + p[17 + h];
-        const int len = dims[h];
-        const double cc = map_boundary(c, len, mode);
-        if (mode == 2 && !(cc > -1.0)) outside = true;
-        const double fl = floor(cc);
-        const long long st = (long long)fl;
-        const double x = cc - fl;
-        w[h][0] = 1.0 - x;
-        w[h][1] = 1.0 - w[h][0];
-        i1[h][0] = map_tap(st, len, mode);
-        i1[h][1] = map_tap(st + 1, len, mode);
-        i0[h] = map_tap((long long)floor(cc + 0.5), len, mode);
-      }
-      if (outside) {  // scipy's constant: cval for image and mask alike, the intensity operations still apply
-        const float cval = apply_ops(0.0f, p);
-#pragma unroll
-        for (int c = 0; c < C; ++c) vi[c][j] = cval;
-        vs[j] = 0;
-        continue;
-      }
-      double t[C];
-#pragma unroll
-      for (int c = 0; c < C; ++c) t[c] = 0.0;
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            const long long s = base + i1[0][a] * pst[0] + i1[1][b] * pst[1] + i1[2][d] * pst[2];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {  // per channel the corners in fit_kernel's order, each ((v * w0) * w1) * w2
-              double coeff = (double)si[c * V + s];
-              coeff = coeff * w[0][a];
-              coeff = coeff * w[1][b];
-              coeff = coeff * w[2][d];
-              t[c] = t[c] + coeff;
-            }
-          }
-#pragma unroll
-      for (int c = 0; c < C; ++c) vi[c][j] = apply_ops((float)t[c], p);
-      vs[j] = ss[base + i0[0] * pst[0] + i0[1] * pst[1] + i0[2] * pst[2]];
-    }
-  }
-  float* di = dst_img + (long long)n * C * TV + in_plane;
-  short* dsg = dst_seg + (long long)n * TV + in_plane;
-  if (VEC) {  // T2 % 4 == 0: every group is whole and 16-byte (image, every plane) / 8-byte (mask) aligned
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-      *reinterpret_cast<float4*>(di + c * TV) = make_float4(vi[c][0], vi[c][1], vi[c][2], vi[c][3]);
-    typedef short short4v __attribute__((ext_vector_type(4)));
-    short4v o;
-    o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2]; o[3] = vs[3];
-    *reinterpret_cast<short4v*>(dsg) = o;
-  } else {
-#pragma unroll
-    for (int j = 0; j < FIT_VEC; ++j) {  // unrolled: vi / vs stay in registers
-      if (j < cnt) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) di[c * TV + j] = vi[c][j];
-        dsg[j] = vs[j];
-      }
-    }
-  }
-}
-
-template <int C, bool WIN>
-void launch_fit_mc(bool vec, dim3 grid, hipStream_t st, const float* arena_img, const short* arena_seg, long long seg_elems,
-                   const long long* table, int n_cases, const double* params, const int* windows, int T0, int T1, int T2,
-                   float* dst_img, short* dst_seg) {
-  if (vec)
-    MSL_LAUNCH(fit_mc_kernel<C, true, WIN>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
-               params, windows, T0, T1, T2, dst_img, dst_seg);
-  else
-    MSL_LAUNCH(fit_mc_kernel<C, false, WIN>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases,
-               params, windows, T0, T1, T2, dst_img, dst_seg);
-}
-
-// the launch of msl_augment_fit_mc (windows null: the centred fit) and msl_augment_window_mc
-template <bool WIN>
-int augment_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
-               int n_cases, const double* params, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
-               short* dst_seg, void* stream) {
-  if (!arena_img || !arena_seg || !table || !params || !dst_img || !dst_seg || seg_elems <= 0 || C < 1 ||
-      C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
-    return MSL_ERR_ARG;
-  const long long groups = (long long)T0 * T1 * ((T2 + FIT_VEC - 1) / FIT_VEC);
-  if (N > 65535 || (groups + DP_THREADS - 1) / DP_THREADS > 0x7FFFFFFFLL) return MSL_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)((groups + DP_THREADS - 1) / DP_THREADS), N);
-  const bool vec = T2 % FIT_VEC == 0 && ((uintptr_t)dst_img & 15) == 0 && ((uintptr_t)dst_seg & 7) == 0;
-  hipStream_t st = (hipStream_t)stream;
-  switch (C) {
-    case 1: launch_fit_mc<1, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
-    case 2: launch_fit_mc<2, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
-    case 3: launch_fit_mc<3, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
-    default: launch_fit_mc<4, WIN>(vec, grid, st, arena_img, arena_seg, seg_elems, table, n_cases, params, windows, T0, T1, T2, dst_img, dst_seg); break;
-  }
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msl_foreground_box_mc(const float* vol, int C, int D, int H, int W, int margin, int* box, void* stream) {
-  if (!vol || !box || C < 1 || C > FIT_MAX_CH || D <= 0 || H <= 0 || W <= 0 || margin < 0) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const long long waves = ((long long)C * D * H + 3) / 4;
-  MSL_LAUNCH(fg_init_kernel, dim3(1), dim3(64), 0, st, box);
-  MSL_LAUNCH(fg_reduce_mc_kernel, dim3((unsigned)(waves < 512 ? waves : 512)), dim3(FG_THREADS), 0, st, vol, C, D, H, W,
-             box);
-  MSL_LAUNCH(fg_final_kernel, dim3(1), dim3(64), 0, st, D, H, W, margin, box);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
-                       int n_cases, const double* params, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg,
-                       void* stream) {
-  return augment_mc<false>(arena_img, arena_seg, seg_elems, C, table, n_cases, params, nullptr, N, T0, T1, T2, dst_img,
-                           dst_seg, stream);
-}
-
-int msl_augment_window_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
-                          const long long* table, int n_cases, const double* params, const int* windows, int N, int T0,
-                          int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
-  if (!windows) return MSL_ERR_ARG;
-  return augment_mc<true>(arena_img, arena_seg, seg_elems, C, table, n_cases, params, windows, N, T0, T1, T2, dst_img,
-                          dst_seg, stream);
 }
 
 }  // extern "C"

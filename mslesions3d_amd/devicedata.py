@@ -14,9 +14,9 @@ AFFINE_MAX_OPS intensity operations raise NotImplementedError.
 
 ``LesionCache`` is the counterpart for ``datasets.LesionsDataModule``: cases of unequal shape, cropped to their
 foreground, in one flat arena; shape-changing rot90s allowed; every batch padded / cropped to one fixed size and its
-instance-labelled masks turned into boxes (msl_foreground_box, msl_augment_fit, msl_instance_boxes); binary masks
+instance-labelled masks turned into boxes (msl_foreground_box_mc, msl_augment_fit_mc, msl_instance_boxes); binary masks
 (``segmentation_mode == "binary"``) are labelled per batch by msl_binary_boxes instead.  A module with
-C > 1 input sequences is cached channel-planar and goes through msl_foreground_box_mc / msl_augment_fit_mc.  A case that
+C > 1 input sequences is cached channel-planar; every C, one sequence included, goes through the same entry points.  A case that
 carries an affine is uploaded on its native grid and put on the LPI 1 mm grid by msl_regrid (``regrid_device``, the
 device form of ``datasets.regrid``, bit for bit) in front of the foreground box.  A module with a ``patch_size`` (patch
 training) gets one sampled window per case and epoch instead of the fit, and validation tiles
@@ -50,15 +50,17 @@ def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-class _BoxOut:
-    """Packed targets + workspace of msl_seg_boxes for one (N, D, H, W, n_classes, capacity)."""
+class _BoxStage:
+    """Packed targets + workspace of one box entry point for (N,) + shape masks and ``capacity`` rows.  Every entry
+    point takes (mask, N, D, H, W, its own arguments, workspace, workspace bytes, gb, gl, obj_off, flag, stream); a
+    subclass names it (``entry``), sizes its workspace, and supplies ``_args()`` (those own arguments) and ``_errors()``
+    ([(flag bit, message)] in the order the bits are tested)."""
 
-    def __init__(self, N, shape, n_classes, capacity, comp_cap, dev):
-        lib = _lib.load()
-        self.N, self.shape, self.n_classes, self.capacity, self.comp_cap = N, tuple(shape), n_classes, capacity, comp_cap
-        nbytes = lib.msl_seg_boxes_workspace_bytes(N, *self.shape, n_classes, comp_cap)
+    def __init__(self, N, shape, capacity, dev, nbytes, unsupported):
+        """``nbytes``: the entry point's workspace size, 0 for sizes it refuses (``unsupported`` says which)."""
+        self.N, self.shape, self.capacity = N, tuple(shape), capacity
         if nbytes == 0:
-            raise _lib.HipKernelError(f"msl_seg_boxes: unsupported sizes N={N} shape={self.shape} n_classes={n_classes}")
+            raise _lib.HipKernelError(f"{self.entry}: unsupported {unsupported}")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.gb = torch.zeros((max(capacity, 1), 6), dtype=torch.float32, device=dev)
         self.gl = torch.ones(max(capacity, 1), dtype=torch.int64, device=dev)
@@ -67,18 +69,42 @@ class _BoxOut:
         self.flag_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
 
     def launch(self, seg, stream):
-        _lib.call("msl_seg_boxes", ptr(seg), self.N, *self.shape, self.n_classes, self.capacity, self.comp_cap,
-                  ptr(self.ws), self.ws.numel(), ptr(self.gb), ptr(self.gl), ptr(self.obj_off), ptr(self.flag), stream)
+        _lib.call(self.entry, ptr(seg), self.N, *self.shape, *self._args(), ptr(self.ws), self.ws.numel(), ptr(self.gb),
+                  ptr(self.gl), ptr(self.obj_off), ptr(self.flag), stream)
         self.flag_host.copy_(self.flag, non_blocking=True)  # read after the next synchronising read: no sync of its own
 
     def raise_on_overflow(self, flag=None):
         f = int(self.flag_host.item() if flag is None else flag)
-        if f & 1:
-            raise _lib.HipKernelError(f"msl_seg_boxes: a batch holds more ground-truth boxes than the capacity of "
-                                      f"{self.capacity} rows")
-        if f & 2:
-            raise _lib.HipKernelError(f"msl_seg_boxes: a batch holds more connected components than comp_cap = "
-                                      f"{self.comp_cap}")
+        for bit, message in self._errors() if f else ():
+            if f & bit:
+                raise _lib.HipKernelError(f"{self.entry}: {message}")
+
+    def boxes(self, seg):
+        """Launch on ``seg`` -> (boxes list, labels list, (gb, gl, obj_off, capacity)): per-image device views and the
+        packed form.  One host synchronisation (obj_off); the flag is read behind it."""
+        self.launch(seg, _stream(seg.device))
+        off = self.obj_off.cpu().tolist()
+        self.raise_on_overflow(self.flag.item())
+        return ([self.gb[off[n]:off[n + 1]] for n in range(self.N)], [self.gl[off[n]:off[n + 1]] for n in range(self.N)],
+                (self.gb, self.gl, self.obj_off, self.capacity))
+
+
+class _BoxOut(_BoxStage):
+    """``_BoxStage`` of msl_seg_boxes for one (N, D, H, W, n_classes, capacity)."""
+
+    entry = "msl_seg_boxes"
+
+    def __init__(self, N, shape, n_classes, capacity, comp_cap, dev):
+        self.n_classes, self.comp_cap = n_classes, comp_cap
+        nbytes = _lib.load().msl_seg_boxes_workspace_bytes(N, *shape, n_classes, comp_cap)
+        super().__init__(N, shape, capacity, dev, nbytes, f"sizes N={N} shape={tuple(shape)} n_classes={n_classes}")
+
+    def _args(self):
+        return self.n_classes, self.capacity, self.comp_cap
+
+    def _errors(self):
+        return [(1, f"a batch holds more ground-truth boxes than the capacity of {self.capacity} rows"),
+                (2, f"a batch holds more connected components than comp_cap = {self.comp_cap}")]
 
 
 def _default_comp_cap(capacity):
@@ -102,13 +128,8 @@ def boxes_from_segmentation_device(seg, n_classes=1, capacity=None, comp_cap=Non
     seg = seg.contiguous()
     N = seg.shape[0]
     capacity = 1024 * N if capacity is None else int(capacity)
-    out = _BoxOut(N, seg.shape[1:], int(n_classes), capacity, comp_cap or _default_comp_cap(capacity), seg.device)
-    out.launch(seg, _stream(seg.device))
-    off = out.obj_off.cpu().tolist()
-    out.raise_on_overflow(out.flag.item())
-    boxes = [out.gb[off[n]:off[n + 1]] for n in range(N)]
-    labels = [out.gl[off[n]:off[n + 1]] for n in range(N)]
-    return boxes, labels, (out.gb, out.gl, out.obj_off, capacity)
+    return _BoxOut(N, seg.shape[1:], int(n_classes), capacity, comp_cap or _default_comp_cap(capacity),
+                   seg.device).boxes(seg)
 
 
 def sample_params(draws, shape, augmentations=None, ragged=False):
@@ -469,36 +490,22 @@ def threshold_table(thresholds):
     return np.ascontiguousarray(t.astype(np.int32))
 
 
-class _InstBoxOut:
-    """Packed targets + workspace of msl_instance_boxes for one (N, D, H, W, thresholds, capacity)."""
+class _InstBoxOut(_BoxStage):
+    """``_BoxStage`` of msl_instance_boxes for one (N, D, H, W, thresholds, capacity)."""
+
+    entry = "msl_instance_boxes"
 
     def __init__(self, N, shape, thresholds, capacity, dev):
-        lib = _lib.load()
-        self.N, self.shape, self.capacity = N, tuple(shape), capacity
         self.thr = threshold_table(thresholds)  # host table, read during every call
-        nbytes = lib.msl_instance_boxes_workspace_bytes(N)
-        if nbytes == 0:
-            raise _lib.HipKernelError(f"msl_instance_boxes: unsupported batch size N={N}")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.gb = torch.zeros((max(capacity, 1), 6), dtype=torch.float32, device=dev)
-        self.gl = torch.ones(max(capacity, 1), dtype=torch.int64, device=dev)
-        self.obj_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
-        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.flag_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        nbytes = _lib.load().msl_instance_boxes_workspace_bytes(N)
+        super().__init__(N, shape, capacity, dev, nbytes, f"batch size N={N}")
 
-    def launch(self, seg, stream):
-        _lib.call("msl_instance_boxes", ptr(seg), self.N, *self.shape, self.thr.ctypes.data, self.thr.shape[0],
-                  self.capacity, ptr(self.ws), self.ws.numel(), ptr(self.gb), ptr(self.gl), ptr(self.obj_off),
-                  ptr(self.flag), stream)
-        self.flag_host.copy_(self.flag, non_blocking=True)  # read after the next synchronising read: no sync of its own
+    def _args(self):
+        return self.thr.ctypes.data, self.thr.shape[0], self.capacity
 
-    def raise_on_overflow(self, flag=None):
-        f = int(self.flag_host.item() if flag is None else flag)
-        if f & 1:
-            raise _lib.HipKernelError(f"msl_instance_boxes: a batch holds more ground-truth boxes than the capacity of "
-                                      f"{self.capacity} rows")
-        if f & 4:
-            raise _lib.HipKernelError("msl_instance_boxes: a mask holds a negative value")
+    def _errors(self):
+        return [(1, f"a batch holds more ground-truth boxes than the capacity of {self.capacity} rows"),
+                (4, "a mask holds a negative value")]
 
 
 def boxes_from_instances_device(seg, thresholds, capacity=None):
@@ -509,50 +516,32 @@ def boxes_from_instances_device(seg, thresholds, capacity=None):
     seg = seg.contiguous()
     N = seg.shape[0]
     capacity = 1024 * N if capacity is None else int(capacity)
-    out = _InstBoxOut(N, seg.shape[1:], thresholds, capacity, seg.device)
-    out.launch(seg, _stream(seg.device))
-    off = out.obj_off.cpu().tolist()
-    out.raise_on_overflow(out.flag.item())
-    return ([out.gb[off[n]:off[n + 1]] for n in range(N)], [out.gl[off[n]:off[n + 1]] for n in range(N)],
-            (out.gb, out.gl, out.obj_off, capacity))
+    return _InstBoxOut(N, seg.shape[1:], thresholds, capacity, seg.device).boxes(seg)
 
 
 MAX_RUNS_PER_IMAGE = 262144  # msl_binary_boxes: runs of non-zero voxels per image (about ten times a 50 mL lesion load)
 
 
-class _BinBoxOut:
-    """Packed targets + workspace of msl_binary_boxes for one (N, D, H, W, capacity, run_cap): ``_InstBoxOut``'s
-    attributes, for binary masks (their 6-connected components are the lesions)."""
+class _BinBoxOut(_BoxStage):
+    """``_BoxStage`` of msl_binary_boxes for one (N, D, H, W, capacity, run_cap): ``_InstBoxOut``'s attributes, for
+    binary masks (their 6-connected components are the lesions)."""
+
+    entry = "msl_binary_boxes"
 
     def __init__(self, N, shape, capacity, dev, max_runs_per_image=MAX_RUNS_PER_IMAGE):
-        lib = _lib.load()
-        self.N, self.shape, self.capacity = N, tuple(shape), capacity
         self.run_cap = int(max_runs_per_image) * N
-        nbytes = lib.msl_binary_boxes_workspace_bytes(N, *self.shape, self.run_cap) if self.run_cap > 0 else 0
-        if nbytes == 0:
-            raise _lib.HipKernelError(f"msl_binary_boxes: unsupported sizes N={N} shape={self.shape} "
-                                      f"max_runs_per_image={max_runs_per_image}")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.gb = torch.zeros((max(capacity, 1), 6), dtype=torch.float32, device=dev)
-        self.gl = torch.ones(max(capacity, 1), dtype=torch.int64, device=dev)
-        self.obj_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
-        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.flag_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        nbytes = _lib.load().msl_binary_boxes_workspace_bytes(N, *shape, self.run_cap) if self.run_cap > 0 else 0
+        super().__init__(N, shape, capacity, dev, nbytes,
+                         f"sizes N={N} shape={tuple(shape)} max_runs_per_image={max_runs_per_image}")
 
-    def launch(self, seg, stream):
-        _lib.call("msl_binary_boxes", ptr(seg), self.N, *self.shape, self.capacity, self.run_cap, ptr(self.ws),
-                  self.ws.numel(), ptr(self.gb), ptr(self.gl), ptr(self.obj_off), ptr(self.flag), stream)
-        self.flag_host.copy_(self.flag, non_blocking=True)  # read after the next synchronising read: no sync of its own
+    def _args(self):
+        return self.capacity, self.run_cap
 
-    def raise_on_overflow(self, flag=None):
-        f = int(self.flag_host.item() if flag is None else flag)
-        if f & 8:
-            raise _lib.HipKernelError(f"msl_binary_boxes: a batch holds more runs of lesion voxels than "
-                                      f"max_runs_per_image = {self.run_cap // self.N} per image allows: raise "
-                                      f"max_runs_per_image")
-        if f & 1:
-            raise _lib.HipKernelError(f"msl_binary_boxes: a batch holds more ground-truth boxes than the capacity of "
-                                      f"{self.capacity} rows: raise max_objects_per_image")
+    def _errors(self):  # the run overflow is reported before the row overflow
+        return [(8, f"a batch holds more runs of lesion voxels than max_runs_per_image = {self.run_cap // self.N} per "
+                    f"image allows: raise max_runs_per_image"),
+                (1, f"a batch holds more ground-truth boxes than the capacity of {self.capacity} rows: raise "
+                    f"max_objects_per_image")]
 
 
 def boxes_from_binary_device(seg, capacity=None, max_runs_per_image=MAX_RUNS_PER_IMAGE):
@@ -564,12 +553,7 @@ def boxes_from_binary_device(seg, capacity=None, max_runs_per_image=MAX_RUNS_PER
     seg = seg.contiguous()
     N = seg.shape[0]
     capacity = 1024 * N if capacity is None else int(capacity)
-    out = _BinBoxOut(N, seg.shape[1:], capacity, seg.device, max_runs_per_image)
-    out.launch(seg, _stream(seg.device))
-    off = out.obj_off.cpu().tolist()
-    out.raise_on_overflow(out.flag.item())
-    return ([out.gb[off[n]:off[n + 1]] for n in range(N)], [out.gl[off[n]:off[n + 1]] for n in range(N)],
-            (out.gb, out.gl, out.obj_off, capacity))
+    return _BinBoxOut(N, seg.shape[1:], capacity, seg.device, max_runs_per_image).boxes(seg)
 
 
 def _box_stage(dataset, N, shape, capacity, dev, max_runs_per_image=MAX_RUNS_PER_IMAGE, who="device pipeline"):
@@ -648,23 +632,30 @@ def _case_on_device(ds, i, dev, who, check_memory=None):
     return vol, mask, plan
 
 
+def _foreground_box(vol, margin, box, stream):
+    """msl_foreground_box_mc on the image ``_case_on_device`` returned -> the six ints in ``box`` (device): a
+    one-sequence image has no channel axis and is the C = 1 launch."""
+    C = vol.shape[0] if vol.dim() == 4 else 1
+    _lib.call("msl_foreground_box_mc", ptr(vol), C, *vol.shape[-3:], int(margin), ptr(box), stream)
+
+
 class LesionCache:
     """The cases of a ``setup()`` ``datasets.LesionsDataModule`` in HBM, cropped to their foreground and normalised: one
     flat arena of f32 images and one of int16 masks with a per-case (offset, shape) table, and the device pipeline that
-    turns them into fixed-size training / validation batches (msl_augment_fit, msl_instance_boxes).
+    turns them into fixed-size training / validation batches (msl_augment_fit_mc, msl_instance_boxes).
 
     Same semantics as ``DeviceCache``: ``train_batches(epoch)`` yields the batches of ``dataset.train_dataloader()`` for
     that epoch (same subjects, same draws) in fixed buffers, ``step(trainer, batch)`` trains on one, ``val_batches()``
     yields ``validation_step`` batches.  At construction every case is uploaded once (a case with an affine on its
     native grid, then regridded by msl_regrid: ``plans`` holds its ``RegridPlan``, None otherwise), boxed by
-    msl_foreground_box (the six ints are the build's only read-back), cropped into the arena and normalised there; the
+    msl_foreground_box_mc (the six ints are the build's only read-back), cropped into the arena and normalised there; the
     cropped cases are staged in tensors of their own until the arena's size is known.  A pipeline with two affine
     stages raises NotImplementedError (a resample of a resample of a ragged case would need a ragged intermediate).
 
-    With C = len(dataset.input_images) > 1 a case is C contiguous f32 planes starting at element C * offset of the image
-    arena (the mask arena and the table do not change): boxed as the union of the channels by msl_foreground_box_mc,
-    every plane normalised on its own (one msl_normalize_nonzero call over the case's C planes), batches written as
-    (N, C) + target by msl_augment_fit_mc.  C = 1 calls the one-channel entry points.
+    With C = len(dataset.input_images) a case is C contiguous f32 planes starting at element C * offset of the image
+    arena (the mask arena and the table are the same for every C): boxed as the union of the channels by
+    msl_foreground_box_mc, every plane normalised on its own (one msl_normalize_nonzero call over the case's C planes),
+    batches written as (N, C) + target by msl_augment_fit_mc.  One sequence is C = 1 of the same calls.
 
     Patch mode (``dataset.patch_size`` set): the batch shape is the patch.  ``train_batches`` makes the host's draws for
     every sample - the augmentation's, then ``datasets.patch_origin``'s eight from the same generator - and
@@ -712,10 +703,7 @@ class LesionCache:
         staged, self.shapes, self.origins, self.full_shapes, self.plans = [], [], [], [], []
         for ds, i in loaders:
             vol, mask, plan = _case_on_device(ds, i, dev, "LesionCache", self._check_memory)
-            if C == 1:
-                _lib.call("msl_foreground_box", ptr(vol), *vol.shape, int(dataset.margin), ptr(box), stream)
-            else:
-                _lib.call("msl_foreground_box_mc", ptr(vol), *vol.shape, int(dataset.margin), ptr(box), stream)
+            _foreground_box(vol, dataset.margin, box, stream)
             b = box.cpu().tolist()  # the one read that sizes the crop
             sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
             staged.append((vol[(...,) + sl].contiguous(), mask[sl].contiguous()))
@@ -823,12 +811,8 @@ class LesionCache:
             b["box"].launch(b["seg"], stream)
             return
         pd = torch.from_numpy(rows.reshape(-1)).pin_memory().to(self.device, non_blocking=True)
-        if self.channels == 1:
-            _lib.call("msl_augment_fit", ptr(self.img), ptr(self.seg), self.img.numel(), ptr(self.table), len(self.shapes),
-                      ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
-        else:
-            _lib.call("msl_augment_fit_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table),
-                      len(self.shapes), ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
+        _lib.call("msl_augment_fit_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table),
+                  len(self.shapes), ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
         b["box"].launch(b["seg"], stream)
 
     def train_batches(self, epoch):
@@ -915,8 +899,8 @@ def boxes_to_case_device(boxes, target, crop_shape, crop_origin, full_shape):
 
 class LesionPredictFeed:
     """``dataset.predict_dataset`` of a ``setup()`` ``datasets.LesionsDataModule`` as batches of one, prepared on the
-    device case by case: upload (a case with an affine on its native grid, then msl_regrid), msl_foreground_box[_mc],
-    crop, msl_normalize_nonzero, msl_augment_fit[_mc] with the identity row into a (1, C) + spatial_size batch,
+    device case by case: upload (a case with an affine on its native grid, then msl_regrid), msl_foreground_box_mc,
+    crop, msl_normalize_nonzero, msl_augment_fit_mc with the identity row into a (1, C) + spatial_size batch,
     msl_instance_boxes on the fitted mask - the kernels ``LesionCache`` runs, on one case at a time, so nothing but the
     case being prepared and the batches handed out is resident.  A batch of a case with an affine also carries
     "native_shape" and "plan" (its ``RegridPlan``), as lists.
@@ -957,10 +941,7 @@ class LesionPredictFeed:
         ds, dev, C, stream = self.dataset.predict_dataset, self.device, self.channels, _stream(self.device)
         vol, mask, plan = _case_on_device(ds, pos, dev, "LesionPredictFeed")
         full_shape = tuple(int(v) for v in mask.shape)
-        if C == 1:
-            _lib.call("msl_foreground_box", ptr(vol), *vol.shape, int(self.dataset.margin), ptr(self._box), stream)
-        else:
-            _lib.call("msl_foreground_box_mc", ptr(vol), *vol.shape, int(self.dataset.margin), ptr(self._box), stream)
+        _foreground_box(vol, self.dataset.margin, self._box, stream)
         b = self._box.cpu().tolist()  # the one read that sizes the crop
         sl = tuple(slice(b[a], b[3 + a]) for a in range(3))
         shape = tuple(b[3 + a] - b[a] for a in range(3))
@@ -972,12 +953,8 @@ class LesionPredictFeed:
         if size:
             _lib.call("msl_normalize_nonzero", ptr(ci), C, size, stream)
         table = torch.tensor([[0, *shape]], dtype=torch.int64).to(dev)
-        if C == 1:
-            _lib.call("msl_augment_fit", ptr(ci), ptr(cs), max(size, 1), ptr(table), 1, ptr(self._row), 1, *self.target,
-                      ptr(slot["img"]), ptr(slot["seg"]), stream)
-        else:
-            _lib.call("msl_augment_fit_mc", ptr(ci), ptr(cs), max(size, 1), C, ptr(table), 1, ptr(self._row), 1,
-                      *self.target, ptr(slot["img"]), ptr(slot["seg"]), stream)
+        _lib.call("msl_augment_fit_mc", ptr(ci), ptr(cs), max(size, 1), C, ptr(table), 1, ptr(self._row), 1,
+                  *self.target, ptr(slot["img"]), ptr(slot["seg"]), stream)
         box = slot["box"]
         box.launch(slot["seg"], stream)
         slot["gb"].copy_(box.gb, non_blocking=True)

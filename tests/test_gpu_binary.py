@@ -10,7 +10,8 @@ import torch
 
 from mslesions3d_amd import _lib
 from mslesions3d_amd import datasets as DS
-from mslesions3d_amd.devicedata import LesionCache, LesionPredictFeed, boxes_from_binary_device
+from mslesions3d_amd.devicedata import (LesionCache, LesionPredictFeed, _BinBoxOut, _BoxOut, _InstBoxOut,
+                                        boxes_from_binary_device)
 from tests import lesion_tree_binary
 
 pytestmark = pytest.mark.gpu
@@ -219,10 +220,45 @@ def test_overflow_flags_and_bounds():
     gb, gl, off, flag = _launch([seg, seg], 64, run_cap=n_runs + 3)  # the second image does not fit
     assert flag & 8 and max(off) <= 64
     t = torch.from_numpy(seg[None]).to(DEV)
-    with pytest.raises(_lib.HipKernelError, match="capacity"):
+    with pytest.raises(_lib.HipKernelError, match=f"msl_binary_boxes: a batch holds more ground-truth boxes than the "
+                                                  f"capacity of {n_boxes - 1} rows: raise max_objects_per_image"):
         boxes_from_binary_device(t, capacity=n_boxes - 1)
-    with pytest.raises(_lib.HipKernelError, match="max_runs_per_image"):
+    with pytest.raises(_lib.HipKernelError, match=f"msl_binary_boxes: a batch holds more runs of lesion voxels than "
+                                                  f"max_runs_per_image = {n_runs - 1} per image allows: raise "
+                                                  f"max_runs_per_image"):
         boxes_from_binary_device(t, max_runs_per_image=n_runs - 1)
+
+
+def test_box_stage_messages_per_flag_bit():
+    """The (flag bit, message) table of every box stage, read off a flag word handed in (no launch): each message in
+    full, the order in which the bits are tested (binary: the run overflow, bit 8, before the row overflow, bit 1), and
+    silence on a word without the stage's bits."""
+    shape, thr = (8, 8, 8), [(1, np.inf)]
+    seg_out = _BoxOut(2, shape, 1, 5, 70, DEV)
+    inst_out = _InstBoxOut(2, shape, thr, 5, DEV)
+    bin_out = _BinBoxOut(2, shape, 5, DEV, max_runs_per_image=7)
+    assert bin_out.run_cap == 14 and seg_out.comp_cap == 70 and seg_out.n_classes == 1 and len(inst_out.thr) == 1
+    rows = "a batch holds more ground-truth boxes than the capacity of 5 rows"
+    cases = [(seg_out, 1, f"msl_seg_boxes: {rows}$"), (seg_out, 3, f"msl_seg_boxes: {rows}$"),
+             (seg_out, 2, "msl_seg_boxes: a batch holds more connected components than comp_cap = 70$"),
+             (inst_out, 1, f"msl_instance_boxes: {rows}$"), (inst_out, 5, f"msl_instance_boxes: {rows}$"),
+             (inst_out, 4, "msl_instance_boxes: a mask holds a negative value$"),
+             (bin_out, 1, f"msl_binary_boxes: {rows}: raise max_objects_per_image$"),
+             (bin_out, 8, "msl_binary_boxes: a batch holds more runs of lesion voxels than max_runs_per_image = 7 per "
+                          "image allows: raise max_runs_per_image$"),
+             (bin_out, 9, "msl_binary_boxes: a batch holds more runs")]
+    for out, flag, message in cases:
+        with pytest.raises(_lib.HipKernelError, match="^" + message):
+            out.raise_on_overflow(flag)
+    for out, flag in ((seg_out, 0), (seg_out, 4), (inst_out, 2), (bin_out, 6)):
+        out.raise_on_overflow(flag)
+    for make, message in ((lambda: _InstBoxOut(0, shape, thr, 5, DEV), "msl_instance_boxes: unsupported batch size N=0$"),
+                          (lambda: _BoxOut(1, shape, 0, 5, 70, DEV),
+                           r"msl_seg_boxes: unsupported sizes N=1 shape=\(8, 8, 8\) n_classes=0$"),
+                          (lambda: _BinBoxOut(1, shape, 5, DEV, max_runs_per_image=0),
+                           r"msl_binary_boxes: unsupported sizes N=1 shape=\(8, 8, 8\) max_runs_per_image=0$")):
+        with pytest.raises(_lib.HipKernelError, match="^" + message):
+            make()
 
 
 def test_argument_errors_launch_nothing():

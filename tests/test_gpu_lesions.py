@@ -1,5 +1,6 @@
-"""msl_foreground_box, msl_augment_fit and msl_instance_boxes (csrc/datapipe.hip) through the C ABI, and their routing
-through devicedata.LesionCache and the entry point, against the host pipeline of datasets.LesionsDataModule."""
+"""msl_foreground_box, msl_augment_fit (the C = 1 forwards of the one foreground / fit kernel) and msl_instance_boxes
+(csrc/datapipe.hip) through the C ABI, and the one-sequence route through devicedata.LesionCache (the _mc entry points
+with C = 1) and the entry point, against the host pipeline of datasets.LesionsDataModule."""
 import json
 import os
 
@@ -9,8 +10,8 @@ import torch
 
 from mslesions3d_amd import _lib
 from mslesions3d_amd import datasets as DS
-from mslesions3d_amd.devicedata import (AFFINE_STRIDE, LesionCache, _InstBoxOut, boxes_from_instances_device, fit_rows,
-                                        sample_params)
+from mslesions3d_amd.devicedata import (AFFINE_STRIDE, LesionCache, LesionPredictFeed, _InstBoxOut,
+                                        boxes_from_instances_device, fit_rows, sample_params)
 from tests import lesion_tree
 
 pytestmark = pytest.mark.gpu
@@ -134,11 +135,14 @@ def test_instance_boxes_overflow_and_bad_values():
     assert _same(gb[:n_boxes], GOLD["random_0__boxes"]) and _same(gb[n_boxes:], GOLD["random_0__boxes"][:2])
     gb, gl, off, flag = _device_boxes([seg, seg], [(1, INF)], 0)
     assert flag & 1 and off == [0, 0, 0]
-    with pytest.raises(_lib.HipKernelError, match="capacity"):
+    with pytest.raises(_lib.HipKernelError, match="msl_instance_boxes: a batch holds more ground-truth boxes than the "
+                                                  "capacity of 2 rows"):
         boxes_from_instances_device(torch.from_numpy(seg[None]).to(DEV), [(1, np.inf)], capacity=2)
     bad = seg.copy()
     bad[0, 0, 0] = -3
     assert _device_boxes([bad], [(1, INF)], 64)[3] & 4
+    with pytest.raises(_lib.HipKernelError, match="msl_instance_boxes: a mask holds a negative value"):
+        boxes_from_instances_device(torch.from_numpy(bad[None]).to(DEV), [(1, np.inf)], capacity=64)
     out = _InstBoxOut(1, seg.shape, [(1, INF)], 8, DEV)
     t = torch.from_numpy(seg[None]).to(DEV)
     for args in ((0, *seg.shape, out.thr.ctypes.data, 1), (1, *seg.shape, out.thr.ctypes.data, 9),
@@ -350,6 +354,35 @@ def test_train_batches_equal_the_host_loader(tmp_path):
         np.testing.assert_allclose(d["img"].cpu().numpy(), h["img"].numpy(), rtol=NORM_RTOL, atol=NORM_ATOL)
         for n in range(len(d["subject"])):
             assert _same(d["boxes"][n], h["boxes"][n]) and torch.equal(d["labels"][n].cpu(), h["labels"][n])
+
+
+def _recorded(work):
+    _lib.start_recording()
+    try:
+        work()
+    finally:
+        prog = _lib.stop_recording()
+    return [fn.__name__ for fn, _, _ in prog if fn is not None]
+
+
+def test_one_sequence_takes_the_entry_points_of_every_channel_count(tmp_path):
+    """One sequence is C = 1 of the calls C > 1 makes: the build's foreground box and the batch's fit of a one-sequence
+    ``LesionCache`` and ``LesionPredictFeed`` go through msl_foreground_box_mc / msl_augment_fit_mc (the values are
+    test_train_batches_equal_the_host_loader's and test_predict_entry_point_on_lesion_cases' to prove)."""
+    dm = _module(tmp_path, None)
+    assert len(dm.input_images) == 1
+
+    def train():
+        next(iter(LesionCache(dm, DEV).train_batches(0)))
+
+    def predict():
+        next(iter(LesionPredictFeed(dm, DEV).batches([0])))
+
+    for work in (train, predict):
+        names = _recorded(work)
+        torch.cuda.synchronize()
+        assert "msl_foreground_box_mc" in names and "msl_augment_fit_mc" in names, names
+        assert "msl_foreground_box" not in names and "msl_augment_fit" not in names, names
 
 
 def _run_train(tmp_path, cache):

@@ -60,7 +60,7 @@ def test_foreground_box_mc_equals_the_host_union_box(margin):
             lo, hi = DS.foreground_box(v, margin)
             assert got[:6] == list(lo) + list(hi), (C, margin)
             assert got[6:] == [-77, -77]
-            if C == 1:
+            if C == 1:  # msl_foreground_box is the forward to this launch with C = 1
                 one = torch.full((8,), -77, dtype=torch.int32, device=DEV)
                 _lib.call("msl_foreground_box", d.data_ptr(), *v.shape[1:], margin, one.data_ptr(), _stream())
                 assert one.cpu().tolist() == got
@@ -175,6 +175,8 @@ def test_augment_fit_mc_equals_the_host_steps(variant, target, C):
 
 @pytest.mark.parametrize("target", [(40, 48, 64), (33, 70, 45)])
 def test_one_channel_launch_is_msl_augment_fit_bit_for_bit(target):
+    """msl_augment_fit forwards to the C = 1 launch of the one fit kernel: this pins the forward (arena_elems as
+    seg_elems, C = 1, no windows) against msl_augment_fit_mc at C = 1, on both store paths."""
     arena = _Arena(1)
     rows = fit_rows(CASES, [h[4] for h in _host("recipe", target)])
     oi, os_ = arena.launch(rows, target)

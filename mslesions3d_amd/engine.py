@@ -126,6 +126,40 @@ class Folds(typing.NamedTuple):
 
 NO_FOLD = Fold(False, False, None, False)  # every layer of an eval-mode pass: nothing folds, nothing is finalized
 
+# Every layer kernel the passes launch: logical op -> (fp32 entry point, bf16 entry point).  A plan takes its column when it
+# is built (``Plan.ops``), a form its storage type lacks (None) is not in it, and the emitters of ``Engine`` (one per layer
+# launch, for both storage types) look the name up there.
+OPS = {
+    "stem_fwd": ("msl_stem_conv_fwd", "msl_stem_conv_fwd_bf16"),
+    "stem_dw_eval": ("msl_stem_dw_fwd_eval", "msl_stem_dw_fwd_eval_bf16"),
+    "dw_fwd": ("msl_dwconv_fwd", "msl_dwconv_fwd_bf16"),
+    "dw_fwd_fold": ("msl_dwconv_fwd_fold", "msl_dwconv_fwd_wave_bf16_fold"),
+    "pw_fwd": ("msl_pwconv_fwd", "msl_pwconv_fwd_bf16"),
+    "pw_fwd_fold": ("msl_pwconv_fwd_fold", "msl_pwconv_fwd_bf16_fold"),
+    "copy": ("msl_bn_relu_materialize", "msl_bn_relu_materialize_bf16_pad32"),
+    "copy_fold": ("msl_bn_relu_materialize_fold", "msl_bn_relu_materialize_bf16_pad32_fold"),
+    "pw_bwd": ("msl_pwconv_bwd_data", "msl_pwconv_bwd_data_bf16"),
+    "pw_bwd_fused": ("msl_pwconv_bwd_fused", None),
+    "link": ("msl_block_bwd_channel_link", "msl_block_bwd_channel_link_bf16"),
+    # "dw_bwd:" + Route.dw (the two link forms are "link" above)
+    "dw_bwd:fused_stem": ("msl_dwconv_s2_bwd_bnreduce_bww", "msl_dwconv_s2_bwd_bnreduce_bww_bf16"),
+    "dw_bwd:s2_bww": ("msl_dwconv_s2_bwd_data_bnreduce_bww", None),
+    "dw_bwd:bnreduce": ("msl_dwconv_bwd_data_bnreduce", None),
+    "dw_bwd:s2_patch": (None, "msl_dwconv_bwd_data_s2_patch_bf16"),
+    "dw_bwd:plain": ("msl_dwconv_bwd_data", "msl_dwconv_bwd_data_bf16"),
+    "pw_bww": ("msl_pwconv_bwd_weight_slabs", "msl_pwconv_bwd_weight_slabs_bf16"),
+    "dw_bww": ("msl_dwconv_bwd_weight", "msl_dwconv_bwd_weight_bf16"),
+    # "stem_bww:" + StemRoute.wgrad (plan_routes never sends a bf16 plan to "plain")
+    "stem_bww:plain": ("msl_stem_conv_bwd_weight", None),
+    "stem_bww:bnapply": ("msl_stem_conv_bwd_weight_bnapply", "msl_stem_conv_bwd_weight_bnapply_bf16"),
+    "stem_bww:fused": ("msl_stem_conv_bwd_weight_fused", "msl_stem_conv_bwd_weight_fused_bf16"),
+    "head_bwd": ("msl_head_conv_bwd_data", "msl_head_conv_bwd_data_bf16"),
+}
+# The two columns take the same argument list, except that the fp32 entry point of these ops takes this many more: an unused
+# slot (the depthwise forward's ``0``, the ``None`` of the feature copy and of the depthwise weight gradient), or the four
+# BatchNorm vectors one by one where the bf16 one takes the (BN_ROWS, C) buffer.  The emitter holds that piece per type.
+F32_EXTRA_ARGS = {"dw_fwd": 1, "copy": 1, "copy_fold": 1, "dw_bww": 1, "dw_bwd:fused_stem": 3}
+
 
 def plan_folds(pl, engine):
     """-> ``Plan.folds``: which BatchNorms a train-mode forward pass folds into their consumers from the statistics partials
@@ -260,6 +294,7 @@ class Plan:
         ncls = m.n_classes
         bf16 = dtype == "bf16"
         self.N, self.in_dims, self.need_grad, self.bf16 = N, tuple(in_dims), need_grad, bf16
+        self.ops = {op: names[bf16] for op, names in OPS.items() if names[bf16] is not None}  # this storage type's kernels
         act = dict(dtype=torch.bfloat16 if bf16 else torch.float32, device=device)  # y, z, g_y, g_z
         f32 = dict(dtype=torch.float32, device=device)
         f64 = dict(dtype=torch.float64, device=device)
@@ -583,10 +618,23 @@ class Engine:
                   ptr(bn.running_var), ptr(bn.num_batches_tracked), mom, bn.eps, ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
                   ptr(vec[3]), vec.shape[1], st)
 
-    def _forward_prologue(self, pl, training, eval_np, st, stH):
+    def _forward_open(self, x, training, need_grad):
+        """What both forward passes do before their first launch -> (plan, chain stream, heads stream).  The heads stream is
+        the chain itself for a one-stream pass and for bf16 inference on the bf16 head kernel (that pass used to be one stream
+        on either head route: 86 us of feature copies and head convolutions on the chain at 192^3 x 2)."""
+        x = x.contiguous().float()
+        self.ensure_arena(x.device)
+        pl = self.plan_for(x, need_grad)
+        pl.generation += 1
+        pl.saved_input, pl.trained_mode = x, training
+        st = self._stream()
+        return pl, st, self.side_streams(x.device)[0].cuda_stream if self.multi_stream and pl.f32_heads else st
+
+    def _forward_prologue(self, pl, training, st, stH):
         """What a forward pass starts with -> the event behind the packed head weights (None: they are on the chain).
-        ``stH`` is the heads stream, or ``st`` for a pass without one; ``eval_np``: the partial counts (of y[i], of z[i]) the
-        eval-mode table is built with."""
+        ``stH`` is the heads stream, or ``st`` for a pass without one."""
+        ones = [1] * len(pl.y)
+        eval_np = (ones, ones) if pl.bf16 else (pl.np_y, pl.np_z)  # partial counts (of y[i], of z[i]) of the eval-mode table
         if not training:
             # eval mode: (scale, shift) of all BatchNorms depend on parameters and running statistics only - one launch.  It
             # is the FIRST launch of the pass, in front of the prologue's fork: the fork's record then rides on it as a stop
@@ -614,6 +662,66 @@ class Engine:
             _lib.call("msl_nan_flag2", ptr(pl.locs), pl.locs.numel(), 1, ptr(pl.scores), pl.scores.numel(), 2, ptr(pl.nan_flag), st)
         return pl.locs, pl.scores
 
+    # -- forward emitters: one layer launch each, for both storage types (entry points: ``pl.ops``, folds: ``pl.folds``) -----
+    def _stem_forward(self, pl, training, st):
+        """features[0]'s convolution -> raw y[0]; eval mode, where the kernel takes the shape: with block 1's depthwise
+        layer, -> z[1] (``pl.stem_dw_eval``)."""
+        feats, sp, N = self.model.base.features, self.layer_specs[0], pl.N
+        D, H, W = pl.in_dims
+        x, w = ptr(pl.saved_input), ptr(feats[0][0].weight)
+        pl.stem_dw_eval = self._stem_dw_eval(self.layer_specs, training, N, D, H, W)
+        if pl.stem_dw_eval:
+            self._k("stem_fwd", pl.ops["stem_dw_eval"], x, w, ptr(pl.bn_y[0][0]), ptr(pl.bn_y[0][1]), ptr(feats[1].conv1.weight),
+                    ptr(pl.z[1]), N, sp["cin"], D, H, W, st)
+        else:
+            self._k("stem_fwd", pl.ops["stem_fwd"], x, w, ptr(pl.y[0]), ptr(pl.part_y[0]) if training else None, N, sp["cin"],
+                    D, H, W, *sp["stride"], st)
+
+    def _dw_forward(self, pl, i, training, st):
+        """Block i's depthwise layer: y[i-1] -> raw z[i], folding the BatchNorm of y[i-1] from its partials (``Fold.dw``) or
+        reading its vectors."""
+        if i == 1 and pl.stem_dw_eval:
+            return  # z1 came with the stem
+        feats, sp, N = self.model.base.features, self.layer_specs[i], pl.N
+        pd, ph, pw = pl.dims[i - 1]
+        w, shape = ptr(feats[i].conv1.weight), (N, sp["cin"], pd, ph, pw, sp["stride"][0])
+        if training and pl.folds.at[i - 1].dw:
+            bn = feats[0][1] if i == 1 else feats[i - 1].bn2
+            self._k(f"dw_fwd{i}", pl.ops["dw_fwd_fold"], ptr(pl.y[i - 1]), ptr(pl.part_y[i - 1]), pl.np_y[i - 1],
+                    float(N * pd * ph * pw), ptr(bn.weight), ptr(bn.bias), bn.eps, w, ptr(pl.z[i]), ptr(pl.part_z[i]), *shape, st)
+        else:
+            unused = () if pl.bf16 else (0,)
+            self._k(f"dw_fwd{i}", pl.ops["dw_fwd"], ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]), ptr(pl.bn_y[i - 1][1]), w,
+                    ptr(pl.z[i]), ptr(pl.part_z[i]) if training else None, *shape, *unused, st)
+
+    def _pw_forward(self, pl, i, training, st):
+        """Block i's pointwise layer: z[i] -> raw y[i], folding the BatchNorm of z[i] (``Fold.pw``) or reading its vectors,
+        which a train-mode pass finalizes right in front."""
+        blk, sp, N = self.model.base.features[i], self.layer_specs[i], pl.N
+        D, H, W = pl.dims[i]
+        w, shape = ptr(blk.conv2.weight), (N, sp["cin"], sp["cout"], D * H * W)
+        if training and pl.folds.at[i].pw:
+            self._k(f"pw_fwd{i}", pl.ops["pw_fwd_fold"], ptr(pl.z[i]), ptr(pl.part_z[i]), pl.np_z[i], float(N * D * H * W),
+                    ptr(blk.bn1.weight), ptr(blk.bn1.bias), blk.bn1.eps, w, ptr(pl.y[i]), ptr(pl.part_y[i]), *shape, st)
+        else:
+            if training:
+                self._bn_finalize(pl, "z", i, st)
+            self._k(f"pw_fwd{i}", pl.ops["pw_fwd"], ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]), w, ptr(pl.y[i]),
+                    ptr(pl.part_y[i]) if training else None, *shape, st)
+
+    def _feature_copy(self, pl, i, training, st):
+        """The zero-haloed fp32 copy of feature map i that its fp32 head convolution reads, with BatchNorm and ReLU applied
+        (``Fold.copy``: from the partials)."""
+        bn, sp, N = self.model.base.features[i].bn2, self.layer_specs[i], pl.N
+        D, H, W = pl.dims[i]
+        dst = (ptr(pl.fpad[i]),) if pl.bf16 else (None, ptr(pl.fpad[i]))  # (fp32: an unused slot in front)
+        if training and pl.folds.at[i].copy:
+            self._k(f"materialize{i}", pl.ops["copy_fold"], ptr(pl.y[i]), ptr(pl.part_y[i]), pl.np_y[i], float(N * D * H * W),
+                    ptr(bn.weight), ptr(bn.bias), bn.eps, *dst, N, sp["cout"], D, H, W, st)
+        else:
+            self._k(f"materialize{i}", pl.ops["copy"], ptr(pl.y[i]), ptr(pl.bn_y[i][0]), ptr(pl.bn_y[i][1]), *dst, N,
+                    sp["cout"], D, H, W, st)
+
     # ------------------------------------------------------------------------------------------------
     def forward(self, x, training, need_grad, nan_check=True, after_block=None):
         """x (N,Cin,D,H,W) fp32 on the GPU -> (locs (N,P,6), scores (N,P,n_classes)).
@@ -625,18 +733,9 @@ class Engine:
         m = self.model
         if getattr(m, "compute_dtype", "f32") == "bf16":
             return self._forward_bf16(x, training=training, need_grad=need_grad, nan_check=nan_check, after_block=after_block)
-        x = x.contiguous().float()
-        self.ensure_arena(x.device)
-        pl = self.plan_for(x, need_grad)
-        pl.generation += 1
-        pl.saved_input = x
-        pl.trained_mode = training
-        st = self._stream()
-        stH = self.side_streams(x.device)[0].cuda_stream if self.multi_stream else st
-        N = pl.N
-        feats = m.base.features
+        pl, st, stH = self._forward_open(x, training, need_grad)
         specs = self.layer_specs
-        ev_pack = self._forward_prologue(pl, training, (pl.np_y, pl.np_z), st, stH)
+        ev_pack = self._forward_prologue(pl, training, st, stH)
         # which BatchNorms the consumers fold from the partials, and which a launch on the chain finalizes right behind its
         # producer: fixed per plan.  The folded ones (bn module, vector buffer, partials, NP, element count) get their running
         # statistics and backward vectors from ONE launch after the last block: nothing in the forward pass reads them
@@ -651,60 +750,18 @@ class Engine:
                 fn()
             deferred = []
 
-        # stem (features[0] = Conv3d + BN + ReLU)
-        D, H, W = pl.in_dims
-        sd, sh, sw = specs[0]["stride"]
-        stem_dw = self._stem_dw_eval(specs, training, N, D, H, W)
-        if stem_dw:
-            self._k("stem_fwd", "msl_stem_dw_fwd_eval", ptr(x), ptr(feats[0][0].weight), ptr(pl.bn_y[0][0]), ptr(pl.bn_y[0][1]),
-                    ptr(feats[1].conv1.weight), ptr(pl.z[1]), N, specs[0]["cin"], D, H, W, st)
-        else:
-            self._k("stem_fwd", "msl_stem_conv_fwd", ptr(x), ptr(feats[0][0].weight), ptr(pl.y[0]),
-                    ptr(pl.part_y[0]) if training else None, N, specs[0]["cin"], D, H, W, sd, sh, sw, st)
-        pl.stem_dw_eval = stem_dw
+        self._stem_forward(pl, training, st)  # (features[0] = Conv3d + BN + ReLU)
         if fo[0].chain:
             self._bn_finalize(pl, "y", 0, st)
         for i in range(1, len(specs)):
-            sp, blk = specs[i], feats[i]
-            pd, ph, pw = pl.dims[i - 1]
-            D, H, W = pl.dims[i]
-            S = D * H * W
-            s = sp["stride"][0]
-            bn_prev = feats[0][1] if i == 1 else feats[i - 1].bn2
-            if i == 1 and stem_dw:
-                pass  # z1 came with the stem
-            elif fo[i - 1].dw:
-                self._k(f"dw_fwd{i}", "msl_dwconv_fwd_fold", ptr(pl.y[i - 1]), ptr(pl.part_y[i - 1]), pl.np_y[i - 1],
-                        float(N * pd * ph * pw), ptr(bn_prev.weight), ptr(bn_prev.bias), bn_prev.eps, ptr(blk.conv1.weight),
-                        ptr(pl.z[i]), ptr(pl.part_z[i]), N, sp["cin"], pd, ph, pw, s, st)
-            else:
-                self._k(f"dw_fwd{i}", "msl_dwconv_fwd", ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]), ptr(pl.bn_y[i - 1][1]),
-                        ptr(blk.conv1.weight), ptr(pl.z[i]), ptr(pl.part_z[i]) if training else None, N, sp["cin"], pd, ph,
-                        pw, s, 0, st)
+            self._dw_forward(pl, i, training, st)
             flush()
-            if fo[i].pw:
-                self._k(f"pw_fwd{i}", "msl_pwconv_fwd_fold", ptr(pl.z[i]), ptr(pl.part_z[i]), pl.np_z[i], float(N * S),
-                        ptr(blk.bn1.weight), ptr(blk.bn1.bias), blk.bn1.eps, ptr(blk.conv2.weight), ptr(pl.y[i]),
-                        ptr(pl.part_y[i]), N, sp["cin"], sp["cout"], S, st)
-            else:
-                if training:
-                    self._bn_finalize(pl, "z", i, st)
-                self._k(f"pw_fwd{i}", "msl_pwconv_fwd", ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]),
-                        ptr(blk.conv2.weight), ptr(pl.y[i]), ptr(pl.part_y[i]) if training else None, N, sp["cin"],
-                        sp["cout"], S, st)
+            self._pw_forward(pl, i, training, st)
             flush()
             if fo[i].chain:
                 self._bn_finalize(pl, "y", i, st)
             ev_feat = None  # the event a side stream waits for at this block, shared by everything forked here
             if i in pl.fpad:
-                def materialize(s_, i=i, sp=sp, blk=blk, D=D, H=H, W=W, S=S):
-                    if fo[i].copy:
-                        self._k(f"materialize{i}", "msl_bn_relu_materialize_fold", ptr(pl.y[i]), ptr(pl.part_y[i]), pl.np_y[i],
-                                float(N * S), ptr(blk.bn2.weight), ptr(blk.bn2.bias), blk.bn2.eps, None, ptr(pl.fpad[i]),
-                                N, sp["cout"], D, H, W, s_)
-                    else:
-                        self._k(f"materialize{i}", "msl_bn_relu_materialize", ptr(pl.y[i]), ptr(pl.bn_y[i][0]),
-                                ptr(pl.bn_y[i][1]), None, ptr(pl.fpad[i]), N, sp["cout"], D, H, W, s_)
                 # this scale's head convolution only needs the feature map: run it beside the remaining blocks - and with it
                 # the zero-haloed activation copy it reads (nothing on the chain reads that copy: the next depthwise layer
                 # re-creates the activation from the raw output itself), when the BatchNorm is folded from the partials
@@ -712,12 +769,12 @@ class Engine:
                 last = i == len(specs) - 1
                 if self.multi_stream and not last:
                     ev = ev_feat = self._record(pl, f"fwd_feat{i}", st)
-                    deferred.append(lambda ev=ev, i=i, materialize=materialize: (self._wait(stH, ev), materialize(stH),
-                                                                               self._head_forward(pl, i, stH)))
+                    deferred.append(lambda ev=ev, i=i: (self._wait(stH, ev), self._feature_copy(pl, i, training, stH),
+                                                        self._head_forward(pl, i, stH)))
                 else:
                     if last and bn_layers and self.multi_stream:
                         ev_bn_done = self._finalize_all_beside(pl, bn_layers, st)
-                    materialize(st)
+                    self._feature_copy(pl, i, training, st)
                     if ev_pack is not None:  # this scale's convolution runs on the chain: the packed weights come from stH
                         self._wait(st, ev_pack)
                         ev_pack = None
@@ -736,62 +793,19 @@ class Engine:
         """Forward with bf16 activations in HBM (csrc/bf16.hip + the bf16 head kernel): fp32 input volume, fp32 weights and
         BatchNorm vectors / statistics, bf16 everything in between, fp32 locs / scores out.  A BatchNorm that is not folded is
         finalized in front of the first launch that reads its vectors (``Fold.chain``)."""
-        m, specs, feats = self.model, self.layer_specs, self.model.base.features
-        x = x.contiguous().float()
-        self.ensure_arena(x.device)
-        pl = self.plan_for(x, need_grad)
-        pl.generation += 1
-        pl.saved_input, pl.trained_mode = x, training
-        st = self._stream()
-        # heads of the earlier scales beside the backbone: the training step, and inference too when the heads run on the fp32
-        # kernels (the bf16 inference pass used to be one stream: 86 us of feature copies and head convolutions on the chain
-        # at 192^3 x 2)
-        ms = self.multi_stream and pl.f32_heads
-        stH = self.side_streams(x.device)[0].cuda_stream if ms else st
-        N = pl.N
-        ncls = m.n_classes
-        last = len(specs) - 1
-        ones = [1] * len(specs)
-        ev_pack = self._forward_prologue(pl, training, (ones, ones), st, stH)
-        part = (lambda t: ptr(t)) if training else (lambda t: None)
+        # The schedule of the fp32 pass, except: nothing is issued a layer late (a feature copy and its head convolution are
+        # forked and issued in place), ``after_block`` fires in front of a "producer" finalize, a "consumer" finalize sits in
+        # front of the depthwise layer, the batched finalize stays on the chain, and inference may take the bf16 head route
+        pl, st, stH = self._forward_open(x, training, need_grad)
+        specs, last = self.layer_specs, len(self.layer_specs) - 1
+        ev_pack = self._forward_prologue(pl, training, st, stH)
         fo = pl.folds.at if training else [NO_FOLD] * len(specs)
-        D, H, W = pl.in_dims
-        stem_dw = self._stem_dw_eval(specs, training, N, D, H, W)
-        if stem_dw:
-            self._k("stem_fwd", "msl_stem_dw_fwd_eval_bf16", ptr(x), ptr(feats[0][0].weight), ptr(pl.bn_y[0][0]),
-                    ptr(pl.bn_y[0][1]), ptr(feats[1].conv1.weight), ptr(pl.z[1]), N, specs[0]["cin"], D, H, W, st)
-        else:
-            self._k("stem_fwd", "msl_stem_conv_fwd_bf16", ptr(x), ptr(feats[0][0].weight), ptr(pl.y[0]), part(pl.part_y[0]), N,
-                    specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
-        pl.stem_dw_eval = stem_dw
+        self._stem_forward(pl, training, st)
         for i in range(1, len(specs)):
-            sp, blk = specs[i], feats[i]
-            pd, ph, pw = pl.dims[i - 1]
-            D, H, W = pl.dims[i]
-            S = D * H * W
-            bn_prev = feats[0][1] if i == 1 else feats[i - 1].bn2
-            # the consumer rebuilds (scale, shift) from the producer's partials when they are few (every wave / workgroup
-            # repeats the sum) - no finalize launch between the two
             if fo[i - 1].chain == "consumer":
                 self._bn_finalize(pl, "y", i - 1, st)
-            if i == 1 and stem_dw:
-                pass  # z1 came with the stem
-            elif fo[i - 1].dw:
-                self._k(f"dw_fwd{i}", "msl_dwconv_fwd_wave_bf16_fold", ptr(pl.y[i - 1]), ptr(pl.part_y[i - 1]), pl.np_y[i - 1],
-                        float(N * pd * ph * pw), ptr(bn_prev.weight), ptr(bn_prev.bias), bn_prev.eps, ptr(blk.conv1.weight),
-                        ptr(pl.z[i]), ptr(pl.part_z[i]), N, sp["cin"], pd, ph, pw, sp["stride"][0], st)
-            else:
-                self._k(f"dw_fwd{i}", "msl_dwconv_fwd_bf16", ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]), ptr(pl.bn_y[i - 1][1]),
-                        ptr(blk.conv1.weight), ptr(pl.z[i]), part(pl.part_z[i]), N, sp["cin"], pd, ph, pw, sp["stride"][0], st)
-            if fo[i].pw:
-                self._k(f"pw_fwd{i}", "msl_pwconv_fwd_bf16_fold", ptr(pl.z[i]), ptr(pl.part_z[i]), pl.np_z[i], float(N * S),
-                        ptr(blk.bn1.weight), ptr(blk.bn1.bias), blk.bn1.eps, ptr(blk.conv2.weight), ptr(pl.y[i]),
-                        ptr(pl.part_y[i]), N, sp["cin"], sp["cout"], S, st)
-            else:
-                if training:
-                    self._bn_finalize(pl, "z", i, st)
-                self._k(f"pw_fwd{i}", "msl_pwconv_fwd_bf16", ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]),
-                        ptr(blk.conv2.weight), ptr(pl.y[i]), part(pl.part_y[i]), N, sp["cin"], sp["cout"], S, st)
+            self._dw_forward(pl, i, training, st)
+            self._pw_forward(pl, i, training, st)
             if after_block and i in after_block:
                 after_block[i](None)
             # a feature map's BatchNorm: folded into the fp32 copy (and into the next depthwise layer) from the partials when
@@ -804,26 +818,13 @@ class Engine:
                 sF = stH if i != last else st
                 if sF != st:
                     self._fork(pl, f"fwd_feat{i}", st, stH)
-                if fo[i].copy:
-                    self._k(f"materialize{i}", "msl_bn_relu_materialize_bf16_pad32_fold", ptr(pl.y[i]), ptr(pl.part_y[i]),
-                            pl.np_y[i], float(N * S), ptr(blk.bn2.weight), ptr(blk.bn2.bias), blk.bn2.eps, ptr(pl.fpad[i]), N,
-                            sp["cout"], D, H, W, sF)
-                else:
-                    self._k(f"materialize{i}", "msl_bn_relu_materialize_bf16_pad32", ptr(pl.y[i]), ptr(pl.bn_y[i][0]),
-                            ptr(pl.bn_y[i][1]), ptr(pl.fpad[i]), N, sp["cout"], D, H, W, sF)
+                self._feature_copy(pl, i, training, sF)
                 if sF == st and ev_pack is not None:  # the packed weights come from the heads stream
                     self._wait(st, ev_pack)
                     ev_pack = None
                 self._head_forward(pl, i, sF)
             elif i in pl.feat_ids:
-                self._k(f"materialize{i}", "msl_bn_relu_materialize_bf16", ptr(pl.y[i]), ptr(pl.bn_y[i][0]), ptr(pl.bn_y[i][1]),
-                        None, ptr(pl.fpad_cl[i]), N, sp["cout"], D, H, W, st)
-                k = pl.feat_ids.index(i)
-                lc, cc = m.pred_convs.loc_convs[k], m.pred_convs.cl_convs[k]
-                self._k(f"head_pack{i}", "msl_head_pack_weights_bf16", ptr(lc.weight), ptr(cc.weight), ptr(pl.Wp[i]), sp["cout"],
-                        ncls, st)
-                self._k(f"head_fwd{i}", "msl_head_conv_fwd_bf16", ptr(pl.fpad_cl[i]), ptr(pl.Wp[i]), ptr(lc.bias), ptr(cc.bias),
-                        ptr(pl.locs), ptr(pl.scores), N, sp["cout"], D, H, W, pl.P, pl.prior_off[i], ncls, st)
+                self._head_forward_bf16(pl, i, st)
         if training and pl.folds.batch:  # running statistics and backward vectors of the folded BatchNorms: one launch
             self._finalize_all(pl, [self._bn_entry(pl, k, i) for k, i in pl.folds.batch], st)
         return self._forward_epilogue(pl, nan_check, st, stH)
@@ -849,127 +850,41 @@ class Engine:
         folded by the batched reduction.  Same three-stream schedule as the fp32 step (dependency chain on the main stream,
         head gradients of the earlier scales on the heads stream, weight gradients alternating over the two side streams);
         a data-parallel reducer gets each bucket as soon as the launches producing it are enqueued (as in the fp32 step)."""
-        m, specs, feats = self.model, self.layer_specs, self.model.base.features
-        gv = self.arena.grad_views
-        st = self._stream()
+        # The schedule of the fp32 pass, except: every side-stream launch is forked and issued in place, not one layer late
+        # (both weight gradients of block i wait for one "dz" record made behind the channel link, in front of any other
+        # depthwise form; odd blocks go to the wgrad stream, even ones to the heads stream), the chain's own scale goes first
+        # on one stream too, and the tail's pointwise weight gradients are never batched
+        st, stH, stW, dlocs, dscores, _, groups, report, last, side_feats, packed = self._backward_open(
+            pl, dlocs, dscores, on_bucket_ready)
         ms = self.multi_stream
-        if ms:
-            sH, sW = self.side_streams(pl.locs.device)
-            stH, stW = sH.cuda_stream, sW.cuda_stream
-        else:
-            stH = stW = st
-        N, ncls = pl.N, m.n_classes
-        prepacked = dlocs is None  # the loss kernel wrote the head-gradient images itself (MultiBoxLoss._run_loss_pack)
-        if not prepacked:
-            dlocs, dscores = dlocs.contiguous(), dscores.contiguous()
-        last = len(specs) - 1
-        if last not in pl.feat_ids:
-            raise RuntimeError("the last backbone feature must feed a head")
-        wanted = getattr(on_bucket_ready, "stages", None)
-        groups = self._bucket_groups(on_bucket_ready) if wanted else {}
-        report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, ms)
-
-        def head(f, s_data, s_weight, done=None):
-            C = specs[f]["cout"]
-            D, H, W = pl.dims[f]
-            if not packed:
-                self._k(f"head_gpack{f}", "msl_head_grad_pack", ptr(dlocs), ptr(dscores), ptr(pl.dO[f]), N, D, H, W, pl.P,
-                        pl.prior_off[f], ncls, s_data)
-            self._k(f"head_bwd{f}", "msl_head_conv_bwd_data_bf16", ptr(pl.dO[f]), ptr(pl.Wb[f]), ptr(pl.g_y[f]), N, C, D, H, W,
-                    ncls, s_data)
-            if done is not None:
-                self._record(pl, done, s_data)
-            if s_weight != s_data:
-                self._wait(s_weight, self._record(pl, f"head_dO{f}", s_data))
-            self._k(f"head_bww{f}", "msl_head_conv_bwd_weight", ptr(pl.dO[f]), ptr(pl.fpad[f]), None, None, None, None,
-                    ptr(pl.head_ws[f]), N, C, D, H, W, ncls, s_weight)
-
-        side_feats = [f for f in pl.feat_ids if f != last] if ms else []
-        packed = prepacked or (bool(side_feats) and self.batch_head_gpack)
-        if packed and not prepacked:
-            self._head_gpack_batch(pl, dlocs, dscores, st)
-        if side_feats:
-            self._fork(pl, "bwd_loss_ready", st, stH)
-        head(last, st, stW)  # its data gradient starts the chain
+        self._head_backward(pl, last, dlocs, dscores, st, weight=False, packed=packed)  # its data gradient starts the chain
+        if stW != st:
+            self._wait(stW, self._record(pl, f"head_dO{last}", st))
+        self._head_backward(pl, last, dlocs, dscores, stW, data=False)
         for f in reversed(side_feats) if ms else [f for f in pl.feat_ids if f != last]:
-            head(f, stH, stH, done=f"head_done{f}" if ms else None)
+            self._head_backward(pl, f, dlocs, dscores, stH, self._event(pl, f"head_done{f}") if ms else None, packed=packed)
         report("heads")
         for i in range(last, 0, -1):
-            sp = specs[i]
-            D, H, W = pl.dims[i]
-            S = D * H * W
-            pd, ph, pw = pl.dims[i - 1]
-            s = sp["stride"][0]
-            name = f"base.features.{i}"
-            r = pl.routes[i]
-            link = r.dw in ("link", "link_bww")  # the per-channel link of the tail blocks, as in the fp32 step
-            if r.bn2 == "bn":  # ("link": the channel link of block i+1 has already turned g_y[i] into dL/dy_i)
-                self._bn_bwd_bf16(pl.g_y[i], pl.y[i], pl.bn_y[i], name + ".bn2", N, sp["cout"], S, pl, st, pre_np=r.y_np)
-            self._k(f"pw_bwd{i}", "msl_pwconv_bwd_data_bf16", ptr(pl.g_y[i]), ptr(feats[i].conv2.weight), ptr(pl.g_z[i]), N,
-                    sp["cin"], sp["cout"], S, st)
+            link = pl.routes[i].dw in ("link", "link_bww")  # the per-channel link of the tail blocks, as in the fp32 step
+            self._pw_backward(pl, i, st)
             accumulate = 1 if (i - 1) in pl.feat_ids else 0  # the heads already wrote their share
             if not link:
-                self._bn_bwd_bf16(pl.g_z[i], pl.z[i], pl.bn_z[i], name + ".bn1", N, sp["cin"], S, pl, st)
+                self._bn_backward(pl, "z", i, st)
             if accumulate and (i - 1) in side_feats:
                 self._wait(st, pl.events[f"head_done{i - 1}"])
             if link:
-                prev = f"base.features.{i - 1}.bn2"
-                self._k(f"link{i}", "msl_block_bwd_channel_link_bf16", ptr(pl.g_z[i]), ptr(pl.z[i]), ptr(pl.bn_z[i]),
-                        ptr(feats[i].conv1.weight), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1]), ptr(pl.g_y[i - 1]),
-                        ptr(gv[name + ".bn1.weight"]), ptr(gv[name + ".bn1.bias"]), ptr(gv[prev + ".weight"]),
-                        ptr(gv[prev + ".bias"]), ptr(gv[name + ".conv1.weight"]) if r.dw == "link_bww" else None, N, sp["cin"],
-                        pd, ph, pw, s, accumulate, st)
+                self._channel_link(pl, i, accumulate, st)
             sX = st
             if ms:  # both weight gradients of the block on a side stream, once dL/dy_i and dL/dz_i are final
                 sX = stW if i % 2 else stH
                 self._wait(sX, self._record(pl, f"dz{i}", st))
-            if r.dw == "fused_stem":
-                # one pass over (dL/dz_1, y_0): the stem's BatchNorm-backward sums + this block's depthwise weight gradient;
-                # the stem weight gradient below rebuilds dL/d(stem activation) from dL/dz_1 on the fly
-                self._k("dw_bwd1", "msl_dwconv_s2_bwd_bnreduce_bww_bf16", ptr(pl.g_z[1]), ptr(feats[1].conv1.weight), ptr(pl.y[0]),
-                        ptr(pl.bn_y[0]), ptr(pl.partials), ptr(pl.partials_wf), ptr(pl.w1_taps_t), N, 32, pd, ph, pw, st)
-            elif r.dw == "s2_patch":
-                # big producer layer: emit the BatchNorm-backward partials of y_{i-1} while its gradient is in registers
-                self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data_s2_patch_bf16", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight),
-                        ptr(pl.g_y[i - 1]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1]), ptr(pl.partials), N, sp["cin"], pd, ph, pw,
-                        accumulate, st)
-            elif not link:
-                self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data_bf16", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight), ptr(pl.g_y[i - 1]),
-                        N, sp["cin"], pd, ph, pw, s, accumulate, st)
-            out = r.pw_part[0] if r.pw_part is not None else gv[name + ".conv2.weight"]
-            self._k(f"pw_bww{i}", "msl_pwconv_bwd_weight_slabs_bf16", ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]),
-                    ptr(pl.bn_z[i][1]), ptr(out), N, sp["cin"], sp["cout"], S, sX)
-            if r.dw in DW_BWW:  # (else its partials came with the fused pass: pl.partials_wf / the link wrote dW)
-                self._k(f"dw_bww{i}", "msl_dwconv_bwd_weight_bf16", ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]),
-                        ptr(pl.bn_y[i - 1][1]), ptr(pl.dw_part[i]), N, sp["cin"], pd, ph, pw, s, sX)
+            if not link:
+                self._dw_backward(pl, i, accumulate, st)
+            self._pw_wgrad(pl, i, sX)
+            self._dw_wgrad(pl, i, sX)
             report(i)
-        # stem: BatchNorm-backward sums, then the weight gradient with the BatchNorm backward applied on load
-        od, oh, ow = pl.dims[0]
-        S0 = od * oh * ow
-        D, H, W = pl.in_dims
-        vec = pl.bn_y[0]
-        r = pl.routes[0]
-        NP = r.y_np
-        if NP is None:
-            NP = _lib.load().msl_bn_relu_bwd_bf16_num_partials(N, S0)
-            self._k("bn_bwd_reduce:stem", "msl_bn_relu_bwd_reduce_bf16", ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(vec[0]), ptr(vec[1]),
-                    ptr(vec[2]), ptr(vec[3]), ptr(pl.partials), N, specs[0]["cout"], S0, st)
-        if r.wgrad == "fused":
-            _lib.call("msl_bn_bwd_finalize_coef", ptr(pl.partials), NP, float(N * S0), ptr(gv["base.features.0.1.weight"]),
-                      ptr(gv["base.features.0.1.bias"]), ptr(vec), specs[0]["cout"], st)
-            self._k("stem_bww", "msl_stem_conv_bwd_weight_fused_bf16", ptr(pl.g_z[1]), ptr(pl.w1_taps_t), ptr(pl.y[0]), ptr(vec),
-                    ptr(pl.saved_input), None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
-        else:
-            _lib.call("msl_bn_bwd_finalize", ptr(pl.partials), NP, float(N * S0), ptr(gv["base.features.0.1.weight"]),
-                      ptr(gv["base.features.0.1.bias"]), ptr(vec[4]), ptr(vec[5]), specs[0]["cout"], st)
-            self._k("stem_bww", "msl_stem_conv_bwd_weight_bnapply_bf16", ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(vec), ptr(pl.saved_input),
-                    None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
-        if ms:  # every gradient is complete once the side streams have been joined
-            self._fork(pl, "bwd_join_w", stW, st)
-            self._fork(pl, "bwd_join_h", stH, st)
-        if not groups:  # single process: ONE reduction launch for every layer's partial sums, in front of the optimiser
-            self._grad_reduce(pl, "all", None, st)
-        report(0, join_heads=False)
+        self._stem_backward(pl, st)
+        self._backward_close(pl, groups, report, st, stH, stW)
 
     def _stem_dw_eval(self, specs, training, N, D, H, W):
         """Eval mode: may the stem and block 1's depthwise convolution run as one launch (csrc/stemdw.hip: the stem
@@ -1058,6 +973,21 @@ class Engine:
         self._k(f"head_fwd{f}", "msl_head_conv_fwd", ptr(pl.fpad[f]), ptr(pl.Wf[f]), ptr(lc.bias), ptr(cc.bias), ptr(pl.locs),
                 ptr(pl.scores), ptr(pl.head_ws[f]), pl.N, C, D, H, W, pl.P, pl.prior_off[f], ncls, st)
 
+    def _head_forward_bf16(self, pl, f, st):
+        """bf16 inference with ``bf16_heads = "bf16"``: the channels-last bf16 copy of feature map f, this scale's packed
+        weights and its head convolution on the bf16 MFMA kernel."""
+        m = self.model
+        ncls = m.n_classes
+        k = pl.feat_ids.index(f)
+        lc, cc = m.pred_convs.loc_convs[k], m.pred_convs.cl_convs[k]
+        C = self.layer_specs[f]["cout"]
+        D, H, W = pl.dims[f]
+        self._k(f"materialize{f}", "msl_bn_relu_materialize_bf16", ptr(pl.y[f]), ptr(pl.bn_y[f][0]), ptr(pl.bn_y[f][1]), None,
+                ptr(pl.fpad_cl[f]), pl.N, C, D, H, W, st)
+        self._k(f"head_pack{f}", "msl_head_pack_weights_bf16", ptr(lc.weight), ptr(cc.weight), ptr(pl.Wp[f]), C, ncls, st)
+        self._k(f"head_fwd{f}", "msl_head_conv_fwd_bf16", ptr(pl.fpad_cl[f]), ptr(pl.Wp[f]), ptr(lc.bias), ptr(cc.bias),
+                ptr(pl.locs), ptr(pl.scores), pl.N, C, D, H, W, pl.P, pl.prior_off[f], ncls, st)
+
     # ------------------------------------------------------------------------------------------------
     def _bn_bwd(self, g, y, vec, bn_name, count, N, C, S, pl, st, pre_np=None, apply=True, coef=False, partials=None):
         """In place: g (= dL/d relu(bn(y))) becomes dL/dy; writes dgamma/dbeta into the gradient arena.
@@ -1110,7 +1040,7 @@ class Engine:
             if not packed:
                 self._k(f"head_gpack{f}", "msl_head_grad_pack", ptr(dlocs), ptr(dscores), ptr(pl.dO[f]), pl.N, D, H, W, pl.P,
                         pl.prior_off[f], ncls, st)
-            self._k(f"head_bwd{f}", "msl_head_conv_bwd_data", ptr(pl.dO[f]), ptr(pl.Wb[f]), ptr(pl.g_y[f]), pl.N, C, D, H, W, ncls, st)
+            self._k(f"head_bwd{f}", pl.ops["head_bwd"], ptr(pl.dO[f]), ptr(pl.Wb[f]), ptr(pl.g_y[f]), pl.N, C, D, H, W, ncls, st)
             if data_done_event is not None:  # the activation-gradient chain only waits for the data gradient
                 _lib.call("msl_event_record", data_done_event, st, tag="event")
         if not weight:
@@ -1173,6 +1103,173 @@ class Engine:
                 self._hook(fire, stage)
         return report
 
+    def _backward_open(self, pl, dlocs, dscores, on_bucket_ready):
+        """What both backward passes do before the first head gradient -> (chain, heads and wgrad stream - the chain three
+        times for a one-stream pass -, contiguous dlocs / dscores, the reducer's stages, groups, report, index of the last
+        block, the scales whose gradients run on the heads stream, whether the head-gradient images are already packed)."""
+        st = self._stream()
+        ms = self.multi_stream
+        stH, stW = (s.cuda_stream for s in self.side_streams(pl.locs.device)) if ms else (st, st)
+        prepacked = dlocs is None  # the loss kernel wrote the head-gradient images itself (MultiBoxLoss._run_loss_pack)
+        if not prepacked:
+            dlocs, dscores = dlocs.contiguous(), dscores.contiguous()
+        last = len(self.layer_specs) - 1
+        if last not in pl.feat_ids:
+            raise RuntimeError("the last backbone feature must feed a head")
+        wanted = getattr(on_bucket_ready, "stages", None)
+        # data parallel: the partial sums of a gradient bucket are folded when the bucket's last stage has been enqueued
+        # (stage -> parameter names); single process: one reduction at the very end
+        groups = self._bucket_groups(on_bucket_ready) if wanted else {}
+        report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, ms)
+        side_feats = [f for f in pl.feat_ids if f != last] if ms else []
+        packed = prepacked or (bool(side_feats) and self.batch_head_gpack)
+        if packed and not prepacked:
+            self._head_gpack_batch(pl, dlocs, dscores, st)
+        if side_feats:
+            # the earlier scales' gradients (heads stream) need the head-gradient images - written by the launch in front
+            # of this point (the loss kernel, or the batched pack), whose stop event this record becomes: no packet on the
+            # chain, and the heads stream starts one launch earlier than behind the chain's own head bwd-data (which was
+            # measured 1-2 % slower: the heads stream's gradients are as critical as the chain here)
+            self._fork(pl, "bwd_loss_ready", st, stH)
+        return st, stH, stW, dlocs, dscores, wanted, groups, report, last, side_feats, packed
+
+    def _backward_close(self, pl, groups, report, st, stH, stW):
+        if self.multi_stream:  # every gradient is complete once the side streams have been joined
+            self._fork(pl, "bwd_join_w", stW, st)
+            self._fork(pl, "bwd_join_h", stH, st)
+        if not groups:  # single process: ONE reduction launch for every layer's partial sums, right in front of the optimiser
+            self._grad_reduce(pl, "all", None, st)
+        report(0, join_heads=False)
+
+    # -- backward emitters: one layer launch each, for both storage types (entry points: ``pl.ops``, forms: ``pl.routes``) ---
+    def _bn_backward(self, pl, kind, i, st):
+        """BatchNorm backward of y[i] ("y") or z[i] ("z") of block i, in place, by the driver of the plan's storage type -
+        from the reduce sums another launch left, where the route says so."""
+        sp, r, N = self.layer_specs[i], pl.routes[i], pl.N
+        D, H, W = pl.dims[i]
+        S = D * H * W
+        if kind == "y":
+            g, t, vec, C, name, pre_np, part = pl.g_y[i], pl.y[i], pl.bn_y[i], sp["cout"], f"base.features.{i}.bn2", r.y_np, None
+        else:  # ("pw_fused", fp32: the one-pass pointwise backward left the sums of z[i] in its own buffer)
+            _, part, pre_np = pl.pw_fused[i] if r.bn2 == "pw_fused" else (None, None, None)
+            g, t, vec, C, name = pl.g_z[i], pl.z[i], pl.bn_z[i], sp["cin"], f"base.features.{i}.bn1"
+        if pl.bf16:
+            self._bn_bwd_bf16(g, t, vec, name, N, C, S, pl, st, pre_np=pre_np)
+        else:
+            self._bn_bwd(g, t, vec, name, N * S, N, C, S, pl, st, pre_np=pre_np, partials=part)
+
+    def _pw_backward(self, pl, i, st):
+        """dL/dy_i -> dL/d relu(bn1(z_i)) in g_z[i]: BatchNorm2 backward where it is still to do (``Route.bn2``), then the
+        pointwise bwd-data GEMM."""
+        blk, sp, r, N = self.model.base.features[i], self.layer_specs[i], pl.routes[i], pl.N
+        D, H, W = pl.dims[i]
+        S = D * H * W
+        if r.bn2 == "pw_fused":
+            # BatchNorm backward of y_i (applied on load), bwd-data GEMM, BatchNorm1-backward sums of z_i and the pointwise
+            # weight gradient in ONE pass (csrc/pwfused.hip)
+            gv, name = self.arena.grad_views, f"base.features.{i}.bn2"
+            slabs_f, part_f, _ = pl.pw_fused[i]
+            self._k(f"pw_bwd_fused{i}", pl.ops["pw_bwd_fused"], ptr(pl.g_y[i]), ptr(pl.y[i]), ptr(pl.bn_y[i]), ptr(pl.partials),
+                    r.y_np, float(N * S), ptr(gv[name + ".weight"]), ptr(gv[name + ".bias"]), ptr(blk.conv2.weight),
+                    ptr(pl.z[i]), ptr(pl.bn_z[i]), ptr(pl.g_z[i]), ptr(part_f), ptr(slabs_f), N, sp["cin"], sp["cout"], S, st)
+            return
+        if r.bn2 == "bn":  # ("link": the channel link of block i+1 has already turned g_y[i] into dL/dy_i)
+            self._bn_backward(pl, "y", i, st)
+        self._k(f"pw_bwd{i}", pl.ops["pw_bwd"], ptr(pl.g_y[i]), ptr(blk.conv2.weight), ptr(pl.g_z[i]), N, sp["cin"], sp["cout"],
+                S, st)
+
+    def _channel_link(self, pl, i, accumulate, st):
+        """Tail block: BatchNorm1 backward of z_i, depthwise bwd-data (+ the heads' share of g_y[i-1]: ``accumulate``) and
+        BatchNorm2 backward of y_{i-1} in one launch; "link_bww": the depthwise weight gradient too."""
+        sp, gv = self.layer_specs[i], self.arena.grad_views
+        name, prev = f"base.features.{i}", "base.features.0.1" if i == 1 else f"base.features.{i - 1}.bn2"
+        self._k(f"link{i}", pl.ops["link"], ptr(pl.g_z[i]), ptr(pl.z[i]), ptr(pl.bn_z[i]),
+                ptr(self.model.base.features[i].conv1.weight), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1]), ptr(pl.g_y[i - 1]),
+                ptr(gv[name + ".bn1.weight"]), ptr(gv[name + ".bn1.bias"]), ptr(gv[prev + ".weight"]), ptr(gv[prev + ".bias"]),
+                ptr(gv[name + ".conv1.weight"]) if pl.routes[i].dw == "link_bww" else None, pl.N, sp["cin"], *pl.dims[i - 1],
+                sp["stride"][0], accumulate, st)
+
+    def _dw_backward(self, pl, i, accumulate, st):
+        """Depthwise bwd-data of block i in the form of ``Route.dw`` (a block without a channel link): dL/dz_i -> g_y[i-1]."""
+        sp, dw, N = self.layer_specs[i], pl.routes[i].dw, pl.N
+        g, w, y = ptr(pl.g_z[i]), ptr(self.model.base.features[i].conv1.weight), ptr(pl.y[i - 1])
+        dims, s = pl.dims[i - 1], sp["stride"][0]
+        # the BatchNorm of y_{i-1}, for the forms that need it: the vectors one by one (fp32) or their buffer (bf16)
+        vec = () if dw == "plain" else (ptr(pl.bn_y[i - 1]),) if pl.bf16 else tuple(ptr(pl.bn_y[i - 1][k]) for k in range(4))
+        if dw == "fused_stem":
+            # one pass over (dL/dz_1, y_0): BatchNorm-backward sums of the stem + the depthwise weight gradient; the stem
+            # weight gradient rebuilds dL/d(stem activation) from dL/dz_1 on the fly
+            args = (g, w, y, *vec, ptr(pl.partials), ptr(pl.partials_wf), ptr(pl.w1_taps_t), N, 32, *dims)
+        elif dw == "s2_bww":
+            # big stride-2 producer layer: bwd-data, the BatchNorm-backward sums of y_{i-1} AND this block's depthwise
+            # weight gradient in one pass over (dL/dz_i, y_{i-1}) - the weight-gradient launch on the side stream (the same
+            # 38 MB read again, 35 us beside the chain at block 2) disappears
+            args = (g, w, ptr(pl.g_y[i - 1]), y, *vec, ptr(pl.partials), ptr(pl.routes[i].dw_part[0]), N, sp["cin"], *dims,
+                    accumulate)
+        elif dw == "bnreduce":
+            # big producer layer: emit the BatchNorm-backward partials of y_{i-1} while its gradient is in registers
+            args = (g, w, ptr(pl.g_y[i - 1]), y, *vec, ptr(pl.partials), N, sp["cin"], *dims, s, accumulate)
+        elif dw == "s2_patch":  # (the same, stride 2)
+            args = (g, w, ptr(pl.g_y[i - 1]), y, *vec, ptr(pl.partials), N, sp["cin"], *dims, accumulate)
+        else:
+            assert dw == "plain", dw
+            args = (g, w, ptr(pl.g_y[i - 1]), N, sp["cin"], *dims, s, accumulate)
+        self._k(f"dw_bwd{i}", pl.ops["dw_bwd:" + dw], *args, st)
+
+    def _pw_wgrad_row(self, pl, i):
+        """(dL/dy_i, z_i, scale and shift of its BatchNorm, destination, Cin, Cout, S) of block i's pointwise weight gradient:
+        partial sums only - slabs stay in this layer's own buffer until Engine._grad_reduce."""
+        sp, r = self.layer_specs[i], pl.routes[i]
+        D, H, W = pl.dims[i]
+        out = r.pw_part[0] if r.pw_part is not None else self.arena.grad_views[f"base.features.{i}.conv2.weight"]
+        return ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]), ptr(out), sp["cin"], sp["cout"], D * H * W
+
+    def _pw_wgrad(self, pl, i, st):
+        row = self._pw_wgrad_row(pl, i)
+        self._k(f"pw_bww{i}", pl.ops["pw_bww"], *row[:5], pl.N, *row[5:], st)
+
+    def _dw_wgrad(self, pl, i, st):
+        """Block i's depthwise weight gradient (fp64 partials for Engine._grad_reduce), where no other pass sums it: else its
+        partials came with the depthwise backward pass (``Route.dw_part``) or the link wrote dW."""
+        if pl.routes[i].dw not in DW_BWW:
+            return
+        sp = self.layer_specs[i]
+        dst = (ptr(pl.dw_part[i]),) if pl.bf16 else (None, ptr(pl.dw_part[i]))  # (fp32: an unused slot in front)
+        self._k(f"dw_bww{i}", pl.ops["dw_bww"], ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]), ptr(pl.bn_y[i - 1][1]),
+                *dst, pl.N, sp["cin"], *pl.dims[i - 1], sp["stride"][0], st)
+
+    def _stem_backward(self, pl, st):
+        """The stem's tail of the backward pass: its BatchNorm backward as far as ``StemRoute`` leaves it to do, then the
+        weight gradient in the form of ``StemRoute.wgrad``."""
+        sp, r, N, gv = self.layer_specs[0], pl.routes[0], pl.N, self.arena.grad_views
+        od, oh, ow = pl.dims[0]
+        S0, vec = od * oh * ow, pl.bn_y[0]
+        if pl.bf16:  # BatchNorm-backward sums (unless block 1's depthwise form left them), then the coefficients
+            NP = r.y_np
+            if NP is None:
+                NP = _lib.load().msl_bn_relu_bwd_bf16_num_partials(N, S0)
+                self._k("bn_bwd_reduce:stem", "msl_bn_relu_bwd_reduce_bf16", ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(vec[0]), ptr(vec[1]),
+                        ptr(vec[2]), ptr(vec[3]), ptr(pl.partials), N, sp["cout"], S0, st)
+            bn = ("base.features.0.1.weight", "base.features.0.1.bias")
+            if r.wgrad == "fused":
+                _lib.call("msl_bn_bwd_finalize_coef", ptr(pl.partials), NP, float(N * S0), ptr(gv[bn[0]]), ptr(gv[bn[1]]),
+                          ptr(vec), sp["cout"], st)
+            else:
+                _lib.call("msl_bn_bwd_finalize", ptr(pl.partials), NP, float(N * S0), ptr(gv[bn[0]]), ptr(gv[bn[1]]),
+                          ptr(vec[4]), ptr(vec[5]), sp["cout"], st)
+        elif r.bn == "bn":  # ("link", tiny inputs: block 1's channel link has already applied the stem's BatchNorm backward)
+            # "bnapply" / "fused": the reduce came with the depthwise bwd-data, the apply is part of the weight gradient
+            self._bn_bwd(pl.g_y[0], pl.y[0], vec, "base.features.0.1", N * S0, N, sp["cout"], S0, pl, st, pre_np=r.y_np,
+                         apply=r.wgrad == "plain", coef=r.wgrad == "fused")
+        if r.wgrad == "fused":  # rebuilt from dL/dz_1, on the coefficients of msl_bn_bwd_finalize_coef
+            src = (ptr(pl.g_z[1]), ptr(pl.w1_taps_t), ptr(pl.y[0]), ptr(vec))
+        elif r.wgrad == "bnapply":  # the BatchNorm backward applied on load
+            src = (ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(vec))
+        else:
+            src = (ptr(pl.g_y[0]),)
+        self._k("stem_bww", pl.ops["stem_bww:" + r.wgrad], *src, ptr(pl.saved_input), None, ptr(pl.ws_stem), N, sp["cin"],
+                *pl.in_dims, *sp["stride"], st)
+
     def backward(self, pl, dlocs, dscores, on_bucket_ready=None):
         """Given dL/dlocs, dL/dscores, fill the flat gradient arena.  ``on_bucket_ready(stage)`` is called right
         after the launches that complete a gradient stage ('heads', 7, ..., 0) have been enqueued; if it has a
@@ -1181,30 +1278,10 @@ class Engine:
             raise RuntimeError("backward needs a train-mode forward made with gradients enabled")
         if pl.bf16:
             return self._backward_bf16(pl, dlocs, dscores, on_bucket_ready)
-        specs, feats, N = self.layer_specs, self.model.base.features, pl.N
-        gv = self.arena.grad_views
-        st = self._stream()
-        ms = self.multi_stream
-        if ms:
-            sH, sW = self.side_streams(pl.locs.device)
-            stH, stW = sH.cuda_stream, sW.cuda_stream
-        else:
-            stH = stW = st
-        prepacked = dlocs is None  # the loss kernel wrote the head-gradient images itself (MultiBoxLoss._run_loss_pack)
-        if not prepacked:
-            dlocs, dscores = dlocs.contiguous(), dscores.contiguous()
-        wanted = getattr(on_bucket_ready, "stages", None)
-        # data parallel: the partial sums of a gradient bucket are folded when the bucket's last stage has been enqueued
-        # (stage -> parameter names); single process: one reduction at the very end
-        groups = self._bucket_groups(on_bucket_ready) if wanted else {}
-        report = self._reporter(pl, on_bucket_ready, groups, st, stH, stW, ms)
-        # heads: the last scale feeds the chain immediately (main stream); the earlier scales are only needed when
-        # the chain reaches their feature map, so they run on the heads stream beside blocks 7..4
-        last = len(specs) - 1
-        side_feats = [f for f in pl.feat_ids if f != last] if ms else []
-        packed = prepacked or (bool(side_feats) and self.batch_head_gpack)
-        if packed and not prepacked:
-            self._head_gpack_batch(pl, dlocs, dscores, st)
+        # (the bf16 step: _backward_bf16, which says how its schedule differs from this one)
+        specs, N, ms = self.layer_specs, pl.N, self.multi_stream
+        st, stH, stW, dlocs, dscores, wanted, groups, report, last, side_feats, packed = self._backward_open(
+            pl, dlocs, dscores, on_bucket_ready)
         L = _lib.load()
         pending = []  # side-stream launches, issued one layer late so that the chain's launches always go first
         sinks = []    # (closure, event) of the weight-gradient launches still to be issued
@@ -1216,12 +1293,8 @@ class Engine:
                     tail.append(i)
             tail = tail[:4] if len(tail) >= 2 else []
         tail_args = []
-        if side_feats:
-            # the earlier scales' gradients (heads stream) need the head-gradient images - written by the launch in front
-            # of this point (the loss kernel, or the batched pack), whose stop event this record becomes: no packet on the
-            # chain, and the heads stream starts one launch earlier than behind the chain's own head bwd-data (which was
-            # measured 1-2 % slower: the heads stream's gradients are as critical as the chain here)
-            self._fork(pl, "bwd_loss_ready", st, stH)
+        # heads: the last scale feeds the chain immediately (main stream); the earlier scales are only needed when
+        # the chain reaches their feature map, so they run on the heads stream beside blocks 7..4
         for f in pl.feat_ids:  # the chain's own scale first: its data gradient starts the backward chain
             if f not in side_feats:
                 if ms:
@@ -1239,94 +1312,41 @@ class Engine:
             pending = []
         report("heads")
         for i in range(last, 0, -1):
-            sp = specs[i]
-            D, H, W = pl.dims[i]
-            S = D * H * W
-            pd, ph, pw = pl.dims[i - 1]
-            s = sp["stride"][0]
-            name = f"base.features.{i}"
-            if i not in pl.fpad and i == last:
-                raise RuntimeError("the last backbone feature must feed a head")
             # y_i = pw(relu(bn1(z_i))): BN2 backward, then the two GEMMs; z_i = dw(relu(bn(y_{i-1}))): BN1 backward,
             # then the depthwise gradients.  The host enqueues the dependency chain (main stream) FIRST and the two
             # weight gradients (wgrad stream, waiting on events recorded in the chain) afterwards: the chain is made of
             # ~10 us kernels, so any launch queued in front of its next link shows up as idle time.
             r = pl.routes[i]
             pw_fused, link = r.bn2 == "pw_fused", r.dw in ("link", "link_bww")
-            slabs_f, part_f, z_np = pl.pw_fused[i] if pw_fused else (None, None, None)
-            if pw_fused:
-                # BatchNorm backward of y_i (applied on load), bwd-data GEMM, BatchNorm1-backward sums of z_i and the pointwise
-                # weight gradient in ONE pass (csrc/pwfused.hip)
-                self._k(f"pw_bwd_fused{i}", "msl_pwconv_bwd_fused", ptr(pl.g_y[i]), ptr(pl.y[i]), ptr(pl.bn_y[i]), ptr(pl.partials),
-                        r.y_np, float(N * S), ptr(gv[name + ".bn2.weight"]), ptr(gv[name + ".bn2.bias"]),
-                        ptr(feats[i].conv2.weight), ptr(pl.z[i]), ptr(pl.bn_z[i]), ptr(pl.g_z[i]), ptr(part_f), ptr(slabs_f), N,
-                        sp["cin"], sp["cout"], S, st)
-            else:
-                if r.bn2 == "bn":  # ("link": the channel link of block i+1 has already turned g_y[i] into dL/dy_i)
-                    self._bn_bwd(pl.g_y[i], pl.y[i], pl.bn_y[i], name + ".bn2", N * S, N, sp["cout"], S, pl, st, pre_np=r.y_np)
-                self._k(f"pw_bwd{i}", "msl_pwconv_bwd_data", ptr(pl.g_y[i]), ptr(feats[i].conv2.weight), ptr(pl.g_z[i]), N,
-                        sp["cin"], sp["cout"], S, st)
+            self._pw_backward(pl, i, st)
             accumulate = 1 if (i - 1) in pl.fpad else 0  # the heads already wrote their share
             # a block whose pointwise weight gradient rides in the tail's batched launch (issued with the shallowest of them) and
             # whose depthwise weight gradient the link produces has nothing waiting for dL/dz_i: no event record on the chain
             idle_sink = (r.dw == "link_bww" and i in tail and i != tail[-1]) or (pw_fused and r.dw == "fused_stem")
             rec_here = ms and not idle_sink
             if not link:
-                self._bn_bwd(pl.g_z[i], pl.z[i], pl.bn_z[i], name + ".bn1", N * S, N, sp["cin"], S, pl, st, pre_np=z_np,
-                             partials=part_f)
+                self._bn_backward(pl, "z", i, st)
                 ev_dz = self._record(pl, f"dz{i}", st) if rec_here else None
             if accumulate and (i - 1) in side_feats:
                 self._wait(st, pl.events[f"head_done{i - 1}"])
             if link:
-                prev = "base.features.0.1" if i == 1 else f"base.features.{i - 1}.bn2"
-                self._k(f"link{i}", "msl_block_bwd_channel_link", ptr(pl.g_z[i]), ptr(pl.z[i]), ptr(pl.bn_z[i]),
-                        ptr(feats[i].conv1.weight), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1]), ptr(pl.g_y[i - 1]),
-                        ptr(gv[name + ".bn1.weight"]), ptr(gv[name + ".bn1.bias"]), ptr(gv[prev + ".weight"]),
-                        ptr(gv[prev + ".bias"]), ptr(gv[name + ".conv1.weight"]) if r.dw == "link_bww" else None, N, sp["cin"],
-                        pd, ph, pw, s, accumulate, st)
+                self._channel_link(pl, i, accumulate, st)
                 ev_dz = self._record(pl, f"dz{i}", st) if rec_here else None
-            elif r.dw == "fused_stem":
-                # one pass over (dL/dz_1, y_0): BatchNorm-backward sums of the stem + the depthwise weight gradient;
-                # the stem weight gradient below rebuilds dL/d(stem activation) from dL/dz_1 on the fly
-                vp = pl.bn_y[0]
-                self._k("dw_bwd1", "msl_dwconv_s2_bwd_bnreduce_bww", ptr(pl.g_z[1]), ptr(feats[1].conv1.weight), ptr(pl.y[0]),
-                        ptr(vp[0]), ptr(vp[1]), ptr(vp[2]), ptr(vp[3]), ptr(pl.partials), ptr(pl.partials_wf), ptr(pl.w1_taps_t),
-                        N, 32, pd, ph, pw, st)
-            elif r.dw == "s2_bww":
-                # big stride-2 producer layer: bwd-data, the BatchNorm-backward sums of y_{i-1} AND this block's depthwise
-                # weight gradient in one pass over (dL/dz_i, y_{i-1}) - the weight-gradient launch on the side stream (the same
-                # 38 MB read again, 35 us beside the chain at block 2) disappears
-                vp = pl.bn_y[i - 1]
-                self._k(f"dw_bwd{i}", "msl_dwconv_s2_bwd_data_bnreduce_bww", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight),
-                        ptr(pl.g_y[i - 1]), ptr(pl.y[i - 1]), ptr(vp[0]), ptr(vp[1]), ptr(vp[2]), ptr(vp[3]), ptr(pl.partials),
-                        ptr(r.dw_part[0]), N, sp["cin"], pd, ph, pw, accumulate, st)
-            elif r.dw == "bnreduce":
-                # big producer layer: emit the BatchNorm-backward partials of y_{i-1} while its gradient is in registers
-                vp = pl.bn_y[i - 1]
-                self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data_bnreduce", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight),
-                        ptr(pl.g_y[i - 1]), ptr(pl.y[i - 1]), ptr(vp[0]), ptr(vp[1]), ptr(vp[2]), ptr(vp[3]), ptr(pl.partials),
-                        N, sp["cin"], pd, ph, pw, s, accumulate, st)
             else:
-                self._k(f"dw_bwd{i}", "msl_dwconv_bwd_data", ptr(pl.g_z[i]), ptr(feats[i].conv1.weight), ptr(pl.g_y[i - 1]),
-                        N, sp["cin"], pd, ph, pw, s, accumulate, st)
-            def wgrads(ev_dz, i=i, sp=sp, S=S, pd=pd, ph=ph, pw=pw, s=s, name=name, r=r, idle_sink=idle_sink, pw_fused=pw_fused):
+                self._dw_backward(pl, i, accumulate, st)
+
+            def wgrads(ev_dz, i=i, idle_sink=idle_sink, pw_fused=pw_fused):
                 # the heads stream is idle once the head gradients are done: odd blocks go there, even ones to the wgrad stream
                 sX = (stH if i % 2 else stW) if ms else st
                 if ms and not idle_sink:  # the pointwise gradient needs dL/dy_i, the depthwise one dL/dz_i (final later)
                     self._wait(sX, ev_dz)
-                # partial sums only: slabs / fp64 partials stay in this layer's own buffers until Engine._grad_reduce
-                out = r.pw_part[0] if r.pw_part is not None else gv[name + ".conv2.weight"]
                 if i in tail and not pw_fused:  # (pw_fused: its slabs came with the fused pointwise backward)
-                    tail_args.append((ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]), ptr(pl.bn_z[i][1]), ptr(out), sp["cin"],
-                                      sp["cout"], S))
+                    tail_args.append(self._pw_wgrad_row(pl, i))
                     if i == tail[-1]:  # the shallowest: every dL/dy of the group is final (same chain, earlier)
                         self._pw_bww_batch(pl, tail_args, N, sX)
                 elif not pw_fused:
-                    self._k(f"pw_bww{i}", "msl_pwconv_bwd_weight_slabs", ptr(pl.g_y[i]), ptr(pl.z[i]), ptr(pl.bn_z[i][0]),
-                            ptr(pl.bn_z[i][1]), ptr(out), N, sp["cin"], sp["cout"], S, sX)
-                if r.dw in DW_BWW:  # (else its partials came with the depthwise backward pass: r.dw_part / the link wrote dW)
-                    self._k(f"dw_bww{i}", "msl_dwconv_bwd_weight", ptr(pl.g_z[i]), ptr(pl.y[i - 1]), ptr(pl.bn_y[i - 1][0]),
-                            ptr(pl.bn_y[i - 1][1]), None, ptr(pl.dw_part[i]), N, sp["cin"], pd, ph, pw, s, sX)
+                    self._pw_wgrad(pl, i, sX)
+                self._dw_wgrad(pl, i, sX)
 
             # issue what earlier layers left for the side streams (the head gradients the chain waits for and the weight
             # gradients, which nothing in the step waits for: one layer late), then queue this layer's
@@ -1344,34 +1364,12 @@ class Engine:
                     fn(e)
                 sinks = []
             report(i)
-        # stem
-        od, oh, ow = pl.dims[0]
-        S0 = od * oh * ow
-        D, H, W = pl.in_dims
-        r = pl.routes[0]
-        if r.bn == "bn":  # ("link", tiny inputs: block 1's channel link has already applied the stem's BatchNorm backward)
-            # "bnapply" / "fused": the reduce came with the depthwise bwd-data above, the apply is part of the weight gradient
-            self._bn_bwd(pl.g_y[0], pl.y[0], pl.bn_y[0], "base.features.0.1", N * S0, N, specs[0]["cout"], S0, pl, st,
-                         pre_np=r.y_np, apply=r.wgrad == "plain", coef=r.wgrad == "fused")
-        if r.wgrad == "fused":
-            self._k("stem_bww", "msl_stem_conv_bwd_weight_fused", ptr(pl.g_z[1]), ptr(pl.w1_taps_t), ptr(pl.y[0]),
-                    ptr(pl.bn_y[0]), ptr(pl.saved_input), None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
-        elif r.wgrad == "bnapply":
-            self._k("stem_bww", "msl_stem_conv_bwd_weight_bnapply", ptr(pl.g_y[0]), ptr(pl.y[0]), ptr(pl.bn_y[0]),
-                    ptr(pl.saved_input), None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
-        else:
-            self._k("stem_bww", "msl_stem_conv_bwd_weight", ptr(pl.g_y[0]), ptr(pl.saved_input),
-                    None, ptr(pl.ws_stem), N, specs[0]["cin"], D, H, W, *specs[0]["stride"], st)
+        self._stem_backward(pl, st)
         for fn in pending:
             fn()
         for fn, e in sinks:
             fn(e)
-        if ms:  # every gradient is complete once the side streams have been joined
-            self._fork(pl, "bwd_join_w", stW, st)
-            self._fork(pl, "bwd_join_h", stH, st)
-        if not groups:  # single process: ONE reduction launch for every layer's partial sums, right in front of the optimiser
-            self._grad_reduce(pl, "all", None, st)
-        report(0, join_heads=False)
+        self._backward_close(pl, groups, report, st, stH, stW)
 
     def _bucket_groups(self, reducer):
         """stage -> set of parameter names whose gradient bucket completes at that stage (GradBucketReducer layout)."""

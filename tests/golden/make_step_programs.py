@@ -1,8 +1,10 @@
 """Mint ``step_programs.json``: the launch program one ``FusedTrainer`` step records per input shape, storage type and
 engine options, and the one a bare eval-mode forward pass records (``EVAL``).  The first twelve step cases were taken at the
 commit BEFORE the backward passes read their kernel routes from ``Plan.routes``; the cases with fold options and the eval
-cases at the commit BEFORE the forward passes read their BatchNorm folds from ``Plan.folds`` (so the file pins which entry
-point the inline decisions of the four passes chose, on which stream, in which order and with which arguments):
+cases at the commit BEFORE the forward passes read their BatchNorm folds from ``Plan.folds``; the one-stream, ``-unbatched``,
+``-tailpw`` and 136 x 128 x 128 cases at the commit BEFORE the passes issued their launches through the emitters of
+``Engine`` (so the file pins which entry point the inline code of the four passes chose, on which stream, in which order
+and with which arguments):
 
     python -m tests.golden.make_step_programs            # writes the file (needs the GPU)
     python -m tests.golden.make_step_programs --dump     # prints every normalised program instead (to diff two commits)
@@ -18,10 +20,15 @@ the same cases and compare.
 
 When minting, every backward route the engine can take must show among the cases of each storage type that has it
 (``ROUTES``), and so must both forms of every forward launch that can fold a BatchNorm (fp32: the folding form and the one
-that reads the vectors of an ``msl_bn_finalize`` on the chain).  Two fp32 routes are out of reach of these cases: ``msl_pwconv_bwd_fused`` and
-``msl_dwconv_s2_bwd_data_bnreduce_bww`` both need a block i >= 2 whose input has more than 65536 positions per channel over
-the batch; at 128^3 x 2, the largest case allowed here, block 2's input has exactly 65536 (128^3 x 4 is the smallest cube
-that takes them).
+that reads the vectors of an ``msl_bn_finalize`` on the chain).  Two fp32 routes, ``msl_pwconv_bwd_fused`` and
+``msl_dwconv_s2_bwd_data_bnreduce_bww``, need a block i >= 2 whose input has more than 65536 positions per channel over the
+batch; at 128^3 x 2 block 2's input has exactly 65536, so one fp32-only case (``F32_ONLY``) has one axis of 136: 69632.
+
+The cases with ``multi_stream=False`` pin the one-stream branches of the four passes and, as the trainer's one-launch loss
+needs the side streams, the per-scale ``msl_head_grad_pack``.  The ``-unbatched`` ones set ``batch_tail_pw`` and
+``batch_head_gpack`` off: that is the default program (the tail is unbatched by default, and on three streams the loss
+kernel writes the head-gradient images itself, so no pack runs either way), pinned under its own name so that a change of
+either default shows.  The fp32 ``-tailpw`` case pins the other side, the tail's pointwise weight gradients in one launch.
 """
 import argparse
 import hashlib
@@ -48,7 +55,12 @@ SHAPES = {"64x2": (2, (64, 64, 64), 1, FUSE),
           "64x2-foldall": (2, (64, 64, 64), 1, dict(FUSE, fold_bn=True)),  # fp32 folds every BatchNorm, bf16 does not consult it
           # fold_np_max does not reach the BatchNorm of a depthwise output (FOLD_NP_MAX_PW = 64 partials, never more at batch
           # 2): 33 tiny volumes leave block 1's with 66, so its pointwise layer reads the vectors of a finalize on the chain
-          "tiny-x33": (33, (TINY,) * 3, 1, FUSE)}
+          "tiny-x33": (33, (TINY,) * 3, 1, FUSE),
+          "64x2-1stream": (2, (64, 64, 64), 1, dict(FUSE, multi_stream=False)),
+          "64x2-unbatched": (2, (64, 64, 64), 1, dict(FUSE, batch_tail_pw=False, batch_head_gpack=False))}
+# the same for fp32 storage only
+F32_ONLY = {"136x128x128x2": (2, (136, 128, 128), 1, FUSE),  # block 2: msl_pwconv_bwd_fused, msl_dwconv_s2_bwd_data_bnreduce_bww
+            "64x2-tailpw": (2, (64, 64, 64), 1, dict(FUSE, batch_tail_pw=True))}  # (the bf16 pass does not consult it)
 # a bare eval-mode forward pass (record_eval): name -> (batch, input size, input channels, options, storage type)
 EVAL = {"eval-64x2-f32": (2, (64, 64, 64), 1, {}, "f32"),
         "eval-64x2-bf16": (2, (64, 64, 64), 1, {"bf16_heads": "f32"}, "bf16"),
@@ -75,9 +87,10 @@ ROUTES = {
     "s2_patch": (("bf16",), _entry("msl_dwconv_bwd_data_s2_patch_bf16")),
     "dw_bwd1 fused": (("f32", "bf16"), lambda p, sfx: (f"msl_dwconv_s2_bwd_bnreduce_bww{sfx}", "dw_bwd1") in p),
     "plain": (("f32", "bf16"), lambda p, sfx: any(e == f"msl_dwconv_bwd_data{sfx}" for e, _ in p)),
-    # fp32 routes no case reaches (module docstring): minting asserts that too, so that the docstring stays true
-    "pw_bwd_fused": ((), _entry("msl_pwconv_bwd_fused")),
-    "msl_dwconv_s2_bwd_data_bnreduce_bww": ((), _entry("msl_dwconv_s2_bwd_data_bnreduce_bww")),
+    "pw_bwd_fused": (("f32",), _entry("msl_pwconv_bwd_fused")),
+    "msl_dwconv_s2_bwd_data_bnreduce_bww": (("f32",), _entry("msl_dwconv_s2_bwd_data_bnreduce_bww")),
+    "pw_bww_tail": (("f32",), _entry("msl_pwconv_bwd_weight_slabs_batch")),
+    "msl_head_grad_pack": (("f32", "bf16"), _entry("msl_head_grad_pack")),
 }
 # the forward pass: a BatchNorm folded into its consumer from the partials, or finalized on the chain and read as vectors
 ROUTES.update({name: (("f32",), _entry(name)) for name in (
@@ -87,7 +100,8 @@ ROUTES.update({name: (("f32",), _entry(name)) for name in (
 
 def cases():
     """name -> (batch, input size, input channels, options, dtype)."""
-    return {f"{tag}-{dtype}": shape + (dtype,) for tag, shape in SHAPES.items() for dtype in ("f32", "bf16")}
+    both = {f"{tag}-{dtype}": shape + (dtype,) for tag, shape in SHAPES.items() for dtype in ("f32", "bf16")}
+    return dict(both, **{f"{tag}-f32": shape + ("f32",) for tag, shape in F32_ONLY.items()})
 
 
 def eval_cases():
@@ -182,15 +196,13 @@ def write(progs, out):
 
 
 def check_routes(progs):
-    """Every route of ROUTES shows in a case of each storage type listed for it (and in none where none is listed)."""
+    """Every route of ROUTES shows in a case of each storage type listed for it."""
     pairs = {name: {(e[1], e[2]) for e in prog if e[0] != "hook"} for name, prog in progs.items()}
     for route, (dtypes, found) in ROUTES.items():
         for dtype in dtypes:
             hit = [name for name, p in pairs.items() if name.endswith("-" + dtype) and found(p, "_bf16" if dtype == "bf16" else "")]
             print(f"route {route!r} ({dtype}): {hit}")
             assert hit, f"no {dtype} case takes the route {route!r}"
-        if not dtypes:
-            assert not any(found(p, "") for p in pairs.values()), f"{route!r} is reached after all: list it for fp32"
 
 
 def main():

@@ -161,3 +161,30 @@ def test_stop_event_fusion_of_launch_programs():
         _lib.STOP_EVENT_FORKS = saved
     plain = list(prog)  # a program without launch counts (not from the recorder): never fused
     assert not any(e[0] is not None and e[0].__name__ == "msl_arm_stop_event" for e in _lib._fuse_stop_events(plain, ()))
+
+
+def test_engine_op_table_names_the_library_entry_points():
+    """``engine.OPS``, the one place the layer kernels of the four passes are named: every name is an entry point of
+    ``_lib._SIGNATURES`` (a plain dict: no library is opened); where both storage types have an op the two entry points take
+    the same number of arguments, except for the fp32 extras the emitters spell out (``engine.F32_EXTRA_ARGS``); and an op
+    one storage type lacks is one of the known one-type forms."""
+    from mslesions3d_amd import _lib
+    from mslesions3d_amd.engine import F32_EXTRA_ARGS, OPS
+    # no bf16 form: the one-pass pointwise backward, the two big-producer depthwise forms and the stem weight gradient
+    # without the BatchNorm backward on load (plan_routes gives a bf16 plan "bnapply" or "fused"); no fp32 form: s2_patch
+    one_type = {"pw_bwd_fused": "f32", "dw_bwd:s2_bww": "f32", "dw_bwd:bnreduce": "f32", "stem_bww:plain": "f32",
+                "dw_bwd:s2_patch": "bf16"}
+    assert set(F32_EXTRA_ARGS) <= set(OPS)
+    names = [n for pair in OPS.values() for n in pair if n is not None]
+    assert len(names) == len(set(names)), "an entry point is listed twice"
+    for op, (f32, bf16) in OPS.items():
+        for name in (f32, bf16):
+            assert name is None or name in _lib._SIGNATURES, f"{op}: {name} is not an entry point"
+        if f32 is None or bf16 is None:
+            assert one_type.get(op) == ("f32" if bf16 is None else "bf16"), f"{op} misses a storage type"
+            assert op not in F32_EXTRA_ARGS
+        else:
+            assert op not in one_type
+            assert bf16.endswith("_bf16") or "_bf16_" in bf16, (op, bf16)
+            n32, n16 = (len(_lib._SIGNATURES[n][1]) for n in (f32, bf16))
+            assert n32 - n16 == F32_EXTRA_ARGS.get(op, 0), f"{op}: {f32} takes {n32} arguments, {bf16} takes {n16}"

@@ -385,7 +385,11 @@ int msl_multibox_loss_var(const float* locs, const float* scores, const long lon
  *   probs (N,K1,P) f32; boxes (N,P,6) f32; sorted_idx (N,K1,cap) i32; ncand (N*K1) i32;
  *   mask (N,K1,cap,Wn) u64; keep_bits (N,K1,Wn) u64; nkept (N*K1) i32; tmp_scores (N,K1*cap) f32; tmp_ref same i32;
  *   select_ws: msl_detect_select_ws_ints(N,P,ncls) i32 (score histogram + shortlist of the candidates that can reach the
- *   best cap: the stable order is then found among ~cap candidates instead of all P)
+ *   best cap: the stable order is then found among ~cap candidates instead of all P); per (image, foreground class)
+ *   2048 + 4 + P ints: [histogram 2048 | threshold bin | shortlist length | pad 2 | shortlist P]
+ * The scratch needs no initialisation: every call sets what it reads (tests/test_gpu_detect.py hands it over poisoned).
+ * After a call: ncand = candidates per (image, class); sorted_idx[.., :min(ncand, cap)] = their stable descending order;
+ * keep_bits = bit r set if rank r is kept, words beyond the last block of 64 zero; nkept = their popcount.
  * Outputs: out_boxes (N,top_k,6), out_scores (N,top_k), out_labels / out_prior (N,top_k) i64, out_count (N) i32. */
 size_t msl_detect_select_ws_ints(int N, int P, int ncls);
 int msl_detect_objects(const float* locs, const float* scores, const float* priors_c, int N, int P, int ncls,

@@ -31,9 +31,12 @@ def nms_keep(boxes_sorted, max_overlap):
     return ~suppress
 
 
-def detect_objects(pred_locs, pred_scores, priors_c, min_score, max_overlap, top_k, return_prior_index=False):
+def detect_objects(pred_locs, pred_scores, priors_c, min_score, max_overlap, top_k, return_prior_index=False, trace=None):
     """-> lists (len N) of boxes (k,6) f32 corner-form fractional, labels (k,) i64, scores (k,) f32
-    [+ prior index (k,) i64, -1 for the placeholder].  ssd3d.py:360-460."""
+    [+ prior index (k,) i64, -1 for the placeholder].  ssd3d.py:360-460.
+
+    ``trace``: a dict that receives, per (image, class), what the loop computes on the way: ``trace[(i, c)] = (number of
+    candidates, ranked candidates after the 10 * top_k cut (prior indices, i64), keep mask over them (bool))``."""
     n, p, n_classes = pred_scores.shape
     assert p == priors_c.size(0) == pred_locs.size(1)  # ssd3d.py:370
     probs = torch.softmax(pred_scores, dim=2)  # ssd3d.py:363
@@ -45,10 +48,15 @@ def detect_objects(pred_locs, pred_scores, priors_c, min_score, max_overlap, top
             cs = probs[i, :, c]
             cand = torch.nonzero(cs > min_score).view(-1)  # strict >   ssd3d.py:388
             if cand.numel() == 0:
+                if trace is not None:
+                    trace[(i, c)] = (0, cand, torch.zeros(0, dtype=torch.bool))
                 continue
+            n_cand = cand.numel()
             order = torch.from_numpy(stable_desc_order(cs[cand].numpy()))  # ssd3d.py:397
             cand = cand[order][: min(10 * top_k, cand.numel())]  # ssd3d.py:401-403
             keep = torch.from_numpy(nms_keep(decoded[cand], max_overlap))
+            if trace is not None:
+                trace[(i, c)] = (n_cand, cand, keep)
             kept = cand[keep]
             ib.append(decoded[kept])
             il.append(torch.full((kept.numel(),), c, dtype=torch.long))

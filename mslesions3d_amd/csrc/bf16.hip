@@ -7,11 +7,12 @@
 //   head kernel (heads.hip) reads 8 consecutive channels of a voxel with one 16-byte load.
 // The statistics of a layer are taken from the fp32 accumulators BEFORE the rounding to bf16.
 #include "common.hpp"
+#include "dwroute.hpp"
 #include <algorithm>
 
-// dwconv.hip: the register-marching wave kernels on bf16 storage (square power-of-two planes)
-extern "C" int msl_dwconv_wave_num_partials(int N, int C, int D, int H, int W, int stride);
-extern "C" int msl_dwconv_fwd_eval_rows_ok(int N, int C, int D, int H, int W, int stride);
+using namespace msl::dw;
+
+// dwconv.hip / dwconv_bwd.hip: the wave, rows, small-map and stride-2 patch kernels on bf16 storage
 extern "C" int msl_dwconv_fwd_wave_bf16(const void* x, const float* in_scale, const float* in_shift, const float* w, void* y,
                                         double* partials, int N, int C, int D, int H, int W, int stride, int flip,
                                         int accumulate, void* stream);
@@ -36,7 +37,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Workgroup = (n, c) x an output tile of TD x TH x TW voxels.  The activated input tile (with halo, zero outside the
 // volume - the padding value AFTER the activation) is staged in LDS as fp32; a thread produces TD outputs of one
 // (h, w) column.  256 threads = TH * TW.
-constexpr int DW_TD = 2, DW_TH = 8, DW_TW = 32;
 
 // flip != 0: taps reversed (w[26 - k]) - the stride-1 bwd-data pass; accumulate != 0: y += result (the feature-map
 // gradient already holds the heads' share).
@@ -559,7 +559,6 @@ __global__ __launch_bounds__(256) void pw_bww_bf16_any_kernel(const u16* __restr
 // ---- depthwise, stride-2 bwd-data ------------------------------------------------------------------------------------
 // g_in[i] = sum over taps k with (i + 1 - k) even of w[k] * dy[(i + 1 - k) / 2].  Workgroup = (n, c) x an input tile of
 // 4 x 8 x 64 voxels; the dy tile it touches (3 x 5 x 33) is staged in LDS as fp32.
-constexpr int DB_TD = 4, DB_TH = 8, DB_TW = 64;
 __global__ __launch_bounds__(256) void dw_bwd_data_s2_bf16_kernel(const u16* __restrict__ dy, const float* __restrict__ w,
                                                                   u16* __restrict__ g_in, int C, int D, int H, int W, int OD,
                                                                   int OH, int OW, int tiles_h, int tiles_w, int accumulate) {
@@ -828,40 +827,25 @@ __global__ __launch_bounds__(NT) void bn_relu_bwd_fused_reg_bf16_kernel(const u1
 
 extern "C" {
 
-static bool dw_bf16_use_wave() {  // (the LDS-tiled any-shape kernels take what the wave kernels do not)
-  constexpr int on = 1;
-  return on != 0;
-}
-
 int msl_dwconv_fwd_bf16_num_partials(int N, int C, int D, int H, int W, int stride) {
-  if (dw_bf16_use_wave()) {
-    const int np = msl_dwconv_wave_num_partials(N, C, D, H, W, stride);
-    if (np > 0) return np;
-  }
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  return N * msl::cdiv(OD, DW_TD) * msl::cdiv(OH, DW_TH) * msl::cdiv(OW, DW_TW);
+  return dw_route(DwOp::Fwd, true, N, C, D, H, W, stride, true, false).num_partials;
 }
 
 // x (N,C,D,H,W) bf16 raw + optional input affine -> y (N,C,OD,OH,OW) bf16 raw (+ fp64 stat partials [2][C][NP] or NULL)
 int msl_dwconv_fwd_bf16(const void* x, const float* in_scale, const float* in_shift, const float* w, void* y,
                         double* partials, int N, int C, int D, int H, int W, int stride, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  if (dw_bf16_use_wave() && (msl_dwconv_wave_num_partials(N, C, D, H, W, stride) > 0 ||
-                             (!partials && msl_dwconv_fwd_eval_rows_ok(N, C, D, H, W, stride) == 1)))
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
+  const DwRoute r = dw_route(DwOp::Fwd, true, N, C, D, H, W, stride, partials != nullptr, false);
+  if (r.kind == DwKind::Wave || r.kind == DwKind::RowsEval)
     return msl_dwconv_fwd_wave_bf16(x, in_scale, in_shift, w, y, partials, N, C, D, H, W, stride, 0, 0, stream);
-  if (!partials && D * H * W <= 512 && (D + 2) * (H + 2) * (W + 2) <= 1024)  // eval mode, a map no wave / rows kernel takes
+  if (r.kind == DwKind::SmallEval)  // eval mode, a map no wave / rows kernel takes
     return msl_dwconv_fwd_small_eval_bf16(x, in_scale, in_shift, w, y, N, C, D, H, W, stride, stream);
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  const int tiles_d = msl::cdiv(OD, DW_TD), tiles_h = msl::cdiv(OH, DW_TH), tiles_w = msl::cdiv(OW, DW_TW);
-  const int NP = N * tiles_d * tiles_h * tiles_w;
-  dim3 grid(tiles_d * tiles_h * tiles_w, N * C);
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1)
-    MSL_LAUNCH(dw_fwd_bf16_kernel<1>, grid, dim3(256), 0, st, (const u16*)x, in_scale, in_shift, w, (u16*)y, partials,
-                       C, D, H, W, OD, OH, OW, tiles_h, tiles_w, NP, 0, 0);
-  else
-    MSL_LAUNCH(dw_fwd_bf16_kernel<2>, grid, dim3(256), 0, st, (const u16*)x, in_scale, in_shift, w, (u16*)y, partials,
-                       C, D, H, W, OD, OH, OW, tiles_h, tiles_w, NP, 0, 0);
+  const dim3 grid(r.tiles_d * r.tiles_h * r.tiles_w, N * C);
+  msl::dispatch_int<1, 2>(stride, [&](auto s) {
+    MSL_LAUNCH(dw_fwd_bf16_kernel<decltype(s)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const u16*)x, in_scale, in_shift,
+               w, (u16*)y, partials, C, D, H, W, r.OD, r.OH, r.OW, r.tiles_h, r.tiles_w, r.num_partials, 0, 0);
+    return MSL_OK;
+  });
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -1011,24 +995,20 @@ int msl_pwconv_bwd_weight_slabs_bf16(const void* dy, const void* z, const float*
 // dy (N,C,OD,OH,OW) bf16 -> g_in (N,C,D,H,W) bf16; accumulate != 0 adds into g_in
 int msl_dwconv_bwd_data_bf16(const void* dy, const float* w, void* g_in, int N, int C, int D, int H, int W, int stride,
                              int accumulate, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 1 && dw_bf16_use_wave() && msl_dwconv_wave_num_partials(N, C, D, H, W, 1) > 0)
+  const DwRoute r = dw_route(DwOp::BwdData, true, N, C, D, H, W, stride, false, false);
+  if (r.kind == DwKind::Wave)
     return msl_dwconv_fwd_wave_bf16(dy, nullptr, nullptr, w, g_in, nullptr, N, C, D, H, W, 1, 1, accumulate, stream);
-  if (stride == 2 && dw_bf16_use_wave() && W % 4 == 0)
+  if (r.kind == DwKind::S2Patch)
     return msl_dwconv_bwd_data_s2_patch_bf16(dy, w, g_in, nullptr, nullptr, nullptr, N, C, D, H, W, accumulate, stream);
-  if (stride == 1) {  // the forward kernel with reversed taps
-    const int tiles_d = msl::cdiv(D, DW_TD), tiles_h = msl::cdiv(H, DW_TH), tiles_w = msl::cdiv(W, DW_TW);
-    dim3 grid(tiles_d * tiles_h * tiles_w, N * C);
-    MSL_LAUNCH(dw_fwd_bf16_kernel<1>, grid, dim3(256), 0, st, (const u16*)dy, nullptr, nullptr, w, (u16*)g_in, nullptr, C,
-                       D, H, W, D, H, W, tiles_h, tiles_w, 0, 1, accumulate);
-  } else {
-    const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-    const int tiles_d = msl::cdiv(D, DB_TD), tiles_h = msl::cdiv(H, DB_TH), tiles_w = msl::cdiv(W, DB_TW);
-    dim3 grid(tiles_d * tiles_h * tiles_w, N * C);
-    MSL_LAUNCH(dw_bwd_data_s2_bf16_kernel, grid, dim3(256), 0, st, (const u16*)dy, w, (u16*)g_in, C, D, H, W, OD, OH, OW,
-                       tiles_h, tiles_w, accumulate);
-  }
+  const dim3 grid(r.tiles_d * r.tiles_h * r.tiles_w, N * C);
+  if (r.kind == DwKind::Tiled)  // stride 1: the forward kernel with reversed taps
+    MSL_LAUNCH(dw_fwd_bf16_kernel<1>, grid, dim3(256), 0, st, (const u16*)dy, nullptr, nullptr, w, (u16*)g_in, nullptr, C, D, H,
+               W, D, H, W, r.tiles_h, r.tiles_w, 0, 1, accumulate);
+  else  // TiledS2
+    MSL_LAUNCH(dw_bwd_data_s2_bf16_kernel, grid, dim3(256), 0, st, (const u16*)dy, w, (u16*)g_in, C, D, H, W, r.OD, r.OH, r.OW,
+               r.tiles_h, r.tiles_w, accumulate);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -1036,20 +1016,16 @@ int msl_dwconv_bwd_data_bf16(const void* dy, const float* w, void* g_in, int N, 
 // dz (N,C,OD,OH,OW), x (N,C,D,H,W) bf16 (+ input affine) -> fp64 partials [C*27][NP], NP = msl_dwconv_fwd_bf16_num_partials
 int msl_dwconv_bwd_weight_bf16(const void* dz, const void* x, const float* in_scale, const float* in_shift, double* partials,
                                int N, int C, int D, int H, int W, int stride, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2) || !partials) return MSL_ERR_ARG;
-  if (dw_bf16_use_wave() && msl_dwconv_wave_num_partials(N, C, D, H, W, stride) > 0)
+  if (!dw_args_ok(N, C, D, H, W, stride) || !partials) return MSL_ERR_ARG;
+  const DwRoute r = dw_route(DwOp::BwdWeight, true, N, C, D, H, W, stride, false, false);
+  if (r.kind == DwKind::Wave)
     return msl_dwconv_bwd_weight_wave_bf16(dz, x, in_scale, in_shift, partials, N, C, D, H, W, stride, stream);
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  const int tiles_d = msl::cdiv(OD, DW_TD), tiles_h = msl::cdiv(OH, DW_TH), tiles_w = msl::cdiv(OW, DW_TW);
-  const int NP = N * tiles_d * tiles_h * tiles_w;
-  dim3 grid(tiles_d * tiles_h * tiles_w, N * C);
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1)
-    MSL_LAUNCH(dw_bww_bf16_kernel<1>, grid, dim3(256), 0, st, (const u16*)dz, (const u16*)x, in_scale, in_shift, partials,
-                       C, D, H, W, OD, OH, OW, tiles_h, tiles_w, NP);
-  else
-    MSL_LAUNCH(dw_bww_bf16_kernel<2>, grid, dim3(256), 0, st, (const u16*)dz, (const u16*)x, in_scale, in_shift, partials,
-                       C, D, H, W, OD, OH, OW, tiles_h, tiles_w, NP);
+  const dim3 grid(r.tiles_d * r.tiles_h * r.tiles_w, N * C);
+  msl::dispatch_int<1, 2>(stride, [&](auto s) {
+    MSL_LAUNCH(dw_bww_bf16_kernel<decltype(s)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const u16*)dz, (const u16*)x,
+               in_scale, in_shift, partials, C, D, H, W, r.OD, r.OH, r.OW, r.tiles_h, r.tiles_w, r.num_partials);
+    return MSL_OK;
+  });
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

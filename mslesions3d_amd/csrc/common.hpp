@@ -68,6 +68,20 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned sme
 }  // namespace msl
 #define MSL_LAUNCH(kernel, ...) msl::launch(kernel, __VA_ARGS__)
 
+// ---- runtime value -> template argument ----------------------------------------------------------------------------
+// dispatch_int<A, B, ...>(v, f) calls f(std::integral_constant<int, V>{}) for the listed V equal to v and returns what f
+// returns (an MSL_* code); MSL_ERR_ARG if v is not listed.  A launcher writes its kernel's argument list once, inside f, and
+// only the listed values are ever instantiated.
+#include <type_traits>
+namespace msl {
+template <int... Vs, typename F>
+inline int dispatch_int(int v, F&& f) {
+  int rc = MSL_ERR_ARG;
+  (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return rc;
+}
+}  // namespace msl
+
 namespace msl {
 
 // ---- cross-lane sums on the VALU (DPP) -------------------------------------------------------------------------

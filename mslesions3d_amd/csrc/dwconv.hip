@@ -19,8 +19,11 @@
 // Workgroup ids are remapped so that the slabs of one volume (which share halo planes) land on the same
 // XCD back to back (per-XCD L2).
 #include "common.hpp"
+#include "dwroute.hpp"
 #include <algorithm>
 #include <cstdlib>
+
+using namespace msl::dw;
 
 namespace {
 
@@ -1372,7 +1375,6 @@ __global__ __launch_bounds__(256) void dw_fwd_naive_kernel(
 // computes outputs from there - 27 LDS reads instead of 27 dependent global loads per output, a quarter of the launch's
 // workgroups.  Taps in the naive kernel's order (kd, kh, kw); a padded tap adds w * 0 where the naive kernel skips it:
 // the same value bit for bit (an fmaf with a zero product leaves a non-negative-zero accumulator unchanged).
-constexpr int DW_SMALL_VOX = 512, DW_SMALL_IMG = 1024;
 template <typename T>
 __global__ __launch_bounds__(256) void dw_small_eval_kernel(const T* __restrict__ x, const float* __restrict__ in_scale,
                                                             const float* __restrict__ in_shift, const float* __restrict__ w,
@@ -1414,7 +1416,6 @@ __global__ __launch_bounds__(256) void dw_small_eval_kernel(const T* __restrict_
   }
 }
 
-constexpr int STATS_CHUNK = 4096;
 __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restrict__ y,
                                                             double* __restrict__ partials, int C, int S,
                                                             int chunks) {
@@ -1438,259 +1439,6 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
   }
 }
 
-struct DwPlan {
-  int variant;  // 0 naive, 1 stream, 2 resident
-  int G, SLAB, nslabs, ipt, lpt;
-  size_t lds_bytes;
-  int num_partials;
-};
-
-inline int pow2_floor(int v) {
-  int p = 1;
-  while (p * 2 <= v) p *= 2;
-  return p;
-}
-
-DwPlan make_plan(int N, int C, int D, int H, int W, int stride) {
-  DwPlan pl{};
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  const bool fast = (W % 4 == 0) && (OW % 4 == 0) && (stride == 1 || (H % 2 == 0 && W % 2 == 0));
-  const int S = OD * OH * OW;
-  if (!fast) {
-    pl.variant = 0;
-    pl.num_partials = N * msl::cdiv(S, STATS_CHUNK);
-    return pl;
-  }
-  const int RS = stride == 1 ? W + 8 : ((OW + 3) & ~3) + ((OW + 4) & ~3);
-  const int PS = (H + 2) * RS;
-  const int OWV = OW / 4, Lp = OH * OWV;
-  constexpr int stream_min_hw = 1024;
-  if (H * W >= stream_min_hw) {  // stream
-    int G = 1;
-    int ipt = msl::cdiv(G * Lp, 256);
-    int lpt = msl::cdiv(G * H * (W / 4), 256);
-    size_t lds = (size_t)G * PS * 4;
-    lds = lds > (size_t)2 * G * Lp * 4 ? lds : (size_t)2 * G * Lp * 4;
-    if (ipt > 4 || lpt > 12 || lds > 160 * 1024) {
-      pl.variant = 0;
-      pl.num_partials = N * msl::cdiv(S, STATS_CHUNK);
-      return pl;
-    }
-    pl.variant = 1;
-    pl.G = G;
-    pl.ipt = ipt <= 1 ? 1 : 4;
-    pl.lpt = lpt <= 4 ? 4 : 12;
-    const int nvol = N * (C / G);
-    int slabs = std::max(1, std::min(OD, 1024 / std::max(1, nvol)));
-    int SLAB = msl::cdiv(OD, slabs);
-    if (SLAB < 4) SLAB = std::min(4, OD);
-    pl.SLAB = SLAB;
-    pl.nslabs = msl::cdiv(OD, SLAB);
-    pl.lds_bytes = lds;
-    pl.num_partials = N * pl.nslabs;
-    return pl;
-  }
-  // resident: choose SLAB (power of two dividing work) and G so that ~256..1024 items and <= 60 KB of LDS
-  int SLAB = OD;
-  const int nvol1 = N * C;
-  while (SLAB > 2 && (nvol1 * msl::cdiv(OD, SLAB) < 1024 || (size_t)(stride * SLAB + 2) * PS * 4 > 40 * 1024) &&
-         SLAB % 2 == 0 && SLAB / 2 >= 2)
-    SLAB /= 2;
-  int NPL = stride * SLAB + (stride == 2 ? 1 : 2);
-  size_t per_ch = (size_t)NPL * PS * 4 + (size_t)2 * SLAB * Lp * 4;
-  if (per_ch > 150 * 1024) {  // + 7.5 KB of static LDS
-    pl.variant = 0;
-    pl.num_partials = N * msl::cdiv(S, STATS_CHUNK);
-    return pl;
-  }
-  int G = std::max(1, 256 / std::max(1, SLAB * Lp));
-  G = std::min(pow2_floor(G), 64);
-  while (G > 1 && (C % G != 0 || per_ch * G > 60 * 1024)) G /= 2;
-  pl.variant = 2;
-  pl.G = G;
-  pl.SLAB = SLAB;
-  pl.nslabs = msl::cdiv(OD, SLAB);
-  pl.lds_bytes = per_ch * G;
-  pl.num_partials = N * pl.nslabs;
-  return pl;
-}
-
-// Register-marching wave kernel (dw_s1_wave_kernel): stride 1, square planes of 4 / 8 / 16.  Two depth slabs per
-// cube of the network's tail (NP = 2N partials per channel, as the resident plan had).
-struct WavePlan {
-  bool ok;
-  int logw4, logh, cpw, SL, nslabs, wpp;  // wpp: waves per plane (stride 2, planes of >= 64 cells)
-};
-
-WavePlan make_wave_plan(int N, int C, int D, int H, int W, int stride) {
-  constexpr int enabled = 3;  // bit 0: stride 1, bit 1: stride 2
-  WavePlan wp{};
-  if (!enabled || H != W) return wp;
-  if (stride == 2) {
-    // (planes up to 64^2: with 32 block 1's 64^2 planes go back to the streamed kernel - slower, tools/ab_dw_wave.sh in round 1)
-    constexpr int maxw = 64;
-    if ((W != 8 && W != 16 && W != 32 && W != 64) || W > maxw || !(enabled & 2)) return wp;
-    wp.logw4 = W == 8 ? 1 : W == 16 ? 2 : W == 32 ? 3 : 4;
-    wp.logh = wp.logw4 + 1;  // log2(OH)
-    const int cells = (H / 2) * (W / 4), OD = (D - 1) / 2 + 1;
-    wp.cpw = cells >= 64 ? 1 : 64 / cells;
-    wp.wpp = cells >= 64 ? cells / 64 : 1;
-    if (C % wp.cpw != 0) return wp;
-    wp.SL = OD >= 8 ? 4 : OD >= 4 ? 2 : 1;
-    constexpr int sl2 = 0;  // tuning knob: cap
-    if (sl2 > 0) wp.SL = std::min(wp.SL, sl2 >= 4 ? 4 : sl2 >= 2 ? 2 : 1);
-    wp.nslabs = msl::cdiv(OD, wp.SL);
-    if ((long long)N * (C / wp.cpw) * wp.nslabs * wp.wpp > (1ll << 30)) return wp;
-    wp.ok = true;
-    return wp;
-  }
-  wp.wpp = 1;
-  if (!(enabled & 1) || stride != 1 || (W != 4 && W != 8 && W != 16)) return wp;
-  wp.logw4 = W == 4 ? 0 : W == 8 ? 1 : 2;
-  wp.logh = wp.logw4 + 2;
-  wp.cpw = 64 / (H * W / 4);
-  if (C % wp.cpw != 0) return wp;
-  wp.SL = D >= 16 ? 8 : D >= 8 ? 4 : D >= 4 ? 2 : 1;
-  constexpr int sl1 = 0;  // tuning knob: cap
-  if (sl1 > 0) wp.SL = std::min(wp.SL, sl1 >= 8 ? 8 : sl1 >= 4 ? 4 : sl1 >= 2 ? 2 : 1);
-  wp.nslabs = msl::cdiv(D, wp.SL);
-  if ((long long)N * (C / wp.cpw) * wp.nslabs > (1ll << 30)) return wp;
-  wp.ok = true;
-  return wp;
-}
-
-template <typename T>
-void launch_wave(const WavePlan& wp, const T* x, const float* in_scale, const float* in_shift, const float* w,
-                 T* y, double* partials, int N, int C, int D, int flip, int accumulate, const msl::BnFold& fold,
-                 hipStream_t st) {
-  const int waves = N * (C / wp.cpw) * wp.nslabs;
-  const dim3 grid(msl::cdiv(waves, 4)), block(256);
-#define MSL_DW_WAVE_SL(LW_, LH_)                                                                                  \
-  switch (wp.SL) {                                                                                                \
-    case 8: MSL_LAUNCH((dw_s1_wave_kernel<LW_, LH_, 8, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, \
-                               partials, C, D, wp.nslabs, N, flip, accumulate, fold); break;                      \
-    case 4: MSL_LAUNCH((dw_s1_wave_kernel<LW_, LH_, 4, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, \
-                               partials, C, D, wp.nslabs, N, flip, accumulate, fold); break;                      \
-    case 2: MSL_LAUNCH((dw_s1_wave_kernel<LW_, LH_, 2, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, \
-                               partials, C, D, wp.nslabs, N, flip, accumulate, fold); break;                      \
-    default: MSL_LAUNCH((dw_s1_wave_kernel<LW_, LH_, 1, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, \
-                                partials, C, D, wp.nslabs, N, flip, accumulate, fold); break;                     \
-  }
-  if (wp.logw4 == 0) { MSL_DW_WAVE_SL(0, 2) }
-  else if (wp.logw4 == 1) { MSL_DW_WAVE_SL(1, 3) }
-  else { MSL_DW_WAVE_SL(2, 4) }
-#undef MSL_DW_WAVE_SL
-}
-
-template <typename T>
-void launch_wave_s2(const WavePlan& wp, const T* x, const float* in_scale, const float* in_shift, const float* w,
-                    T* y, double* partials, int N, int C, int D, const msl::BnFold& fold, hipStream_t st) {
-  const int waves = N * (C / wp.cpw) * wp.nslabs * wp.wpp, OD = (D - 1) / 2 + 1;
-  const int wpg = wp.wpp > 1 ? std::min(wp.wpp, 4) : 4;
-  const dim3 grid(msl::cdiv(waves, wpg)), block(64 * wpg);
-#define MSL_DW_WAVE2_SL(LW_, LH_)                                                                                  \
-  switch (wp.SL) {                                                                                                 \
-    case 4: MSL_LAUNCH((dw_s2_wave_kernel<LW_, LH_, 4, T>), grid, block, 0, st, x, in_scale, in_shift, w, y,  \
-                               partials, C, D, OD, wp.nslabs, N, fold); break;                                     \
-    case 2: MSL_LAUNCH((dw_s2_wave_kernel<LW_, LH_, 2, T>), grid, block, 0, st, x, in_scale, in_shift, w, y,  \
-                               partials, C, D, OD, wp.nslabs, N, fold); break;                                     \
-    default: MSL_LAUNCH((dw_s2_wave_kernel<LW_, LH_, 1, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, \
-                                partials, C, D, OD, wp.nslabs, N, fold); break;                                    \
-  }
-  if (wp.logw4 == 1) { MSL_DW_WAVE2_SL(1, 2) }
-  else if (wp.logw4 == 2) { MSL_DW_WAVE2_SL(2, 3) }
-  else if (wp.logw4 == 3) { MSL_DW_WAVE2_SL(3, 4) }
-  else { MSL_DW_WAVE2_SL(4, 5) }
-#undef MSL_DW_WAVE2_SL
-}
-
-// eval-mode forward on dw_s2_rows_eval_kernel / dw_s1_rows_eval_kernel: no statistics, planes the power-of-two wave kernels do not take
-// (the LDS kernels remain for the shapes these do not take)
-bool rows_eval_ok(int N, int C, int D, int H, int W, int stride) {
-  constexpr int on = 1;
-  if (!on || W % 4 != 0 || W < 8 || W > 256 || D < 2) return false;
-  if (stride == 2 && H % 2 != 0) return false;
-  if (make_wave_plan(N, C, D, H, W, stride).ok) return false;
-  const int OD = (D - 1) / stride + 1, SL = OD >= 8 ? 4 : OD >= 4 ? 2 : 1, RPW = 64 / (W / 4);
-  return (long long)N * C * msl::cdiv(OD, SL) * msl::cdiv(stride == 2 ? H / 2 : H, RPW) < (1ll << 30);
-}
-
-template <typename T>
-void launch_rows_eval(const T* x, const float* in_scale, const float* in_shift, const float* w, T* y, int N, int C, int D,
-                      int H, int W, int stride, hipStream_t st) {
-  if (stride == 1) {
-    const int SL = D >= 8 ? 4 : D >= 4 ? 2 : 1, nslabs = msl::cdiv(D, SL);
-    const int RPW = 64 / (W / 4), RG = msl::cdiv(H, RPW);
-    const int waves = N * C * nslabs * RG;
-    const dim3 grid(msl::cdiv(waves, 4)), block(256);
-    switch (SL) {
-      case 4: MSL_LAUNCH((dw_s1_rows_eval_kernel<4, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W,
-                                 nslabs, RPW, RG, waves); break;
-      case 2: MSL_LAUNCH((dw_s1_rows_eval_kernel<2, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W,
-                                 nslabs, RPW, RG, waves); break;
-      default: MSL_LAUNCH((dw_s1_rows_eval_kernel<1, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W,
-                                  nslabs, RPW, RG, waves); break;
-    }
-    return;
-  }
-  const int OD = (D - 1) / 2 + 1, SL = OD >= 8 ? 4 : OD >= 4 ? 2 : 1, nslabs = msl::cdiv(OD, SL);
-  const int RPW = 64 / (W / 4), RG = msl::cdiv(H / 2, RPW);
-  const int waves = N * C * nslabs * RG;
-  const dim3 grid(msl::cdiv(waves, 4)), block(256);
-  switch (SL) {
-    case 4: MSL_LAUNCH((dw_s2_rows_eval_kernel<4, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W, OD,
-                               nslabs, RPW, RG, waves); break;
-    case 2: MSL_LAUNCH((dw_s2_rows_eval_kernel<2, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W, OD,
-                               nslabs, RPW, RG, waves); break;
-    default: MSL_LAUNCH((dw_s2_rows_eval_kernel<1, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W, OD,
-                                nslabs, RPW, RG, waves); break;
-  }
-}
-
-// weight gradient on the wave kernels (the LDS-tiled / generic kernels remain for the other shapes)
-int wave_bww_num_partials(const WavePlan& wp, int N) { return N * wp.nslabs * (wp.wpp > 4 ? wp.wpp / 4 : 1); }
-
-template <typename T>
-void launch_wave_bww(const WavePlan& wp, int stride, const T* x, const float* in_scale, const float* in_shift,
-                     const T* dy, double* partials, int N, int C, int D, hipStream_t st) {
-  const int waves = N * (C / wp.cpw) * wp.nslabs * wp.wpp;
-  if (stride == 1) {
-    const dim3 grid(msl::cdiv(waves, 4)), block(256);
-#define MSL_DW_WAVE_BWW1(LW_, LH_)                                                                                \
-  switch (wp.SL) {                                                                                                \
-    case 8: MSL_LAUNCH((dw_s1_wave_bww_kernel<LW_, LH_, 8, T>), grid, block, 0, st, x, in_scale, in_shift,   \
-                               dy, partials, C, D, wp.nslabs, N); break;                                          \
-    case 4: MSL_LAUNCH((dw_s1_wave_bww_kernel<LW_, LH_, 4, T>), grid, block, 0, st, x, in_scale, in_shift,   \
-                               dy, partials, C, D, wp.nslabs, N); break;                                          \
-    case 2: MSL_LAUNCH((dw_s1_wave_bww_kernel<LW_, LH_, 2, T>), grid, block, 0, st, x, in_scale, in_shift,   \
-                               dy, partials, C, D, wp.nslabs, N); break;                                          \
-    default: MSL_LAUNCH((dw_s1_wave_bww_kernel<LW_, LH_, 1, T>), grid, block, 0, st, x, in_scale, in_shift,  \
-                                dy, partials, C, D, wp.nslabs, N); break;                                         \
-  }
-    if (wp.logw4 == 0) { MSL_DW_WAVE_BWW1(0, 2) }
-    else if (wp.logw4 == 1) { MSL_DW_WAVE_BWW1(1, 3) }
-    else { MSL_DW_WAVE_BWW1(2, 4) }
-#undef MSL_DW_WAVE_BWW1
-    return;
-  }
-  const int wpg = wp.wpp > 1 ? std::min(wp.wpp, 4) : 4, OD = (D - 1) / 2 + 1;
-  const dim3 grid(msl::cdiv(waves, wpg)), block(64 * wpg);
-#define MSL_DW_WAVE_BWW2(LW_, LH_)                                                                                \
-  switch (wp.SL) {                                                                                                \
-    case 4: MSL_LAUNCH((dw_s2_wave_bww_kernel<LW_, LH_, 4, T>), grid, block, 0, st, x, in_scale, in_shift,   \
-                               dy, partials, C, D, OD, wp.nslabs, N); break;                                      \
-    case 2: MSL_LAUNCH((dw_s2_wave_bww_kernel<LW_, LH_, 2, T>), grid, block, 0, st, x, in_scale, in_shift,   \
-                               dy, partials, C, D, OD, wp.nslabs, N); break;                                      \
-    default: MSL_LAUNCH((dw_s2_wave_bww_kernel<LW_, LH_, 1, T>), grid, block, 0, st, x, in_scale, in_shift,  \
-                                dy, partials, C, D, OD, wp.nslabs, N); break;                                     \
-  }
-  if (wp.logw4 == 1) { MSL_DW_WAVE_BWW2(1, 2) }
-  else if (wp.logw4 == 2) { MSL_DW_WAVE_BWW2(2, 3) }
-  else if (wp.logw4 == 3) { MSL_DW_WAVE_BWW2(3, 4) }
-  else { MSL_DW_WAVE_BWW2(4, 5) }
-#undef MSL_DW_WAVE_BWW2
-}
-
 template <typename K>
 int set_lds(K kernel, size_t bytes) {
   if (bytes > 64 * 1024) {
@@ -1701,58 +1449,210 @@ int set_lds(K kernel, size_t bytes) {
   return 0;
 }
 
+const msl::BnFold nofold{nullptr, 0, 0, 1.0, nullptr, nullptr, 0.f};
+
+// ---- one launcher per kernel family: the route's runtime values pick the template instantiation ----------------------------
+// Wave forward.  stride 1: planes of 4 / 8 / 16, slabs of 8 / 4 / 2 / 1 planes; flip: reversed taps (stride-1 bwd-data),
+// accumulate: y += result.  stride 2: planes of 8 .. 64, slabs of 4 / 2 / 1 (no flip / accumulate).
+template <typename T>
+int launch_wave(const DwRoute& r, int stride, const T* x, const float* in_scale, const float* in_shift, const float* w, T* y,
+                double* partials, int N, int C, int D, int flip, int accumulate, const msl::BnFold& fold, hipStream_t st) {
+  const int waves = N * (C / r.cpw) * r.nslabs * r.wpp;
+  if (stride == 1) {
+    const dim3 grid(msl::cdiv(waves, 4)), block(256);
+    return msl::dispatch_int<0, 1, 2>(r.logw4, [&](auto lw) {
+      return msl::dispatch_int<8, 4, 2, 1>(r.SLAB, [&](auto sl) {
+        constexpr int LW = decltype(lw)::value, SL = decltype(sl)::value;
+        MSL_LAUNCH((dw_s1_wave_kernel<LW, LW + 2, SL, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, partials, C, D,
+                   r.nslabs, N, flip, accumulate, fold);
+        return MSL_OK;
+      });
+    });
+  }
+  const int wpg = r.wpp > 1 ? std::min(r.wpp, 4) : 4;
+  const dim3 grid(msl::cdiv(waves, wpg)), block(64 * wpg);
+  return msl::dispatch_int<1, 2, 3, 4>(r.logw4, [&](auto lw) {
+    return msl::dispatch_int<4, 2, 1>(r.SLAB, [&](auto sl) {
+      constexpr int LW = decltype(lw)::value, SL = decltype(sl)::value;
+      MSL_LAUNCH((dw_s2_wave_kernel<LW, LW + 1, SL, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, partials, C, D, r.OD,
+                 r.nslabs, N, fold);
+      return MSL_OK;
+    });
+  });
+}
+
+// weight gradient on the wave kernels: the same grids and instantiation lists as the forward
+template <typename T>
+int launch_wave_bww(const DwRoute& r, int stride, const T* x, const float* in_scale, const float* in_shift, const T* dy,
+                    double* partials, int N, int C, int D, hipStream_t st) {
+  const int waves = N * (C / r.cpw) * r.nslabs * r.wpp;
+  if (stride == 1) {
+    const dim3 grid(msl::cdiv(waves, 4)), block(256);
+    return msl::dispatch_int<0, 1, 2>(r.logw4, [&](auto lw) {
+      return msl::dispatch_int<8, 4, 2, 1>(r.SLAB, [&](auto sl) {
+        constexpr int LW = decltype(lw)::value, SL = decltype(sl)::value;
+        MSL_LAUNCH((dw_s1_wave_bww_kernel<LW, LW + 2, SL, T>), grid, block, 0, st, x, in_scale, in_shift, dy, partials, C, D,
+                   r.nslabs, N);
+        return MSL_OK;
+      });
+    });
+  }
+  const int wpg = r.wpp > 1 ? std::min(r.wpp, 4) : 4;
+  const dim3 grid(msl::cdiv(waves, wpg)), block(64 * wpg);
+  return msl::dispatch_int<1, 2, 3, 4>(r.logw4, [&](auto lw) {
+    return msl::dispatch_int<4, 2, 1>(r.SLAB, [&](auto sl) {
+      constexpr int LW = decltype(lw)::value, SL = decltype(sl)::value;
+      MSL_LAUNCH((dw_s2_wave_bww_kernel<LW, LW + 1, SL, T>), grid, block, 0, st, x, in_scale, in_shift, dy, partials, C, D, r.OD,
+                 r.nslabs, N);
+      return MSL_OK;
+    });
+  });
+}
+
+// eval-mode forward on dw_s1_rows_eval_kernel / dw_s2_rows_eval_kernel: a wave owns a group of RPW rows of a slab
+template <typename T>
+int launch_rows_eval(const DwRoute& r, int stride, const T* x, const float* in_scale, const float* in_shift, const float* w,
+                     T* y, int N, int C, int D, int H, int W, hipStream_t st) {
+  const int RPW = 64 / (W / 4), RG = msl::cdiv(stride == 2 ? H / 2 : H, RPW);
+  const int waves = N * C * r.nslabs * RG;
+  const dim3 grid(msl::cdiv(waves, 4)), block(256);
+  return msl::dispatch_int<4, 2, 1>(r.SLAB, [&](auto sl) {
+    constexpr int SL = decltype(sl)::value;
+    if (stride == 1)
+      MSL_LAUNCH((dw_s1_rows_eval_kernel<SL, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W, r.nslabs, RPW, RG,
+                 waves);
+    else
+      MSL_LAUNCH((dw_s2_rows_eval_kernel<SL, T>), grid, block, 0, st, x, in_scale, in_shift, w, y, C, D, H, W, r.OD, r.nslabs,
+                 RPW, RG, waves);
+    return MSL_OK;
+  });
+}
+
+template <typename T>
+void launch_small_eval(int stride, const T* x, const float* in_scale, const float* in_shift, const float* w, T* y, int N, int C,
+                       int D, int H, int W, hipStream_t st) {
+  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+  MSL_LAUNCH(dw_small_eval_kernel<T>, dim3(msl::cdiv(N * C, 4)), dim3(256), 0, st, x, in_scale, in_shift, w, y, N * C, C, D, H,
+             W, OD, OH, OW, stride);
+}
+
+// Stream / Resident.  MODE 0: forward (Resident also the flipped forward); MODE 1: weight gradient - y holds dy and is only
+// read, w is unused, partials are the [C*27][NP] tap sums.
+template <int MODE>
+int launch_lds(const DwRoute& r, int stride, const float* x, const float* in_scale, const float* in_shift, const float* w,
+               float* y, double* partials, int N, int C, int D, int H, int W, int flip, int accumulate,
+               const msl::BnFold& fold, hipStream_t st) {
+  const dim3 grid(N * (C / r.G) * r.nslabs), block(256);
+  return msl::dispatch_int<1, 2>(stride, [&](auto s) {
+    constexpr int S = decltype(s)::value;
+    if (r.kind == DwKind::Resident) {
+      const auto k = dw_fwd_resident_kernel<S, MODE>;
+      if (const int e = set_lds(k, r.lds_bytes)) return e;
+      MSL_LAUNCH(k, grid, block, r.lds_bytes, st, x, in_scale, in_shift, w, y, partials, C, D, H, W, r.OD, r.OH, r.OW, r.G,
+                 r.SLAB, r.nslabs, N, flip, accumulate, fold);
+      return MSL_OK;
+    }
+    return msl::dispatch_int<1, 4>(r.ipt, [&](auto i) {
+      constexpr int IPT = decltype(i)::value, LPT = IPT == 1 ? 4 : 12;
+      const auto k = dw_fwd_stream_kernel<S, IPT, LPT, MODE>;
+      if (const int e = set_lds(k, r.lds_bytes)) return e;
+      MSL_LAUNCH(k, grid, block, r.lds_bytes, st, x, in_scale, in_shift, w, y, partials, C, D, H, W, r.OD, r.OH, r.OW, r.SLAB,
+                 r.nslabs, N, fold);
+      return MSL_OK;
+    });
+  });
+}
+
+int dwconv_fwd_impl(const float* x, const float* in_scale, const float* in_shift, const msl::BnFold& fold, const float* w,
+                    float* y, double* partials, int N, int C, int D, int H, int W, int stride, int force_naive, void* stream) {
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const DwRoute r = dw_route(DwOp::Fwd, false, N, C, D, H, W, stride, partials || fold.partials, force_naive != 0);
+  int rc = MSL_OK;
+  switch (r.kind) {
+    case DwKind::Wave: rc = launch_wave(r, stride, x, in_scale, in_shift, w, y, partials, N, C, D, 0, 0, fold, st); break;
+    case DwKind::RowsEval: rc = launch_rows_eval(r, stride, x, in_scale, in_shift, w, y, N, C, D, H, W, st); break;
+    case DwKind::SmallEval: launch_small_eval(stride, x, in_scale, in_shift, w, y, N, C, D, H, W, st); break;
+    case DwKind::Stream:
+    case DwKind::Resident:
+      rc = launch_lds<0>(r, stride, x, in_scale, in_shift, w, y, partials, N, C, D, H, W, 0, 0, fold, st);
+      break;
+    default: {  // Naive
+      const int S = r.OD * r.OH * r.OW;
+      MSL_LAUNCH(dw_fwd_naive_kernel, dim3(std::min(msl::cdiv(S, 256), 256), N * C), dim3(256), 0, st, x, in_scale, in_shift, w,
+                 y, C, D, H, W, r.OD, r.OH, r.OW, stride, fold);
+      MSL_LAUNCH_CHECK();
+      if (partials) MSL_LAUNCH(channel_stats_kernel, dim3(r.chunks, C, N), dim3(256), 0, st, y, partials, C, S, r.chunks);
+    }
+  }
+  if (rc != MSL_OK) return rc;
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
 }  // namespace
+
+// ---- library-internal launchers for dwconv_bwd.hip (declared in dwroute.hpp) ---------------------------------------------
+int dwconv_launch_bwd_weight(const DwRoute& r, const float* dy, const float* x, const float* in_scale, const float* in_shift,
+                             double* partials, int N, int C, int D, int H, int W, int stride, hipStream_t st) {
+  if (r.kind == DwKind::Wave) return launch_wave_bww(r, stride, x, in_scale, in_shift, dy, partials, N, C, D, st);
+  return launch_lds<1>(r, stride, x, in_scale, in_shift, nullptr, const_cast<float*>(dy), partials, N, C, D, H, W, 0, 0, nofold,
+                       st);
+}
+
+int dwconv_launch_s1_bwd_data(const DwRoute& r, const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
+                              int accumulate, hipStream_t st) {
+  if (r.kind == DwKind::Wave) return launch_wave(r, 1, dy, nullptr, nullptr, w, g_in, nullptr, N, C, D, 1, accumulate, nofold, st);
+  return launch_lds<0>(r, 1, dy, nullptr, nullptr, w, g_in, nullptr, N, C, D, H, W, 1, accumulate, nofold, st);
+}
 
 extern "C" {
 
 int msl_dwconv_fwd_num_partials(int N, int C, int D, int H, int W, int stride) {
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-  if (wp.ok) return N * wp.nslabs * (wp.wpp > 4 ? wp.wpp / 4 : 1);
-  return make_plan(N, C, D, H, W, stride).num_partials;
+  return dw_route(DwOp::Fwd, false, N, C, D, H, W, stride, true, false).num_partials;
 }
 
-// variant actually chosen for a shape (0 naive, 1 stream, 2 resident, 3 wave) — for tests / DESIGN.md
+// kernel a training-mode forward of the shape runs (0 naive, 1 stream, 2 resident, 3 wave) — for tests / DESIGN.md
 int msl_dwconv_fwd_variant(int N, int C, int D, int H, int W, int stride) {
-  if (make_wave_plan(N, C, D, H, W, stride).ok) return 3;
-  return make_plan(N, C, D, H, W, stride).variant;
+  switch (dw_route(DwOp::Fwd, false, N, C, D, H, W, stride, true, false).kind) {
+    case DwKind::Wave: return 3;
+    case DwKind::Resident: return 2;
+    case DwKind::Stream: return 1;
+    default: return 0;
+  }
 }
 
-static const msl::BnFold nofold{nullptr, 0, 0, 1.0, nullptr, nullptr, 0.f};
-
-// ---- bf16 storage on the wave kernels (the bf16 activation path, bf16.hip, tries these first) ---------------------------
-// number of statistics / weight-gradient partials per channel, or MSL_ERR_UNSUPPORTED when the shape has no wave plan
+// ---- bf16 storage on the wave / rows / small-map kernels (bf16.hip routes here; it decides from the same dw_route) ----------
+// number of statistics / weight-gradient partials per channel, or MSL_ERR_UNSUPPORTED when the shape has no wave route
 int msl_dwconv_wave_num_partials(int N, int C, int D, int H, int W, int stride) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-  return wp.ok ? N * wp.nslabs * (wp.wpp > 4 ? wp.wpp / 4 : 1) : MSL_ERR_UNSUPPORTED;
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
+  const DwRoute r = dw_route(DwOp::Fwd, false, N, C, D, H, W, stride, true, false);
+  return r.kind == DwKind::Wave ? r.num_partials : MSL_ERR_UNSUPPORTED;
 }
 
-// 1 when a statistics-free (eval-mode) forward of this shape runs on dw_s2_rows_eval_kernel / dw_s1_rows_eval_kernel (fp32: inside
-// msl_dwconv_fwd; bf16: msl_dwconv_fwd_wave_bf16 with partials == NULL), else 0
+// 1 when a statistics-free (eval-mode) forward of this shape runs on dw_s2_rows_eval_kernel / dw_s1_rows_eval_kernel (fp32:
+// msl_dwconv_fwd; bf16: msl_dwconv_fwd_bf16, both with partials == NULL), else 0
 int msl_dwconv_fwd_eval_rows_ok(int N, int C, int D, int H, int W, int stride) {
-  return (N > 0 && C > 0 && D > 0 && H > 0 && W > 0 && rows_eval_ok(N, C, D, H, W, stride)) ? 1 : 0;
+  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  return dw_route(DwOp::Fwd, false, N, C, D, H, W, stride, false, false).kind == DwKind::RowsEval ? 1 : 0;
 }
 
 // x (N,C,D,H,W) bf16 raw (+ input affine) -> y bf16 raw (+ fp64 statistics partials [2][C][NP] from the fp32 accumulators);
-// flip: reversed taps (stride-1 bwd-data), accumulate: y += result
+// flip: reversed taps (stride-1 bwd-data), accumulate: y += result.  Wave routes, and RowsEval routes (partials == NULL, no
+// flip / accumulate); MSL_ERR_UNSUPPORTED for every other shape.
 int msl_dwconv_fwd_wave_bf16(const void* x, const float* in_scale, const float* in_shift, const float* w, void* y,
                              double* partials, int N, int C, int D, int H, int W, int stride, int flip, int accumulate,
                              void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-  if (!wp.ok && !partials && !flip && !accumulate && rows_eval_ok(N, C, D, H, W, stride)) {  // eval-mode forward
-    launch_rows_eval(reinterpret_cast<const dwu16*>(x), in_scale, in_shift, w, reinterpret_cast<dwu16*>(y), N, C, D, H, W,
-                     stride, (hipStream_t)stream);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  if (!wp.ok || (stride == 2 && (flip || accumulate))) return MSL_ERR_UNSUPPORTED;
-  if (stride == 1)
-    launch_wave(wp, reinterpret_cast<const dwu16*>(x), in_scale, in_shift, w, reinterpret_cast<dwu16*>(y), partials, N, C, D, flip,
-                accumulate, nofold, (hipStream_t)stream);
-  else
-    launch_wave_s2(wp, reinterpret_cast<const dwu16*>(x), in_scale, in_shift, w, reinterpret_cast<dwu16*>(y), partials, N, C, D,
-                   nofold, (hipStream_t)stream);
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
+  const DwRoute r = dw_route(flip ? DwOp::BwdDataS1 : DwOp::Fwd, true, N, C, D, H, W, stride, partials != nullptr, false);
+  const dwu16* xb = reinterpret_cast<const dwu16*>(x);
+  dwu16* yb = reinterpret_cast<dwu16*>(y);
+  int rc = MSL_ERR_UNSUPPORTED;
+  if (r.kind == DwKind::RowsEval && !accumulate)
+    rc = launch_rows_eval(r, stride, xb, in_scale, in_shift, w, yb, N, C, D, H, W, (hipStream_t)stream);
+  else if (r.kind == DwKind::Wave && !(stride == 2 && accumulate))
+    rc = launch_wave(r, stride, xb, in_scale, in_shift, w, yb, partials, N, C, D, flip, accumulate, nofold, (hipStream_t)stream);
+  if (rc != MSL_OK) return rc;
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -1762,16 +1662,13 @@ int msl_dwconv_fwd_wave_bf16(const void* x, const float* in_scale, const float* 
 int msl_dwconv_fwd_wave_bf16_fold(const void* x, const double* in_partials, int in_np, double in_count, const float* gamma,
                                   const float* beta, float eps, const float* w, void* y, double* partials, int N, int C, int D,
                                   int H, int W, int stride, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2) || !in_partials || in_np <= 0) return MSL_ERR_ARG;
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-  if (!wp.ok) return MSL_ERR_UNSUPPORTED;
+  if (!dw_args_ok(N, C, D, H, W, stride) || !in_partials || in_np <= 0) return MSL_ERR_ARG;
+  const DwRoute r = dw_route(DwOp::Fwd, true, N, C, D, H, W, stride, true, false);
+  if (r.kind != DwKind::Wave) return MSL_ERR_UNSUPPORTED;
   const msl::BnFold fold{in_partials, in_np, C, in_count, gamma, beta, eps};
-  if (stride == 1)
-    launch_wave(wp, reinterpret_cast<const dwu16*>(x), (const float*)nullptr, (const float*)nullptr, w, reinterpret_cast<dwu16*>(y),
-                partials, N, C, D, 0, 0, fold, (hipStream_t)stream);
-  else
-    launch_wave_s2(wp, reinterpret_cast<const dwu16*>(x), (const float*)nullptr, (const float*)nullptr, w,
-                   reinterpret_cast<dwu16*>(y), partials, N, C, D, fold, (hipStream_t)stream);
+  const int rc = launch_wave(r, stride, reinterpret_cast<const dwu16*>(x), (const float*)nullptr, (const float*)nullptr, w,
+                             reinterpret_cast<dwu16*>(y), partials, N, C, D, 0, 0, fold, (hipStream_t)stream);
+  if (rc != MSL_OK) return rc;
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -1779,100 +1676,23 @@ int msl_dwconv_fwd_wave_bf16_fold(const void* x, const double* in_partials, int 
 // dz (N,C,OD,OH,OW), x (N,C,D,H,W) bf16 (+ input affine) -> fp64 partials [C*27][NP], NP = msl_dwconv_wave_num_partials
 int msl_dwconv_bwd_weight_wave_bf16(const void* dz, const void* x, const float* in_scale, const float* in_shift,
                                     double* partials, int N, int C, int D, int H, int W, int stride, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2) || !partials) return MSL_ERR_ARG;
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-  if (!wp.ok) return MSL_ERR_UNSUPPORTED;
-  launch_wave_bww(wp, stride, reinterpret_cast<const dwu16*>(x), in_scale, in_shift, reinterpret_cast<const dwu16*>(dz), partials,
-                  N, C, D, (hipStream_t)stream);
+  if (!dw_args_ok(N, C, D, H, W, stride) || !partials) return MSL_ERR_ARG;
+  const DwRoute r = dw_route(DwOp::BwdWeight, true, N, C, D, H, W, stride, false, false);
+  if (r.kind != DwKind::Wave) return MSL_ERR_UNSUPPORTED;
+  const int rc = launch_wave_bww(r, stride, reinterpret_cast<const dwu16*>(x), in_scale, in_shift,
+                                 reinterpret_cast<const dwu16*>(dz), partials, N, C, D, (hipStream_t)stream);
+  if (rc != MSL_OK) return rc;
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
 
-// bf16 storage, statistics-free forward of a map of at most 512 voxels (dw_small_eval_kernel); MSL_ERR_UNSUPPORTED if larger
+// bf16 storage, statistics-free forward of a map of at most DW_SMALL_VOX voxels (dw_small_eval_kernel); MSL_ERR_UNSUPPORTED if
+// larger
 int msl_dwconv_fwd_small_eval_bf16(const void* x, const float* in_scale, const float* in_shift, const float* w, void* y, int N,
                                    int C, int D, int H, int W, int stride, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
   if (D * H * W > DW_SMALL_VOX || (D + 2) * (H + 2) * (W + 2) > DW_SMALL_IMG) return MSL_ERR_UNSUPPORTED;
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  MSL_LAUNCH(dw_small_eval_kernel<dwu16>, dim3(msl::cdiv(N * C, 4)), dim3(256), 0, (hipStream_t)stream, (const dwu16*)x,
-             in_scale, in_shift, w, (dwu16*)y, N * C, C, D, H, W, OD, OH, OW, stride);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-static int dwconv_fwd_impl(const float* x, const float* in_scale, const float* in_shift, const msl::BnFold& fold,
-                           const float* w, float* y, double* partials, int N, int C, int D, int H, int W, int stride,
-                           int force_naive, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (!force_naive) {
-    const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-    if (wp.ok) {
-      if (stride == 2) launch_wave_s2(wp, x, in_scale, in_shift, w, y, partials, N, C, D, fold, st);
-      else launch_wave(wp, x, in_scale, in_shift, w, y, partials, N, C, D, 0, 0, fold, st);
-      MSL_LAUNCH_CHECK();
-      return MSL_OK;
-    }
-    if (!partials && !fold.partials && rows_eval_ok(N, C, D, H, W, stride)) {  // eval-mode forward, no statistics
-      launch_rows_eval(x, in_scale, in_shift, w, y, N, C, D, H, W, stride, st);
-      MSL_LAUNCH_CHECK();
-      return MSL_OK;
-    }
-  }
-  if (!force_naive && !partials && !fold.partials && D * H * W <= DW_SMALL_VOX && (D + 2) * (H + 2) * (W + 2) <= DW_SMALL_IMG) {
-    MSL_LAUNCH(dw_small_eval_kernel<float>, dim3(msl::cdiv(N * C, 4)), dim3(256), 0, st, x, in_scale, in_shift, w, y, N * C, C,
-               D, H, W, OD, OH, OW, stride);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  DwPlan pl = make_plan(N, C, D, H, W, stride);
-  if (force_naive && pl.variant != 0) {
-    pl.variant = 0;
-    pl.num_partials = N * msl::cdiv(OD * OH * OW, STATS_CHUNK);
-  }
-  if (pl.variant == 0) {
-    const int S = OD * OH * OW;
-    MSL_LAUNCH(dw_fwd_naive_kernel, dim3(std::min(msl::cdiv(S, 256), 256), N * C), dim3(256), 0, st, x,
-                       in_scale, in_shift, w, y, C, D, H, W, OD, OH, OW, stride, fold);
-    MSL_LAUNCH_CHECK();
-    if (partials) {
-      const int chunks = msl::cdiv(S, STATS_CHUNK);
-      MSL_LAUNCH(channel_stats_kernel, dim3(chunks, C, N), dim3(256), 0, st, y, partials, C, S, chunks);
-      MSL_LAUNCH_CHECK();
-    }
-    return MSL_OK;
-  }
-  const int nblocks = N * (C / pl.G) * pl.nslabs;
-  if (pl.variant == 1) {
-#define MSL_DW_STREAM(S_, I_, L_)                                                                              \
-  do {                                                                                                         \
-    int e_ = set_lds(dw_fwd_stream_kernel<S_, I_, L_, 0>, pl.lds_bytes);                                          \
-    if (e_) return e_;                                                                                         \
-    MSL_LAUNCH((dw_fwd_stream_kernel<S_, I_, L_, 0>), dim3(nblocks), dim3(256), pl.lds_bytes, st, x,      \
-                       in_scale, in_shift, w, y, partials, C, D, H, W, OD, OH, OW, pl.SLAB, pl.nslabs, N, fold);  \
-  } while (0)
-    if (stride == 2) {
-      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_STREAM(2, 1, 4);
-      else MSL_DW_STREAM(2, 4, 12);
-    } else {
-      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_STREAM(1, 1, 4);
-      else MSL_DW_STREAM(1, 4, 12);
-    }
-#undef MSL_DW_STREAM
-  } else {
-    if (stride == 2) {
-      int e_ = set_lds(dw_fwd_resident_kernel<2, 0>, pl.lds_bytes);
-      if (e_) return e_;
-      MSL_LAUNCH((dw_fwd_resident_kernel<2, 0>), dim3(nblocks), dim3(256), pl.lds_bytes, st, x, in_scale,
-                         in_shift, w, y, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, fold);
-    } else {
-      int e_ = set_lds(dw_fwd_resident_kernel<1, 0>, pl.lds_bytes);
-      if (e_) return e_;
-      MSL_LAUNCH((dw_fwd_resident_kernel<1, 0>), dim3(nblocks), dim3(256), pl.lds_bytes, st, x, in_scale,
-                         in_shift, w, y, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, fold);
-    }
-  }
+  launch_small_eval(stride, (const dwu16*)x, in_scale, in_shift, w, (dwu16*)y, N, C, D, H, W, (hipStream_t)stream);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -1894,85 +1714,3 @@ int msl_dwconv_fwd_fold(const float* x, const double* in_partials, int in_np, do
 }
 
 }  // extern "C"
-
-// ---- library-internal entry points of the LDS-tiled kernels (C++ linkage: not part of the C ABI) ----------------------------
-// bwd-weight on the wave kernels or the LDS-tiled kernels (MODE 1), for msl_dwconv_bwd_weight (dwconv_bwd.hip).  Returns
-// MSL_ERR_UNSUPPORTED for shapes on the generic path.  partials: fp64 [C*27][NP], NP = dwconv_bwd_weight_tiled_num_partials().
-int dwconv_bwd_weight_tiled(const float* dy, const float* x, const float* in_scale, const float* in_shift,
-                            double* partials, int N, int C, int D, int H, int W, int stride, void* stream) {
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-  if (wp.ok) {
-    launch_wave_bww(wp, stride, x, in_scale, in_shift, dy, partials, N, C, D, (hipStream_t)stream);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  DwPlan pl = make_plan(N, C, D, H, W, stride);
-  // many channels per workgroup (tiny tail volumes): the per-channel epilogue reduction dominates and the
-  // barrier-free wave-per-item kernel of dwconv_bwd.hip is faster
-  if (pl.variant == 0 || pl.G > 4) return MSL_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblocks = N * (C / pl.G) * pl.nslabs;
-  const size_t lds = std::max(pl.lds_bytes, (size_t)27 * 256 * sizeof(float));
-  float* dyp = const_cast<float*>(dy);
-  if (pl.variant == 1) {
-#define MSL_DW_BWW(S_, I_, L_)                                                                                  \
-  do {                                                                                                          \
-    int e_ = set_lds(dw_fwd_stream_kernel<S_, I_, L_, 1>, lds);                                                 \
-    if (e_) return e_;                                                                                          \
-    MSL_LAUNCH((dw_fwd_stream_kernel<S_, I_, L_, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale,   \
-                       in_shift, nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.SLAB, pl.nslabs, N, nofold); \
-  } while (0)
-    if (stride == 2) {
-      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_BWW(2, 1, 4);
-      else MSL_DW_BWW(2, 4, 12);
-    } else {
-      if (pl.ipt == 1 && pl.lpt == 4) MSL_DW_BWW(1, 1, 4);
-      else MSL_DW_BWW(1, 4, 12);
-    }
-#undef MSL_DW_BWW
-  } else {
-    if (stride == 2) {
-      int e_ = set_lds(dw_fwd_resident_kernel<2, 1>, lds);
-      if (e_) return e_;
-      MSL_LAUNCH((dw_fwd_resident_kernel<2, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale, in_shift,
-                         nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, nofold);
-    } else {
-      int e_ = set_lds(dw_fwd_resident_kernel<1, 1>, lds);
-      if (e_) return e_;
-      MSL_LAUNCH((dw_fwd_resident_kernel<1, 1>), dim3(nblocks), dim3(256), lds, st, x, in_scale, in_shift,
-                         nullptr, dyp, partials, C, D, H, W, OD, OH, OW, pl.G, pl.SLAB, pl.nslabs, N, 0, 0, nofold);
-    }
-  }
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-int dwconv_bwd_weight_tiled_num_partials(int N, int C, int D, int H, int W, int stride) {
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, stride);
-  if (wp.ok) return wave_bww_num_partials(wp, N);
-  DwPlan pl = make_plan(N, C, D, H, W, stride);
-  return (pl.variant == 0 || pl.G > 4) ? -1 : pl.num_partials;
-}
-
-// Stride-1 bwd-data is the forward convolution of dy with the taps reversed (w[26-k]); reuse the wave / LDS-resident
-// forward kernels, for msl_dwconv_bwd_data (dwconv_bwd.hip).  Returns MSL_ERR_UNSUPPORTED when the shape is on neither.
-int dwconv_s1_bwd_data_resident(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
-                                int accumulate, void* stream) {
-  const WavePlan wp = make_wave_plan(N, C, D, H, W, 1);
-  if (wp.ok) {
-    launch_wave(wp, dy, nullptr, nullptr, w, g_in, nullptr, N, C, D, 1, accumulate, nofold, (hipStream_t)stream);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  DwPlan pl = make_plan(N, C, D, H, W, 1);
-  if (pl.variant != 2) return MSL_ERR_UNSUPPORTED;
-  const int nblocks = N * (C / pl.G) * pl.nslabs;
-  int e_ = set_lds(dw_fwd_resident_kernel<1, 0>, pl.lds_bytes);
-  if (e_) return e_;
-  MSL_LAUNCH((dw_fwd_resident_kernel<1, 0>), dim3(nblocks), dim3(256), pl.lds_bytes, (hipStream_t)stream, dy,
-                     nullptr, nullptr, w, g_in, nullptr, C, D, H, W, D, H, W, pl.G, pl.SLAB, pl.nslabs, N, 1, accumulate, nofold);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}

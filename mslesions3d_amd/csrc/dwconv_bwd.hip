@@ -6,7 +6,10 @@
 // enumerated explicitly instead of testing 27 taps.  bwd-weight keeps 27 accumulators per thread and ends
 // in a fixed-order workgroup reduction to fp64 partials (no atomics -> bit-reproducible).
 #include "common.hpp"
+#include "dwroute.hpp"
 #include <algorithm>
+
+using namespace msl::dw;
 
 namespace {
 
@@ -283,7 +286,6 @@ __global__ __launch_bounds__(256) void dw_bwd_data_naive_kernel(const float* __r
 
 // bwd-weight: one WAVE per work item (n, c, chunk of BW_CHUNK outputs): 27 accumulators per lane, a shuffle
 // reduction at the end, no workgroup barrier at all (the tail layers have only 64 outputs per (n, c)).
-constexpr int BW_CHUNK = 1024;
 __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ in_scale,
                                                             const float* __restrict__ in_shift,
@@ -484,39 +486,61 @@ __global__ __launch_bounds__(64) void dw_bwd_weight_finalize_kernel(const double
   if (lane == 0) dw[i] = (float)s;
 }
 
-}  // namespace
+constexpr int S2F_PPT = 4;
 
-// dwconv.hip (library-internal)
-int dwconv_bwd_weight_tiled(const float* dy, const float* x, const float* in_scale, const float* in_shift, double* partials,
-                            int N, int C, int D, int H, int W, int stride, void* stream);
-int dwconv_bwd_weight_tiled_num_partials(int N, int C, int D, int H, int W, int stride);
-int dwconv_s1_bwd_data_resident(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W, int accumulate,
-                                void* stream);
+// The stride-2 patch kernels take every shape with W % 4 == 0: no route, one grid each for the launch and its partial count.
+// workgroups per (n, c) of dw_bwd_data_s2_patch_kernel (a thread owns one patch of 2 x 2 x 4 input voxels) ...
+int s2_patch_blocks(int D, int H, int W) { return msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256); }
+// ... and of dw_s2_bwd_reduce_bww_kernel (S2F_PPT patches per thread)
+int s2_fused_blocks(int D, int H, int W) { return msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256 * S2F_PPT); }
+
+// REDUCE: also emit the BatchNorm-backward partials [2][C][N * s2_patch_blocks] of the layer whose gradient is written
+template <bool REDUCE, typename T>
+void launch_s2_patch(const T* dy, const float* w, T* g_in, const T* y_prev, const float* bn_scale, const float* bn_shift,
+                     const float* bn_mean, const float* bn_invstd, double* partials, int N, int C, int D, int H, int W,
+                     int accumulate, void* stream) {
+  MSL_LAUNCH((dw_bwd_data_s2_patch_kernel<REDUCE, T>), dim3(s2_patch_blocks(D, H, W), N * C), dim3(256), 0, (hipStream_t)stream,
+             dy, w, g_in, C, D, H, W, (D - 1) / 2 + 1, (H - 1) / 2 + 1, (W - 1) / 2 + 1, accumulate, y_prev, bn_scale, bn_shift,
+             bn_mean, bn_invstd, partials);
+}
+
+template <typename T>
+void launch_s2_fused(const T* dy, const float* w, const T* y_prev, const float* bn_scale, const float* bn_shift,
+                     const float* bn_mean, const float* bn_invstd, double* bn_partials, double* w_partials, float* w_taps_t,
+                     T* g_in, int accumulate, int N, int C, int D, int H, int W, void* stream) {
+  MSL_LAUNCH((dw_s2_bwd_reduce_bww_kernel<S2F_PPT, T>), dim3(s2_fused_blocks(D, H, W), N * C), dim3(256), 0, (hipStream_t)stream,
+             dy, w, C, D, H, W, (D - 1) / 2 + 1, (H - 1) / 2 + 1, (W - 1) / 2 + 1, y_prev, bn_scale, bn_shift, bn_mean, bn_invstd,
+             bn_partials, w_partials, w_taps_t, g_in, accumulate);
+}
+
+}  // namespace
 
 extern "C" {
 
 // dy (N,C,OD,OH,OW) -> g_in (N,C,D,H,W); accumulate != 0 adds into g_in
 int msl_dwconv_bwd_data(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
                         int stride, int accumulate, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) {
-    const int rc = dwconv_s1_bwd_data_resident(dy, w, g_in, N, C, D, H, W, accumulate, stream);
-    if (rc != MSL_ERR_UNSUPPORTED) return rc;
-  }
-  if (W % 4 == 0) {
-    if (stride == 2) {
-      dim3 grid(msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256), N * C);
-      MSL_LAUNCH((dw_bwd_data_s2_patch_kernel<false, float>), grid, dim3(256), 0, st, dy, w, g_in, C, D, H, W, OD, OH, OW,
-                         accumulate, (const float*)nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    } else {
-      dim3 grid(msl::cdiv(D * H * (W / 4), 256), N * C);
-      MSL_LAUNCH(dw_bwd_data_kernel<1>, grid, dim3(256), 0, st, dy, w, g_in, C, D, H, W, OD, OH, OW, accumulate);
+  const DwRoute r = dw_route(DwOp::BwdData, false, N, C, D, H, W, stride, false, false);
+  switch (r.kind) {
+    case DwKind::Wave:
+    case DwKind::Resident: {
+      const int rc = dwconv_launch_s1_bwd_data(r, dy, w, g_in, N, C, D, H, W, accumulate, st);
+      if (rc != MSL_OK) return rc;
+      break;
     }
-  } else {
-    dim3 grid(std::min(msl::cdiv(D * H * W, 256), 256), N * C);
-    MSL_LAUNCH(dw_bwd_data_naive_kernel, grid, dim3(256), 0, st, dy, w, g_in, C, D, H, W, OD, OH, OW, stride, accumulate);
+    case DwKind::S2Patch:
+      launch_s2_patch<false, float>(dy, w, g_in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, D, H, W, accumulate,
+                                    stream);
+      break;
+    case DwKind::DataVec:
+      MSL_LAUNCH(dw_bwd_data_kernel<1>, dim3(msl::cdiv(D * H * (W / 4), 256), N * C), dim3(256), 0, st, dy, w, g_in, C, D, H, W,
+                 r.OD, r.OH, r.OW, accumulate);
+      break;
+    default:  // DataNaive
+      MSL_LAUNCH(dw_bwd_data_naive_kernel, dim3(std::min(msl::cdiv(D * H * W, 256), 256), N * C), dim3(256), 0, st, dy, w, g_in,
+                 C, D, H, W, r.OD, r.OH, r.OW, stride, accumulate);
   }
   MSL_LAUNCH_CHECK();
   return MSL_OK;
@@ -524,22 +548,19 @@ int msl_dwconv_bwd_data(const float* dy, const float* w, float* g_in, int N, int
 
 // Stride-2 bwd-data that also emits the BatchNorm-backward partials (sum gm, sum gm*xhat; fp64 [2][C][NP]) of the
 // layer whose activation gradient it writes (y_prev = that layer's raw conv output, vec = its folded BatchNorm).
-// -2 unless stride == 2 and W % 4 == 0.
+// NP, or -1 unless W % 4 == 0.
 int msl_dwconv_bwd_data_bnreduce_num_partials(int N, int C, int D, int H, int W) {
-  if (W % 4 != 0) return -1;
-  return N * msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256);
+  return W % 4 != 0 ? -1 : N * s2_patch_blocks(D, H, W);
 }
 
 int msl_dwconv_bwd_data_bnreduce(const float* dy, const float* w, float* g_in, const float* y_prev,
                                  const float* bn_scale, const float* bn_shift, const float* bn_mean,
                                  const float* bn_invstd, double* partials, int N, int C, int D, int H, int W, int stride,
                                  int accumulate, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, 2)) return MSL_ERR_ARG;
   if (stride != 2 || W % 4 != 0) return MSL_ERR_UNSUPPORTED;
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  dim3 grid(msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256), N * C);
-  MSL_LAUNCH((dw_bwd_data_s2_patch_kernel<true, float>), grid, dim3(256), 0, (hipStream_t)stream, dy, w, g_in, C, D, H, W,
-                     OD, OH, OW, accumulate, y_prev, bn_scale, bn_shift, bn_mean, bn_invstd, partials);
+  launch_s2_patch<true, float>(dy, w, g_in, y_prev, bn_scale, bn_shift, bn_mean, bn_invstd, partials, N, C, D, H, W, accumulate,
+                               stream);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -549,68 +570,53 @@ int msl_dwconv_bwd_data_bnreduce(const float* dy, const float* w, float* g_in, c
 // layer whose activation gradient is written, computed from the ROUNDED gradient.  W % 4 == 0, else MSL_ERR_UNSUPPORTED.
 int msl_dwconv_bwd_data_s2_patch_bf16(const void* dy, const float* w, void* g_in, const void* y_prev, const float* bn_vec,
                                       double* partials, int N, int C, int D, int H, int W, int accumulate, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, 2)) return MSL_ERR_ARG;
   if (W % 4 != 0) return MSL_ERR_UNSUPPORTED;
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  dim3 grid(msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256), N * C);
   typedef msl::su16 u16;
   if (y_prev) {
     if (!bn_vec || !partials) return MSL_ERR_ARG;
-    MSL_LAUNCH((dw_bwd_data_s2_patch_kernel<true, u16>), grid, dim3(256), 0, (hipStream_t)stream, (const u16*)dy, w,
-                       (u16*)g_in, C, D, H, W, OD, OH, OW, accumulate, (const u16*)y_prev, bn_vec, bn_vec + C, bn_vec + 2 * C,
-                       bn_vec + 3 * C, partials);
+    launch_s2_patch<true, u16>((const u16*)dy, w, (u16*)g_in, (const u16*)y_prev, bn_vec, bn_vec + C, bn_vec + 2 * C,
+                               bn_vec + 3 * C, partials, N, C, D, H, W, accumulate, stream);
   } else {
-    MSL_LAUNCH((dw_bwd_data_s2_patch_kernel<false, u16>), grid, dim3(256), 0, (hipStream_t)stream, (const u16*)dy, w,
-                       (u16*)g_in, C, D, H, W, OD, OH, OW, accumulate, (const u16*)nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr);
+    launch_s2_patch<false, u16>((const u16*)dy, w, (u16*)g_in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, D, H,
+                                W, accumulate, stream);
   }
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
 
 int msl_dwconv_bwd_weight_num_partials(int N, int C, int D, int H, int W, int stride) {
-  const int tiled = dwconv_bwd_weight_tiled_num_partials(N, C, D, H, W, stride);
-  if (tiled > 0) return tiled;
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-  return N * msl::cdiv(OD * OH * OW, BW_CHUNK);
+  const DwRoute r = dw_route(DwOp::BwdWeight, false, N, C, D, H, W, stride, false, false);
+  // (a non-positive batch launches nothing; it has always been answered with the generic kernel's formula)
+  return r.kind == DwKind::Chunks || r.num_partials > 0 ? r.num_partials : N * msl::cdiv(r.OD * r.OH * r.OW, BW_CHUNK);
 }
 
 // dw (C,27) from dy and the raw input x (+ its affine); partials: fp64 [C*27][NP], NP = msl_dwconv_bwd_weight_num_partials.
 // dw == NULL: leave the partials (deferred reduction, msl_grad_reduce_batch kind 1).
 int msl_dwconv_bwd_weight(const float* dy, const float* x, const float* in_scale, const float* in_shift, float* dw,
                           double* partials, int N, int C, int D, int H, int W, int stride, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return MSL_ERR_ARG;
-  const int OD = (D - 1) / stride + 1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  {
-    const int rc = dwconv_bwd_weight_tiled(dy, x, in_scale, in_shift, partials, N, C, D, H, W, stride, stream);
-    if (rc == MSL_OK) {
-      if (!dw) return MSL_OK;
-      const int NPt = dwconv_bwd_weight_tiled_num_partials(N, C, D, H, W, stride);
-      MSL_LAUNCH(dw_bwd_weight_finalize_kernel, dim3(C * 27), dim3(64), 0, st, partials, NPt, dw, C * 27);
-      MSL_LAUNCH_CHECK();
-      return MSL_OK;
-    }
-    if (rc != MSL_ERR_UNSUPPORTED) return rc;
+  const DwRoute r = dw_route(DwOp::BwdWeight, false, N, C, D, H, W, stride, false, false);
+  if (r.kind == DwKind::Chunks) {
+    const int total_items = N * C * r.chunks;
+    MSL_LAUNCH(dw_bwd_weight_kernel, dim3(msl::cdiv(total_items, 4)), dim3(256), 0, st, dy, x, in_scale, in_shift, partials, C,
+               D, H, W, r.OD, r.OH, r.OW, stride, r.chunks, r.num_partials, total_items);
+  } else {
+    const int rc = dwconv_launch_bwd_weight(r, dy, x, in_scale, in_shift, partials, N, C, D, H, W, stride, st);
+    if (rc != MSL_OK) return rc;
   }
-  const int chunks = msl::cdiv(OD * OH * OW, BW_CHUNK);
-  const int total_items = N * C * chunks;
-  MSL_LAUNCH(dw_bwd_weight_kernel, dim3(msl::cdiv(total_items, 4)), dim3(256), 0, st, dy, x, in_scale, in_shift,
-                     partials, C, D, H, W, OD, OH, OW, stride, chunks, N * chunks, total_items);
   MSL_LAUNCH_CHECK();
   if (!dw) return MSL_OK;
-  MSL_LAUNCH(dw_bwd_weight_finalize_kernel, dim3(C * 27), dim3(64), 0, st, partials, N * chunks, dw, C * 27);
+  MSL_LAUNCH(dw_bwd_weight_finalize_kernel, dim3(C * 27), dim3(64), 0, st, partials, r.num_partials, dw, C * 27);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
 
-constexpr int S2F_PPT = 4;
-
 // Number of fp64 partials per channel (BatchNorm sums) and per (channel, tap) (weight gradient) written by
 // msl_dwconv_s2_bwd_bnreduce_bww; -1 if the shape is not supported.
 int msl_dwconv_s2_bwd_bnreduce_bww_num_partials(int N, int C, int D, int H, int W) {
-  if (W % 4 != 0) return -1;
-  return N * msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256 * S2F_PPT);
+  return W % 4 != 0 ? -1 : N * s2_fused_blocks(D, H, W);
 }
 
 // dy = dL/dz (N,C,OD,OH,OW) of a stride-2 depthwise layer, y_prev (N,C,D,H,W) = raw output of the producer layer with
@@ -621,12 +627,10 @@ int msl_dwconv_s2_bwd_bnreduce_bww(const float* dy, const float* w, const float*
                                    const float* bn_shift, const float* bn_mean, const float* bn_invstd,
                                    double* bn_partials, double* w_partials, float* w_taps_t, int N, int C, int D, int H,
                                    int W, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, 2)) return MSL_ERR_ARG;
   if (W % 4 != 0) return MSL_ERR_UNSUPPORTED;
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  dim3 grid(msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256 * S2F_PPT), N * C);
-  MSL_LAUNCH((dw_s2_bwd_reduce_bww_kernel<S2F_PPT, float>), grid, dim3(256), 0, (hipStream_t)stream, dy, w, C, D, H, W, OD,
-                     OH, OW, y_prev, bn_scale, bn_shift, bn_mean, bn_invstd, bn_partials, w_partials, w_taps_t, (float*)nullptr, 0);
+  launch_s2_fused<float>(dy, w, y_prev, bn_scale, bn_shift, bn_mean, bn_invstd, bn_partials, w_partials, w_taps_t, nullptr, 0, N,
+                         C, D, H, W, stream);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -639,13 +643,10 @@ int msl_dwconv_s2_bwd_data_bnreduce_bww(const float* dy, const float* w, float* 
                                         const float* bn_scale, const float* bn_shift, const float* bn_mean,
                                         const float* bn_invstd, double* bn_partials, double* w_partials, int N, int C, int D,
                                         int H, int W, int accumulate, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || !g_in) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, 2) || !g_in) return MSL_ERR_ARG;
   if (W % 4 != 0) return MSL_ERR_UNSUPPORTED;
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  dim3 grid(msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256 * S2F_PPT), N * C);
-  MSL_LAUNCH((dw_s2_bwd_reduce_bww_kernel<S2F_PPT, float>), grid, dim3(256), 0, (hipStream_t)stream, dy, w, C, D, H, W, OD,
-                     OH, OW, y_prev, bn_scale, bn_shift, bn_mean, bn_invstd, bn_partials, w_partials, (float*)nullptr, g_in,
-                     accumulate);
+  launch_s2_fused<float>(dy, w, y_prev, bn_scale, bn_shift, bn_mean, bn_invstd, bn_partials, w_partials, nullptr, g_in, accumulate,
+                         N, C, D, H, W, stream);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -654,14 +655,11 @@ int msl_dwconv_s2_bwd_data_bnreduce_bww(const float* dy, const float* w, float* 
 int msl_dwconv_s2_bwd_bnreduce_bww_bf16(const void* dy, const float* w, const void* y_prev, const float* bn_vec,
                                         double* bn_partials, double* w_partials, float* w_taps_t, int N, int C, int D, int H,
                                         int W, void* stream) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || !bn_vec) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, 2) || !bn_vec) return MSL_ERR_ARG;
   if (W % 4 != 0) return MSL_ERR_UNSUPPORTED;
-  const int OD = (D - 1) / 2 + 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  dim3 grid(msl::cdiv(((D + 1) / 2) * ((H + 1) / 2) * (W / 4), 256 * S2F_PPT), N * C);
   typedef msl::su16 u16;
-  MSL_LAUNCH((dw_s2_bwd_reduce_bww_kernel<S2F_PPT, u16>), grid, dim3(256), 0, (hipStream_t)stream, (const u16*)dy, w, C,
-                     D, H, W, OD, OH, OW, (const u16*)y_prev, bn_vec, bn_vec + C, bn_vec + 2 * C, bn_vec + 3 * C, bn_partials,
-                     w_partials, w_taps_t, (u16*)nullptr, 0);
+  launch_s2_fused<u16>((const u16*)dy, w, (const u16*)y_prev, bn_vec, bn_vec + C, bn_vec + 2 * C, bn_vec + 3 * C, bn_partials,
+                       w_partials, w_taps_t, nullptr, 0, N, C, D, H, W, stream);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

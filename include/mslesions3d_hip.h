@@ -582,6 +582,26 @@ int msl_augment_fit_mc(const float* arena_img, const short* arena_seg, long long
 int msl_augment_window_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
                           const long long* table, int n_cases, const double* params, const int* windows, int N, int T0,
                           int T1, int T2, float* dst_img, short* dst_seg, void* stream);
+/* Separable warps (datasets.zoom_table / grid_table, devicedata.WarpStage / warp_numpy).
+ * msl_augment_warp_mc: msl_augment_window_mc's arenas, table, (N,32) f64 rows, outputs and zero rows (1 <= C <= 4), with
+ * windows null meaning the centred fit of msl_augment_fit_mc.  A row with [7] = 0 is the permuted copy of those two entry
+ * points, bit for bit (intensity operations included).  A row with [7] = 2 is a warp: [8] is the element offset of the
+ * sample's three coordinate tables in coords (device, coords_len doubles): n'0 + n'1 + n'2 doubles for the permuted case
+ * shape n', axis 0 first; [20] the boundary (0 reflect, 1 nearest, 2 constant) and [21..] the intensity operations as in
+ * msl_augment_affine's rows.  Output voxel o maps to q = clamp(o + d, 0, n' - 1) and samples the permuted case at the
+ * coordinate (t_0[q_0], t_1[q_1], t_2[q_2]): scipy's boundary map, taps and weights as msl_augment_affine forms them
+ * from a coordinate (scipy.ndimage.map_coordinates), order 1 for every image plane and order 0 for the mask, then the
+ * intensity operations.  One difference: under boundary 1 the weights come from the coordinate as it is and only the
+ * taps are clamped, which is scipy's "nearest" to the bit (msl_regrid's rule); msl_augment_affine clamps the coordinate,
+ * which rounds to another f32 at half-integer coordinates past an end - a zoom's tables hold those.  Any other [7] (an affine's 1 among them), an invalid case or axis list, or tables that do
+ * not lie inside [0, coords_len) write zeros to the row.  Taps are clamped into the axis whatever the coordinate is: a
+ * non-finite table value is outside the contract but reads inside the case.  Every output voxel is written exactly
+ * once: no memset, no atomics.  -1 (nothing launched, nothing written): a null pointer other than windows, a size or
+ * coords_len < 1, C outside 1..4.  -2: N > 65535 or T0 * T1 >= 2^31 - 4. */
+int msl_augment_warp_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                        const long long* table, int n_cases, const double* params, const double* coords,
+                        long long coords_len, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
+                        short* dst_seg, void* stream);
 
 /* ---- native grid -> LPI at 1 mm (csrc/datapipe.hip, devicedata.LesionCache / LesionPredictFeed)
  * msl_regrid: datasets.regrid of one case, bit for bit.  src_img (C,n0,n1,n2) f32 with 1 <= C <= 4, src_seg (n0,n1,n2)

@@ -149,6 +149,7 @@ _SIGNATURES = {
     "msl_foreground_box_mc": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "msl_augment_fit_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_augment_window_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "msl_augment_warp_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _P, _Q, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_regrid": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "msl_boxes_to_case": (_I, [_P, _P, _P, _I, _P, _P]),
     "msl_draw_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P]),

@@ -16,6 +16,8 @@
 //               atomics, then one workgroup drops flat components and writes the packed targets of msl_multibox_match.
 //   regrid    : a native case onto the LPI 1 mm grid (signed axis permutation + per-axis step), bit-identical to
 //               datasets.regrid; at the end of this file
+//   warp      : zoom / grid distortion of a ragged case through three per-axis coordinate tables (msl_augment_warp_mc,
+//               behind the fit kernel), bit-identical to scipy.ndimage.map_coordinates on their meshgrid
 // Launch boundaries on one stream are the only hand-offs between workgroups, except the union-find links, which are
 // read with agent-scope atomic loads and written with atomicMin (the result does not depend on the order).
 #include "common.hpp"
@@ -1026,6 +1028,193 @@ int augment_mc(const float* arena_img, const short* arena_seg, long long seg_ele
   return MSL_OK;
 }
 
+// ---- separable warp (zoom / grid distortion): msl_augment_warp_mc -------------------------------------------------------
+// Host mirrors: datasets._aug_zoom / _aug_griddistortion (scipy.ndimage.map_coordinates on np.meshgrid(t0, t1, t2)) and
+// devicedata.warp_numpy.  The arenas, the table, the rows and the outputs are fit_kernel's; a row with [7] = 2 carries at
+// [8] the element offset of its three coordinate tables in `coords` (n'0 + n'1 + n'2 doubles for the permuted shape n')
+// and at [20] the boundary.  Output voxel o reads voxel q = clamp(o + d, 0, n' - 1) of the warped case, which samples the
+// permuted case at (t0[q0], t1[q1], t2[q2]): from the coordinate on, affine_kernel's arithmetic.
+//
+// One wave per output row, a lane per voxel of it (x = lane, lane + 64, ...): q0, q1, their two table reads, boundary
+// maps, tap indices and weights are the same for the whole row, so they are formed from a wave-uniform row index
+// (readfirstlane) once per row, as are the four tap-row bases; along the row consecutive lanes read consecutive
+// elements of t2 and store consecutive voxels.  A row with [7] = 0 is the permuted copy of fit_kernel (its values, by
+// the same index arithmetic), any other row is written as zeros.
+constexpr int WARP_WAVES = DP_THREADS / 64;  // output rows per workgroup
+
+// floor(cc) / floor(cc + 0.5) as the integer map_tap clamps, itself clamped to [-2, len] as a double first (map_tap maps
+// everything below 0 and above len - 1 as it maps -2 and len under boundaries 1 and 2, and reflect leaves [-1, len - 1]):
+// no coordinate, a non-finite one included, becomes an undefined conversion or an overflowing + 1
+__device__ __forceinline__ long long warp_tap_base(double fl, int len) {
+  return !(fl >= -2.0) ? -2LL : (fl > (double)len ? (long long)len : (long long)fl);
+}
+
+struct WarpAxis {  // one axis of one coordinate: order-1 taps and weights, the order-0 tap, outside under "zeros"
+  int i1[2], i0;
+  double w[2];
+  bool outside;
+};
+
+// Boundary 1 is "nearest" as scipy computes it, msl_regrid's form: the taps are clamped into the axis and the weights are
+// taken from the coordinate as it is (past either end both taps are the end voxel, weights (1 - x, x)).  affine_kernel
+// clamps the coordinate instead (weights (1, 0) there): the same sum up to its last f64 bit, another f32 where that sum
+// is a tie - and a zoom's table is full of half-integer coordinates, which a rotation's never are.
+__device__ __forceinline__ WarpAxis warp_axis(double c, int len, int mode) {
+  WarpAxis r;
+  const double cc = mode == 1 ? c : map_boundary(c, len, mode);
+  r.outside = mode == 2 && !(cc > -1.0);
+  const double fl = floor(cc);
+  const long long st = warp_tap_base(fl, len);
+  const double x = cc - fl;
+  r.w[0] = 1.0 - x;
+  r.w[1] = 1.0 - r.w[0];
+  r.i1[0] = map_tap(st, len, mode);
+  r.i1[1] = map_tap(st + 1, len, mode);
+  r.i0 = map_tap(warp_tap_base(floor(cc + 0.5), len), len, mode);
+  return r;
+}
+
+template <int C>
+__global__ __launch_bounds__(DP_THREADS) void warp_kernel(
+    const float* __restrict__ src_img, const short* __restrict__ src_seg, long long seg_elems,
+    const long long* __restrict__ table, int n_cases, const double* __restrict__ params,
+    const double* __restrict__ coords, long long coords_len, const int* __restrict__ windows, int T0, int T1, int T2,
+    float* __restrict__ dst_img, short* __restrict__ dst_seg) {
+  const int lane = threadIdx.x & 63;
+  // wave-uniform: everything derived from it alone is computed once per row (T0 * T1 fits an int: checked at launch)
+  const int rowi = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WARP_WAVES + (threadIdx.x >> 6)));
+  if ((long long)rowi >= (long long)T0 * T1) return;
+  const int n = blockIdx.y;
+  const int oc0 = rowi / T1, oc1 = rowi % T1;
+  const long long TV = (long long)T0 * T1 * T2;
+  float* di = dst_img + (long long)n * C * TV + (long long)rowi * T2;
+  short* dsg = dst_seg + (long long)n * TV + (long long)rowi * T2;
+  const double* p = params + (size_t)n * AFFINE_STRIDE;
+  const int cs = (int)p[0];
+  int ax[3], rev[3];
+  bool ok = cs >= 0 && cs < n_cases && (p[7] == 0.0 || p[7] == 2.0);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ax[a] = (int)p[1 + a];
+    rev[a] = (int)p[4 + a];
+    ok = ok && ax[a] >= 0 && ax[a] < 3;
+  }
+  ok = ok && ax[0] != ax[1] && ax[0] != ax[2] && ax[1] != ax[2];
+  long long coff = 0, sn[3] = {1, 1, 1};
+  if (ok) {  // rejected on the host; never read out of bounds
+    coff = table[(long long)cs * 4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) sn[a] = table[(long long)cs * 4 + 1 + a];
+    ok = coff >= 0 && sn[0] > 0 && sn[1] > 0 && sn[2] > 0 && sn[0] < (1 << 20) && sn[1] < (1 << 20) && sn[2] < (1 << 20);
+    ok = ok && coff + sn[0] * sn[1] * sn[2] <= seg_elems;
+  }
+  const bool warp = p[7] == 2.0;
+  long long toff = 0;
+  if (ok && warp) {  // the three tables lie inside [0, coords_len): the sizes are below 2^20 each, so the sum is exact
+    ok = p[8] >= 0.0 && p[8] <= (double)coords_len;
+    if (ok) {
+      toff = (long long)p[8];
+      ok = toff + sn[0] + sn[1] + sn[2] <= coords_len;
+    }
+  }
+  if (!ok) {
+    for (int x = lane; x < T2; x += 64) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) di[c * TV + x] = 0.0f;
+      dsg[x] = 0;
+    }
+    return;
+  }
+  const long long V = sn[0] * sn[1] * sn[2];
+  const float* si = src_img + (long long)C * coff;  // plane c at si + c * V
+  const short* ss = src_seg + coff;
+  const long long sstride[3] = {sn[1] * sn[2], sn[2], 1LL};
+  const int T[3] = {T0, T1, T2};
+  int dims[3], dsh[3];  // permuted shape n' and the shift d (windows null: the centred fit's)
+  long long pst[3];
+  long long base = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    dims[a] = (int)sn[ax[a]];
+    dsh[a] = windows ? windows[3 * (long long)n + a]
+                     : (dims[a] < T[a] ? -((T[a] - dims[a]) / 2) : dims[a] / 2 - T[a] / 2);
+    pst[a] = rev[a] ? -sstride[ax[a]] : sstride[ax[a]];
+    if (rev[a]) base += (long long)(dims[a] - 1) * sstride[ax[a]];
+  }
+  const int q0 = fit_src<true>(oc0, dsh[0], dims[0]), q1 = fit_src<true>(oc1, dsh[1], dims[1]);
+  if (!warp) {  // permuted copy, the intensity arithmetic in the store
+    const long long rbase = base + q0 * pst[0] + q1 * pst[1];
+    for (int x = lane; x < T2; x += 64) {
+      const long long s = rbase + fit_src<true>(x, dsh[2], dims[2]) * pst[2];
+#pragma unroll
+      for (int c = 0; c < C; ++c) di[c * TV + x] = apply_ops(si[c * V + s], p);
+      dsg[x] = ss[s];
+    }
+    return;
+  }
+  const int mode = (int)p[20];
+  const double* t0 = coords + toff;
+  const double* t1 = t0 + dims[0];
+  const double* t2 = t1 + dims[1];
+  const WarpAxis a0 = warp_axis(t0[q0], dims[0], mode), a1 = warp_axis(t1[q1], dims[1], mode);
+  long long r1[2][2];  // the four tap rows of the image, the one of the mask
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) r1[a][b] = base + a0.i1[a] * pst[0] + a1.i1[b] * pst[1];
+  const long long r0 = base + a0.i0 * pst[0] + a1.i0 * pst[1];
+  const float cval = apply_ops(0.0f, p);  // scipy's constant: cval for image and mask alike, the operations still apply
+  for (int x = lane; x < T2; x += 64) {
+    const WarpAxis a2 = warp_axis(t2[fit_src<true>(x, dsh[2], dims[2])], dims[2], mode);
+    if (a0.outside || a1.outside || a2.outside) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) di[c * TV + x] = cval;
+      dsg[x] = 0;
+      continue;
+    }
+    double t[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) t[c] = 0.0;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+          const long long s = r1[a][b] + a2.i1[d] * pst[2];
+#pragma unroll
+          for (int c = 0; c < C; ++c) {  // per channel the corners in one order, each ((v * w0) * w1) * w2
+            double coeff = (double)si[c * V + s];
+            coeff = coeff * a0.w[a];
+            coeff = coeff * a1.w[b];
+            coeff = coeff * a2.w[d];
+            t[c] = t[c] + coeff;
+          }
+        }
+#pragma unroll
+    for (int c = 0; c < C; ++c) di[c * TV + x] = apply_ops((float)t[c], p);
+    dsg[x] = ss[r0 + a2.i0 * pst[2]];
+  }
+}
+
+int augment_warp(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+                 int n_cases, const double* params, const double* coords, long long coords_len, const int* windows, int N,
+                 int T0, int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
+  if (!arena_img || !arena_seg || !table || !params || !coords || !dst_img || !dst_seg || seg_elems <= 0 ||
+      coords_len <= 0 || C < 1 || C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
+    return MSL_ERR_ARG;
+  const long long rows = (long long)T0 * T1;
+  if (N > 65535 || rows > 0x7FFFFFFFLL - WARP_WAVES) return MSL_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((rows + WARP_WAVES - 1) / WARP_WAVES), N);
+  hipStream_t st = (hipStream_t)stream;
+  return msl::dispatch_int<1, 2, 3, 4>(C, [&](auto ch) {
+    MSL_LAUNCH(warp_kernel<decltype(ch)::value>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table,
+               n_cases, params, coords, coords_len, windows, T0, T1, T2, dst_img, dst_seg);
+    MSL_LAUNCH_CHECK();
+    return MSL_OK;
+  });
+}
+
 struct InstPairs {
   int n;
   int lo[INST_MAX_PAIRS], hi[INST_MAX_PAIRS];
@@ -1216,6 +1405,14 @@ int msl_augment_window_mc(const float* arena_img, const short* arena_seg, long l
   if (!windows) return MSL_ERR_ARG;
   return augment_mc<true>(arena_img, arena_seg, seg_elems, C, table, n_cases, params, windows, N, T0, T1, T2, dst_img,
                           dst_seg, stream);
+}
+
+int msl_augment_warp_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                        const long long* table, int n_cases, const double* params, const double* coords,
+                        long long coords_len, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
+                        short* dst_seg, void* stream) {
+  return augment_warp(arena_img, arena_seg, seg_elems, C, table, n_cases, params, coords, coords_len, windows, N, T0, T1,
+                      T2, dst_img, dst_seg, stream);
 }
 
 size_t msl_instance_boxes_workspace_bytes(int N) { return N > 0 && N <= 65535 ? inst_ws_bytes(N) : 0; }

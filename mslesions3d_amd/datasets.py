@@ -189,9 +189,105 @@ def _aug_scaleintensity(img, seg, rs, factors=0.1, prob=0.1):
     return (img, seg) if f is None else (img * np.float32(1.0 + f), seg)
 
 
+# RandZoomd / RandGridDistortiond (the registry's 'zoom' / 'griddistortion'): separable warps.  A warp of a (n0, n1, n2)
+# volume is three f64 tables t_a of length n_a; output voxel o samples the input at (t_0[o_0], t_1[o_1], t_2[o_2]) with
+# bilinear (image) / nearest (mask) interpolation.  MONAI is absent: the tables below are this project's contract,
+# restated from memory and NOT pinned.
+
+def zoom_table(n, z):
+    """RandZoom(keep_size=True) on one axis of n voxels: t[o] = (o - c) / z + c about the centre c = (n - 1) / 2, each
+    operation one rounded f64 operation; z > 1 magnifies."""
+    c = (n - 1) / 2
+    return (np.arange(n, dtype=np.float64) - c) / float(z) + c
+
+
+def grid_table(n, num_cells, steps):
+    """RandGridDistortion on one axis of n voxels: ``steps`` holds num_cells + 1 positive f64 values.  With cell =
+    max(n // num_cells, 1) and prev = 0.0, segments s = 0, 1, ... run while start = s * cell < n, with end =
+    min(start + cell, n): cur = float(n) where start + cell > n, else prev + cell * steps[min(s, num_cells)];
+    t[start:end] = np.linspace(prev, cur, end - start); prev = cur.  Every index is written (on a short axis too, where
+    MONAI's rule would leave a tail) and the last coordinate of a segment is the first of the next one.  The table is
+    non-decreasing on an axis without a remainder segment (n % cell == 0) and, with one, as long as the full segments end
+    at or below n; where they end beyond n the remainder segment runs backwards to n (MONAI's rule does the same, and
+    the rule is kept as it is: the resampling takes any table, only ``centres_to_augmented`` assumes a sorted one)."""
+    n, num_cells = int(n), int(num_cells)
+    steps = np.asarray(steps, dtype=np.float64).reshape(-1)
+    if n < 1 or num_cells < 1 or steps.size != num_cells + 1 or not (steps > 0).all():
+        raise ValueError(f"grid_table: n >= 1, num_cells >= 1 and num_cells + 1 positive steps expected, got {n}, "
+                         f"{num_cells}, {steps.tolist()}")
+    cell = max(n // num_cells, 1)
+    t = np.empty(n, dtype=np.float64)
+    prev, s = 0.0, 0
+    while s * cell < n:
+        start = s * cell
+        end = min(start + cell, n)
+        cur = float(n) if start + cell > n else prev + cell * steps[min(s, num_cells)]
+        t[start:end] = np.linspace(prev, cur, end - start)
+        prev = cur
+        s += 1
+    return t
+
+
+def _draw_zoom(rs, min_zoom=0.9, max_zoom=1.1, mode=("bilinear", "nearest"), padding_mode="border", prob=0.1):
+    """The random draws of ``_aug_zoom`` -> the zoom factor (f64, one for all axes), or None."""
+    if rs.rand() >= prob:
+        return None
+    return float(rs.uniform(min_zoom, max_zoom))
+
+
+def _draw_griddistortion(rs, num_cells=5, distort_limit=(-0.03, 0.03), mode=("bilinear", "nearest"),
+                         padding_mode="border", prob=0.1):
+    """The random draws of ``_aug_griddistortion`` -> the steps of axes 0, 1, 2 (three f64 arrays of num_cells + 1
+    values, 1 + uniform(lo, hi)), or None.  A number f as ``distort_limit`` means (-f, f)."""
+    lo, hi = distort_limit if isinstance(distort_limit, (tuple, list)) else (-distort_limit, distort_limit)
+    if abs(lo) >= 1 or abs(hi) >= 1:
+        raise ValueError(f"griddistortion: |distort_limit| must stay below 1 (steps are positive), got {distort_limit}")
+    if rs.rand() >= prob:
+        return None
+    return tuple(1.0 + rs.uniform(lo, hi, num_cells + 1) for _ in range(3))
+
+
+def _warp(img, seg, tables, mode, padding_mode):
+    """The (image, mask) pair sampled at ``np.meshgrid(t0, t1, t2, indexing="ij")``: per channel
+    ``scipy.ndimage.map_coordinates`` of the f32 channel, order 1 (bilinear) / 0 (nearest), cast back as ``_aug_affine``
+    casts."""
+    from scipy.ndimage import map_coordinates
+    pad = SCIPY_BOUNDARY[padding_mode]
+    coords = np.meshgrid(*tables, indexing="ij")
+    outs = []
+    for a, m in ((img, mode[0]), (seg, mode[1])):
+        order = 1 if m == "bilinear" else 0
+        outs.append(np.stack([map_coordinates(c.astype(np.float32), coords, order=order, mode=pad) for c in a]).astype(a.dtype))
+    return outs[0], outs[1]
+
+
+def _aug_zoom(img, seg, rs, min_zoom=0.9, max_zoom=1.1, mode=("bilinear", "nearest"), padding_mode="border", prob=0.1):
+    z = _draw_zoom(rs, min_zoom, max_zoom, mode, padding_mode, prob)
+    if z is None:
+        return img, seg
+    return _warp(img, seg, [zoom_table(n, z) for n in img.shape[1:]], mode, padding_mode)
+
+
+def _aug_griddistortion(img, seg, rs, num_cells=5, distort_limit=(-0.03, 0.03), mode=("bilinear", "nearest"),
+                        padding_mode="border", prob=0.1):
+    steps = _draw_griddistortion(rs, num_cells, distort_limit, mode, padding_mode, prob)
+    if steps is None:
+        return img, seg
+    return _warp(img, seg, [grid_table(n, num_cells, s) for n, s in zip(img.shape[1:], steps)], mode, padding_mode)
+
+
+def warp_tables(name, draw, shape, kw):
+    """The three tables of a drawn 'zoom' / 'griddistortion' (``DRAWS[name]``'s result) on a volume of ``shape``."""
+    if name == "zoom":
+        return [zoom_table(n, draw) for n in shape]
+    return [grid_table(n, kw.get("num_cells", 5), s) for n, s in zip(shape, draw)]
+
+
 AUGMENTATIONS = {"flip": _aug_flip, "rotate90": _aug_rotate90, "affine": _aug_affine,
+                 "zoom": _aug_zoom, "griddistortion": _aug_griddistortion,
                  "shiftintensity": _aug_shiftintensity, "scaleintensity": _aug_scaleintensity}
 DRAWS = {"flip": _draw_flip, "rotate90": _draw_rotate90, "affine": _draw_affine,
+         "zoom": _draw_zoom, "griddistortion": _draw_griddistortion,
          "shiftintensity": _draw_shiftintensity, "scaleintensity": _draw_scaleintensity}
 
 
@@ -230,6 +326,27 @@ def select_augmentations(names):
         raise ValueError(f"unknown augmentation(s) {sorted(unknown)}; known: {' '.join(dict.fromkeys(known))}")
     out = [(n.replace("translate", "affine").replace("scale", "affine"), kw) for n, kw in REFERENCE_AUGMENTATIONS if n in names]
     return out + [(n, kw) for n, kw in LESIONS_AUGMENTATIONS if n in names]
+
+
+# the registry's two spatial transforms that neither list of train.py binds (datasets.py:99-119): parameters of this
+# project's choosing, MONAI's defaults for the ranges
+WARP_AUGMENTATIONS = [("zoom", {"min_zoom": 0.9, "max_zoom": 1.1, "padding_mode": "border", "prob": 0.5}),
+                      ("griddistortion", {"num_cells": 5, "distort_limit": 0.03, "padding_mode": "border", "prob": 0.5})]
+INTENSITY_NAMES = ("shiftintensity", "scaleintensity")
+
+
+def select_training_augmentations(names):
+    """What ``train.py -a`` binds: ``select_augmentations`` for the reference's names, unchanged, plus the entries of
+    ``WARP_AUGMENTATIONS`` that were asked for, in that list's order, behind the flips / rot90s / affines and in front of
+    the intensity operations (the order ``devicedata.sample_params`` takes).  Unknown names raise ValueError."""
+    warp = [n for n, _ in WARP_AUGMENTATIONS]
+    known = [n for n, _ in REFERENCE_AUGMENTATIONS + LESIONS_AUGMENTATIONS] + warp
+    unknown = set(names) - set(known)
+    if unknown:
+        raise ValueError(f"unknown augmentation(s) {sorted(unknown)}; known: {' '.join(dict.fromkeys(known))}")
+    out = select_augmentations([n for n in names if n not in warp])
+    at = next((k for k, (n, _) in enumerate(out) if n in INTENSITY_NAMES), len(out))
+    return out[:at] + [(n, kw) for n, kw in WARP_AUGMENTATIONS if n in names] + out[at:]
 
 
 def _load(path_noext):
@@ -616,8 +733,11 @@ def centres_to_augmented(centres, shape, perm, stages=()):
     """Voxel positions (K, 3) f64 of a case of ``shape`` -> the same points in the frame of the augmented case.  ``perm``
     = (ax, rev) and ``stages`` come from ``devicedata.sample_params(..., ragged=True)``, the parameters both routes share.
     Signed permutation: c'_a = n'_a - 1 - c[ax_a] where rev_a, else c[ax_a], with n'_a = shape[ax_a].  Then per affine
-    stage, in order, q = solve(M, c' - offset): the inverse of "output voxel q samples at M q + offset" (f64).  Stages
-    without a matrix (None, intensity operations) do not move a point."""
+    stage, in order, q = solve(M, c' - offset): the inverse of "output voxel q samples at M q + offset" (f64).  Per warp
+    stage (``tables``: output voxel q samples at t_a[q_a]), per axis the smallest real q in [0, n' - 1] with t(q) = c',
+    t being the table under linear interpolation: i = np.searchsorted(t, c', "left"), q = i - 1 + (c' - t[i - 1]) /
+    (t[i] - t[i - 1]), and 0 / n' - 1 where c' lies at or below t[0] / above t[n' - 1].  Stages without a matrix or tables
+    (None, intensity operations) do not move a point."""
     c = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
     ax, rev = perm
     out = np.empty_like(c)
@@ -627,7 +747,22 @@ def centres_to_augmented(centres, shape, perm, stages=()):
         if hasattr(st, "matrix") and out.shape[0]:
             out = np.linalg.solve(np.asarray(st.matrix, dtype=np.float64),
                                   (out - np.asarray(st.offset, dtype=np.float64)).T).T
+        elif hasattr(st, "tables") and out.shape[0]:
+            out = np.stack([_table_inverse(st.tables[a], out[:, a]) for a in range(3)], 1)
     return out
+
+
+def _table_inverse(table, c):
+    """``centres_to_augmented``'s rule on one axis: the smallest q in [0, n - 1] with t(q) = c, clamped."""
+    t = np.asarray(table, dtype=np.float64)
+    n = t.size
+    if n == 1:
+        return np.zeros(c.shape[0])
+    i = np.searchsorted(t, c, "left")  # t[i - 1] < c <= t[i]
+    k = np.clip(i, 1, n - 1)
+    with np.errstate(divide="ignore", invalid="ignore"):  # (a flat interval is only met where the clamp decides)
+        q = (k - 1) + (c - t[k - 1]) / (t[k] - t[k - 1])
+    return np.clip(np.where(i == 0, 0.0, np.where(i >= n, n - 1.0, q)), 0.0, n - 1.0)
 
 
 def patch_origin(rs, shape, patch, centres, foreground):

@@ -20,7 +20,9 @@ C > 1 input sequences is cached channel-planar; every C, one sequence included, 
 carries an affine is uploaded on its native grid and put on the LPI 1 mm grid by msl_regrid (``regrid_device``, the
 device form of ``datasets.regrid``, bit for bit) in front of the foreground box.  A module with a ``patch_size`` (patch
 training) gets one sampled window per case and epoch instead of the fit, and validation tiles
-(msl_augment_window_mc with the origins ``datasets.patch_origin`` / ``datasets.view_plan`` give on the host).
+(msl_augment_window_mc with the origins ``datasets.patch_origin`` / ``datasets.view_plan`` give on the host).  A batch in
+which some sample drew a zoom / griddistortion (a ``WarpStage``: three per-axis coordinate tables, DESIGN.md section
+4.13) goes through msl_augment_warp_mc instead, on either route; ``DeviceCache`` refuses the two names.
 """
 from collections import namedtuple
 
@@ -31,7 +33,7 @@ from os.path import join as pjoin
 from . import _lib
 from ._lib import ptr
 from .datasets import (SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset, centres_to_augmented,
-                       draw_augmentations, patch_origin, regrid_plan, sample_rng, view_plan)
+                       draw_augmentations, patch_origin, regrid_plan, sample_rng, view_plan, warp_tables)
 
 PARAM_STRIDE = 16  # f64 per sample of msl_augment_resample
 AFFINE_STRIDE = 32  # f64 per sample of msl_augment_affine
@@ -44,6 +46,11 @@ NEAREST_UNCLAMPED = 3  # affine_numpy only: the boundary rule of msl_regrid (sci
 AffineStage = namedtuple("AffineStage", "matrix offset boundary")
 # kind (OP_ADD / OP_MUL) and the np.float32 operand of the host's one f32 operation
 IntensityOp = namedtuple("IntensityOp", "kind value")
+# a stage msl_augment_warp_mc runs (zoom / griddistortion): three f64 coordinate tables, one per axis of the permuted
+# case (output voxel q samples at t_a[q_a]), and the boundary code
+WarpStage = namedtuple("WarpStage", "tables boundary")
+WARP_NAMES = ("zoom", "griddistortion")
+ROW_COPY, ROW_AFFINE, ROW_WARP = 0.0, 1.0, 2.0  # field [7] of a parameter row
 
 
 def _stream(dev):
@@ -141,7 +148,9 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
     list order: None (not drawn), (zoom, offset) in f64 for a diagonal affine with reflection padding (the stage
     msl_augment_resample runs), ``AffineStage`` for a rotating affine or another boundary, ``IntensityOp``.
     ``ragged`` (msl_augment_fit): a rot90 may change the shape, and every affine stage is an ``AffineStage`` computed
-    for the permuted shape."""
+    for the permuted shape.  A drawn zoom / griddistortion is a ``WarpStage`` with the tables of the permuted shape
+    (``ragged`` only; padding "border" unless the entry says otherwise); it is a resampling stage like an affine: behind
+    the flips / rot90s, in front of the intensity operations."""
     axis, rev = [0, 1, 2], [0, 0, 0]
     stages = []
     n_ops = 0
@@ -163,6 +172,19 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
             else:  # flips / rot90s come first: the permutation is final, and it keeps the shape unless ragged
                 stages.append(AffineStage(*affine_matrix(tuple(shape[a] for a in axis), *d), BOUNDARY[pad]))
             continue
+        if name in WARP_NAMES:
+            if n_ops:
+                raise NotImplementedError("device pipeline: a warp stage after an intensity operation")
+            if not ragged:
+                raise NotImplementedError("device pipeline: zoom / griddistortion on the example cache")
+            t = augmentations[k] if augmentations is not None else name
+            kw = {} if isinstance(t, str) else t[1]
+            if d is None:
+                stages.append(None)
+            else:  # the permutation is final here, as for an affine
+                stages.append(WarpStage(warp_tables(name, d, tuple(shape[a] for a in axis), kw),
+                                        BOUNDARY[kw.get("padding_mode", "border")]))
+            continue
         if name in ("shiftintensity", "scaleintensity"):
             n_ops += 1
             if n_ops > AFFINE_MAX_OPS:
@@ -177,7 +199,7 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
         if n_ops:
             raise NotImplementedError("device pipeline: a flip / rot90 after an intensity operation")
         if stages:
-            raise NotImplementedError("device pipeline: a flip / rot90 after an affine stage")
+            raise NotImplementedError("device pipeline: a flip / rot90 after an affine stage")  # (a warp stage counts)
         if d is None:
             continue
         if name == "flip":
@@ -227,10 +249,37 @@ def affine_numpy(vol, matrix, offset, order, boundary, output_shape=None):
     either end both taps are the end voxel with weights (1 - x, x).  Boundary 1 clamps the coordinate itself, which
     gives (1, 0) there: the same value up to the last f64 bit of the sum, and so another f32 wherever that sum is a tie
     (half-integer coordinates: a step of 0.5 or 2.5).  msl_augment_affine is boundary 1; DESIGN.md section 4.10."""
-    dims = vol.shape
-    odims = dims if output_shape is None else tuple(int(n) for n in output_shape)
+    odims = vol.shape if output_shape is None else tuple(int(n) for n in output_shape)
     o = [x.astype(np.float64) for x in np.meshgrid(*(np.arange(n) for n in odims), indexing="ij")]
     M, off = np.asarray(matrix, dtype=np.float64), np.asarray(offset, dtype=np.float64)
+    coords = []
+    for h in range(3):
+        c = np.zeros(odims)
+        for k in range(3):
+            c = c + o[k] * M[h, k]
+        coords.append(c + off[h])
+    return _sample_numpy(vol, coords, order, boundary)
+
+
+def warp_numpy(vol, tables, order, boundary):
+    """Host mirror of msl_augment_warp_mc's resample of one (D, H, W) volume, operation by operation in f64: output voxel
+    o has the coordinate (t_0[o_0], t_1[o_1], t_2[o_2]); from there the boundary map, the taps and the weights of
+    ``affine_numpy`` (scipy 1.15's NI_GeometricTransform, which ``scipy.ndimage.map_coordinates`` runs as well).
+    ``boundary`` is a ``BOUNDARY`` code; "border" (1) is computed as scipy computes "nearest", ``affine_numpy``'s
+    ``NEAREST_UNCLAMPED``: a zoom's tables hold half-integer coordinates, the ties at which the clamped form of
+    msl_augment_affine rounds to another f32."""
+    tables = [np.asarray(t, dtype=np.float64) for t in tables]
+    if tuple(t.shape for t in tables) != tuple((n,) for n in vol.shape):
+        raise ValueError(f"warp_numpy: one table per axis of {vol.shape} expected, got {[t.shape for t in tables]}")
+    return _sample_numpy(vol, np.meshgrid(*tables, indexing="ij"), order,
+                         NEAREST_UNCLAMPED if boundary == BOUNDARY["border"] else boundary)
+
+
+def _sample_numpy(vol, coords, order, boundary):
+    """The tail ``affine_numpy`` and ``warp_numpy`` share: ``vol`` sampled at the three f64 coordinate arrays (one output
+    grid), from the boundary map on."""
+    dims = vol.shape
+    odims = coords[0].shape
 
     def reflect(c, n):
         c = np.array(c, dtype=np.float64)
@@ -249,10 +298,7 @@ def affine_numpy(vol, matrix, offset, order, boundary, output_shape=None):
 
     cc, outside = [], np.zeros(odims, dtype=bool)
     for h in range(3):
-        c = np.zeros(odims)
-        for k in range(3):
-            c = c + o[k] * M[h, k]
-        c = c + off[h]
+        c = coords[h]
         n = dims[h]
         if boundary == 0:
             c = reflect(c, n)
@@ -347,6 +393,8 @@ class DeviceCache:
         self.dataset, self.device = dataset, torch.device(device)
         self.n_classes, self.batch_size = int(dataset.n_classes), int(dataset.batch_size)
         self.augmentations = list(dataset.train_dataset.augmentations)
+        if any((t if isinstance(t, str) else t[0]) in WARP_NAMES for t in self.augmentations):
+            raise NotImplementedError("device pipeline: zoom / griddistortion on the example cache")
         tr, te = dataset.train_dataset, dataset.test_dataset
         if dataset.world_size > 1:
             val_idx = ShardSampler(len(te), dataset.rank, dataset.world_size, False, dataset.random_state).indices()
@@ -570,13 +618,43 @@ def _box_stage(dataset, N, shape, capacity, dev, max_runs_per_image=MAX_RUNS_PER
 def fit_rows(cases, per_sample):
     """-> (N, AFFINE_STRIDE) f64 rows of one msl_augment_fit launch: per sample its case and the (perm, stages) of
     ``sample_params(..., ragged=True)``: at most one affine stage, then the intensity operations."""
+    rows, coords = warp_rows(cases, per_sample)
+    if coords.size:
+        raise ValueError("fit_rows: a sample drew a warp stage; warp_rows returns its tables with the rows")
+    return rows
+
+
+def warp_rows(cases, per_sample):
+    """-> ((N, AFFINE_STRIDE) f64 rows, f64 coords) of one msl_augment_warp_mc launch: ``fit_rows``'s rows, where a
+    sample whose one resampling stage is a ``WarpStage`` has [7] = ROW_WARP, at [8] the offset of its three tables in
+    ``coords`` (concatenated, axis 0 first) and at [20] the boundary.  Without a warp drawn ``coords`` is empty and the rows
+    are those of msl_augment_fit_mc / msl_augment_window_mc."""
     rows = np.zeros((len(cases), AFFINE_STRIDE), dtype=np.float64)
+    coords, at = [], 0
     for n, (case, (perm, stages)) in enumerate(zip(cases, per_sample)):
         geo = [st for st in stages if not isinstance(st, IntensityOp)]
         if len(geo) > 1:
             raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
-        rows[n] = affine_row(case, perm, geo[0] if geo else None, [st for st in stages if isinstance(st, IntensityOp)])
-    return rows
+        st = geo[0] if geo else None
+        ops = [x for x in stages if isinstance(x, IntensityOp)]
+        if isinstance(st, WarpStage):
+            rows[n] = affine_row(case, perm, None, ops)
+            rows[n, 7], rows[n, 8], rows[n, 20] = ROW_WARP, at, st.boundary
+            coords += [np.asarray(t, dtype=np.float64) for t in st.tables]
+            at += sum(len(t) for t in st.tables)
+        else:
+            rows[n] = affine_row(case, perm, st, ops)
+    return rows, (np.concatenate(coords) if coords else np.zeros(0, dtype=np.float64))
+
+
+def check_ragged_pipeline(augmentations):
+    """What ``LesionCache`` refuses at construction, drawn or not: more than one resampling stage (affine / zoom /
+    griddistortion: a resample of a resample of a ragged case would need a ragged intermediate) and the order limits of
+    ``sample_params``.  NotImplementedError."""
+    names = [(t if isinstance(t, str) else t[0]) for t in augmentations]
+    if sum(n == "affine" or n in WARP_NAMES for n in names) > 1:
+        raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
+    sample_params([(n, None) for n in names], (1, 1, 1), augmentations, ragged=True)
 
 
 def plan_row(plan):
@@ -649,8 +727,11 @@ class LesionCache:
     yields ``validation_step`` batches.  At construction every case is uploaded once (a case with an affine on its
     native grid, then regridded by msl_regrid: ``plans`` holds its ``RegridPlan``, None otherwise), boxed by
     msl_foreground_box_mc (the six ints are the build's only read-back), cropped into the arena and normalised there; the
-    cropped cases are staged in tensors of their own until the arena's size is known.  A pipeline with two affine
-    stages raises NotImplementedError (a resample of a resample of a ragged case would need a ragged intermediate).
+    cropped cases are staged in tensors of their own until the arena's size is known.  A pipeline with two resampling
+    stages (affine / zoom / griddistortion entries, ``check_ragged_pipeline``) raises NotImplementedError (a resample of
+    a resample of a ragged case would need a ragged intermediate).  A batch in which a sample drew a warp is written by
+    msl_augment_warp_mc (the tables ride behind the rows in the batch's one pinned upload); every other batch by the
+    launch it always had.
 
     With C = len(dataset.input_images) a case is C contiguous f32 planes starting at element C * offset of the image
     arena (the mask arena and the table are the same for every C): boxed as the union of the channels by
@@ -673,10 +754,7 @@ class LesionCache:
         self.target = tuple(dataset.spatial_size) if self.patch is None else tuple(self.patch)
         self.channels = C = len(dataset.input_images)
         self.augmentations = list(dataset.train_dataset.augmentations)
-        names = [(t if isinstance(t, str) else t[0]) for t in self.augmentations]
-        if names.count("affine") > 1:
-            raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
-        sample_params([(n, None) for n in names], (1, 1, 1), self.augmentations, ragged=True)  # the order limits
+        check_ragged_pipeline(self.augmentations)
         if dataset.segmentation_mode not in ("instances", "binary"):
             raise NotImplementedError(f"LesionCache: no device box stage for segmentation mode "
                                       f"{dataset.segmentation_mode!r}")
@@ -798,7 +876,21 @@ class LesionCache:
 
     def _run(self, slots, per_sample, b, windows=None):
         stream = _stream(self.device)
-        rows = fit_rows(slots, per_sample)
+        rows, coords = warp_rows(slots, per_sample)
+        if coords.size:  # some sample drew a warp.  One upload: the f64 rows, the tables, then the int32 origins
+            N = len(slots)
+            packed = np.zeros(rows.size + coords.size + (0 if windows is None else (3 * N + 1) // 2), dtype=np.float64)
+            packed[:rows.size] = rows.reshape(-1)
+            packed[rows.size:rows.size + coords.size] = coords
+            if windows is not None:
+                packed[rows.size + coords.size:].view(np.int32)[:3 * N] = np.asarray(windows, dtype=np.int32).reshape(-1)
+            pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
+            _lib.call("msl_augment_warp_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels,
+                      ptr(self.table), len(self.shapes), ptr(pd), pd.data_ptr() + 8 * rows.size, coords.size,
+                      None if windows is None else pd.data_ptr() + 8 * (rows.size + coords.size), N, *self.target,
+                      ptr(b["img"]), ptr(b["seg"]), stream)
+            b["box"].launch(b["seg"], stream)
+            return
         if windows is not None:  # one upload: the f64 rows, then the (N, 3) int32 origins in the doubles behind them
             N = len(slots)
             packed = np.zeros(rows.size + (3 * N + 1) // 2, dtype=np.float64)

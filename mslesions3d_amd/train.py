@@ -38,7 +38,8 @@ def build_parser():
     p.add_argument('-maxos', '--max_object_size', type=int, default=14)
     p.add_argument('--alpha', type=float, default=1.)
     p.add_argument('-a', '--augmentations', type=str, nargs='*', default=[],
-                   help='flip rotate90 translate scale (example recipe); affine shiftintensity scaleintensity (train_lesions)')
+                   help='flip rotate90 translate scale (example recipe); affine shiftintensity scaleintensity (train_lesions); '
+                        'zoom griddistortion (separable warps, one resampling stage per run with -dm lesions -c 1)')
     p.add_argument('-ld', '--logdir', type=str, default=r'../logs/artificial_dataset')
     p.add_argument('-nw', '--num_workers', type=int, default=0)
     p.add_argument('-wm', '--width_mult', type=float, default=1.)
@@ -181,7 +182,7 @@ def example(args):
     its shard of the cases (``datasets.ShardSampler``; BatchNorm statistics and the loss normaliser per replica), exchanges
     gradients through ``FusedTrainer``'s bucketed RCCL all-reduce overlapped with the backward pass, validates its shard of
     the validation cases, and rank 0 writes metrics and checkpoints.  N = 1 is the reference's single-GPU run."""
-    from .datasets import ExampleDataset, LesionsDataModule, select_augmentations
+    from .datasets import ExampleDataset, LesionsDataModule, select_training_augmentations
     from .ssd3d import LSSD3D
     from .trainer import FusedTrainer
     input_images = input_images_of(args)  # before the first GPU call: a refused command line touches no device
@@ -201,7 +202,7 @@ def example(args):
     layers = [int(x) for x in args.prediction_layers.split()]
     aspect_ratios = {l: [1.] for l in layers}
     scales = {int(k): v for k, v in args.scales.items()}
-    augmentations = select_augmentations(args.augmentations)  # train.py:132-145, :196-205
+    augmentations = select_training_augmentations(args.augmentations)  # train.py:132-145, :196-205, + the warps
     lesions = getattr(args, "data_module", "example") == "lesions"
     if lesions:
         dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), subject=args.subject,

@@ -5,7 +5,10 @@ against a float64 reference with derived bounds.  Likewise the fp32 pointwise co
 test_pw_random_shapes here compare with torch fp32 under stated tolerances; tests/test_gpu_pw.py walks every dispatch branch and
 template instantiation of csrc/pwconv.hip / csrc/pwfused.hip against the float64 reference of tests/pw_ref.py.  And the stem
 (msl_stem_conv_*): the stem tests here compare with torch fp32 at a few shapes; tests/test_gpu_stem.py walks every dispatch
-branch and template instantiation of csrc/stem.hip against the float64 reference of tests/stem_ref.py."""
+branch and template instantiation of csrc/stem.hip against the float64 reference of tests/stem_ref.py.  And the optimiser stage
+(msl_adam_step, msl_grad_reduce_*, msl_nan_flag*, msl_fill_u32): test_adam_matches_torch, test_grad_reduce_batch_all_kinds_in_one_launch
+and test_nan_flag here are smoke-level; tests/test_gpu_optim.py walks every path of csrc/optim.hip - the grid-stride passes, both
+fold forms in the search and the indexed launch, every kind and loop boundary, the refusals - against tests/optim_ref.py."""
 import numpy as np
 import pytest
 import torch

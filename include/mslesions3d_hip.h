@@ -165,6 +165,12 @@ int msl_dwconv_bwd_weight_finalize(const double* w_partials, int num_partials, f
 int msl_dwconv_bwd_weight_num_partials(int N, int C, int D, int H, int W, int stride);
 int msl_dwconv_bwd_weight(const float* dy, const float* x, const float* in_scale, const float* in_shift, float* dw,
                           double* partials, int N, int C, int D, int H, int W, int stride, void* stream);
+/* Which kernel family a depthwise call of this shape runs (host arithmetic only, nothing is launched) - for tests / DESIGN.md.
+ * op: 0 statistics-free forward, 1 stride-1 bwd-data as the flipped forward, 2 bwd-data, 3 bwd-weight; bf16 != 0: bf16 storage.
+ * Returns 0 none, 1 wave, 2 rows-eval, 3 small-eval, 4 stream, 5 resident, 6 naive, 7 tiled (bf16), 8 tiled stride-2 bwd-data
+ * (bf16), 9 stride-2 patch, 10 vectorised bwd-data, 11 generic bwd-data, 12 wave-per-chunk bwd-weight; MSL_ERR_ARG for an unknown
+ * op, a bf16 flag other than 0 / 1, or a shape the entry points refuse. */
+int msl_dwconv_route_kind(int op, int bf16, int N, int C, int D, int H, int W, int stride);
 
 /* ---- pointwise Conv3d(Cin,Cout,k1) = per-image GEMM on MFMA : Block.conv2, mobilenet.py:40,45 ------------- */
 int msl_pwconv_fwd_num_partials(int N, int Cin, int Cout, int S);

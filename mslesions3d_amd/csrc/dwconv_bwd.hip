@@ -517,6 +517,13 @@ void launch_s2_fused(const T* dy, const float* w, const T* y_prev, const float* 
 
 extern "C" {
 
+// (int)DwKind of the route a call of this shape takes: host arithmetic only, nothing is launched (tests name their cases by it)
+int msl_dwconv_route_kind(int op, int bf16, int N, int C, int D, int H, int W, int stride) {
+  if (op < (int)DwOp::Fwd || op > (int)DwOp::BwdWeight || (bf16 != 0 && bf16 != 1)) return MSL_ERR_ARG;
+  if (!dw_args_ok(N, C, D, H, W, stride)) return MSL_ERR_ARG;
+  return (int)dw_route((DwOp)op, bf16 != 0, N, C, D, H, W, stride, false, false).kind;
+}
+
 // dy (N,C,OD,OH,OW) -> g_in (N,C,D,H,W); accumulate != 0 adds into g_in
 int msl_dwconv_bwd_data(const float* dy, const float* w, float* g_in, int N, int C, int D, int H, int W,
                         int stride, int accumulate, void* stream) {

@@ -76,6 +76,13 @@ def test_pure_host_entry_points():
     assert lib.msl_dwconv_bwd_weight_num_partials(4, 64, 32, 32, 32, 2) == 4 * 4
     assert lib.msl_dwconv_bwd_weight_num_partials(4, 256, 8, 8, 8, 1) == 4 * 2
     assert lib.msl_multibox_loss_var_workspace_bytes(4, 9344) == 4 * 9344 * 4 + 4 * 8
+    # the route query (op 2 bwd-data, 3 bwd-weight; the DwKind of csrc/dwroute.hpp) on config A's layers
+    assert lib.msl_dwconv_route_kind(2, 0, 4, 32, 64, 64, 64, 2) == 9     # block 1 bwd-data: the stride-2 patch kernel
+    assert lib.msl_dwconv_route_kind(2, 0, 4, 128, 16, 16, 16, 1) == 1    # L3 bwd-data: the wave kernel on flipped taps
+    assert lib.msl_dwconv_route_kind(3, 0, 4, 64, 32, 32, 32, 2) == 1     # block 2 weight gradient: wave
+    assert lib.msl_dwconv_route_kind(3, 0, 2, 512, 2, 2, 2, 1) == 12      # 64^3 config tail: wave-per-chunk
+    assert lib.msl_dwconv_route_kind(2, 1, 2, 8, 9, 24, 24, 1) == 7       # bf16 storage, no wave plane: LDS-tiled
+    assert lib.msl_dwconv_route_kind(5, 0, 4, 32, 64, 64, 64, 2) == -1 and lib.msl_dwconv_route_kind(2, 0, 0, 32, 64, 64, 64, 2) == -1
 
 
 def test_native_program_runner_covers_the_abi():

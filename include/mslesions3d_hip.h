@@ -622,6 +622,30 @@ int msl_augment_warp_mc(const float* arena_img, const short* arena_seg, long lon
 int msl_regrid(const float* src_img, const short* src_seg, int C, int n0, int n1, int n2, const double* plan, int m0,
                int m1, int m2, float* dst_img, short* dst_seg, void* stream);
 
+/* ---- MR acquisition stage (csrc/mraug.hip, devicedata.MRStageRunner / mr_tables) ----
+ * msl_augment_mr: Gaussian blur, multiplicative bias field and additive noise on a built batch, out of place: src and
+ * dst (N,C,D,H,W) f32, bit-identical to datasets.gaussian_smooth / bias_field / gaussian_noise.  All device tables:
+ * params (N,8) f64 per sample: [0] flags (1 blur + 2 bias + 4 noise), [1..3] the blur radii R_0..R_2 (clamped to 0..8),
+ * [4] the noise deviation (an f32 value), [5] [6] the Philox key words k0, k1 (32-bit values); taps (N,3,17) f32, axis a
+ * of sample n in [n][a][0 .. 2 R_a]; lattice (N,L,L,L) f32 with 2 <= L <= 9.  The host computes the taps and the lattice
+ * (datasets.gaussian_taps / bias_lattice): the device evaluates no exponential.
+ *   blur: three passes over axis 0, 1, 2 of every channel; each acc = 0.0 (f64), acc += (double)w[k] * (double)v[i+k-R]
+ *     for k ascending, a tap outside the axis contributing nothing, and one rounding to f32.  Axis 0 is a launch of its
+ *     own into the workspace; axes 1 and 2 are fused through an LDS tile with a halo of R.
+ *   bias: voxel o samples the lattice at x_a = o_a (L-1) / (n_a-1) in f64 (0 where n_a = 1) with the taps, weights and
+ *     eight-corner sum of msl_augment_affine (csrc/resample.hpp); field = (float)sum; v * field, one f32 multiply.
+ *   noise: Philox4x32-10 under key (k0,k1) of counter (d H W + h W + w, channel, 0, 0); S = the sum of the eight 16-bit
+ *     halves of the four output words; z = (float)(S - 262140) * f32(1 / sqrt(8 (2^32 - 1) / 12)); v + z * std: three
+ *     rounded f32 operations.
+ * Bias and noise are the epilogue of the last blur pass, or of the copy for a sample without blur; a sample that drew
+ * nothing is copied.  Every output voxel is written exactly once: no memset, no atomics.  Two launches on `stream`, no
+ * synchronisation.  workspace: msl_augment_mr_workspace_bytes(N,C,D,H,W) bytes (0 for sizes the entry point refuses).
+ * -1 (nothing launched): a null pointer, src == dst, a size < 1, L outside 2..9, a workspace too small.  -2 (nothing
+ * launched): D H W >= 2^32 (the counter's index word), N C > 65535. */
+size_t msl_augment_mr_workspace_bytes(int N, int C, int D, int H, int W);
+int msl_augment_mr(const float* src, const double* params, const float* taps, const float* lattice, int N, int C, int D,
+                   int H, int W, int L, float* dst, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- prediction overlays (csrc/overlay.hip, devicedata.LesionPredictFeed, predict.py -si 1) ----
  * Packed detections of N images: boxes (K,6) f32 corner boxes, labels (K) i64, scores (K) f32 on the device; offsets
  * (HOST, N + 1 ints, read during the call): image n owns rows offsets[n] .. offsets[n+1].  Both launch on `stream` and

@@ -283,12 +283,247 @@ def warp_tables(name, draw, shape, kw):
     return [grid_table(n, kw.get("num_cells", 5), s) for n, s in zip(shape, draw)]
 
 
+# RandGaussianSmoothd / RandBiasFieldd / RandGaussianNoised (the MR stage): resolution loss, coil
+# inhomogeneity and thermal noise, on the image only.  MONAI is absent: parameter names and default ranges follow it as
+# remembered, the arithmetic below is this project's contract and its parity is NOT pinned.  Every operation is exact
+# integer arithmetic, an f64 sum of exact products in a fixed order or one rounded f32 operation, so that msl_augment_mr
+# (csrc/mraug.hip) computes the same bits.  All channels of a sample share one blur and one bias field; the noise differs
+# per channel.  The three act on the FINISHED sample: ``_LesionCases`` draws them in list order and applies them behind
+# its fit / window, where the device route applies them to the built batch.
+
+MR_MAX_RADIUS = 8  # taps reach 4 sigma: sigma <= 2.0
+PHILOX_M0, PHILOX_M1, PHILOX_W0, PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+# the eight 16-bit halves of a Philox block are uniform on 0 .. 65535: mean 32767.5, variance (2^32 - 1) / 12 each
+NOISE_MEAN = 262140
+NOISE_SCALE = np.float32(1.0 / np.sqrt(8.0 * (2.0 ** 32 - 1.0) / 12.0))
+
+
+def gaussian_radius(sigma):
+    """R = int(4 sigma + 0.5); a sigma outside (0, 2.0] (R > 8) raises ValueError."""
+    sigma = float(sigma)
+    if not 0.0 < sigma <= 2.0:
+        raise ValueError(f"gaussiansmooth: sigma must lie in (0, 2.0] (a radius of at most {MR_MAX_RADIUS}), got {sigma}")
+    return int(4.0 * sigma + 0.5)
+
+
+def gaussian_taps(sigma):
+    """-> the 2R + 1 f32 taps of one axis: e[k] = exp(-k^2 / (2 sigma^2)) in f64 for k = -R .. R, divided by their sum
+    (accumulated one after the other in ascending k) and rounded to f32."""
+    R = gaussian_radius(sigma)
+    k = np.arange(-R, R + 1, dtype=np.float64)
+    e = np.exp(-(k * k) / (2.0 * float(sigma) * float(sigma)))
+    s = 0.0
+    for v in e:
+        s += float(v)
+    return (e / s).astype(np.float32)
+
+
+def blur_axis(vol, taps, axis):
+    """One pass of the blur over ``axis`` of an f32 array: acc = 0.0 (f64); for k ascending acc += f64(w[k]) *
+    f64(v[i + k - R]), a tap outside the axis contributing nothing; the result rounded to f32 once."""
+    vol = np.asarray(vol, dtype=np.float32)
+    taps = np.asarray(taps, dtype=np.float32)
+    R, n = (taps.size - 1) // 2, vol.shape[axis]
+    pad = [(0, 0)] * vol.ndim
+    pad[axis] = (R, R)
+    padded = np.pad(vol.astype(np.float64), pad)  # (a zero product adds +0.0, which changes no partial sum)
+    acc = np.zeros(vol.shape, dtype=np.float64)
+    for k in range(taps.size):
+        sl = [slice(None)] * vol.ndim
+        sl[axis] = slice(k, k + n)
+        acc = acc + np.float64(taps[k]) * padded[tuple(sl)]
+    return acc.astype(np.float32)
+
+
+def gaussian_smooth(img, sigmas):
+    """The blur of a (C, D, H, W) f32 image: three passes, over axis 0, then 1, then 2 of every channel, each rounding
+    to f32 once."""
+    for a, s in enumerate(sigmas):
+        img = blur_axis(img, gaussian_taps(s), a + 1)
+    return img
+
+
+def bias_terms(degree):
+    """The exponents (i, j, k) with i + j + k <= degree in the order their coefficients are drawn: lexicographic, i
+    slowest."""
+    degree = int(degree)
+    return [(i, j, k) for i in range(degree + 1) for j in range(degree + 1 - i) for k in range(degree + 1 - i - j)]
+
+
+def _legendre(degree, u):
+    """P_0 .. P_degree at the f64 points u by the recurrence (m + 1) P_{m+1} = (2m + 1) u P_m - m P_{m-1}."""
+    u = np.asarray(u, dtype=np.float64)
+    P = [np.ones_like(u), u]
+    for m in range(1, degree):
+        P.append(((2 * m + 1) * u * P[m] - m * P[m - 1]) / (m + 1))
+    return P[:degree + 1]
+
+
+def bias_polynomial(coeffs, degree, u0, u1, u2):
+    """sum c_ijk P_i(u0) P_j(u1) P_k(u2) on the grid u0 x u1 x u2 in f64: the terms in ``bias_terms`` order, each
+    ((c P_i) P_j) P_k, added one after the other from 0.0."""
+    terms = bias_terms(degree)
+    coeffs = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+    if coeffs.size != len(terms):
+        raise ValueError(f"biasfield: degree {degree} takes {len(terms)} coefficients, got {coeffs.size}")
+    P0, P1, P2 = (_legendre(int(degree), u) for u in (u0, u1, u2))
+    s = np.zeros((len(P0[0]), len(P1[0]), len(P2[0])), dtype=np.float64)
+    for c, (i, j, k) in zip(coeffs, terms):
+        s = s + ((c * P0[i])[:, None, None] * P1[j][None, :, None]) * P2[k][None, None, :]
+    return s
+
+
+def bias_lattice(coeffs, degree=3, lattice=9):
+    """-> (L, L, L) f32: F = exp(``bias_polynomial``) at the lattice points u_j = -1 + 2 j / (L - 1) of every axis,
+    rounded to f32."""
+    L = int(lattice)
+    if L < 2:
+        raise ValueError(f"biasfield: a lattice of at least 2 points per axis, got {lattice}")
+    u = -1.0 + 2.0 * np.arange(L, dtype=np.float64) / (L - 1)
+    return np.exp(bias_polynomial(coeffs, degree, u, u, u)).astype(np.float32)
+
+
+def bias_field(lattice, shape):
+    """The (L, L, L) f32 lattice sampled on a volume of ``shape`` -> f32 field.  Output voxel o samples at x_a = o_a *
+    (L - 1) / (n_a - 1) in f64 (0 where n_a == 1) with the trilinear arithmetic of ``devicedata.affine_numpy`` /
+    csrc/resample.hpp: taps floor(x), floor(x) + 1 clamped to L - 1, weights w0 = 1 - (x - floor(x)), w1 = 1 - w0, the
+    eight corners accumulated axis 0 slowest, each ((F w_0) w_1) w_2; the sum rounded to f32."""
+    F = np.asarray(lattice, dtype=np.float32).astype(np.float64)
+    L = F.shape[0]
+    idx, w = [], []
+    for n in shape:
+        o = np.arange(int(n), dtype=np.float64)
+        x = o * (L - 1) / (n - 1) if n > 1 else np.zeros(int(n))
+        fl = np.floor(x)
+        w0 = 1.0 - (x - fl)
+        w.append((w0, 1.0 - w0))
+        idx.append((np.minimum(fl, L - 1).astype(np.int64), np.minimum(fl + 1, L - 1).astype(np.int64)))
+    t = np.zeros(tuple(int(n) for n in shape), dtype=np.float64)
+    for a in range(2):
+        for b in range(2):
+            for d in range(2):
+                coeff = F[idx[0][a][:, None, None], idx[1][b][None, :, None], idx[2][d][None, None, :]]
+                coeff = coeff * w[0][a][:, None, None]
+                coeff = coeff * w[1][b][None, :, None]
+                coeff = coeff * w[2][d][None, None, :]
+                t = t + coeff
+    return t.astype(np.float32)
+
+
+def philox4x32(counter, key, rounds=10):
+    """Philox4x32-10 (Salmon et al., Random123) in numpy uint64: ``counter`` four and ``key`` two 32-bit words (arrays
+    broadcast against each other) -> the four output words as uint64 arrays holding 32-bit values."""
+    mask = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(v, dtype=np.uint64) & mask for v in counter]
+    k = [np.asarray(v, dtype=np.uint64) & mask for v in key]
+    for r in range(rounds):
+        if r:
+            k = [(k[0] + np.uint64(PHILOX_W0)) & mask, (k[1] + np.uint64(PHILOX_W1)) & mask]
+        p0, p1 = np.uint64(PHILOX_M0) * c[0], np.uint64(PHILOX_M1) * c[2]  # 32 x 32 bits: no overflow in 64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
+    return c
+
+
+def philox_normal(index, channel, k0, k1):
+    """The eight-term Irwin-Hall normal of voxel ``index`` (the spatial linear index) and ``channel``: the Philox block
+    of counter (index, channel, 0, 0) under key (k0, k1), its four words split into eight 16-bit halves with sum S;
+    z = f32(S - 262140) * f32(1 / sqrt(8 (2^32 - 1) / 12)), one f32 multiply.  Mean 0, variance 1, tails end at
+    +-4.9."""
+    words = philox4x32((index, channel, 0, 0), (k0, k1))
+    S = np.zeros(np.broadcast(*words).shape, dtype=np.int64)
+    for wd in words:
+        S = S + (wd & np.uint64(0xFFFF)).astype(np.int64) + (wd >> np.uint64(16)).astype(np.int64)
+    return (S - NOISE_MEAN).astype(np.float32) * NOISE_SCALE
+
+
+def gaussian_noise(img, std, k0, k1):
+    """(C, D, H, W) f32 image + noise: n = z * f32(std) with z = ``philox_normal`` of (d H W + h W + w, channel), then
+    v + n: three separately rounded f32 operations.  D H W >= 2^32 raises ValueError."""
+    img = np.asarray(img, dtype=np.float32)
+    V = int(np.prod(img.shape[1:]))
+    if V >= 2 ** 32:
+        raise ValueError(f"gaussiannoise: {V} voxels per channel do not fit the 32-bit counter word")
+    index = np.arange(V, dtype=np.uint64).reshape(img.shape[1:])
+    out = np.empty_like(img)
+    for c in range(img.shape[0]):
+        out[c] = img[c] + philox_normal(index, c, k0, k1) * np.float32(std)
+    return out
+
+
+def _draw_gaussiansmooth(rs, sigma=(0.25, 1.5), prob=0.1):
+    """The random draws of ``_aug_gaussiansmooth`` -> the sigmas of axes 0, 1, 2 (f64), or None."""
+    if rs.rand() >= prob:
+        return None
+    return tuple(float(rs.uniform(sigma[0], sigma[1])) for _ in range(3))
+
+
+def _draw_biasfield(rs, degree=3, coeff_range=(0.0, 0.1), lattice=9, prob=0.1):
+    """The random draws of ``_aug_biasfield`` -> the f64 coefficients in ``bias_terms`` order, or None."""
+    if rs.rand() >= prob:
+        return None
+    return rs.uniform(coeff_range[0], coeff_range[1], len(bias_terms(degree)))
+
+
+def _draw_gaussiannoise(rs, std=0.1, prob=0.1):
+    """The random draws of ``_aug_gaussiannoise`` -> (std f64, k0, k1), or None."""
+    if rs.rand() >= prob:
+        return None
+    s = float(rs.uniform(0, std))
+    k0, k1 = rs.randint(0, 2 ** 32, 2, dtype=np.uint32)
+    return s, int(k0), int(k1)
+
+
+def apply_mr(name, img, draw, kw):
+    """A drawn MR transform (``DRAWS[name]``'s result, None: not drawn) on a (C, D, H, W) f32 image."""
+    if draw is None:
+        return img
+    if name == "gaussiansmooth":
+        return gaussian_smooth(img, draw)
+    if name == "biasfield":
+        field = bias_field(bias_lattice(draw, kw.get("degree", 3), kw.get("lattice", 9)), img.shape[1:])
+        return np.asarray(img, dtype=np.float32) * field[None]  # one f32 multiply
+    if name == "gaussiannoise":
+        return gaussian_noise(img, *draw)
+    raise ValueError(f"not an MR transform: {name!r}")
+
+
+def _aug_gaussiansmooth(img, seg, rs, **kw):
+    return apply_mr("gaussiansmooth", img, _draw_gaussiansmooth(rs, **kw), kw), seg
+
+
+def _aug_biasfield(img, seg, rs, **kw):
+    return apply_mr("biasfield", img, _draw_biasfield(rs, **kw), kw), seg
+
+
+def _aug_gaussiannoise(img, seg, rs, **kw):
+    return apply_mr("gaussiannoise", img, _draw_gaussiannoise(rs, **kw), kw), seg
+
+
 AUGMENTATIONS = {"flip": _aug_flip, "rotate90": _aug_rotate90, "affine": _aug_affine,
                  "zoom": _aug_zoom, "griddistortion": _aug_griddistortion,
-                 "shiftintensity": _aug_shiftintensity, "scaleintensity": _aug_scaleintensity}
+                 "shiftintensity": _aug_shiftintensity, "scaleintensity": _aug_scaleintensity,
+                 "gaussiansmooth": _aug_gaussiansmooth, "biasfield": _aug_biasfield, "gaussiannoise": _aug_gaussiannoise}
 DRAWS = {"flip": _draw_flip, "rotate90": _draw_rotate90, "affine": _draw_affine,
          "zoom": _draw_zoom, "griddistortion": _draw_griddistortion,
-         "shiftintensity": _draw_shiftintensity, "scaleintensity": _draw_scaleintensity}
+         "shiftintensity": _draw_shiftintensity, "scaleintensity": _draw_scaleintensity,
+         "gaussiansmooth": _draw_gaussiansmooth, "biasfield": _draw_biasfield, "gaussiannoise": _draw_gaussiannoise}
+MR_NAMES = ("gaussiansmooth", "biasfield", "gaussiannoise")
+
+
+def transform_name(t):
+    return t if isinstance(t, str) else t[0]
+
+
+def check_mr_last(augmentations):
+    """The MR transforms act on the finished sample: an entry of another kind behind one of them raises
+    NotImplementedError (``devicedata.sample_params`` refuses the same lists)."""
+    names = [transform_name(t) for t in augmentations]
+    seen = False
+    for n in names:
+        if n in MR_NAMES:
+            seen = True
+        elif seen:
+            raise NotImplementedError(f"{n} placed behind an MR transform ({' / '.join(MR_NAMES)} come last)")
 
 
 def draw_augmentations(augmentations, rs):
@@ -333,20 +568,27 @@ def select_augmentations(names):
 WARP_AUGMENTATIONS = [("zoom", {"min_zoom": 0.9, "max_zoom": 1.1, "padding_mode": "border", "prob": 0.5}),
                       ("griddistortion", {"num_cells": 5, "distort_limit": 0.03, "padding_mode": "border", "prob": 0.5})]
 INTENSITY_NAMES = ("shiftintensity", "scaleintensity")
+# the MR acquisition stage, in acquisition order: resolution loss, coil inhomogeneity, thermal
+# noise; MONAI's names and default ranges as remembered
+MR_AUGMENTATIONS = [("gaussiansmooth", {"sigma": (0.25, 1.5), "prob": 0.1}),
+                    ("biasfield", {"degree": 3, "coeff_range": (0.0, 0.1), "lattice": 9, "prob": 0.1}),
+                    ("gaussiannoise", {"std": 0.1, "prob": 0.1})]
 
 
 def select_training_augmentations(names):
     """What ``train.py -a`` binds: ``select_augmentations`` for the reference's names, unchanged, plus the entries of
     ``WARP_AUGMENTATIONS`` that were asked for, in that list's order, behind the flips / rot90s / affines and in front of
-    the intensity operations (the order ``devicedata.sample_params`` takes).  Unknown names raise ValueError."""
+    the intensity operations (the order ``devicedata.sample_params`` takes), plus the entries of ``MR_AUGMENTATIONS`` that
+    were asked for, in that list's order, behind everything else.  Unknown names raise ValueError."""
     warp = [n for n, _ in WARP_AUGMENTATIONS]
-    known = [n for n, _ in REFERENCE_AUGMENTATIONS + LESIONS_AUGMENTATIONS] + warp
+    known = [n for n, _ in REFERENCE_AUGMENTATIONS + LESIONS_AUGMENTATIONS] + warp + list(MR_NAMES)
     unknown = set(names) - set(known)
     if unknown:
         raise ValueError(f"unknown augmentation(s) {sorted(unknown)}; known: {' '.join(dict.fromkeys(known))}")
-    out = select_augmentations([n for n in names if n not in warp])
+    out = select_augmentations([n for n in names if n not in warp and n not in MR_NAMES])
     at = next((k for k, (n, _) in enumerate(out) if n in INTENSITY_NAMES), len(out))
-    return out[:at] + [(n, kw) for n, kw in WARP_AUGMENTATIONS if n in names] + out[at:]
+    out = out[:at] + [(n, kw) for n, kw in WARP_AUGMENTATIONS if n in names] + out[at:]
+    return out + [(n, kw) for n, kw in MR_AUGMENTATIONS if n in names]
 
 
 def _load(path_noext):
@@ -970,7 +1212,9 @@ class _LesionCases(Dataset):
     NormalizeIntensity(nonzero) -> training augmentations at the cropped shape -> resize_with_pad_or_crop(replicate) ->
     boxes ('instances' / 'binary' mode).  With C = len(input_images) > 1 the image is channel-first throughout: the crop
     box is the union of the channels' foregrounds, every channel is normalised over its own non-zero voxels, and one set
-    of augmentation draws moves all channels and the mask (the intensity operands are shared, as in MONAI)."""
+    of augmentation draws moves all channels and the mask (the intensity operands are shared, as in MONAI).  The MR
+    transforms (``MR_NAMES``) are drawn in list order with the others but applied to the fitted / windowed sample, where
+    the device route applies them; they must come last (``check_mr_last``)."""
 
     def __init__(self, module, subjects, augmentations=None, seed=0, patch=None):
         self.module, self.subjects = module, list(subjects)
@@ -979,6 +1223,7 @@ class _LesionCases(Dataset):
         for t in self.augmentations:
             if (t if isinstance(t, str) else t[0]) not in AUGMENTATIONS:
                 raise ValueError(f"unknown transform {t!r}")
+        check_mr_last(self.augmentations)  # they are applied behind the fit / window
         self.seed, self.epoch = seed, 0
         self.patch = None if patch is None else tuple(int(t) for t in patch)  # training windows instead of the fit
         self._plans = {}  # position -> the RegridPlan of the case's last load (None: no affine); native_plan
@@ -1085,8 +1330,12 @@ class _LesionCases(Dataset):
         if patch is not None and origin is None:  # on the cropped mask, before it moves
             centres = lesion_centres(seg, m.thresholds, m.segmentation_mode)
         rs = self.sample_rng(i) if self.augmentations or centres is not None else None
+        mr = []  # drawn in list order, applied to the finished sample (the device route runs them on the built batch)
         for t in self.augmentations:
             name, kw = (t, {}) if isinstance(t, str) else t
+            if name in MR_NAMES:
+                mr.append((name, DRAWS[name](rs, **kw), kw))
+                continue
             img, seg = AUGMENTATIONS[name](img, seg, rs, **kw)
         if centres is not None:
             # the window's draws follow every augmentation draw: a sample's augmentation does not depend on patch mode
@@ -1099,6 +1348,8 @@ class _LesionCases(Dataset):
             img, seg = window(img, origin, patch), window(seg, origin, patch)
         elif fit:
             img, seg = resize_with_pad_or_crop(img, m.spatial_size), resize_with_pad_or_crop(seg, m.spatial_size)
+        for name, draw, kw in mr:
+            img = apply_mr(name, img, draw, kw)
         img = np.ascontiguousarray(img)
         boxes, labels = boxes_from_instances(seg, m.thresholds, m.segmentation_mode)
         out = {"img": torch.from_numpy(img), "boxes": boxes, "labels": labels, "seg": [boxes, labels],

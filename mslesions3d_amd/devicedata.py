@@ -22,7 +22,9 @@ device form of ``datasets.regrid``, bit for bit) in front of the foreground box.
 training) gets one sampled window per case and epoch instead of the fit, and validation tiles
 (msl_augment_window_mc with the origins ``datasets.patch_origin`` / ``datasets.view_plan`` give on the host).  A batch in
 which some sample drew a zoom / griddistortion (a ``WarpStage``: three per-axis coordinate tables, DESIGN.md section
-4.13) goes through msl_augment_warp_mc instead, on either route; ``DeviceCache`` refuses the two names.
+4.13) goes through msl_augment_warp_mc instead, on either route; ``DeviceCache`` refuses the two names.  An augmentation
+list that names gaussiansmooth / biasfield / gaussiannoise (the MR stage) adds msl_augment_mr
+(csrc/mraug.hip) behind the batch build of either cache: ``mr_tables`` lowers the draws, ``MRStageRunner`` launches.
 """
 from collections import namedtuple
 
@@ -32,8 +34,9 @@ from os.path import join as pjoin
 
 from . import _lib
 from ._lib import ptr
-from .datasets import (SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset, centres_to_augmented,
-                       draw_augmentations, patch_origin, regrid_plan, sample_rng, view_plan, warp_tables)
+from .datasets import (MR_MAX_RADIUS, MR_NAMES, SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset,
+                       bias_lattice, centres_to_augmented, draw_augmentations, gaussian_taps, patch_origin, regrid_plan,
+                       sample_rng, transform_name, view_plan, warp_tables)
 
 PARAM_STRIDE = 16  # f64 per sample of msl_augment_resample
 AFFINE_STRIDE = 32  # f64 per sample of msl_augment_affine
@@ -51,6 +54,14 @@ IntensityOp = namedtuple("IntensityOp", "kind value")
 WarpStage = namedtuple("WarpStage", "tables boundary")
 WARP_NAMES = ("zoom", "griddistortion")
 ROW_COPY, ROW_AFFINE, ROW_WARP = 0.0, 1.0, 2.0  # field [7] of a parameter row
+# an MR transform of the augmentation list (gaussiansmooth / biasfield / gaussiannoise): its name,
+# its draw (``datasets.DRAWS[name]``'s result; None: not drawn) and its keyword arguments.  msl_augment_mr runs them on
+# the built batch; the batch build itself does not see them
+MRStage = namedtuple("MRStage", "name draw kw")
+MR_STRIDE = 8  # f64 per sample of msl_augment_mr
+MR_TAPS = 2 * MR_MAX_RADIUS + 1  # f32 per axis of its taps table
+MR_LATTICE = 9  # points per axis of its lattice table
+MR_BLUR, MR_BIAS, MR_NOISE = 1, 2, 4  # bits of field [0] of its parameter row
 
 
 def _stream(dev):
@@ -150,7 +161,9 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
     ``ragged`` (msl_augment_fit): a rot90 may change the shape, and every affine stage is an ``AffineStage`` computed
     for the permuted shape.  A drawn zoom / griddistortion is a ``WarpStage`` with the tables of the permuted shape
     (``ragged`` only; padding "border" unless the entry says otherwise); it is a resampling stage like an affine: behind
-    the flips / rot90s, in front of the intensity operations."""
+    the flips / rot90s, in front of the intensity operations.  gaussiansmooth / biasfield / gaussiannoise are the last
+    group: each appends an ``MRStage`` (drawn or not), which moves no point and which the batch build skips
+    (``mr_tables`` lowers them for msl_augment_mr); any other entry behind one of them raises NotImplementedError."""
     axis, rev = [0, 1, 2], [0, 0, 0]
     stages = []
     n_ops = 0
@@ -159,7 +172,17 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
         axis[a], axis[b] = axis[b], axis[a]
         rev[a], rev[b] = rev[b], rev[a]
 
+    n_mr = 0
     for k, (name, d) in enumerate(draws):
+        if name in MR_NAMES:  # the last group: an MRStage each, drawn or not
+            t = augmentations[k] if augmentations is not None else name
+            stages.append(MRStage(name, d, {} if isinstance(t, str) else t[1]))
+            if MR_NAMES.index(name) < n_mr:  # one launch carries blur, then bias, then noise
+                raise NotImplementedError(f"device pipeline: {' / '.join(MR_NAMES)} once each, in that order")
+            n_mr = MR_NAMES.index(name) + 1
+            continue
+        if n_mr:
+            raise NotImplementedError(f"device pipeline: {name} after an MR transform ({' / '.join(MR_NAMES)} come last)")
         if name == "affine":
             if n_ops:
                 raise NotImplementedError("device pipeline: an affine stage after an intensity operation")
@@ -337,7 +360,7 @@ def batch_launches(slots, per_sample):
     permutation; the last one carries the intensity operations.  A launch whose stages are all diagonal with
     reflection padding and that carries no operation stays on msl_augment_resample."""
     N = len(slots)
-    geo = [[st for st in stages if not isinstance(st, IntensityOp)] for _, stages in per_sample]
+    geo = [[st for st in stages if not isinstance(st, (IntensityOp, MRStage))] for _, stages in per_sample]
     ops = [[st for st in stages if isinstance(st, IntensityOp)] for _, stages in per_sample]
     n_geo = max((len(g) for g in geo), default=0)
     used = [j for j in range(n_geo) if any(j < len(g) and g[j] is not None for g in geo)] or [None]
@@ -453,6 +476,8 @@ class DeviceCache:
         for b in self._bufs.values():
             n += sum(t.numel() * t.element_size() for t in (b["img"], b["seg"], *b["tmp"], b["box"].ws, b["box"].gb,
                                                              b["box"].gl))
+            if "mr" in b:
+                n += b["built"].numel() * 4 + b["mr"].ws.numel()
         return n
 
     def footprint(self):
@@ -470,6 +495,9 @@ class DeviceCache:
                                  "seg": torch.empty((N,) + self.shape, dtype=torch.uint8, device=dev),
                                  "tmp": [t for pair in tmp for t in pair],
                                  "box": _BoxOut(N, self.shape, self.n_classes, self.capacity, self.comp_cap, dev)}
+            if names_mr(self.augmentations):  # msl_augment_mr works out of place
+                b["built"] = torch.empty_like(b["img"])
+                b["mr"] = MRStageRunner(N, 1, self.shape, dev)
         return b
 
     def _run(self, slots, per_sample, b):
@@ -479,13 +507,18 @@ class DeviceCache:
         pd = torch.from_numpy(np.concatenate([rows.reshape(-1) for _, rows in launches])).pin_memory().to(dev, non_blocking=True)
         N = len(slots)
         src_img, src_seg, n_src = self.img, self.seg, self.img.shape[0]
+        # with the MR stage behind it the build writes the stage's source; "img" stays the batch's fixed output
+        mr = "mr" in b and any(isinstance(st, MRStage) for _, stages in per_sample for st in stages)
         at = 0
         for k, (fn, rows) in enumerate(launches):
             last = k == len(launches) - 1
-            dst_img, dst_seg = (b["img"], b["seg"]) if last else (b["tmp"][2 * (k % 2)], b["tmp"][2 * (k % 2) + 1])
+            dst_img, dst_seg = (b["built"] if mr else b["img"], b["seg"]) if last else \
+                (b["tmp"][2 * (k % 2)], b["tmp"][2 * (k % 2) + 1])
             _lib.call(fn, ptr(src_img), ptr(src_seg), n_src, ptr(pd[at:]), N, *self.shape, ptr(dst_img), ptr(dst_seg), stream)
             at += rows.size
             src_img, src_seg, n_src = dst_img, dst_seg, N
+        if mr:
+            b["mr"].run(b["built"], per_sample, b["img"], stream)
         b["box"].launch(b["seg"], stream)
 
     def train_batches(self, epoch):
@@ -632,7 +665,7 @@ def warp_rows(cases, per_sample):
     rows = np.zeros((len(cases), AFFINE_STRIDE), dtype=np.float64)
     coords, at = [], 0
     for n, (case, (perm, stages)) in enumerate(zip(cases, per_sample)):
-        geo = [st for st in stages if not isinstance(st, IntensityOp)]
+        geo = [st for st in stages if not isinstance(st, (IntensityOp, MRStage))]
         if len(geo) > 1:
             raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
         st = geo[0] if geo else None
@@ -645,6 +678,75 @@ def warp_rows(cases, per_sample):
         else:
             rows[n] = affine_row(case, perm, st, ops)
     return rows, (np.concatenate(coords) if coords else np.zeros(0, dtype=np.float64))
+
+
+def names_mr(augmentations):
+    """Does the augmentation list name gaussiansmooth, biasfield or gaussiannoise?"""
+    return any(transform_name(t) in MR_NAMES for t in augmentations)
+
+
+def mr_tables(per_sample):
+    """The ``MRStage``s of a batch's ``sample_params`` results -> (rows (N, MR_STRIDE) f64, taps (N, 3, MR_TAPS) f32,
+    lattice (N, L, L, L) f32), the three tables msl_augment_mr reads.  Row: [0] the sum of MR_BLUR / MR_BIAS / MR_NOISE
+    for what the sample drew, [1..3] the blur radii R_0..R_2, [4] the noise deviation as an f32, [5] [6] the key words
+    k0, k1.  Taps: ``datasets.gaussian_taps`` of axis a in [n, a, 0 .. 2 R_a].  Lattice: ``datasets.bias_lattice``.  Both
+    are the host's own values: the device computes no exponential.  A sigma above 2.0 raises ValueError, a lattice of
+    more than MR_LATTICE points per axis NotImplementedError."""
+    N = len(per_sample)
+    L = MR_LATTICE
+    for _, stages in per_sample:
+        for st in stages:
+            if isinstance(st, MRStage) and st.name == "biasfield":
+                L = int(st.kw.get("lattice", 9))
+    if not 2 <= L <= MR_LATTICE:
+        raise NotImplementedError(f"device pipeline: a bias lattice of 2 .. {MR_LATTICE} points per axis, got {L}")
+    rows = np.zeros((N, MR_STRIDE), dtype=np.float64)
+    taps = np.zeros((N, 3, MR_TAPS), dtype=np.float32)
+    lattice = np.ones((N, L, L, L), dtype=np.float32)
+    for n, (_, stages) in enumerate(per_sample):
+        for st in stages:
+            if not isinstance(st, MRStage) or st.draw is None:
+                continue
+            if st.name == "gaussiansmooth":
+                rows[n, 0] += MR_BLUR
+                for a, sigma in enumerate(st.draw):
+                    w = gaussian_taps(sigma)
+                    rows[n, 1 + a] = (w.size - 1) // 2
+                    taps[n, a, :w.size] = w
+            elif st.name == "biasfield":
+                rows[n, 0] += MR_BIAS
+                lattice[n] = bias_lattice(st.draw, st.kw.get("degree", 3), L)
+            else:
+                rows[n, 0] += MR_NOISE
+                rows[n, 4], rows[n, 5], rows[n, 6] = np.float32(st.draw[0]), st.draw[1], st.draw[2]
+    return rows, taps, lattice
+
+
+class MRStageRunner:
+    """msl_augment_mr for (N, C) + shape f32 batches: the workspace, and one launch per batch behind the batch build.
+    ``run`` uploads the three tables of ``mr_tables`` in one pinned copy and writes ``dst`` from ``src`` (out of place) on
+    the current stream; a sample that drew nothing is copied."""
+
+    def __init__(self, N, C, shape, dev):
+        self.N, self.C, self.shape, self.device = int(N), int(C), tuple(int(n) for n in shape), dev
+        nbytes = _lib.load().msl_augment_mr_workspace_bytes(self.N, self.C, *self.shape)
+        if nbytes == 0:
+            raise _lib.HipKernelError(f"msl_augment_mr: unsupported sizes N={N} C={C} shape={self.shape}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def run(self, src, per_sample, dst, stream):
+        rows, taps, lattice = mr_tables(per_sample)
+        if rows.shape[0] != self.N:
+            raise ValueError(f"msl_augment_mr: {rows.shape[0]} samples on a stage for {self.N}")
+        packed = np.zeros(rows.size + (taps.size + lattice.size + 1) // 2, dtype=np.float64)
+        packed[:rows.size] = rows.reshape(-1)
+        f32 = packed[rows.size:].view(np.float32)  # the f32 tables ride in the doubles behind the rows
+        f32[:taps.size] = taps.reshape(-1)
+        f32[taps.size:taps.size + lattice.size] = lattice.reshape(-1)
+        pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
+        at = pd.data_ptr() + 8 * rows.size
+        _lib.call("msl_augment_mr", ptr(src), ptr(pd), at, at + 4 * taps.size, self.N, self.C, *self.shape,
+                  lattice.shape[1], ptr(dst), ptr(self.ws), self.ws.numel(), stream)
 
 
 def check_ragged_pipeline(augmentations):
@@ -853,6 +955,8 @@ class LesionCache:
         n = self.cache_bytes
         for b in self._bufs.values():
             n += sum(t.numel() * t.element_size() for t in (b["img"], b["seg"], b["box"].ws, b["box"].gb, b["box"].gl))
+            if "mr" in b:
+                n += b["built"].numel() * 4 + b["mr"].ws.numel()
         return n
 
     def footprint(self):
@@ -872,11 +976,17 @@ class LesionCache:
                                  "seg": torch.empty((N,) + self.target, dtype=torch.int16, device=dev),
                                  "box": _box_stage(self.dataset, N, self.target, self.capacity, dev,
                                                    self.max_runs_per_image, "LesionCache")}
+            if names_mr(self.augmentations):  # msl_augment_mr works out of place
+                b["built"] = torch.empty_like(b["img"])
+                b["mr"] = MRStageRunner(N, self.channels, self.target, dev)
         return b
 
     def _run(self, slots, per_sample, b, windows=None):
         stream = _stream(self.device)
         rows, coords = warp_rows(slots, per_sample)
+        # with the MR stage behind it the build writes the stage's source; "img" stays the batch's fixed output
+        built = b["built"] if "mr" in b and any(isinstance(st, MRStage) for _, stages in per_sample for st in stages) \
+            else b["img"]
         if coords.size:  # some sample drew a warp.  One upload: the f64 rows, the tables, then the int32 origins
             N = len(slots)
             packed = np.zeros(rows.size + coords.size + (0 if windows is None else (3 * N + 1) // 2), dtype=np.float64)
@@ -888,8 +998,8 @@ class LesionCache:
             _lib.call("msl_augment_warp_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels,
                       ptr(self.table), len(self.shapes), ptr(pd), pd.data_ptr() + 8 * rows.size, coords.size,
                       None if windows is None else pd.data_ptr() + 8 * (rows.size + coords.size), N, *self.target,
-                      ptr(b["img"]), ptr(b["seg"]), stream)
-            b["box"].launch(b["seg"], stream)
+                      ptr(built), ptr(b["seg"]), stream)
+            self._finish(b, per_sample, stream)
             return
         if windows is not None:  # one upload: the f64 rows, then the (N, 3) int32 origins in the doubles behind them
             N = len(slots)
@@ -899,12 +1009,19 @@ class LesionCache:
             pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
             _lib.call("msl_augment_window_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels,
                       ptr(self.table), len(self.shapes), ptr(pd), pd.data_ptr() + 8 * rows.size, N, *self.target,
-                      ptr(b["img"]), ptr(b["seg"]), stream)
-            b["box"].launch(b["seg"], stream)
+                      ptr(built), ptr(b["seg"]), stream)
+            self._finish(b, per_sample, stream)
             return
         pd = torch.from_numpy(rows.reshape(-1)).pin_memory().to(self.device, non_blocking=True)
         _lib.call("msl_augment_fit_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table),
-                  len(self.shapes), ptr(pd), len(slots), *self.target, ptr(b["img"]), ptr(b["seg"]), stream)
+                  len(self.shapes), ptr(pd), len(slots), *self.target, ptr(built), ptr(b["seg"]), stream)
+        self._finish(b, per_sample, stream)
+
+    def _finish(self, b, per_sample, stream):
+        """Behind the batch build: the MR stage on the built images (a batch of a list that names one of the three and
+        carries draws: validation batches carry none), then the box stage."""
+        if "mr" in b and any(isinstance(st, MRStage) for _, stages in per_sample for st in stages):
+            b["mr"].run(b["built"], per_sample, b["img"], stream)
         b["box"].launch(b["seg"], stream)
 
     def train_batches(self, epoch):

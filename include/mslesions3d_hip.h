@@ -608,6 +608,27 @@ int msl_augment_warp_mc(const float* arena_img, const short* arena_seg, long lon
                         const long long* table, int n_cases, const double* params, const double* coords,
                         long long coords_len, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
                         short* dst_seg, void* stream);
+/* Free-form deformation (datasets.deform_lattice / deform_coords, devicedata.DeformStage / deform_numpy; DESIGN.md
+ * section 4.15).  msl_augment_deform_mc: msl_augment_warp_mc's arenas, table, (N,32) f64 rows, windows, outputs, zero
+ * rows and return codes.  A row with [7] = 0 is the permuted copy of msl_augment_fit_mc / msl_augment_window_mc, bit for
+ * bit (intensity operations included).  A row with [7] = 3 is a deformation: [8] is the element offset of the sample's
+ * lattice P in lattices (device, lattices_len doubles): 3 L^3 doubles [m][i0][i1][i2], component m displacing along axis
+ * m of the permuted case; [9] is L, the control points per axis (4 .. 16); [20] the boundary (1 is sampled as scipy's
+ * "nearest", as msl_augment_warp_mc samples it) and [21..] the intensity operations.  Output voxel o maps to q =
+ * clamp(o + d, 0, n' - 1) and samples the permuted case at q + d(q), d the cubic B-spline of P, every operation one
+ * rounded f64 operation in a fixed order: per axis a, u = q_a (L - 3) / (n'_a - 1) (0 where n'_a = 1), cell =
+ * min(floor(u), L - 4), t = u - cell, b0 = (1 - t)^3 / 6, b1 = (3 t^3 - 6 t^2 + 4) / 6, b2 = (-3 t^3 + 3 t^2 + 3 t + 1) / 6,
+ * b3 = t^3 / 6; d_m = sum_k b[2][k] * (sum_j b[1][j] * (sum_i b[0][i] * P[m][cell_0 + i][cell_1 + j][cell_2 + k])), each
+ * sum from 0.0 upwards.  Any other [7] (an affine's 1 and a warp's 2 among them), an invalid case or axis list, an L
+ * outside 4 .. 16 or a lattice that does not lie inside [0, lattices_len) write zeros to the row.  cell is clamped into
+ * [0, L - 4] and the taps into the axis, so a non-finite lattice value is outside the contract but reads inside the
+ * lattice and the case.  Every output voxel is written exactly once: no memset, no atomics.  -1 (nothing launched,
+ * nothing written): a null pointer other than windows, a size or lattices_len < 1, C outside 1..4.  -2: N > 65535 or
+ * T0 * T1 >= 2^31 - 4. */
+int msl_augment_deform_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                          const long long* table, int n_cases, const double* params, const double* lattices,
+                          long long lattices_len, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
+                          short* dst_seg, void* stream);
 
 /* ---- native grid -> LPI at 1 mm (csrc/datapipe.hip, devicedata.LesionCache / LesionPredictFeed)
  * msl_regrid: datasets.regrid of one case, bit for bit.  src_img (C,n0,n1,n2) f32 with 1 <= C <= 4, src_seg (n0,n1,n2)

@@ -151,6 +151,7 @@ _SIGNATURES = {
     "msl_augment_fit_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_augment_window_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_augment_warp_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _P, _Q, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "msl_augment_deform_mc": (_I, [_P, _P, _Q, _I, _P, _I, _P, _P, _Q, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msl_regrid": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "msl_augment_mr_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "msl_augment_mr": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),

@@ -4,7 +4,7 @@
 //
 //   normalize : one workgroup per cached case, population mean / std of the non-zero voxels in f64 with a fixed
 //               combination order, then (x - mean) / std in f32 as the host writes it
-//   sampling  : five kernels resample a volume, all through the one core of resample.hpp (row decode, permuted source
+//   sampling  : six kernels resample a volume, all through the one core of resample.hpp (row decode, permuted source
 //               view, axis taps, eight-corner sum, intensity operations, four-wide store), which follows scipy's
 //               NI_GeometricTransform for order 0 / 1 operation by operation in f64 (this file is built with
 //               -ffp-contract=off).  Each adds its coordinates and its layout:
@@ -15,6 +15,8 @@
 //     fit     : affine on a ragged case of C channels behind a clamped shift (centred fit or window), four voxels a thread
 //     warp    : zoom / grid distortion of a ragged case through three per-axis coordinate tables (msl_augment_warp_mc),
 //               bit-identical to scipy.ndimage.map_coordinates on their meshgrid; one wave per output row
+//     deform  : free-form deformation of a ragged case (msl_augment_deform_mc): the coordinates are q + d(q), d a cubic
+//               B-spline of a 3 x L^3 lattice evaluated per voxel; one wave per output row, the row's part in LDS
 //     regrid  : a native case onto the LPI 1 mm grid (signed axis permutation + per-axis step), bit-identical to
 //               datasets.regrid; column entries in LDS; at the end of this file
 //   boxes     : 6-connected components of every class by union-find (hook the larger root under the smaller: root =
@@ -826,6 +828,30 @@ int augment_mc(const float* arena_img, const short* arena_seg, long long seg_ele
 // the same index arithmetic), any other row is written as zeros.
 constexpr int WARP_WAVES = DP_THREADS / 64;  // output rows per workgroup
 
+// The two rows every one-wave-per-row kernel (warp_kernel, deform_kernel) writes besides its own: zeros for a row the
+// entry point rejects, and fit_kernel's permuted copy (its values, by the same index arithmetic) with the intensity
+// arithmetic in the store.  di / dsg: the row's first voxel in plane 0 of the image and in the mask.
+template <int C>
+__device__ __forceinline__ void row_zeros(float* __restrict__ di, short* __restrict__ dsg, long long TV, int T2, int lane) {
+  for (int x = lane; x < T2; x += 64) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) di[c * TV + x] = 0.0f;
+    dsg[x] = 0;
+  }
+}
+
+template <int C>
+__device__ __forceinline__ void row_copy(const SrcView<short>& v, const double* __restrict__ p, int q0, int q1, int d2,
+                                         float* __restrict__ di, short* __restrict__ dsg, long long TV, int T2, int lane) {
+  const long long rbase = v.base + q0 * v.pst[0] + q1 * v.pst[1];
+  for (int x = lane; x < T2; x += 64) {
+    const long long s = rbase + fit_src<true>(x, d2, v.dims[2]) * v.pst[2];
+#pragma unroll
+    for (int c = 0; c < C; ++c) di[c * TV + x] = apply_ops(v.si[c * v.V + s], p);
+    dsg[x] = v.ss[s];
+  }
+}
+
 template <int C>
 __global__ __launch_bounds__(DP_THREADS) void warp_kernel(
     const float* __restrict__ src_img, const short* __restrict__ src_seg, long long seg_elems,
@@ -854,11 +880,7 @@ __global__ __launch_bounds__(DP_THREADS) void warp_kernel(
     }
   }
   if (!ok) {
-    for (int x = lane; x < T2; x += 64) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) di[c * TV + x] = 0.0f;
-      dsg[x] = 0;
-    }
+    row_zeros<C>(di, dsg, TV, T2, lane);
     return;
   }
   const int T[3] = {T0, T1, T2};
@@ -866,14 +888,8 @@ __global__ __launch_bounds__(DP_THREADS) void warp_kernel(
 #pragma unroll
   for (int a = 0; a < 3; ++a) dsh[a] = fit_shift(windows ? windows + 3 * (long long)n + a : nullptr, v.dims[a], T[a]);
   const int q0 = fit_src<true>(oc0, dsh[0], v.dims[0]), q1 = fit_src<true>(oc1, dsh[1], v.dims[1]);
-  if (!warp) {  // permuted copy, the intensity arithmetic in the store
-    const long long rbase = v.base + q0 * v.pst[0] + q1 * v.pst[1];
-    for (int x = lane; x < T2; x += 64) {
-      const long long s = rbase + fit_src<true>(x, dsh[2], v.dims[2]) * v.pst[2];
-#pragma unroll
-      for (int c = 0; c < C; ++c) di[c * TV + x] = apply_ops(v.si[c * v.V + s], p);
-      dsg[x] = v.ss[s];
-    }
+  if (!warp) {
+    row_copy<C>(v, p, q0, q1, dsh[2], di, dsg, TV, T2, lane);
     return;
   }
   // the row's "nearest" is scipy's own here, not affine_kernel's clamp of the coordinate (resample.hpp, at the codes)
@@ -919,6 +935,149 @@ int augment_warp(const float* arena_img, const short* arena_seg, long long seg_e
   return msl::dispatch_int<1, 2, 3, 4>(C, [&](auto ch) {
     MSL_LAUNCH(warp_kernel<decltype(ch)::value>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table,
                n_cases, params, coords, coords_len, windows, T0, T1, T2, dst_img, dst_seg);
+    MSL_LAUNCH_CHECK();
+    return MSL_OK;
+  });
+}
+
+// ---- free-form deformation (elastic3d): msl_augment_deform_mc ------------------------------------------------------------
+// Host mirrors: datasets.deform_coords / _aug_elastic3d (scipy.ndimage.map_coordinates at q + d(q)) and
+// devicedata.deform_numpy; the contract is DESIGN.md section 4.15.  The arenas, the table, the rows and the outputs are
+// warp_kernel's; a row with [7] = 3 carries at [8] the element offset of its lattice P in `lattices` (3 L^3 doubles,
+// [m][i0][i1][i2]: component m displaces along axis m of the permuted case), at [9] L (4 .. 16 control points per axis)
+// and at [20] the boundary.  Output voxel o reads voxel q = clamp(o + d, 0, n' - 1) of the deformed case, which samples
+// the permuted case at q + d(q), d_m(q) the cubic B-spline of P[m]: per axis u = q (L - 3) / (n' - 1), cell, t and the
+// four weights of spline_taps, then d_m = sum_k b2[k] * R_m[cell2 + k] with R_m[k2] = sum_j b1[j] * (sum_i b0[i] *
+// P[m][cell0 + i][cell1 + j][k2]), every sum from 0.0 upwards, one rounded f64 operation each.
+//
+// One wave per output row, as warp_kernel.  q0, q1, their cells and weights belong to the row; so do the 3 L <= 48
+// values R_m[k2], which lane 16 m + k2 computes (16 multiply-adds) and leaves in its wave's own LDS slot.  Along the row
+// a lane forms its axis-2 weights, reads its 12 R values, and samples at the three coordinates through the core.
+constexpr int DEFORM_MIN_L = 4, DEFORM_MAX_L = 16;
+
+struct SplineTaps {  // one axis of one voxel: the first of its four control points, their weights
+  int cell;
+  double b[4];
+};
+
+// u = 0.0 on an axis of one voxel.  cell is clamped into [0, L - 4] as a double, so any u reads inside the lattice.
+__device__ __forceinline__ SplineTaps spline_taps(int q, int n, int L) {
+  SplineTaps r;
+  const double u = n > 1 ? ((double)q * (double)(L - 3)) / (double)(n - 1) : 0.0;
+  const double uf = floor(u);
+  r.cell = !(uf >= 0.0) ? 0 : (uf > (double)(L - 4) ? L - 4 : (int)uf);
+  const double t = u - (double)r.cell;  // 1.0 at the last voxel
+  const double t2 = t * t, t3 = t2 * t, s = 1.0 - t;
+  r.b[0] = ((s * s) * s) / 6.0;
+  r.b[1] = (((3.0 * t3) - (6.0 * t2)) + 4.0) / 6.0;
+  r.b[2] = ((((-3.0 * t3) + (3.0 * t2)) + (3.0 * t)) + 1.0) / 6.0;
+  r.b[3] = t3 / 6.0;
+  return r;
+}
+
+template <int C>
+__global__ __launch_bounds__(DP_THREADS) void deform_kernel(
+    const float* __restrict__ src_img, const short* __restrict__ src_seg, long long seg_elems,
+    const long long* __restrict__ table, int n_cases, const double* __restrict__ params,
+    const double* __restrict__ lattices, long long lattices_len, const int* __restrict__ windows, int T0, int T1, int T2,
+    float* __restrict__ dst_img, short* __restrict__ dst_seg) {
+  __shared__ double rows_r[WARP_WAVES][3 * DEFORM_MAX_L];  // R_m[k2] at [16 m + k2], one slot per wave
+  const int lane = threadIdx.x & 63;
+  const int rowi = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WARP_WAVES + (threadIdx.x >> 6)));
+  if ((long long)rowi >= (long long)T0 * T1) return;  // whole wave; the kernel has no workgroup barrier
+  const int n = blockIdx.y;
+  const int oc0 = rowi / T1, oc1 = rowi % T1;
+  const long long TV = (long long)T0 * T1 * T2;
+  float* di = dst_img + (long long)n * C * TV + (long long)rowi * T2;
+  short* dsg = dst_seg + (long long)n * TV + (long long)rowi * T2;
+  const double* p = params + (size_t)n * AFFINE_STRIDE;
+  const SrcView<short> v = view_arena<C>(src_img, src_seg, seg_elems, table, n_cases, p);
+  const bool deform = p[7] == 3.0;
+  bool ok = v.ok && (deform || p[7] == 0.0);
+  int L = 0;
+  long long loff = 0;
+  if (ok && deform) {  // L is one of 4 .. 16 and the 3 L^3 doubles lie inside [0, lattices_len)
+    ok = p[9] >= (double)DEFORM_MIN_L && p[9] <= (double)DEFORM_MAX_L && p[8] >= 0.0 && p[8] <= (double)lattices_len;
+    if (ok) {
+      L = (int)p[9];
+      loff = (long long)p[8];
+      ok = p[9] == (double)L && loff + 3LL * L * L * L <= lattices_len;
+    }
+  }
+  if (!ok) {
+    row_zeros<C>(di, dsg, TV, T2, lane);
+    return;
+  }
+  const int T[3] = {T0, T1, T2};
+  int dsh[3];  // windows null: the centred fit's shift
+#pragma unroll
+  for (int a = 0; a < 3; ++a) dsh[a] = fit_shift(windows ? windows + 3 * (long long)n + a : nullptr, v.dims[a], T[a]);
+  const int q0 = fit_src<true>(oc0, dsh[0], v.dims[0]), q1 = fit_src<true>(oc1, dsh[1], v.dims[1]);
+  if (!deform) {
+    row_copy<C>(v, p, q0, q1, dsh[2], di, dsg, TV, T2, lane);
+    return;
+  }
+  double* R = rows_r[threadIdx.x >> 6];
+  {
+    const SplineTaps s0 = spline_taps(q0, v.dims[0], L), s1 = spline_taps(q1, v.dims[1], L);
+    const int m = lane >> 4, k2 = lane & 15;
+    if (m < 3 && k2 < L) {  // cell + 3 <= L - 1 on both axes and k2 <= L - 1: inside the sample's 3 L^3 doubles
+      const double* P = lattices + loff + (((long long)m * L + s0.cell) * L + s1.cell) * L + k2;
+      double r = 0.0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        double in = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) in = in + s0.b[i] * P[(i * L + j) * L];
+        r = r + s1.b[j] * in;
+      }
+      R[lane] = r;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // (a wave's LDS operations execute in order; this only pins the compiler's order)
+  // the row's "nearest" is scipy's own, as warp_kernel's
+  const int rb = row_boundary(p), mode = rb == boundary::NEAREST ? boundary::NEAREST_UNCLAMPED : rb;
+  const float cval = apply_ops(0.0f, p);  // scipy's constant: cval for image and mask alike, the operations still apply
+  for (int x = lane; x < T2; x += 64) {
+    const int q[3] = {q0, q1, fit_src<true>(x, dsh[2], v.dims[2])};
+    const SplineTaps s2 = spline_taps(q[2], v.dims[2], L);
+    AxisTaps t[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      double d = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d = d + s2.b[k] * R[16 * m + s2.cell + k];
+      t[m] = axis_taps((double)q[m] + d, v.dims[m], mode);
+    }
+    if (t[0].outside || t[1].outside || t[2].outside) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) di[c * TV + x] = cval;
+      dsg[x] = 0;
+      continue;
+    }
+    long long r1[2][2], col[2], r0;
+    tap_offsets(v, t, r1, col, r0);
+    double acc[C];
+    trilinear<C>(v.si, v.V, r1, col, t[0].w, t[1].w, t[2].w, acc);
+#pragma unroll
+    for (int c = 0; c < C; ++c) di[c * TV + x] = apply_ops((float)acc[c], p);
+    dsg[x] = v.ss[r0];
+  }
+}
+
+int augment_deform(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+                   int n_cases, const double* params, const double* lattices, long long lattices_len, const int* windows,
+                   int N, int T0, int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
+  if (!arena_img || !arena_seg || !table || !params || !lattices || !dst_img || !dst_seg || seg_elems <= 0 ||
+      lattices_len <= 0 || C < 1 || C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
+    return MSL_ERR_ARG;
+  const long long rows = (long long)T0 * T1;
+  if (N > 65535 || rows > 0x7FFFFFFFLL - WARP_WAVES) return MSL_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((rows + WARP_WAVES - 1) / WARP_WAVES), N);
+  hipStream_t st = (hipStream_t)stream;
+  return msl::dispatch_int<1, 2, 3, 4>(C, [&](auto ch) {
+    MSL_LAUNCH(deform_kernel<decltype(ch)::value>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table,
+               n_cases, params, lattices, lattices_len, windows, T0, T1, T2, dst_img, dst_seg);
     MSL_LAUNCH_CHECK();
     return MSL_OK;
   });
@@ -1122,6 +1281,14 @@ int msl_augment_warp_mc(const float* arena_img, const short* arena_seg, long lon
                         short* dst_seg, void* stream) {
   return augment_warp(arena_img, arena_seg, seg_elems, C, table, n_cases, params, coords, coords_len, windows, N, T0, T1,
                       T2, dst_img, dst_seg, stream);
+}
+
+int msl_augment_deform_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                          const long long* table, int n_cases, const double* params, const double* lattices,
+                          long long lattices_len, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
+                          short* dst_seg, void* stream) {
+  return augment_deform(arena_img, arena_seg, seg_elems, C, table, n_cases, params, lattices, lattices_len, windows, N, T0,
+                        T1, T2, dst_img, dst_seg, stream);
 }
 
 size_t msl_instance_boxes_workspace_bytes(int N) { return N > 0 && N <= 65535 ? inst_ws_bytes(N) : 0; }

@@ -1,4 +1,4 @@
-// The sampling core of datapipe.hip's five resampling kernels (resample, affine, fit / window, warp, regrid): a parameter
+// The sampling core of datapipe.hip's six resampling kernels (resample, affine, fit / window, warp, deform, regrid): a parameter
 // row's decode, the permuted view of its source, one axis coordinate's taps, the eight-corner sum, the intensity
 // operations and the four-wide store, once each.  Everything follows scipy's NI_GeometricTransform for order 1 (image) /
 // order 0 (mask) operation by operation in f64, so the including file is built with FMA contraction off; the host mirror

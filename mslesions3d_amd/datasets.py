@@ -251,9 +251,13 @@ def _warp(img, seg, tables, mode, padding_mode):
     """The (image, mask) pair sampled at ``np.meshgrid(t0, t1, t2, indexing="ij")``: per channel
     ``scipy.ndimage.map_coordinates`` of the f32 channel, order 1 (bilinear) / 0 (nearest), cast back as ``_aug_affine``
     casts."""
+    return _sample_at(img, seg, np.meshgrid(*tables, indexing="ij"), mode, padding_mode)
+
+
+def _sample_at(img, seg, coords, mode, padding_mode):
+    """The (image, mask) pair sampled at three dense f64 coordinate arrays, as ``_warp`` states it."""
     from scipy.ndimage import map_coordinates
     pad = SCIPY_BOUNDARY[padding_mode]
-    coords = np.meshgrid(*tables, indexing="ij")
     outs = []
     for a, m in ((img, mode[0]), (seg, mode[1])):
         order = 1 if m == "bilinear" else 0
@@ -281,6 +285,124 @@ def warp_tables(name, draw, shape, kw):
     if name == "zoom":
         return [zoom_table(n, draw) for n in shape]
     return [grid_table(n, kw.get("num_cells", 5), s) for n, s in zip(shape, draw)]
+
+
+# Rand3DElasticd / RandomElasticDeformation ('elastic3d'): a dense, smooth, non-rigid deformation (DESIGN.md section
+# 4.15).  MONAI and TorchIO are absent: the contract below is this project's own and its parity is NOT pinned.  A lattice
+# P of (3, L, L, L) f64 coefficients spans the volume with one control point of margin at either end; output voxel q
+# samples the input at q + d(q), d_m the cubic B-spline of P[m].  Every operation is one rounded f64 operation in a fixed
+# order, so that msl_augment_deform_mc (csrc/datapipe.hip) forms the same coordinates.
+
+DEFORM_POINTS = (4, 16)  # control points per axis: a cubic needs four, the kernel's row buffer holds sixteen
+
+
+def _check_elastic3d(control_points, max_displacement):
+    lo, hi = DEFORM_POINTS
+    if int(control_points) != control_points or not lo <= control_points <= hi:
+        raise ValueError(f"elastic3d: control_points must be one of {lo} .. {hi}, got {control_points}")
+    if not (np.isfinite(max_displacement) and max_displacement > 0):
+        raise ValueError(f"elastic3d: max_displacement must be positive and finite, got {max_displacement}")
+
+
+def _draw_elastic3d(rs, control_points=7, max_displacement=7.5, mode=("bilinear", "nearest"), padding_mode="border",
+                    prob=0.1):
+    """The random draws of ``_aug_elastic3d`` -> uniform(-1, 1) of shape (3, L, L, L) (f64), or None."""
+    _check_elastic3d(control_points, max_displacement)
+    if rs.rand() >= prob:
+        return None
+    L = int(control_points)
+    return rs.uniform(-1.0, 1.0, (3, L, L, L))
+
+
+def deform_lattice(shape, draw, max_displacement):
+    """A draw of ``_draw_elastic3d`` on a volume of ``shape`` -> the lattice P = draw * A (f64, (3, L, L, L); component m
+    displaces along axis m).  A = min(max_displacement, min_a spacing_a / 4) with spacing_a = (n_a - 1) / (L - 3) over
+    the axes of two voxels or more; an axis of one voxel has its component zeroed, and A = 0 without any other axis.
+    The cap keeps the map q -> q + d(q) from folding: a cubic B-spline of coefficients bounded by A has derivatives
+    bounded by A / spacing <= 1 / 4 per axis (sup_t sum_i |B_i'(t)| = 1), so the gradient of d has norm below 1."""
+    draw = np.asarray(draw, dtype=np.float64)
+    shape = tuple(int(n) for n in shape)
+    if draw.ndim != 4 or draw.shape[0] != 3 or len(set(draw.shape[1:])) != 1 or len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"deform_lattice: a (3, L, L, L) draw and three positive sizes expected, got {draw.shape}, {shape}")
+    L = draw.shape[1]
+    _check_elastic3d(L, max_displacement)
+    spacing = [(n - 1) / (L - 3) for n in shape if n >= 2]
+    A = min(float(max_displacement), min(spacing) / 4) if spacing else 0.0
+    P = draw * A
+    for m, n in enumerate(shape):
+        if n == 1:
+            P[m] = 0.0
+    return P
+
+
+def _spline_taps(q, n, L):
+    """One axis of the deformation's contract at the positions ``q`` (f64 array; whole voxels or not) of an axis of n
+    voxels -> (cell, [b0, b1, b2, b3]): u = q * (L - 3) / (n - 1) (the product first; 0.0 where n == 1), cell =
+    min(floor(u), L - 4) (and at least 0), t = u - cell (1.0 exactly at the last voxel), then the four cubic B-spline
+    weights, operation by operation as written."""
+    q = np.asarray(q, dtype=np.float64)
+    u = q * float(L - 3) / float(n - 1) if n > 1 else np.zeros_like(q)
+    cell = np.clip(np.floor(u), 0, L - 4).astype(np.int64)
+    t = u - cell
+    t2 = t * t
+    t3 = t2 * t
+    s = 1.0 - t
+    return cell, [((s * s) * s) / 6.0,
+                  (((3.0 * t3) - (6.0 * t2)) + 4.0) / 6.0,
+                  ((((-3.0 * t3) + (3.0 * t2)) + (3.0 * t)) + 1.0) / 6.0,
+                  t3 / 6.0]
+
+
+def deform_coords(shape, P):
+    """-> the three f64 coordinate arrays of ``shape``: voxel q samples at c_m = q_m + d_m(q) with, per component m,
+    R_m[k2] = sum_j b1[j] * (sum_i b0[i] * P[m][cell0 + i][cell1 + j][k2]) (a function of the row (q_0, q_1) alone) and
+    d_m = sum_k b2[k] * R_m[cell2 + k]; every sum starts at 0.0 and ascends, each term as sum = sum + (weight * value)."""
+    P = np.asarray(P, dtype=np.float64)
+    shape = tuple(int(n) for n in shape)
+    L = P.shape[1]
+    (c0, b0), (c1, b1), (c2, b2) = [_spline_taps(np.arange(n), n, L) for n in shape]
+    out = []
+    for m in range(3):
+        R = np.zeros((shape[0], shape[1], L))
+        for j in range(4):
+            inner = np.zeros((shape[0], shape[1], L))
+            for i in range(4):
+                inner = inner + b0[i][:, None, None] * P[m][c0 + i][:, c1 + j, :]
+            R = R + b1[j][None, :, None] * inner
+        d = np.zeros(shape)
+        for k in range(4):
+            d = d + b2[k][None, None, :] * R[:, :, c2 + k]
+        out.append(np.arange(shape[m], dtype=np.float64).reshape([-1 if a == m else 1 for a in range(3)]) + d)
+    return out
+
+
+def deform_displacement(shape, P, q):
+    """d(q) (K, 3) f64 at the positions ``q`` (K, 3) f64 of a volume of ``shape``, whole voxels or not: the spline of
+    ``deform_coords`` in the same nesting (at whole voxels, its values)."""
+    P = np.asarray(P, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64).reshape(-1, 3)
+    L = P.shape[1]
+    (c0, b0), (c1, b1), (c2, b2) = [_spline_taps(q[:, a], shape[a], L) for a in range(3)]
+    d = np.zeros_like(q)
+    for m in range(3):
+        for k in range(4):
+            R = np.zeros(q.shape[0])
+            for j in range(4):
+                inner = np.zeros(q.shape[0])
+                for i in range(4):
+                    inner = inner + b0[i] * P[m][c0 + i, c1 + j, c2 + k]
+                R = R + b1[j] * inner
+            d[:, m] = d[:, m] + b2[k] * R
+    return d
+
+
+def _aug_elastic3d(img, seg, rs, control_points=7, max_displacement=7.5, mode=("bilinear", "nearest"),
+                   padding_mode="border", prob=0.1):
+    d = _draw_elastic3d(rs, control_points, max_displacement, mode, padding_mode, prob)
+    if d is None:
+        return img, seg
+    shape = img.shape[1:]
+    return _sample_at(img, seg, deform_coords(shape, deform_lattice(shape, d, max_displacement)), mode, padding_mode)
 
 
 # RandGaussianSmoothd / RandBiasFieldd / RandGaussianNoised (the MR stage, DESIGN.md section 4.14): resolution loss, coil
@@ -500,11 +622,11 @@ def _aug_gaussiannoise(img, seg, rs, **kw):
 
 
 AUGMENTATIONS = {"flip": _aug_flip, "rotate90": _aug_rotate90, "affine": _aug_affine,
-                 "zoom": _aug_zoom, "griddistortion": _aug_griddistortion,
+                 "zoom": _aug_zoom, "griddistortion": _aug_griddistortion, "elastic3d": _aug_elastic3d,
                  "shiftintensity": _aug_shiftintensity, "scaleintensity": _aug_scaleintensity,
                  "gaussiansmooth": _aug_gaussiansmooth, "biasfield": _aug_biasfield, "gaussiannoise": _aug_gaussiannoise}
 DRAWS = {"flip": _draw_flip, "rotate90": _draw_rotate90, "affine": _draw_affine,
-         "zoom": _draw_zoom, "griddistortion": _draw_griddistortion,
+         "zoom": _draw_zoom, "griddistortion": _draw_griddistortion, "elastic3d": _draw_elastic3d,
          "shiftintensity": _draw_shiftintensity, "scaleintensity": _draw_scaleintensity,
          "gaussiansmooth": _draw_gaussiansmooth, "biasfield": _draw_biasfield, "gaussiannoise": _draw_gaussiannoise}
 MR_NAMES = ("gaussiansmooth", "biasfield", "gaussiannoise")
@@ -567,6 +689,9 @@ def select_augmentations(names):
 # project's choosing, MONAI's defaults for the ranges
 WARP_AUGMENTATIONS = [("zoom", {"min_zoom": 0.9, "max_zoom": 1.1, "padding_mode": "border", "prob": 0.5}),
                       ("griddistortion", {"num_cells": 5, "distort_limit": 0.03, "padding_mode": "border", "prob": 0.5})]
+# the free-form deformation: a 7^3 lattice, at most 7.5 voxels (the cap of ``deform_lattice``
+# binds first on axes shorter than 121 voxels)
+DEFORM_AUGMENTATIONS = [("elastic3d", {"control_points": 7, "max_displacement": 7.5, "padding_mode": "border", "prob": 0.2})]
 INTENSITY_NAMES = ("shiftintensity", "scaleintensity")
 # the MR acquisition stage, in acquisition order: resolution loss, coil inhomogeneity, thermal
 # noise; MONAI's names and default ranges as remembered
@@ -578,16 +703,18 @@ MR_AUGMENTATIONS = [("gaussiansmooth", {"sigma": (0.25, 1.5), "prob": 0.1}),
 def select_training_augmentations(names):
     """What ``train.py -a`` binds: ``select_augmentations`` for the reference's names, unchanged, plus the entries of
     ``WARP_AUGMENTATIONS`` that were asked for, in that list's order, behind the flips / rot90s / affines and in front of
-    the intensity operations (the order ``devicedata.sample_params`` takes), plus the entries of ``MR_AUGMENTATIONS`` that
-    were asked for, in that list's order, behind everything else.  Unknown names raise ValueError."""
-    warp = [n for n, _ in WARP_AUGMENTATIONS]
-    known = [n for n, _ in REFERENCE_AUGMENTATIONS + LESIONS_AUGMENTATIONS] + warp + list(MR_NAMES)
+    the intensity operations (the order ``devicedata.sample_params`` takes), the entry of ``DEFORM_AUGMENTATIONS`` behind
+    those, plus the entries of ``MR_AUGMENTATIONS`` that were asked for, in that list's order, behind everything else.
+    Unknown names raise ValueError."""
+    resample = WARP_AUGMENTATIONS + DEFORM_AUGMENTATIONS
+    own = [n for n, _ in resample] + list(MR_NAMES)
+    known = [n for n, _ in REFERENCE_AUGMENTATIONS + LESIONS_AUGMENTATIONS] + own
     unknown = set(names) - set(known)
     if unknown:
         raise ValueError(f"unknown augmentation(s) {sorted(unknown)}; known: {' '.join(dict.fromkeys(known))}")
-    out = select_augmentations([n for n in names if n not in warp and n not in MR_NAMES])
+    out = select_augmentations([n for n in names if n not in own])
     at = next((k for k, (n, _) in enumerate(out) if n in INTENSITY_NAMES), len(out))
-    out = out[:at] + [(n, kw) for n, kw in WARP_AUGMENTATIONS if n in names] + out[at:]
+    out = out[:at] + [(n, kw) for n, kw in resample if n in names] + out[at:]
     return out + [(n, kw) for n, kw in MR_AUGMENTATIONS if n in names]
 
 
@@ -978,8 +1105,9 @@ def centres_to_augmented(centres, shape, perm, stages=()):
     stage, in order, q = solve(M, c' - offset): the inverse of "output voxel q samples at M q + offset" (f64).  Per warp
     stage (``tables``: output voxel q samples at t_a[q_a]), per axis the smallest real q in [0, n' - 1] with t(q) = c',
     t being the table under linear interpolation: i = np.searchsorted(t, c', "left"), q = i - 1 + (c' - t[i - 1]) /
-    (t[i] - t[i - 1]), and 0 / n' - 1 where c' lies at or below t[0] / above t[n' - 1].  Stages without a matrix or tables
-    (None, intensity operations) do not move a point."""
+    (t[i] - t[i - 1]), and 0 / n' - 1 where c' lies at or below t[0] / above t[n' - 1].  Per deformation stage
+    (``lattice``: output voxel q samples at q + d(q)) the fixed point of ``_deform_inverse``.  Stages without a matrix,
+    tables or a lattice (None, intensity operations) do not move a point."""
     c = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
     ax, rev = perm
     out = np.empty_like(c)
@@ -991,7 +1119,20 @@ def centres_to_augmented(centres, shape, perm, stages=()):
                                   (out - np.asarray(st.offset, dtype=np.float64)).T).T
         elif hasattr(st, "tables") and out.shape[0]:
             out = np.stack([_table_inverse(st.tables[a], out[:, a]) for a in range(3)], 1)
+        elif hasattr(st, "lattice") and out.shape[0]:
+            out = _deform_inverse(st.lattice, tuple(shape[ax[a]] for a in range(3)), out)
     return out
+
+
+def _deform_inverse(P, shape, c):
+    """``centres_to_augmented``'s rule for a deformation stage: the q with q + d(q) = c', by q_0 = c' and q_{k+1} =
+    clip(c' - d(q_k), 0, n' - 1), 30 times (f64).  ``deform_lattice``'s cap makes d a contraction, so the iteration
+    converges to the one solution."""
+    hi = np.asarray(shape, dtype=np.float64) - 1.0
+    q = c
+    for _ in range(30):
+        q = np.clip(c - deform_displacement(shape, P, q), 0.0, hi)
+    return q
 
 
 def _table_inverse(table, c):

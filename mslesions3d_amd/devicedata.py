@@ -22,7 +22,9 @@ device form of ``datasets.regrid``, bit for bit) in front of the foreground box.
 training) gets one sampled window per case and epoch instead of the fit, and validation tiles
 (msl_augment_window_mc with the origins ``datasets.patch_origin`` / ``datasets.view_plan`` give on the host).  A batch in
 which some sample drew a zoom / griddistortion (a ``WarpStage``: three per-axis coordinate tables, DESIGN.md section
-4.13) goes through msl_augment_warp_mc instead, on either route; ``DeviceCache`` refuses the two names.  An augmentation
+4.13) goes through msl_augment_warp_mc instead, on either route; ``DeviceCache`` refuses the two names.  A batch in
+which some sample drew an elastic3d (a ``DeformStage``: a cubic B-spline lattice) goes through
+msl_augment_deform_mc in the same way.  An augmentation
 list that names gaussiansmooth / biasfield / gaussiannoise (the MR stage) adds msl_augment_mr
 (csrc/mraug.hip) behind the batch build of either cache: ``mr_tables`` lowers the draws, ``MRStageRunner`` launches.
 """
@@ -35,8 +37,8 @@ from os.path import join as pjoin
 from . import _lib
 from ._lib import ptr
 from .datasets import (MR_MAX_RADIUS, MR_NAMES, SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset,
-                       bias_lattice, centres_to_augmented, draw_augmentations, gaussian_taps, patch_origin, regrid_plan,
-                       sample_rng, transform_name, view_plan, warp_tables)
+                       bias_lattice, centres_to_augmented, deform_coords, deform_lattice, draw_augmentations,
+                       gaussian_taps, patch_origin, regrid_plan, sample_rng, transform_name, view_plan, warp_tables)
 
 PARAM_STRIDE = 16  # f64 per sample of msl_augment_resample
 AFFINE_STRIDE = 32  # f64 per sample of msl_augment_affine
@@ -53,7 +55,11 @@ IntensityOp = namedtuple("IntensityOp", "kind value")
 # case (output voxel q samples at t_a[q_a]), and the boundary code
 WarpStage = namedtuple("WarpStage", "tables boundary")
 WARP_NAMES = ("zoom", "griddistortion")
-ROW_COPY, ROW_AFFINE, ROW_WARP = 0.0, 1.0, 2.0  # field [7] of a parameter row
+# a stage msl_augment_deform_mc runs (elastic3d): the (3, L, L, L) f64 lattice of ``datasets.deform_lattice`` for the
+# permuted case (output voxel q samples at q + d(q)) and the boundary code
+DeformStage = namedtuple("DeformStage", "lattice boundary")
+DEFORM_NAMES = ("elastic3d",)
+ROW_COPY, ROW_AFFINE, ROW_WARP, ROW_DEFORM = 0.0, 1.0, 2.0, 3.0  # field [7] of a parameter row
 # an MR transform of the augmentation list (gaussiansmooth / biasfield / gaussiannoise): its name,
 # its draw (``datasets.DRAWS[name]``'s result; None: not drawn) and its keyword arguments.  msl_augment_mr runs them on
 # the built batch; the batch build itself does not see them
@@ -161,7 +167,8 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
     ``ragged`` (msl_augment_fit): a rot90 may change the shape, and every affine stage is an ``AffineStage`` computed
     for the permuted shape.  A drawn zoom / griddistortion is a ``WarpStage`` with the tables of the permuted shape
     (``ragged`` only; padding "border" unless the entry says otherwise); it is a resampling stage like an affine: behind
-    the flips / rot90s, in front of the intensity operations.  gaussiansmooth / biasfield / gaussiannoise are the last
+    the flips / rot90s, in front of the intensity operations.  A drawn elastic3d is a ``DeformStage`` with the lattice of
+    the permuted shape, under the same rules.  gaussiansmooth / biasfield / gaussiannoise are the last
     group: each appends an ``MRStage`` (drawn or not), which moves no point and which the batch build skips
     (``mr_tables`` lowers them for msl_augment_mr); any other entry behind one of them raises NotImplementedError."""
     axis, rev = [0, 1, 2], [0, 0, 0]
@@ -207,6 +214,19 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
             else:  # the permutation is final here, as for an affine
                 stages.append(WarpStage(warp_tables(name, d, tuple(shape[a] for a in axis), kw),
                                         BOUNDARY[kw.get("padding_mode", "border")]))
+            continue
+        if name in DEFORM_NAMES:
+            if n_ops:
+                raise NotImplementedError("device pipeline: a deformation stage after an intensity operation")
+            if not ragged:
+                raise NotImplementedError("device pipeline: elastic3d on the example cache")
+            t = augmentations[k] if augmentations is not None else name
+            kw = {} if isinstance(t, str) else t[1]
+            if d is None:
+                stages.append(None)
+            else:  # the permutation is final here, as for an affine
+                stages.append(DeformStage(deform_lattice(tuple(shape[a] for a in axis), d, kw.get("max_displacement", 7.5)),
+                                          BOUNDARY[kw.get("padding_mode", "border")]))
             continue
         if name in ("shiftintensity", "scaleintensity"):
             n_ops += 1
@@ -298,8 +318,16 @@ def warp_numpy(vol, tables, order, boundary):
                          NEAREST_UNCLAMPED if boundary == BOUNDARY["border"] else boundary)
 
 
+def deform_numpy(vol, P, order, boundary):
+    """Host mirror of msl_augment_deform_mc's resample of one (D, H, W) volume, operation by operation in f64: output
+    voxel q has the coordinates ``datasets.deform_coords(vol.shape, P)``; from there ``warp_numpy``'s sampling, "border"
+    (1) as scipy computes "nearest"."""
+    return _sample_numpy(vol, deform_coords(vol.shape, P), order,
+                         NEAREST_UNCLAMPED if boundary == BOUNDARY["border"] else boundary)
+
+
 def _sample_numpy(vol, coords, order, boundary):
-    """The tail ``affine_numpy`` and ``warp_numpy`` share: ``vol`` sampled at the three f64 coordinate arrays (one output
+    """The tail ``affine_numpy``, ``warp_numpy`` and ``deform_numpy`` share: ``vol`` sampled at the three f64 coordinate arrays (one output
     grid), from the boundary map on."""
     dims = vol.shape
     odims = coords[0].shape
@@ -418,6 +446,8 @@ class DeviceCache:
         self.augmentations = list(dataset.train_dataset.augmentations)
         if any((t if isinstance(t, str) else t[0]) in WARP_NAMES for t in self.augmentations):
             raise NotImplementedError("device pipeline: zoom / griddistortion on the example cache")
+        if any(transform_name(t) in DEFORM_NAMES for t in self.augmentations):
+            raise NotImplementedError("device pipeline: elastic3d on the example cache")
         tr, te = dataset.train_dataset, dataset.test_dataset
         if dataset.world_size > 1:
             val_idx = ShardSampler(len(te), dataset.rank, dataset.world_size, False, dataset.random_state).indices()
@@ -651,9 +681,7 @@ def _box_stage(dataset, N, shape, capacity, dev, max_runs_per_image=MAX_RUNS_PER
 def fit_rows(cases, per_sample):
     """-> (N, AFFINE_STRIDE) f64 rows of one msl_augment_fit launch: per sample its case and the (perm, stages) of
     ``sample_params(..., ragged=True)``: at most one affine stage, then the intensity operations."""
-    rows, coords = warp_rows(cases, per_sample)
-    if coords.size:
-        raise ValueError("fit_rows: a sample drew a warp stage; warp_rows returns its tables with the rows")
+    rows, tables = _stage_rows(cases, per_sample, ())
     return rows
 
 
@@ -662,6 +690,21 @@ def warp_rows(cases, per_sample):
     sample whose one resampling stage is a ``WarpStage`` has [7] = ROW_WARP, at [8] the offset of its three tables in
     ``coords`` (concatenated, axis 0 first) and at [20] the boundary.  Without a warp drawn ``coords`` is empty and the rows
     are those of msl_augment_fit_mc / msl_augment_window_mc."""
+    return _stage_rows(cases, per_sample, (WarpStage,))
+
+
+def deform_rows(cases, per_sample):
+    """-> ((N, AFFINE_STRIDE) f64 rows, f64 lattices) of one msl_augment_deform_mc launch: ``fit_rows``'s rows, where a
+    sample whose one resampling stage is a ``DeformStage`` has [7] = ROW_DEFORM, at [8] the offset of its 3 L^3
+    coefficients in ``lattices`` (concatenated, C order), at [9] L and at [20] the boundary.  Without a deformation drawn
+    ``lattices`` is empty and the rows are those of msl_augment_fit_mc / msl_augment_window_mc."""
+    return _stage_rows(cases, per_sample, (DeformStage,))
+
+
+def _stage_rows(cases, per_sample, own):
+    """The rows of one launch and the f64 table that rides with them: the tables of the ``WarpStage``s or the lattices of
+    the ``DeformStage``s, whichever of the two ``own`` names.  A stage with a table that is not the launch's own raises
+    ValueError."""
     rows = np.zeros((len(cases), AFFINE_STRIDE), dtype=np.float64)
     coords, at = [], 0
     for n, (case, (perm, stages)) in enumerate(zip(cases, per_sample)):
@@ -670,11 +713,19 @@ def warp_rows(cases, per_sample):
             raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
         st = geo[0] if geo else None
         ops = [x for x in stages if isinstance(x, IntensityOp)]
+        if isinstance(st, (WarpStage, DeformStage)) and not isinstance(st, own):
+            raise ValueError(f"a sample drew a {type(st).__name__}: warp_rows / deform_rows return its table with the rows")
         if isinstance(st, WarpStage):
             rows[n] = affine_row(case, perm, None, ops)
             rows[n, 7], rows[n, 8], rows[n, 20] = ROW_WARP, at, st.boundary
             coords += [np.asarray(t, dtype=np.float64) for t in st.tables]
             at += sum(len(t) for t in st.tables)
+        elif isinstance(st, DeformStage):
+            P = np.ascontiguousarray(st.lattice, dtype=np.float64)
+            rows[n] = affine_row(case, perm, None, ops)
+            rows[n, 7], rows[n, 8], rows[n, 9], rows[n, 20] = ROW_DEFORM, at, P.shape[1], st.boundary
+            coords.append(P.reshape(-1))
+            at += P.size
         else:
             rows[n] = affine_row(case, perm, st, ops)
     return rows, (np.concatenate(coords) if coords else np.zeros(0, dtype=np.float64))
@@ -751,10 +802,10 @@ class MRStageRunner:
 
 def check_ragged_pipeline(augmentations):
     """What ``LesionCache`` refuses at construction, drawn or not: more than one resampling stage (affine / zoom /
-    griddistortion: a resample of a resample of a ragged case would need a ragged intermediate) and the order limits of
+    griddistortion / elastic3d: a resample of a resample of a ragged case would need a ragged intermediate) and the order limits of
     ``sample_params``.  NotImplementedError."""
     names = [(t if isinstance(t, str) else t[0]) for t in augmentations]
-    if sum(n == "affine" or n in WARP_NAMES for n in names) > 1:
+    if sum(n == "affine" or n in WARP_NAMES or n in DEFORM_NAMES for n in names) > 1:
         raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
     sample_params([(n, None) for n in names], (1, 1, 1), augmentations, ragged=True)
 
@@ -832,8 +883,8 @@ class LesionCache:
     cropped cases are staged in tensors of their own until the arena's size is known.  A pipeline with two resampling
     stages (affine / zoom / griddistortion entries, ``check_ragged_pipeline``) raises NotImplementedError (a resample of
     a resample of a ragged case would need a ragged intermediate).  A batch in which a sample drew a warp is written by
-    msl_augment_warp_mc (the tables ride behind the rows in the batch's one pinned upload); every other batch by the
-    launch it always had.
+    msl_augment_warp_mc (the tables ride behind the rows in the batch's one pinned upload), one in which a sample drew an
+    elastic3d by msl_augment_deform_mc (the lattices ride there); every other batch by the launch it always had.
 
     With C = len(dataset.input_images) a case is C contiguous f32 planes starting at element C * offset of the image
     arena (the mask arena and the table are the same for every C): boxed as the union of the channels by
@@ -983,11 +1034,13 @@ class LesionCache:
 
     def _run(self, slots, per_sample, b, windows=None):
         stream = _stream(self.device)
-        rows, coords = warp_rows(slots, per_sample)
+        # one resampling entry per pipeline: a batch holds warp stages or deformation stages, never both
+        deform = any(isinstance(st, DeformStage) for _, stages in per_sample for st in stages)
+        rows, coords = (deform_rows if deform else warp_rows)(slots, per_sample)
         # with the MR stage behind it the build writes the stage's source; "img" stays the batch's fixed output
         built = b["built"] if "mr" in b and any(isinstance(st, MRStage) for _, stages in per_sample for st in stages) \
             else b["img"]
-        if coords.size:  # some sample drew a warp.  One upload: the f64 rows, the tables, then the int32 origins
+        if coords.size:  # some sample drew a warp / deformation.  One upload: the f64 rows, the tables, then the int32 origins
             N = len(slots)
             packed = np.zeros(rows.size + coords.size + (0 if windows is None else (3 * N + 1) // 2), dtype=np.float64)
             packed[:rows.size] = rows.reshape(-1)
@@ -995,8 +1048,9 @@ class LesionCache:
             if windows is not None:
                 packed[rows.size + coords.size:].view(np.int32)[:3 * N] = np.asarray(windows, dtype=np.int32).reshape(-1)
             pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
-            _lib.call("msl_augment_warp_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels,
-                      ptr(self.table), len(self.shapes), ptr(pd), pd.data_ptr() + 8 * rows.size, coords.size,
+            _lib.call("msl_augment_deform_mc" if deform else "msl_augment_warp_mc", ptr(self.img), ptr(self.seg),
+                      self.seg.numel(), self.channels, ptr(self.table), len(self.shapes), ptr(pd),
+                      pd.data_ptr() + 8 * rows.size, coords.size,
                       None if windows is None else pd.data_ptr() + 8 * (rows.size + coords.size), N, *self.target,
                       ptr(built), ptr(b["seg"]), stream)
             self._finish(b, per_sample, stream)

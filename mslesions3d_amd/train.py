@@ -39,7 +39,8 @@ def build_parser():
     p.add_argument('--alpha', type=float, default=1.)
     p.add_argument('-a', '--augmentations', type=str, nargs='*', default=[],
                    help='flip rotate90 translate scale (example recipe); affine shiftintensity scaleintensity (train_lesions); '
-                        'zoom griddistortion (separable warps, one resampling stage per run with -dm lesions -c 1); '
+                        'zoom griddistortion (separable warps) elastic3d (free-form deformation): one resampling stage '
+                        'per run with -dm lesions -c 1; '
                         'gaussiansmooth biasfield gaussiannoise (the MR stage, applied last to the finished sample)')
     p.add_argument('-ld', '--logdir', type=str, default=r'../logs/artificial_dataset')
     p.add_argument('-nw', '--num_workers', type=int, default=0)

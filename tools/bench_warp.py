@@ -53,7 +53,7 @@ class Arena:
         stream = torch.cuda.current_stream().cuda_stream
         args = [self.img.data_ptr(), self.seg.data_ptr(), self.seg.numel(), 1, self.table.data_ptr(), self.table.shape[0],
                 p.data_ptr()]
-        if fn == "msl_augment_warp_mc":
+        if fn in ("msl_augment_warp_mc", "msl_augment_deform_mc"):  # (the deformation's lattices ride where the tables do)
             args += [t.data_ptr(), t.numel(), None]  # windows null: the centred fit
         keep = (p, t)  # the launch reads them: they live as long as the closure
         return lambda: (_lib.call(fn, *args, len(rows), *target, dst_img.data_ptr(), dst_seg.data_ptr(), stream), keep)[0]

@@ -922,24 +922,6 @@ __global__ __launch_bounds__(DP_THREADS) void warp_kernel(
   }
 }
 
-int augment_warp(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
-                 int n_cases, const double* params, const double* coords, long long coords_len, const int* windows, int N,
-                 int T0, int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
-  if (!arena_img || !arena_seg || !table || !params || !coords || !dst_img || !dst_seg || seg_elems <= 0 ||
-      coords_len <= 0 || C < 1 || C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
-    return MSL_ERR_ARG;
-  const long long rows = (long long)T0 * T1;
-  if (N > 65535 || rows > 0x7FFFFFFFLL - WARP_WAVES) return MSL_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)((rows + WARP_WAVES - 1) / WARP_WAVES), N);
-  hipStream_t st = (hipStream_t)stream;
-  return msl::dispatch_int<1, 2, 3, 4>(C, [&](auto ch) {
-    MSL_LAUNCH(warp_kernel<decltype(ch)::value>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table,
-               n_cases, params, coords, coords_len, windows, T0, T1, T2, dst_img, dst_seg);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  });
-}
-
 // ---- free-form deformation (elastic3d): msl_augment_deform_mc ------------------------------------------------------------
 // Host mirrors: datasets.deform_coords / _aug_elastic3d (scipy.ndimage.map_coordinates at q + d(q)) and
 // devicedata.deform_numpy; the contract is DESIGN.md section 4.15.  The arenas, the table, the rows and the outputs are
@@ -1065,19 +1047,22 @@ __global__ __launch_bounds__(DP_THREADS) void deform_kernel(
   }
 }
 
-int augment_deform(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
-                   int n_cases, const double* params, const double* lattices, long long lattices_len, const int* windows,
-                   int N, int T0, int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
-  if (!arena_img || !arena_seg || !table || !params || !lattices || !dst_img || !dst_seg || seg_elems <= 0 ||
-      lattices_len <= 0 || C < 1 || C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
+// The launch of msl_augment_warp_mc / msl_augment_deform_mc, the one-wave-per-row kernels.  kernel_of(ch): the kernel for
+// decltype(ch)::value channels; side / side_len: the f64 table that rides with the rows (coordinate tables / lattices).
+template <typename KernelOf>
+int augment_rows(KernelOf kernel_of, const float* arena_img, const short* arena_seg, long long seg_elems, int C,
+                 const long long* table, int n_cases, const double* params, const double* side, long long side_len,
+                 const int* windows, int N, int T0, int T1, int T2, float* dst_img, short* dst_seg, void* stream) {
+  if (!arena_img || !arena_seg || !table || !params || !side || !dst_img || !dst_seg || seg_elems <= 0 || side_len <= 0 ||
+      C < 1 || C > FIT_MAX_CH || n_cases <= 0 || N <= 0 || T0 <= 0 || T1 <= 0 || T2 <= 0)
     return MSL_ERR_ARG;
   const long long rows = (long long)T0 * T1;
   if (N > 65535 || rows > 0x7FFFFFFFLL - WARP_WAVES) return MSL_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((rows + WARP_WAVES - 1) / WARP_WAVES), N);
   hipStream_t st = (hipStream_t)stream;
   return msl::dispatch_int<1, 2, 3, 4>(C, [&](auto ch) {
-    MSL_LAUNCH(deform_kernel<decltype(ch)::value>, grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table,
-               n_cases, params, lattices, lattices_len, windows, T0, T1, T2, dst_img, dst_seg);
+    MSL_LAUNCH(kernel_of(ch), grid, dim3(DP_THREADS), 0, st, arena_img, arena_seg, seg_elems, table, n_cases, params, side,
+               side_len, windows, T0, T1, T2, dst_img, dst_seg);
     MSL_LAUNCH_CHECK();
     return MSL_OK;
   });
@@ -1279,16 +1264,16 @@ int msl_augment_warp_mc(const float* arena_img, const short* arena_seg, long lon
                         const long long* table, int n_cases, const double* params, const double* coords,
                         long long coords_len, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
                         short* dst_seg, void* stream) {
-  return augment_warp(arena_img, arena_seg, seg_elems, C, table, n_cases, params, coords, coords_len, windows, N, T0, T1,
-                      T2, dst_img, dst_seg, stream);
+  return augment_rows([](auto ch) { return warp_kernel<decltype(ch)::value>; }, arena_img, arena_seg, seg_elems, C, table,
+                      n_cases, params, coords, coords_len, windows, N, T0, T1, T2, dst_img, dst_seg, stream);
 }
 
 int msl_augment_deform_mc(const float* arena_img, const short* arena_seg, long long seg_elems, int C,
                           const long long* table, int n_cases, const double* params, const double* lattices,
                           long long lattices_len, const int* windows, int N, int T0, int T1, int T2, float* dst_img,
                           short* dst_seg, void* stream) {
-  return augment_deform(arena_img, arena_seg, seg_elems, C, table, n_cases, params, lattices, lattices_len, windows, N, T0,
-                        T1, T2, dst_img, dst_seg, stream);
+  return augment_rows([](auto ch) { return deform_kernel<decltype(ch)::value>; }, arena_img, arena_seg, seg_elems, C, table,
+                      n_cases, params, lattices, lattices_len, windows, N, T0, T1, T2, dst_img, dst_seg, stream);
 }
 
 size_t msl_instance_boxes_workspace_bytes(int N) { return N > 0 && N <= 65535 ? inst_ws_bytes(N) : 0; }

@@ -60,6 +60,32 @@ WARP_NAMES = ("zoom", "griddistortion")
 DeformStage = namedtuple("DeformStage", "lattice boundary")
 DEFORM_NAMES = ("elastic3d",)
 ROW_COPY, ROW_AFFINE, ROW_WARP, ROW_DEFORM = 0.0, 1.0, 2.0, 3.0  # field [7] of a parameter row
+# The resampling transforms, by name: the stage type a drawn one becomes, ``fields(draw, permuted shape, kw)`` -> that
+# stage's fields in front of the boundary, the default padding mode, what ``sample_params``'s order error calls it, and
+# whether only the ragged cache runs it
+_Resampler = namedtuple("_Resampler", "stage fields pad what ragged_only")
+RESAMPLERS = {"affine": _Resampler(AffineStage, lambda d, shape, kw: affine_matrix(shape, *d), "reflection",
+                                   "an affine stage", False),
+              "zoom": _Resampler(WarpStage, lambda d, shape, kw: (warp_tables("zoom", d, shape, kw),), "border",
+                                 "a warp stage", True),
+              "griddistortion": _Resampler(WarpStage, lambda d, shape, kw: (warp_tables("griddistortion", d, shape, kw),),
+                                           "border", "a warp stage", True),
+              "elastic3d": _Resampler(DeformStage,
+                                      lambda d, shape, kw: (deform_lattice(shape, d, kw.get("max_displacement", 7.5)),),
+                                      "border", "a deformation stage", True)}
+assert all((RESAMPLERS[n].stage is WarpStage) == (n in WARP_NAMES) and (RESAMPLERS[n].stage is DeformStage) == (n in DEFORM_NAMES)
+           for n in RESAMPLERS)
+
+
+def _example_cache_refusal(name):
+    """The error of a ragged-only transform on the example cache: it names every transform of that stage type."""
+    kin = [n for n, rs in RESAMPLERS.items() if rs.stage is RESAMPLERS[name].stage]
+    return NotImplementedError(f"device pipeline: {' / '.join(kin)} on the example cache")
+
+
+def transform_kw(t):
+    """The keyword arguments of an augmentation list's entry (``datasets.transform_name``'s counterpart)."""
+    return {} if isinstance(t, str) else t[1]
 # an MR transform of the augmentation list (gaussiansmooth / biasfield / gaussiannoise, DESIGN.md section 4.14): its name,
 # its draw (``datasets.DRAWS[name]``'s result; None: not drawn) and its keyword arguments.  msl_augment_mr runs them on
 # the built batch; the batch build itself does not see them
@@ -181,52 +207,28 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
 
     n_mr = 0
     for k, (name, d) in enumerate(draws):
+        kw = transform_kw(augmentations[k]) if augmentations is not None else {}
         if name in MR_NAMES:  # the last group: an MRStage each, drawn or not
-            t = augmentations[k] if augmentations is not None else name
-            stages.append(MRStage(name, d, {} if isinstance(t, str) else t[1]))
+            stages.append(MRStage(name, d, kw))
             if MR_NAMES.index(name) < n_mr:  # one launch carries blur, then bias, then noise
                 raise NotImplementedError(f"device pipeline: {' / '.join(MR_NAMES)} once each, in that order")
             n_mr = MR_NAMES.index(name) + 1
             continue
         if n_mr:
             raise NotImplementedError(f"device pipeline: {name} after an MR transform ({' / '.join(MR_NAMES)} come last)")
-        if name == "affine":
+        if name in RESAMPLERS:
+            rs = RESAMPLERS[name]
             if n_ops:
-                raise NotImplementedError("device pipeline: an affine stage after an intensity operation")
-            t = augmentations[k] if augmentations is not None else name
-            pad = ({} if isinstance(t, str) else t[1]).get("padding_mode", "reflection")
+                raise NotImplementedError(f"device pipeline: {rs.what} after an intensity operation")
+            if rs.ragged_only and not ragged:
+                raise _example_cache_refusal(name)
+            pad = kw.get("padding_mode", rs.pad)
             if d is None:
                 stages.append(None)
-            elif len(d) == 2 and pad == "reflection" and not ragged:
+            elif name == "affine" and len(d) == 2 and pad == "reflection" and not ragged:
                 stages.append((list(d[0]), list(affine_offset(shape, *d))))
             else:  # flips / rot90s come first: the permutation is final, and it keeps the shape unless ragged
-                stages.append(AffineStage(*affine_matrix(tuple(shape[a] for a in axis), *d), BOUNDARY[pad]))
-            continue
-        if name in WARP_NAMES:
-            if n_ops:
-                raise NotImplementedError("device pipeline: a warp stage after an intensity operation")
-            if not ragged:
-                raise NotImplementedError("device pipeline: zoom / griddistortion on the example cache")
-            t = augmentations[k] if augmentations is not None else name
-            kw = {} if isinstance(t, str) else t[1]
-            if d is None:
-                stages.append(None)
-            else:  # the permutation is final here, as for an affine
-                stages.append(WarpStage(warp_tables(name, d, tuple(shape[a] for a in axis), kw),
-                                        BOUNDARY[kw.get("padding_mode", "border")]))
-            continue
-        if name in DEFORM_NAMES:
-            if n_ops:
-                raise NotImplementedError("device pipeline: a deformation stage after an intensity operation")
-            if not ragged:
-                raise NotImplementedError("device pipeline: elastic3d on the example cache")
-            t = augmentations[k] if augmentations is not None else name
-            kw = {} if isinstance(t, str) else t[1]
-            if d is None:
-                stages.append(None)
-            else:  # the permutation is final here, as for an affine
-                stages.append(DeformStage(deform_lattice(tuple(shape[a] for a in axis), d, kw.get("max_displacement", 7.5)),
-                                          BOUNDARY[kw.get("padding_mode", "border")]))
+                stages.append(rs.stage(*rs.fields(d, tuple(shape[a] for a in axis), kw), BOUNDARY[pad]))
             continue
         if name in ("shiftintensity", "scaleintensity"):
             n_ops += 1
@@ -428,6 +430,31 @@ def permute_numpy(vol, perm):
     return np.flip(out, flip) if flip else out
 
 
+# ---- what the two caches share: free functions on a batch's buffer set b and its sample_params results ----------------
+def _drew_mr(per_sample):
+    """Does the batch carry MR draws?  (Validation batches carry none.)  msl_augment_mr runs behind the build of a batch
+    that does and whose buffer set has the stage ("mr" in b: the list names an MR transform)."""
+    return any(isinstance(st, MRStage) for _, stages in per_sample for st in stages)
+
+
+def _batch_nbytes(b):
+    """Device bytes of one batch buffer set."""
+    n = sum(t.numel() * t.element_size() for t in (b["img"], b["seg"], *b.get("tmp", ()), b["box"].ws, b["box"].gb,
+                                                    b["box"].gl))
+    return n + (b["built"].numel() * 4 + b["mr"].ws.numel() if "mr" in b else 0)
+
+
+def _val_batch(b, subjects):
+    """The ``validation_step`` batch of a launched buffer set: one host synchronisation (obj_off, the flag behind it),
+    the image and the per-image box lists cloned out of the fixed buffers.  The callers add their geometry keys."""
+    box = b["box"]
+    off = box.obj_off.cpu().tolist()
+    box.raise_on_overflow(box.flag.item())
+    boxes = [box.gb[off[n]:off[n + 1]].clone() for n in range(len(subjects))]
+    labels = [box.gl[off[n]:off[n + 1]].clone() for n in range(len(subjects))]
+    return {"img": b["img"].clone(), "seg": [boxes, labels], "boxes": boxes, "labels": labels, "subject": list(subjects)}
+
+
 class DeviceCache:
     """The cases of a ``setup()`` ``ExampleDataset`` in HBM (image f32 normalised, mask u8), and the device pipeline that
     turns them into training / validation batches.
@@ -444,10 +471,10 @@ class DeviceCache:
         self.dataset, self.device = dataset, torch.device(device)
         self.n_classes, self.batch_size = int(dataset.n_classes), int(dataset.batch_size)
         self.augmentations = list(dataset.train_dataset.augmentations)
-        if any((t if isinstance(t, str) else t[0]) in WARP_NAMES for t in self.augmentations):
-            raise NotImplementedError("device pipeline: zoom / griddistortion on the example cache")
-        if any(transform_name(t) in DEFORM_NAMES for t in self.augmentations):
-            raise NotImplementedError("device pipeline: elastic3d on the example cache")
+        names = [transform_name(t) for t in self.augmentations]
+        refused = [n for n, rs in RESAMPLERS.items() if rs.ragged_only and n in names]
+        if refused:  # before anything is loaded
+            raise _example_cache_refusal(refused[0])
         tr, te = dataset.train_dataset, dataset.test_dataset
         if dataset.world_size > 1:
             val_idx = ShardSampler(len(te), dataset.rank, dataset.world_size, False, dataset.random_state).indices()
@@ -488,27 +515,20 @@ class DeviceCache:
         self.capacity = int(max_objects_per_image) * self.batch_size
         self.comp_cap = comp_cap or _default_comp_cap(self.capacity)
         self._bufs = {}
-        for name, kw in ((t, {}) if isinstance(t, str) else t for t in self.augmentations):
-            if name == "rotate90":
-                a, b = kw.get("spatial_axes", (0, 1))
+        for t in self.augmentations:
+            if transform_name(t) == "rotate90":
+                a, b = transform_kw(t).get("spatial_axes", (0, 1))
                 if self.shape[a] != self.shape[b]:
                     raise NotImplementedError(f"device pipeline: rot90 over axes {(a, b)} of sizes "
                                               f"{self.shape[a]} != {self.shape[b]} changes the volume's shape")
-        self.n_affine = sum(1 for t in self.augmentations if (t if isinstance(t, str) else t[0]) == "affine")
+        self.n_affine = names.count("affine")
         # the order limits of sample_params hold for the list itself, drawn or not: refuse it here, not at the first batch
-        sample_params([((t if isinstance(t, str) else t[0]), None) for t in self.augmentations], self.shape,
-                      self.augmentations)
+        sample_params([(n, None) for n in names], self.shape, self.augmentations)
 
     # ---- footprint ----------------------------------------------------------------------------------------------------
     def nbytes(self):
         """Device bytes held: the cached cases plus every batch buffer set allocated so far."""
-        n = self.cache_bytes
-        for b in self._bufs.values():
-            n += sum(t.numel() * t.element_size() for t in (b["img"], b["seg"], *b["tmp"], b["box"].ws, b["box"].gb,
-                                                             b["box"].gl))
-            if "mr" in b:
-                n += b["built"].numel() * 4 + b["mr"].ws.numel()
-        return n
+        return self.cache_bytes + sum(_batch_nbytes(b) for b in self._bufs.values())
 
     def footprint(self):
         return (f"DeviceCache: {self.img.shape[0]} cases of {self.shape} on {self.device}: "
@@ -538,7 +558,7 @@ class DeviceCache:
         N = len(slots)
         src_img, src_seg, n_src = self.img, self.seg, self.img.shape[0]
         # with the MR stage behind it the build writes the stage's source; "img" stays the batch's fixed output
-        mr = "mr" in b and any(isinstance(st, MRStage) for _, stages in per_sample for st in stages)
+        mr = "mr" in b and _drew_mr(per_sample)
         at = 0
         for k, (fn, rows) in enumerate(launches):
             last = k == len(launches) - 1
@@ -579,13 +599,7 @@ class DeviceCache:
             chunk = self.val_order[i0:i0 + self.batch_size]
             b = self._buffers(len(chunk))
             self._run([slot for _, slot in chunk], [ident] * len(chunk), b)
-            box = b["box"]
-            off = box.obj_off.cpu().tolist()
-            box.raise_on_overflow(box.flag.item())
-            boxes = [box.gb[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
-            labels = [box.gl[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
-            yield {"img": b["img"].clone(), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
-                   "subject": [s for s, _ in chunk]}
+            yield _val_batch(b, [s for s, _ in chunk])
 
 
 # ---- clinical cases: ragged sources, instance masks (datasets.LesionsDataModule) ---------------------------------------
@@ -731,6 +745,21 @@ def _stage_rows(cases, per_sample, own):
     return rows, (np.concatenate(coords) if coords else np.zeros(0, dtype=np.float64))
 
 
+def pack_launch(rows, table, windows=None):
+    """The one f64 upload of a ragged launch -> (packed, table offset, windows offset), the offsets in f64 elements:
+    the (N, AFFINE_STRIDE) ``rows``, then the f64 ``table`` that rides with them (``warp_rows`` / ``deform_rows``; may be
+    empty), then, where ``windows`` is given, its (N, 3) int32 origins in the doubles behind them (N odd: a last int of
+    0).  Pure numpy; with an empty table and no windows the upload is ``rows.reshape(-1)``."""
+    at_table, at_windows = rows.size, rows.size + table.size
+    n_int = 0 if windows is None else 3 * rows.shape[0]
+    packed = np.zeros(at_windows + (n_int + 1) // 2, dtype=np.float64)
+    packed[:at_table] = rows.reshape(-1)
+    packed[at_table:at_windows] = table
+    if windows is not None:
+        packed[at_windows:].view(np.int32)[:n_int] = np.asarray(windows, dtype=np.int32).reshape(-1)
+    return packed, at_table, at_windows
+
+
 def names_mr(augmentations):
     """Does the augmentation list name gaussiansmooth, biasfield or gaussiannoise?"""
     return any(transform_name(t) in MR_NAMES for t in augmentations)
@@ -804,8 +833,8 @@ def check_ragged_pipeline(augmentations):
     """What ``LesionCache`` refuses at construction, drawn or not: more than one resampling stage (affine / zoom /
     griddistortion / elastic3d: a resample of a resample of a ragged case would need a ragged intermediate) and the order limits of
     ``sample_params``.  NotImplementedError."""
-    names = [(t if isinstance(t, str) else t[0]) for t in augmentations]
-    if sum(n == "affine" or n in WARP_NAMES or n in DEFORM_NAMES for n in names) > 1:
+    names = [transform_name(t) for t in augmentations]
+    if sum(n in RESAMPLERS for n in names) > 1:
         raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
     sample_params([(n, None) for n in names], (1, 1, 1), augmentations, ragged=True)
 
@@ -978,10 +1007,7 @@ class LesionCache:
         shape = self.shapes[slot]
         if not int(np.prod(shape)):
             return np.zeros((0, 3), dtype=np.float64)
-        if self.dataset.segmentation_mode == "binary":
-            out = _BinBoxOut(1, shape, INST_MAX_IDS, self.device, self.max_runs_per_image)
-        else:
-            out = _InstBoxOut(1, shape, self.dataset.thresholds, INST_MAX_IDS, self.device)
+        out = _box_stage(self.dataset, 1, shape, INST_MAX_IDS, self.device, self.max_runs_per_image, "LesionCache")
         out.launch(self.case(slot)[1], _stream(self.device))
         n = out.obj_off.cpu().tolist()[1]  # (synchronises: the flag and the rows are there too)
         out.raise_on_overflow(out.flag.item())
@@ -1003,12 +1029,7 @@ class LesionCache:
     # ---- footprint ----------------------------------------------------------------------------------------------------
     def nbytes(self):
         """Device bytes held: the cached cases plus every batch buffer set allocated so far."""
-        n = self.cache_bytes
-        for b in self._bufs.values():
-            n += sum(t.numel() * t.element_size() for t in (b["img"], b["seg"], b["box"].ws, b["box"].gb, b["box"].gl))
-            if "mr" in b:
-                n += b["built"].numel() * 4 + b["mr"].ws.numel()
-        return n
+        return self.cache_bytes + sum(_batch_nbytes(b) for b in self._bufs.values())
 
     def footprint(self):
         lo, hi = np.min(self.shapes, 0).tolist(), np.max(self.shapes, 0).tolist()
@@ -1033,48 +1054,27 @@ class LesionCache:
         return b
 
     def _run(self, slots, per_sample, b, windows=None):
-        stream = _stream(self.device)
+        stream, N = _stream(self.device), len(slots)
         # one resampling entry per pipeline: a batch holds warp stages or deformation stages, never both
         deform = any(isinstance(st, DeformStage) for _, stages in per_sample for st in stages)
-        rows, coords = (deform_rows if deform else warp_rows)(slots, per_sample)
+        rows, table = (deform_rows if deform else warp_rows)(slots, per_sample)
+        packed, at_table, at_windows = pack_launch(rows, table, windows)
+        pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
+        origins = None if windows is None else pd.data_ptr() + 8 * at_windows
+        if table.size:  # some sample drew a warp / deformation; every other batch keeps the launch it always had
+            entry, own = "msl_augment_deform_mc" if deform else "msl_augment_warp_mc", \
+                (pd.data_ptr() + 8 * at_table, table.size, origins)
+        else:
+            entry, own = ("msl_augment_fit_mc", ()) if windows is None else ("msl_augment_window_mc", (origins,))
         # with the MR stage behind it the build writes the stage's source; "img" stays the batch's fixed output
-        built = b["built"] if "mr" in b and any(isinstance(st, MRStage) for _, stages in per_sample for st in stages) \
-            else b["img"]
-        if coords.size:  # some sample drew a warp / deformation.  One upload: the f64 rows, the tables, then the int32 origins
-            N = len(slots)
-            packed = np.zeros(rows.size + coords.size + (0 if windows is None else (3 * N + 1) // 2), dtype=np.float64)
-            packed[:rows.size] = rows.reshape(-1)
-            packed[rows.size:rows.size + coords.size] = coords
-            if windows is not None:
-                packed[rows.size + coords.size:].view(np.int32)[:3 * N] = np.asarray(windows, dtype=np.int32).reshape(-1)
-            pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
-            _lib.call("msl_augment_deform_mc" if deform else "msl_augment_warp_mc", ptr(self.img), ptr(self.seg),
-                      self.seg.numel(), self.channels, ptr(self.table), len(self.shapes), ptr(pd),
-                      pd.data_ptr() + 8 * rows.size, coords.size,
-                      None if windows is None else pd.data_ptr() + 8 * (rows.size + coords.size), N, *self.target,
-                      ptr(built), ptr(b["seg"]), stream)
-            self._finish(b, per_sample, stream)
-            return
-        if windows is not None:  # one upload: the f64 rows, then the (N, 3) int32 origins in the doubles behind them
-            N = len(slots)
-            packed = np.zeros(rows.size + (3 * N + 1) // 2, dtype=np.float64)
-            packed[:rows.size] = rows.reshape(-1)
-            packed[rows.size:].view(np.int32)[:3 * N] = np.asarray(windows, dtype=np.int32).reshape(-1)
-            pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
-            _lib.call("msl_augment_window_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels,
-                      ptr(self.table), len(self.shapes), ptr(pd), pd.data_ptr() + 8 * rows.size, N, *self.target,
-                      ptr(built), ptr(b["seg"]), stream)
-            self._finish(b, per_sample, stream)
-            return
-        pd = torch.from_numpy(rows.reshape(-1)).pin_memory().to(self.device, non_blocking=True)
-        _lib.call("msl_augment_fit_mc", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table),
-                  len(self.shapes), ptr(pd), len(slots), *self.target, ptr(built), ptr(b["seg"]), stream)
+        built = b["built"] if "mr" in b and _drew_mr(per_sample) else b["img"]
+        _lib.call(entry, ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table), len(self.shapes),
+                  ptr(pd), *own, N, *self.target, ptr(built), ptr(b["seg"]), stream)
         self._finish(b, per_sample, stream)
 
     def _finish(self, b, per_sample, stream):
-        """Behind the batch build: the MR stage on the built images (a batch of a list that names one of the three and
-        carries draws: validation batches carry none), then the box stage."""
-        if "mr" in b and any(isinstance(st, MRStage) for _, stages in per_sample for st in stages):
+        """Behind the batch build: the MR stage on the built images, then the box stage."""
+        if "mr" in b and _drew_mr(per_sample):
             b["mr"].run(b["built"], per_sample, b["img"], stream)
         b["box"].launch(b["seg"], stream)
 
@@ -1103,22 +1103,19 @@ class LesionCache:
 
     step = DeviceCache.step
 
+    def _geometry(self, slots):
+        """The keys ``datasets.fit_to_case_frame`` maps a validation batch's boxes back to the case with."""
+        return {"crop_origin": [self.origins[k] for k in slots], "crop_shape": [tuple(self.shapes[k]) for k in slots],
+                "full_shape": [self.full_shapes[k] for k in slots]}
+
     def _val_tile_batches(self):
         ident = (([0, 1, 2], [0, 0, 0]), [])
         for i0 in range(0, len(self.val_tiles), self.batch_size):
             chunk = self.val_tiles[i0:i0 + self.batch_size]
             b = self._buffers(len(chunk))
             self._run([slot for _, slot, _ in chunk], [ident] * len(chunk), b, [o for _, _, o in chunk])
-            box = b["box"]
-            off = box.obj_off.cpu().tolist()
-            box.raise_on_overflow(box.flag.item())
-            boxes = [box.gb[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
-            labels = [box.gl[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
-            yield {"img": b["img"].clone(), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
-                   "subject": [s for s, _, _ in chunk], "patch_origin": [o for _, _, o in chunk],
-                   "crop_origin": [self.origins[slot] for _, slot, _ in chunk],
-                   "crop_shape": [tuple(self.shapes[slot]) for _, slot, _ in chunk],
-                   "full_shape": [self.full_shapes[slot] for _, slot, _ in chunk]}
+            yield {**_val_batch(b, [s for s, _, _ in chunk]), "patch_origin": [o for _, _, o in chunk],
+                   **self._geometry([slot for _, slot, _ in chunk])}
 
     def val_batches(self):
         """``validation_step`` batches (device tensors, per-image box lists) of this rank's validation shard; in patch
@@ -1131,15 +1128,7 @@ class LesionCache:
             chunk = self.val_order[i0:i0 + self.batch_size]
             b = self._buffers(len(chunk))
             self._run([slot for _, slot in chunk], [ident] * len(chunk), b)
-            box = b["box"]
-            off = box.obj_off.cpu().tolist()
-            box.raise_on_overflow(box.flag.item())
-            boxes = [box.gb[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
-            labels = [box.gl[off[n]:off[n + 1]].clone() for n in range(len(chunk))]
-            yield {"img": b["img"].clone(), "seg": [boxes, labels], "boxes": boxes, "labels": labels,
-                   "subject": [s for s, _ in chunk], "crop_origin": [self.origins[slot] for _, slot in chunk],
-                   "crop_shape": [tuple(self.shapes[slot]) for _, slot in chunk],
-                   "full_shape": [self.full_shapes[slot] for _, slot in chunk]}
+            yield {**_val_batch(b, [s for s, _ in chunk]), **self._geometry([slot for _, slot in chunk])}
 
 
 def boxes_to_case_device(boxes, target, crop_shape, crop_origin, full_shape):

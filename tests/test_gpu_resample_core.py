@@ -1,4 +1,4 @@
-"""The five resampling kernels of csrc/datapipe.hip share one sampling core (csrc/resample.hpp): wherever two entry
+"""The six resampling kernels of csrc/datapipe.hip share one sampling core (csrc/resample.hpp): wherever two entry
 points of the C ABI are handed the same sampling problem in their own parameters, they return the same bytes, image and
 mask.  Each kernel is tested against scipy or its numpy mirror elsewhere; these tests pin the kernels to each other."""
 import functools
@@ -62,8 +62,9 @@ def _fixed(fn, stride, vols, segs, rows):
 
 
 def _ragged(fn, C, shape, rows, target, windows=None, coords=None):
-    """msl_augment_fit_mc / _window_mc / _warp_mc on an arena that holds ``_case(shape)`` as its single case ->
-    (image (N, C) + target f32, mask (N,) + target int64)."""
+    """msl_augment_fit_mc / _window_mc / _warp_mc / _deform_mc on an arena that holds ``_case(shape)`` as its single case
+    -> (image (N, C) + target f32, mask (N,) + target int64).  ``coords``: the f64 table of the last two (coordinate
+    tables / lattices).  The outputs start out non-zero, so a row of zeros was written."""
     img, seg = _case(shape)
     N, target = len(rows), tuple(target)
     ai, asg = _dev(img[:C].reshape(-1), np.float32), _dev(seg.reshape(-1), np.int16)
@@ -71,10 +72,10 @@ def _ragged(fn, C, shape, rows, target, windows=None, coords=None):
     p = _dev(np.stack(rows), np.float64)
     w = None if windows is None else _dev(np.asarray(windows).reshape(N, 3), np.int32)
     t = None if coords is None else _dev(coords, np.float64)
-    di = torch.empty((N, C) + target, dtype=torch.float32, device=DEV)
-    ds = torch.empty((N,) + target, dtype=torch.int16, device=DEV)
+    di = torch.full((N, C) + target, 7.0, dtype=torch.float32, device=DEV)
+    ds = torch.full((N,) + target, 7, dtype=torch.int16, device=DEV)
     args = [ai.data_ptr(), asg.data_ptr(), asg.numel(), C, table.data_ptr(), 1, p.data_ptr()]
-    if fn == "msl_augment_warp_mc":
+    if fn in ("msl_augment_warp_mc", "msl_augment_deform_mc"):
         args += [t.data_ptr(), t.numel()]
     if fn != "msl_augment_fit_mc":
         args.append(None if w is None else w.data_ptr())
@@ -203,3 +204,60 @@ def test_regrid_is_warp_under_the_unclamped_nearest_rule(shape, C):
         row = _row(IDENT, 2, boundary=BOUNDARY["border"])
         warp = _ragged("msl_augment_warp_mc", C, shape, [row], shape, coords=_tables(shape, step, start))
         _same((di.cpu().numpy()[None], ds.cpu().numpy().astype(np.int64)[None]), warp)
+
+
+SHAPE_TARGET = [((5, 6, 7), (4, 5, 6)), ((5, 6, 7), (8, 7, 8)), ((6, 6, 6), (4, 5, 6)), ((6, 6, 6), (8, 7, 8))]
+OFF_BOTH_ENDS = (-2, 1, 3)  # a window origin: with the larger target it leaves the case at both ends of axis 0
+
+
+def _identity_tables(dims):
+    return np.concatenate([np.arange(n, dtype=np.float64) for n in dims])
+
+
+@pytest.mark.parametrize("origin", [None, OFF_BOTH_ENDS])
+@pytest.mark.parametrize("L", [4, 16])
+@pytest.mark.parametrize("C", [1, 2])
+@pytest.mark.parametrize("shape,target", SHAPE_TARGET)
+def test_deform_with_a_zero_lattice_is_warp_with_identity_tables(shape, target, C, L, origin):
+    """msl_augment_deform_mc with a zero lattice (q + d(q) is q exactly) == msl_augment_warp_mc with tables t_a[q] =
+    float(q): the three permutations (a ragged case may change shape under one) with two operations under the three
+    boundaries, the smallest and the largest lattice, the centred fit and window origins that run off both ends."""
+    perms = [perm for perm in (IDENT, FLIP, ROT) for _ in BOUNDARY]
+    bounds = sorted(BOUNDARY.values()) * 3
+    deform_rows, warp_rows, coords = [], [], []
+    for perm, b in zip(perms, bounds):
+        d = _row(perm, 3, boundary=b, ops=OPS)
+        d[8], d[9] = 0, L  # every sample reads the one zero lattice
+        w = _row(perm, 2, boundary=b, ops=OPS)
+        w[8] = sum(len(t) for t in coords)
+        coords.append(_identity_tables(_permuted(shape, perm)))
+        deform_rows.append(d)
+        warp_rows.append(w)
+    windows = None if origin is None else [origin] * len(perms)
+    _same(_ragged("msl_augment_deform_mc", C, shape, deform_rows, target, windows, np.zeros(3 * L ** 3)),
+          _ragged("msl_augment_warp_mc", C, shape, warp_rows, target, windows, np.concatenate(coords)))
+
+
+@pytest.mark.parametrize("origin", [None, OFF_BOTH_ENDS])
+@pytest.mark.parametrize("C", [1, 2])
+@pytest.mark.parametrize("target", [(4, 5, 6), (8, 7, 8)])
+def test_copied_and_rejected_rows_are_the_same_in_every_row_kernel(target, C, origin):
+    """The rows warp_kernel and deform_kernel do not sample: a kind-0 row (the permuted copy, with operations) is the fit's (the window's, given origins) byte for byte in both, and a row of a foreign kind, a row
+    whose table offset lies past the table and a row whose case is out of range are zeros in both."""
+    shape, L = (5, 6, 7), 4
+    sides = {"msl_augment_warp_mc": (2, _identity_tables(shape)), "msl_augment_deform_mc": (3, np.zeros(3 * L ** 3))}
+    m, off = _rotation(shape)
+    windows = None if origin is None else [origin] * 4
+    copied, foreign, no_case = _row(FLIP, 0, ops=OPS), _row(IDENT, 1, m, off, BOUNDARY["reflection"]), _row(IDENT, 0, source=1)
+    out = {}
+    for fn, (kind, side) in sides.items():
+        past = _row(IDENT, kind, boundary=BOUNDARY["border"])
+        past[8], past[9] = side.size + 5, L
+        out[fn] = _ragged(fn, C, shape, [copied, foreign, past, no_case], target, windows, side)
+        assert not out[fn][0][1:].view(np.uint32).any() and not out[fn][1][1:].any(), f"{fn}: a rejected row is not zeros"
+    # the same batch through the fit (the row past its table left out: the fit has no table and takes any non-zero kind
+    # for its affine): only the kind-0 row is comparable
+    fit = _ragged("msl_augment_fit_mc" if origin is None else "msl_augment_window_mc", C, shape, [copied, foreign, no_case],
+                  target, None if origin is None else windows[:3])
+    for o in out.values():
+        _same((o[0][:1], o[1][:1]), (fit[0][:1], fit[1][:1]))

@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256) void pw_bww_bf16_any_kernel(const u16* __restr
           if (co0 + r < Cout) a = msl::bf2f(dY[((size_t)n * Cout + co0 + r) * S + p]);
           if (ci0 + r < Cin) {
             b = msl::bf2f(Z[((size_t)n * Cin + ci0 + r) * S + p]);
-            if (AFFINE) b = msl::bf2f(msl::f2bf(fmaxf(fmaf(b, in_scale[ci0 + r], in_shift[ci0 + r]), 0.f)));
+            if (AFFINE) b = msl::bf2f(msl::f2bf(msl::act(b, in_scale[ci0 + r], in_shift[ci0 + r])));  // NaN survives, as in the forward
           }
         }
         sy[r][c] = a;

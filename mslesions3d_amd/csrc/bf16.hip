@@ -6,6 +6,9 @@
 //   BatchNorm+ReLU materialisation of the head feature maps: bf16 CHANNELS-LAST zero-haloed copy, so that the bf16
 //   head kernel (heads.hip) reads 8 consecutive channels of a voxel with one 16-byte load.
 // The statistics of a layer are taken from the fp32 accumulators BEFORE the rounding to bf16.
+// Not here: what runs on either storage type from one templated kernel - the depthwise wave, rows, small-map and stride-2
+// patch kernels (dwconv.hip, dwconv_bwd.hip; declared below), the channel links (chanlink.hip) and the BatchNorm+ReLU
+// backward (bn.hip, which also holds its _bf16 entry points).
 #include "common.hpp"
 #include "dwroute.hpp"
 #include <algorithm>
@@ -677,152 +680,6 @@ __global__ __launch_bounds__(256) void dw_bww_bf16_kernel(const u16* __restrict_
   }
 }
 
-// ---- BatchNorm + ReLU backward ---------------------------------------------------------------------------------------
-// gm = g * [fma(y, scale, shift) > 0];  dbeta = sum gm;  dgamma = sum gm * xhat;  dy = scale * (gm - c1 - xhat * c2),
-// c1 = dbeta / count, c2 = dgamma / count (same algebra and vectors as the fp32 kernels of bn.hip).
-constexpr int BB_CHUNK = 4096;
-__global__ __launch_bounds__(256) void bn_relu_bwd_reduce_bf16_kernel(const u16* __restrict__ g, const u16* __restrict__ y,
-                                                                      const float* __restrict__ scale,
-                                                                      const float* __restrict__ shift,
-                                                                      const float* __restrict__ mean,
-                                                                      const float* __restrict__ invstd,
-                                                                      double* __restrict__ partials, int C, int S, int chunks) {
-  __shared__ double scratch[8];
-  const int ck = blockIdx.x, c = blockIdx.y, n = blockIdx.z;
-  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
-  const size_t base = ((size_t)n * C + c) * S;
-  const int lo = ck * BB_CHUNK, hi = min(S, lo + BB_CHUNK);
-  float s1 = 0.f, s2 = 0.f;
-  for (int i = lo + threadIdx.x; i < hi; i += 256) {
-    const float yv = msl::bf2f(y[base + i]);
-    const float gm = fmaf(yv, sc, sh) > 0.f ? msl::bf2f(g[base + i]) : 0.f;
-    s1 += gm;
-    s2 += gm * ((yv - mu) * is);
-  }
-  const double t1 = msl::block_sum((double)s1, scratch);
-  __syncthreads();
-  const double t2 = msl::block_sum((double)s2, scratch);
-  if (threadIdx.x == 0) {
-    const int NP = gridDim.z * chunks, p = n * chunks + ck;
-    partials[(size_t)c * NP + p] = t1;
-    partials[((size_t)C + c) * NP + p] = t2;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_relu_bwd_apply_bf16_kernel(const u16* __restrict__ g, const u16* __restrict__ y,
-                                                                     const float* __restrict__ vec, u16* __restrict__ dy, int C,
-                                                                     int S) {
-  const int c = blockIdx.y, n = blockIdx.z;
-  const float sc = vec[c], sh = vec[C + c], mu = vec[2 * C + c], is = vec[3 * C + c], k1 = vec[4 * C + c], k2 = vec[5 * C + c];
-  const size_t base = ((size_t)n * C + c) * S;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < S; i += gridDim.x * 256) {
-    const float yv = msl::bf2f(y[base + i]);
-    const float gm = fmaf(yv, sc, sh) > 0.f ? msl::bf2f(g[base + i]) : 0.f;
-    dy[base + i] = msl::f2bf(sc * (gm - k1 - ((yv - mu) * is) * k2));
-  }
-}
-
-// one workgroup per channel: reduce, then apply (the channel's data is re-read from cache): small layers in one launch
-__global__ __launch_bounds__(256) void bn_relu_bwd_fused_bf16_kernel(const u16* __restrict__ g, const u16* __restrict__ y,
-                                                                     const float* __restrict__ vec, float* __restrict__ dgamma,
-                                                                     float* __restrict__ dbeta, u16* __restrict__ dy, int N,
-                                                                     int C, int S, double count) {
-  __shared__ double scratch[8];
-  __shared__ float coef[2];
-  const int c = blockIdx.x;
-  const float sc = vec[c], sh = vec[C + c], mu = vec[2 * C + c], is = vec[3 * C + c];
-  float s1 = 0.f, s2 = 0.f;
-  for (int n = 0; n < N; ++n) {
-    const size_t base = ((size_t)n * C + c) * S;
-    for (int i = threadIdx.x; i < S; i += 256) {
-      const float yv = msl::bf2f(y[base + i]);
-      const float gm = fmaf(yv, sc, sh) > 0.f ? msl::bf2f(g[base + i]) : 0.f;
-      s1 += gm;
-      s2 += gm * ((yv - mu) * is);
-    }
-  }
-  const double t1 = msl::block_sum((double)s1, scratch);
-  __syncthreads();
-  const double t2 = msl::block_sum((double)s2, scratch);
-  if (threadIdx.x == 0) {
-    dbeta[c] = (float)t1;
-    dgamma[c] = (float)t2;
-    coef[0] = (float)(t1 / count);
-    coef[1] = (float)(t2 / count);
-  }
-  __syncthreads();
-  const float k1 = coef[0], k2 = coef[1];
-  for (int n = 0; n < N; ++n) {
-    const size_t base = ((size_t)n * C + c) * S;
-    for (int i = threadIdx.x; i < S; i += 256) {
-      const float yv = msl::bf2f(y[base + i]);
-      const float gm = fmaf(yv, sc, sh) > 0.f ? msl::bf2f(g[base + i]) : 0.f;
-      dy[base + i] = msl::f2bf(sc * (gm - k1 - ((yv - mu) * is) * k2));
-    }
-  }
-}
-
-// Register-resident form for N*S <= NT*IPT*8 elements per channel (S % 8 == 0): the channel's g and y are read ONCE (16-byte
-// loads, all of a thread's loads in flight together), kept in registers across the block-wide reduction, and dL/dy is
-// written from them (bn.hip: bn_relu_bwd_fused_reg_kernel, here with 8 bf16 per load).
-template <int NT, int IPT>
-__global__ __launch_bounds__(NT) void bn_relu_bwd_fused_reg_bf16_kernel(const u16* __restrict__ g, const u16* __restrict__ y,
-                                                                        const float* __restrict__ vec, float* __restrict__ dgamma,
-                                                                        float* __restrict__ dbeta, u16* __restrict__ dy, int N,
-                                                                        int C, int S, double count) {
-  __shared__ double scratch[16];
-  __shared__ float coef[2];
-  const int c = blockIdx.x;
-  const float sc = vec[c], sh = vec[C + c], mu = vec[2 * C + c], is = vec[3 * C + c];
-  const int S8 = S >> 3, total8 = N * S8;
-  u16x8 gv[IPT], yv[IPT];
-  size_t off[IPT];
-#pragma unroll
-  for (int u = 0; u < IPT; ++u) {
-    const int t = threadIdx.x + u * NT;
-    const int tt = t < total8 ? t : 0;
-    const int n = tt / S8, i8 = tt - n * S8;
-    off[u] = ((size_t)n * C + c) * S + (size_t)i8 * 8;
-    gv[u] = *reinterpret_cast<const u16x8*>(g + off[u]);
-    yv[u] = *reinterpret_cast<const u16x8*>(y + off[u]);
-  }
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int u = 0; u < IPT; ++u) {
-    const bool in = threadIdx.x + u * NT < total8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float yy = msl::bf2f(yv[u][k]);
-      const bool on = in && fmaf(yy, sc, sh) > 0.f;
-      if (!on) gv[u][k] = 0;  // gm (bf16 zero)
-      const float gm = msl::bf2f(gv[u][k]);
-      s1 += gm;
-      s2 += gm * ((yy - mu) * is);
-    }
-  }
-  const double t1 = msl::block_sum((double)s1, scratch);
-  __syncthreads();
-  const double t2 = msl::block_sum((double)s2, scratch);
-  if (threadIdx.x == 0) {
-    dbeta[c] = (float)t1;
-    dgamma[c] = (float)t2;
-    coef[0] = (float)(t1 / count);
-    coef[1] = (float)(t2 / count);
-  }
-  __syncthreads();
-  const float k1 = coef[0], k2 = coef[1];
-#pragma unroll
-  for (int u = 0; u < IPT; ++u) {
-    if (threadIdx.x + u * NT < total8) {
-      u16x8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        o[k] = msl::f2bf(sc * (msl::bf2f(gv[u][k]) - k1 - ((msl::bf2f(yv[u][k]) - mu) * is) * k2));
-      *reinterpret_cast<u16x8*>(dy + off[u]) = o;
-    }
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -1026,54 +883,6 @@ int msl_dwconv_bwd_weight_bf16(const void* dz, const void* x, const float* in_sc
                in_scale, in_shift, partials, C, D, H, W, r.OD, r.OH, r.OW, r.tiles_h, r.tiles_w, r.num_partials);
     return MSL_OK;
   });
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-int msl_bn_relu_bwd_bf16_num_partials(int N, int S) { return N * msl::cdiv(S, BB_CHUNK); }
-
-// partials [2][C][NP] of (sum gm, sum gm * xhat); fold them with msl_bn_bwd_finalize (bn.hip), then _apply_bf16
-int msl_bn_relu_bwd_reduce_bf16(const void* g, const void* y, const float* scale, const float* shift, const float* mean,
-                                const float* invstd, double* partials, int N, int C, int S, void* stream) {
-  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
-  const int chunks = msl::cdiv(S, BB_CHUNK);
-  MSL_LAUNCH(bn_relu_bwd_reduce_bf16_kernel, dim3(chunks, C, N), dim3(256), 0, (hipStream_t)stream, (const u16*)g,
-                     (const u16*)y, scale, shift, mean, invstd, partials, C, S, chunks);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-// vec = (6, C) rows [scale, shift, mean, invstd, c1, c2]; dy may alias g
-int msl_bn_relu_bwd_apply_bf16(const void* g, const void* y, const float* vec, void* dy, int N, int C, int S, void* stream) {
-  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
-  MSL_LAUNCH(bn_relu_bwd_apply_bf16_kernel, dim3(std::min(msl::cdiv(S, 1024), 64), C, N), dim3(256), 0, (hipStream_t)stream,
-                     (const u16*)g, (const u16*)y, vec, (u16*)dy, C, S);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-// whole BatchNorm + ReLU backward of small layers in one launch (one workgroup per channel); vec rows 0-3 are read
-int msl_bn_relu_bwd_fused_bf16(const void* g, const void* y, const float* vec, float* dgamma, float* dbeta, void* dy, int N,
-                               int C, int S, void* stream) {
-  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const long long total8 = (long long)N * (S >> 3);
-#define MSL_BN_REG(NT_, IPT_)                                                                                              \
-  MSL_LAUNCH((bn_relu_bwd_fused_reg_bf16_kernel<NT_, IPT_>), dim3(C), dim3(NT_), 0, st, (const u16*)g, (const u16*)y, \
-                     vec, dgamma, dbeta, (u16*)dy, N, C, S, (double)N * (double)S)
-  if ((S & 7) == 0 && total8 <= 4096) {
-    if (total8 <= 64) MSL_BN_REG(64, 1);
-    else if (total8 <= 256) MSL_BN_REG(256, 1);
-    else if (total8 <= 512) MSL_BN_REG(256, 2);
-    else if (total8 <= 1024) MSL_BN_REG(512, 2);
-    else if (total8 <= 2048) MSL_BN_REG(1024, 2);
-    else MSL_BN_REG(1024, 4);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-#undef MSL_BN_REG
-  MSL_LAUNCH(bn_relu_bwd_fused_bf16_kernel, dim3(C), dim3(256), 0, st, (const u16*)g, (const u16*)y, vec,
-                     dgamma, dbeta, (u16*)dy, N, C, S, (double)N * (double)S);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

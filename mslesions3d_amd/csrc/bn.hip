@@ -156,45 +156,69 @@ __global__ __launch_bounds__(256) void bn_relu_materialize_kernel(
 // For a_out = relu(bn(y)), given g = dL/da_out:
 //   gm = g * [a_out > 0];  dbeta = sum gm;  dgamma = sum gm * xhat,  xhat = (y - mean) * invstd
 //   dL/dy = gamma*invstd * (gm - dbeta/n - xhat * dgamma/n)
+// One kernel family serves both activation storage types: T = float, or msl::su16 for bf16 (g, y and dy are widened on
+// load and rounded on store; vectors, sums and all arithmetic are fp32 either way).  Only fp32 storage takes the float4
+// branches (by4): a thread of the bf16 instantiations adds its elements in the scalar branch's order.  The register
+// kernel moves 16 bytes per load in both, 4 floats or 8 bf16.  The apply alone has a kernel per storage type (see there).
 constexpr int BWD_CHUNK = 4096;  // elements of one (n,c) row handled by one workgroup
 
+template <typename T>
+__device__ __forceinline__ bool by4(int S) {
+  if constexpr (sizeof(T) == 4) return (S & 3) == 0;
+  else return false;
+}
+
+// One channel's forward vectors and the three lines of arithmetic that every form below runs on, written once.
+// gm * xhat joins its sum with two roundings - except in the register kernel on bf16 storage (FMA), with one: that is what
+// the compiler's contraction made of the fp32 and the bf16 kernels when they were two families, and the bits recorded then
+// (tests/golden/bn_bwd_bits.json) hold it.  Spelled out here, so that the bits no longer hang on what contraction picks.
+struct BnBwd {
+  float sc, sh, mu, is;
+  __device__ __forceinline__ BnBwd(const float* scale, const float* shift, const float* mean, const float* invstd, int c)
+      : sc(scale[c]), sh(shift[c]), mu(mean[c]), is(invstd[c]) {}
+  __device__ __forceinline__ bool open(float y) const { return fmaf(y, sc, sh) > 0.f; }  // gm = open ? g : 0
+  template <bool FMA = false>
+  __device__ __forceinline__ void sums(float gm, float y, float& s1, float& s2) const {
+#pragma clang fp contract(off)
+    const float xhat = (y - mu) * is;
+    s1 += gm;
+    s2 = FMA ? fmaf(gm, xhat, s2) : s2 + gm * xhat;
+  }
+  __device__ __forceinline__ float dy(float gm, float y, float k1, float k2) const { return sc * (gm - k1 - ((y - mu) * is) * k2); }
+};
+
+template <typename T>
 __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(
-    const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ scale,
+    const T* __restrict__ g, const T* __restrict__ y, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
     double* __restrict__ partials, int C, int S, int chunks) {
   __shared__ double scratch[8];
   const int chunk = blockIdx.x, c = blockIdx.y, n = blockIdx.z;
-  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
+  const BnBwd ch(scale, shift, mean, invstd, c);
   const size_t base = ((size_t)n * C + c) * S;
   const int lo = chunk * BWD_CHUNK, hi = min(S, lo + BWD_CHUNK);
   float s1 = 0.f, s2 = 0.f;
-  if ((S & 3) == 0) {
+  if (by4<T>(S)) {
     // BWD_CHUNK = 4 x 1024: the thread's four float4 pairs are loaded back to back (clamped addresses, masked)
     float4 gv[4], yv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = lo + threadIdx.x * 4 + u * 1024;
       const size_t o = base + (i < hi ? i : lo);
-      gv[u] = *reinterpret_cast<const float4*>(g + o);
-      yv[u] = *reinterpret_cast<const float4*>(y + o);
+      gv[u] = msl::ld4(g + o);
+      yv[u] = msl::ld4(y + o);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const bool in = lo + threadIdx.x * 4 + u * 1024 < hi;
       const float ga[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w}, ya[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float gm = (in && fmaf(ya[k], sc, sh) > 0.f) ? ga[k] : 0.f;
-        s1 += gm;
-        s2 += gm * ((ya[k] - mu) * is);
-      }
+      for (int k = 0; k < 4; ++k) ch.sums((in && ch.open(ya[k])) ? ga[k] : 0.f, ya[k], s1, s2);
     }
   } else {
     for (int i = lo + threadIdx.x; i < hi; i += 256) {
-      const float yy = y[base + i];
-      const float gm = fmaf(yy, sc, sh) > 0.f ? g[base + i] : 0.f;
-      s1 += gm;
-      s2 += gm * ((yy - mu) * is);
+      const float yy = msl::ld1(y + base + i);
+      ch.sums(ch.open(yy) ? msl::ld1(g + base + i) : 0.f, yy, s1, s2);
     }
   }
   const int NP = gridDim.z * chunks;
@@ -254,6 +278,7 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const double* __res
   }
 }
 
+// fp32 storage only (bf16: bn_relu_bwd_apply_bf16_kernel below)
 __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(
     const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -261,7 +286,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(
     const double* __restrict__ partials, int NP, double count, float* __restrict__ dgamma, float* __restrict__ dbeta,
     float* __restrict__ c1_out, float* __restrict__ c2_out) {
   const int c = blockIdx.y, n = blockIdx.z;
-  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
+  const BnBwd ch(scale, shift, mean, invstd, c);
   float k1, k2;
   if (partials) {
     // finalize folded in (NP is small here): every workgroup of the channel sums the same partials in the same order
@@ -296,59 +321,66 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(
   const size_t base = ((size_t)n * C + c) * S;
   if ((S & 3) == 0) {
     for (int i = (blockIdx.x * 256 + threadIdx.x) * 4; i < S; i += gridDim.x * 256 * 4) {
-      const float4 gv = *reinterpret_cast<const float4*>(g + base + i);
-      const float4 yv = *reinterpret_cast<const float4*>(y + base + i);
+      const float4 gv = msl::ld4(g + base + i), yv = msl::ld4(y + base + i);
       const float ga[4] = {gv.x, gv.y, gv.z, gv.w}, ya[4] = {yv.x, yv.y, yv.z, yv.w};
       float o[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float gm = fmaf(ya[k], sc, sh) > 0.f ? ga[k] : 0.f;
-        o[k] = sc * (gm - k1 - ((ya[k] - mu) * is) * k2);
-      }
-      *reinterpret_cast<float4*>(dy + base + i) = make_float4(o[0], o[1], o[2], o[3]);
+      for (int k = 0; k < 4; ++k) o[k] = ch.dy(ch.open(ya[k]) ? ga[k] : 0.f, ya[k], k1, k2);
+      msl::st4(dy + base + i, make_float4(o[0], o[1], o[2], o[3]));
     }
   } else {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < S; i += gridDim.x * 256) {
       const float yy = y[base + i];
-      const float gm = fmaf(yy, sc, sh) > 0.f ? g[base + i] : 0.f;
-      dy[base + i] = sc * (gm - k1 - ((yy - mu) * is) * k2);
+      dy[base + i] = ch.dy(ch.open(yy) ? g[base + i] : 0.f, yy, k1, k2);
     }
+  }
+}
+
+// The one form that keeps a kernel per storage type.  As an instantiation of the kernel above (the six vectors through six
+// pointers, 136 bytes of kernel arguments for 40, the vector loads of the prologue in two dependent groups) the apply on
+// bf16 storage measured 6.67 us against 6.39 at 4 x 32 x 32768, outside the old kernel's run-to-run range; it has no
+// folded finalize either.  vec = (6, C) rows [scale, shift, mean, invstd, c1, c2].
+__global__ __launch_bounds__(256) void bn_relu_bwd_apply_bf16_kernel(const msl::su16* __restrict__ g,
+                                                                     const msl::su16* __restrict__ y,
+                                                                     const float* __restrict__ vec,
+                                                                     msl::su16* __restrict__ dy, int C, int S) {
+  const int c = blockIdx.y, n = blockIdx.z;
+  const BnBwd ch(vec, vec + C, vec + 2 * C, vec + 3 * C, c);
+  const float k1 = vec[4 * C + c], k2 = vec[5 * C + c];
+  const size_t base = ((size_t)n * C + c) * S;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < S; i += gridDim.x * 256) {
+    const float yy = msl::bf2f(y[base + i]);
+    dy[base + i] = msl::f2bf(ch.dy(ch.open(yy) ? msl::bf2f(g[base + i]) : 0.f, yy, k1, k2));
   }
 }
 
 // Whole BatchNorm+ReLU backward of one channel in ONE workgroup (reduce -> coefficients -> apply) for the layers
 // whose per-channel data is small (<= 64 K elements: blocks 2-7).  Replaces three launches (two of them pure
 // launch latency) by one; the second pass re-reads g and y from L2.
+template <typename T>
 __global__ __launch_bounds__(256) void bn_relu_bwd_fused_kernel(
-    const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ scale,
+    const T* __restrict__ g, const T* __restrict__ y, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
-    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dy, int N, int C, int S, double count) {
+    float* __restrict__ dgamma, float* __restrict__ dbeta, T* __restrict__ dy, int N, int C, int S, double count) {
   __shared__ double scratch[8];
   __shared__ float coef[2];
   const int c = blockIdx.x;
-  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
-  const bool vec = (S & 3) == 0;
+  const BnBwd ch(scale, shift, mean, invstd, c);
+  const bool vec = by4<T>(S);
   float s1 = 0.f, s2 = 0.f;
   for (int n = 0; n < N; ++n) {
     const size_t base = ((size_t)n * C + c) * S;
     if (vec) {
       for (int i = threadIdx.x * 4; i < S; i += 1024) {
-        const float4 gv = *reinterpret_cast<const float4*>(g + base + i);
-        const float4 yv = *reinterpret_cast<const float4*>(y + base + i);
+        const float4 gv = msl::ld4(g + base + i), yv = msl::ld4(y + base + i);
         const float ga[4] = {gv.x, gv.y, gv.z, gv.w}, ya[4] = {yv.x, yv.y, yv.z, yv.w};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float gm = fmaf(ya[k], sc, sh) > 0.f ? ga[k] : 0.f;
-          s1 += gm;
-          s2 += gm * ((ya[k] - mu) * is);
-        }
+        for (int k = 0; k < 4; ++k) ch.sums(ch.open(ya[k]) ? ga[k] : 0.f, ya[k], s1, s2);
       }
     } else {
       for (int i = threadIdx.x; i < S; i += 256) {
-        const float yy = y[base + i];
-        const float gm = fmaf(yy, sc, sh) > 0.f ? g[base + i] : 0.f;
-        s1 += gm;
-        s2 += gm * ((yy - mu) * is);
+        const float yy = msl::ld1(y + base + i);
+        ch.sums(ch.open(yy) ? msl::ld1(g + base + i) : 0.f, yy, s1, s2);
       }
     }
   }
@@ -367,62 +399,58 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_fused_kernel(
     const size_t base = ((size_t)n * C + c) * S;
     if (vec) {
       for (int i = threadIdx.x * 4; i < S; i += 1024) {
-        const float4 gv = *reinterpret_cast<const float4*>(g + base + i);
-        const float4 yv = *reinterpret_cast<const float4*>(y + base + i);
+        const float4 gv = msl::ld4(g + base + i), yv = msl::ld4(y + base + i);
         const float ga[4] = {gv.x, gv.y, gv.z, gv.w}, ya[4] = {yv.x, yv.y, yv.z, yv.w};
         float o[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float gm = fmaf(ya[k], sc, sh) > 0.f ? ga[k] : 0.f;
-          o[k] = sc * (gm - k1 - ((ya[k] - mu) * is) * k2);
-        }
-        *reinterpret_cast<float4*>(dy + base + i) = make_float4(o[0], o[1], o[2], o[3]);
+        for (int k = 0; k < 4; ++k) o[k] = ch.dy(ch.open(ya[k]) ? ga[k] : 0.f, ya[k], k1, k2);
+        msl::st4(dy + base + i, make_float4(o[0], o[1], o[2], o[3]));
       }
     } else {
       for (int i = threadIdx.x; i < S; i += 256) {
-        const float yy = y[base + i];
-        const float gm = fmaf(yy, sc, sh) > 0.f ? g[base + i] : 0.f;
-        dy[base + i] = sc * (gm - k1 - ((yy - mu) * is) * k2);
+        const float yy = msl::ld1(y + base + i);
+        dy[base + i] = msl::narrow<T>(ch.dy(ch.open(yy) ? msl::ld1(g + base + i) : 0.f, yy, k1, k2));
       }
     }
   }
 }
 
-// Register-resident form of the above for N*S <= NT*IPT*4 elements per channel (S % 4 == 0): the channel's g and y are
-// read ONCE, all loads of a thread in flight together, kept in registers across the reduction, and dL/dy is written from
-// them - one memory round trip, a block-wide reduction, one burst of stores.
-template <int NT, int IPT>
+// Register-resident form of the above for N*S <= NT*IPT*VW elements per channel (VW = 16 / sizeof(T) elements of one
+// 16-byte load, S % VW == 0): the channel's g and y are read ONCE, all loads of a thread in flight together, kept in
+// registers IN THE STORAGE TYPE across the reduction (gm written back over g: a bf16 zero where the mask is shut), and
+// dL/dy is written from them - one memory round trip, a block-wide reduction, one burst of stores.
+template <typename T, int NT, int IPT>
 __global__ __launch_bounds__(NT) void bn_relu_bwd_fused_reg_kernel(
-    const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ scale,
+    const T* __restrict__ g, const T* __restrict__ y, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
-    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dy, int N, int C, int S, double count) {
+    float* __restrict__ dgamma, float* __restrict__ dbeta, T* __restrict__ dy, int N, int C, int S, double count) {
+  constexpr int VW = 16 / sizeof(T);
+  typedef T V __attribute__((ext_vector_type(VW)));
   __shared__ double scratch[16];
   __shared__ float coef[2];
   const int c = blockIdx.x;
-  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
-  const int S4 = S >> 2, total4 = N * S4;
-  float4 gv[IPT], yv[IPT];
+  const BnBwd ch(scale, shift, mean, invstd, c);
+  const int SV = S >> (VW == 4 ? 2 : 3), totalv = N * SV;
+  V gv[IPT], yv[IPT];
   size_t off[IPT];
 #pragma unroll
   for (int u = 0; u < IPT; ++u) {
     const int t = threadIdx.x + u * NT;
-    const int tt = t < total4 ? t : 0;
-    const int n = tt / S4, i4 = tt - n * S4;
-    off[u] = ((size_t)n * C + c) * S + (size_t)i4 * 4;
-    gv[u] = *reinterpret_cast<const float4*>(g + off[u]);
-    yv[u] = *reinterpret_cast<const float4*>(y + off[u]);
+    const int tt = t < totalv ? t : 0;
+    const int n = tt / SV, iv = tt - n * SV;
+    off[u] = ((size_t)n * C + c) * S + (size_t)iv * VW;
+    gv[u] = *reinterpret_cast<const V*>(g + off[u]);
+    yv[u] = *reinterpret_cast<const V*>(y + off[u]);
   }
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int u = 0; u < IPT; ++u) {
-    const bool in = threadIdx.x + u * NT < total4;
-    float* ga = reinterpret_cast<float*>(&gv[u]);
-    const float* ya = reinterpret_cast<const float*>(&yv[u]);
+    const bool in = threadIdx.x + u * NT < totalv;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      ga[k] = (in && fmaf(ya[k], sc, sh) > 0.f) ? ga[k] : 0.f;  // gm
-      s1 += ga[k];
-      s2 += ga[k] * ((ya[k] - mu) * is);
+    for (int k = 0; k < VW; ++k) {
+      const float yy = msl::widen(yv[u][k]);
+      gv[u][k] = (in && ch.open(yy)) ? gv[u][k] : T(0);  // gm
+      ch.sums<sizeof(T) == 2>(msl::widen(gv[u][k]), yy, s1, s2);
     }
   }
   const double t1 = msl::block_sum((double)s1, scratch);
@@ -438,15 +466,62 @@ __global__ __launch_bounds__(NT) void bn_relu_bwd_fused_reg_kernel(
   const float k1 = coef[0], k2 = coef[1];
 #pragma unroll
   for (int u = 0; u < IPT; ++u) {
-    if (threadIdx.x + u * NT < total4) {
-      const float* ga = reinterpret_cast<const float*>(&gv[u]);
-      const float* ya = reinterpret_cast<const float*>(&yv[u]);
-      float o[4];
+    if (threadIdx.x + u * NT < totalv) {
+      V o;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = sc * (ga[k] - k1 - ((ya[k] - mu) * is) * k2);
-      *reinterpret_cast<float4*>(dy + off[u]) = make_float4(o[0], o[1], o[2], o[3]);
+      for (int k = 0; k < VW; ++k) o[k] = msl::narrow<T>(ch.dy(msl::widen(gv[u][k]), msl::widen(yv[u][k]), k1, k2));
+      *reinterpret_cast<V*>(dy + off[u]) = o;
     }
   }
+}
+
+// ---- launchers of the backward kernels, shared by the fp32 and the bf16 entry points
+template <typename T>
+int bwd_reduce(const T* g, const T* y, const float* scale, const float* shift, const float* mean, const float* invstd,
+               double* partials, int N, int C, int S, void* stream) {
+  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
+  const int chunks = msl::cdiv(S, BWD_CHUNK);
+  MSL_LAUNCH(bn_relu_bwd_reduce_kernel<T>, dim3(chunks, C, N), dim3(256), 0, (hipStream_t)stream, g, y, scale, shift, mean,
+             invstd, partials, C, S, chunks);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+// partials == nullptr: c1 / c2 are read; otherwise the finalize is folded in and writes the last four
+int bwd_apply(const float* g, const float* y, const float* scale, const float* shift, const float* mean, const float* invstd,
+              const float* c1, const float* c2, float* dy, int N, int C, int S, void* stream, const double* partials = nullptr,
+              int NP = 0, double count = 1.0, float* dgamma = nullptr, float* dbeta = nullptr, float* c1_out = nullptr,
+              float* c2_out = nullptr) {
+  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
+  const int gx = min(msl::cdiv(S, 1024), 64);
+  MSL_LAUNCH(bn_relu_bwd_apply_kernel, dim3(gx, C, N), dim3(256), 0, (hipStream_t)stream, g, y, scale, shift, mean, invstd,
+             c1, c2, dy, C, S, partials, NP, count, dgamma, dbeta, c1_out, c2_out);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+template <typename T>
+int bwd_fused(const T* g, const T* y, const float* scale, const float* shift, const float* mean, const float* invstd,
+              float* dgamma, float* dbeta, T* dy, int N, int C, int S, void* stream) {
+  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  constexpr int VW = 16 / sizeof(T);  // elements of one 16-byte load
+  const long long totalv = (long long)N * (S / VW);
+#define MSL_BN_REG(NT_, IPT_)                                                                                           \
+  MSL_LAUNCH((bn_relu_bwd_fused_reg_kernel<T, NT_, IPT_>), dim3(C), dim3(NT_), 0, st, g, y, scale, shift, mean, invstd, \
+             dgamma, dbeta, dy, N, C, S, (double)N * S)
+  if (S % VW != 0 || totalv > 4096)
+    MSL_LAUNCH(bn_relu_bwd_fused_kernel<T>, dim3(C), dim3(256), 0, st, g, y, scale, shift, mean, invstd, dgamma, dbeta, dy, N,
+               C, S, (double)N * S);
+  else if (totalv <= 64) MSL_BN_REG(64, 1);
+  else if (totalv <= 256) MSL_BN_REG(256, 1);
+  else if (totalv <= 512) MSL_BN_REG(256, 2);
+  else if (totalv <= 1024) MSL_BN_REG(512, 2);
+  else if (totalv <= 2048) MSL_BN_REG(1024, 2);
+  else MSL_BN_REG(1024, 4);
+#undef MSL_BN_REG
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
 }
 
 }  // namespace
@@ -540,17 +615,21 @@ int msl_bn_relu_materialize_fold(const float* y, const double* partials, int num
   return MSL_OK;
 }
 
+// ---- BatchNorm + ReLU backward.  The _bf16 entry points take g, y and dy as bf16 and the vectors as ONE block ``vec`` of
+// (>= 6, C) rows [scale, shift, mean, invstd, c1, c2]; everything else is as in their fp32 namesakes.  dy may alias g.
 int msl_bn_relu_bwd_num_partials(int N, int S) { return N * msl::cdiv(S, BWD_CHUNK); }
+int msl_bn_relu_bwd_bf16_num_partials(int N, int S) { return msl_bn_relu_bwd_num_partials(N, S); }
 
+// partials [2][C][NP] of (sum gm, sum gm * xhat); fold them with msl_bn_bwd_finalize, then _apply
 int msl_bn_relu_bwd_reduce(const float* g, const float* y, const float* scale, const float* shift,
                            const float* mean, const float* invstd, double* partials, int N, int C, int S,
                            void* stream) {
-  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
-  const int chunks = msl::cdiv(S, BWD_CHUNK);
-  MSL_LAUNCH(bn_relu_bwd_reduce_kernel, dim3(chunks, C, N), dim3(256), 0, (hipStream_t)stream, g, y,
-                     scale, shift, mean, invstd, partials, C, S, chunks);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return bwd_reduce(g, y, scale, shift, mean, invstd, partials, N, C, S, stream);
+}
+
+int msl_bn_relu_bwd_reduce_bf16(const void* g, const void* y, const float* scale, const float* shift, const float* mean,
+                                const float* invstd, double* partials, int N, int C, int S, void* stream) {
+  return bwd_reduce((const msl::su16*)g, (const msl::su16*)y, scale, shift, mean, invstd, partials, N, C, S, stream);
 }
 
 int msl_bn_bwd_finalize(const double* partials, int num_partials, double count, float* dgamma, float* dbeta,
@@ -577,37 +656,25 @@ int msl_bn_bwd_finalize_coef(const double* partials, int num_partials, double co
 int msl_bn_relu_bwd_fused(const float* g, const float* y, const float* scale, const float* shift, const float* mean,
                           const float* invstd, float* dgamma, float* dbeta, float* dy, int N, int C, int S,
                           void* stream) {
-  if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const long long total4 = (long long)N * (S >> 2);
-#define MSL_BN_REG(NT_, IPT_)                                                                                          \
-  MSL_LAUNCH((bn_relu_bwd_fused_reg_kernel<NT_, IPT_>), dim3(C), dim3(NT_), 0, st, g, y, scale, shift, mean, \
-                     invstd, dgamma, dbeta, dy, N, C, S, (double)N * S)
-  if ((S & 3) == 0 && total4 <= 4096) {
-    if (total4 <= 64) MSL_BN_REG(64, 1);
-    else if (total4 <= 256) MSL_BN_REG(256, 1);
-    else if (total4 <= 512) MSL_BN_REG(256, 2);
-    else if (total4 <= 1024) MSL_BN_REG(512, 2);
-    else if (total4 <= 2048) MSL_BN_REG(1024, 2);
-    else MSL_BN_REG(1024, 4);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-#undef MSL_BN_REG
-  MSL_LAUNCH(bn_relu_bwd_fused_kernel, dim3(C), dim3(256), 0, st, g, y, scale, shift, mean,
-                     invstd, dgamma, dbeta, dy, N, C, S, (double)N * S);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return bwd_fused(g, y, scale, shift, mean, invstd, dgamma, dbeta, dy, N, C, S, stream);
+}
+
+int msl_bn_relu_bwd_fused_bf16(const void* g, const void* y, const float* vec, float* dgamma, float* dbeta, void* dy, int N,
+                               int C, int S, void* stream) {
+  return bwd_fused((const msl::su16*)g, (const msl::su16*)y, vec, vec + C, vec + 2 * C, vec + 3 * C, dgamma, dbeta,
+                   (msl::su16*)dy, N, C, S, stream);
 }
 
 int msl_bn_relu_bwd_apply(const float* g, const float* y, const float* scale, const float* shift,
                           const float* mean, const float* invstd, const float* c1, const float* c2, float* dy,
                           int N, int C, int S, void* stream) {
+  return bwd_apply(g, y, scale, shift, mean, invstd, c1, c2, dy, N, C, S, stream);
+}
+
+int msl_bn_relu_bwd_apply_bf16(const void* g, const void* y, const float* vec, void* dy, int N, int C, int S, void* stream) {
   if (N <= 0 || C <= 0 || S <= 0) return MSL_ERR_ARG;
-  const int gx = min(msl::cdiv(S, 1024), 64);
-  MSL_LAUNCH(bn_relu_bwd_apply_kernel, dim3(gx, C, N), dim3(256), 0, (hipStream_t)stream, g, y, scale,
-                     shift, mean, invstd, c1, c2, dy, C, S, (const double*)nullptr, 0, 1.0, (float*)nullptr,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  MSL_LAUNCH(bn_relu_bwd_apply_bf16_kernel, dim3(min(msl::cdiv(S, 1024), 64), C, N), dim3(256), 0, (hipStream_t)stream,
+             (const msl::su16*)g, (const msl::su16*)y, vec, (msl::su16*)dy, C, S);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -617,13 +684,9 @@ int msl_bn_relu_bwd_apply(const float* g, const float* y, const float* scale, co
 int msl_bn_relu_bwd_finalize_apply(const double* partials, int num_partials, double count, const float* g, const float* y,
                                    float* bn_vec, float* dgamma, float* dbeta, float* dy, int N, int C, int S,
                                    void* stream) {
-  if (N <= 0 || C <= 0 || S <= 0 || num_partials <= 0 || !partials || !bn_vec) return MSL_ERR_ARG;
-  const int gx = min(msl::cdiv(S, 1024), 64);
-  MSL_LAUNCH(bn_relu_bwd_apply_kernel, dim3(gx, C, N), dim3(256), 0, (hipStream_t)stream, g, y, bn_vec,
-                     bn_vec + C, bn_vec + 2 * C, bn_vec + 3 * C, (const float*)nullptr, (const float*)nullptr, dy, C, S,
-                     partials, num_partials, count, dgamma, dbeta, bn_vec + 4 * C, bn_vec + 5 * C);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  if (num_partials <= 0 || !partials || !bn_vec) return MSL_ERR_ARG;
+  return bwd_apply(g, y, bn_vec, bn_vec + C, bn_vec + 2 * C, bn_vec + 3 * C, nullptr, nullptr, dy, N, C, S, stream, partials,
+                   num_partials, count, dgamma, dbeta, bn_vec + 4 * C, bn_vec + 5 * C);
 }
 
 }  // extern "C"

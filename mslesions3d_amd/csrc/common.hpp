@@ -213,6 +213,13 @@ __device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float
 typedef unsigned short su16;
 typedef su16 su16x4 __attribute__((ext_vector_type(4)));
 typedef su16 su16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float widen(float v) { return v; }
+__device__ __forceinline__ float widen(su16 v) { return bf2f(v); }
+template <typename T>
+__device__ __forceinline__ T narrow(float v) {
+  if constexpr (sizeof(T) == 2) return f2bf(v);
+  else return v;
+}
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const su16* p) { return bf2f(*p); }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }

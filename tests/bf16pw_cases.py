@@ -1,5 +1,6 @@
 """Case tables of tests/test_gpu_bf16pw.py, shared with tests/test_bf16pw_ref_cpu.py: plain CPU data, nothing here imports
-the package.  Every case id names the kernel instantiation of csrc/bf16.hip it is meant to reach, and carries the path that the
+the package.  Every case id names the kernel instantiation of csrc/bf16.hip (BatchNorm backward: csrc/bn.hip on bf16 storage) it is
+meant to reach, and carries the path that the
 dispatch arithmetic mirrored below (``tile_path`` = pw_tr_ok + pw_tr_launch, ``bww_path`` = bww_bf16_plan, ``fused_path`` =
 msl_bn_relu_bwd_fused_bf16, ``apply_grid`` / ``reduce_chunks``) must give for it: ``assert_path`` fails loudly when a changed
 heuristic would silently move a case to another kernel.  Every shape is the smallest that reaches its path.
@@ -61,7 +62,7 @@ def apply_grid(S):
 
 
 def reduce_chunks(S):
-    return cdiv(S, 4096)  # BB_CHUNK; a thread adds at most 4096 / 256 = 16 terms
+    return cdiv(S, 4096)  # BWD_CHUNK (bn.hip); a thread adds at most 4096 / 256 = 16 terms
 
 
 # ------------------------------------------------------------------------------------------------- GEMM cases

@@ -1,5 +1,6 @@
 """The bf16 pointwise GEMM family (msl_pwconv_fwd_bf16, _fold, msl_pwconv_bwd_data_bf16, msl_pwconv_bwd_weight_slabs_bf16), the
-materialise kernels and the four BatchNorm+ReLU-backward kernels of csrc/bf16.hip, path by path, against the float64 reference
+materialise kernels of csrc/bf16.hip and the four BatchNorm+ReLU-backward kernels of csrc/bn.hip on bf16 storage, path by path,
+against the float64 reference
 of tests/bf16pw_ref.py (bounds derived there from the kernel text, not tuned).
 
 bf16 outputs meet the rounding-interval test - bf16_rne(ref - B) <= stored <= bf16_rne(ref + B) - which pins most elements to

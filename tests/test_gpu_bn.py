@@ -691,3 +691,69 @@ def test_bn_chain_matches_float64_autograd(N, C, dims):
         check("chain " + name, "dgamma", dgam, gt.grad, b_dg)
         bound = R.bwd_apply_bound(g, y, vec64, c1, c2, b_db / count + R.U * c1.abs(), b_dg / count + R.U * c2.abs()) + extra_dy(c1, c2)
         check("chain " + name, "dy", dyk.view(y.shape), yt.grad, bound)
+
+
+# ------------------------------------------------------------------------------------------------- recorded bits, both storage types
+def test_bn_relu_bwd_bits_are_the_recorded_ones():
+    """Every output buffer of the eight BatchNorm+ReLU-backward entry points, fp32 and bf16, has the SHA-256 that
+    tests/golden/bn_bwd_bits.json recorded before the two kernel families became one (make_bn_bwd_bits's docstring): a
+    mismatch means the kernels changed their bits, never that the file wants minting again."""
+    import json
+    from tests.golden import make_bn_bwd_bits as M
+    with open(M.OUT) as f:
+        want = json.load(f)
+    got = M.digests(DEV)
+    assert sorted(got) == sorted(want), "the cases are not the recorded ones"
+    assert {k.split()[0] for k in want} == {
+        "msl_bn_relu_bwd_reduce", "msl_bn_relu_bwd_apply", "msl_bn_relu_bwd_fused", "msl_bn_relu_bwd_finalize_apply",
+        "msl_bn_relu_bwd_reduce_bf16", "msl_bn_relu_bwd_apply_bf16", "msl_bn_relu_bwd_fused_bf16", "msl_bn_bwd_finalize"}
+    bad = [k for k in want if got[k] != want[k]]
+    assert not bad, f"{len(bad)}/{len(want)} buffers differ from the recorded bits: {bad[:8]}"
+
+
+def test_bn_relu_bwd_fp32_scalar_branch_and_bf16_do_the_same_fp32_operations():
+    """On g and y that are bf16 values, an fp32 launch on its scalar branch (S % 4 != 0) and a bf16 launch run the same fp32
+    operations in the same order: equal partials / dgamma / dbeta, and the bf16 dy is the fp32 dy rounded to nearest even."""
+    BF = torch.bfloat16
+
+    def case(N, C, S, seed):
+        g, y, vec = bwd_case(N, C, S, seed)
+        g, y = g.to(BF), y.to(BF)
+        k = torch.randn((2, C), generator=gen(seed + 1)) * 0.1  # c1, c2: any fp32 values
+        vd = K(torch.cat([vec, k]))
+        return K(g.float()), K(y.float()), K(g), K(y), vd, [ptr(vd[r]) for r in range(4)]
+
+    def bits(t):
+        return t.contiguous().view(torch.int16)
+
+    L = _lib.load()
+    N, C, S = 2, 3, 4099  # two chunks, the second ragged
+    g32, y32, g16, y16, vd, rows = case(N, C, S, 12000)
+    NP = L.msl_bn_relu_bwd_num_partials(N, S)
+    assert NP == L.msl_bn_relu_bwd_bf16_num_partials(N, S) == 4
+    p32, p16 = Guarded(2 * C * NP, dtype=torch.float64), Guarded(2 * C * NP, dtype=torch.float64)
+    _lib.call("msl_bn_relu_bwd_reduce", ptr(g32), ptr(y32), *rows, ptr(p32.v), N, C, S, st())
+    _lib.call("msl_bn_relu_bwd_reduce_bf16", ptr(g16), ptr(y16), *rows, ptr(p16.v), N, C, S, st())
+    p32.intact("fp32 partials")
+    p16.intact("bf16 partials")
+    assert bool(torch.isfinite(p32.v).all()) and torch.equal(p32.v, p16.v), "reduce: the partials differ between the storage types"
+    dy32, dy16 = Guarded(N * C * S), Guarded(N * C * S, dtype=BF)
+    _lib.call("msl_bn_relu_bwd_apply", ptr(g32), ptr(y32), *rows, ptr(vd[4]), ptr(vd[5]), ptr(dy32.v), N, C, S, st())
+    _lib.call("msl_bn_relu_bwd_apply_bf16", ptr(g16), ptr(y16), ptr(vd), ptr(dy16.v), N, C, S, st())
+    dy32.intact("fp32 dy")
+    dy16.intact("bf16 dy")
+    assert bool(torch.isfinite(dy32.v).all())
+    assert torch.equal(bits(dy16.v), bits(dy32.v.to(BF))), "apply: the bf16 dy is not the rounded fp32 dy"
+
+    N, C, S = 2, 3, 1027  # the generic fused kernel on both sides
+    g32, y32, g16, y16, vd, rows = case(N, C, S, 12100)
+    o32 = [Guarded(C), Guarded(C), Guarded(N * C * S)]
+    o16 = [Guarded(C), Guarded(C), Guarded(N * C * S, dtype=BF)]
+    _lib.call("msl_bn_relu_bwd_fused", ptr(g32), ptr(y32), *rows, ptr(o32[0].v), ptr(o32[1].v), ptr(o32[2].v), N, C, S, st())
+    _lib.call("msl_bn_relu_bwd_fused_bf16", ptr(g16), ptr(y16), ptr(vd), ptr(o16[0].v), ptr(o16[1].v), ptr(o16[2].v), N, C, S, st())
+    for o in o32 + o16:
+        o.intact("fused")
+    assert bool(torch.isfinite(o32[2].v).all())
+    assert torch.equal(o32[0].v, o16[0].v), "fused: dgamma differs between the storage types"
+    assert torch.equal(o32[1].v, o16[1].v), "fused: dbeta differs between the storage types"
+    assert torch.equal(bits(o16[2].v), bits(o32[2].v.to(BF))), "fused: the bf16 dy is not the rounded fp32 dy"

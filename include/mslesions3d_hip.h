@@ -173,6 +173,14 @@ int msl_dwconv_bwd_weight(const float* dy, const float* x, const float* in_scale
 int msl_dwconv_route_kind(int op, int bf16, int N, int C, int D, int H, int W, int stride);
 
 /* ---- pointwise Conv3d(Cin,Cout,k1) = per-image GEMM on MFMA : Block.conv2, mobilenet.py:40,45 ------------- */
+/* Which kernel family a pointwise call of this shape runs (host arithmetic only, nothing is launched) - for tests / DESIGN.md.
+ * op: 0 forward, 1 bwd-data, 2 bwd-weight, 3 the one-pass backward of msl_pwconv_bwd_fused; bf16 != 0: bf16 storage; stats != 0:
+ * the forward writes statistics partials (as every *_num_partials query assumes).
+ * Returns 0 none, 1 strip, 2 wave, 3 K-split GEMM, 4 GEMM, 5 wave-autonomous weight gradient, 6 tiled weight gradient, 7 bf16
+ * transposed-read GEMM, 8 bf16 plain GEMM, 9 bf16 MFMA weight gradient, 10 bf16 one-slab weight gradient, 11 fused one-pass
+ * backward; MSL_ERR_ARG for an unknown op, a bf16 flag other than 0 / 1, or a size <= 0.  Channel counts an entry point refuses
+ * still get the planners' answer. */
+int msl_pwconv_route_kind(int op, int bf16, int N, int Cin, int Cout, int S, int stats);
 int msl_pwconv_fwd_num_partials(int N, int Cin, int Cout, int S);
 int msl_pwconv_fwd(const float* z, const float* in_scale, const float* in_shift, const float* w, float* y,
                    double* partials, int N, int Cin, int Cout, int S, void* stream);

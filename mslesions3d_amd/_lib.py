@@ -53,6 +53,7 @@ _SIGNATURES = {
     "msl_dwconv_bwd_weight_num_partials": (_I, [_I, _I, _I, _I, _I, _I]),
     "msl_dwconv_bwd_weight": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "msl_dwconv_route_kind": (_I, [_I] * 8),
+    "msl_pwconv_route_kind": (_I, [_I] * 7),
     "msl_pwconv_fwd_num_partials": (_I, [_I, _I, _I, _I]),
     "msl_pwconv_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "msl_pwconv_fwd_fold": (_I, [_P, _P, _I, _D, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -11,9 +11,11 @@
 // backward (bn.hip, which also holds its _bf16 entry points).
 #include "common.hpp"
 #include "dwroute.hpp"
+#include "pwroute.hpp"
 #include <algorithm>
 
 using namespace msl::dw;
+using namespace msl::pw;
 
 // dwconv.hip / dwconv_bwd.hip: the wave, rows, small-map and stride-2 patch kernels on bf16 storage
 extern "C" int msl_dwconv_fwd_wave_bf16(const void* x, const float* in_scale, const float* in_shift, const float* w, void* y,
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(256) void dw_fwd_bf16_kernel(const u16* __restrict_
 // Y_n[M x S] = W[M x K] . act(Z_n)[K x S].  Workgroup tile 64 (rows) x 64 (columns); K in chunks of 32; both operands go
 // through LDS as bf16 with k contiguous (the MFMA wants 8 consecutive k per lane; NCDHW has k strided by S, so the
 // activation chunk is transposed on its way into LDS).  4 waves = 2 x 2 tiles of 32 x 32.
-constexpr int PB_BM = 64, PB_BN = 64, PB_BK = 32, PB_LD = PB_BK + 8, PB_MAXK = 1024;  // 80-byte rows: 16-byte aligned fragments
+constexpr int PB_LD = PB_BK + 8;  // 80-byte rows: 16-byte aligned fragments
 
 // TRANS_W: weight element (m, k) = Wt[k * M + m] (bwd-data: M = Cin, K = Cout, the same weights read transposed).
 template <bool STATS, bool TRANS_W = false>
@@ -246,7 +248,7 @@ __global__ __launch_bounds__(256) void pw_fwd_bf16_kernel(const u16* __restrict_
 // flattened, so a workgroup that owns several position tiles never waits for a cold load between tiles; (3) BK up to
 // 128: the deep layers (K = 256 / 512 over 32-128 workgroups) take 2-4 memory round trips instead of 8-16.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-constexpr int PT_BM = 64, PT_BN = 64, PT_RS = PT_BN + 32;  // LDS row stride of a k-major image: 192 bytes
+constexpr int PT_RS = PT_BN + 32;  // LDS row stride of a k-major image: 192 bytes
 
 __device__ __forceinline__ bf16x8 pt_tr_operand(const u16* img, int krow0, int col0, int lane) {
   // 32-column operand tile of a k-major image: lane (c = lane & 31, h = lane >> 5) gets k = krow0 + 8h .. + 7 of column col0 + c
@@ -382,26 +384,6 @@ __global__ __launch_bounds__(256) void pw_bf16_tr_kernel(const u16* __restrict__
       acc = (f32x16){0};
     }
   }
-}
-
-// the pipelined transposed-read kernel takes maps of whole 8-position groups and K in whole chunks (always, when the shape allows)
-static bool pw_tr_ok(int M, int K, int S) {
-  constexpr int on = 1;
-  return on && S % 8 == 0 && K % 32 == 0 && K <= PB_MAXK && M % 8 == 0;
-}
-template <bool STATS, bool TRANS_W>
-static void pw_tr_launch(const u16* z, const float* in_scale, const float* in_shift, const float* w, u16* y, double* partials,
-                         int N, int M, int K, int S, const msl::BnFold& fold, hipStream_t st) {
-  const int tiles_img = msl::cdiv(S, PT_BN), mtiles = msl::cdiv(M, PT_BM);
-  // several position tiles per workgroup once the launch has more than ~2 workgroups per CU (block 1: 2048 tiles)
-  const int T = std::max(1, std::min(std::min(4, tiles_img), (tiles_img * mtiles * N) / 512));
-  dim3 grid(msl::cdiv(tiles_img, T), mtiles, N);
-#define MSL_PT(BK_) MSL_LAUNCH((pw_bf16_tr_kernel<BK_, STATS, TRANS_W>), grid, dim3(256), 0, st, z, in_scale, in_shift, w, y, \
-                                       partials, M, K, S, T, fold)
-  if (K % 128 == 0) MSL_PT(128);
-  else if (K % 64 == 0) MSL_PT(64);
-  else MSL_PT(32);
-#undef MSL_PT
 }
 
 // ---- materialise -------------------------------------------------------------------------------------------------
@@ -680,6 +662,66 @@ __global__ __launch_bounds__(256) void dw_bww_bf16_kernel(const u16* __restrict_
   }
 }
 
+// ---- pointwise launchers: the PwRoute (pwroute.hpp) names the kernel, its template arguments and the grid ---------------------------
+struct PwGemmArgs {  // forward: X = z, Y = y; bwd-data (TRANS_W): X = dy, Y = g_in, no affine, no statistics
+  const u16* X;
+  const float *in_scale, *in_shift, *w;
+  u16* Y;
+  double* partials;
+  int S;
+  const msl::BnFold& fold;
+  hipStream_t st;
+};
+
+template <bool STATS, bool TRANS_W>
+int launch_pw_tr(const PwRoute& r, const PwGemmArgs& a) {
+  return msl::dispatch_int<32, 64, 128>(r.bk, [&](auto bk) {
+    MSL_LAUNCH((pw_bf16_tr_kernel<decltype(bk)::value, STATS, TRANS_W>), r.grid, dim3(r.threads), 0, a.st, a.X, a.in_scale,
+               a.in_shift, a.w, a.Y, a.partials, r.M, r.K, a.S, r.tpw, a.fold);
+    return MSL_OK;
+  });
+}
+
+template <bool STATS, bool TRANS_W>
+int launch_pw_plain(const PwRoute& r, const PwGemmArgs& a) {
+  MSL_LAUNCH((pw_fwd_bf16_kernel<STATS, TRANS_W>), r.grid, dim3(r.threads), 0, a.st, a.X, a.in_scale, a.in_shift, a.w, a.Y, a.partials,
+             r.M, r.K, a.S, a.fold);
+  return MSL_OK;
+}
+
+// the three instantiations of either kernel: forward with and without statistics, bwd-data on transposed weights
+template <bool TRANS_W>
+int launch_pw_gemm(const PwRoute& r, const PwGemmArgs& a) {
+  const bool tr = r.kind == PwKind::Bf16Tr;
+  int rc;
+  if constexpr (TRANS_W) {
+    rc = tr ? launch_pw_tr<false, true>(r, a) : launch_pw_plain<false, true>(r, a);
+  } else {
+    rc = msl::dispatch_bool(a.partials != nullptr, [&](auto stats) {
+      return tr ? launch_pw_tr<decltype(stats)::value, false>(r, a) : launch_pw_plain<decltype(stats)::value, false>(r, a);
+    });
+  }
+  if (rc != MSL_OK) return rc;
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+int launch_pw_bww(const PwRoute& r, const u16* dy, const u16* z, const float* in_scale, const float* in_shift, float* out, int N,
+                  int Cin, int Cout, int S, hipStream_t st) {
+  return msl::dispatch_bool(in_scale != nullptr, [&](auto affine) {
+    constexpr bool A = decltype(affine)::value;
+    if (r.kind == PwKind::Bf16BwwAny) {
+      MSL_LAUNCH(pw_bww_bf16_any_kernel<A>, r.grid, dim3(r.threads), 0, st, dy, z, in_scale, in_shift, out, N, Cout, Cin, S);
+      return MSL_OK;
+    }
+    return msl::dispatch_int<1, 2>(r.mt, [&](auto mt) {
+      MSL_LAUNCH((pw_bww_bf16_kernel<decltype(mt)::value, A>), r.grid, dim3(r.threads), 0, st, dy, z, in_scale, in_shift, out, Cout,
+                 Cin, S, r.chunks_per_img, r.total_chunks, r.chunks_per_block);
+      return MSL_OK;
+    });
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -707,7 +749,8 @@ int msl_dwconv_fwd_bf16(const void* x, const float* in_scale, const float* in_sh
   return MSL_OK;
 }
 
-int msl_pwconv_fwd_bf16_num_partials(int N, int S) { return N * msl::cdiv(S, PB_BN) * 2; }
+// (the count does not depend on the channel numbers: any pair gives it)
+int msl_pwconv_fwd_bf16_num_partials(int N, int S) { return pw_route(PwOp::Fwd, true, N, PB_BK, PB_BM, S, true).num_partials; }
 
 // z (N,Cin,S) bf16 raw + optional input affine -> y (N,Cout,S) bf16 raw (+ stat partials [2][Cout][NP] or NULL)
 static const msl::BnFold pb_nofold{nullptr, 0, 0, 1.0, nullptr, nullptr, 0.f};
@@ -715,22 +758,8 @@ static const msl::BnFold pb_nofold{nullptr, 0, 0, 1.0, nullptr, nullptr, 0.f};
 static int pw_fwd_bf16_impl(const void* z, const float* in_scale, const float* in_shift, const msl::BnFold& fold, const float* w,
                             void* y, double* partials, int N, int Cin, int Cout, int S, void* stream) {
   if (N <= 0 || S <= 0 || Cin % PB_BK != 0 || Cout <= 0) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (pw_tr_ok(Cout, Cin, S)) {
-    if (partials) pw_tr_launch<true, false>((const u16*)z, in_scale, in_shift, w, (u16*)y, partials, N, Cout, Cin, S, fold, st);
-    else pw_tr_launch<false, false>((const u16*)z, in_scale, in_shift, w, (u16*)y, partials, N, Cout, Cin, S, fold, st);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  dim3 grid(msl::cdiv(S, PB_BN), msl::cdiv(Cout, PB_BM), N);
-  if (partials)
-    MSL_LAUNCH(pw_fwd_bf16_kernel<true>, grid, dim3(256), 0, st, (const u16*)z, in_scale, in_shift, w, (u16*)y,
-                       partials, Cout, Cin, S, fold);
-  else
-    MSL_LAUNCH(pw_fwd_bf16_kernel<false>, grid, dim3(256), 0, st, (const u16*)z, in_scale, in_shift, w, (u16*)y,
-                       partials, Cout, Cin, S, fold);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  const PwGemmArgs a{(const u16*)z, in_scale, in_shift, w, (u16*)y, partials, S, fold, (hipStream_t)stream};
+  return launch_pw_gemm<false>(pw_route(PwOp::Fwd, true, N, Cin, Cout, S, partials != nullptr), a);
 }
 
 int msl_pwconv_fwd_bf16(const void* z, const float* in_scale, const float* in_shift, const float* w, void* y,
@@ -788,63 +817,23 @@ int msl_bn_relu_materialize_bf16_pad32_fold(const void* y, const double* in_part
 // dy (N,Cout,S) bf16 -> g_in (N,Cin,S) bf16 = W^T . dy   (bf16 MFMA, fp32 accumulate)
 int msl_pwconv_bwd_data_bf16(const void* dy, const float* w, void* g_in, int N, int Cin, int Cout, int S, void* stream) {
   if (N <= 0 || S <= 0 || Cout % PB_BK != 0 || Cin % 8 != 0) return MSL_ERR_ARG;
-  if (pw_tr_ok(Cin, Cout, S)) {
-    pw_tr_launch<false, true>((const u16*)dy, nullptr, nullptr, w, (u16*)g_in, nullptr, N, Cin, Cout, S, pb_nofold, (hipStream_t)stream);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  dim3 grid(msl::cdiv(S, PB_BN), msl::cdiv(Cin, PB_BM), N);
-  MSL_LAUNCH((pw_fwd_bf16_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, (const u16*)dy, nullptr, nullptr,
-                     w, (u16*)g_in, nullptr, Cin, Cout, S, pb_nofold);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  const PwGemmArgs a{(const u16*)dy, nullptr, nullptr, w, (u16*)g_in, nullptr, S, pb_nofold, (hipStream_t)stream};
+  return launch_pw_gemm<true>(pw_route(PwOp::BwdData, true, N, Cin, Cout, S, false), a);
 }
 
-// position split of msl_pwconv_bwd_weight_slabs_bf16 (number of [Cout][Cin] fp32 slabs; 1: the result itself)
-static inline bool bww_bf16_plan(int N, int Cin, int Cout, int S, int& mt, int& tiles, int& cpi, int& total, int& ks, int& cpb) {
-  if (S % 64 != 0 || Cin % 32 != 0 || Cout % 32 != 0) return false;
-  mt = (Cout % 64 == 0) ? 2 : 1;
-  tiles = (Cout / (32 * mt)) * (Cin / 32);
-  cpi = S / 64;
-  total = N * cpi;
-  ks = std::max(1, std::min(256 / std::max(1, tiles), total / 4));
-  cpb = msl::cdiv(total, ks);
-  ks = msl::cdiv(total, cpb);
-  return true;
-}
+// number of [Cout][Cin] fp32 slabs of msl_pwconv_bwd_weight_slabs_bf16 (1: the result itself)
 int msl_pwconv_bwd_weight_bf16_nslabs(int N, int Cin, int Cout, int S) {
-  int mt, tiles, cpi, total, ks, cpb;
   if (N <= 0 || Cin <= 0 || Cout <= 0 || S <= 0) return MSL_ERR_ARG;
-  return bww_bf16_plan(N, Cin, Cout, S, mt, tiles, cpi, total, ks, cpb) ? ks : 1;
+  return pw_route(PwOp::BwdWeight, true, N, Cin, Cout, S, false).nslabs;
 }
 // dy (N,Cout,S), z (N,Cin,S) bf16 -> out = [nslabs][Cout][Cin] fp32 partial weight gradients (MFMA kernel when S % 64 == 0
 // and the channel counts are multiples of 32; a plain one-slab kernel otherwise)
 int msl_pwconv_bwd_weight_slabs_bf16(const void* dy, const void* z, const float* in_scale, const float* in_shift, float* out,
                                      int N, int Cin, int Cout, int S, void* stream) {
-  int mt, tiles, cpi, total, ks, cpb;
   if (N <= 0 || Cin <= 0 || Cout <= 0 || S <= 0) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (!bww_bf16_plan(N, Cin, Cout, S, mt, tiles, cpi, total, ks, cpb)) {
-    dim3 g(msl::cdiv(Cin, 16), msl::cdiv(Cout, 16));
-    if (in_scale)
-      MSL_LAUNCH(pw_bww_bf16_any_kernel<true>, g, dim3(256), 0, st, (const u16*)dy, (const u16*)z, in_scale, in_shift, out,
-                         N, Cout, Cin, S);
-    else
-      MSL_LAUNCH(pw_bww_bf16_any_kernel<false>, g, dim3(256), 0, st, (const u16*)dy, (const u16*)z, in_scale, in_shift, out,
-                         N, Cout, Cin, S);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  dim3 grid(ks, tiles);
-#define MSL_BW(MT_, A_)                                                                                              \
-  MSL_LAUNCH((pw_bww_bf16_kernel<MT_, A_>), grid, dim3(256), 0, st, (const u16*)dy, (const u16*)z, in_scale, \
-                     in_shift, out, Cout, Cin, S, cpi, total, cpb)
-  if (mt == 2) {
-    if (in_scale) MSL_BW(2, true); else MSL_BW(2, false);
-  } else {
-    if (in_scale) MSL_BW(1, true); else MSL_BW(1, false);
-  }
-#undef MSL_BW
+  const int rc = launch_pw_bww(pw_route(PwOp::BwdWeight, true, N, Cin, Cout, S, false), (const u16*)dy, (const u16*)z, in_scale,
+                               in_shift, out, N, Cin, Cout, S, (hipStream_t)stream);
+  if (rc != MSL_OK) return rc;
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

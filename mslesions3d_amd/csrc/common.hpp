@@ -80,6 +80,11 @@ inline int dispatch_int(int v, F&& f) {
   (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
   return rc;
 }
+// dispatch_bool(v, f) calls f(std::true_type{}) or f(std::false_type{}) and returns what f returns
+template <typename F>
+inline int dispatch_bool(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
 }  // namespace msl
 
 namespace msl {

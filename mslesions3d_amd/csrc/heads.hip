@@ -916,8 +916,7 @@ __global__ __launch_bounds__(256) void head_bww_lds_kernel(const float* __restri
 // the LDS-staged kernels take cubic W = H in {4, 8, 16} feature maps (W = 4: whole groups of 4 planes) and 16 output
 // channels (12 + 2*2: two classes)
 inline int head_lds_w(int C, int D, int H, int W, int MT = 1) {
-  constexpr int on = 1;
-  if (!on || MT != 1 || H != W || C % 16 != 0 || (D * H * W) % 64 != 0) return 0;
+  if (MT != 1 || H != W || C % 16 != 0 || (D * H * W) % 64 != 0) return 0;
   if (W == 16 || W == 8) return W;
   if (W == 4 && D % 4 == 0) return 4;
   return 0;

@@ -10,16 +10,13 @@
 //   bwd-data: M = Cin,  K = Cout, W element (m,k) = W[k*M + m]   (transposed read of the same weights)
 //   bwd-wgt : dW[Cout x Cin] = sum_{n,s} dY[co,s] * A[ci,s]      (split over s, fixed-order slab reduction)
 #include "common.hpp"
-#include <algorithm>
-#include <cstdlib>
+#include "pwroute.hpp"
+
+using namespace msl::pw;  // tile sizes, PwRoute
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 64, BN = 128, BK = 32;
-constexpr int FOLD_MAXK = 512;  // input channels whose (scale, shift) are kept in LDS
-constexpr int WS_LD = BK + 1;
 
 template <bool AFFINE, bool STATS, bool TRANS_W>
 __global__ __launch_bounds__(256) void pw_gemm_kernel(const float* __restrict__ X,
@@ -160,8 +157,6 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float* __restrict__ 
 // (down to 512 x 64 x 512 per image), so a 64 x 128 tile with a serial K loop leaves the chip idle behind load
 // latency.  Here a workgroup owns a 32 x 64 tile and its 4 waves each take a quarter of K (private LDS
 // staging, next chunk prefetched into registers during the MFMAs), followed by a fixed-order reduction.
-constexpr int KS_BM = 32, KS_BN = 64;
-constexpr int KS_WAVE_LDS = BK * KS_BN + KS_BM * WS_LD;  // floats per wave
 
 template <bool AFFINE, bool STATS, bool TRANS_W, int NW>
 __global__ __launch_bounds__(NW * 64) void pw_gemm_ksplit_kernel(const float* __restrict__ X,
@@ -598,95 +593,10 @@ __global__ __launch_bounds__(256) void pw_strip_kernel(const float* __restrict__
   }
 }
 
-// which (K, M, S) take the column-strip kernel, and with which strip width (0: none): the forward and bwd-data GEMMs of
-// blocks 1-3 (K = input channels of the GEMM, M = output rows)
-static inline int strip_cols(int N, int K, int M, int S) {
-  constexpr int on = 1;
-  if (!on) return 0;
-  int cols = 0;
-  if (K == 32 && M == 64) cols = 256;
-  else if (K == 64 && M == 32) cols = 128;
-  else if ((K == 64 && M == 128) || (K == 128 && (M == 128 || M == 64))) cols = 64;
-  // (32-column strips - two workgroups per CU - measured equal or slower: 8.2 -> 9.4 us and 11.1 -> 12.4 us on blocks 2 / 3)
-  if (!cols || S % cols != 0 || (long long)N * (S / cols) < 128) return 0;
-  return cols;
-}
-
-template <bool AFFINE, bool STATS, bool TRANS_W>
-static int launch_strip(const float* X, const float* in_scale, const float* in_shift, const float* Wt, float* Y,
-                        double* partials, int N, int M, int K, int S, int cols, const msl::BnFold& fold, hipStream_t st) {
-  dim3 grid(S / cols, N);
-#define MSL_ST(K_, C_, MT_) \
-  MSL_LAUNCH((pw_strip_kernel<K_, C_, MT_, AFFINE, STATS, TRANS_W>), grid, dim3(256), 0, st, X, in_scale, in_shift, Wt, Y, partials, S, fold)
-  if (K == 32 && M == 64) MSL_ST(32, 256, 2);
-  else if (K == 64 && M == 32) MSL_ST(64, 128, 1);
-  else if (K == 64 && M == 128) MSL_ST(64, 64, 4);
-  else if (K == 128 && M == 128) MSL_ST(128, 64, 4);
-  else if (K == 128 && M == 64) MSL_ST(128, 64, 2);
-  else return MSL_ERR_UNSUPPORTED;
-#undef MSL_ST
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
-// column tiles per wave of the unsplit form (K <= 64): two when that still leaves >= 2 waves per SIMD - the weight rows, the
-// input affine and the statistics reduction are then paid once per 64 columns
-static inline int wave_nt(int N, int K, int M, int S) {
-  constexpr int force = 0;
-  if (K > 64) return 1;
-  if (force) return force;
-  const int mt = (M % 64 == 0) ? 2 : 1;
-  const long long waves = (long long)N * msl::cdiv(S, 32) * (M / (32 * mt));
-  return waves >= 4096 ? 2 : 1;
-}
-
-// which form runs a (K, M) GEMM: 0 = the LDS-staged kernels above, else KW (NWK = K / KW)
-static inline int wave_form(int K, int M) {
-  if (M % 32 != 0) return 0;
-  if (K == 32) return 32;
-  if (K == 64 || K == 128 || K == 256 || K == 512) return 64;
-  return 0;
-}
-
-template <bool AFFINE, bool STATS, bool TRANS_W>
-static int launch_wave(const float* X, const float* in_scale, const float* in_shift, const float* Wt, float* Y,
-                       double* partials, int N, int M, int K, int S, const msl::BnFold& fold, hipStream_t st) {
-#define MSL_WV(KW_, MT_, NWK_)                                                                                        \
-  MSL_LAUNCH((pw_wave_kernel<KW_, MT_, AFFINE, STATS, TRANS_W, NWK_>),                                        \
-                     dim3(msl::cdiv(S, NWK_ == 1 ? 128 : 32), M / (32 * MT_), N), dim3(NWK_ == 1 ? 256 : NWK_ * 64), \
-                     0, st, X, in_scale, in_shift, Wt, Y, partials, M, K, S, fold)
-#define MSL_WV1(KW_, MT_)                                                                                              \
-  do {                                                                                                                 \
-    if (nt == 2)                                                                                                       \
-      MSL_LAUNCH((pw_wave_kernel<KW_, MT_, AFFINE, STATS, TRANS_W, 1, 2>), dim3(msl::cdiv(S, 256), M / (32 * MT_), N), \
-                         dim3(256), 0, st, X, in_scale, in_shift, Wt, Y, partials, M, K, S, fold);                     \
-    else                                                                                                               \
-      MSL_WV(KW_, MT_, 1);                                                                                             \
-  } while (0)
-  const bool two = M % 64 == 0;
-  const int nt = STATS ? wave_nt(N, K, M, S) : 1;  // pays where the statistics epilogue is amortised (measured: tools/bench_pw.py)
-  if (K == 32) {
-    if (two) MSL_WV1(32, 2); else MSL_WV1(32, 1);
-  } else if (K == 64) {
-    if (two) MSL_WV1(64, 2); else MSL_WV1(64, 1);
-  } else {
-    switch (K / 64) {
-      case 2: MSL_WV(64, 1, 2); break;
-      case 4: MSL_WV(64, 1, 4); break;
-      case 8: MSL_WV(64, 1, 8); break;
-      default: return MSL_ERR_UNSUPPORTED;
-    }
-  }
-#undef MSL_WV1
-#undef MSL_WV
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // bwd-weight.  Block = (k-split, output tile 64 x BNN).  The 4 waves split every 64-position chunk four
 // ways and each keeps the whole tile's accumulators; fixed-order in-block reduction, then one slab per block.
-constexpr int PC = 64, PC_LD = PC + 1;
+constexpr int PC_LD = PC + 1;
 
 template <int BNN, bool AFFINE>
 __global__ __launch_bounds__(256) void pw_bwd_weight_kernel(const float* __restrict__ dY,
@@ -920,7 +830,6 @@ __global__ __launch_bounds__(256) void pw_bww_wave_kernel(const float* __restric
 // two to eight chunks each: four launches of ~8 us that are all latency.  ONE launch runs up to four such layers side by
 // side: workgroup b belongs to the layer k with first[k] <= b < first[k+1] and is that layer's workgroup
 // (ks, tile) = ((b - first[k]) % ksplit[k], (b - first[k]) / ksplit[k]); same arithmetic, same slabs, same bits.
-constexpr int PW_BWW_BATCH_MAX = 4;
 struct PwBwwBatch {
   const float* dY[PW_BWW_BATCH_MAX];
   const float* Z[PW_BWW_BATCH_MAX];
@@ -943,27 +852,6 @@ __global__ __launch_bounds__(256) void pw_bww_wave_batch_kernel(PwBwwBatch b, in
                             local / b.ksplit[k]);
 }
 
-struct BwwWavePlan {
-  int mt, tiles, chunks_per_img, total_chunks, ksplit, chunks_per_block;
-};
-
-// Supported: whole 32-position chunks and 32-channel tiles.  nslabs == 1 -> the kernel writes dW itself.
-static inline bool bww_wave_plan(int N, int Cin, int Cout, int S, BwwWavePlan& p) {
-  constexpr int off = 1;
-  if (!off || S % 32 != 0 || Cin % 32 != 0 || Cout % 32 != 0) return false;
-  p.mt = (Cout % 64 == 0) ? 2 : 1;
-  p.tiles = (Cout / (32 * p.mt)) * (Cin / 32);
-  p.chunks_per_img = S / 32;
-  p.total_chunks = N * p.chunks_per_img;
-  // position split: about one workgroup per CU in total, at least 8 chunks (2 per wave) each - every split costs a
-  // Cout x Cin slab written and read back
-  constexpr int target = 256;
-  int ks = std::max(1, std::min(target / std::max(1, p.tiles), p.total_chunks / 8));
-  p.chunks_per_block = msl::cdiv(p.total_chunks, ks);
-  p.ksplit = msl::cdiv(p.total_chunks, p.chunks_per_block);
-  return true;
-}
-
 // out[i] = sum_k slabs[k][i], k ascending (fixed order)
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ out,
                                                           int count, int nslabs) {
@@ -973,103 +861,140 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   if ((threadIdx.x >> 5) == 0 && i < count) out[i] = t;
 }
 
-struct BwPlan {
-  int bnn, ksplit, chunks_per_img, chunks_per_block;
+
+// ---- launchers: one per kernel family; the PwRoute (pwroute.hpp) names the instantiation, the grid and the dynamic LDS -------------
+struct GemmArgs {  // forward: X = z, Y = y; bwd-data (TRANS_W): X = dy, Y = g_in, no affine, no statistics
+  const float *X, *in_scale, *in_shift, *Wt;
+  float* Y;
+  double* partials;
+  int S;
+  const msl::BnFold& fold;
+  hipStream_t st;
 };
 
-BwPlan bw_plan(int N, int Cin, int Cout, int S) {
-  BwPlan p;
-  p.bnn = (Cin % 64 == 0) ? 64 : 32;
-  p.chunks_per_img = msl::cdiv(S, PC);
-  const int total = N * p.chunks_per_img;
-  const int tiles = (Cout / 64) * (Cin / p.bnn);
-  // K split: enough workgroups to matter, but at least 8 position chunks each - every split costs a Cout x Cin slab
-  // written and read back (a 256-way split of block 2 moved 8 MB of slabs for 12 MB of operands), and this kernel
-  // runs on the weight-gradient stream beside the dependency chain, where fewer, longer workgroups interfere less
-  int ks = std::max(1, std::min(total, 512 / std::max(1, tiles)));
-  constexpr int min_cpb = 1;
-  ks = std::max(1, std::min(ks, total / std::max(1, min_cpb)));
-  p.chunks_per_block = msl::cdiv(total, ks);
-  p.ksplit = msl::cdiv(total, p.chunks_per_block);
-  return p;
+// f(AFFINE, STATS) for the instantiations that exist: all four forms of the forward, the plain form on transposed weights
+template <bool TRANS_W, typename F>
+int dispatch_form(const GemmArgs& a, F&& f) {
+  if constexpr (TRANS_W) {
+    return f(std::false_type{}, std::false_type{});
+  } else {
+    return msl::dispatch_bool(a.in_scale || a.fold.partials, [&](auto affine) {
+      return msl::dispatch_bool(a.partials != nullptr, [&](auto stats) { return f(affine, stats); });
+    });
+  }
+}
+
+template <bool TRANS_W>
+int launch_strip(const PwRoute& r, const GemmArgs& a) {
+  return msl::dispatch_int<0, 1, 2, 3, 4>(r.form, [&](auto f) {
+    constexpr const int* F = STRIP_FORMS[decltype(f)::value];
+    return dispatch_form<TRANS_W>(a, [&](auto affine, auto stats) {
+      MSL_LAUNCH((pw_strip_kernel<F[0], F[1], F[2], decltype(affine)::value, decltype(stats)::value, TRANS_W>), r.grid,
+                 dim3(r.threads), 0, a.st, a.X, a.in_scale, a.in_shift, a.Wt, a.Y, a.partials, a.S, a.fold);
+      return MSL_OK;
+    });
+  });
+}
+
+template <bool TRANS_W>
+int launch_wave(const PwRoute& r, const GemmArgs& a) {
+  return msl::dispatch_int<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(r.form, [&](auto f) {
+    constexpr const int* F = WAVE_FORMS[decltype(f)::value];
+    return dispatch_form<TRANS_W>(a, [&](auto affine, auto stats) {
+      MSL_LAUNCH((pw_wave_kernel<F[0], F[1], decltype(affine)::value, decltype(stats)::value, TRANS_W, F[2], F[3]>), r.grid,
+                 dim3(r.threads), 0, a.st, a.X, a.in_scale, a.in_shift, a.Wt, a.Y, a.partials, r.M, r.K, a.S, a.fold);
+      return MSL_OK;
+    });
+  });
+}
+
+template <bool TRANS_W>
+int launch_ksplit(const PwRoute& r, const GemmArgs& a) {
+  return msl::dispatch_int<4, 8>(r.nw, [&](auto nw) {
+    return dispatch_form<TRANS_W>(a, [&](auto affine, auto stats) {
+      auto k = pw_gemm_ksplit_kernel<decltype(affine)::value, decltype(stats)::value, TRANS_W, decltype(nw)::value>;
+      if (r.lds_bytes > 64 * 1024) {  // the 8-wave form
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds_bytes);
+        if (e != hipSuccess) return (int)e;
+      }
+      MSL_LAUNCH(k, r.grid, dim3(r.threads), r.lds_bytes, a.st, a.X, a.in_scale, a.in_shift, a.Wt, a.Y, a.partials, r.M, r.K, a.S,
+                 a.fold);
+      return MSL_OK;
+    });
+  });
+}
+
+template <bool TRANS_W>
+int launch_gemm(const PwRoute& r, const GemmArgs& a) {
+  return dispatch_form<TRANS_W>(a, [&](auto affine, auto stats) {
+    MSL_LAUNCH((pw_gemm_kernel<decltype(affine)::value, decltype(stats)::value, TRANS_W>), r.grid, dim3(r.threads), 0, a.st, a.X,
+               a.in_scale, a.in_shift, a.Wt, a.Y, a.partials, r.M, r.K, a.S, a.fold);
+    return MSL_OK;
+  });
+}
+
+template <bool TRANS_W>
+int launch_route(const PwRoute& r, const GemmArgs& a) {
+  const int rc = r.kind == PwKind::Strip ? launch_strip<TRANS_W>(r, a)
+                 : r.kind == PwKind::Wave ? launch_wave<TRANS_W>(r, a)
+                 : r.kind == PwKind::KSplit ? launch_ksplit<TRANS_W>(r, a)
+                                            : launch_gemm<TRANS_W>(r, a);
+  if (rc != MSL_OK) return rc;
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
+}
+
+struct BwwArgs {
+  const float *dy, *z, *in_scale, *in_shift;
+  float* out;
+  int N, Cin, Cout, S;
+  hipStream_t st;
+};
+
+int launch_bww_wave(const PwRoute& r, const BwwArgs& a) {
+  return msl::dispatch_int<1, 2>(r.mt, [&](auto mt) {
+    return msl::dispatch_bool(a.in_scale != nullptr, [&](auto affine) {
+      MSL_LAUNCH((pw_bww_wave_kernel<decltype(mt)::value, decltype(affine)::value>), r.grid, dim3(r.threads), 0, a.st, a.dy, a.z,
+                 a.in_scale, a.in_shift, a.out, a.Cout, a.Cin, a.S, r.chunks_per_img, r.total_chunks, r.chunks_per_block);
+      return MSL_OK;
+    });
+  });
+}
+
+int launch_bww_tile(const PwRoute& r, const BwwArgs& a) {
+  return msl::dispatch_int<32, 64>(r.bnn, [&](auto bnn) {
+    return msl::dispatch_bool(a.in_scale != nullptr, [&](auto affine) {
+      MSL_LAUNCH((pw_bwd_weight_kernel<decltype(bnn)::value, decltype(affine)::value>), r.grid, dim3(r.threads), 0, a.st, a.dy, a.z,
+                 a.in_scale, a.in_shift, a.out, a.Cout, a.Cin, a.S, a.N, r.chunks_per_img, r.chunks_per_block);
+      return MSL_OK;
+    });
+  });
+}
+
+const msl::BnFold pw_nofold{nullptr, 0, 0, 1.0, nullptr, nullptr, 0.f};
+
+// z (N,Cin,S) raw + input affine -> y (N,Cout,S) raw + stat partials [2][Cout][NP]
+int pwconv_fwd_impl(const float* z, const float* in_scale, const float* in_shift, const msl::BnFold& fold, const float* w, float* y,
+                    double* partials, int N, int Cin, int Cout, int S, void* stream) {
+  if (N <= 0 || S <= 0 || Cin % BK != 0 || Cout % 4 != 0) return MSL_ERR_ARG;
+  if ((in_scale || fold.partials) && Cin > FOLD_MAXK) return MSL_ERR_UNSUPPORTED;
+  return launch_route<false>(pw_route(PwOp::Fwd, false, N, Cin, Cout, S, partials != nullptr),
+                             GemmArgs{z, in_scale, in_shift, w, y, partials, S, fold, (hipStream_t)stream});
 }
 
 }  // namespace
 
 extern "C" {
 
-// K-split pays when the plain 64 x 128 tiling cannot fill the chip (tail layers); with >= 256 plain tiles the
-// serial-K kernel wins (no cross-wave reduction).
-static inline bool use_ksplit(int K, int M, int S, int N) {
-  return K >= 128 && K % 128 == 0 && msl::cdiv(S, BN) * msl::cdiv(M, BM) * N < 256;
+// (int)PwKind of the route a call of this shape takes: host arithmetic only, nothing is launched (tests name their cases by it)
+int msl_pwconv_route_kind(int op, int bf16, int N, int Cin, int Cout, int S, int stats) {
+  if (op < (int)PwOp::Fwd || op > (int)PwOp::BwdFused || (bf16 != 0 && bf16 != 1)) return MSL_ERR_ARG;
+  if (N <= 0 || Cin <= 0 || Cout <= 0 || S <= 0) return MSL_ERR_ARG;
+  return (int)pw_route((PwOp)op, bf16 != 0, N, Cin, Cout, S, stats != 0).kind;
 }
 
 int msl_pwconv_fwd_num_partials(int N, int Cin, int Cout, int S) {
-  if (const int cols = strip_cols(N, Cin, Cout, S)) return N * (S / cols);
-  if (wave_form(Cin, Cout)) return N * msl::cdiv(S, Cin <= 64 ? 128 * wave_nt(N, Cin, Cout, S) : 32);
-  return N * msl::cdiv(S, use_ksplit(Cin, Cout, S, N) ? KS_BN : BN);
-}
-
-// z (N,Cin,S) raw + input affine -> y (N,Cout,S) raw + stat partials [2][Cout][NP]
-static const msl::BnFold pw_nofold{nullptr, 0, 0, 1.0, nullptr, nullptr, 0.f};
-
-static int pwconv_fwd_impl(const float* z, const float* in_scale, const float* in_shift, const msl::BnFold& fold,
-                           const float* w, float* y, double* partials, int N, int Cin, int Cout, int S, void* stream) {
-  if (N <= 0 || S <= 0 || Cin % BK != 0 || Cout % 4 != 0) return MSL_ERR_ARG;
-  if ((in_scale || fold.partials) && Cin > FOLD_MAXK) return MSL_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (const int cols = strip_cols(N, Cin, Cout, S)) {
-    if (in_scale || fold.partials) {
-      if (partials) return launch_strip<true, true, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, cols, fold, st);
-      return launch_strip<true, false, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, cols, fold, st);
-    }
-    if (partials) return launch_strip<false, true, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, cols, fold, st);
-    return launch_strip<false, false, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, cols, fold, st);
-  }
-  if (wave_form(Cin, Cout)) {
-    if (in_scale || fold.partials) {
-      if (partials) return launch_wave<true, true, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, fold, st);
-      return launch_wave<true, false, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, fold, st);
-    }
-    if (partials) return launch_wave<false, true, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, fold, st);
-    return launch_wave<false, false, false>(z, in_scale, in_shift, w, y, partials, N, Cout, Cin, S, fold, st);
-  }
-  if (use_ksplit(Cin, Cout, S, N)) {
-    dim3 g2(msl::cdiv(S, KS_BN), msl::cdiv(Cout, KS_BM), N);
-#define MSL_KS(A_, S_, T_, X_, Wp_, Y_, P_, M_, K_)                                                                  \
-  do {                                                                                                             \
-    if ((K_) % 256 == 0) {                                                                                         \
-      const size_t lds_ = (size_t)8 * KS_WAVE_LDS * sizeof(float);                                                 \
-      hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_gemm_ksplit_kernel<A_, S_, T_, 8>),    \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_);                  \
-      if (e_ != hipSuccess) return (int)e_;                                                                        \
-      MSL_LAUNCH((pw_gemm_ksplit_kernel<A_, S_, T_, 8>), g2, dim3(512), lds_, st, X_, in_scale, in_shift,  \
-                         Wp_, Y_, P_, M_, K_, S, fold);                                                            \
-    } else {                                                                                                       \
-      MSL_LAUNCH((pw_gemm_ksplit_kernel<A_, S_, T_, 4>), g2, dim3(256),                                    \
-                         (size_t)4 * KS_WAVE_LDS * sizeof(float), st, X_, in_scale, in_shift, Wp_, Y_, P_, M_, K_, S, fold); \
-    }                                                                                                              \
-  } while (0)
-    if (in_scale || fold.partials) {
-      if (partials) MSL_KS(true, true, false, z, w, y, partials, Cout, Cin);
-      else MSL_KS(true, false, false, z, w, y, partials, Cout, Cin);
-    } else {
-      if (partials) MSL_KS(false, true, false, z, w, y, partials, Cout, Cin);
-      else MSL_KS(false, false, false, z, w, y, partials, Cout, Cin);
-    }
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  dim3 grid(msl::cdiv(S, BN), msl::cdiv(Cout, BM), N);
-  if (in_scale || fold.partials) {
-    if (partials) MSL_LAUNCH((pw_gemm_kernel<true, true, false>), grid, dim3(256), 0, st, z, in_scale, in_shift, w, y, partials, Cout, Cin, S, fold);
-    else MSL_LAUNCH((pw_gemm_kernel<true, false, false>), grid, dim3(256), 0, st, z, in_scale, in_shift, w, y, partials, Cout, Cin, S, fold);
-  } else {
-    if (partials) MSL_LAUNCH((pw_gemm_kernel<false, true, false>), grid, dim3(256), 0, st, z, in_scale, in_shift, w, y, partials, Cout, Cin, S, fold);
-    else MSL_LAUNCH((pw_gemm_kernel<false, false, false>), grid, dim3(256), 0, st, z, in_scale, in_shift, w, y, partials, Cout, Cin, S, fold);
-  }
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return pw_route(PwOp::Fwd, false, N, Cin, Cout, S, true).num_partials;
 }
 
 int msl_pwconv_fwd(const float* z, const float* in_scale, const float* in_shift, const float* w, float* y,
@@ -1090,41 +1015,17 @@ int msl_pwconv_fwd_fold(const float* z, const double* in_partials, int in_np, do
 int msl_pwconv_bwd_data(const float* dy, const float* w, float* g_in, int N, int Cin, int Cout, int S,
                         void* stream) {
   if (N <= 0 || S <= 0 || Cout % BK != 0 || Cin % 4 != 0) return MSL_ERR_ARG;
-  if (const int cols = strip_cols(N, Cout, Cin, S))
-    return launch_strip<false, false, true>(dy, nullptr, nullptr, w, g_in, nullptr, N, Cin, Cout, S, cols, pw_nofold,
-                                            (hipStream_t)stream);
-  if (wave_form(Cout, Cin))
-    return launch_wave<false, false, true>(dy, nullptr, nullptr, w, g_in, nullptr, N, Cin, Cout, S, pw_nofold,
-                                           (hipStream_t)stream);
-  if (use_ksplit(Cout, Cin, S, N)) {
-    dim3 g2(msl::cdiv(S, KS_BN), msl::cdiv(Cin, KS_BM), N);
-    hipStream_t st = (hipStream_t)stream;
-    const float *in_scale = nullptr, *in_shift = nullptr;
-    double* nopart = nullptr;
-    const msl::BnFold fold = pw_nofold;
-    MSL_KS(false, false, true, dy, w, g_in, nopart, Cin, Cout);
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  dim3 grid(msl::cdiv(S, BN), msl::cdiv(Cin, BM), N);
-  MSL_LAUNCH((pw_gemm_kernel<false, false, true>), grid, dim3(256), 0, (hipStream_t)stream, dy, nullptr,
-                     nullptr, w, g_in, nullptr, Cin, Cout, S, pw_nofold);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return launch_route<true>(pw_route(PwOp::BwdData, false, N, Cin, Cout, S, false),
+                            GemmArgs{dy, nullptr, nullptr, w, g_in, nullptr, S, pw_nofold, (hipStream_t)stream});
 }
 
 size_t msl_pwconv_bwd_weight_workspace_bytes(int N, int Cin, int Cout, int S) {
-  BwwWavePlan wp;
-  if (bww_wave_plan(N, Cin, Cout, S, wp)) return (size_t)wp.ksplit * Cout * Cin * sizeof(float);
-  BwPlan p = bw_plan(N, Cin, Cout, S);
-  return (size_t)p.ksplit * Cout * Cin * sizeof(float);
+  return (size_t)pw_route(PwOp::BwdWeight, false, N, Cin, Cout, S, false).nslabs * Cout * Cin * sizeof(float);
 }
 
 // Number of [Cout][Cin] slabs msl_pwconv_bwd_weight_slabs writes for this shape (1: the result itself).
 int msl_pwconv_bwd_weight_nslabs(int N, int Cin, int Cout, int S) {
-  BwwWavePlan wp;
-  if (bww_wave_plan(N, Cin, Cout, S, wp)) return wp.ksplit;
-  return bw_plan(N, Cin, Cout, S).ksplit;
+  return pw_route(PwOp::BwdWeight, false, N, Cin, Cout, S, false).nslabs;
 }
 
 // Partial weight gradients: out = [nslabs][Cout][Cin] (nslabs from msl_pwconv_bwd_weight_nslabs); their sum in slab
@@ -1132,40 +1033,20 @@ int msl_pwconv_bwd_weight_nslabs(int N, int Cin, int Cout, int S) {
 int msl_pwconv_bwd_weight_slabs(const float* dy, const float* z, const float* in_scale, const float* in_shift,
                                 float* out, int N, int Cin, int Cout, int S, void* stream) {
   if (N <= 0 || S <= 0 || Cin % 32 != 0 || Cout % 32 != 0) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  BwwWavePlan wp;
-  if (bww_wave_plan(N, Cin, Cout, S, wp)) {
-    dim3 grid(wp.ksplit, wp.tiles);
-#define MSL_BWW(MT_, A_)                                                                                          \
-  MSL_LAUNCH((pw_bww_wave_kernel<MT_, A_>), grid, dim3(256), 0, st, dy, z, in_scale, in_shift, out, Cout, Cin, \
-                     S, wp.chunks_per_img, wp.total_chunks, wp.chunks_per_block)
-    if (wp.mt == 2) {
-      if (in_scale) MSL_BWW(2, true); else MSL_BWW(2, false);
-    } else {
-      if (in_scale) MSL_BWW(1, true); else MSL_BWW(1, false);
-    }
-#undef MSL_BWW
-    MSL_LAUNCH_CHECK();
-    return MSL_OK;
-  }
-  if (Cout % 64 != 0) return MSL_ERR_ARG;
-  BwPlan p = bw_plan(N, Cin, Cout, S);
-  dim3 grid(p.ksplit, (Cout / 64) * (Cin / p.bnn));
-  if (p.bnn == 64) {
-    if (in_scale) MSL_LAUNCH((pw_bwd_weight_kernel<64, true>), grid, dim3(256), 0, st, dy, z, in_scale, in_shift, out, Cout, Cin, S, N, p.chunks_per_img, p.chunks_per_block);
-    else MSL_LAUNCH((pw_bwd_weight_kernel<64, false>), grid, dim3(256), 0, st, dy, z, in_scale, in_shift, out, Cout, Cin, S, N, p.chunks_per_img, p.chunks_per_block);
-  } else {
-    if (in_scale) MSL_LAUNCH((pw_bwd_weight_kernel<32, true>), grid, dim3(256), 0, st, dy, z, in_scale, in_shift, out, Cout, Cin, S, N, p.chunks_per_img, p.chunks_per_block);
-    else MSL_LAUNCH((pw_bwd_weight_kernel<32, false>), grid, dim3(256), 0, st, dy, z, in_scale, in_shift, out, Cout, Cin, S, N, p.chunks_per_img, p.chunks_per_block);
-  }
+  const PwRoute r = pw_route(PwOp::BwdWeight, false, N, Cin, Cout, S, false);
+  if (r.kind == PwKind::BwwTile && Cout % 64 != 0) return MSL_ERR_ARG;
+  const BwwArgs a{dy, z, in_scale, in_shift, out, N, Cin, Cout, S, (hipStream_t)stream};
+  const int rc = r.kind == PwKind::BwwWave ? launch_bww_wave(r, a) : launch_bww_tile(r, a);
+  if (rc != MSL_OK) return rc;
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
 
 // 1 when msl_pwconv_bwd_weight_slabs_batch takes this shape (the wave-autonomous form with 64-row tiles), else 0
 int msl_pwconv_bwd_weight_batchable(int N, int Cin, int Cout, int S) {
-  BwwWavePlan wp;
-  return (N > 0 && S > 0 && bww_wave_plan(N, Cin, Cout, S, wp) && wp.mt == 2) ? 1 : 0;
+  if (N <= 0 || S <= 0) return 0;
+  const PwRoute r = pw_route(PwOp::BwdWeight, false, N, Cin, Cout, S, false);
+  return (r.kind == PwKind::BwwWave && r.mt == 2) ? 1 : 0;
 }
 
 // msl_pwconv_bwd_weight_slabs for n <= 4 layers in ONE launch (host arrays of n entries each; every layer must be
@@ -1174,24 +1055,21 @@ int msl_pwconv_bwd_weight_slabs_batch(const float* const* dy, const float* const
                                       const float* const* in_shift, float* const* out, const int* Cin, const int* Cout,
                                       const int* S, int n, int N, void* stream) {
   if (n < 1 || n > PW_BWW_BATCH_MAX || N <= 0) return MSL_ERR_ARG;
-  PwBwwBatch b;
+  PwBwwBatch b{};  // layers past n: null pointers, zero sizes
   int total = 0;
   for (int k = 0; k < n; ++k) {
-    BwwWavePlan wp;
     if (!dy[k] || !z[k] || !in_scale[k] || !in_shift[k] || !out[k]) return MSL_ERR_ARG;
-    if (S[k] <= 0 || !bww_wave_plan(N, Cin[k], Cout[k], S[k], wp) || wp.mt != 2) return MSL_ERR_UNSUPPORTED;
+    if (!msl_pwconv_bwd_weight_batchable(N, Cin[k], Cout[k], S[k])) return MSL_ERR_UNSUPPORTED;
+    const PwRoute r = pw_route(PwOp::BwdWeight, false, N, Cin[k], Cout[k], S[k], false);
     b.dY[k] = dy[k]; b.Z[k] = z[k]; b.in_scale[k] = in_scale[k]; b.in_shift[k] = in_shift[k]; b.out[k] = out[k];
     b.Cout[k] = Cout[k]; b.Cin[k] = Cin[k]; b.S[k] = S[k];
-    b.chunks_per_img[k] = wp.chunks_per_img; b.total_chunks[k] = wp.total_chunks;
-    b.chunks_per_block[k] = wp.chunks_per_block; b.ksplit[k] = wp.ksplit;
+    b.chunks_per_img[k] = r.chunks_per_img; b.total_chunks[k] = r.total_chunks;
+    b.chunks_per_block[k] = r.chunks_per_block; b.ksplit[k] = r.nslabs;
     b.first[k] = total;
-    total += wp.ksplit * wp.tiles;
+    total += r.nslabs * r.tiles;
   }
   for (int k = n; k <= PW_BWW_BATCH_MAX; ++k) b.first[k] = total;
-  for (int k = n; k < PW_BWW_BATCH_MAX; ++k) {
-    b.dY[k] = b.Z[k] = b.in_scale[k] = b.in_shift[k] = nullptr; b.out[k] = nullptr;
-    b.Cout[k] = b.Cin[k] = b.S[k] = b.chunks_per_img[k] = b.total_chunks[k] = b.chunks_per_block[k] = 0; b.ksplit[k] = 1;
-  }
+  for (int k = n; k < PW_BWW_BATCH_MAX; ++k) b.ksplit[k] = 1;
   MSL_LAUNCH(pw_bww_wave_batch_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, b, n);
   MSL_LAUNCH_CHECK();
   return MSL_OK;

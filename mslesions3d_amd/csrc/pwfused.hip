@@ -14,7 +14,10 @@
 // columns as lanes for the data gradient - is conflict-free); the weight-gradient tile and the statistics stay in registers
 // across the workgroup's strips.  HBM-bound; MFMA only for the two 1x1x1 contractions.  No atomics: fixed summation order.
 #include "common.hpp"
+#include "pwroute.hpp"
 #include "../../include/mslesions3d_hip.h"
+
+using namespace msl::pw;
 
 namespace {
 
@@ -244,35 +247,26 @@ __global__ __launch_bounds__(512) void pw_bwd_fused_kernel(
     pw_bwd_fused_role<K, M, COLS, false>(g, y, Wt, z, gz, zpart, slabs, S, strips_per_img, total_strips, lds, coef, cz);
 }
 
-// workgroups (= statistics partials per channel = weight-gradient slabs): <= 256, so that the BatchNorm backward of z can fold
-// them in its own prologue (msl_bn_relu_bwd_finalize_apply)
-int fused_wgs(int N, int Cin, int Cout, int S) {
-  if (N <= 0 || Cin != 32 || Cout != 64 || S % 128 != 0) return 0;
-  const long long strips = (long long)N * (S / 128);
-  if (strips < 512) return 0;  // small layers: the separate launches are latency-, not bandwidth-bound
-  return 256;
-}
-
 }  // namespace
 
 extern "C" {
 
-int msl_pwconv_bwd_fused_num_partials(int N, int Cin, int Cout, int S) { return fused_wgs(N, Cin, Cout, S); }
+int msl_pwconv_bwd_fused_num_partials(int N, int Cin, int Cout, int S) {
+  return pw_route(PwOp::BwdFused, false, N, Cin, Cout, S, false).num_partials;
+}
 
 int msl_pwconv_bwd_fused(const float* g_y, const float* y, const float* bn_y_vec, const double* y_partials, int y_np,
                          double y_count, float* dgamma_y, float* dbeta_y, const float* w, const float* z,
                          const float* bn_z_vec, float* g_z, double* z_partials, float* dw_slabs, int N, int Cin, int Cout, int S,
                          void* stream) {
-  const int wgs = fused_wgs(N, Cin, Cout, S);
+  const PwRoute r = pw_route(PwOp::BwdFused, false, N, Cin, Cout, S, false);
   if (!g_y || !y || !bn_y_vec || !y_partials || y_np <= 0 || !w || !z || !bn_z_vec || !g_z || !z_partials || !dw_slabs)
     return MSL_ERR_ARG;
-  if (!wgs) return MSL_ERR_UNSUPPORTED;
-  constexpr int K = 64, M = 32, COLS = 128;
-  const size_t smem = ((size_t)(K + 2 * M) * (COLS + 1) + 4 * K + 4 * M) * sizeof(float);
-  auto k = pw_bwd_fused_kernel<K, M, COLS>;
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  MSL_LAUNCH(k, dim3(wgs), dim3(512), smem, (hipStream_t)stream, g_y, y, bn_y_vec, y_partials, y_np, y_count, dgamma_y,
-                     dbeta_y, w, z, bn_z_vec, g_z, z_partials, dw_slabs, S, S / COLS, N * (S / COLS));
+  if (r.kind != PwKind::Fused) return MSL_ERR_UNSUPPORTED;
+  auto k = pw_bwd_fused_kernel<FUSED_K, FUSED_M, FUSED_COLS>;
+  if (r.lds_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds_bytes);
+  MSL_LAUNCH(k, r.grid, dim3(r.threads), r.lds_bytes, (hipStream_t)stream, g_y, y, bn_y_vec, y_partials, y_np, y_count, dgamma_y, dbeta_y,
+             w, z, bn_z_vec, g_z, z_partials, dw_slabs, S, S / FUSED_COLS, N * (S / FUSED_COLS));
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

@@ -1,11 +1,11 @@
 // Stem: dense Conv3d(C_in -> 32, k3, stride (2,2,2) for cubes / (1,2,2) otherwise, pad 1, no bias)
 // Reference: conv_bn (lesions3d/mobilenet.py:26-31) used as features[0] (lesions3d/ssd3d.py:60-61).
 //
-// HBM-bound layer (C_in = 1: 33.5 MB in, 134 MB out at 128^3 x 4).  One thread owns ONE output voxel
-// and produces all 32 output channels from a single 27*C_in-value register patch, so the input is read
-// once; every per-channel store is a 256-B row segment per wave (lanes run along W, the fastest axis).
-// Weights are wave-uniform -> scalar loads feeding v_fma with an SGPR operand (no LDS, no VGPRs).
-// BN statistics: per-workgroup (sum, sumsq) per channel via an LDS transpose, emitted as fp64 partials.
+// HBM-bound layer (C_in = 1: 33.5 MB in, 134 MB out at 128^3 x 4), run as a GEMM on the matrix cores:
+// Y[32 x positions] = W[32 x 27 C_in] . im2col(x), exact fp32 MFMA.  The forward has two forms - operands straight from
+// global memory (stem_fwd_mfma_kernel, every shape) and rows staged in LDS (stem_fwd_rows_kernel, stride-2 rows of whole
+// 16-byte groups, C_in <= 2) - and the weight gradient has the matching pair (stem_bwd_weight_kernel, stem_bww_tile_kernel).
+// BN statistics: per-lane (sum, sumsq) per channel carried across a wave's chunks, emitted as fp64 partials.
 #include "common.hpp"
 #include <algorithm>
 #include <type_traits>
@@ -15,95 +15,9 @@ namespace {
 constexpr int STEM_COUT = 32;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int CIN>
-__global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__ x,
-                                                       const float* __restrict__ w, float* __restrict__ y,
-                                                       double* __restrict__ partials, int D, int H, int W,
-                                                       int OD, int OH, int OW, int sd, int sh, int sw) {
-  constexpr int K = CIN * 27;
-  __shared__ float red[8][256];
-  const int n = blockIdx.y;
-  const int OS = OD * OH * OW;
-  const int o = blockIdx.x * 256 + threadIdx.x;
-  const bool valid = o < OS;
-  const int oo = valid ? o : 0;
-  const int ow = oo % OW, oh = (oo / OW) % OH, od = oo / (OW * OH);
-
-  float in[K];
-  {
-    const int id0 = od * sd - 1, ih0 = oh * sh - 1, iw0 = ow * sw - 1;
-#pragma unroll
-    for (int ci = 0; ci < CIN; ++ci) {
-      const float* xc = x + ((size_t)n * CIN + ci) * D * H * W;
-#pragma unroll
-      for (int kd = 0; kd < 3; ++kd) {
-        const int id = id0 + kd;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const int ih = ih0 + kh;
-#pragma unroll
-          for (int kw = 0; kw < 3; ++kw) {
-            const int iw = iw0 + kw;
-            const bool ok = valid && id >= 0 && id < D && ih >= 0 && ih < H && iw >= 0 && iw < W;
-            in[ci * 27 + kd * 9 + kh * 3 + kw] = ok ? xc[((size_t)id * H + ih) * W + iw] : 0.f;
-          }
-        }
-      }
-    }
-  }
-
-  const int lane32 = threadIdx.x & 31, grp = threadIdx.x >> 5;  // 8 groups of 32 threads
-  double chs[4], chq[4];
-  float* yo = y + (size_t)n * STEM_COUT * OS + oo;
-#pragma unroll
-  for (int gp = 0; gp < 4; ++gp) {
-    float acc[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      float a = 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k) a = fmaf(w[(gp * 8 + c) * K + k], in[k], a);
-      acc[c] = valid ? a : 0.f;
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (valid) yo[(size_t)(gp * 8 + c) * OS] = acc[c];
-      red[c][threadIdx.x] = acc[c];
-    }
-    __syncthreads();
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float v = red[grp][i * 32 + lane32];
-      s += v;
-      q = fmaf(v, v, q);
-    }
-    double ds = (double)s, dq = (double)q;
-#pragma unroll
-    for (int m = 16; m > 0; m >>= 1) {
-      ds += __shfl_xor(ds, m, 64);
-      dq += __shfl_xor(dq, m, 64);
-    }
-    chs[gp] = ds;
-    chq[gp] = dq;
-    __syncthreads();
-  }
-  if (partials && lane32 == 0) {
-    const int NP = gridDim.x * gridDim.y;
-    const int p = n * gridDim.x + blockIdx.x;
-#pragma unroll
-    for (int gp = 0; gp < 4; ++gp) {
-      const int c = gp * 8 + grp;
-      partials[(size_t)c * NP + p] = chs[gp];
-      partials[((size_t)STEM_COUT + c) * NP + p] = chq[gp];
-    }
-  }
-}
-
-
 // ---------------------------------------------------------------------------------------------
-// Stem forward on the matrix cores.  The VALU form above spends 27*Cin FMAs per output and channel (864 per voxel at
-// Cin = 1): 23 us of pure VALU issue at 128^3 x 4 next to a 34 us HBM floor.  As a GEMM  Y[32 x pos] = W[32 x K] .
+// Stem forward on the matrix cores.  A VALU form (one thread per output voxel) spends 27*Cin FMAs per output and channel
+// (864 per voxel at Cin = 1): 23 us of pure VALU issue at 128^3 x 4 next to a 34 us HBM floor.  As a GEMM  Y[32 x pos] = W[32 x K] .
 // im2col[K x pos]  (K = 27*Cin, padded to even) on v_mfma_f32_32x32x2_f32 the same work is 12 us of MFMA time and the
 // kernel becomes a streaming one.  A wave owns 64 consecutive outputs of one row (two 32-column tiles):
 //   A operand  lane (h, c): W[c][2kk + h]                               - registers, loaded once per wave
@@ -856,7 +770,7 @@ constexpr int SBT_RP = 131;   // input-row pitch (1 + 128 used); 131 % 32 == 3
 // NW = waves per workgroup (4 or 8): wave w produces channels [CPW*w, CPW*(w+1)), CPW = 32 / NW, and multiplies positions
 // [PPW*w, PPW*(w+1)), PPW = 256 / NW, of the tile.
 template <int CIN, bool BF16ACT, int NW>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2))) void stem_bww_tile_kernel(const void* __restrict__ dzp, const void* __restrict__ yp,
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void stem_bww_tile_kernel(const void* __restrict__ dzp, const void* __restrict__ yp,
                                                             const float* __restrict__ x, float* __restrict__ slabs, int N,
                                                             int D, int H, int OD, int OH, int tiles_total, int iters,
                                                             const float* __restrict__ bnv, const float* __restrict__ w1p) {
@@ -1146,12 +1060,7 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_reduce_kernel(const float
   }
 }
 
-constexpr int STEM_BW_BLOCKS = 512;
-// workgroups of the stem weight gradient (= partial slabs): two per CU
-static inline int stem_bw_blocks() {
-  constexpr int v = STEM_BW_BLOCKS;
-  return v > 0 ? v : STEM_BW_BLOCKS;
-}
+constexpr int STEM_BW_BLOCKS = 512;  // workgroups of the stem weight gradient (= partial slabs): two per CU
 
 }  // namespace
 
@@ -1179,8 +1088,7 @@ static int stem_fwd_impl(const float* x, const float* w, void* y, double* partia
   const int iters = msl::cdiv(chunks_per_n, nb * 4);
   dim3 grid(nb, N);
   hipStream_t st = (hipStream_t)stream;
-  constexpr int rows_on = 1;
-  if (rows_on && sw == 2 && W % 4 == 0 && OW % 32 == 0 && Cin <= 2) {
+  if (sw == 2 && W % 4 == 0 && OW % 32 == 0 && Cin <= 2) {
     // row-staged form (contiguous 16-byte row loads, operands from LDS)
     const size_t lds = (size_t)4 * 2 * Cin * 9 * SFR_RP * sizeof(float);
 #define MSL_STEM_FR(CI, B_)                                                                                             \
@@ -1233,14 +1141,14 @@ int msl_stem_conv_fwd_bf16(const float* x, const float* w, void* y_bf16, double*
 
 size_t msl_stem_conv_bwd_weight_workspace_bytes(int Cin) {
   const int NT = (Cin * 27 + 31) / 32;
-  return (size_t)stem_bw_blocks() * 32 * 32 * NT * sizeof(float);
+  return (size_t)STEM_BW_BLOCKS * 32 * 32 * NT * sizeof(float);
 }
 
 // number of [32][32*NT] slabs the stem weight-gradient kernels leave in `workspace` (NT = ceil(Cin*27 / 32))
 int msl_stem_conv_bwd_weight_nslabs(int N, int D, int H, int W, int sd, int sh, int sw) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || sd < 1 || sh < 1 || sw < 1) return MSL_ERR_ARG;
   const int OD = (D - 1) / sd + 1, OH = (H - 1) / sh + 1, OW = (W - 1) / sw + 1;
-  return std::min(stem_bw_blocks(), msl::cdiv(N * OD * OH * msl::cdiv(OW, 64), 4));
+  return std::min(STEM_BW_BLOCKS, msl::cdiv(N * OD * OH * msl::cdiv(OW, 64), 4));
 }
 
 // dw (32,Cin,3,3,3) = correlation of dy (N,32,OD,OH,OW) with x (N,Cin,D,H,W).  For all three forms: dw == NULL leaves
@@ -1313,40 +1221,32 @@ static int stem_bww_impl(const float* dy, const float* x, float* dw, float* work
   const int OD = (D - 1) / sd + 1, OH = (H - 1) / sh + 1, OW = (W - 1) / sw + 1;
   const int chunks_per_row = msl::cdiv(OW, 64);
   const int total_chunks = N * OD * OH * chunks_per_row;
-  const int nblocks = std::min(stem_bw_blocks(), msl::cdiv(total_chunks, 4));
+  const int nblocks = std::min(STEM_BW_BLOCKS, msl::cdiv(total_chunks, 4));
   const int iters = msl::cdiv(total_chunks, nblocks * 4);
   hipStream_t st = (hipStream_t)stream;
   const int NT = (Cin * 27 + 31) / 32;
   const size_t lds = (size_t)4 * (32 * SB_DY_LD + Cin * 9 * SB_ROW_LD) * sizeof(float);
   const StemFusedSrc fs{(OD - 1) / 2 + 1, (OH - 1) / 2 + 1, (OW - 1) / 2 + 1};
-  constexpr int tile_on = 1;
-  if (tile_on && w1 && sd == 2 && sh == 2 && sw == 2 && W == 128 && H % 16 == 0 && Cin <= 2 &&
+  if (w1 && sd == 2 && sh == 2 && sw == 2 && W == 128 && H % 16 == 0 && Cin <= 2 &&
       (long long)N * Cin * D * H * W * 4 < (1ll << 32)) {
     // tile-staged form (stem_bww_tile_kernel): a workgroup per 4 output rows of one parity; same slab count as below
     const int tiles_total = N * OD * (OH / 4);
-    const int nb = std::min(stem_bw_blocks(), tiles_total);
+    const int nb = std::min(STEM_BW_BLOCKS, tiles_total);
     const int it = msl::cdiv(tiles_total, nb);
     const size_t tl = (size_t)(32 * SBT_LDA + 36 * Cin * SBT_RP) * sizeof(float);
-    constexpr int tile_nw = 4;
-#define MSL_STEM_BWT2(CI, B_, NW_)                                                                                   \
+#define MSL_STEM_BWT(CI, B_)                                                                                   \
   do {                                                                                                               \
     if (tl > 64 * 1024) {                                                                                            \
-      hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_bww_tile_kernel<CI, B_, NW_>),          \
+      hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_bww_tile_kernel<CI, B_, 4>),          \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl);                      \
       if (e_ != hipSuccess) return (int)e_;                                                                          \
     }                                                                                                                \
-    MSL_LAUNCH((stem_bww_tile_kernel<CI, B_, NW_>), dim3(nb), dim3(NW_ * 64), tl, st, (const void*)dy,       \
+    MSL_LAUNCH((stem_bww_tile_kernel<CI, B_, 4>), dim3(nb), dim3(256), tl, st, (const void*)dy,       \
                        (const void*)yraw, x, workspace, N, D, H, OD, OH, tiles_total, it, bnv, w1);                  \
-  } while (0)
-#define MSL_STEM_BWT(CI, B_)                          \
-  do {                                                \
-    if (tile_nw == 8) MSL_STEM_BWT2(CI, B_, 8);       \
-    else MSL_STEM_BWT2(CI, B_, 4);                    \
   } while (0)
     if (Cin == 1) { if (bf16act) MSL_STEM_BWT(1, true); else MSL_STEM_BWT(1, false); }
     else { if (bf16act) MSL_STEM_BWT(2, true); else MSL_STEM_BWT(2, false); }
 #undef MSL_STEM_BWT
-#undef MSL_STEM_BWT2
     MSL_LAUNCH_CHECK();
     if (!dw) return MSL_OK;
     MSL_LAUNCH(stem_bwd_weight_reduce_kernel, dim3(msl::cdiv(32 * 32 * NT, 32)), dim3(256), 0, st, workspace, dw,

@@ -1,9 +1,10 @@
 """Case tables of tests/test_gpu_bf16pw.py, shared with tests/test_bf16pw_ref_cpu.py: plain CPU data, nothing here imports
 the package.  Every case id names the kernel instantiation of csrc/bf16.hip (BatchNorm backward: csrc/bn.hip on bf16 storage) it is
 meant to reach, and carries the path that the
-dispatch arithmetic mirrored below (``tile_path`` = pw_tr_ok + pw_tr_launch, ``bww_path`` = bww_bf16_plan, ``fused_path`` =
-msl_bn_relu_bwd_fused_bf16, ``apply_grid`` / ``reduce_chunks``) must give for it: ``assert_path`` fails loudly when a changed
-heuristic would silently move a case to another kernel.  Every shape is the smallest that reaches its path.
+dispatch arithmetic mirrored below (``tile_path`` and ``bww_path`` = the bf16 branches of pw_route in csrc/pwroute.hpp,
+``fused_path`` = msl_bn_relu_bwd_fused_bf16, ``apply_grid`` / ``reduce_chunks``) must give for it: ``assert_path`` fails loudly
+when a changed heuristic would silently move a case to another kernel, and tests/test_bf16pw_ref_cpu.py holds the mirror against
+the library's own answer (msl_pwconv_route_kind).  Every shape is the smallest that reaches its path.
 
 forward and backward data share the tile kernels with (M, K) = (Cout, Cin) and (Cin, Cout).  J (fp32 additions that combine
 K-split partial tiles) is 0 in every case: both tile kernels run the MFMA chain over K serially inside a wave (bf16.hip,
@@ -26,8 +27,13 @@ def bf(t):
 
 
 # ------------------------------------------------------------------------------------------------- dispatch mirrors
+# op of msl_pwconv_route_kind per table, and the PwKind (csrc/pwroute.hpp) behind the first field of a mirrored path
+ROUTE_OP = dict(fwd=0, bwd_data=1, bww=2)
+ROUTE_KIND = dict(tr=7, plain=8, mfma=9, any=10)
+
+
 def tile_path(N, M, K, S):
-    """pw_tr_ok / pw_tr_launch: ("tr", BK, T) or ("plain", vec_ok)."""
+    """pw_route, bf16 forward / bwd-data: ("tr", BK, T) or ("plain", vec_ok)."""
     if S % 8 == 0 and K % 32 == 0 and K <= 1024 and M % 8 == 0:
         tiles_img, mtiles = cdiv(S, 64), cdiv(M, 64)
         T = max(1, min(min(4, tiles_img), (tiles_img * mtiles * N) // 512))
@@ -36,7 +42,7 @@ def tile_path(N, M, K, S):
 
 
 def bww_path(N, Cin, Cout, S):
-    """bww_bf16_plan: ("mfma", MT, nslabs, chunks per slab, total chunks) or ("any", 1, fp32 chain length)."""
+    """pw_route, bf16 weight gradient: ("mfma", MT, nslabs, chunks per slab, total chunks) or ("any", 1, fp32 chain length)."""
     if S % 64 or Cin % 32 or Cout % 32:
         return ("any", 1, N * cdiv(S, 64) * 64)  # one accumulator per thread: N * ceil(S / 64) * 64 fmaf, zeros past S
     mt = 2 if Cout % 64 == 0 else 1

@@ -12,7 +12,7 @@ Operands are reproduced, not bounded (bf16.hip line numbers of the parent of thi
 GEMM bound.  y64 = Wb . A in float64, absdot = |Wb| . |A|; the products of two bf16 values are exact in fp32, the fp32
 accumulator meets at most one rounding per term: B = (K + J) U absdot (pw_ref.gemm_bound), J = 0 in both tile kernels (the MFMA
 chain over K is serial in a wave: ``acc = mfma(a, b, acc)`` :214 / :361, one accumulator, no K split).  Weight gradient:
-(L + ns) U absdot with L = chunks per slab * 64 (bww_bf16_plan :947-956; the four waves of a workgroup interleave the slab's
+(L + ns) U absdot with L = chunks per slab * 64 (bww_route of csrc/pwroute.hpp; the four waves of a workgroup interleave the slab's
 chunks and meet in three additions :517-520, L / 4 + 3 <= L) and ns = msl_pwconv_bwd_weight_bf16_nslabs; the any-kernel is one
 fmaf chain over N * ceil(S / 64) * 64 positions (:536-554), one slab.
 

@@ -1,8 +1,25 @@
 """Case tables of tests/test_gpu_pw.py (shared with tests/test_pw_ref_cpu.py, which proves every bound at every shape with
-honest fp32 on the CPU).  Plain data: (id, N, Cin, Cout, S, J).  The id names the kernel path the shape is meant to reach
-(read off strip_cols / wave_form / wave_nt / use_ksplit / bww_wave_plan / bw_plan / fused_wgs; DESIGN.md, Appendix A, lists
-every kernel instantiation with its case - the path is documented there, not asserted).  J = fp32 additions that
+honest fp32 on the CPU).  Plain data: (id, N, Cin, Cout, S, J).  The id names the kernel path the shape is meant to reach - the
+PwKind of csrc/pwroute.hpp that ``expected_kind`` reads off it and tests/test_pw_ref_cpu.py asserts against the library's own
+answer (msl_pwconv_route_kind); DESIGN.md, Appendix A, lists every kernel instantiation with its case.  J = fp32 additions that
 combine K-split partial tiles: 0 serial K, NWK for the split wave form, the wave count for the K-split GEMM."""
+
+# PwKind of csrc/pwroute.hpp, as msl_pwconv_route_kind returns it, and its ops
+KIND = dict(none=0, strip=1, wave=2, ksplit=3, gemm=4, bww_wave=5, bww_tile=6, bf16_tr=7, bf16_plain=8, bf16_bww_mfma=9,
+            bf16_bww_any=10, fused=11)
+OP_FWD, OP_BWD_DATA, OP_BWD_WEIGHT, OP_BWD_FUSED = 0, 1, 2, 3
+
+
+def expected_kind(id_):
+    """The PwKind a case id spells: ``<path>[:<detail>]``, or ``<family>-declined-<why>:<path>`` where a family declines the shape."""
+    head, _, tail = id_.partition(":")
+    name = tail if "declined" in head else head
+    for prefix, kind in (("bww-wave", "bww_wave"), ("bww-fallback", "bww_tile"), ("strip", "strip"), ("wave", "wave"),
+                         ("split", "wave"), ("ksplit", "ksplit"), ("gemm", "gemm")):
+        if name.startswith(prefix):
+            return KIND[kind]
+    raise KeyError(id_)
+
 
 WAVE_S = (1, 31, 32, 33, 127, 128, 129, 130)  # lane, tile and workgroup tails; S - 1 clamp of the columns past S
 

@@ -83,6 +83,14 @@ def test_pure_host_entry_points():
     assert lib.msl_dwconv_route_kind(3, 0, 2, 512, 2, 2, 2, 1) == 12      # 64^3 config tail: wave-per-chunk
     assert lib.msl_dwconv_route_kind(2, 1, 2, 8, 9, 24, 24, 1) == 7       # bf16 storage, no wave plane: LDS-tiled
     assert lib.msl_dwconv_route_kind(5, 0, 4, 32, 64, 64, 64, 2) == -1 and lib.msl_dwconv_route_kind(2, 0, 0, 32, 64, 64, 64, 2) == -1
+    # the pointwise route query (op 0 forward, 1 bwd-data, 2 bwd-weight, 3 fused backward; the PwKind of csrc/pwroute.hpp)
+    assert lib.msl_pwconv_route_kind(0, 0, 4, 32, 64, 32768, 1) == 1      # block 1 forward: the strip kernel
+    assert lib.msl_pwconv_route_kind(3, 0, 4, 32, 64, 32768, 0) == 11     # block 1 backward: one fused pass
+    assert lib.msl_pwconv_route_kind(1, 0, 4, 128, 256, 512, 0) == 2      # block 4 bwd-data: the wave kernel, K split over 4 waves
+    assert lib.msl_pwconv_route_kind(2, 0, 4, 64, 128, 4096, 0) == 5      # block 2 weight gradient: wave-autonomous
+    assert lib.msl_pwconv_route_kind(0, 1, 4, 32, 64, 32768, 1) == 7      # bf16 storage, block 1 forward: transposed-read GEMM
+    assert lib.msl_pwconv_route_kind(2, 1, 4, 512, 512, 64, 0) == 9       # bf16 storage, block 7 weight gradient: MFMA
+    assert lib.msl_pwconv_route_kind(4, 0, 4, 32, 64, 32768, 0) == -1 and lib.msl_pwconv_route_kind(0, 0, 4, 32, 64, 0, 1) == -1
 
 
 def test_native_program_runner_covers_the_abi():

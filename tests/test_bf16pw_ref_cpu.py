@@ -77,6 +77,10 @@ ALL_PATHS = ([("fwd", c) for c in C.FWD_CASES] + [("bwd_data", c) for c in C.BWD
 def test_case_reaches_the_path_it_names(kind, case):
     C.assert_path(kind, case)
     L = _lib.load()
+    if kind in ("fwd", "bwd_data", "bww"):  # the library's own route agrees with the mirror
+        _, N, Cin, Cout, S, want = case
+        got = L.msl_pwconv_route_kind(C.ROUTE_OP[kind], 1, N, Cin, Cout, S, 1 if kind == "fwd" else 0)
+        assert got == C.ROUTE_KIND[want[0]], f"{case[0]}: route kind {got}, the mirror gives {want[0]}"
     if kind == "fwd":
         _, N, Cin, Cout, S, _ = case
         assert L.msl_pwconv_fwd_bf16_num_partials(N, S) == N * C.cdiv(S, 64) * 2

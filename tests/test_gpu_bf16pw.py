@@ -514,3 +514,19 @@ def test_bn_relu_bwd_fused_bf16(case):
     rep = B.Report(id_)
     B.check_fused(rep, B.fused_expect(d["g"], d["y"], d["vec"], n_t), dy.v.float().cpu().view(N, Cc, S), dg.v.cpu(), db.v.cpu())
     finish(rep)
+
+
+# ------------------------------------------------------------------------------------------------- recorded bits
+def test_pw_bf16_bits_are_the_recorded_ones():
+    """Every output buffer of the GEMM, fold, bwd-data and weight-gradient tables has the SHA-256 that tests/golden/pw_bits.json
+    recorded before the host code got its single route (make_pw_bits's docstring)."""
+    import json
+    from tests.golden import make_pw_bits as M
+    with open(M.OUT) as f:
+        want = json.load(f)["bf16"]
+    got = M.digests_bf16("cuda")
+    assert sorted(got) == sorted(want), "the cases are not the recorded ones"
+    assert {k.split()[0] for k in want} == {"msl_pwconv_fwd_bf16", "msl_pwconv_fwd_bf16_fold", "msl_pwconv_bwd_data_bf16",
+                                            "msl_pwconv_bwd_weight_slabs_bf16"}
+    bad = [k for k in want if got[k] != want[k]]
+    assert not bad, f"{len(bad)}/{len(want)} buffers differ from the recorded bits: {bad[:8]}"

@@ -213,12 +213,16 @@ def fold_partials(Cin, in_np, count, g, special=False):
     return torch.stack([s[:, None] * wgt, q[:, None] * wgt]).contiguous()
 
 
-def run_fold_case(path, N, Cin, Cout, S, in_np, count, special=False, order=False):
+def fold_inputs(N, Cin, Cout, S, in_np, count, special=False):
     g = gen(7000 + in_np + S)
     z = torch.randn((N, Cin, S), generator=g)
     w = torch.randn((Cout, Cin), generator=g) / Cin ** 0.5
     gamma, beta = torch.randn(Cin, generator=g).abs() + 0.5, torch.randn(Cin, generator=g) * 0.3
-    parts = fold_partials(Cin, in_np, count, g, special)
+    return z, w, gamma, beta, fold_partials(Cin, in_np, count, g, special)
+
+
+def run_fold_case(path, N, Cin, Cout, S, in_np, count, special=False, order=False):
+    z, w, gamma, beta, parts = fold_inputs(N, Cin, Cout, S, in_np, count, special)
     if order:  # +-B in slots 0 and 32, B far above the other slots' reach in float64: every summation order has its own sum
         parts[0, :, 0] += 1e22
         parts[0, :, 32] -= 1e22
@@ -296,12 +300,16 @@ def test_pw_fwd_fold_refusals():
 
 
 # ------------------------------------------------------------------------------------------------- msl_pwconv_bwd_data
+def bwd_data_inputs(N, Cin, Cout, S):
+    g_ = gen(300 + 31 * N + 7 * Cin + 3 * Cout + S)
+    dy = torch.randn((N, Cout, S), generator=g_)
+    return dy, torch.randn((Cout, Cin), generator=g_) / Cin ** 0.5
+
+
 @pytest.mark.parametrize("case", C.BWD_DATA_CASES, ids=[c[0] for c in C.BWD_DATA_CASES])
 def test_pw_bwd_data(case):
     path, N, Cin, Cout, S, J = case
-    g_ = gen(300 + 31 * N + 7 * Cin + 3 * Cout + S)
-    dy = torch.randn((N, Cout, S), generator=g_)
-    w = torch.randn((Cout, Cin), generator=g_) / Cin ** 0.5
+    dy, w = bwd_data_inputs(N, Cin, Cout, S)
     ref, absdot = P.bwd_data_ref(dy, w)
     out = Guarded(N * Cin * S)
     _lib.call("msl_pwconv_bwd_data", ptr(dev(dy)), ptr(dev(w)), ptr(out.v), N, Cin, Cout, S, st())
@@ -411,6 +419,27 @@ def test_pw_bwd_weight_batch_is_the_single_launches(shapes):
 
 
 # ------------------------------------------------------------------------------------------------- msl_pwconv_bwd_fused
+def fused_inputs():
+    """Host operands of FUSED_CASE -> (gy, y, z, w, vy, vz, y partials (2, Cout, ynp) fp64, ynp, count)."""
+    N, Cin, Cout, S = C.FUSED_CASE
+    g_ = gen(900)
+    gy = torch.randn((N, Cout, S), generator=g_)
+    y = torch.randn((N, Cout, S), generator=g_) * 1.5 + 0.3
+    z = torch.randn((N, Cin, S), generator=g_) * 2.0 + 0.5
+    w = torch.randn((Cout, Cin), generator=g_) * 0.2
+    gam_y, bet_y = torch.rand(Cout, generator=g_) + 0.5, torch.randn(Cout, generator=g_) * 0.3
+    gam_z, bet_z = torch.rand(Cin, generator=g_) + 0.5, torch.randn(Cin, generator=g_) * 0.3
+    y, _ = R.separate_preactivation(y, gam_y, bet_y, EPS)
+    z, _ = R.separate_preactivation(z, gam_z, bet_z, EPS)
+    vy, vz = R.host_vectors(y, gam_y, bet_y, EPS), R.host_vectors(z, gam_z, bet_z, EPS)
+    dbeta, dgamma = R.bwd_sums_ref(gy, y, vy)
+    ynp = 5
+    wgt = torch.rand(ynp, generator=g_, dtype=torch.float64) + 0.1
+    wgt /= wgt.sum()
+    parts = torch.stack([dbeta[:, None] * wgt, dgamma[:, None] * wgt]).contiguous()
+    return gy, y, z, w, vy, vz, parts, ynp, float(N * S)
+
+
 def test_pw_bwd_fused_uneven_strips():
     """513 strips over 256 workgroups (workgroup 0 walks three, the others two; strips cross images), against the float64
     evaluation of the launches it replaces: BatchNorm2 backward applied on load (bn_ref.coef_ref), g_z = W^T dL/dy, the
@@ -423,22 +452,7 @@ def test_pw_bwd_fused_uneven_strips():
     N, Cin, Cout, S = C.FUSED_CASE
     NPW = L.msl_pwconv_bwd_fused_num_partials(N, Cin, Cout, S)
     assert NPW == 256
-    g_ = gen(900)
-    gy = torch.randn((N, Cout, S), generator=g_)
-    y = torch.randn((N, Cout, S), generator=g_) * 1.5 + 0.3
-    z = torch.randn((N, Cin, S), generator=g_) * 2.0 + 0.5
-    w = torch.randn((Cout, Cin), generator=g_) * 0.2
-    gam_y, bet_y = torch.rand(Cout, generator=g_) + 0.5, torch.randn(Cout, generator=g_) * 0.3
-    gam_z, bet_z = torch.rand(Cin, generator=g_) + 0.5, torch.randn(Cin, generator=g_) * 0.3
-    y, _ = R.separate_preactivation(y, gam_y, bet_y, EPS)
-    z, _ = R.separate_preactivation(z, gam_z, bet_z, EPS)
-    vy, vz = R.host_vectors(y, gam_y, bet_y, EPS), R.host_vectors(z, gam_z, bet_z, EPS)
-    count = float(N * S)
-    dbeta, dgamma = R.bwd_sums_ref(gy, y, vy)
-    ynp = 5
-    wgt = torch.rand(ynp, generator=g_, dtype=torch.float64) + 0.1
-    wgt /= wgt.sum()
-    parts = torch.stack([dbeta[:, None] * wgt, dgamma[:, None] * wgt]).contiguous()
+    gy, y, z, w, vy, vz, parts, ynp, count = fused_inputs()
     gz, zpart, slabs = Guarded(N * Cin * S), Guarded(2 * Cin * NPW, dtype=torch.float64), Guarded(NPW * Cout * Cin)
     dgam, dbet = Guarded(Cout), Guarded(Cout)
     gyd, yd_, vyd, pd, wd, zd_, vzd = dev(gy), dev(y), dev(vy), dev(parts), dev(w), dev(z), dev(vz)
@@ -642,3 +656,20 @@ def test_pw_fwd_one_nan_poisons_its_column_only(case):
     wantp[:, :, slot] = True
     assert torch.equal(pnan, wantp), f"{int(pnan.sum())} NaN statistics, expected the {2 * Cout} of partial {slot}"
     assert same_bits(p1.v.view(2, Cout, NP)[~wantp], p0.v.view(2, Cout, NP)[~wantp])
+
+
+# ------------------------------------------------------------------------------------------------- recorded bits
+def test_pw_bits_are_the_recorded_ones():
+    """Every output buffer of every case of tests/pw_cases.py has the SHA-256 that tests/golden/pw_bits.json recorded before the
+    host code got its single route (make_pw_bits's docstring): a mismatch means a launch changed its kernel, its grid or its
+    bits, never that the file wants minting again."""
+    import json
+    from tests.golden import make_pw_bits as M
+    with open(M.OUT) as f:
+        want = json.load(f)["fp32"]
+    got = M.digests_fp32(DEV)
+    assert sorted(got) == sorted(want), "the cases are not the recorded ones"
+    assert {k.split()[0] for k in want} == {"msl_pwconv_fwd", "msl_pwconv_fwd_fold", "msl_pwconv_bwd_data", "msl_pwconv_bwd_weight",
+                                            "msl_pwconv_bwd_weight_slabs_batch", "msl_pwconv_bwd_fused"}
+    bad = [k for k in want if got[k] != want[k]]
+    assert not bad, f"{len(bad)}/{len(want)} buffers differ from the recorded bits: {bad[:8]}"

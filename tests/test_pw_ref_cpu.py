@@ -152,3 +152,36 @@ def test_fp32_weight_gradient_inside_bound(case):
         acc = acc + torch.matmul(df[:, k:k + L], af[:, k:k + L].t())
     r, bad = _ratio(acc, dw, P.bww_bound(absdot, N, S, ns))
     assert bad == 0 and 0 < r <= 1, r
+
+
+# ------------------------------------------------------------------------------------------------- paths
+ROUTE_CASES = ([(C.OP_FWD, c) for c in C.FWD_CASES] + [(C.OP_FWD, c) for c in C.FOLD_CASES]
+               + [(C.OP_BWD_DATA, c) for c in C.BWD_DATA_CASES] + [(C.OP_BWD_WEIGHT, c) for c in C.BWW_CASES])
+
+
+@pytest.mark.parametrize("op,case", ROUTE_CASES, ids=[f"op{op}:{c[0]}" for op, c in ROUTE_CASES])
+def test_case_reaches_the_kernel_its_id_names(op, case):
+    """The library's own route (host arithmetic) for every case of the four tables; the forward's kind holds with and without
+    statistics, and the NT2 / NT1 ids name the column tiles per wave that the partial count shows."""
+    id_, N, Cin, Cout, S = case[:5]
+    L = _lib.load()
+    want = C.expected_kind(id_)
+    for stats in ((0, 1) if op == C.OP_FWD else (0,)):
+        got = L.msl_pwconv_route_kind(op, 0, N, Cin, Cout, S, stats)
+        assert got == want, f"{id_}: route kind {got}, the id names {want}"
+    if "NT2" in id_ or "NT1" in id_:
+        assert L.msl_pwconv_fwd_num_partials(N, Cin, Cout, S) == N * -(-S // (256 if "NT2" in id_ else 128))
+
+
+def test_fused_case_and_route_query_refusals():
+    L = _lib.load()
+    N, Cin, Cout, S = C.FUSED_CASE
+    assert L.msl_pwconv_route_kind(C.OP_BWD_FUSED, 0, N, Cin, Cout, S, 0) == C.KIND["fused"]
+    assert L.msl_pwconv_route_kind(C.OP_BWD_FUSED, 1, N, Cin, Cout, S, 0) == C.KIND["none"]       # fp32 only
+    assert L.msl_pwconv_route_kind(C.OP_BWD_FUSED, 0, 1, Cin, Cout, 65408, 0) == C.KIND["none"]   # 511 strips
+    ok = (2, 32, 64, 4096, 0)
+    assert L.msl_pwconv_route_kind(0, 0, *ok) == C.KIND["wave"]
+    for args in ((-1, 0) + ok, (4, 0) + ok, (0, 2) + ok, (0, -1) + ok, (0, 0, 0, 32, 64, 4096, 0), (0, 0, 2, 0, 64, 4096, 0),
+                 (0, 0, 2, 32, -64, 4096, 0), (0, 0, 2, 32, 64, 0, 0)):
+        assert L.msl_pwconv_route_kind(*args) == -1, args
+

@@ -424,6 +424,27 @@ __global__ __launch_bounds__(256) void head_bwd_weight_kernel(const float* __res
   }
 }
 
+// Fold of one output element over the partial slabs, in the order msl_grad_reduce_batch (optim.hip) folds the same slabs when
+// the reduction is deferred, so that the direct and the deferred form give the same bits (for 16-byte aligned buffers):
+// `few` (at most 16 slabs of a count that is a multiple of 4) in slab order; otherwise eight chains k = g, g + 8, ..., folded
+// g = 0 .. 7.
+__device__ __forceinline__ float head_fold_slabs(const float* __restrict__ p, size_t kstride, int nslabs, bool few) {
+  if (few) {
+    float s = 0.f;
+    for (int k = 0; k < nslabs; ++k) s += p[(size_t)k * kstride];
+    return s;
+  }
+  float t = 0.f;
+#pragma unroll 1
+  for (int g = 0; g < 8; ++g) {
+    float s = 0.f;
+    for (int k = g; k < nslabs; k += 8) s += p[(size_t)k * kstride];
+    t += s;
+  }
+  return t;
+}
+constexpr int HEAD_FOLD_FEW = 16;  // GR_FEW of optim.hip
+
 // dW[co][ci][tap] = sum over slabs (fixed order); also splits into the loc / cls weight gradients
 __global__ __launch_bounds__(256) void head_bwd_weight_reduce_kernel(const float* __restrict__ slabs,
                                                                      float* __restrict__ dloc_w,
@@ -435,18 +456,9 @@ __global__ __launch_bounds__(256) void head_bwd_weight_reduce_kernel(const float
   const int tap = i % 27, ci = (i / 27) % C, co = i / (27 * C);
   const int ct = ci / 16, cil = ci % 16, mt = co / 16, col = co % 16;
   const int CT = C / 16;
-  float s = 0.f;
   const float* p = slabs + (size_t)ct * (27 * MT * 256) + (size_t)(tap * MT + mt) * 256 + col * 16 + cil;
   const size_t kstride = (size_t)CT * (27 * MT * 256);
-  int k = 0;
-  for (; k + 8 <= nslabs; k += 8) {  // 8 independent loads in flight; additions in slab order
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(k + u) * kstride];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; k < nslabs; ++k) s += p[(size_t)k * kstride];
+  const float s = head_fold_slabs(p, kstride, nslabs, nslabs <= HEAD_FOLD_FEW);
   if (co < 12) dloc_w[((size_t)co * C + ci) * 27 + tap] = s;
   else dcl_w[((size_t)(co - 12) * C + ci) * 27 + tap] = s;
 }
@@ -457,8 +469,9 @@ __global__ __launch_bounds__(64) void head_bias_reduce_kernel(const float* __res
                                                               int CO, int nslabs, int co_total) {
   const int co = threadIdx.x;
   if (co >= co_total) return;
-  float s = 0.f;
-  for (int k = 0; k < nslabs; ++k) s += bias_slabs[(size_t)k * CO + co];
+  // the deferred form folds rows 0-11 and rows 12.. as two entries of 12 and co_total - 12 elements
+  const bool few = nslabs <= HEAD_FOLD_FEW && (co < 12 || (co_total - 12) % 4 == 0);
+  const float s = head_fold_slabs(bias_slabs + co, (size_t)CO, nslabs, few);
   if (co < 12) dloc_b[co] = s;
   else dcl_b[co - 12] = s;
 }
@@ -1018,6 +1031,10 @@ __global__ __launch_bounds__(256) void head_fwd_bf16_kernel(const hu16* __restri
 }
 
 inline int head_mt(int ncls) { return (12 + 2 * ncls + 15) / 16; }
+// what every fp32 head entry accepts: both output-row tiles the kernels are instantiated for, whole 16-channel tiles
+inline bool head_args_ok(int N, int C, int D, int H, int W, int ncls) {
+  return N > 0 && C > 0 && C % 16 == 0 && D > 0 && H > 0 && W > 0 && ncls >= 1 && head_mt(ncls) <= 2;
+}
 
 inline int head_ksg(int N, int C, int S) {
   int blocks = msl::cdiv(S, 32) * N;
@@ -1173,6 +1190,7 @@ int msl_head_conv_fwd(const float* a_pad, const float* Wf, const float* loc_b, c
 // (dlocs, dscores) rows of this scale -> dO_pad (N, 16*MT, D+2, H+2, W+2); halo must already be zero
 int msl_head_grad_pack(const float* dlocs, const float* dscores, float* dO_pad, int N, int D, int H, int W,
                        int Ptot, int prior_off, int ncls, void* stream) {
+  if (!head_args_ok(N, 16, D, H, W, ncls)) return MSL_ERR_ARG;
   const int MT = head_mt(ncls), CO = 16 * MT;
   const int total = N * CO * D * H * W;
   MSL_LAUNCH(head_grad_pack_kernel, dim3(std::min(msl::cdiv(total, 256), 2048)), dim3(256), 0,
@@ -1185,7 +1203,7 @@ int msl_head_grad_pack(const float* dlocs, const float* dscores, float* dO_pad, 
 // msl_head_grad_pack for all (n <= 4) scales in one launch; dO_pad / D / H / W / prior_off: host arrays of n entries
 int msl_head_grad_pack_batch(const float* dlocs, const float* dscores, float* const* dO_pad, const int* D, const int* H,
                              const int* W, const int* prior_off, int n, int N, int Ptot, int ncls, void* stream) {
-  if (n < 1 || n > 4 || N <= 0 || head_mt(ncls) > 2) return MSL_ERR_ARG;
+  if (n < 1 || n > 4 || N <= 0 || ncls < 1 || head_mt(ncls) > 2) return MSL_ERR_ARG;
   const int MT = head_mt(ncls), CO = 16 * MT;
   HeadGradPackBatch b;
   int smax = 0;
@@ -1203,7 +1221,7 @@ int msl_head_grad_pack_batch(const float* dlocs, const float* dscores, float* co
 
 static int head_bwd_data_impl(const float* dO_pad, const float* Wb, void* g_a, int N, int C, int D, int H, int W, int ncls,
                               bool bf16_out, void* stream) {
-  if (C % 16 != 0) return MSL_ERR_ARG;
+  if (!head_args_ok(N, C, D, H, W, ncls)) return MSL_ERR_ARG;
   const int S = D * H * W, MT = head_mt(ncls);
   hipStream_t st = (hipStream_t)stream;
   const int lw = head_lds_w(C, D, H, W, MT);
@@ -1280,7 +1298,7 @@ int msl_head_conv_bwd_weight_bf16(const float* dO_pad, const void* a_cl, float* 
 
 static int head_bww_impl(const float* dO_pad, const void* a_pad, bool bf16_cl, float* dloc_w, float* dcl_w, float* dloc_b,
                          float* dcl_b, float* workspace, int N, int C, int D, int H, int W, int ncls, void* stream) {
-  if (C % 16 != 0) return MSL_ERR_ARG;
+  if (!head_args_ok(N, C, D, H, W, ncls)) return MSL_ERR_ARG;
   const int MT = head_mt(ncls), co_total = 12 + 2 * ncls;
   HwPlan p = head_bw_plan(N, C, D, H, W, MT);
   hipStream_t st = (hipStream_t)stream;

@@ -675,6 +675,29 @@ size_t msl_augment_mr_workspace_bytes(int N, int C, int D, int H, int W);
 int msl_augment_mr(const float* src, const double* params, const float* taps, const float* lattice, int N, int C, int D,
                    int H, int W, int L, float* dst, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- lesionpaste (csrc/lesionpaste.hip, devicedata.LesionCache) ----
+ * msl_paste_lesions: copy-paste of cached lesions on to a built batch, in place, bit-identical to datasets.paste_lesions.
+ * arena_img, arena_seg, seg_elems, C, table, n_cases: the arenas of msl_augment_fit_mc (1 <= C <= 4).  img (N,C,T0,T1,T2)
+ * f32 and seg (N,T0,T1,T2) i16 are the built batch; report (N,K) i32.  rows (device): N x K rows of 13 + 3 n_cand ints,
+ *   [0] active (0: the row is skipped), [1] donor case, [2..4] min_0..2 and [5..7] e_0..2: the donor box, e voxels from
+ *   min on, in the donor case, [8] flips (bit a: axis a of the box is mirrored), [9] the mask value written (1 .. 32767),
+ *   [10..12] the destination of the donor box's centre voxel relative to the destination corner (in [0, e)), then per
+ *   candidate j the destination corner lo_0..2 at [13 + 3 j].
+ * One workgroup per sample applies its K rows in order, each on the mask the earlier ones left.  The first candidate is
+ * taken whose (a) box [lo - 1, lo + e] clamped to the sample holds no non-zero voxel of seg and (b) image voxel at
+ * lo + [10..12] is != 0 in every channel.  With p in [-1, e] per axis, destination voxel lo + p has the donor coordinate
+ * d_a = min_a + (flip_a ? e_a - 1 - p_a : p_a).  Written voxels - p inside the box, donor mask at d non-zero: img = the donor's
+ * value in every channel, seg = [9].  Rim voxels - inside the sample, not written, a 6-neighbour of a written voxel, d inside
+ * the donor case: img = 0.5f * img + 0.5f * donor (two rounded products, one rounded sum; no contraction), seg unchanged.
+ * report: the accepted candidate's index, -1 when none passed, -2 for a refused row, which writes nothing: [0] = 0, a case
+ * outside [0, n_cases) or a table entry outside the arena, a donor box not inside the case's table shape, an extent > 32 or
+ * < 1, [9] outside 1 .. 32767, [10..12] outside the box, or any candidate that would put the box outside the sample.  One
+ * launch on `stream`, no synchronisation, no atomics.  -1 (nothing launched): a null pointer, a size < 1.  -2 (nothing
+ * launched): C > 4, K > 8 or n_cand > 16. */
+int msl_paste_lesions(const float* arena_img, const short* arena_seg, long long seg_elems, int C, const long long* table,
+                      int n_cases, const int* rows, int N, int K, int n_cand, int T0, int T1, int T2, float* img,
+                      short* seg, int* report, void* stream);
+
 /* ---- prediction overlays (csrc/overlay.hip, devicedata.LesionPredictFeed, predict.py -si 1) ----
  * Packed detections of N images: boxes (K,6) f32 corner boxes, labels (K) i64, scores (K) f32 on the device; offsets
  * (HOST, N + 1 ints, read during the call): image n owns rows offsets[n] .. offsets[n+1].  Both launch on `stream` and

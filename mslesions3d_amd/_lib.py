@@ -156,6 +156,7 @@ _SIGNATURES = {
     "msl_regrid": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "msl_augment_mr_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "msl_augment_mr": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "msl_paste_lesions": (_I, [_P, _P, _Q, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msl_boxes_to_case": (_I, [_P, _P, _P, _I, _P, _P]),
     "msl_draw_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P]),
     "msl_view_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),

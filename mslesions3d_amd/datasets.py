@@ -621,14 +621,232 @@ def _aug_gaussiannoise(img, seg, rs, **kw):
     return apply_mr("gaussiannoise", img, _draw_gaussiannoise(rs, **kw), kw), seg
 
 
+# ---- lesionpaste: copy-paste of cached lesions on to the finished sample -----------------------
+# The draws are a fixed number of uniforms; ``lower_pastes`` turns them into integer rows before anything touches a voxel,
+# and ``paste_lesions`` applies the rows: integer arithmetic throughout, apart from the rim blend (two rounded f32 products
+# and one rounded sum), so that msl_paste_lesions (csrc/lesionpaste.hip) computes the same bits.
+PASTE_NAME = "lesionpaste"
+PASTE_MAX_EXTENT = 32      # voxels per axis of a donor lesion's box
+PASTE_MAX_LESIONS = 8      # pastes per sample one msl_paste_lesions launch walks
+PASTE_MAX_CANDIDATES = 16  # destination candidates per paste
+PASTE_HEAD = 13            # ints of a paste row in front of its candidates
+PASTE_MAX_VALUE = 32767    # the mask is int16 on the device: msl_instance_boxes labels ids 1 .. 32767
+
+# rows (R, 8) int64: [case, label, min0..2, max0..2] (inclusive extents in the cropped case; ``case`` counts the training
+# cases in ``train_dataset.subjects`` order); max_ids (n_cases, n_classes) int64: per case and class the largest id
+# present, lo - 1 where the class holds none (instances mode; unused in binary mode); shapes: the cropped shapes
+LesionBank = collections.namedtuple("LesionBank", "rows max_ids shapes")
+
+
+def check_lesionpaste(prob=0.5, max_lesions=4, candidates=8, max_volume=None):
+    """The keyword limits of ``lesionpaste``: ValueError."""
+    if not 1 <= int(max_lesions) <= PASTE_MAX_LESIONS or int(max_lesions) != max_lesions:
+        raise ValueError(f"lesionpaste: max_lesions of 1 .. {PASTE_MAX_LESIONS}, got {max_lesions}")
+    if not 1 <= int(candidates) <= PASTE_MAX_CANDIDATES or int(candidates) != candidates:
+        raise ValueError(f"lesionpaste: candidates of 1 .. {PASTE_MAX_CANDIDATES}, got {candidates}")
+    if max_volume is not None and not max_volume > 0:
+        raise ValueError(f"lesionpaste: max_volume is a number of voxels > 0 or None, got {max_volume}")
+
+
+def paste_draw_count(max_lesions=4, candidates=8):
+    return 2 + int(max_lesions) * (4 + 3 * int(candidates))
+
+
+def _draw_lesionpaste(rs, prob=0.5, max_lesions=4, candidates=8, max_volume=None):
+    """The random draws of ``lesionpaste``: always ``paste_draw_count`` uniforms in ONE ``rs.random_sample`` call,
+    whatever they say and whatever the bank holds - [0] apply (u < prob), [1] the count K = 1 + floor(u max_lesions),
+    then per paste k < max_lesions: the donor, three flip bits (u >= 0.5 mirrors the axis) and ``candidates`` triples.
+    -> None (not applied) or K tuples (donor u, (f0, f1, f2), (candidates, 3) f64)."""
+    check_lesionpaste(prob, max_lesions, candidates, max_volume)
+    u = rs.random_sample(paste_draw_count(max_lesions, candidates))
+    if u[0] >= prob:
+        return None
+    K = min(1 + int(np.floor(u[1] * max_lesions)), int(max_lesions))
+    per = u[2:].reshape(int(max_lesions), 4 + 3 * int(candidates))
+    return [(float(r[0]), tuple(int(v >= 0.5) for v in r[1:4]), r[4:].reshape(int(candidates), 3).copy()) for r in per[:K]]
+
+
+def _aug_lesionpaste(img, seg, rs, **kw):
+    raise NotImplementedError("lesionpaste pastes lesions of a LesionsDataModule's bank on to the finished sample: it runs "
+                              "inside _LesionCases._sample / LesionCache, not as a transform of its own (-dm lesions)")
+
+
+def class_max_ids(seg, thresholds, mode):
+    """Per class the largest id of a mask inside the class's threshold pair [lo, hi), lo - 1 where it holds none; zeros
+    in binary mode (unused there).  -> list of ints."""
+    if mode == "binary":
+        return [0] * len(thresholds)
+    seg = np.asarray(seg)
+    out = []
+    for lo, hi in thresholds:
+        inside = seg[(seg >= lo) & (seg < hi)]
+        out.append(int(inside.max()) if inside.size else int(lo) - 1)
+    return out
+
+
+def bank_from_lesions(per_case, max_volume=None):
+    """``per_case``: per training case (extents (K, 6) ints [min..., max...] of the boxes its box stage keeps, labels (K,),
+    the cropped shape, ``class_max_ids``) -> ``LesionBank``.  A lesion enters when every extent e_a = max_a - min_a + 1 is
+    at most PASTE_MAX_EXTENT, its box dilated by one voxel and clamped to the case intersects the box of no other kept
+    lesion of the case, and its bounding-box volume prod(max_a - min_a) - the measure of ``eval --size_bins`` - is at
+    most ``max_volume`` (None: no limit)."""
+    rows, max_ids, shapes = [], [], []
+    for case, (extents, labels, shape, ids) in enumerate(per_case):
+        ext = np.asarray(extents, dtype=np.int64).reshape(-1, 6)
+        shapes.append(tuple(int(n) for n in shape))
+        max_ids.append([int(v) for v in ids])
+        for k in range(ext.shape[0]):
+            lo, hi = ext[k, :3], ext[k, 3:]
+            if (hi - lo + 1).max() > PASTE_MAX_EXTENT:
+                continue
+            if max_volume is not None and int(np.prod(hi - lo)) > max_volume:
+                continue
+            dlo, dhi = np.maximum(lo - 1, 0), np.minimum(hi + 1, np.asarray(shape) - 1)
+            others = np.delete(ext, k, axis=0)
+            if ((others[:, :3] <= dhi) & (others[:, 3:] >= dlo)).all(1).any():
+                continue
+            rows.append([case, int(labels[k]), *lo.tolist(), *hi.tolist()])
+    return LesionBank(np.asarray(rows, dtype=np.int64).reshape(-1, 8), np.asarray(max_ids, dtype=np.int64).reshape(len(shapes), -1),
+                      shapes)
+
+
+def lower_pastes(draw, bank, case, target, thresholds, mode, max_lesions, candidates):
+    """One sample's ``_draw_lesionpaste`` result -> (max_lesions, PASTE_HEAD + 3 candidates) int32 rows, the layout of
+    msl_paste_lesions (include/mslesions3d_hip.h): [0] active, [1] donor case, [2..4] min, [5..7] extents e, [8] flips
+    (bit a mirrors axis a), [9] the mask value, [10..12] where the donor box's centre floor((min + max) / 2) lands inside
+    the destination box (mirrored), [13 + 3 j ..] corner of candidate j, floor(u_a (t_a - e_a + 1)).  ``case`` is the
+    target's position in the bank's case order, ``target`` the sample's size.  Rows past the drawn count, a paste with
+    some e_a > t_a and, in instances mode, one whose id (the target case's largest id of the donor's class + 1 + the
+    earlier active pastes of that class) reaches min(hi, 32768) are inactive: all zeros.  ``draw`` None: all inactive."""
+    rows = np.zeros((int(max_lesions), PASTE_HEAD + 3 * int(candidates)), dtype=np.int32)
+    if draw is None:
+        return rows
+    if not len(bank.rows):
+        raise ValueError("lesionpaste: the lesion bank is empty")
+    t = np.asarray(target, dtype=np.int64)
+    used = {}
+    for k, (u, flips, cand) in enumerate(draw):
+        row = bank.rows[min(int(np.floor(u * len(bank.rows))), len(bank.rows) - 1)]
+        donor, label, lo, hi = int(row[0]), int(row[1]), row[2:5], row[5:8]
+        e = hi - lo + 1
+        if (e > t).any():
+            continue
+        value = 1
+        if mode != "binary":
+            value = int(bank.max_ids[case][label - 1]) + 1 + used.get(label, 0)
+            if value >= min(thresholds[label - 1][1], PASTE_MAX_VALUE + 1):
+                continue
+            used[label] = used.get(label, 0) + 1
+        centre = (lo + hi) // 2 - lo
+        centre = np.where(np.asarray(flips) != 0, e - 1 - centre, centre)
+        rows[k, 0], rows[k, 1], rows[k, 2:5], rows[k, 5:8] = 1, donor, lo, e
+        rows[k, 8], rows[k, 9], rows[k, 10:13] = flips[0] + 2 * flips[1] + 4 * flips[2], value, centre
+        rows[k, PASTE_HEAD:] = np.floor(np.asarray(cand, dtype=np.float64) * (t - e + 1)).astype(np.int64).reshape(-1)
+    return rows
+
+
+def _paste_row_ok(r, donors, target):
+    """What msl_paste_lesions refuses (report -2): an inactive row, a case out of range, a donor box outside the case, an
+    extent outside 1 .. PASTE_MAX_EXTENT, a value outside 1 .. 32767, a centre outside the box, a candidate outside the
+    sample."""
+    if r[0] == 0 or not 0 <= r[1] < len(donors):
+        return False
+    lo, e = r[2:5], r[5:8]
+    if (e < 1).any() or (e > PASTE_MAX_EXTENT).any() or not 1 <= r[9] <= PASTE_MAX_VALUE:
+        return False
+    if (lo < 0).any() or (lo + e > np.asarray(donors[int(r[1])][1].shape[-3:])).any():
+        return False
+    if (r[10:13] < 0).any() or (r[10:13] >= e).any():
+        return False
+    cand = r[PASTE_HEAD:].reshape(-1, 3)
+    return bool((cand >= 0).all() and (cand + e <= np.asarray(target)).all())
+
+
+def paste_lesions(img, seg, pastes, donors):
+    """Apply one sample's paste rows (``lower_pastes``) IN PLACE to ``img`` (C, T0, T1, T2) f32 and ``seg`` (T0, T1, T2) or
+    (1, T0, T1, T2), both C-contiguous numpy arrays; ``donors[case]`` -> (image (C, n0, n1, n2) f32, mask (n0, n1, n2) or
+    (1, ...)) of a cached case.  -> report, one int per row: the accepted candidate's index, -1 none accepted, -2 an
+    inactive or refused row (``_paste_row_ok``).
+
+    Rows are applied in order, each on the mask the earlier ones left.  The first candidate j passes whose (a)
+    destination box, dilated by one voxel and clamped to the sample, holds no non-zero mask voxel and (b) image voxel at
+    the destination of the donor box's centre is non-zero in every channel.  Writing, donor coordinates mirrored per
+    flip bit: where the donor mask inside its box is non-zero, image = the donor's value in every channel and mask = the
+    row's value; a rim voxel - inside the dilated box and the sample, not written, a 6-neighbour of a written voxel, its
+    donor coordinate inside the donor case - gets image = 0.5f * dst + 0.5f * donor (two rounded products, one rounded sum)
+    and keeps its mask."""
+    img = np.asarray(img)
+    mask = seg[0] if seg.ndim == 4 else seg
+    T = np.asarray(mask.shape)
+    half = np.float32(0.5)
+    report = []
+    for r in np.asarray(pastes, dtype=np.int64):
+        if not _paste_row_ok(r, donors, T):
+            report.append(-2)
+            continue
+        dimg, dseg = donors[int(r[1])]
+        dseg = dseg[0] if dseg.ndim == 4 else dseg
+        dimg = dimg[None] if dimg.ndim == 3 else dimg
+        lo_d, e, flips, value, centre = r[2:5], r[5:8], [(r[8] >> a) & 1 for a in range(3)], r[9], r[10:13]
+        accepted = -1
+        for j, c in enumerate(r[PASTE_HEAD:].reshape(-1, 3)):
+            a, b = np.maximum(c - 1, 0), np.minimum(c + e + 1, T)
+            if mask[a[0]:b[0], a[1]:b[1], a[2]:b[2]].any():
+                continue
+            at = tuple(c + centre)
+            if not all(img[ch][at] != 0 for ch in range(img.shape[0])):
+                continue
+            accepted = j
+            break
+        report.append(accepted)
+        if accepted < 0:
+            continue
+        c = r[PASTE_HEAD + 3 * accepted:PASTE_HEAD + 3 * accepted + 3]
+        # the dilated box in destination order, p = -1 .. e per axis; its donor coordinate, mirrored where flipped
+        n = np.asarray(dseg.shape)
+        idx, inside = [], []
+        for ax in range(3):
+            p = np.arange(-1, e[ax] + 1)
+            d = lo_d[ax] + (e[ax] - 1 - p if flips[ax] else p)
+            idx.append(np.clip(d, 0, n[ax] - 1))
+            inside.append((d >= 0) & (d < n[ax]))
+        grid = np.ix_(*idx)
+        in_case = inside[0][:, None, None] & inside[1][None, :, None] & inside[2][None, None, :]
+        in_box = np.zeros(tuple(e + 2), dtype=bool)
+        in_box[1:-1, 1:-1, 1:-1] = True
+        written = (dseg[grid] != 0) & in_box
+        near = np.zeros_like(written)
+        near[1:] |= written[:-1]
+        near[:-1] |= written[1:]
+        near[:, 1:] |= written[:, :-1]
+        near[:, :-1] |= written[:, 1:]
+        near[:, :, 1:] |= written[:, :, :-1]
+        near[:, :, :-1] |= written[:, :, 1:]
+        rim = near & ~written & in_case
+        # clip the dilated box to the sample
+        a, b = np.maximum(c - 1, 0), np.minimum(c + e + 1, T)
+        cut = tuple(slice(a[k] - (c[k] - 1), b[k] - (c[k] - 1)) for k in range(3))
+        dst = tuple(slice(a[k], b[k]) for k in range(3))
+        written, rim = written[cut], rim[cut]
+        for ch in range(img.shape[0]):
+            src = dimg[ch][grid][cut].astype(np.float32)
+            view = img[ch][dst]
+            view[rim] = (half * view[rim]) + (half * src[rim])
+            view[written] = src[written]
+        mask[dst][written] = value
+    return report
+
+
 AUGMENTATIONS = {"flip": _aug_flip, "rotate90": _aug_rotate90, "affine": _aug_affine,
                  "zoom": _aug_zoom, "griddistortion": _aug_griddistortion, "elastic3d": _aug_elastic3d,
                  "shiftintensity": _aug_shiftintensity, "scaleintensity": _aug_scaleintensity,
-                 "gaussiansmooth": _aug_gaussiansmooth, "biasfield": _aug_biasfield, "gaussiannoise": _aug_gaussiannoise}
+                 "gaussiansmooth": _aug_gaussiansmooth, "biasfield": _aug_biasfield, "gaussiannoise": _aug_gaussiannoise,
+                 PASTE_NAME: _aug_lesionpaste}
 DRAWS = {"flip": _draw_flip, "rotate90": _draw_rotate90, "affine": _draw_affine,
          "zoom": _draw_zoom, "griddistortion": _draw_griddistortion, "elastic3d": _draw_elastic3d,
          "shiftintensity": _draw_shiftintensity, "scaleintensity": _draw_scaleintensity,
-         "gaussiansmooth": _draw_gaussiansmooth, "biasfield": _draw_biasfield, "gaussiannoise": _draw_gaussiannoise}
+         "gaussiansmooth": _draw_gaussiansmooth, "biasfield": _draw_biasfield, "gaussiannoise": _draw_gaussiannoise,
+         PASTE_NAME: _draw_lesionpaste}
 MR_NAMES = ("gaussiansmooth", "biasfield", "gaussiannoise")
 
 
@@ -638,14 +856,19 @@ def transform_name(t):
 
 def check_mr_last(augmentations):
     """The MR transforms act on the finished sample: an entry of another kind behind one of them raises
-    NotImplementedError (``devicedata.sample_params`` refuses the same lists)."""
+    NotImplementedError (``devicedata.sample_params`` refuses the same lists).  ``lesionpaste`` acts there as well, in
+    front of them: it stands once, behind every other entry and in front of the MR transforms, or the list is refused."""
     names = [transform_name(t) for t in augmentations]
-    seen = False
+    seen = pasted = False
     for n in names:
         if n in MR_NAMES:
             seen = True
         elif seen:
             raise NotImplementedError(f"{n} placed behind an MR transform ({' / '.join(MR_NAMES)} come last)")
+        elif pasted:  # lesionpaste acts on the finished sample too: once, behind every entry that is not an MR transform
+            raise NotImplementedError(f"{n} placed behind {PASTE_NAME} (only {' / '.join(MR_NAMES)} follow it)")
+        elif n == PASTE_NAME:
+            pasted = True
 
 
 def draw_augmentations(augmentations, rs):
@@ -698,6 +921,8 @@ INTENSITY_NAMES = ("shiftintensity", "scaleintensity")
 MR_AUGMENTATIONS = [("gaussiansmooth", {"sigma": (0.25, 1.5), "prob": 0.1}),
                     ("biasfield", {"degree": 3, "coeff_range": (0.0, 0.1), "lattice": 9, "prob": 0.1}),
                     ("gaussiannoise", {"std": 0.1, "prob": 0.1})]
+# copy-paste of cached lesions on to the finished sample: -dm lesions only
+PASTE_AUGMENTATIONS = [(PASTE_NAME, {"prob": 0.5, "max_lesions": 4, "candidates": 8, "max_volume": None})]
 
 
 def select_training_augmentations(names):
@@ -705,9 +930,10 @@ def select_training_augmentations(names):
     ``WARP_AUGMENTATIONS`` that were asked for, in that list's order, behind the flips / rot90s / affines and in front of
     the intensity operations (the order ``devicedata.sample_params`` takes), the entry of ``DEFORM_AUGMENTATIONS`` behind
     those, plus the entries of ``MR_AUGMENTATIONS`` that were asked for, in that list's order, behind everything else.
+    ``lesionpaste`` (``PASTE_AUGMENTATIONS``) stands behind every entry that is not an MR transform and in front of those.
     Unknown names raise ValueError."""
     resample = WARP_AUGMENTATIONS + DEFORM_AUGMENTATIONS
-    own = [n for n, _ in resample] + list(MR_NAMES)
+    own = [n for n, _ in resample] + [PASTE_NAME] + list(MR_NAMES)
     known = [n for n, _ in REFERENCE_AUGMENTATIONS + LESIONS_AUGMENTATIONS] + own
     unknown = set(names) - set(known)
     if unknown:
@@ -715,7 +941,7 @@ def select_training_augmentations(names):
     out = select_augmentations([n for n in names if n not in own])
     at = next((k for k, (n, _) in enumerate(out) if n in INTENSITY_NAMES), len(out))
     out = out[:at] + [(n, kw) for n, kw in resample if n in names] + out[at:]
-    return out + [(n, kw) for n, kw in MR_AUGMENTATIONS if n in names]
+    return out + [(n, kw) for n, kw in PASTE_AUGMENTATIONS + MR_AUGMENTATIONS if n in names]
 
 
 def _load(path_noext):
@@ -784,6 +1010,8 @@ class _Cases(Dataset):
         for t in self.augmentations:
             if (t if isinstance(t, str) else t[0]) not in AUGMENTATIONS:
                 raise ValueError(f"unknown transform {t!r}")
+            if transform_name(t) == PASTE_NAME:  # uint8 class masks, no instances, no bank
+                raise NotImplementedError(f"{PASTE_NAME} needs the lesion bank of a LesionsDataModule (-dm lesions)")
         # augmentation randomness is drawn per SAMPLE from (seed, epoch, subject): DataLoader workers are forked copies of
         # this object, so a generator stored here would hand every worker - and every epoch - the same stream
         self.seed, self.epoch = seed, 0
@@ -827,7 +1055,7 @@ def collate_fn(batch):
            "subject": [b["subject"] for b in batch], "img_meta_dict": [b["img_meta_dict"] for b in batch],
            "seg_meta_dict": [b["seg_meta_dict"] for b in batch], "img_transforms": [b["img_transforms"] for b in batch],
            "seg_transforms": [b["seg_transforms"] for b in batch]}
-    for key in GEOMETRY_KEYS + ("native_shape", "patch_origin"):  # LesionsDataModule samples carry them; passed through as lists
+    for key in GEOMETRY_KEYS + ("native_shape", "patch_origin", "paste_report"):  # LesionsDataModule samples carry them; passed through as lists
         if all(key in b for b in batch):
             out[key] = [b[key] for b in batch]
     return out
@@ -1347,6 +1575,26 @@ def _same_affine(affine, other, case, name):
         raise ValueError(f"case {case}: image {name} and the mask carry different affines")
 
 
+class _DonorCases:
+    """``paste_lesions``'s donors on the host route: ``self[j]`` -> (image, mask) of ``cases.cropped(j)``, the last
+    ``keep`` cases held, so that the samples of one batch do not load the same donor twice."""
+
+    def __init__(self, cases, keep=8):
+        self.cases, self.keep, self._held = cases, int(keep), collections.OrderedDict()
+
+    def __len__(self):
+        return len(self.cases)
+
+    def __getitem__(self, j):
+        if j in self._held:
+            self._held.move_to_end(j)
+        else:
+            self._held[j] = self.cases.cropped(j)[:2]
+            while len(self._held) > self.keep:
+                self._held.popitem(last=False)
+        return self._held[j]
+
+
 class _LesionCases(Dataset):
     """The per-sample pipeline of LesionsDataModule (datasets.py:199-236): load -> orientation("LPI") + spacing(1 mm)
     for a case that carries an affine (``regrid_plan`` / ``regrid``) -> crop_foreground(margin 5) ->
@@ -1355,7 +1603,9 @@ class _LesionCases(Dataset):
     box is the union of the channels' foregrounds, every channel is normalised over its own non-zero voxels, and one set
     of augmentation draws moves all channels and the mask (the intensity operands are shared, as in MONAI).  The MR
     transforms (``MR_NAMES``) are drawn in list order with the others but applied to the fitted / windowed sample, where
-    the device route applies them; they must come last (``check_mr_last``)."""
+    the device route applies them; they must come last (``check_mr_last``).  ``lesionpaste`` is
+    drawn in list order too and applied to the fitted / windowed sample in front of them: ``lower_pastes`` on the data
+    set's ``bank``, ``paste_lesions`` with the donors ``cropped(j)`` gives; the sample then carries "paste_report"."""
 
     def __init__(self, module, subjects, augmentations=None, seed=0, patch=None):
         self.module, self.subjects = module, list(subjects)
@@ -1368,6 +1618,30 @@ class _LesionCases(Dataset):
         self.seed, self.epoch = seed, 0
         self.patch = None if patch is None else tuple(int(t) for t in patch)  # training windows instead of the fit
         self._plans = {}  # position -> the RegridPlan of the case's last load (None: no affine); native_plan
+        self.paste_kw = next((dict(PASTE_AUGMENTATIONS[0][1], **({} if isinstance(t, str) else t[1]))
+                              for t in self.augmentations if transform_name(t) == PASTE_NAME), None)
+        if self.paste_kw is not None:
+            check_lesionpaste(**self.paste_kw)
+        self.bank = None  # LesionBank of a list that names lesionpaste: build_bank, at set-up
+        self.donors = _DonorCases(self)
+
+    def build_bank(self):
+        """The lesion bank of this data set's cases, in ``subjects`` order: per case the extents
+        and labels its box stage gives on the cropped, un-augmented mask.  Every case is loaded once.  An empty bank
+        raises ValueError."""
+        m = self.module
+        per_case = []
+        for i in range(len(self)):
+            seg = self.cropped(i)[1]
+            extents, labels, shape = _instance_extents(seg, m.thresholds, m.segmentation_mode)
+            keep = _fractional_boxes(extents, shape)[1].numpy() if extents else np.zeros(0, dtype=bool)
+            per_case.append((np.asarray(extents, dtype=np.int64).reshape(-1, 6)[keep], np.asarray(labels, dtype=np.int64)[keep],
+                             shape, class_max_ids(seg, m.thresholds, m.segmentation_mode)))
+        self.bank = bank_from_lesions(per_case, self.paste_kw.get("max_volume"))
+        if not len(self.bank.rows):
+            raise ValueError(f"{PASTE_NAME}: the lesion bank is empty: no lesion of the {len(self)} training cases is at most "
+                             f"{PASTE_MAX_EXTENT} voxels wide, clear of its neighbours and within max_volume")
+        return self.bank
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -1472,10 +1746,14 @@ class _LesionCases(Dataset):
             centres = lesion_centres(seg, m.thresholds, m.segmentation_mode)
         rs = self.sample_rng(i) if self.augmentations or centres is not None else None
         mr = []  # drawn in list order, applied to the finished sample (the device route runs them on the built batch)
+        paste = None  # lesionpaste's draw: applied there too, in front of the MR transforms
         for t in self.augmentations:
             name, kw = (t, {}) if isinstance(t, str) else t
             if name in MR_NAMES:
                 mr.append((name, DRAWS[name](rs, **kw), kw))
+                continue
+            if name == PASTE_NAME:
+                paste = DRAWS[name](rs, **kw)
                 continue
             img, seg = AUGMENTATIONS[name](img, seg, rs, **kw)
         if centres is not None:
@@ -1489,6 +1767,16 @@ class _LesionCases(Dataset):
             img, seg = window(img, origin, patch), window(seg, origin, patch)
         elif fit:
             img, seg = resize_with_pad_or_crop(img, m.spatial_size), resize_with_pad_or_crop(seg, m.spatial_size)
+        report = None
+        if self.paste_kw is not None:
+            if self.bank is None:
+                raise ValueError(f"{PASTE_NAME}: no lesion bank (LesionsDataModule.setup builds it)")
+            rows = lower_pastes(paste, self.bank, i, img.shape[1:], m.thresholds, m.segmentation_mode,
+                                self.paste_kw["max_lesions"], self.paste_kw["candidates"])
+            report = [-2] * len(rows)
+            if paste is not None:  # in place, on copies of its own: the fit / window may have returned views of the case
+                img, seg = np.array(img, dtype=np.float32, order="C"), np.array(seg, order="C")
+                report = paste_lesions(img, seg, rows, self.donors)
         for name, draw, kw in mr:
             img = apply_mr(name, img, draw, kw)
         img = np.ascontiguousarray(img)
@@ -1500,6 +1788,8 @@ class _LesionCases(Dataset):
                "crop_origin": lo, "crop_shape": crop_shape, "full_shape": full_shape}
         if origin is not None:  # of the window, in the (augmented) cropped case's voxels
             out["patch_origin"] = tuple(int(v) for v in origin)
+        if report is not None:  # per paste row: the accepted candidate, -1 none, -2 inactive or refused
+            out["paste_report"] = report
         if plan is not None:  # a case with an affine: full_shape is the regridded shape, the stored one rides along
             out["img_meta_dict"] = {"affine": plan.out_affine}
             out["native_shape"] = tuple(plan.src_shape)
@@ -1649,6 +1939,8 @@ class LesionsDataModule(ExampleDataset):
             train, test = train_test_split(self.subjects_list, train_size=0.8, test_size=0.2,
                                            random_state=self.random_state)
         self.train_dataset = _LesionCases(self, train, self.augmentations, self.random_state, patch=self.patch_size)
+        if self.train_dataset.paste_kw is not None:  # lesionpaste: the bank, once, over the training cases (every rank's)
+            self.train_dataset.build_bank()
         self.test_dataset = _LesionCases(self, test)
         if self.patch_size is not None:
             self.test_dataset = _LesionTiles(self.test_dataset, self.patch_size, self.tile_margin)

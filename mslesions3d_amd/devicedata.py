@@ -27,6 +27,8 @@ which some sample drew an elastic3d (a ``DeformStage``: a cubic B-spline lattice
 msl_augment_deform_mc in the same way.  An augmentation
 list that names gaussiansmooth / biasfield / gaussiannoise (the MR stage) adds msl_augment_mr
 (csrc/mraug.hip) behind the batch build of either cache: ``mr_tables`` lowers the draws, ``MRStageRunner`` launches.
+A list that names lesionpaste adds msl_paste_lesions (csrc/lesionpaste.hip) between the two on
+``LesionCache``: copy-paste of lesions of the cached training cases, lowered to integer rows by ``datasets.lower_pastes``.
 """
 from collections import namedtuple
 
@@ -36,9 +38,10 @@ from os.path import join as pjoin
 
 from . import _lib
 from ._lib import ptr
-from .datasets import (MR_MAX_RADIUS, MR_NAMES, SCIPY_BOUNDARY, ShardSampler, _load, affine_matrix, affine_offset,
-                       bias_lattice, centres_to_augmented, deform_coords, deform_lattice, draw_augmentations,
-                       gaussian_taps, patch_origin, regrid_plan, sample_rng, transform_name, view_plan, warp_tables)
+from .datasets import (MR_MAX_RADIUS, MR_NAMES, PASTE_AUGMENTATIONS, PASTE_HEAD, PASTE_NAME, SCIPY_BOUNDARY, ShardSampler,
+                       _load, affine_matrix, affine_offset, bank_from_lesions, bias_lattice, centres_to_augmented,
+                       check_lesionpaste, deform_coords, deform_lattice, draw_augmentations, gaussian_taps, lower_pastes,
+                       patch_origin, regrid_plan, sample_rng, transform_name, view_plan, warp_tables)
 
 PARAM_STRIDE = 16  # f64 per sample of msl_augment_resample
 AFFINE_STRIDE = 32  # f64 per sample of msl_augment_affine
@@ -94,6 +97,11 @@ MR_STRIDE = 8  # f64 per sample of msl_augment_mr
 MR_TAPS = 2 * MR_MAX_RADIUS + 1  # f32 per axis of its taps table
 MR_LATTICE = 9  # points per axis of its lattice table
 MR_BLUR, MR_BIAS, MR_NOISE = 1, 2, 4  # bits of field [0] of its parameter row
+# lesionpaste of the augmentation list: its draw (``datasets._draw_lesionpaste``'s result; None: not
+# applied) and its keyword arguments.  msl_paste_lesions runs it on the built batch in front of the MR stage; like an
+# ``MRStage`` it moves no point and the batch build does not see it
+PasteStage = namedtuple("PasteStage", "draw kw")
+POST_STAGES = (MRStage, PasteStage)  # what runs on the built batch
 
 
 def _stream(dev):
@@ -196,7 +204,9 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
     the flips / rot90s, in front of the intensity operations.  A drawn elastic3d is a ``DeformStage`` with the lattice of
     the permuted shape, under the same rules.  gaussiansmooth / biasfield / gaussiannoise are the last
     group: each appends an ``MRStage`` (drawn or not), which moves no point and which the batch build skips
-    (``mr_tables`` lowers them for msl_augment_mr); any other entry behind one of them raises NotImplementedError."""
+    (``mr_tables`` lowers them for msl_augment_mr); any other entry behind one of them raises NotImplementedError.
+    lesionpaste appends a ``PasteStage`` (drawn or not) under the same terms: ``ragged`` only, once, behind every entry
+    that is not an MR transform and in front of those; any other position raises NotImplementedError."""
     axis, rev = [0, 1, 2], [0, 0, 0]
     stages = []
     n_ops = 0
@@ -206,8 +216,20 @@ def sample_params(draws, shape, augmentations=None, ragged=False):
         rev[a], rev[b] = rev[b], rev[a]
 
     n_mr = 0
+    pasted = False
     for k, (name, d) in enumerate(draws):
         kw = transform_kw(augmentations[k]) if augmentations is not None else {}
+        if name == PASTE_NAME:  # once, behind every other entry, in front of the MR transforms: a PasteStage, drawn or not
+            if pasted or n_mr:
+                raise NotImplementedError(f"device pipeline: {PASTE_NAME} once, in front of the MR transforms "
+                                          f"({' / '.join(MR_NAMES)})")
+            if not ragged:
+                raise NotImplementedError(f"device pipeline: {PASTE_NAME} on the example cache (no lesion bank)")
+            pasted = True
+            stages.append(PasteStage(d, dict(PASTE_AUGMENTATIONS[0][1], **kw)))
+            continue
+        if pasted and name not in MR_NAMES:
+            raise NotImplementedError(f"device pipeline: {name} after {PASTE_NAME} (only {' / '.join(MR_NAMES)} follow it)")
         if name in MR_NAMES:  # the last group: an MRStage each, drawn or not
             stages.append(MRStage(name, d, kw))
             if MR_NAMES.index(name) < n_mr:  # one launch carries blur, then bias, then noise
@@ -390,7 +412,7 @@ def batch_launches(slots, per_sample):
     permutation; the last one carries the intensity operations.  A launch whose stages are all diagonal with
     reflection padding and that carries no operation stays on msl_augment_resample."""
     N = len(slots)
-    geo = [[st for st in stages if not isinstance(st, (IntensityOp, MRStage))] for _, stages in per_sample]
+    geo = [[st for st in stages if not isinstance(st, (IntensityOp,) + POST_STAGES)] for _, stages in per_sample]
     ops = [[st for st in stages if isinstance(st, IntensityOp)] for _, stages in per_sample]
     n_geo = max((len(g) for g in geo), default=0)
     used = [j for j in range(n_geo) if any(j < len(g) and g[j] is not None for g in geo)] or [None]
@@ -722,7 +744,7 @@ def _stage_rows(cases, per_sample, own):
     rows = np.zeros((len(cases), AFFINE_STRIDE), dtype=np.float64)
     coords, at = [], 0
     for n, (case, (perm, stages)) in enumerate(zip(cases, per_sample)):
-        geo = [st for st in stages if not isinstance(st, (IntensityOp, MRStage))]
+        geo = [st for st in stages if not isinstance(st, (IntensityOp,) + POST_STAGES)]
         if len(geo) > 1:
             raise NotImplementedError("device pipeline: two affine stages on cases of unequal shape")
         st = geo[0] if geo else None
@@ -758,6 +780,24 @@ def pack_launch(rows, table, windows=None):
     if windows is not None:
         packed[at_windows:].view(np.int32)[:n_int] = np.asarray(windows, dtype=np.int32).reshape(-1)
     return packed, at_table, at_windows
+
+
+def pack_ints(packed, ints):
+    """An int32 table behind a ``pack_launch`` upload -> (packed, offset in f64 elements): the ints ride in the doubles
+    behind what is there (an odd count: a last int of 0), as the windows do.  msl_paste_lesions's rows travel this way."""
+    ints = np.ascontiguousarray(ints, dtype=np.int32).reshape(-1)
+    out = np.zeros(packed.size + (ints.size + 1) // 2, dtype=np.float64)
+    out[:packed.size] = packed
+    out[packed.size:].view(np.int32)[:ints.size] = ints
+    return out, packed.size
+
+
+def paste_kw(augmentations):
+    """The keyword arguments of the list's lesionpaste entry over the defaults, or None where it names none."""
+    for t in augmentations:
+        if transform_name(t) == PASTE_NAME:
+            return dict(PASTE_AUGMENTATIONS[0][1], **transform_kw(t))
+    return None
 
 
 def names_mr(augmentations):
@@ -925,7 +965,13 @@ class LesionCache:
     msl_augment_window_mc cuts the window out of the augmented case in the launch that augments it; the batch carries
     "patch_origin".  The lesion centres ``patch_origin`` aims at are taken once per training case at construction
     (``centres``).  ``val_batches`` yields the tiles of ``datasets._LesionTiles`` (every validation case is cached on every
-    rank: the tile list, not the case list, is what the ranks share out), ``batch_size`` tiles at a time."""
+    rank: the tile list, not the case list, is what the ranks share out), ``batch_size`` tiles at a time.
+
+    lesionpaste: a list that names it gets the lesion bank at construction (``bank``, the host's
+    ``_LesionCases.build_bank`` from the device's own box stage); ``train_batches`` lowers every sample's draw with
+    ``datasets.lower_pastes`` and, in a batch where some sample drew one, msl_paste_lesions (csrc/lesionpaste.hip) runs on
+    the built batch in front of the MR stage and the box stage.  The batch carries "paste_report" (N, max_lesions) i32;
+    ``paste_counts()`` reads the epoch's totals once."""
 
     def __init__(self, dataset, device, max_objects_per_image=64, max_runs_per_image=MAX_RUNS_PER_IMAGE):
         if dataset.train_dataset is None:
@@ -989,30 +1035,73 @@ class LesionCache:
                                   dtype=torch.int64, device=dev).reshape(-1, 4)
         self.capacity = int(max_objects_per_image) * self.batch_size
         self._bufs = {}
+        self.paste = paste_kw(self.augmentations)
+        if self.paste is not None:  # lesionpaste: the bank over the training cases, in train_dataset.subjects order
+            check_lesionpaste(**self.paste)
+            self.bank = self._lesion_bank()
+            self._paste_counts = torch.zeros(2, dtype=torch.int64, device=dev)  # rows that were tested / accepted
         if self.patch is not None:
             self.centres = {k: self._case_centres(k) for k in sorted(set(self.train_slots))}
-            tiles = [(s, k, tuple(int(v) for v in row[:3])) for s, k in self.val_order
+            tiles =[(s, k, tuple(int(v) for v in row[:3])) for s, k in self.val_order
                      for row in view_plan(self.shapes[k], self.patch, dataset.tile_margin)]
             if dataset.world_size > 1:
                 own = ShardSampler(len(tiles), dataset.rank, dataset.world_size, False, dataset.random_state).indices()
                 tiles = [tiles[i] for i in own]
             self.val_tiles = tiles  # (subject, slot, origin): this rank's share of dataset.test_dataset.tiles
 
-    def _case_centres(self, slot):
-        """``datasets.lesion_centres`` of a cached case -> f64 (K, 3): one msl_instance_boxes call (msl_binary_boxes on
-        a binary mask: the components of the cropped, un-augmented mask) on the cropped mask, read back once.  The kernel writes f32(e / n) for an inclusive integer extent e on an axis of n voxels; the extent
+    def _case_lesions(self, slot):
+        """The boxes the box stage keeps on a cached case -> (inclusive integer extents f64 (K, 6) [min..., max...], labels
+        i64 (K,)), in its order: one msl_instance_boxes call (msl_binary_boxes on a binary mask: the components of the
+        cropped, un-augmented mask) on the cropped mask, read back once.  The kernel writes f32(e / n) for an inclusive
+        integer extent e on an axis of n voxels; the extent
         is recovered as rint(f32(e / n) * n) in f64.  The division's relative error is at most 2^-24 and the f64 product
         adds 2^-53, so the product is within e * 2^-23 of e: exact while e < 2^22, and the arena refuses axes of 2^20
         voxels or more."""
         shape = self.shapes[slot]
         if not int(np.prod(shape)):
-            return np.zeros((0, 3), dtype=np.float64)
+            return np.zeros((0, 6), dtype=np.float64), np.zeros(0, dtype=np.int64)
         out = _box_stage(self.dataset, 1, shape, INST_MAX_IDS, self.device, self.max_runs_per_image, "LesionCache")
         out.launch(self.case(slot)[1], _stream(self.device))
         n = out.obj_off.cpu().tolist()[1]  # (synchronises: the flag and the rows are there too)
         out.raise_on_overflow(out.flag.item())
         ext = np.rint(out.gb[:n].cpu().numpy().astype(np.float64) * np.asarray(shape * 2, dtype=np.float64))
+        return ext, out.gl[:n].cpu().numpy().astype(np.int64)
+
+    def _case_centres(self, slot):
+        """``datasets.lesion_centres`` of a cached case -> f64 (K, 3), from ``_case_lesions``'s extents."""
+        ext, _ = self._case_lesions(slot)
         return (ext[:, :3] + ext[:, 3:]) / 2
+
+    def _lesion_bank(self):
+        """``datasets.bank_from_lesions`` over the training cases in ``train_dataset.subjects`` order, the bank
+        ``_LesionCases.build_bank`` makes on the host: per case the extents and labels of ``_case_lesions`` and, in
+        instances mode, the largest id of every class's threshold pair on the cached mask (torch; set-up plumbing)."""
+        thr = self.dataset.thresholds
+        per_case = []
+        for slot in self.train_slots:
+            ext, labels = self._case_lesions(slot)
+            ids = [0] * len(thr)
+            if self.dataset.segmentation_mode == "instances":
+                seg = self.case(slot)[1]
+                for c, (lo, hi) in enumerate(thr):
+                    inside = seg[(seg >= int(lo)) & (seg < min(float(hi), 32768.0))]
+                    ids[c] = int(inside.max().item()) if inside.numel() else int(lo) - 1
+            per_case.append((ext.astype(np.int64), labels, self.shapes[slot], ids))
+        bank = bank_from_lesions(per_case, self.paste.get("max_volume"))
+        if not len(bank.rows):
+            raise ValueError(f"{PASTE_NAME}: the lesion bank is empty: no lesion of the {len(per_case)} training cases is "
+                             f"small enough and clear of its neighbours")
+        return bank
+
+    def paste_counts(self, reset=True):
+        """-> (pastes tested, pastes accepted) since the last reset: ONE read of the device counters (train.py reads them
+        at the end of an epoch); (0, 0) without lesionpaste."""
+        if self.paste is None:
+            return 0, 0
+        asked, accepted = self._paste_counts.cpu().tolist()
+        if reset:
+            self._paste_counts.zero_()
+        return int(asked), int(accepted)
 
     def _check_memory(self, nbytes, what):
         free, _ = torch.cuda.mem_get_info(self.device)
@@ -1051,14 +1140,20 @@ class LesionCache:
             if names_mr(self.augmentations):  # msl_augment_mr works out of place
                 b["built"] = torch.empty_like(b["img"])
                 b["mr"] = MRStageRunner(N, self.channels, self.target, dev)
+            if self.paste is not None:  # msl_paste_lesions's report: -2 where nothing was asked
+                b["paste_report"] = torch.full((N, int(self.paste["max_lesions"])), -2, dtype=torch.int32, device=dev)
         return b
 
-    def _run(self, slots, per_sample, b, windows=None):
+    def _run(self, slots, per_sample, b, windows=None, pastes=None):
+        """``pastes``: the (N, K, stride) int32 rows of ``datasets.lower_pastes`` for a training batch in which some
+        sample drew a lesionpaste; they ride in the batch's one pinned upload behind the build's rows."""
         stream, N = _stream(self.device), len(slots)
         # one resampling entry per pipeline: a batch holds warp stages or deformation stages, never both
         deform = any(isinstance(st, DeformStage) for _, stages in per_sample for st in stages)
         rows, table = (deform_rows if deform else warp_rows)(slots, per_sample)
         packed, at_table, at_windows = pack_launch(rows, table, windows)
+        if pastes is not None:
+            packed, at_pastes = pack_ints(packed, pastes)
         pd = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
         origins = None if windows is None else pd.data_ptr() + 8 * at_windows
         if table.size:  # some sample drew a warp / deformation; every other batch keeps the launch it always had
@@ -1070,10 +1165,21 @@ class LesionCache:
         built = b["built"] if "mr" in b and _drew_mr(per_sample) else b["img"]
         _lib.call(entry, ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table), len(self.shapes),
                   ptr(pd), *own, N, *self.target, ptr(built), ptr(b["seg"]), stream)
-        self._finish(b, per_sample, stream)
+        self._finish(b, per_sample, stream, built, None if pastes is None else (pd, at_pastes, pastes.shape))
 
-    def _finish(self, b, per_sample, stream):
-        """Behind the batch build: the MR stage on the built images, then the box stage."""
+    def _finish(self, b, per_sample, stream, built=None, pastes=None):
+        """Behind the batch build: the paste stage on the built batch (only where some sample drew one; ``pastes``: the
+        upload, the rows' offset in it in f64 elements and their (N, K, stride) shape), then the MR stage on the built
+        images, then the box stage."""
+        if "paste_report" in b:
+            b["paste_report"].fill_(-2)
+        if pastes is not None:
+            pd, at, (N, K, stride) = pastes
+            _lib.call("msl_paste_lesions", ptr(self.img), ptr(self.seg), self.seg.numel(), self.channels, ptr(self.table),
+                      len(self.shapes), pd.data_ptr() + 8 * at, N, K, (stride - PASTE_HEAD) // 3, *self.target, ptr(built),
+                      ptr(b["seg"]), ptr(b["paste_report"]), stream)
+            rep = b["paste_report"]  # the epoch's counters stay on the device: train.py reads them once per epoch
+            self._paste_counts += torch.stack([(rep > -2).sum(), (rep >= 0).sum()])
         if "mr" in b and _drew_mr(per_sample):
             b["mr"].run(b["built"], per_sample, b["img"], stream)
         b["box"].launch(b["seg"], stream)
@@ -1093,12 +1199,22 @@ class LesionCache:
                     centres = centres_to_augmented(self.centres[slot], self.shapes[slot], perm, stages)
                     windows.append(patch_origin(rs, tuple(self.shapes[slot][a] for a in perm[0]), self.patch, centres,
                                                 self.dataset.patch_foreground))
+            pastes = None
+            if self.paste is not None:  # the host's lowering, sample by sample; a launch only where some sample drew one
+                drawn = [next(st.draw for st in stages if isinstance(st, PasteStage)) for _, stages in per_sample]
+                if any(d is not None for d in drawn):
+                    pastes = np.stack([lower_pastes(d, self.bank, i, self.target, self.dataset.thresholds,
+                                                    self.dataset.segmentation_mode, self.paste["max_lesions"],
+                                                    self.paste["candidates"]) for d, i in zip(drawn, idx)])
+                    pastes[:, :, 1] = np.asarray(self.train_slots, dtype=np.int32)[pastes[:, :, 1]]  # bank case -> arena slot
             b = self._buffers(len(idx))
-            self._run([self.train_slots[i] for i in idx], per_sample, b, windows)
+            self._run([self.train_slots[i] for i in idx], per_sample, b, windows, pastes)
             out = {"img": b["img"], "seg": b["seg"], "gb": b["box"].gb, "gl": b["box"].gl, "obj_off": b["box"].obj_off,
                    "capacity": self.capacity, "subject": [tr.subjects[i] for i in idx], "_box": b["box"]}
             if windows is not None:
                 out["patch_origin"] = windows
+            if self.paste is not None:
+                out["paste_report"] = b["paste_report"]
             yield out
 
     step = DeviceCache.step

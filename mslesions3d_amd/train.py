@@ -41,7 +41,11 @@ def build_parser():
                    help='flip rotate90 translate scale (example recipe); affine shiftintensity scaleintensity (train_lesions); '
                         'zoom griddistortion (separable warps) elastic3d (free-form deformation): one resampling stage '
                         'per run with -dm lesions -c 1; '
+                        'lesionpaste (-dm lesions: copy-paste of lesions of the training cases on to the finished sample); '
                         'gaussiansmooth biasfield gaussiannoise (the MR stage, applied last to the finished sample)')
+    p.add_argument('--paste_max_volume', type=float, default=None, metavar='V',
+                   help="lesionpaste: only lesions whose bounding-box volume is at most V voxels enter the bank "
+                        "(the measure of eval --size_bins; default: no limit)")
     p.add_argument('-ld', '--logdir', type=str, default=r'../logs/artificial_dataset')
     p.add_argument('-nw', '--num_workers', type=int, default=0)
     p.add_argument('-wm', '--width_mult', type=float, default=1.)
@@ -150,6 +154,20 @@ def patch_options_of(args):
             "tile_margin": tuple(getattr(args, "tile_margin", (8, 8, 8)))}
 
 
+def paste_options_of(args, augmentations):
+    """-> (the augmentation list with --paste_max_volume bound to its lesionpaste entry, whether it names one).
+    lesionpaste with the synthetic data module, or --paste_max_volume without lesionpaste, is an error."""
+    volume = getattr(args, "paste_max_volume", None)
+    pasting = any(n == "lesionpaste" for n, _ in augmentations)
+    if pasting and getattr(args, "data_module", "example") != "lesions":
+        raise ValueError("lesionpaste pastes lesions of clinical training cases: it needs -dm lesions")
+    if volume is not None and not pasting:
+        raise ValueError("--paste_max_volume bounds the lesions lesionpaste copies: name lesionpaste in -a")
+    if volume is not None:
+        augmentations = [(n, dict(kw, max_volume=volume) if n == "lesionpaste" else kw) for n, kw in augmentations]
+    return augmentations, pasting
+
+
 def check_input_channels(model, input_images, checkpoint):
     """A checkpoint's network reads as many channels as it was trained with: refuse another number of sequences."""
     if int(model.input_channels) != len(input_images):
@@ -206,6 +224,7 @@ def example(args):
     scales = {int(k): v for k, v in args.scales.items()}
     augmentations = select_training_augmentations(args.augmentations)  # train.py:132-145, :196-205, + the warps
     lesions = getattr(args, "data_module", "example") == "lesions"
+    augmentations, pasting = paste_options_of(args, augmentations)
     if lesions:
         dataset = LesionsDataModule(data_dir=args.dataset_path, centers=tuple(args.centers), subject=args.subject,
                                     input_images=input_images, segmentation=segmentation,
@@ -283,7 +302,11 @@ def example(args):
         dataset.set_epoch(epoch)
         # training metrics (ssd3d.py:497-515): detection + mAP on every step's own forward outputs, on the device
         train_metrics = epoch % (2 * max(int(model.compute_metric_every_n_epochs), 1)) == 0
+        pastes = [0, 0]  # lesionpaste on the host route: rows tested / accepted in this rank's samples of the epoch
         for batch in (cache.train_batches(epoch) if cache else dataset.train_dataloader()):
+            if pasting and not cache:
+                flat = [v for report in batch["paste_report"] for v in report]
+                pastes = [pastes[0] + sum(v > -2 for v in flat), pastes[1] + sum(v >= 0 for v in flat)]
             stats = ghist.before_step(trainer, model.global_step, epoch) if ghist is not None else False
             if cache:
                 out = cache.step(trainer, batch, metrics=train_metrics, stats=stats)
@@ -303,6 +326,12 @@ def example(args):
             # Lightning steps a scheduler returned by configure_optimizers once per epoch (interval="epoch") on top of
             # the manual per-step call inside training_step: one extra cosine step per epoch
             trainer.sch.step()
+        if pasting:  # the device route keeps its counters in HBM: one read per epoch
+            asked, accepted = cache.paste_counts() if cache else pastes
+            if log is not None:
+                log.write(json.dumps({"step": model.global_step, "epoch": epoch, "lesionpaste/asked": asked,
+                                      "lesionpaste/accepted": accepted}) + "\n")
+                print(f"epoch {epoch}: lesionpaste accepted {accepted} of {asked} pastes")
         if train_metrics:
             # training_epoch_end (ssd3d.py:657-690): epoch means of the per-step values, summed over every rank's steps
             # (the vector length depends on the epoch alone, so every rank joins the same all-reduce)

@@ -445,6 +445,26 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
                             const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
                             size_t workspace_bytes, float* out, void* stream);
 
+/* ---- the same with ignored ground truth.  gt_ignore (G) u8 on the device, or NULL: a non-zero
+ * byte on a class-1 box makes it "ignored" (a byte on a box of another label has no effect).  An ignored box takes part
+ * in a detection's first-maximum-IoU pick like every class-1 box; a detection whose pick is ignored and has IoU > thr is
+ * ABSORBED: neither true nor false positive, and it claims nothing (any number may be absorbed by one box).  n_true_boxes
+ * counts the class-1 boxes that are not ignored, false negatives are the unclaimed ones among them, and at a score cut
+ * FP = K_c - TP - absorbed.  The claim entry of an ignored box is -2.  absorbed (i32, required with gt_ignore):
+ * (n_iou, n_sc) absorbed detections among the first K_c ranks | (n_iou, D) absorbed flag per rank.  workspace:
+ * _workspace_bytes_ign(...) bytes with gt_ignore (0 for exactly the sizes _workspace_bytes refuses), _workspace_bytes(...)
+ * suffice without.  gt_ignore NULL: the launches and results of msl_evaluate_detections, bit for bit; absorbed, when
+ * given, is zeroed.  The workspace records whether it carries absorbed flags: msl_evaluate_froc and msl_evaluate_strata,
+ * given that workspace WITH ITS FULL SIZE, then leave absorbed detections out of their false positives, and
+ * msl_evaluate_strata leaves ignored boxes out of every bin; the caller passes msl_evaluate_froc the per-image counts of
+ * class-1 boxes that are not ignored. */
+size_t msl_evaluate_workspace_bytes_ign(int D, int N, int G, int n_iou, int n_sc);
+int msl_evaluate_detections_ign(const float* det_rows, const int* det_off, int D, int N, const float* gt_boxes,
+                                const long long* gt_labels, const int* obj_off, int G, const float* iou_thr, int n_iou,
+                                const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
+                                size_t workspace_bytes, float* out, const unsigned char* gt_ignore, int* absorbed,
+                                void* stream);
+
 /* ---- FROC from a completed msl_evaluate_detections call ("FROC"): eval_workspace is that call's workspace,
  * sorted_scores the sorted-scores part of its result buffer, and D, N, G, n_iou its sizes, on the same stream.  The
  * workspace keeps the rank order, the image of every detection, the TP flag per (IoU threshold, rank) and K.

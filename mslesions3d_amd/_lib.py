@@ -133,6 +133,8 @@ _SIGNATURES = {
     "msl_detection_metrics": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P] + [_P] * 7 + [_P]),
     "msl_evaluate_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "msl_evaluate_detections": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _Z, _P, _P]),
+    "msl_evaluate_workspace_bytes_ign": (_Z, [_I, _I, _I, _I, _I]),
+    "msl_evaluate_detections_ign": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _Z, _P, _P, _P, _P]),
     "msl_evaluate_froc": (_I, [_P, _Z, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
     "msl_evaluate_strata": (_I, [_P, _Z, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _Z, _P, _P]),
     "msl_prior_fit_workspace_bytes": (_Z, [_I]),

@@ -19,6 +19,13 @@
 //   sweep   : one workgroup per (IoU, score threshold): K_c by an f64 compare (retrieve_boxes compares Python floats), the
 //             11-point table as range maxima of cprec over [first rank with crec >= r, K_c), AP / precision / recall / F1
 // Integer counts are exact in f32 while they stay below 2^24.
+//
+// Ignored ground truth (msl_evaluate_detections_ign): a class-1 box with its gt_ignore byte set
+// takes part in the best-IoU pick like any other, but a detection that hits it (IoU > thr) is "absorbed": neither TP nor
+// FP, and the box is not claimed.  Absorbed flags live in a plane of their own beside the TP flags (abf, scanned into cab
+// the way tpf is scanned into cum), so the TP scan and everything that reads it keep their arithmetic; every kernel takes
+// the plane as a pointer that is null without flags and then runs the statements it has always run.  hdr[2] records
+// whether the workspace carries the plane, which is how the FROC and strata consumers learn of it.
 #include "detmetrics.hpp"
 #pragma clang fp contract(off)
 
@@ -34,6 +41,7 @@ constexpr int EV_SUMMARY = 8;    // AP, mAP, precision, recall, f1, n_true_boxes
 constexpr int EV_SCAN_ONE = 16384;     // scans up to this length run in one workgroup
 constexpr int EV_MATCH_LDS_G = 16384;  // claim flags of an image with up to this many ground-truth boxes live in LDS
 constexpr int NEVER = 0x7FFFFFFF;      // claim rank of an unclaimed class-1 ground-truth box
+constexpr int IGNORED = -2;            // claim entry of an ignored class-1 box (-1: a box of another label)
 constexpr unsigned KEY_NAN = 0xFFFFFFFEu, KEY_SKIP = 0xFFFFFFFFu;
 
 // first index in [0, n) whose key is >= v (keys ascending)
@@ -79,9 +87,10 @@ __global__ __launch_bounds__(EV_THREADS) void ev_key_kernel(
     const float* __restrict__ det_rows, const int* __restrict__ det_off, int D, int N, const float* __restrict__ gt_boxes,
     const long long* __restrict__ gt_labels, int G, int n_iou, unsigned* __restrict__ key, int* __restrict__ val,
     int* __restrict__ img_of, int* __restrict__ tpf, int* __restrict__ claim, float* __restrict__ gt_vol,
-    int* __restrict__ hdr) {
+    int* __restrict__ hdr, const unsigned char* __restrict__ gt_ignore, int* __restrict__ abf) {
   __shared__ int red[EV_WAVES];
   const int i = blockIdx.x * EV_THREADS + threadIdx.x;
+  if (gt_ignore && i == 0) hdr[2] = 1;  // the workspace carries absorbed flags
   if (i < D) {
     const float s = det_rows[(size_t)i * 8 + 6];
     unsigned k;
@@ -105,13 +114,18 @@ __global__ __launch_bounds__(EV_THREADS) void ev_key_kernel(
     }
     img_of[i] = lo;
     for (int t = 0; t < n_iou; ++t) tpf[(size_t)t * D + i] = 0;
+    if (gt_ignore)
+      for (int t = 0; t < n_iou; ++t) abf[(size_t)t * D + i] = 0;
   }
   int easy = 0;
   if (i < G) {
     const float* b = gt_boxes + (size_t)i * 6;
     gt_vol[i] = (b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);  // utils.py:152-154
-    easy = gt_labels[i] == 1;
-    for (int t = 0; t < n_iou; ++t) claim[(size_t)t * G + i] = easy ? NEVER : -1;
+    const bool c1 = gt_labels[i] == 1;
+    const bool ign = gt_ignore && c1 && gt_ignore[i] != 0;  // a flag on a box of another label has no effect
+    easy = c1 && !ign;
+    const int unclaimed = ign ? IGNORED : c1 ? NEVER : -1;
+    for (int t = 0; t < n_iou; ++t) claim[(size_t)t * G + i] = unclaimed;
   }
   const int cnt = block_sum_int(easy, red);
   if (threadIdx.x == 0 && cnt) atomicAdd(&hdr[0], cnt);  // integer count: order-independent
@@ -273,7 +287,7 @@ __global__ __launch_bounds__(64) void ev_match_kernel(
     const float* __restrict__ det_rows, const int* __restrict__ order, const unsigned* __restrict__ img_key,
     const int* __restrict__ img_rank, int D, int N, const float* __restrict__ gt_boxes,
     const long long* __restrict__ gt_labels, const int* __restrict__ obj_off, int G, const float* __restrict__ iou_thr,
-    int* __restrict__ tpf, int* __restrict__ claim) {
+    int* __restrict__ tpf, int* __restrict__ claim, const unsigned char* __restrict__ gt_ignore, int* __restrict__ abf) {
   __shared__ unsigned char cl[EV_MATCH_LDS_G];
   const int n = blockIdx.x % N, t = blockIdx.x / N, lane = threadIdx.x;
   const int Gtot = min(max(obj_off[N], 0), G);
@@ -297,6 +311,7 @@ __global__ __launch_bounds__(64) void ev_match_kernel(
   }
   int* clg = claim + (size_t)t * G;
   int* tp = tpf + (size_t)t * D;
+  int* ab = gt_ignore ? abf + (size_t)t * D : nullptr;
   for (int pb = p0; pb < p1; pb += 64) {
     const int nb = min(64, p1 - pb);
     int r_l = 0;
@@ -320,10 +335,13 @@ __global__ __launch_bounds__(64) void ev_match_kernel(
         best = msl::pick(best, c);
       }
       best = msl::wave_pick(best);
-      // no class-1 GT in the image -> FP; NaN > thr is false -> FP; a claimed GT -> FP (difficult flags are all False)
+      // no class-1 GT in the image -> FP; NaN > thr is false -> FP; a claimed GT -> FP; an ignored GT (it took part in
+      // the pick like every class-1 box) -> absorbed: flagged at the rank, nothing claimed
       if (lane == 0 && best.g >= 0 && best.v > thr) {
         const bool taken = in_lds ? cl[best.g - lo] != 0 : clg[best.g] != NEVER;
-        if (!taken) {
+        if (ab && gt_ignore[best.g] != 0) {
+          ab[r] = 1;
+        } else if (!taken) {
           if (in_lds) cl[best.g - lo] = 1;
           clg[best.g] = r;
           tp[r] = 1;
@@ -337,11 +355,13 @@ __global__ __launch_bounds__(64) void ev_match_kernel(
 __global__ __launch_bounds__(EV_THREADS) void ev_curve_kernel(const int* __restrict__ tpf, const int* __restrict__ cum,
                                                               int D, const int* __restrict__ hdr, float* __restrict__ cprec,
                                                               float* __restrict__ tp_out, float* __restrict__ tile_max,
-                                                              int ntile) {
+                                                              int ntile, const int* __restrict__ abf,
+                                                              const int* __restrict__ cab, int* __restrict__ ab_out) {
   __shared__ float red[EV_WAVES];
   const int K = hdr[1], t = blockIdx.y;
   const size_t row = (size_t)t * D;
   const int base = cum[row];  // the scan runs over all thresholds' flags at once
+  const int base_ab = abf ? cab[row] : 0;
   float m = 0.f;
   for (int k = 0; k < EV_TILE / EV_THREADS; ++k) {
     const int r = blockIdx.x * EV_TILE + k * EV_THREADS + threadIdx.x;
@@ -351,11 +371,14 @@ __global__ __launch_bounds__(EV_THREADS) void ev_curve_kernel(const int* __restr
     float cp = 0.f;
     if (r < K) {
       const int ctp = cum[row + r] - base + f;
-      const float ctpf = (float)ctp, cfpf = (float)(r + 1 - ctp);
+      int cfp = r + 1 - ctp;
+      if (abf) cfp -= cab[row + r] - base_ab + abf[row + r];  // cfp = ranked, not TP, not absorbed
+      const float ctpf = (float)ctp, cfpf = (float)cfp;
       cp = ctpf / ((ctpf + cfpf) + 1e-10f);  // utils.py: ctp / (ctp + cfp + 1e-10)
       m = fmaxf(m, cp);
     }
     cprec[row + r] = cp;
+    if (abf) ab_out[row + r] = abf[row + r];
   }
   m = block_max(m, red);
   if (threadIdx.x == 0) tile_max[(size_t)t * ntile + blockIdx.x] = m;
@@ -381,7 +404,8 @@ __device__ float range_max(const float* cp, const float* tmax, int a, int b, flo
 __global__ __launch_bounds__(EV_THREADS) void ev_sweep_kernel(
     const float* __restrict__ sorted_scores, const int* __restrict__ tpf, const int* __restrict__ cum,
     const float* __restrict__ cprec, const float* __restrict__ tile_max, int ntile, int D, const int* __restrict__ hdr,
-    const double* __restrict__ score_thr, int n_sc, const float* __restrict__ recall_thr, float* __restrict__ summary) {
+    const double* __restrict__ score_thr, int n_sc, const float* __restrict__ recall_thr, float* __restrict__ summary,
+    const int* __restrict__ abf, const int* __restrict__ cab, int* __restrict__ abs_out) {
   __shared__ int Kc_s, start_s[MT_NREC];
   __shared__ float red[EV_WAVES];
   const int c = blockIdx.x, t = blockIdx.y;
@@ -418,12 +442,14 @@ __global__ __launch_bounds__(EV_THREADS) void ev_sweep_kernel(
   for (int i = 0; i < MT_NREC; ++i) p[i] = range_max(cprec + row, tile_max + (size_t)t * ntile, start_s[i], Kc, red);
   if (threadIdx.x != 0) return;
   float ap = 0.f, precision = 0.f, recall = 0.f, f1 = 0.f;
-  int tpc = 0;
+  int tpc = 0, absc = 0;
   if (Kc > 0) {
     tpc = cum[row + Kc - 1] - base + tpf[row + Kc - 1];
+    if (abf) absc = cab[row + Kc - 1] - cab[row] + abf[row + Kc - 1];
     ap = msl::mean11_pairwise(p);
-    // every TP claims one ground-truth box and every claimed box has one TP: found = TP count
-    const float tps = (float)tpc, fps = (float)(Kc - tpc), fn = (float)(n_easy - tpc);
+    // every TP claims one ground-truth box and every claimed box has one TP: found = TP count.  Ignored boxes are not in
+    // n_easy and are never claimed; an absorbed detection is no false positive
+    const float tps = (float)tpc, fps = (float)(Kc - tpc - absc), fn = (float)(n_easy - tpc);
     recall = tps / (tps + fn);
     precision = tps / (tps + fps);
     f1 = (2.0f * precision * recall) / (precision + recall);
@@ -437,6 +463,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_sweep_kernel(
   out[5] = (float)n_easy;
   out[6] = (float)Kc;
   out[7] = (float)tpc;
+  if (abs_out) abs_out[(size_t)t * n_sc + c] = absc;
 }
 
 // ---- FROC: sensitivity at fixed numbers of false positives per image, for (R1 weight rows) x (IoU thresholds), from the
@@ -466,7 +493,8 @@ __device__ __forceinline__ long long shfl_xor_i64(long long v, int o) {
 __global__ __launch_bounds__(EV_THREADS) void ev_froc_kernel(
     const int* __restrict__ order, const int* __restrict__ img_of, const int* __restrict__ tpf,
     const float* __restrict__ sorted_scores, const int* __restrict__ hdr, int D, int N, const int* __restrict__ gt_count,
-    const int* __restrict__ weights, const long long* __restrict__ rates, int n_rates, long long* __restrict__ out) {
+    const int* __restrict__ weights, const long long* __restrict__ rates, int n_rates, long long* __restrict__ out,
+    const int* __restrict__ abf) {
   __shared__ long long scan_a[EV_WAVES], scan_b[EV_WAVES];
   __shared__ long long lim_s[EV_FROC_MAX_RATES];
   __shared__ long long best_tp_s[EV_WAVES][EV_FROC_MAX_RATES];
@@ -476,6 +504,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_froc_kernel(
   const int K = min(max(hdr[1], 0), D);
   const int* __restrict__ w = weights + (size_t)row * N;
   const int* __restrict__ tp = tpf + (size_t)t * D;
+  const int* __restrict__ ab = (abf && hdr[2] != 0) ? abf + (size_t)t * D : nullptr;  // absorbed: no false positives
 
   // Gw = sum w[n] * g[n], Nw = sum w[n]
   long long gw = 0, nw = 0;
@@ -536,7 +565,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_froc_kernel(
       if (r < K) {
         const long long wi = w[img_of[order[r]]];
         if (tp[r] != 0) a[q] = wi;
-        else b[q] = wi;
+        else if (ab == nullptr || ab[r] == 0) b[q] = wi;
         s[q] = sorted_scores[r];
       }
       sa += a[q];
@@ -672,7 +701,8 @@ __global__ __launch_bounds__(EV_THREADS) void ev_stratify_kernel(
       if (obj_off[mid] <= i) lo = mid;
       else hi = mid;
     }
-    const bool counts = claim0[i] >= 0 && i >= obj_off[lo] && i < obj_off[lo + 1];  // class 1 and inside its image
+    // class 1, not ignored (IGNORED < 0) and inside its image
+    const bool counts = claim0[i] >= 0 && i >= obj_off[lo] && i < obj_off[lo + 1];
     gt_img[i] = lo;
     gt_str[i] = (signed char)(counts ? stratum_of(gt_vol[i], voxels[lo], edges, m) : STRATUM_SKIP);
   }
@@ -699,7 +729,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_strata_count_kernel(
     const int* __restrict__ tpf, const int* __restrict__ claim, const int* __restrict__ hdr, int D, int N, int G,
     const int* __restrict__ rk_img, const signed char* __restrict__ rk_str, const int* __restrict__ gt_img,
     const signed char* __restrict__ gt_str, const int* __restrict__ weights, const long long* __restrict__ cuts, int n_cuts,
-    int S1, long long* __restrict__ out) {
+    int S1, long long* __restrict__ out, const int* __restrict__ abf) {
   __shared__ long long acc[EV_STRATA_MAX_CUTS * EV_STRATA_SLOTS * 2];
   __shared__ long long gws[EV_STRATA_SLOTS], tail[2];
   __shared__ int raw[EV_STRATA_MAX_CUTS], sc[EV_STRATA_MAX_CUTS], pos[EV_STRATA_MAX_CUTS];
@@ -743,6 +773,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_strata_count_kernel(
   }
   // detections: FPw over the ranks below the longest cut; the first threshold also counts the unbinned ones of all K
   const int* __restrict__ tp = tpf + (size_t)t * D;
+  const int* __restrict__ ab = (abf && hdr[2] != 0) ? abf + (size_t)t * D : nullptr;
   long long unb = 0, nw = 0;
   const int end = first ? K : top;
   for (int j = tid; j < end; j += EV_THREADS) {
@@ -750,7 +781,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_strata_count_kernel(
     const long long wi = w[min(max(rk_img[j], 0), N - 1)];
     if (wi == 0 || s == STRATUM_SKIP) continue;
     if (first && s < 0) unb += wi;
-    if (j < top && tp[j] == 0) {
+    if (j < top && tp[j] == 0 && (ab == nullptr || ab[j] == 0)) {
       const int slot = s < 0 ? S1 - 1 : min(s, S1 - 2);
       lds_add_i64(&acc[cuts_upto(sc, n_cuts, j) * cell + slot * 2 + 1], wi);
     }
@@ -786,9 +817,13 @@ __global__ __launch_bounds__(EV_THREADS) void ev_strata_count_kernel(
 // in (keyA, valA) after its four passes), img_of = image of every detection index, tpf = the TP flag per (IoU threshold,
 // rank).  The sorted scores, the claim ranks and the ground-truth volumes live in the caller's result buffer, not here.
 // Nothing reads these after the sweep, so a consumer on the same stream may; the layout below is part of that contract.
+// A call with ignore flags (msl_evaluate_detections_ign, gt_ignore not null) sets hdr[2] = 1 and keeps the absorbed flag
+// per (IoU threshold, rank) in abf and its exclusive scan in cab, both BEHIND the layout of a call without flags
+// (total_ign bytes in all): the consumers compute abf's address from the sizes and read it only when hdr[2] says so.
 struct EvPlan {
   int nblk, ntile, radix2_passes;
   size_t hdr, keyA, keyB, keyC, valA, valB, valC, img_of, hist, sums, tpf, cum, cprec, tile_max, total;
+  size_t abf, cab, total_ign;
 };
 
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -831,6 +866,9 @@ EvPlan ev_plan(int D, int N, int G, int n_iou) {
   p.cprec = take((size_t)n_iou * Dz * 4);
   p.tile_max = take((size_t)n_iou * p.ntile * 4);
   p.total = o;
+  p.abf = take((size_t)n_iou * Dz * 4);
+  p.cab = take((size_t)n_iou * Dz * 4);
+  p.total_ign = o;
   return p;
 }
 
@@ -863,25 +901,19 @@ void ev_radix_sort(unsigned* k0, int* v0, unsigned* k1, int* v1, int n, int pass
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t msl_evaluate_workspace_bytes(int D, int N, int G, int n_iou, int n_sc) {
-  if (!ev_supported(D, N, G, n_iou, n_sc)) return 0;
-  return ev_plan(D, N, G, n_iou).total;
-}
-
-int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, int N, const float* gt_boxes,
-                            const long long* gt_labels, const int* obj_off, int G, const float* iou_thr, int n_iou,
-                            const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
-                            size_t workspace_bytes, float* out, void* stream) {
+// the sweep; gt_ignore null: the launches and the statements of a run without flags.  absorbed (i32): (n_iou, n_sc)
+// absorbed detections among the first K_c ranks | (n_iou, D) absorbed flags in rank order
+int ev_run(const float* det_rows, const int* det_off, int D, int N, const float* gt_boxes, const long long* gt_labels,
+           const int* obj_off, int G, const float* iou_thr, int n_iou, const double* score_thr, int n_sc,
+           const float* recall_thr, void* workspace, size_t workspace_bytes, float* out, const unsigned char* gt_ignore,
+           int* absorbed, void* stream) {
   if (N <= 0 || D < 0 || G < 0 || n_iou <= 0 || n_sc <= 0 || !det_off || !obj_off || !iou_thr || !score_thr ||
-      !recall_thr || !workspace || !out || (D > 0 && !det_rows) || (G > 0 && (!gt_boxes || !gt_labels)))
+      !recall_thr || !workspace || !out || (D > 0 && !det_rows) || (G > 0 && (!gt_boxes || !gt_labels)) ||
+      (gt_ignore && !absorbed))
     return MSL_ERR_ARG;
   if (!ev_supported(D, N, G, n_iou, n_sc)) return MSL_ERR_UNSUPPORTED;
   const EvPlan p = ev_plan(D, N, G, n_iou);
-  if (workspace_bytes < p.total) return MSL_ERR_ARG;
+  if (workspace_bytes < (gt_ignore ? p.total_ign : p.total)) return MSL_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   int* hdr = (int*)(ws + p.hdr);
@@ -900,21 +932,29 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
   float* tp_out = sorted_scores + D;
   int* claim = (int*)(tp_out + (size_t)n_iou * D);
   float* gt_vol = (float*)(claim + (size_t)n_iou * G);
+  // without flags every one of these is null, and a kernel that sees null runs what it ran before flags existed
+  int* abf = gt_ignore ? (int*)(ws + p.abf) : nullptr;
+  int* cab = gt_ignore ? (int*)(ws + p.cab) : nullptr;
+  int* abs_cnt = gt_ignore ? absorbed : nullptr;
+  int* ab_out = gt_ignore ? absorbed + (size_t)n_iou * n_sc : nullptr;
 
   if (hipMemsetAsync(hdr, 0, 64 * sizeof(int), st) != hipSuccess) return (int)hipGetLastError();
+  if (!gt_ignore && absorbed &&
+      hipMemsetAsync(absorbed, 0, ((size_t)n_iou * n_sc + (size_t)n_iou * D) * sizeof(int), st) != hipSuccess)
+    return (int)hipGetLastError();
   if (D == 0) {  // nothing detected anywhere: only the ground-truth bookkeeping and the K_c == 0 summaries
     MSL_LAUNCH(ev_key_kernel, dim3(msl::cdiv(G > 0 ? G : 1, EV_THREADS)), dim3(EV_THREADS), 0, st, det_rows, det_off, 0,
-               N, gt_boxes, gt_labels, G, n_iou, kA, vA, img_of, tpf, claim, gt_vol, hdr);
+               N, gt_boxes, gt_labels, G, n_iou, kA, vA, img_of, tpf, claim, gt_vol, hdr, gt_ignore, abf);
     const float* zs = cprec;  // never read: K = 0
     MSL_LAUNCH(ev_sweep_kernel, dim3(n_sc, n_iou), dim3(EV_THREADS), 0, st, (const float*)sorted_scores, (const int*)tpf,
                (const int*)cum, zs, (const float*)tile_max, p.ntile, 1, (const int*)hdr, score_thr, n_sc, recall_thr,
-               summary);
+               summary, (const int*)abf, (const int*)cab, abs_cnt);
     MSL_LAUNCH_CHECK();
     return MSL_OK;
   }
   const int nthreads = D > G ? D : G;
   MSL_LAUNCH(ev_key_kernel, dim3(msl::cdiv(nthreads, EV_THREADS)), dim3(EV_THREADS), 0, st, det_rows, det_off, D, N,
-             gt_boxes, gt_labels, G, n_iou, kA, vA, img_of, tpf, claim, gt_vol, hdr);
+             gt_boxes, gt_labels, G, n_iou, kA, vA, img_of, tpf, claim, gt_vol, hdr, gt_ignore, abf);
   // global rank: 4 passes, the order ends in (kA, vA)
   ev_radix_sort(kA, vA, kB, vB, D, 4, p.nblk, hist, sums, st);
   MSL_LAUNCH(ev_rank_kernel, dim3(msl::cdiv(D, EV_THREADS)), dim3(EV_THREADS), 0, st, (const unsigned*)kA,
@@ -924,16 +964,48 @@ int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, in
   const unsigned* img_key = (p.radix2_passes % 2) ? kC : kB;
   const int* img_rank = (p.radix2_passes % 2) ? vC : vB;
   MSL_LAUNCH(ev_match_kernel, dim3(N * n_iou), dim3(64), 0, st, det_rows, (const int*)vA, img_key, img_rank, D, N,
-             gt_boxes, gt_labels, obj_off, G, iou_thr, tpf, claim);
+             gt_boxes, gt_labels, obj_off, G, iou_thr, tpf, claim, gt_ignore, abf);
   // cumulative TP counts of every threshold (one scan over all of them: each row subtracts its first entry)
   ev_scan(tpf, cum, n_iou * D, sums, st);
+  if (gt_ignore) ev_scan(abf, cab, n_iou * D, sums, st);  // the same for the absorbed flags: the only added launches
   MSL_LAUNCH(ev_curve_kernel, dim3(p.ntile, n_iou), dim3(EV_THREADS), 0, st, (const int*)tpf, (const int*)cum, D,
-             (const int*)hdr, cprec, tp_out, tile_max, p.ntile);
+             (const int*)hdr, cprec, tp_out, tile_max, p.ntile, (const int*)abf, (const int*)cab, ab_out);
   MSL_LAUNCH(ev_sweep_kernel, dim3(n_sc, n_iou), dim3(EV_THREADS), 0, st, (const float*)sorted_scores, (const int*)tpf,
              (const int*)cum, (const float*)cprec, (const float*)tile_max, p.ntile, D, (const int*)hdr, score_thr, n_sc,
-             recall_thr, summary);
+             recall_thr, summary, (const int*)abf, (const int*)cab, abs_cnt);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t msl_evaluate_workspace_bytes(int D, int N, int G, int n_iou, int n_sc) {
+  if (!ev_supported(D, N, G, n_iou, n_sc)) return 0;
+  return ev_plan(D, N, G, n_iou).total;
+}
+
+size_t msl_evaluate_workspace_bytes_ign(int D, int N, int G, int n_iou, int n_sc) {
+  if (!ev_supported(D, N, G, n_iou, n_sc)) return 0;
+  return ev_plan(D, N, G, n_iou).total_ign;
+}
+
+int msl_evaluate_detections(const float* det_rows, const int* det_off, int D, int N, const float* gt_boxes,
+                            const long long* gt_labels, const int* obj_off, int G, const float* iou_thr, int n_iou,
+                            const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
+                            size_t workspace_bytes, float* out, void* stream) {
+  return ev_run(det_rows, det_off, D, N, gt_boxes, gt_labels, obj_off, G, iou_thr, n_iou, score_thr, n_sc, recall_thr,
+                workspace, workspace_bytes, out, nullptr, nullptr, stream);
+}
+
+int msl_evaluate_detections_ign(const float* det_rows, const int* det_off, int D, int N, const float* gt_boxes,
+                                const long long* gt_labels, const int* obj_off, int G, const float* iou_thr, int n_iou,
+                                const double* score_thr, int n_sc, const float* recall_thr, void* workspace,
+                                size_t workspace_bytes, float* out, const unsigned char* gt_ignore, int* absorbed,
+                                void* stream) {
+  return ev_run(det_rows, det_off, D, N, gt_boxes, gt_labels, obj_off, G, iou_thr, n_iou, score_thr, n_sc, recall_thr,
+                workspace, workspace_bytes, out, gt_ignore, absorbed, stream);
 }
 
 int msl_evaluate_froc(const void* eval_workspace, size_t eval_workspace_bytes, const float* sorted_scores, int D, int N,
@@ -948,7 +1020,7 @@ int msl_evaluate_froc(const void* eval_workspace, size_t eval_workspace_bytes, c
   const char* ws = (const char*)eval_workspace;
   MSL_LAUNCH(ev_froc_kernel, dim3(R1, n_iou), dim3(EV_THREADS), 0, (hipStream_t)stream, (const int*)(ws + p.valA),
              (const int*)(ws + p.img_of), (const int*)(ws + p.tpf), sorted_scores, (const int*)(ws + p.hdr), D, N, gt_count,
-             weights, rates, n_rates, out);
+             weights, rates, n_rates, out, eval_workspace_bytes >= p.total_ign ? (const int*)(ws + p.abf) : nullptr);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }
@@ -982,7 +1054,7 @@ int msl_evaluate_strata(const void* eval_workspace, size_t eval_workspace_bytes,
                n_edges, rk_img, rk_str, gt_img, gt_str);
   MSL_LAUNCH(ev_strata_count_kernel, dim3(R1, n_iou), dim3(EV_THREADS), 0, st, (const int*)(ws + p.tpf), claim, hdr, D, N, G,
              (const int*)rk_img, (const signed char*)rk_str, (const int*)gt_img, (const signed char*)gt_str, weights, cuts,
-             n_cuts, n_edges + 2, out);
+             n_cuts, n_edges + 2, out, eval_workspace_bytes >= p.total_ign ? (const int*)(ws + p.abf) : nullptr);
   MSL_LAUNCH_CHECK();
   return MSL_OK;
 }

@@ -19,6 +19,14 @@ positives per case, their mean CPM, ``--bootstrap R`` resamples of the cases for
 adds ``strata_(min_IoU=<iou>).json`` per ``-iou``: lesions, sensitivity and false positives per case in every size bin, at
 each ``-sc`` threshold and, with ``--froc``, at each FROC rate, with ``--bootstrap`` intervals (DESIGN.md "Eval by lesion
 size").
+
+``--ignore_below V`` scores the way lesion-detection studies do: a ground-truth lesion whose size
+(what ``--size_bins`` measures: f32 bounding-box volume times the voxels of its image) is below ``V`` is neither hit nor
+miss - missing it is no false negative, a detection on it no false positive.  It applies to the grid, ``--froc``,
+``--bootstrap`` and ``--size_bins`` (a bin wholly below ``V`` is reported empty); every output file gains an ``"ignored"``
+block.  Without the flag the files are what they have always been.
+
+    python -m mslesions3d_amd.eval -dm lesions -d RAW -pd PREDICTIONS --froc --size_bins 27,125,1000 --ignore_below 3
 """
 import argparse
 import json
@@ -66,6 +74,9 @@ def build_parser():
     p.add_argument('--size_bins', type=size_bin_list, default=S,
                    help="also write strata_(min_IoU=<iou>).json: sensitivity and false positives per case by lesion size; "
                         "comma-separated ascending bounding-box volumes in voxels, e.g. 27,125,1000")
+    p.add_argument('--ignore_below', type=ignore_size, default=S, metavar='V',
+                   help="ground-truth lesions smaller than V (bounding-box volume in voxels, as --size_bins) are neither "
+                        "hit nor miss; every output file gains an \"ignored\" block")
     p.add_argument('-dm', '--data_module', choices=["example", "lesions"], default=S,
                    help="lesions: the clinical data module, -d is its data_dir (default: example)")
     p.add_argument('--centers', type=str, nargs='+', default=S, help="as predict.py (default: CHUV_RIM_OK BASEL_INSIDER_OK)")
@@ -100,7 +111,19 @@ def size_bin_list(text):
     return vals
 
 
-EVAL_DEFAULTS = {"size_bins": None, "froc": False, "froc_rates": None, "bootstrap": 0, "bootstrap_seed": 0, "data_module": "example",
+def ignore_size(text):
+    """``3`` -> 3.0: one finite size > 0."""
+    import math
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a number, got {text!r}")
+    if not math.isfinite(v) or v <= 0:
+        raise argparse.ArgumentTypeError(f"expected a finite size > 0, got {text!r}")
+    return v
+
+
+EVAL_DEFAULTS = {"ignore_below": None, "size_bins": None, "froc": False, "froc_rates": None, "bootstrap": 0, "bootstrap_seed": 0, "data_module": "example",
                  "centers": ('CHUV_RIM_OK', 'BASEL_INSIDER_OK'), "spatial_size": (250, 300, 300), "input_images": ("FLAIR",),
                  "segmentation": "labeled_lesions"}
 
@@ -261,6 +284,38 @@ def strata_json(summary):
     return conv(summary)
 
 
+def ignored_block(below, true_ignore, absorbed):
+    """The ``"ignored"`` block of an output file: the threshold, the number of ignored lesions (flags on class-1 boxes are
+    the only ones that count, and ``gather`` hands over class-1 boxes only where it matters: the count is of set flags), and
+    the absorbed detections - one number for a grid point, a list (one per rate / cut) otherwise."""
+    return {"below": float(below), "n_ignored": int(sum(int(f.sum()) for f in true_ignore)),
+            "absorbed": [int(v) for v in absorbed] if isinstance(absorbed, (list, tuple)) else int(absorbed)}
+
+
+def with_ignored(d, below, true_ignore):
+    """The JSON dict of an output file under ``--ignore_below``: its ``absorbed`` entry (what ``true_ignore`` added to the
+    summary: a tensor / list per rank for a grid point, a list per rate / cut otherwise) becomes the ``"ignored"`` block.
+    Without the flag (``true_ignore`` None) ``d`` is returned as it is."""
+    if true_ignore is None:
+        return d
+    ab = d.pop("absorbed")
+    if "TP" in d:  # a grid point: convert_metrics made a number of a one-element vector, a list of any other
+        ab = int(sum(ab)) if isinstance(ab, list) else int(ab)
+    d["ignored"] = ignored_block(below, true_ignore, ab)
+    return d
+
+
+def lesion_ignore_flags(gt_boxes, gt_labels, frames, below):
+    """``--ignore_below``: per image, the class-1 boxes whose size is below ``below`` (``utils.ignore_below``; a flag is
+    only set on a class-1 box, so the count of set flags is the count of ignored lesions).  ``below`` None -> None."""
+    if below is None:
+        return None
+    import numpy as np
+    from .utils import _np, ignore_below
+    flags = ignore_below(gt_boxes, frames, below)
+    return [f & (_np(l, np.int64).reshape(-1) == 1) for f, l in zip(flags, gt_labels)]
+
+
 def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_workers=8, predict_subset="train",
              n_classes=1, percentage=1., confidence_threshold=0.5, min_iou=0.5, options=None):
     """eval.py:61-151 for every (min_iou, confidence_threshold) pair of the given values (a number or a list each).
@@ -298,13 +353,16 @@ def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_wo
     if opt.froc:
         from .utils import evaluate_froc
         # every prediction in the files counts (NaN scores fail the compare and stay out)
-        det_b, det_l, det_s, gt_b, gt_l = gather(float("-inf"), log=lambda *_: None)
+        voxels = []
+        det_b, det_l, det_s, gt_b, gt_l = gather(float("-inf"), log=lambda *_: None,
+                                                 frames=voxels if opt.ignore_below is not None else None)
         if not gt_l:
             raise RuntimeError("FROC: no case with a prediction file")
+        ign = lesion_ignore_flags(gt_b, gt_l, voxels, opt.ignore_below)
         froc = evaluate_froc(det_b, det_l, det_s, gt_b, gt_l, min_overlaps=ious, fp_rates=opt.froc_rates,
-                             n_boot=opt.bootstrap, seed=opt.bootstrap_seed)
+                             n_boot=opt.bootstrap, seed=opt.bootstrap_seed, **({} if ign is None else {"true_ignore": ign}))
         for iou in ious:
-            d = froc_json(froc[iou])
+            d = with_ignored(froc_json(froc[iou]), opt.ignore_below, ign)
             print(f"\nFROC for IoU = {iou}: CPM {d['cpm']}  sensitivity {d['sensitivity']} at {d['rates']} FP / case")
             with open(pjoin(prediction_dir, froc_file_name(iou)), "w") as json_file:
                 json.dump(d, json_file, indent=4)
@@ -315,10 +373,12 @@ def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_wo
         det_b, det_l, det_s, gt_b, gt_l = gather(float("-inf"), log=lambda *_: None, frames=voxels)
         if not gt_l:
             raise RuntimeError("size bins: no case with a prediction file")
+        ign = lesion_ignore_flags(gt_b, gt_l, voxels, opt.ignore_below)
         strata = evaluate_strata(det_b, det_l, det_s, gt_b, gt_l, voxels, opt.size_bins, min_overlaps=ious, min_scores=scores,
-                                 fp_rates=opt.froc_rates if opt.froc else None, n_boot=opt.bootstrap, seed=opt.bootstrap_seed)
+                                 fp_rates=opt.froc_rates if opt.froc else None, n_boot=opt.bootstrap, seed=opt.bootstrap_seed,
+                                 **({} if ign is None else {"true_ignore": ign}))
         for iou in ious:
-            d = strata_json(strata[iou])
+            d = with_ignored(strata_json(strata[iou]), opt.ignore_below, ign)
             print(f"\nLesions by size for IoU = {iou}: edges {d['edges']} lesions {d['n_lesions']}")
             for cut in d["cuts"]:
                 at = f"min score {cut['min_score']}" if "min_score" in cut else f"{cut['fp_rate']} FP / case"
@@ -327,11 +387,13 @@ def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_wo
                 json.dump(d, json_file, indent=4)
 
     with torch.no_grad():
-        det_b, det_l, det_s, gt_b, gt_l = gather(min(scores))
+        voxels = []
+        det_b, det_l, det_s, gt_b, gt_l = gather(min(scores), frames=voxels if opt.ignore_below is not None else None)
         dif = [torch.zeros(len(l), dtype=torch.bool) for l in gt_l]
+        ign = lesion_ignore_flags(gt_b, gt_l, voxels, opt.ignore_below)
         print("\n+-+-+- Computing metrics! +-+-+-+")
         grid = evaluate_detections(det_b, det_l, det_s, gt_b, gt_l, dif, min_overlaps=ious, min_scores=scores,
-                                   return_detail=True)
+                                   return_detail=True, **({} if ign is None else {"true_ignore": ign}))
     for iou in ious:
         for sc in scores:
             metrics = grid[(iou, sc)]
@@ -341,7 +403,7 @@ def evaluate(prediction_dir, dataset_path, model_name, dataset_name=None, num_wo
             print("recall: ", metrics["recall"])
             print("f1_score: ", metrics["f1_score"])
             print()
-            metrx = convert_metrics(metrics)
+            metrx = with_ignored(convert_metrics(metrics), opt.ignore_below, ign)
             print(metrx)
             with open(pjoin(prediction_dir, metrics_file_name(iou, sc)), "w") as json_file:
                 json.dump(metrx, json_file, indent=4)

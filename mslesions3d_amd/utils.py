@@ -142,7 +142,14 @@ def compute_metrics_per_class(det_class_images, det_class_boxes, det_class_score
 def calculate_mAP(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_difficulties, min_overlap=0.5,
                   return_detail=False):
     """utils.py:242-396.  Inputs: lists (one entry per image) of tensors (any device) or arrays.
-    Returns ``(APs, mAP)`` or, with ``return_detail``, the reference's detail dict (torch CPU tensors / floats)."""
+    Returns ``(APs, mAP)`` or, with ``return_detail``, the reference's detail dict (torch CPU tensors / floats).
+
+    This is the literal mirror of the reference, 'difficult' flags included, and the device paths do not reproduce those
+    flags' semantics because the reference's are broken twice: utils.py:230-233 indexes a volume vector that has the
+    difficult boxes removed with a mask that still has them (IndexError as soon as a flag is set - the mirror above keeps
+    the mask consistent instead), and utils.py:323-324 still counts difficult boxes as false negatives in ``recall``.
+    Ground truth that must not count is expressed with ``true_ignore`` of ``evaluate_detections`` / ``evaluate_froc`` /
+    ``evaluate_strata``, whose semantics are defined there, not copied from the reference."""
     assert len(det_boxes) == len(det_labels) == len(det_scores) == len(true_boxes) == len(true_labels) == len(true_difficulties)
     n_classes = len(label_map)
     n_img = len(true_labels)
@@ -295,7 +302,8 @@ def calculate_mAP_device(det_boxes, det_labels, det_scores, true_boxes, true_lab
     from .ssd3d import MultiBoxLoss
     assert len(det_boxes) == len(det_labels) == len(det_scores) == len(true_boxes) == len(true_labels) == len(true_difficulties)
     if any(bool(torch.as_tensor(d).bool().any()) for d in true_difficulties):
-        raise NotImplementedError("calculate_mAP_device: 'difficult' ground-truth boxes are not supported")
+        raise NotImplementedError("calculate_mAP_device: 'difficult' ground-truth boxes are not supported (ground truth "
+                                  "that must not be scored: true_ignore of evaluate_detections, DESIGN.md section 4.6d)")
     N = len(true_labels)
     dev = next((t.device for t in list(det_boxes) + list(true_boxes) if torch.is_tensor(t) and t.is_cuda), None)
     if dev is None:
@@ -329,26 +337,58 @@ def _host(x, dtype):
     return torch.as_tensor(x).detach().to(device="cpu", dtype=dtype)
 
 
-def evaluate_capacity_check(D, N, G, n_iou, n_sc):
+def evaluate_capacity_check(D, N, G, n_iou, n_sc, ignore=False):
     """Host planning of ``msl_evaluate_detections``: its workspace size in bytes, or HipKernelError for sizes it cannot
-    index (the limits are int32 indexing and memory; there is no fixed cap)."""
+    index (the limits are int32 indexing and memory; there is no fixed cap).  ``ignore``: the size
+    ``msl_evaluate_detections_ign`` takes with ignore flags."""
     if N <= 0 or n_iou <= 0 or n_sc <= 0:
         raise _lib.HipKernelError(f"evaluate_detections: {N} images, {n_iou} IoU thresholds, {n_sc} score thresholds")
-    ws = _lib.load().msl_evaluate_workspace_bytes(D, N, G, n_iou, n_sc)
+    lib = _lib.load()
+    ws = (lib.msl_evaluate_workspace_bytes_ign if ignore else lib.msl_evaluate_workspace_bytes)(D, N, G, n_iou, n_sc)
     if ws == 0:
         raise _lib.HipKernelError(f"evaluate_detections: {D} detections, {N} images, {G} ground-truth boxes x {n_iou} IoU "
                                   f"thresholds x {n_sc} score thresholds exceed int32 indexing")
     return ws
 
 
-def prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores):
+def ignore_flags(true_ignore, true_labels):
+    """``true_ignore`` (None, or one bool tensor / array per image, aligned with ``true_boxes``) -> None, or a list of
+    (n_i,) bool arrays.  A list of another length, or an entry whose length is not its image's number of boxes:
+    ValueError (before anything is packed or launched)."""
+    if true_ignore is None:
+        return None
+    if len(true_ignore) != len(true_labels):
+        raise ValueError(f"true_ignore: {len(true_ignore)} entries for {len(true_labels)} images")
+    out = []
+    for i, (f, l) in enumerate(zip(true_ignore, true_labels)):
+        f = _np(f).astype(bool).reshape(-1)
+        n = int(_np(l).reshape(-1).shape[0])
+        if f.shape[0] != n:
+            raise ValueError(f"true_ignore: image {i} has {f.shape[0]} flags for {n} ground-truth boxes")
+        out.append(f)
+    return out
+
+
+def ignore_below(true_boxes, voxels, min_size):
+    """The flags ``eval.py --ignore_below`` sets: per image, ``size < min_size`` with the size ``evaluate_strata`` bins by
+    (the f32 bounding-box volume times the image's voxel count, one f64 multiply).  A NaN size is not below anything."""
+    vox = _strata_voxels(voxels, len(true_boxes))
+    with np.errstate(invalid="ignore"):
+        return [_volume_f32(_np(b, np.float32)).astype(np.float64) * vox[i] < float(min_size) for i, b in enumerate(true_boxes)]
+
+
+def prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores,
+                       true_ignore=None):
     """Pack one evaluation for ``msl_evaluate_detections``: the detections into one host buffer with one host-to-device
     copy, the ground truth with ``MultiBoxLoss.pack_targets``, the workspace and the result buffer allocated.  Returns a
     dict with ``launch()`` (enqueue the whole pipeline on the current stream, no synchronisation), ``out`` (the device
-    result buffer) and the sizes."""
+    result buffer) and the sizes.  With ``true_ignore`` (see ``ignore_flags``) the call is
+    ``msl_evaluate_detections_ign`` on its larger workspace, and the dict also has ``absorbed`` (device int32: (n_iou, n_sc)
+    absorbed counts | (n_iou, D) absorbed flags in rank order); ``None`` is the path without flags, unchanged."""
     from .ssd3d import MultiBoxLoss
     ious, scs = list(min_overlaps), list(min_scores)
     N, n_iou, n_sc = len(true_labels), len(ious), len(scs)
+    ign = ignore_flags(true_ignore, true_labels)
     dev = next((t.device for t in [*det_boxes, *det_scores, *true_boxes] if torch.is_tensor(t) and t.is_cuda), None)
     if dev is None:
         if not torch.cuda.is_available():
@@ -362,7 +402,7 @@ def prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_label
     D = sum(counts)
     gb, gl, goff, G = MultiBoxLoss.pack_targets([_host(b, torch.float32).reshape(-1, 6) for b in true_boxes],
                                                 [_host(l, torch.int64).reshape(-1) for l in true_labels], dev)
-    ws_bytes = evaluate_capacity_check(D, N, G, n_iou, n_sc)
+    ws_bytes = evaluate_capacity_check(D, N, G, n_iou, n_sc, ignore=ign is not None)
     # one host buffer, one copy: detection rows (D,8) [box, score, label as f32] | det_off (N+1) i32 | IoU thresholds f32 |
     # (8-byte aligned) score thresholds f64
     det_off = np.zeros(N + 1, dtype=np.int32)
@@ -381,19 +421,28 @@ def prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_label
     args = (base, base + 4 * o_off, D, N, ptr(gb), ptr(gl), ptr(goff), G, base + 4 * o_iou, n_iou, base + 4 * o_sc, n_sc,
             ptr(recall), ptr(ws), ws_bytes, ptr(out))
 
+    absorbed = gi = None
+    if ign is not None:
+        flat = np.concatenate(ign + [np.zeros(0, bool)]).astype(np.uint8)
+        gi = torch.from_numpy(flat if G else np.zeros(1, np.uint8)).to(dev)
+        absorbed = torch.empty(n_iou * n_sc + n_iou * D, dtype=torch.int32, device=dev)
+
     def launch():
-        _lib.call("msl_evaluate_detections", *args, _stream())
+        if ign is None:
+            _lib.call("msl_evaluate_detections", *args, _stream())
+        else:
+            _lib.call("msl_evaluate_detections_ign", *args, ptr(gi), ptr(absorbed), _stream())
 
     # "ws" / "ws_bytes" / "sorted_scores": what msl_evaluate_froc consumes after launch() on the same stream;
     # msl_evaluate_strata also reads "det_rows" and "obj_off" (device addresses of this call's inputs)
     return {"launch": launch, "out": out, "D": D, "N": N, "G": G, "ious": ious, "scores": scs,
             "ws": ws, "ws_bytes": ws_bytes, "sorted_scores": out[n_iou * n_sc * METRIC_SUMMARY:n_iou * n_sc * METRIC_SUMMARY + D],
-            "det_rows": base, "obj_off": ptr(goff),
-            "keep": (packed, ws, gb, gl, goff, recall)}
+            "det_rows": base, "obj_off": ptr(goff), "absorbed": absorbed, "args": args, "gt_ignore": gi,
+            "keep": (packed, ws, gb, gl, goff, recall, gi)}
 
 
 def evaluate_detections(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_difficulties,
-                        min_overlaps=(0.5,), min_scores=(0.0,), return_detail=False):
+                        min_overlaps=(0.5,), min_scores=(0.0,), return_detail=False, true_ignore=None):
     """The grid of the reference's eval.py on the HIP device: ``{(min_overlap, min_score): calculate_mAP(<the detections
     with score >= min_score>, ..., min_overlap=min_overlap, return_detail=return_detail)}``, bit for bit, NaNs included.
     A detection is kept iff ``float(score) >= float(min_score)`` (f64, as eval.py's retrieve_boxes compares).
@@ -401,11 +450,19 @@ def evaluate_detections(det_boxes, det_labels, det_scores, true_boxes, true_labe
     Inputs: lists (one entry per image) of tensors on any device, or arrays.  The detections are packed on the host and
     copied to the device once; the ground truth is packed by ``MultiBoxLoss.pack_targets``; every grid point comes from
     one enqueue of ``msl_evaluate_detections`` and one device-to-host copy.  No cap on detections or ground truth.
-    'difficult' ground truth is not supported."""
+    'difficult' ground truth is not supported.
+
+    ``true_ignore`` (one bool tensor / array per image, aligned with ``true_boxes``): a class-1 box
+    with its flag set is neither hit nor miss.  A detection whose first-maximum-IoU box is ignored and has IoU >
+    min_overlap is absorbed (neither TP nor FP, nothing claimed); ``n_true_boxes``, recall and the found / not-found volumes
+    cover the other boxes only.  The detail dict then gains ``n_ignored_boxes`` and ``absorbed`` (per rank, beside ``TP``
+    and ``FP``), at the price of a second device-to-host copy.  ``None``: the path above, unchanged."""
     assert len(det_boxes) == len(det_labels) == len(det_scores) == len(true_boxes) == len(true_labels) == len(true_difficulties)
     if any(bool(torch.as_tensor(d).bool().any()) for d in true_difficulties):
-        raise NotImplementedError("evaluate_detections: 'difficult' ground-truth boxes are not supported")
-    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores)
+        raise NotImplementedError("evaluate_detections: 'difficult' ground-truth boxes are not supported (ground truth "
+                                  "that must not be scored: the true_ignore keyword, DESIGN.md section 4.6d)")
+    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores,
+                              true_ignore=true_ignore)
     plan["launch"]()
     ious, scs, D, G = plan["ious"], plan["scores"], plan["D"], plan["G"]
     n_iou, n_sc = len(ious), len(scs)
@@ -419,13 +476,23 @@ def evaluate_detections(det_boxes, det_labels, det_scores, true_boxes, true_labe
     tp = host[n_sum + D:n_sum + D + n_iou * D].reshape(n_iou, D)
     claim = host[n_sum + D + n_iou * D:n_sum + D + n_iou * (D + G)].view(np.int32).reshape(n_iou, G)
     vol = host[n_sum + D + n_iou * (D + G):]
+    ab = n_ign = None
+    if plan["absorbed"] is not None:
+        ab = plan["absorbed"].cpu().numpy()[n_iou * n_sc:].reshape(n_iou, D).astype(np.float32)
+        n_ign = int((claim[0] == _IGNORED).sum()) if n_iou else 0
     res = {}
     for t in range(n_iou):
-        fp = np.float32(1) - tp[t]
+        fp = np.float32(1) - tp[t] if ab is None else np.float32(1) - tp[t] - ab[t]
         for c in range(n_sc):
             K = int(summary[t, c, 6])
-            status = np.where(claim[t] < 0, 2, np.where(claim[t] < K, 1, 0))
-            res[(ious[t], scs[c])] = _detail_dict(summary[t, c], sorted_scores, tp[t], fp, vol, status)
+            status = np.where(claim[t] < 0, 2, np.where(claim[t] < K, 1, 0))  # ignored boxes (-2) are in neither volume list
+            d = _detail_dict(summary[t, c], sorted_scores, tp[t], fp, vol, status)
+            if ab is not None:
+                d["n_ignored_boxes"] = n_ign
+                d["absorbed"] = torch.from_numpy(np.ascontiguousarray(ab[t, :K])) if K else torch.zeros(0)
+                if K == 0:  # nothing detected: "not found" lists every volume but the ignored boxes'
+                    d["not_found_boxes_volumes_per_class"] = torch.from_numpy(np.ascontiguousarray(vol[claim[t] != _IGNORED]))
+            res[(ious[t], scs[c])] = d
     return res
 
 
@@ -477,10 +544,12 @@ def _froc_weights(weights, N, n_boot, seed):
     return np.ascontiguousarray(w, dtype=np.int32)
 
 
-def _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels):
+def _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_ignore=None):
     """The class-1 detections and ground truth as calculate_mAP concatenates them, the per-image ground-truth counts and
-    the scores in rank order (compute_metrics_per_class's lexsort).  NaN scores: ValueError."""
+    the scores in rank order (compute_metrics_per_class's lexsort).  NaN scores: ValueError.  With ``true_ignore``:
+    ``t_ign`` (the flag of every class-1 box) and ``g`` counting the boxes that are not ignored; else ``t_ign`` is None."""
     n_img = len(true_labels)
+    ign = ignore_flags(true_ignore, true_labels)
     assert len(det_boxes) == len(det_labels) == len(det_scores) == len(true_boxes) == n_img > 0
     t_lab = [_np(l, np.int64).reshape(-1) for l in true_labels]
     d_lab = [_np(l, np.int64).reshape(-1) for l in det_labels]
@@ -494,15 +563,46 @@ def _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels):
     if np.isnan(d_sco).any():
         raise ValueError("FROC: NaN detection scores")
     order = np.lexsort((np.arange(d_sco.shape[0]), -d_sco.astype(np.float64)))
+    t_ign = None if ign is None else np.concatenate(ign + [np.zeros(0, bool)])[ts]
+    counted = t_img[ts] if t_ign is None else t_img[ts][~t_ign]
     return {"d_img": d_img, "d_box": d_box, "d_sco": d_sco, "t_img": t_img[ts], "t_box": t_box[ts], "order": order,
-            "g": np.bincount(t_img[ts], minlength=n_img).astype(np.int64), "N": n_img}
+            "g": np.bincount(counted, minlength=n_img).astype(np.int64), "N": n_img, "t_ign": t_ign}
 
 
-def froc_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, fp_rates, weights):
+def match_with_ignore(c, min_overlap):
+    """The matching of DESIGN.md section 4.6d on the class-1 sets of ``_froc_class1`` (``t_ign`` given): detections in rank
+    order; the candidate is the first-maximum-IoU box of the image over ALL its class-1 boxes; IoU > f32(min_overlap) and
+    the candidate ignored: absorbed (nothing claimed); not ignored: TP if unclaimed (it claims the box), else FP; anything
+    else FP.  -> (tp (K,), absorbed (K,), claim (class-1 boxes,): rank, _NEVER, or _IGNORED), int64."""
+    order, t_img, t_box, t_ign = c["order"], c["t_img"], c["t_box"], c["t_ign"]
+    img, box = c["d_img"][order], c["d_box"][order]
+    K, thr = order.shape[0], np.float32(min_overlap)
+    tp, ab = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+    claim = np.where(t_ign, _IGNORED, _NEVER).astype(np.int64)
+    for j in range(K):
+        same = np.nonzero(t_img == img[j])[0]
+        if same.size == 0:
+            continue
+        ov = _iou_one_to_many(box[j], t_box[same])
+        ind = int(np.argmax(ov))  # first maximum; a NaN wins and then fails the compare
+        if not ov[ind] > thr:
+            continue
+        g = same[ind]
+        if t_ign[g]:
+            ab[j] = 1
+        elif claim[g] == _NEVER:
+            claim[g] = j
+            tp[j] = 1
+    return tp, ab, claim
+
+
+def froc_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, fp_rates, weights, true_ignore=None):
     """The numpy twin of ``msl_evaluate_froc``: rank order and TP flags from ``compute_metrics_per_class``, then the
     definitions of DESIGN.md "FROC" as written.  -> ``{"k", "tp": (rows, n_iou, n_rates) int64, "gw", "nw": (rows,)
-    int64, "scores": the class-1 scores in rank order (K,) f32}``: the integers the kernel writes."""
-    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)
+    int64, "scores": the class-1 scores in rank order (K,) f32}``: the integers the kernel writes.  ``true_ignore``
+    (DESIGN.md section 4.6d): FPw sums the detections that are neither TP nor absorbed, Gw the boxes that are not ignored;
+    the dict gains ``"absorbed"`` (rows, n_iou, n_rates): the weighted absorbed detections among the first k*."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_ignore)
     ious, rates, N = list(min_overlaps), froc_rates(fp_rates), c["N"]
     w = _froc_weights(weights, N, 0, 0).astype(np.int64)
     R1, K = w.shape[0], c["d_sco"].shape[0]
@@ -513,27 +613,36 @@ def froc_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_ov
     adm[1:K] = scores[:-1] != scores[1:]
     k_out = np.zeros((R1, len(ious), len(rates)), dtype=np.int64)
     tp_out = np.zeros_like(k_out)
+    ab_out = np.zeros_like(k_out)
     # int64 holds every product while these stay below 2^63; Python integers otherwise
     big = int(w.max(initial=0)) * K * max(d for _, d in rates) >= 2 ** 63 or \
         int(nw.max(initial=0)) * max(n for n, _ in rates) >= 2 ** 63
     dt = object if big else np.int64
     for t, ov in enumerate(ious):
-        tp = np.zeros(K, dtype=np.int64)
-        if K:
+        tp = ab = np.zeros(K, dtype=np.int64)
+        if K and c["t_ign"] is not None:
+            tp, ab, _ = match_with_ignore(c, ov)
+        elif K:
             tp = compute_metrics_per_class(c["d_img"], c["d_box"], c["d_sco"], c["t_img"], c["t_box"],
                                            np.zeros(c["t_box"].shape[0], dtype=bool), ov)[0].astype(np.int64)
         for r0 in range(0, R1, 128):
             wj = w[r0:r0 + 128][:, img].astype(dt)  # (rows, K): the weight of every ranked detection's image
             TP = np.zeros((wj.shape[0], K + 1), dtype=dt)
             FP = np.zeros((wj.shape[0], K + 1), dtype=dt)
+            AB = np.zeros((wj.shape[0], K + 1), dtype=dt)
             TP[:, 1:] = np.cumsum(wj * tp[None, :], axis=1)
-            FP[:, 1:] = np.cumsum(wj * (1 - tp)[None, :], axis=1)
+            FP[:, 1:] = np.cumsum(wj * (1 - tp - ab)[None, :], axis=1)
+            AB[:, 1:] = np.cumsum(wj * ab[None, :], axis=1)
             for ci, (num, den) in enumerate(rates):
                 ok = adm[None, :] & (FP * den <= (nw[r0:r0 + 128].astype(dt) * num)[:, None])
                 ks = K - np.argmax(ok[:, ::-1], axis=1)  # the largest qualifying admissible k (k = 0 always qualifies)
                 k_out[r0:r0 + 128, t, ci] = ks
                 tp_out[r0:r0 + 128, t, ci] = TP[np.arange(wj.shape[0]), ks].astype(np.int64)
-    return {"k": k_out, "tp": tp_out, "gw": gw, "nw": nw, "scores": scores}
+                ab_out[r0:r0 + 128, t, ci] = AB[np.arange(wj.shape[0]), ks].astype(np.int64)
+    out = {"k": k_out, "tp": tp_out, "gw": gw, "nw": nw, "scores": scores}
+    if c["t_ign"] is not None:
+        out["absorbed"] = ab_out
+    return out
 
 
 def froc_summary(ints, min_overlaps, fp_rates):
@@ -593,28 +702,61 @@ def froc_ints(host_out, R1, n_iou, n_rates, scores):
     return {"k": kt[..., 0].copy(), "tp": kt[..., 1].copy(), "gw": gn[:, 0].copy(), "nw": gn[:, 1].copy(), "scores": scores}
 
 
-def evaluate_froc_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, fp_rates, weights):
+def _absorbed_upto(plan, img, k, w):
+    """Weighted absorbed detections among the first ``k`` ranks (``k``: (rows, n_iou, n) host integers) from the absorbed
+    flags a sweep with ignore flags left in ``plan["absorbed"]``; ``img``: the image of every rank (the host's lexsort is
+    the device's rank order).  Reporting only: the flags are the device's, the prefix sums are taken on the host."""
+    D, n_iou, n_sc = plan["D"], len(plan["ious"]), len(plan["scores"])
+    ab = plan["absorbed"].cpu().numpy()[n_iou * n_sc:].reshape(n_iou, D).astype(np.int64)
+    K = img.shape[0]
+    out = np.zeros(k.shape, dtype=np.int64)
+    for t in range(n_iou):
+        for r in range(k.shape[0]):
+            cum = np.concatenate([[0], np.cumsum(w[r, img].astype(np.int64) * ab[t, :K])])
+            out[r, t] = cum[np.clip(k[r, t], 0, K)]
+    return out
+
+
+def evaluate_froc_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, fp_rates, weights,
+                       true_ignore=None):
     """``froc_host`` on the HIP device: the sweep of ``prepare_evaluation``, one upload of weights, rates and ground-truth
-    counts, ``msl_evaluate_froc`` on the workspace the sweep left, one device-to-host copy."""
-    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)  # rejects NaN scores; rank-ordered scores
+    counts, ``msl_evaluate_froc`` on the workspace the sweep left, one device-to-host copy.  ``true_ignore``: as
+    ``froc_host`` (the sweep is ``msl_evaluate_detections_ign``; ``"absorbed"`` costs further copies)."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_ignore)  # rejects NaN scores
     rates = froc_rates(fp_rates)
     w = _froc_weights(weights, c["N"], 0, 0)
-    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, [0.0])
+    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, [0.0],
+                              true_ignore=true_ignore)
     f = prepare_froc(plan, c["g"], w, rates)
     plan["launch"]()
     f["launch"]()
     host = f["out"].cpu().numpy()  # the one device-to-host copy
-    return froc_ints(host, f["R1"], f["n_iou"], f["n_rates"], c["d_sco"][c["order"]])
+    ints = froc_ints(host, f["R1"], f["n_iou"], f["n_rates"], c["d_sco"][c["order"]])
+    if true_ignore is not None:
+        ints["absorbed"] = _absorbed_upto(plan, c["d_img"][c["order"]], ints["k"], w)
+    return ints
+
+
+def ignored_summary(ints, t):
+    """The ``absorbed`` entry a summary gains with ``true_ignore``: row 0's absorbed detections per rate / cut at IoU ``t``."""
+    return [int(v) for v in ints["absorbed"][0, t]]
 
 
 def evaluate_froc(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps=(0.5,),
-                  fp_rates=DEFAULT_FP_RATES, n_boot=0, seed=0, weights=None):
+                  fp_rates=DEFAULT_FP_RATES, n_boot=0, seed=0, weights=None, true_ignore=None):
     """FROC of a detection set on the HIP device -> ``froc_summary``'s dict per IoU threshold.  ``weights`` (rows, N)
-    replaces the bootstrap matrix ``bootstrap_weights(N, n_boot, seed)``; its row 0 is reported as the plain curve."""
+    replaces the bootstrap matrix ``bootstrap_weights(N, n_boot, seed)``; its row 0 is reported as the plain curve.
+    ``true_ignore``: ignored boxes are no lesions, absorbed detections no false positives; every
+    IoU threshold's dict gains ``absorbed`` (the absorbed detections among the first k* of every rate).  ``None``: unchanged."""
     ious = list(min_overlaps)
     w = _froc_weights(weights, len(true_labels), n_boot, seed)
-    ints = evaluate_froc_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, ious, fp_rates, w)
-    return froc_summary(ints, ious, fp_rates)
+    ints = evaluate_froc_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, ious, fp_rates, w,
+                              true_ignore=true_ignore)
+    out = froc_summary(ints, ious, fp_rates)
+    if true_ignore is not None:
+        for t, ov in enumerate(ious):
+            out[ov]["absorbed"] = ignored_summary(ints, t)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -624,6 +766,7 @@ def evaluate_froc(det_boxes, det_labels, det_scores, true_boxes, true_labels, mi
 STRATA_MAX_EDGES = 15  # EV_STRATA_MAX_EDGES of csrc/evaluate.hip
 STRATA_MAX_CUTS = 32   # EV_STRATA_MAX_CUTS
 _NEVER = 0x7FFFFFFF    # claim rank of a ground-truth box nobody claimed
+_IGNORED = -2          # claim entry of an ignored class-1 box (IGNORED of csrc/evaluate.hip)
 
 
 def strata_edges(size_edges):
@@ -667,7 +810,8 @@ def _strata_cuts(cuts, R1, n_iou):
     return np.ascontiguousarray(c, dtype=np.int64)
 
 
-def strata_cuts_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores, fp_rates, weights):
+def strata_cuts_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, min_scores, fp_rates, weights,
+                     true_ignore=None):
     """The cuts ``evaluate_strata`` takes, on the host -> (rows, n_iou, n_sc + n_rates) int64: ``K_c`` of every score
     threshold (class-1 detections with ``float(score) >= float(threshold)``, the same for every row and IoU), then
     ``froc_host``'s ``k*`` of every rate (``fp_rates`` None: none)."""
@@ -677,7 +821,7 @@ def strata_cuts_host(det_boxes, det_labels, det_scores, true_boxes, true_labels,
     kc = np.array([int((c["d_sco"].astype(np.float64) >= float(s)).sum()) for s in min_scores], dtype=np.int64)
     cuts = np.broadcast_to(kc[None, None, :], (w.shape[0], len(ious), kc.size))
     if fp_rates is not None:
-        k = froc_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, ious, fp_rates, w)["k"]
+        k = froc_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, ious, fp_rates, w, true_ignore=true_ignore)["k"]
         cuts = np.concatenate([cuts, k], axis=2)
     return np.ascontiguousarray(cuts, dtype=np.int64)
 
@@ -689,13 +833,16 @@ def _cum_by_slot(values, slots, S1):
     return np.cumsum(m, axis=0)
 
 
-def strata_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, min_overlaps, weights, cuts):
+def strata_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, min_overlaps, weights, cuts,
+                true_ignore=None):
     """The numpy twin of ``msl_evaluate_strata``: rank order and TP flags from ``compute_metrics_per_class``, the claim rank
     of a ground-truth box = the rank of the true positive whose first-maximum IoU it is, then the definitions of DESIGN.md
     "Eval by lesion size" as written.  ``cuts``: prefix lengths, (n_cuts,) or (rows, n_iou, n_cuts), clamped to 0 .. K.
     With S strata and slot S the unbinned one -> ``{"tp", "fp": (rows, n_iou, n_cuts, S + 1), "gw": (rows, S + 1),
-    "det_unbinned", "nw": (rows,), "cuts": the clamped cuts}``, all int64: the integers the kernel writes."""
-    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)
+    "det_unbinned", "nw": (rows,), "cuts": the clamped cuts}``, all int64: the integers the kernel writes.  ``true_ignore``
+    (DESIGN.md section 4.6d): an ignored box is in no bin (neither ``gw`` nor ``tp``), an absorbed detection in no ``fp``;
+    the dict gains ``"absorbed"`` (rows, n_iou, n_cuts): the weighted absorbed detections below every cut."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_ignore)
     ious, N, edges = list(min_overlaps), c["N"], strata_edges(size_edges)
     vox = _strata_voxels(voxels, N)
     w = _froc_weights(weights, N, 0, 0).astype(np.int64)
@@ -708,29 +855,40 @@ def strata_host(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxe
     g_slot = size_stratum(_volume_f32(t_box), vox[t_img], edges)
     d_slot[d_slot < 0] = S1 - 1
     g_slot[g_slot < 0] = S1 - 1
+    t_ign = c["t_ign"]
+    scored = np.ones(t_box.shape[0], dtype=bool) if t_ign is None else ~t_ign  # the boxes that belong to a bin at all
     gw = np.zeros((R1, S1), dtype=np.int64)
     for s in range(S1):
-        gw[:, s] = w[:, t_img[g_slot == s]].sum(1)
+        gw[:, s] = w[:, t_img[scored & (g_slot == s)]].sum(1)
     tp_out = np.zeros((R1, len(ious), cuts.shape[2], S1), dtype=np.int64)
     fp_out = np.zeros_like(tp_out)
+    ab_out = np.zeros((R1, len(ious), cuts.shape[2]), dtype=np.int64)
     for t, ov in enumerate(ious):
-        tp = np.zeros(K, dtype=np.int64)
-        if K:
-            tp = compute_metrics_per_class(c["d_img"], c["d_box"], c["d_sco"], t_img, t_box,
-                                           np.zeros(t_box.shape[0], dtype=bool), ov)[0].astype(np.int64)
+        tp = ab = np.zeros(K, dtype=np.int64)
         claim = np.full(t_box.shape[0], _NEVER, dtype=np.int64)
-        for j in np.nonzero(tp)[0]:
-            same = np.nonzero(t_img == img[j])[0]
-            claim[same[int(np.argmax(_iou_one_to_many(box[j], t_box[same])))]] = j
+        if t_ign is not None:
+            tp, ab, claim = match_with_ignore(c, ov)
+        else:
+            if K:
+                tp = compute_metrics_per_class(c["d_img"], c["d_box"], c["d_sco"], t_img, t_box,
+                                               np.zeros(t_box.shape[0], dtype=bool), ov)[0].astype(np.int64)
+            for j in np.nonzero(tp)[0]:
+                same = np.nonzero(t_img == img[j])[0]
+                claim[same[int(np.argmax(_iou_one_to_many(box[j], t_box[same])))]] = j
         by_claim = np.argsort(claim, kind="stable")
+        by_claim = by_claim[scored[by_claim]]
         for r in range(R1):
             TP = _cum_by_slot(w[r, t_img[by_claim]], g_slot[by_claim], S1)  # boxes in claim-rank order
-            FP = _cum_by_slot(w[r, img] * (1 - tp), d_slot, S1)
+            FP = _cum_by_slot(w[r, img] * (1 - tp - ab), d_slot, S1)
             k = cuts[r, t]
             tp_out[r, t] = TP[np.searchsorted(claim[by_claim], k, side="left")]  # boxes with claim rank < k
             fp_out[r, t] = FP[k]
+            ab_out[r, t] = np.concatenate([[0], np.cumsum(w[r, img] * ab)])[k]
     unb = (w[:, img] * (d_slot == S1 - 1)[None, :]).sum(1) if K else np.zeros(R1, dtype=np.int64)
-    return {"tp": tp_out, "fp": fp_out, "gw": gw, "det_unbinned": unb.astype(np.int64), "nw": w.sum(1), "cuts": cuts}
+    out = {"tp": tp_out, "fp": fp_out, "gw": gw, "det_unbinned": unb.astype(np.int64), "nw": w.sum(1), "cuts": cuts}
+    if t_ign is not None:
+        out["absorbed"] = ab_out
+    return out
 
 
 def strata_ints(host_out, R1, n_iou, n_cuts, S1, cuts=None):
@@ -785,14 +943,16 @@ def prepare_strata(plan, voxels, size_edges, weights, cuts):
 
 
 def evaluate_strata_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, min_overlaps,
-                         min_scores, fp_rates, weights):
+                         min_scores, fp_rates, weights, true_ignore=None):
     """``strata_host`` at the cuts of ``strata_cuts_host``, on the HIP device: the sweep of ``prepare_evaluation``, FROC
     when ``fp_rates`` is given, one upload of voxels, edges and weights, ``msl_evaluate_strata`` at cuts that never leave
-    the device (``K_c`` from the sweep's summary, ``k*`` from FROC's result), one device-to-host copy."""
-    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels)  # rejects NaN scores
+    the device (``K_c`` from the sweep's summary, ``k*`` from FROC's result), one device-to-host copy.  ``true_ignore``: as
+    ``strata_host`` (``"absorbed"`` costs one further copy)."""
+    c = _froc_class1(det_boxes, det_labels, det_scores, true_boxes, true_labels, true_ignore)  # rejects NaN scores
     w = _froc_weights(weights, c["N"], 0, 0)
     scs = list(min_scores)
-    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, scs)
+    plan = prepare_evaluation(det_boxes, det_labels, det_scores, true_boxes, true_labels, min_overlaps, scs,
+                              true_ignore=true_ignore)
     n_iou, n_sc, R1 = len(plan["ious"]), len(scs), w.shape[0]
     f = prepare_froc(plan, c["g"], w, froc_rates(fp_rates)) if fp_rates is not None else None
     plan["launch"]()
@@ -806,7 +966,10 @@ def evaluate_strata_ints(det_boxes, det_labels, det_scores, true_boxes, true_lab
     s["launch"]()
     host = torch.cat([s["out"], s["cuts"].reshape(-1)]).cpu().numpy()  # the one device-to-host copy
     n = s["out"].numel()
-    return strata_ints(host[:n], R1, n_iou, s["n_cuts"], s["S1"], host[n:].reshape(R1, n_iou, s["n_cuts"]).copy())
+    ints = strata_ints(host[:n], R1, n_iou, s["n_cuts"], s["S1"], host[n:].reshape(R1, n_iou, s["n_cuts"]).copy())
+    if true_ignore is not None:
+        ints["absorbed"] = _absorbed_upto(plan, c["d_img"][c["order"]], ints["cuts"], w)
+    return ints
 
 
 def _ratio(a, b):
@@ -859,17 +1022,23 @@ def strata_cut_labels(min_scores, fp_rates):
 
 
 def evaluate_strata(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, min_overlaps=(0.5,),
-                    min_scores=(0.5,), fp_rates=None, n_boot=0, seed=0, weights=None):
+                    min_scores=(0.5,), fp_rates=None, n_boot=0, seed=0, weights=None, true_ignore=None):
     """Sensitivity and false positives per case by lesion size on the HIP device -> ``strata_summary``'s dict per IoU
     threshold, at every score threshold of ``min_scores`` and, with ``fp_rates``, at the FROC operating point of every rate.
     ``voxels``: the voxel count of the frame each image's boxes are fractions of (one value, or one per image);
     ``size_edges``: ascending bin edges in voxels.  ``weights`` replaces ``bootstrap_weights(N, n_boot, seed)``.  NaN
-    scores: ValueError."""
+    scores: ValueError.  ``true_ignore``: an ignored box belongs to no bin, an absorbed detection
+    is no false positive of any; every IoU threshold's dict gains ``absorbed`` (the absorbed detections below every cut).
+    ``None``: unchanged."""
     ious, scs = list(min_overlaps), list(min_scores)
     w = _froc_weights(weights, len(true_labels), n_boot, seed)
     ints = evaluate_strata_ints(det_boxes, det_labels, det_scores, true_boxes, true_labels, voxels, size_edges, ious, scs,
-                                fp_rates, w)
-    return strata_summary(ints, size_edges, ious, strata_cut_labels(scs, fp_rates))
+                                fp_rates, w, true_ignore=true_ignore)
+    out = strata_summary(ints, size_edges, ious, strata_cut_labels(scs, fp_rates))
+    if true_ignore is not None:
+        for t, ov in enumerate(ious):
+            out[ov]["absorbed"] = ignored_summary(ints, t)
+    return out
 
 
 # ---- prior fit report (DESIGN.md section 4.6c, csrc/priorfit.hip): which lesions the prior boxes can match ---------------

@@ -394,6 +394,18 @@ int msl_multibox_loss_var(const float* locs, const float* scores, const long lon
                           float* dscores, int* nan_flag, int N, int P, int ncls, int flags, int neg_pos_ratio,
                           void* stream);
 
+/* The same call with an IoU-family localisation loss on the DECODED boxes of the positive priors (not in the reference):
+ * kind 1 = IoU (1 - iou), 2 = GIoU (+ (enclosure - union) / enclosure), 3 = DIoU (+ centre distance^2 / sum of squared
+ * enclosure extents); loc_loss = sum / n_positives.  Predicted box: centre g p_size / 10 + p_centre, size
+ * exp(clamp(g / 5, -4, 4)) p_size; target box: the same decode of true_locs without the clamp.  priors_c: the (P, 6)
+ * centre-size priors of the matcher.  flags: the confidence bits of msl_multibox_loss_var only (0, 1, 4, 5; bit 2 ->
+ * MSL_ERR_ARG); confidence loss, mined mask and dscores have the bits msl_multibox_loss_var(flags) gives.  workspace,
+ * var_ws, loss_out, upstream, dlocs / dscores (both or neither) and nan_flag as there.  Without a positive loc_loss is NaN. */
+int msl_multibox_loss_iou(const float* locs, const float* scores, const long long* true_classes, const float* true_locs,
+                          const float* priors_c, double* workspace, void* var_ws, float* loss_out, const float* upstream,
+                          float* dlocs, float* dscores, int* nan_flag, int N, int P, int ncls, int flags, int neg_pos_ratio,
+                          int kind, void* stream);
+
 /* ---- LSSD3D.detect_objects (ssd3d.py:344-460): softmax, decode, filter, sort, 3D NMS, top-k ---------------
  * cap = 10*top_k (<= 4096), Wn = ceil(cap/64), K1 = ncls-1.  Caller-allocated scratch:
  *   probs (N,K1,P) f32; boxes (N,P,6) f32; sorted_idx (N,K1,cap) i32; ncand (N*K1) i32;

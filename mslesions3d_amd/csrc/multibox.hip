@@ -462,12 +462,97 @@ __device__ __forceinline__ unsigned sortable_key(float v) {  // larger float <=>
   return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
+// ---- IoU-family localisation losses (msl_multibox_loss_iou) ----
+// LOC = 0: the (smooth-)L1 of encoded offsets above; 1 IoU, 2 GIoU, 3 DIoU on the DECODED boxes of a positive prior:
+//   c_a = g_a p_{3+a} / 10 + p_a,  s_a = exp(clamp(g_{3+a} / 5, -4, 4)) p_{3+a}   (target: the same without the clamp)
+//   iou = inter / union,  e_a = extent of the enclosing box;  l = 1 - iou  (+ (prod e - union) / prod e   GIoU)
+//                                                                          (+ sum (c - tc)^2 / sum e^2    DIoU)
+// The clamp keeps an untrained head's exp finite (its derivative outside [-4, 4] is 0); sizes stay positive, so neither
+// union nor enclosure is ever 0 and there is no epsilon.  At a tie of a max / min or an intersection extent of exactly 0
+// the derivative taken is the one of the strict comparisons below (0 for the prediction's side).
+// One prior is ~150 flops and a few percent of the priors are positives, so the term and its gradient are evaluated in
+// fp64: the value that reaches the fp64 partials / the fp32 gradient is rounded once, and no cancellation in
+// min(hi) - max(lo) of boxes a few voxels wide eats the fp32 mantissa.
+constexpr int LOC_L1 = 0, LOC_IOU = 1, LOC_GIOU = 2, LOC_DIOU = 3;
+
+// -> l of one prior; GRAD: dg[0..5] = d l / d g
+template <int LOC, bool GRAD>
+__device__ __forceinline__ double iou_loss_term(const float* __restrict__ g, const float* __restrict__ t,
+                                                const float* __restrict__ p, double* dg) {
+  double c[3], s[3], lo[3], hi[3], tcen[3], tlo[3], thi[3], w[3], iw[3], e[3];
+  bool clamped[3];
+  double vp = 1.0, vt = 1.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double pc = (double)p[a], ps = (double)p[3 + a];
+    const double z = (double)g[3 + a] / 5.0;
+    clamped[a] = z < -4.0 || z > 4.0;
+    const double zc = z < -4.0 ? -4.0 : (z > 4.0 ? 4.0 : z);  // (a NaN passes through)
+    c[a] = (double)g[a] * ps / 10.0 + pc;
+    s[a] = exp(zc) * ps;
+    tcen[a] = (double)t[a] * ps / 10.0 + pc;
+    const double ts = exp((double)t[3 + a] / 5.0) * ps;
+    lo[a] = c[a] - s[a] / 2.0;
+    hi[a] = c[a] + s[a] / 2.0;
+    tlo[a] = tcen[a] - ts / 2.0;
+    thi[a] = tcen[a] + ts / 2.0;
+    w[a] = (hi[a] < thi[a] ? hi[a] : thi[a]) - (lo[a] > tlo[a] ? lo[a] : tlo[a]);
+    iw[a] = w[a] > 0.0 ? w[a] : 0.0;
+    e[a] = (hi[a] > thi[a] ? hi[a] : thi[a]) - (lo[a] < tlo[a] ? lo[a] : tlo[a]);
+    vp *= s[a];
+    vt *= ts;
+  }
+  const double inter = iw[0] * iw[1] * iw[2];
+  const double uni = vp + vt - inter;
+  double l = 1.0 - inter / uni;
+  // d l / d inter (union = vp + vt - inter moves with it), d l / d vp, d l / d (prod e), d l / d (sum e^2), d l / d (sum dc^2)
+  double kI = -(vp + vt) / (uni * uni), kV = inter / (uni * uni), kE = 0.0, kC = 0.0, kD = 0.0;
+  if (LOC == LOC_GIOU) {
+    const double enc = e[0] * e[1] * e[2];
+    l += (enc - uni) / enc;
+    kI += 1.0 / enc;
+    kV -= 1.0 / enc;
+    kE = uni / (enc * enc);
+  } else if (LOC == LOC_DIOU) {
+    double d2 = 0.0, e2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      d2 += (c[a] - tcen[a]) * (c[a] - tcen[a]);
+      e2 += e[a] * e[a];
+    }
+    l += d2 / e2;
+    kD = 1.0 / e2;
+    kC = -d2 / (e2 * e2);
+  }
+  if (GRAD) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int b1 = (a + 1) % 3, b2 = (a + 2) % 3;
+      const double pI = w[a] > 0.0 ? iw[b1] * iw[b2] : 0.0, pS = s[b1] * s[b2];
+      // the enclosure's share: prod e (GIoU) or sum e^2 (DIoU), whichever is live
+      const double pE = LOC == LOC_GIOU ? kE * e[b1] * e[b2] : (LOC == LOC_DIOU ? kC * 2.0 * e[a] : 0.0);
+      double dhi = kV * pS, dlo = -kV * pS;
+      if (hi[a] < thi[a]) dhi += kI * pI;
+      if (lo[a] > tlo[a]) dlo -= kI * pI;
+      if (hi[a] > thi[a]) dhi += pE;
+      if (lo[a] < tlo[a]) dlo -= pE;
+      const double dc = dhi + dlo + kD * 2.0 * (c[a] - tcen[a]);
+      const double ds = (dhi - dlo) / 2.0;
+      dg[a] = dc * (double)p[3 + a] / 10.0;
+      dg[3 + a] = clamped[a] ? 0.0 : ds * s[a] / 5.0;
+    }
+  }
+  return l;
+}
+
 // forward partial sums.  With VAR_HNM the negatives' losses go to conf_all (positives / ignored priors = 0, exactly the
-// reference's conf_loss_neg) and only the positives' confidence loss is summed here.
+// reference's conf_loss_neg) and only the positives' confidence loss is summed here.  LOC != 0: the localisation sum is the
+// IoU-family term of the prior (priors_c (P, 6) centre-size; prior of entry i = i % P) - the confidence side is this one code.
+template <int LOC>
 __global__ __launch_bounds__(256) void multibox_loss_partial_var_kernel(
     const float* __restrict__ locs, const float* __restrict__ scores, const long long* __restrict__ true_classes,
-    const float* __restrict__ true_locs, double* __restrict__ partials, float* __restrict__ conf_all, int total,
-    int ncls, int flags, int* __restrict__ nan_flag) {
+    const float* __restrict__ true_locs, const float* __restrict__ priors_c, int P, double* __restrict__ partials,
+    float* __restrict__ conf_all, int total, int ncls, int flags, int* __restrict__ nan_flag) {
   __shared__ double scratch[8];
   const bool hnm = flags & VAR_HNM, smooth = flags & VAR_SMOOTH, focal = flags & VAR_FOCAL;
   double ce = 0.0, l1 = 0.0, np = 0.0;
@@ -489,14 +574,19 @@ __global__ __launch_bounds__(256) void multibox_loss_partial_var_kernel(
     }
     if (tc > 0) {
       np += 1.0;
-      float a = 0.f;
+      if (LOC == LOC_L1) {
+        float a = 0.f;
 #pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const float d = locs[(size_t)i * 6 + q] - true_locs[(size_t)i * 6 + q];
-        const float ad = fabsf(d);
-        a += smooth ? (ad < 1.f ? 0.5f * d * d : ad - 0.5f) : ad;
+        for (int q = 0; q < 6; ++q) {
+          const float d = locs[(size_t)i * 6 + q] - true_locs[(size_t)i * 6 + q];
+          const float ad = fabsf(d);
+          a += smooth ? (ad < 1.f ? 0.5f * d * d : ad - 0.5f) : ad;
+        }
+        l1 += (double)a;
+      } else {
+        l1 += iou_loss_term<LOC, false>(locs + (size_t)i * 6, true_locs + (size_t)i * 6, priors_c + (size_t)(i % P) * 6,
+                                        nullptr);
       }
-      l1 += (double)a;
     }
   }
   if (nan_flag) {
@@ -603,11 +693,14 @@ __global__ __launch_bounds__(1024) void multibox_hnm_select_kernel(const long lo
 
 // backward of the variants; every workgroup folds the forward partials (+ the per-image mined sums) itself and workgroup
 // 0 publishes loss_out = [conf, loc, n_positives], as multibox_loss_bwd_kernel<true> does.  write_grads = 0: losses only.
+// LOC != 0: loc = sum of the IoU-family terms / n_positives (no factor 6) and dlocs its gradient through the decode.
+template <int LOC>
 __global__ __launch_bounds__(256) void multibox_loss_bwd_var_kernel(
     const float* __restrict__ locs, const float* __restrict__ scores, const long long* __restrict__ true_classes,
-    const float* __restrict__ true_locs, float* __restrict__ loss_out, const double* __restrict__ partials, int nparts,
-    const double* __restrict__ hnm_sum, int nimages, const float* __restrict__ sel, const float* __restrict__ upstream,
-    float* __restrict__ dlocs, float* __restrict__ dscores, int total, int ncls, int flags, int write_grads) {
+    const float* __restrict__ true_locs, const float* __restrict__ priors_c, int P, float* __restrict__ loss_out,
+    const double* __restrict__ partials, int nparts, const double* __restrict__ hnm_sum, int nimages,
+    const float* __restrict__ sel, const float* __restrict__ upstream, float* __restrict__ dlocs,
+    float* __restrict__ dscores, int total, int ncls, int flags, int write_grads) {
   __shared__ float s_np;
   const bool hnm = flags & VAR_HNM, smooth = flags & VAR_SMOOTH, focal = flags & VAR_FOCAL;
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -628,7 +721,7 @@ __global__ __launch_bounds__(256) void multibox_loss_bwd_var_kernel(
       s_np = f;
       if (blockIdx.x == 0) {
         loss_out[0] = (float)ce / f;
-        loss_out[1] = (float)l1 / (f * 6.0f);
+        loss_out[1] = LOC == LOC_L1 ? (float)l1 / (f * 6.0f) : (float)(l1 / np);  // without a positive: 0 / 0 = NaN either way
         loss_out[2] = f;
       }
     }
@@ -660,6 +753,15 @@ __global__ __launch_bounds__(256) void multibox_loss_bwd_var_kernel(
       ds[c] = gc * (sm - (c == (int)tc ? 1.0f : 0.0f));
     }
   }
+  if (LOC != LOC_L1) {
+    double dg[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (tc > 0)
+      (void)iou_loss_term<LOC, true>(locs + (size_t)i * 6, true_locs + (size_t)i * 6, priors_c + (size_t)(i % P) * 6, dg);
+    const double k = (double)upstream[1] / (double)npf;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) dlocs[(size_t)i * 6 + q] = tc > 0 ? (float)(k * dg[q]) : 0.f;
+    return;
+  }
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
     float g = 0.f;
@@ -670,6 +772,30 @@ __global__ __launch_bounds__(256) void multibox_loss_bwd_var_kernel(
     }
     dlocs[(size_t)i * 6 + q] = g;
   }
+}
+
+// the launches of a variant call (arguments checked by the entry points); LOC: the localisation term (LOC_*)
+template <int LOC>
+int loss_var_launch(const float* locs, const float* scores, const long long* true_classes, const float* true_locs,
+                           const float* priors_c, double* workspace, void* var_ws, float* loss_out, const float* upstream,
+                           float* dlocs, float* dscores, int* nan_flag, int N, int P, int ncls, int flags, int neg_pos_ratio,
+                           void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  float* sel = (float*)var_ws;
+  double* sums = (double*)((char*)var_ws + (((size_t)N * P * sizeof(float) + 15) & ~(size_t)15));
+  MSL_LAUNCH(multibox_loss_partial_var_kernel<LOC>, dim3(LOSS_BLOCKS), dim3(256), 0, st, locs, scores, true_classes,
+                     true_locs, priors_c, P, workspace, sel, N * P, ncls, flags, nan_flag);
+  MSL_LAUNCH_CHECK();
+  if (flags & VAR_HNM) {
+    MSL_LAUNCH(multibox_hnm_select_kernel, dim3(N), dim3(1024), 0, st, true_classes, sel, sums, P, neg_pos_ratio);
+    MSL_LAUNCH_CHECK();
+  }
+  const int write = dlocs != nullptr;
+  MSL_LAUNCH(multibox_loss_bwd_var_kernel<LOC>, dim3(write ? msl::cdiv(N * P, 256) : 1), dim3(256), 0, st, locs,
+                     scores, true_classes, true_locs, priors_c, P, loss_out, workspace, LOSS_BLOCKS, sums, N, sel, upstream,
+                     dlocs, dscores, N * P, ncls, flags, write);
+  MSL_LAUNCH_CHECK();
+  return MSL_OK;
 }
 
 }  // namespace
@@ -832,22 +958,27 @@ int msl_multibox_loss_var(const float* locs, const float* scores, const long lon
   if (N <= 0 || P <= 0 || ncls < 2 || ncls > MAXC || flags < 0 || flags > 7 || neg_pos_ratio < 0) return MSL_ERR_ARG;
   if ((flags & VAR_FOCAL) && ncls != 2) return MSL_ERR_UNSUPPORTED;  // defined for background + one class
   if ((dlocs == nullptr) != (dscores == nullptr) || (dlocs && !upstream) || !var_ws) return MSL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  float* sel = (float*)var_ws;
-  double* sums = (double*)((char*)var_ws + (((size_t)N * P * sizeof(float) + 15) & ~(size_t)15));
-  MSL_LAUNCH(multibox_loss_partial_var_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, st, locs, scores, true_classes,
-                     true_locs, workspace, sel, N * P, ncls, flags, nan_flag);
-  MSL_LAUNCH_CHECK();
-  if (flags & VAR_HNM) {
-    MSL_LAUNCH(multibox_hnm_select_kernel, dim3(N), dim3(1024), 0, st, true_classes, sel, sums, P, neg_pos_ratio);
-    MSL_LAUNCH_CHECK();
-  }
-  const int write = dlocs != nullptr;
-  MSL_LAUNCH(multibox_loss_bwd_var_kernel, dim3(write ? msl::cdiv(N * P, 256) : 1), dim3(256), 0, st, locs,
-                     scores, true_classes, true_locs, loss_out, workspace, LOSS_BLOCKS, sums, N, sel, upstream, dlocs,
-                     dscores, N * P, ncls, flags, write);
-  MSL_LAUNCH_CHECK();
-  return MSL_OK;
+  return loss_var_launch<LOC_L1>(locs, scores, true_classes, true_locs, nullptr, workspace, var_ws, loss_out, upstream, dlocs,
+                                 dscores, nan_flag, N, P, ncls, flags, neg_pos_ratio, stream);
+}
+
+// The same call with an IoU-family localisation term on the decoded boxes (kind 1 IoU, 2 GIoU, 3 DIoU; see iou_loss_term):
+// loc = sum over positives / n_positives.  priors_c: the (P, 6) centre-size priors the matcher took.  flags: the confidence
+// bits only (1 mining, 4 focal); the confidence loss, the mined mask and dscores come from the code msl_multibox_loss_var runs
+// and have its bits.
+int msl_multibox_loss_iou(const float* locs, const float* scores, const long long* true_classes, const float* true_locs,
+                          const float* priors_c, double* workspace, void* var_ws, float* loss_out, const float* upstream,
+                          float* dlocs, float* dscores, int* nan_flag, int N, int P, int ncls, int flags, int neg_pos_ratio,
+                          int kind, void* stream) {
+  if (N <= 0 || P <= 0 || ncls < 2 || ncls > MAXC || flags < 0 || flags > 7 || (flags & VAR_SMOOTH) || neg_pos_ratio < 0 ||
+      kind < LOC_IOU || kind > LOC_DIOU)
+    return MSL_ERR_ARG;
+  if ((flags & VAR_FOCAL) && ncls != 2) return MSL_ERR_UNSUPPORTED;
+  if ((dlocs == nullptr) != (dscores == nullptr) || (dlocs && !upstream) || !var_ws || !priors_c) return MSL_ERR_ARG;
+  return msl::dispatch_int<LOC_IOU, LOC_GIOU, LOC_DIOU>(kind, [&](auto loc) {
+    return loss_var_launch<decltype(loc)::value>(locs, scores, true_classes, true_locs, priors_c, workspace, var_ws, loss_out,
+                                                 upstream, dlocs, dscores, nan_flag, N, P, ncls, flags, neg_pos_ratio, stream);
+  });
 }
 
 }  // extern "C"

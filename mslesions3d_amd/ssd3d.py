@@ -284,6 +284,18 @@ class LSSD3D(nn.Module):
         self.priors_cxcycz = self.create_prior_boxes(_draw=False) if torch.cuda.is_available() else None
         self.loss_fn = MultiBoxLoss(self.priors_cxcycz, threshold=threshold, alpha=alpha, **self._loss_variants)
 
+    def set_loc_loss(self, kind):
+        """Localisation loss of training and validation: ``"l1"`` (the reference's, default) or an IoU-family loss on the
+        decoded boxes, ``"iou"`` / ``"giou"`` / ``"diou"`` (``MultiBoxLoss.set_loc_loss``).  A setter and not a constructor
+        parameter: the constructor keeps the reference's signature.  Only a non-default kind enters the hyper-parameters
+        (default checkpoints keep the reference's key set); ``load_from_checkpoint`` applies it."""
+        self.loss_fn.set_loc_loss(kind)
+        if kind == "l1":
+            self.hparams.pop("loc_loss", None)
+        else:
+            self.hparams["loc_loss"] = kind
+        return self
+
     # -- Lightning surface ------------------------------------------------------------------------------
     @property
     def device(self):
@@ -818,14 +830,20 @@ class LSSD3D(nn.Module):
         ckpt = cls.read_checkpoint(path, map_location)
         hp = dict(ckpt.get("hyper_parameters", {}))
         hp.update(overrides)
+        loc_loss = hp.get("loc_loss", "l1")  # not a constructor parameter (set_loc_loss): read before the filter drops it
         hp = {k: v for k, v in hp.items() if k in cls.__init__.__code__.co_varnames}
         if "aspect_ratios" in hp:  # JSON-ish round trips may have turned the feature indices into strings
             hp["aspect_ratios"] = {int(k): v for k, v in hp["aspect_ratios"].items()}
         model = cls(**hp)
+        model.set_loc_loss(loc_loss)
         model.load_state_dict(ckpt["state_dict"])
         model.current_epoch = int(ckpt.get("epoch", 0))
         model.global_step = int(ckpt.get("global_step", 0))
         return model
+
+
+# localisation loss of MultiBoxLoss -> ``kind`` of msl_multibox_loss_iou ("l1": the reference's loss, on its own kernels)
+LOC_LOSS_KINDS = {"l1": 0, "iou": 1, "giou": 2, "diou": 3}
 
 
 class _MultiBoxLossFunction(torch.autograd.Function):
@@ -846,7 +864,12 @@ class _MultiBoxLossFunction(torch.autograd.Function):
         st["upstream"].copy_(torch.stack([g_conf.reshape(()), g_loc.reshape(())]))
         N, P, ncls = locs.shape[0], locs.shape[1], scores.shape[2]
         lm = ctx.loss_mod
-        if lm.variant_flags:  # forward + backward of the variant in one call (the mined mask is rebuilt)
+        if lm.loc_loss != "l1":  # IoU-family localisation term: forward + backward in one call, like the variants
+            _lib.call("msl_multibox_loss_iou", ptr(locs), ptr(scores), ptr(st["true_classes"]), ptr(st["true_locs"]),
+                      ptr(lm.priors_cxcycz), ptr(st["ws"]), ptr(lm._var_ws(st, N, P)), ptr(st["loss_out"]), ptr(st["upstream"]),
+                      ptr(st["dlocs"]), ptr(st["dscores"]), None, N, P, ncls, lm.variant_flags & 5, int(lm.neg_pos_ratio),
+                      LOC_LOSS_KINDS[lm.loc_loss], _stream())
+        elif lm.variant_flags:  # forward + backward of the variant in one call (the mined mask is rebuilt)
             _lib.call("msl_multibox_loss_var", ptr(locs), ptr(scores), ptr(st["true_classes"]), ptr(st["true_locs"]),
                       ptr(st["ws"]), ptr(lm._var_ws(st, N, P)), ptr(st["loss_out"]), ptr(st["upstream"]), ptr(st["dlocs"]),
                       ptr(st["dscores"]), None, N, P, ncls, lm.variant_flags, int(lm.neg_pos_ratio), _stream())
@@ -862,7 +885,11 @@ class MultiBoxLoss(nn.Module):
 
     ``hard_negative_mining`` / ``smooth_l1`` / ``focal`` (keyword-only, default off = the reference's live code) switch on
     the variants the reference keeps as commented code: the mining recipe of ssd3d.py:926-932 with ``neg_pos_ratio``,
-    ``nn.SmoothL1Loss`` for the attribute it calls ``smooth_l1`` (ssd3d.py:758), MONAI's ``FocalLoss`` of ssd3d.py:760."""
+    ``nn.SmoothL1Loss`` for the attribute it calls ``smooth_l1`` (ssd3d.py:758), MONAI's ``FocalLoss`` of ssd3d.py:760.
+
+    ``loc_loss`` (an attribute, set with ``set_loc_loss``; the constructor keeps the reference's parameters): ``"l1"`` is
+    the loss above; ``"iou"`` / ``"giou"`` / ``"diou"`` put an IoU-family loss on the decoded boxes of the positive priors
+    in its place (``msl_multibox_loss_iou``; mean over positives, in [0, 1] / [0, 2) / [0, 2))."""
 
     def __init__(self, priors_cxcycz, threshold=0.5, neg_pos_ratio=3, alpha=1., *, hard_negative_mining=False,
                  smooth_l1=False, focal=False):
@@ -873,6 +900,7 @@ class MultiBoxLoss(nn.Module):
         self.neg_pos_ratio = neg_pos_ratio
         self.alpha = alpha
         self.variant_flags = (1 if hard_negative_mining else 0) | (2 if smooth_l1 else 0) | (4 if focal else 0)
+        self.loc_loss = "l1"
         if type(self.threshold) == list:  # ssd3d.py:762-773
             if len(self.threshold) == 1:
                 self.thresholding_mode = "hard"
@@ -890,6 +918,15 @@ class MultiBoxLoss(nn.Module):
     def set_priors(self, priors_cxcycz):
         self.priors_cxcycz = priors_cxcycz
         self.priors_xyz = None
+
+    def set_loc_loss(self, kind):
+        """``"l1"`` (default) | ``"iou"`` | ``"giou"`` | ``"diou"``.  An IoU-family loss replaces the localisation term, so it
+        cannot be combined with ``smooth_l1``."""
+        if kind not in LOC_LOSS_KINDS:
+            raise ValueError(f"loc_loss must be one of {sorted(LOC_LOSS_KINDS)}, got {kind!r}")
+        if kind != "l1" and self.variant_flags & 2:
+            raise ValueError(f"loc_loss {kind!r} replaces the localisation term: it cannot be combined with smooth_l1")
+        self.loc_loss = kind
 
     def _state(self, N, P, ncls, total_objects, dev):
         key = (N, P, ncls, dev)
@@ -956,7 +993,7 @@ class MultiBoxLoss(nn.Module):
 
     def can_pack(self, n_scales):
         """Is the one-launch loss + gradient + head-gradient-image form available (the live loss, at most four scales)?"""
-        return not self.variant_flags and n_scales <= 4
+        return not self.variant_flags and self.loc_loss == "l1" and n_scales <= 4
 
     def _run_loss_pack(self, st, locs, scores, upstream, nan_flag, dO, dims, prior_off):
         """Loss terms, their gradients and the zero-haloed head-gradient images in one launch (training hot loop; the targets
@@ -986,10 +1023,17 @@ class MultiBoxLoss(nn.Module):
         sm = _stream()
         if not matched:
             self._run_match(st, N, gt_boxes, gt_labels, obj_off, T)
-        if self.variant_flags:
+        if self.variant_flags or self.loc_loss != "l1":
             if int(self.neg_pos_ratio) != self.neg_pos_ratio or self.neg_pos_ratio < 0:
                 raise ValueError("neg_pos_ratio must be a non-negative integer")
             up = with_backward_upstream
+            if self.loc_loss != "l1":
+                _lib.call("msl_multibox_loss_iou", ptr(locs), ptr(scores), ptr(st["true_classes"]), ptr(st["true_locs"]),
+                          ptr(self.priors_cxcycz), ptr(st["ws"]), ptr(self._var_ws(st, N, P)), ptr(st["loss_out"]), ptr(up),
+                          ptr(st["dlocs"]) if up is not None else None, ptr(st["dscores"]) if up is not None else None,
+                          ptr(nan_flag), N, P, ncls, self.variant_flags & 5, int(self.neg_pos_ratio),
+                          LOC_LOSS_KINDS[self.loc_loss], sm)
+                return
             _lib.call("msl_multibox_loss_var", ptr(locs), ptr(scores), ptr(st["true_classes"]), ptr(st["true_locs"]),
                       ptr(st["ws"]), ptr(self._var_ws(st, N, P)), ptr(st["loss_out"]), ptr(up),
                       ptr(st["dlocs"]) if up is not None else None, ptr(st["dscores"]) if up is not None else None,

@@ -61,6 +61,11 @@ def build_parser():
     p.add_argument('--hard_negative_mining', action='store_true')
     p.add_argument('--smooth_l1', action='store_true')
     p.add_argument('--focal_loss', action='store_true')
+    # not in the reference either: the localisation loss.  l1 is the reference's (mean |.| of encoded offsets); iou / giou / diou
+    # score the decoded boxes of the positive priors (MultiBoxLoss.set_loc_loss).  Not with --smooth_l1 (parse_args, loc_loss_of)
+    p.add_argument('--loc_loss', choices=["l1", "iou", "giou", "diou"], default=None,
+                   help="localisation loss; not given: l1 for a new model, the checkpoint's own kind with -cp "
+                        "(given, it replaces the checkpoint's; a checkpoint trained with --smooth_l1 takes l1 only)")
     # build-side extension (the reference trains in fp32): activations and activation gradients stored as bf16
     p.add_argument('--dtype', choices=["f32", "bf16"], default="f32")
     # train.py:51 of the reference (MONAI CacheDataset): 1 = cases normalised once into HBM, every batch augmented and
@@ -87,6 +92,27 @@ def build_parser():
     p.add_argument('--grad_histograms', type=int, default=0, metavar='N',
                    help='per-parameter gradient / weight histograms every N steps (0: off; the reference logs every 25)')
     return p
+
+
+def parse_args(argv=None):
+    """The command line of this module: ``build_parser().parse_args`` plus the flags that exclude each other, as an
+    argparse error (exit status 2)."""
+    p = build_parser()
+    args = p.parse_args(argv)
+    try:
+        loc_loss_of(args)
+    except ValueError as e:
+        p.error(str(e))
+    return args
+
+
+def loc_loss_of(args):
+    """The kind named by --loc_loss, or None (not given: a new model trains with l1, a resumed one with its checkpoint's
+    kind).  An IoU kind replaces the localisation term, so together with --smooth_l1 it is an error."""
+    kind = getattr(args, "loc_loss", None)
+    if kind not in (None, "l1") and getattr(args, "smooth_l1", False):
+        raise ValueError(f"--loc_loss {kind} replaces the localisation loss: it cannot be combined with --smooth_l1")
+    return kind
 
 
 class GradHistogramLog:
@@ -208,6 +234,7 @@ def example(args):
     input_images = input_images_of(args)  # before the first GPU call: a refused command line touches no device
     patch_options = patch_options_of(args)
     segmentation = segmentation_of(args)
+    loc_loss = loc_loss_of(args)
     world, rank, local = _dist_env()
     dp = world > 1
     if dp:  # join the job BEFORE the first GPU call of this process (RCCL binds the communicator to the device)
@@ -252,6 +279,8 @@ def example(args):
                        base_network_config=args.base_network_config, boxes_per_location=args.boxes_per_location,
                        hard_negative_mining=args.hard_negative_mining, smooth_l1=args.smooth_l1,
                        focal_loss=args.focal_loss)
+    if loc_loss is not None:  # given: it replaces the kind a checkpoint carries (ValueError on a smooth_l1 checkpoint)
+        model.set_loc_loss(loc_loss)
     model.init()
     model = model.to(dev)
     model.compute_dtype = args.dtype
@@ -403,4 +432,4 @@ def example(args):
 
 
 if __name__ == "__main__":
-    example(build_parser().parse_args())
+    example(parse_args())

@@ -274,7 +274,8 @@ class FusedTrainer:
                                                                                   total_objects)
             st0 = m.loss_fn._state(images.shape[0], m.priors_cxcycz.shape[0], m.n_classes, total_objects, dev)
             key = (st0["prior_for_obj"].data_ptr(), images.data_ptr(), tuple(images.shape), gt_boxes.data_ptr(),
-                   gt_labels.data_ptr(), obj_off.data_ptr(), total_objects, stream, id(arena), float(m.loss_fn.alpha))
+                   gt_labels.data_ptr(), obj_off.data_ptr(), total_objects, stream, id(arena), float(m.loss_fn.alpha),
+                   m.loss_fn.loc_loss)  # (a program replays the loss entry point of the step it was recorded on)
             entry = self._programs.get(key) if self.use_programs else None
             if entry is not None:
                 self._programs.move_to_end(key)
